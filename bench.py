@@ -22,6 +22,13 @@ Also on the line:
                  never instead of it
   cpu_baseline   real libjpeg-turbo (through Pillow, when the box has it) on the host cores, T=1 and T=all, including the
                  reference extension's extra row copy; the oracle port beside it
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0), as float32/float64 .npy files, 51 MB in all:
+  rgb_sample.npy     [256, 16384, 3] float32: the RGB values of every output image at 16384 fixed pixel positions (seeded draw)
+  rgb_sample_yx.npy  [16384, 2] float64: those positions (row, column)
+  rgb_sum.npy        [256, 3] float64: per image and channel, the exact sum over all pixels
+  status.npy         [256] float64: the per-image status codes (0 = success)
+The inputs are seeded, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import hashlib
@@ -43,6 +50,8 @@ HBM_PEAK_GBS = 8000.0             # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_COPY_GBS = 6290.0             # ... and what a float4 device-to-device copy reaches there ("report fraction of both")
 NUM_SOURCES = 8                   # distinct synthetic images cycled through the batch
 STEADY_PREWARM_STEPS = 40
+DUMP_PIXELS, DUMP_SEED = 16384, 20240611   # --dump-outputs: pixel positions sampled per image (same ones in every image)
+DUMP_MAX_BYTES = 64 * 10**6
 # BENCH_REHEARSE_ON_ONE_GPU=1: every rank on GPU 0 with a gloo process group -- a rehearsal of the N > 1 code path (spawning, sharding
 # of configs[3], NUMA split, max over ranks, the JSON line) on a box with one card.  Its figures mean nothing and the line says so.
 REHEARSAL = os.environ.get("BENCH_REHEARSE_ON_ONE_GPU") == "1"
@@ -331,6 +340,27 @@ def config4_progressive(dec, host_threads):
     return res
 
 
+def dump_outputs(outdir, outs, statuses):
+    """--dump-outputs: a fixed seeded sample of the batch's RGB outputs, their exact per-channel sums and the statuses."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(DUMP_SEED)
+    flat = rng.choice(HEIGHT * WIDTH, size=DUMP_PIXELS, replace=False)
+    flat.sort()
+    idx = torch.from_numpy(flat).to(outs[0].device)
+    arrays = {
+        "rgb_sample": torch.stack([o.reshape(-1, 3).index_select(0, idx) for o in outs]).cpu().numpy().astype(np.float32),
+        "rgb_sample_yx": np.stack([flat // WIDTH, flat % WIDTH], axis=1).astype(np.float64),
+        "rgb_sum": torch.stack([o.reshape(-1, 3).sum(0, dtype=torch.int64) for o in outs]).cpu().numpy().astype(np.float64),
+        "status": np.asarray(statuses, dtype=np.float64),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def device_stage_flavours(dec, jpegs):
     """The pixel kernels' other flavours on the same batch (configs[1] times the everyday one: interleaved RGB, fancy upsampling):
     K1 + K2 per step by HIP events, coefficients resident in HBM.  The generic flavour of K2 runs at the same five-waves bound with
@@ -453,9 +483,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernels-only", action="store_true",
                     help="setup + warm-up + timed steps and nothing else: the run to put under rocprofv3 --kernel-trace --stats / --pmc")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see the top of this file)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)  # does not return
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -540,6 +574,8 @@ def main():
     elapsed, (ent_ms, k1_ms, k2_ms) = timed(args.steps)
     statuses = dec.statuses(BATCH)   # settles the GPU entropy stage's verdicts of the last step
     assert all(s == 0 for s in statuses), statuses
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs, statuses)
 
     # ---- the same protocol again with the clocks settled (reported beside `value`)
     for _ in range(STEADY_PREWARM_STEPS):

@@ -1,5 +1,6 @@
 import sys, json, os, time
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, oracle
 from conftest import GOLDEN, load_decode_case
 from nvimagecodec_amd.lowlevel import BatchDecoder
