@@ -71,6 +71,10 @@ typedef enum {
 #define HIPJPEG_FLAG_GPU_HUFFMAN 2u      /* entropy-decode eligible streams on the GPU (sequential Huffman with one interleaved scan, with or
                                             without restart intervals; progressive SOF2 with up to 24 scans); the host then only finds the
                                             scans.  Other streams keep the host entropy stage. */
+#define HIPJPEG_FLAG_FAST_IDCT 4u        /* the fast integer IDCT (plugin option hipjpeg_decoder:fast_idct=1; the reference's fast_idct, which
+                                            selects JDCT_IFAST): the pixels are those of libjpeg-turbo's x86-64 SIMD routine
+                                            jsimd_idct_ifast_sse2, which differs from jidctfst.c only on streams whose samples leave the
+                                            gamut.  Without the flag: JDCT_ISLOW (jsimd_idct_islow), the library's default. */
 
 typedef struct {
     int32_t width, height, num_components;

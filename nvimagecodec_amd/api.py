@@ -264,7 +264,11 @@ class _ExecMixin:
 class Decoder(_ExecMixin):
     """nvimgcodec.Decoder (python/decoder.cpp:262-300).  Note one deliberate difference in defaults: the reference's Python
     layer passes options=":fancy_upsampling=0" (decoder.cpp:283); here the default is the plugins' own default (fancy on),
-    which is the setting under which pixels are bit-exact against the libjpeg-turbo CPU path."""
+    which is the setting under which pixels are bit-exact against the libjpeg-turbo CPU path.
+
+    options reach the plugins as they are.  options="hipjpeg_decoder:fast_idct=1" makes the HIP decoder use the fast integer IDCT
+    (JDCT_IFAST, the pixels of libjpeg-turbo's x86-64 SIMD routine, what the reference's libjpeg_turbo_decoder gives with fast_idct=1);
+    an unnamed ":fast_idct=1" is the chain's setting and hands every sample to the next decoder of the chain instead."""
 
     def __init__(self, device_id=A.DEVICE_CURRENT, max_num_cpu_threads=0, backends=None, options=""):
         import torch

@@ -7,12 +7,14 @@ namespace hipjpeg {
 
 // K1: IDCT of component blocks into u8 planes.  One WorkUnit = 128 blocks.  (Rounds 1-2 had three builds of K1 and K2 for three
 // pass-1 arithmetics chosen per image; since round 3 the transform is the SIMD routine's int16 arithmetic for every image.)
-int launch_idct_plane(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream);
+// fast_idct: the JDCT_IFAST flavour of K1 / K2 (jsimd_idct_ifast_sse2 restated); the descriptors' qpk must then hold the IFAST multiplier
+// tables (DecodeComponent::qpk).  The FUSED builds have no such flavour.
+int launch_idct_plane(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream, bool fast_idct = false);
 // K2: fused luma IDCT + chroma upsample (factors hs x vs, 0 = no chroma) + colour conversion + store.
 // layout: which instantiation of the fused luma kernel (decode_kernels.hip luma_color_body): 0 = generic (format flags read at run
 // time), 1 = COMMON (YCbCr source, interleaved RGB / BGR, fancy upsampling), 2 = COMMON with planar RGB / BGR output
 constexpr int kNumLumaLayouts = 3;
-int launch_luma_color(int layout, int hs, int vs, const DecodeImage* images, const WorkUnit* units, int nunits, void* stream);
+int launch_luma_color(int layout, int hs, int vs, const DecodeImage* images, const WorkUnit* units, int nunits, void* stream, bool fast_idct = false);
 // FUSED builds of K1 / K2 for images of the GPU entropy stage (baseline): the blocks are Huffman-decoded inside the kernel, into the LDS
 // slots the IDCT reads, from the start positions the position pass recorded (HuffImage::block_pos) -- no coefficient block is written
 // to or read from HBM.  himages = the batch's HuffImage array (DecodeImage::huff_index points into it), pool_bytes = dynamic LDS for

@@ -499,10 +499,130 @@ __device__ __forceinline__ void idct_block_pair(const u32x4 (&cols)[4], const un
     }
 }
 
+// ---- the fast integer IDCT (JDCT_IFAST, decoder option fast_idct) ----------------------------------------------------------
+// What is restated: jsimd_idct_ifast_sse2 (simd/x86_64/jidctfst-sse2.asm), the routine behind jpeg_idct_ifast on x86-64 -- not
+// jidctfst.c, which differs from it out of gamut (tests/golden/manifest_fast_idct.json pins both; tests/helpers/ifast_idct.py restates
+// both in numpy).  Every value is an int16 lane there, and here two of them share a register:
+//   pmullw         dequantisation by the int16 multiplier table (q * aanscales + 2048) >> 12, low 16 bits -> v_pk_mul_lo_u16
+//   paddw/psubw    every sum wraps                                                                   -> v_pk_add_u16 / v_pk_sub_u16
+//   psllw + pmulhw a constant multiply is the high half of (x << 2) * (c << 6) in 16 bits            -> v_pk_lshlrev_b16, two
+//                  v_dot2_i32_i16 (one lane each, the other constant half zero) and a v_perm_b32 of the two high halves
+//   psraw + packsswb + paddb 128   the result >> 5, saturated to int8, + 128 (the caller's saturation, as for ISLOW)
+// The routine's "AC terms all zero" shortcut needs no statement: on such a block the full column pass gives the dequantised DC in every
+// row as well.  Both passes run on registers that hold one value of TWO columns (pass 1) or TWO rows (pass 2), so each packed
+// instruction does two of the routine's lanes; the lane pair layout, the hand-over and the result are those of idct_block_pair.
+constexpr int kIfF1414 = 362 << 6, kIfF1847 = 473 << 6, kIfMF1613 = -((669 - 256) << 6), kIfF1082 = 277 << 6;
+__device__ __forceinline__ unsigned pkw_add(unsigned a, unsigned b)
+{
+    return __builtin_bit_cast(unsigned, (u16x2)(__builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b)));
+}
+__device__ __forceinline__ unsigned pk_ashr16_5(unsigned a)
+{
+    return __builtin_bit_cast(unsigned, (i16x2)(__builtin_bit_cast(i16x2, a) >> (short)5));
+}
+// pmulhw of both halves of x by the int16 constant K
+template <int K>
+__device__ __forceinline__ unsigned pk_mulhi16(unsigned x)
+{
+    return hi_pair(dot2(x, pk16(K, 0)), dot2(x, pk16(0, K)));
+}
+
+// One 1-D pass of the SSE2 routine on eight packed values (two independent lanes per register); o[k] = output k, wrapped to 16 bits.
+__device__ __forceinline__ void ifast1d_pk(const unsigned (&i)[8], unsigned (&o)[8])
+{
+    // even part
+    const unsigned tmp10 = pkw_add(i[0], i[4]), tmp11 = pk_sub16(i[0], i[4]), tmp13 = pkw_add(i[2], i[6]);
+    const unsigned tmp12 = pk_sub16(pk_mulhi16<kIfF1414>(pk_shl16_2(pk_sub16(i[2], i[6]))), tmp13);
+    const unsigned e0 = pkw_add(tmp10, tmp13), e3 = pk_sub16(tmp10, tmp13), e1 = pkw_add(tmp11, tmp12), e2 = pk_sub16(tmp11, tmp12);
+    // odd part
+    const unsigned z13 = pkw_add(i[5], i[3]), z10 = pk_sub16(i[5], i[3]), z11 = pkw_add(i[1], i[7]), z12 = pk_sub16(i[1], i[7]);
+    const unsigned t7 = pkw_add(z11, z13);
+    const unsigned t11 = pk_mulhi16<kIfF1414>(pk_shl16_2(pk_sub16(z11, z13)));
+    const unsigned z10s = pk_shl16_2(z10), z12s = pk_shl16_2(z12);
+    const unsigned z5 = pk_mulhi16<kIfF1847>(pkw_add(z10s, z12s));
+    const unsigned t12 = pkw_add(pk_sub16(pk_mulhi16<kIfMF1613>(z10s), z10), z5);  // -2.613 z10 + z5 as (-1.613 z10 - z10) + z5
+    const unsigned t10 = pk_sub16(pk_mulhi16<kIfF1082>(z12s), z5);
+    const unsigned t6 = pk_sub16(t12, t7), t5 = pk_sub16(t11, t6), t4 = pkw_add(t10, t5);
+    o[0] = pkw_add(e0, t7);
+    o[7] = pk_sub16(e0, t7);
+    o[1] = pkw_add(e1, t6);
+    o[6] = pk_sub16(e1, t6);
+    o[2] = pkw_add(e2, t5);
+    o[5] = pk_sub16(e2, t5);
+    o[3] = pk_sub16(e3, t4);
+    o[4] = pkw_add(e3, t4);
+}
+
+// Same contract as idct_block_pair; qp holds the IFAST multiplier table in the qpk layout (the host fills it for fast_idct batches).
+__device__ __forceinline__ void idct_block_pair_ifast(const u32x4 (&cols)[4], const unsigned* __restrict__ qp, unsigned (&out)[4][4])
+{
+    unsigned dq[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const u32x4 q4 = *reinterpret_cast<const u32x4*>(qp + j * 4);
+        dq[j][0] = pk_mul16(cols[j].x, q4.x);
+        dq[j][1] = pk_mul16(cols[j].y, q4.y);
+        dq[j][2] = pk_mul16(cols[j].z, q4.z);
+        dq[j][3] = pk_mul16(cols[j].w, q4.w);
+    }
+    // pass 1: ws[jj][r] = (column 4p+2jj, column 4p+2jj+1) of row r -- the layout idct_block_pair hands over
+    unsigned ws[2][8];
+#pragma unroll
+    for (int jj = 0; jj < 2; jj++) {
+        unsigned in[8];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            in[2 * k] = lo_pair((int)dq[2 * jj][k], (int)dq[2 * jj + 1][k]);
+            in[2 * k + 1] = hi_pair((int)dq[2 * jj][k], (int)dq[2 * jj + 1][k]);
+        }
+        ifast1d_pk(in, ws[jj]);
+    }
+    unsigned own_fwd[8], own_rev[8], X[8], Y[8];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        own_fwd[i] = ws[0][i];
+        own_fwd[4 + i] = ws[1][i];
+        own_rev[i] = ws[0][7 - i];
+        own_rev[4 + i] = ws[1][7 - i];
+    }
+    pair_select8<false>(X, own_rev, own_fwd, 0x5555555555555555ull);
+    pair_select8<true>(Y, own_fwd, own_rev, 0xAAAAAAAAAAAAAAAAull);
+    // pass 2 on the lane's slots 2m, 2m+1 together: in[c] = (slot 2m, slot 2m+1) of column c
+#pragma unroll
+    for (int m = 0; m < 2; m++) {
+        const int a = 2 * m, b = 2 * m + 1;
+        const unsigned ra[4] = {X[a], X[4 + a], Y[a], Y[4 + a]}, rb[4] = {X[b], X[4 + b], Y[b], Y[4 + b]};
+        unsigned in[8], o[8];
+#pragma unroll
+        for (int h = 0; h < 4; h++) {
+            in[2 * h] = lo_pair((int)ra[h], (int)rb[h]);
+            in[2 * h + 1] = hi_pair((int)ra[h], (int)rb[h]);
+        }
+        ifast1d_pk(in, o);
+#pragma unroll
+        for (int c = 0; c < 8; c++) o[c] = pk_ashr16_5(o[c]);
+#pragma unroll
+        for (int h = 0; h < 4; h++) {
+            out[a][h] = lo_pair((int)o[2 * h], (int)o[2 * h + 1]);
+            out[b][h] = hi_pair((int)o[2 * h], (int)o[2 * h + 1]);
+        }
+    }
+}
+
+// the transform of a kernel flavour, fixed at compile time
+template <bool IFAST>
+__device__ __forceinline__ void idct_block(const u32x4 (&cols)[4], const unsigned* __restrict__ qp, bool p, unsigned (&out)[4][4])
+{
+    if constexpr (IFAST)
+        idct_block_pair_ifast(cols, qp, out);
+    else
+        idct_block_pair(cols, qp, p, out);
+}
+
 // ------------------------------------------------------------------------------------------------
 // K1: IDCT of 128 consecutive blocks of one component into a u8 plane (internal plane or user output).
 // ------------------------------------------------------------------------------------------------
-template <bool FUSED>
+template <bool FUSED, bool IFAST = false>
 __device__ __forceinline__ void idct_plane_body(const DecodeImage& im, const WorkUnit& u, char* lds, HuffImage* hi = nullptr, HJ_LDS uint16_t* pool = nullptr,
                                                 FusedShared* fs = nullptr)
 {
@@ -526,7 +646,7 @@ __device__ __forceinline__ void idct_plane_body(const DecodeImage& im, const Wor
     const int b = wave_first + (lane >> 1);
     if (b >= nblocks) return;  // whole pairs leave together
     unsigned rows[4][4];
-    idct_block_pair(cols, cd.qpk[p], p, rows);
+    idct_block<IFAST>(cols, cd.qpk[p], p, rows);
 
     const int by = b / bw, bx = b - by * bw;
     const bool to_out = (u.mode & 0xFF) == kToOutput;
@@ -566,6 +686,14 @@ __global__ __launch_bounds__(kThreads, HJ_MIN_WAVES) void idct_plane_kernel(cons
     __shared__ __attribute__((aligned(16))) char lds[4 * kBlocksPerWave * kLdsBlockStride];
     const WorkUnit u = units[blockIdx.x];
     idct_plane_body<false>(images[u.image], u, lds);
+}
+
+// the fast-IDCT flavour (decoder option fast_idct): a kernel of its own, so that the default one above stays as it is
+__global__ __launch_bounds__(kThreads, HJ_MIN_WAVES) void idct_plane_ifast_kernel(const DecodeImage* __restrict__ images, const WorkUnit* __restrict__ units)
+{
+    __shared__ __attribute__((aligned(16))) char lds[4 * kBlocksPerWave * kLdsBlockStride];
+    const WorkUnit u = units[blockIdx.x];
+    idct_plane_body<false, true>(images[u.image], u, lds);
 }
 
 __global__ __launch_bounds__(kThreads, HJ_MIN_WAVES) void idct_plane_fused_kernel(const DecodeImage* __restrict__ images, const WorkUnit* __restrict__ units,
@@ -684,7 +812,7 @@ constexpr int kNarrowRowBytes = 16 * 24;                // narrow tiles: 16 pixe
 // LAYOUT: 0 = whatever the descriptor says (run-time branches), 1 = COMMON, 2 = COMMON with planar output (P_RGB / P_BGR: what
 // CHW consumers ask for) -- same arithmetic, one set of format flags fixed at compile time each
 enum LumaLayout : int { kLayoutAny = 0, kLayoutInterleaved = 1, kLayoutPlanar = 2 };
-template <int HS, int VS, int LAYOUT, bool FUSED = false>
+template <int HS, int VS, int LAYOUT, bool FUSED = false, bool IFAST = false>
 __device__ __forceinline__ void luma_color_body(const DecodeImage& im, const WorkUnit& u, char* lds, HuffImage* hi = nullptr, HJ_LDS uint16_t* pool = nullptr,
                                                 FusedShared* fs = nullptr)
 {
@@ -749,7 +877,7 @@ __device__ __forceinline__ void luma_color_body(const DecodeImage& im, const Wor
         }
 
         unsigned rows[4][4];
-        idct_block_pair(cols, im.comp[0].qpk[p], p, rows);
+        idct_block<IFAST>(cols, im.comp[0].qpk[p], p, rows);
         // additive constants of the colour conversion (kept in VGPRs: a VOP3 instruction reads one scalar operand at most)
         // (+ 128 << 16: the luma offset, see the packed colour stage below)
         const bool swapped = ycc && bgr;  // crw holds Cb and cbw holds Cr (see the window loads above)
@@ -940,6 +1068,14 @@ __global__ __launch_bounds__(kThreads, HJ_MIN_WAVES_LUMA) void luma_color_kernel
     __shared__ __attribute__((aligned(16))) char lds[4 * kLdsLumaWaveBytes];
     const WorkUnit u = units[blockIdx.x];
     luma_color_body<HS, VS, LAYOUT>(images[u.image], u, lds);
+}
+
+template <int HS, int VS, int LAYOUT>
+__global__ __launch_bounds__(kThreads, HJ_MIN_WAVES_LUMA) void luma_color_ifast_kernel(const DecodeImage* __restrict__ images, const WorkUnit* __restrict__ units)
+{
+    __shared__ __attribute__((aligned(16))) char lds[4 * kLdsLumaWaveBytes];
+    const WorkUnit u = units[blockIdx.x];
+    luma_color_body<HS, VS, LAYOUT, false, true>(images[u.image], u, lds);
 }
 
 #ifndef HJ_MIN_WAVES_FUSED
@@ -1165,10 +1301,13 @@ __global__ __launch_bounds__(kThreads) void transform_kernel(const TransformImag
 
 }  // namespace
 
-int launch_idct_plane(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream)
+int launch_idct_plane(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream, bool fast_idct)
 {
     if (nunits <= 0) return 0;
-    hipLaunchKernelGGL(idct_plane_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
+    if (fast_idct)
+        hipLaunchKernelGGL(idct_plane_ifast_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
+    else
+        hipLaunchKernelGGL(idct_plane_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
     return (int)hipGetLastError();
 }
 
@@ -1210,32 +1349,47 @@ int launch_luma_color_fused(int layout, int hs, int vs, const DecodeImage* image
     }
 }
 
-template <int LAYOUT>
+// one instantiation of K2: the default (ISLOW) kernel or its fast-IDCT twin
+template <int HS, int VS, int LAYOUT, bool IFAST>
+static void launch_luma_one(const DecodeImage* images, const WorkUnit* units, int nunits, hipStream_t s)
+{
+    if constexpr (IFAST)
+        hipLaunchKernelGGL((luma_color_ifast_kernel<HS, VS, LAYOUT>), dim3(nunits), dim3(kThreads), 0, s, images, units);
+    else
+        hipLaunchKernelGGL((luma_color_kernel<HS, VS, LAYOUT>), dim3(nunits), dim3(kThreads), 0, s, images, units);
+}
+
+template <int LAYOUT, bool IFAST>
 static int launch_luma_color_t(int hs, int vs, const DecodeImage* images, const WorkUnit* units, int nunits, hipStream_t s)
 {
     if (hs == 0) {
         if constexpr (LAYOUT != kLayoutAny) return (int)hipErrorInvalidValue;  // gray sources have no colour conversion to specialise
-        else hipLaunchKernelGGL((luma_color_kernel<0, 0, kLayoutAny>), dim3(nunits), dim3(kThreads), 0, s, images, units);
+        else launch_luma_one<0, 0, kLayoutAny, IFAST>(images, units, nunits, s);
     } else if (hs == 1 && vs == 1)
-        hipLaunchKernelGGL((luma_color_kernel<1, 1, LAYOUT>), dim3(nunits), dim3(kThreads), 0, s, images, units);
+        launch_luma_one<1, 1, LAYOUT, IFAST>(images, units, nunits, s);
     else if (hs == 2 && vs == 1)
-        hipLaunchKernelGGL((luma_color_kernel<2, 1, LAYOUT>), dim3(nunits), dim3(kThreads), 0, s, images, units);
+        launch_luma_one<2, 1, LAYOUT, IFAST>(images, units, nunits, s);
     else if (hs == 2 && vs == 2)
-        hipLaunchKernelGGL((luma_color_kernel<2, 2, LAYOUT>), dim3(nunits), dim3(kThreads), 0, s, images, units);
+        launch_luma_one<2, 2, LAYOUT, IFAST>(images, units, nunits, s);
     else if (hs == 1 && vs == 2)
-        hipLaunchKernelGGL((luma_color_kernel<1, 2, LAYOUT>), dim3(nunits), dim3(kThreads), 0, s, images, units);
+        launch_luma_one<1, 2, LAYOUT, IFAST>(images, units, nunits, s);
     else
         return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
 
-int launch_luma_color(int layout, int hs, int vs, const DecodeImage* images, const WorkUnit* units, int nunits, void* stream)
+int launch_luma_color(int layout, int hs, int vs, const DecodeImage* images, const WorkUnit* units, int nunits, void* stream, bool fast_idct)
 {
     if (nunits <= 0) return 0;
+    const hipStream_t s = (hipStream_t)stream;
     switch (layout) {
-    case 0: return launch_luma_color_t<kLayoutAny>(hs, vs, images, units, nunits, (hipStream_t)stream);
-    case 1: return launch_luma_color_t<kLayoutInterleaved>(hs, vs, images, units, nunits, (hipStream_t)stream);
-    case 2: return launch_luma_color_t<kLayoutPlanar>(hs, vs, images, units, nunits, (hipStream_t)stream);
+    case 0: return fast_idct ? launch_luma_color_t<kLayoutAny, true>(hs, vs, images, units, nunits, s) : launch_luma_color_t<kLayoutAny, false>(hs, vs, images, units, nunits, s);
+    case 1:
+        return fast_idct ? launch_luma_color_t<kLayoutInterleaved, true>(hs, vs, images, units, nunits, s)
+                         : launch_luma_color_t<kLayoutInterleaved, false>(hs, vs, images, units, nunits, s);
+    case 2:
+        return fast_idct ? launch_luma_color_t<kLayoutPlanar, true>(hs, vs, images, units, nunits, s)
+                         : launch_luma_color_t<kLayoutPlanar, false>(hs, vs, images, units, nunits, s);
     default: return (int)hipErrorInvalidValue;
     }
 }

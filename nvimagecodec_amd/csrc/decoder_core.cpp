@@ -92,6 +92,18 @@ DecodeBatch::~DecodeBatch()
 
 namespace {
 
+// jddctmgr.c, JDCT_IFAST: the multiplier of quantiser q at natural-order position k, (q * aanscales[k] + 2048) >> 12, as the
+// library stores it (IFAST_MULT_TYPE = short for 8-bit samples: a 16-bit table's large products wrap)
+uint32_t ifast_multiplier(uint16_t q, int k)
+{
+    static const int32_t aanscales[64] = {
+        16384, 22725, 21407, 19266, 16384, 12873, 8867,  4520,  22725, 31521, 29692, 26722, 22725, 17855, 12299, 6270,
+        21407, 29692, 27969, 25172, 21407, 16819, 11585, 5906,  19266, 26722, 25172, 22654, 19266, 15137, 10426, 5315,
+        16384, 22725, 21407, 19266, 16384, 12873, 8867,  4520,  12873, 17855, 16819, 15137, 12873, 10114, 6967,  3552,
+        8867,  12299, 11585, 10426, 8867,  6967,  4799,  2446,  4520,  6270,  5906,  5315,  4520,  3552,  2446,  1247};
+    return (uint32_t)(((int64_t)q * aanscales[k] + 2048) >> 12);
+}
+
 // Decide which kernels handle this frame.  Returns false when the layout is outside the decoder's scope.
 bool choose_variant(const FrameInfo& f, OutFormat fmt, bool fancy, int* variant)
 {
@@ -196,6 +208,7 @@ hipjpegStatus_t DecodeBatch::plan_once(const uint8_t* const* data, const size_t*
     desc_.resize((size_t)n);
     const bool fancy = (flags & HIPJPEG_FLAG_FANCY_UPSAMPLING) != 0;
     const bool want_gpu_entropy = (flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0;
+    fast_idct_ = (flags & HIPJPEG_FLAG_FAST_IDCT) != 0;
     entropy_done_ = false;
     entropy_pending_ = false;  // a caller that re-plans without resolve() gives up the statuses of the previous batch
     huff_images_.clear();
@@ -323,7 +336,8 @@ hipjpegStatus_t DecodeBatch::plan_once(const uint8_t* const* data, const size_t*
             for (int pp = 0; pp < 2; pp++)
                 for (int j = 0; j < 4; j++)
                     for (int r = 0; r < 8; r++) {
-                        const uint32_t q16 = (uint32_t)f.qtab[c][r * 8 + 4 * pp + j] & 0xFFFFu;
+                        const int k = r * 8 + 4 * pp + j;
+                        const uint32_t q16 = (fast_idct_ ? ifast_multiplier(f.qtab[c][k], k) : (uint32_t)f.qtab[c][k]) & 0xFFFFu;
                         uint32_t& pk = dc.qpk[pp][j * 4 + (r >> 1)];
                         pk = (r & 1) ? (pk | (q16 << 16)) : q16;
                     }
@@ -756,7 +770,7 @@ void DecodeBatch::finalize(hipjpegStatus_t* statuses)
     // its TIME rises (2.72 -> 3.20 ms per 256 x 1080p): both halves are bound by instruction issue, and inside the pixel kernels only 32
     // of a wave's 64 lanes have a block to decode.  Off by default; kept as a switch and covered by the parity tests.
     static const bool fused_enabled = getenv("HIPJPEG_FUSED_DECODE") != nullptr && atoi(getenv("HIPJPEG_FUSED_DECODE")) != 0;
-    fused_ = fused_enabled;
+    fused_ = fused_enabled && !fast_idct_;  // the FUSED builds compute ISLOW only: a fast-IDCT batch takes the plain ones
     const int n = (int)images_.size();
     // all or nothing per batch: with fused_ set the block pass is not launched at all, so every GPU-decoded baseline picture must be one the
     // FUSED builds cover completely -- a region of interest launches only the tiles that touch it, the other blocks would go undecoded and
@@ -1365,8 +1379,8 @@ int DecodeBatch::launch_taken_pixels(void* stream, int which)
     int rc = 0;
     for (const Run& r : runs) {
         if (rc != 0) break;
-        rc = r.layout < 0 ? launch_idct_plane(dimg, du + r.first, (int)r.count, stream)
-                          : launch_luma_color(r.layout, hs[r.variant], vs[r.variant], dimg, du + r.first, (int)r.count, stream);
+        rc = r.layout < 0 ? launch_idct_plane(dimg, du + r.first, (int)r.count, stream, fast_idct_)
+                          : launch_luma_color(r.layout, hs[r.variant], vs[r.variant], dimg, du + r.first, (int)r.count, stream, fast_idct_);
     }
     return rc;
 }
@@ -1398,12 +1412,12 @@ int DecodeBatch::launch_pixel_kernels(void* stream, int which)
             size_t first = 0;
             {
                 const int cnt = slice(plane_units_, a, a + chunk, &first);
-                rc = launch_idct_plane(dimg, units_at(unit_off_plane_) + first, cnt, stream);
+                rc = launch_idct_plane(dimg, units_at(unit_off_plane_) + first, cnt, stream, fast_idct_);
             }
             for (int e = 0; e < kNumLumaLayouts; e++)
                 for (int k = 0; k < kNumLumaVariants && rc == 0; k++) {
                     const int cnt = slice(luma_units_[e][k], a, a + chunk, &first);
-                    rc = launch_luma_color(e, hs[k], vs[k], dimg, units_at(unit_off_luma_[e][k]) + first, cnt, stream);
+                    rc = launch_luma_color(e, hs[k], vs[k], dimg, units_at(unit_off_luma_[e][k]) + first, cnt, stream, fast_idct_);
                 }
         }
         return rc;
@@ -1411,14 +1425,14 @@ int DecodeBatch::launch_pixel_kernels(void* stream, int which)
     HuffImage* himg = reinterpret_cast<HuffImage*>(device_.data() + huff_desc_offset_);
     const unsigned pool_bytes = (unsigned)align_up(max_pool_words_ * 2, 256);
     if (rc == 0 && (which < 0 || which == 0)) {
-        rc = launch_idct_plane(dimg, units_at(unit_off_plane_), (int)plane_units_.size(), stream);
+        rc = launch_idct_plane(dimg, units_at(unit_off_plane_), (int)plane_units_.size(), stream, fast_idct_);
         check("idct_plane", (int)plane_units_.size());
         if (rc == 0) rc = launch_idct_plane_fused(dimg, units_at(unit_off_fused_plane_), (int)fused_plane_units_.size(), himg, pool_bytes, stream);
         check("idct_plane_fused", (int)fused_plane_units_.size());
     }
     for (int e = 0; e < kNumLumaLayouts; e++)
         for (int k = 0; k < kNumLumaVariants && rc == 0 && (which < 0 || which == 1); k++) {
-            rc = launch_luma_color(e, hs[k], vs[k], dimg, units_at(unit_off_luma_[e][k]), (int)luma_units_[e][k].size(), stream);
+            rc = launch_luma_color(e, hs[k], vs[k], dimg, units_at(unit_off_luma_[e][k]), (int)luma_units_[e][k].size(), stream, fast_idct_);
             check("luma_color", (int)luma_units_[e][k].size());
             if (rc == 0)
                 rc = launch_luma_color_fused(e, hs[k], vs[k], dimg, units_at(unit_off_fused_luma_[e][k]), (int)fused_luma_units_[e][k].size(), himg, pool_bytes,

@@ -187,6 +187,9 @@ private:
     std::vector<WorkUnit> fused_plane_units_, fused_luma_units_[kNumLumaLayouts][kNumLumaVariants];
     size_t unit_off_fused_plane_ = 0, unit_off_fused_luma_[kNumLumaLayouts][kNumLumaVariants] = {{0}};
     bool fused_ = false;
+    // HIPJPEG_FLAG_FAST_IDCT of the batch being planned: the descriptors' qpk hold IFAST multiplier tables and K1 / K2 launch their
+    // fast-IDCT flavour; such a batch never takes the FUSED builds (they have no IFAST flavour).  Set by every plan().
+    bool fast_idct_ = false;
     uint64_t gpu_entropy_min_pixels_ = 0;
     size_t raw_region_begin_ = 0, raw_region_end_ = 0;  // the staged bitstreams inside the H2D part of the staging area
     // Host-decoded coefficients are handed out of their region [coef_offset_, h2d_bytes_) first come first served while the pool threads

@@ -129,7 +129,11 @@ private:
     bool fancy_ = true;  // same default as the reference plugins (nvjpeg_utils.cpp:46, libjpeg_turbo_decoder.cpp:253)
     bool gpu_huffman_ = true;  // entropy-decode eligible streams on the GPU (the reference's GPU_HYBRID backend analogue)
     uint64_t hybrid_huffman_threshold_ = 0;  // ... those of more than this many pixels (cuda_decoder.cpp:188-209; 0 = all of them)
-    bool fast_idct_ = false;  // asked for JDCT_FASTEST (libjpeg_turbo_decoder.cpp:250-276): not offered here, see canDecode
+    // fast_idct (JDCT_FASTEST, libjpeg_turbo_decoder.cpp:250-276).  A key without a module name is the chain's setting: it hands every
+    // sample to the next decoder (fast_idct_, see canDecode).  hipjpeg_decoder:fast_idct=1 opts in to this decoder's own IFAST kernels
+    // (ifast_; HIPJPEG_FLAG_FAST_IDCT) and takes the samples; the named key wins over an unnamed one.
+    bool fast_idct_ = false;
+    bool ifast_ = false;
     bool ok_ = false;
     int device_ = 0;
     static constexpr int kJobPages = 6;  // batches (or pieces of one) in flight: each has its own page (arenas), stream and event; arenas are sized on first use
@@ -154,23 +158,33 @@ private:
 HipJpegDecoder::HipJpegDecoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgcodecExecutionParams_t* ep, const char* options)
     : fw_(fw), ep_(ep), device_(ep->device_id)
 {
+    bool chain_fast_idct = false, named_fast_idct = false, named_fast_idct_given = false;
+    size_t named_seen = 0;
     for_each_option(options, kDecoderId, [&](const std::string& key, const std::string& value) {
         std::istringstream v(value);
+        const bool named = addressed_keys_.size() > named_seen;  // for_each_option records a key named for this module before the call
+        named_seen = addressed_keys_.size();
         if (key == "fancy_upsampling") v >> fancy_;
         else if (key == "gpu_huffman") v >> gpu_huffman_;
         else if (key == "pipeline_chunks") v >> pipeline_chunks_;
         else if (key == "hybrid_huffman_threshold") v >> hybrid_huffman_threshold_;
-        else if (key == "fast_idct") v >> fast_idct_;
+        else if (key == "fast_idct" && named) {
+            v >> named_fast_idct;
+            named_fast_idct_given = true;
+        } else if (key == "fast_idct")
+            v >> chain_fast_idct;
         else unknown_keys_.push_back(key);
     }, &addressed_keys_);
+    ifast_ = named_fast_idct_given && named_fast_idct;
+    fast_idct_ = !named_fast_idct_given && chain_fast_idct;
     // keys addressed to this decoder by name that it does not know: say so (a key without a module name may be meant for another
     // plugin of the chain and is passed over in silence, as the reference's plugins do)
     for (const std::string& k : unknown_keys_)
         if (std::find(addressed_keys_.begin(), addressed_keys_.end(), k) != addressed_keys_.end())
             HJ_LOG_WARNING(fw_, kDecoderId, "unknown option '" << k << "' ignored (known: fancy_upsampling, gpu_huffman, hybrid_huffman_threshold, pipeline_chunks, fast_idct)");
     if (fast_idct_)
-        HJ_LOG_WARNING(fw_, kDecoderId, "fast_idct=1: this decoder computes jpeg_idct_islow only (bit-exact with the reference's default); "
-                                        "canDecode hands every sample to the next decoder of the chain");
+        HJ_LOG_WARNING(fw_, kDecoderId, "fast_idct=1 without a module name: canDecode hands every sample to the next decoder of the chain; "
+                                        "hipjpeg_decoder:fast_idct=1 decodes them here with the fast integer IDCT (libjpeg-turbo's JDCT_IFAST SIMD routine)");
     {
         int threads = 0;
         if (ep->executor && ep->executor->getNumThreads) threads = ep->executor->getNumThreads(ep->executor->instance);
@@ -277,7 +291,8 @@ void HipJpegDecoder::single_can_decode(nvimgcodecProcessingStatus_t* status, nvi
 {
     *status = NVIMGCODEC_PROCESSING_STATUS_SUCCESS;
     if (fast_idct_) {
-        // JDCT_FASTEST gives other pixels than JDCT_ISLOW; the decoder that implements it (libjpeg_turbo_ext) is next in the chain
+        // the chain's fast_idct: JDCT_FASTEST gives other pixels than JDCT_ISLOW, and without the opt-in addressed to this decoder by name
+        // the decoder meant to implement it (libjpeg_turbo_ext) is next in the chain
         *status = NVIMGCODEC_PROCESSING_STATUS_BACKEND_UNSUPPORTED;
         return;
     }
@@ -663,7 +678,8 @@ nvimgcodecStatus_t HipJpegDecoder::decode_chunk(nvimgcodecCodeStreamDesc_t** cod
         const auto t_marshal = std::chrono::steady_clock::now();
         const bool planned = hipSetDevice(device_) == hipSuccess &&
                              job->batch.plan(data.data(), sizes.data(), n, outs.data(), HIPJPEG_OUTPUT_RGBI,
-                                             (fancy_ ? HIPJPEG_FLAG_FANCY_UPSAMPLING : 0u) | (gpu_huffman_ ? HIPJPEG_FLAG_GPU_HUFFMAN : 0u),
+                                             (fancy_ ? HIPJPEG_FLAG_FANCY_UPSAMPLING : 0u) | (gpu_huffman_ ? HIPJPEG_FLAG_GPU_HUFFMAN : 0u) |
+                                                 (ifast_ ? HIPJPEG_FLAG_FAST_IDCT : 0u),
                                              job->statuses.data(), formats.data(), parse_pool_.get(),
                                              any_geometry ? geometry.data() : nullptr) == HIPJPEG_STATUS_SUCCESS;
         if (!planned) throw std::runtime_error("could not plan the decode batch");

@@ -102,6 +102,11 @@ def entropy_decode_gpu_algorithm_host(data):
     return coefs, passes.value
 
 
+
+def _decode_flags(fancy, gpu_huffman, fast_idct):
+    return (N.FLAG_FANCY_UPSAMPLING if fancy else 0) | (N.FLAG_GPU_HUFFMAN if gpu_huffman else 0) | (N.FLAG_FAST_IDCT if fast_idct else 0)
+
+
 class BatchDecoder:
     """hipjpegCreate / hipjpegDecodeBatch* on one device."""
 
@@ -210,15 +215,16 @@ class BatchDecoder:
         if st:
             raise N.HipJpegError(st, "hipjpegDecodeBatchSetTransforms")
 
-    def decode(self, jpegs, fmt="rgb", fancy=True, outs=None, stream=None, check=True, gpu_huffman=False, transforms=None):
+    def decode(self, jpegs, fmt="rgb", fancy=True, outs=None, stream=None, check=True, gpu_huffman=False, transforms=None, fast_idct=False):
         """Full pipeline.  Returns (outputs, statuses).  gpu_huffman=True: entropy-decode eligible streams on the GPU.
+        fast_idct=True: the fast integer IDCT (JDCT_IFAST of libjpeg-turbo's x86-64 SIMD routine) instead of the default ISLOW one.
         transforms: per-image (roi, orientation) or None -- region of interest and EXIF orientation applied on the device."""
         if outs is None:
             outs = self.allocate_outputs(jpegs, fmt, transforms)
         if transforms is not None:
             self.set_transforms(transforms, len(jpegs))
         ptrs, lens, O, statuses = self._marshal(jpegs, outs, fmt)
-        flags = (N.FLAG_FANCY_UPSAMPLING if fancy else 0) | (N.FLAG_GPU_HUFFMAN if gpu_huffman else 0)
+        flags = _decode_flags(fancy, gpu_huffman, fast_idct)
         st = N.load().hipjpegDecodeBatch(self._h, ptrs, lens, len(jpegs), O, _FORMATS[fmt], flags, statuses, self._stream_ptr(stream))
         if st:
             raise N.HipJpegError(st, "hipjpegDecodeBatch")
@@ -260,9 +266,9 @@ class BatchDecoder:
         if st:
             raise N.HipJpegError(st, "hipjpegSetPipelineDepth")
 
-    def submit(self, jpegs, outs, fmt="rgb", fancy=True, stream=None, gpu_huffman=True):
+    def submit(self, jpegs, outs, fmt="rgb", fancy=True, stream=None, gpu_huffman=True, fast_idct=False):
         ptrs, lens, O, statuses = self._marshal(jpegs, outs, fmt)
-        flags = (N.FLAG_FANCY_UPSAMPLING if fancy else 0) | (N.FLAG_GPU_HUFFMAN if gpu_huffman else 0)
+        flags = _decode_flags(fancy, gpu_huffman, fast_idct)
         st = N.load().hipjpegDecodeBatchSubmit(self._h, ptrs, lens, len(jpegs), O, _FORMATS[fmt], flags, self._stream_ptr(stream))
         if st:
             raise N.HipJpegError(st, "hipjpegDecodeBatchSubmit")
@@ -282,9 +288,9 @@ class BatchDecoder:
         return statuses
 
     # -- the three phases separately (bench.py times device_stage with coefficients resident in HBM)
-    def host_stage(self, jpegs, outs, fmt="rgb", fancy=True, gpu_huffman=False):
+    def host_stage(self, jpegs, outs, fmt="rgb", fancy=True, gpu_huffman=False, fast_idct=False):
         ptrs, lens, O, statuses = self._marshal(jpegs, outs, fmt)
-        flags = (N.FLAG_FANCY_UPSAMPLING if fancy else 0) | (N.FLAG_GPU_HUFFMAN if gpu_huffman else 0)
+        flags = _decode_flags(fancy, gpu_huffman, fast_idct)
         st = N.load().hipjpegDecodeBatchHost(self._h, ptrs, lens, len(jpegs), O, _FORMATS[fmt], flags, statuses)
         if st:
             raise N.HipJpegError(st, "hipjpegDecodeBatchHost")
