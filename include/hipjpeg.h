@@ -153,7 +153,9 @@ HIPJPEG_API hipjpegStatus_t hipjpegEntropyDecodeHostSparse(const uint8_t* data, 
 /* The GPU entropy decoder's algorithm (self-synchronizing subsequence decoding, csrc/huffman_gpu_core.h) executed on the
  * host, lane by lane, with the very code the kernels run: lets the algorithm be verified without a GPU.  Same output
  * layout as hipjpegEntropyDecodeHost; returns HIPJPEG_STATUS_UNSUPPORTED for streams the GPU entropy path does not take
- * (sequential streams in several scans, arithmetic coding, progressive scripts beyond the walker's limits). */
+ * (sequential streams in several scans, arithmetic coding, progressive scripts beyond the walker's limits), and
+ * HIPJPEG_STATUS_INTERNAL_ERROR when one of its self-checks fails (a block-start record of the synchronisation decodes that
+ * disagrees with the position walk). */
 HIPJPEG_API hipjpegStatus_t hipjpegEntropyDecodeGpuAlgorithmHost(const uint8_t* data, size_t length, int16_t* coef,
                                                                  size_t coef_capacity_bytes, uint64_t comp_offsets[4],
                                                                  int32_t* sync_passes);

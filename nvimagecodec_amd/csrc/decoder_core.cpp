@@ -581,7 +581,9 @@ hipjpegStatus_t DecodeBatch::plan_once(const uint8_t* const* data, const size_t*
     work_tail_ = align_up(work_incoming_ + max_huff_units_ * 8, 256);  // tail tasks (256 B per unit) + counts
     work_dc_diff_ = align_up(work_tail_ + max_huff_units_ * (kTailTaskBytes + 4), 256);
     work_block_pos_ = align_up(work_dc_diff_ + huff_blocks_total * 2, 256);
-    work_drops_ = align_up(work_block_pos_ + huff_blockpos_total * 4, 256);
+    work_records_ = align_up(work_block_pos_ + huff_blockpos_total * 4, 256);  // block-start records: 64 bytes per subsequence
+    work_walkers_ = align_up(work_records_ + total_subseq_ * kRecShorts * 2, 256);  // per sync unit: walks left to the position pass
+    work_drops_ = align_up(work_walkers_ + max_huff_units_ * 4, 256);
     work_prog_pos_ = align_up(work_drops_ + huff_chunks_total * 4, 256);
     work_group_sums_ = align_up(work_prog_pos_ + prog_pos_total * 4, 256);  // per block-pass workgroup: DC difference sums of its MCUs
     work_streams_ = align_up(work_group_sums_ + max_huff_wunits_ * 16, 256);
@@ -1099,9 +1101,9 @@ hipjpegStatus_t DecodeBatch::enqueue_gpu_entropy(void* stream)
     uint16_t* tail_tasks = reinterpret_cast<uint16_t*>(work_.data() + work_tail_);
     uint32_t* tail_count = reinterpret_cast<uint32_t*>(work_.data() + work_tail_ + (size_t)max_huff_units_ * kTailTaskBytes);
     if (launch_huff_sync(L.dimg, L.dunits, L.nunits, L.states, L.incoming, L.changed, 1, tail_after > 0 ? tail_after : 1 << 20,
-                         tail_after > 0 ? tail_tasks : nullptr, tail_after > 0 ? tail_count : nullptr, L.pool_bytes, stream) != 0)
+                         tail_after > 0 ? tail_tasks : nullptr, tail_after > 0 ? tail_count : nullptr, L.records, L.pool_bytes, stream) != 0)
         return HIPJPEG_STATUS_HIP_ERROR;
-    if (launch_huff_sync(L.dimg, L.dunits, L.nunits, L.states, L.incoming, L.changed, 0, 1 << 20, nullptr, nullptr, L.pool_bytes, stream, 1) != 0)
+    if (launch_huff_sync(L.dimg, L.dunits, L.nunits, L.states, L.incoming, L.changed, 0, 1 << 20, nullptr, nullptr, L.records, L.pool_bytes, stream, 1) != 0)
         return HIPJPEG_STATUS_HIP_ERROR;
     if (!entropy_write_passes(L, stream)) return HIPJPEG_STATUS_HIP_ERROR;
     if (hipMemcpyAsync(L.host_changed, L.changed, 8 * sizeof(unsigned int), hipMemcpyDeviceToHost, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
@@ -1151,6 +1153,12 @@ DecodeBatch::EntropyLaunch DecodeBatch::entropy_launch_args()
     L.dlist = reinterpret_cast<const uint32_t*>(device_.data() + huff_list_offset_);
     L.states = reinterpret_cast<unsigned long long*>(work_.data());
     L.first_block = reinterpret_cast<uint32_t*>(work_.data() + work_first_block_);
+    // HIPJPEG_POSITION_PASS=1: the position pass walks every subsequence, as before the records (A/B aid).  So it does for a batch
+    // whose record offsets do not fit 32 bits (the kernels' offsets wrap inside the region: never read, never outside it).
+    static const bool full_position_pass = getenv("HIPJPEG_POSITION_PASS") != nullptr && atoi(getenv("HIPJPEG_POSITION_PASS")) != 0;
+    L.records = reinterpret_cast<uint16_t*>(work_.data() + work_records_);
+    L.use_records = !full_position_pass && total_subseq_ * kRecShorts * 2 < (1ull << 32) ? L.records : nullptr;
+    L.walkers = reinterpret_cast<uint32_t*>(work_.data() + work_walkers_);
     L.group_sums = reinterpret_cast<int32_t*>(work_.data() + work_group_sums_);
     L.changed = reinterpret_cast<unsigned int*>(work_.data() + work_changed_);
     L.incoming = reinterpret_cast<unsigned long long*>(work_.data() + work_incoming_);
@@ -1164,7 +1172,7 @@ DecodeBatch::EntropyLaunch DecodeBatch::entropy_launch_args()
 bool DecodeBatch::entropy_write_passes(const EntropyLaunch& L, void* stream)
 {
     return launch_huff_scan(L.dimg, L.dlist, (int)huff_list_.size(), L.states, L.first_block, stream) == 0 &&
-           launch_huff_write(L.dimg, L.dunits, L.nunits, L.dwunits, (int)huff_wunits_.size(), L.states, L.first_block, L.group_sums, L.pool_bytes,
+           launch_huff_write(L.dimg, L.dunits, L.nunits, L.dwunits, (int)huff_wunits_.size(), L.states, L.first_block, L.use_records, L.walkers, L.group_sums, L.pool_bytes,
                              stream, fused_) == 0 &&
            launch_huff_dc(L.dimg, L.ddc, (int)huff_dc_units_.size(), L.dwunits, (int)huff_wunits_.size(), L.group_sums, stream) == 0;
 }
@@ -1219,7 +1227,7 @@ hipjpegStatus_t DecodeBatch::resolve(void* stream)
     if (!converged) {
         for (int pass = 0; pass < kExtraRippleLaunches && !converged; pass++) {
             if (hipMemsetAsync(changed, 0, sizeof(unsigned int), s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-            if (launch_huff_sync(dimg, dunits, nunits, states, incoming, changed, 0, 1 << 20, nullptr, nullptr, pool_bytes, stream, ++last_pass) != 0)
+            if (launch_huff_sync(dimg, dunits, nunits, states, incoming, changed, 0, 1 << 20, nullptr, nullptr, L.records, pool_bytes, stream, ++last_pass) != 0)
                 return HIPJPEG_STATUS_HIP_ERROR;
             if (hipMemcpyAsync(host_changed, changed, sizeof(unsigned int), hipMemcpyDeviceToHost, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
             if (hipStreamSynchronize(s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;

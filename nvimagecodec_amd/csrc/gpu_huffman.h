@@ -30,18 +30,24 @@ int launch_destuff(HuffImage* images, const HuffUnit* chunk_units, int nchunks, 
 // first_pass == 0: a ripple launch (corrections across group borders), pass_id = its number (1, 2, ...): HuffImage::moved_pass
 // receives it for every image in which a group's own last end state still changed.  HuffImage::gave_up is set for images with a
 // group that exceeded its round budget (periodic streams); such images are skipped by later ripple launches.
+// records: block-start records of the synchronisation decodes (huffman_gpu_core.h), kRecShorts uint16 per subsequence, batch-wide
+// like the end states (index HuffImage::first_subseq + subsequence).  Every correction decode of an owned subsequence records
+// where its blocks start and writes its mark (not in streams with restart intervals); pass 0 records nothing, and round 1 decodes
+// every owned subsequence again.
 int launch_huff_sync(HuffImage* images, const HuffUnit* units, int nunits, unsigned long long* states, unsigned long long* incoming,
-                     unsigned int* changed, int first_pass, int max_rounds, uint16_t* tail_tasks, uint32_t* tail_count, unsigned pool_bytes, void* stream,
-                     unsigned pass_id = 0);
+                     unsigned int* changed, int first_pass, int max_rounds, uint16_t* tail_tasks, uint32_t* tail_count, uint16_t* records,
+                     unsigned pool_bytes, void* stream, unsigned pass_id = 0);
 int launch_huff_scan(HuffImage* images, const uint32_t* image_list, int nimages, const unsigned long long* states, uint32_t* first_block, void* stream);
 // Write pass: position kernel over the sync units, then the block kernel over block_units ({image, first MCU}, kHuffMcusPerWg
-// MCUs each).
+// MCUs each).  A copy kernel puts every usable record into HuffImage::block_pos, and the position kernel walks only the other
+// subsequences: overflowed records, images with restart intervals; every subsequence when records == nullptr
+// (HIPJPEG_POSITION_PASS=1).  walkers: one uint32 per sync unit, between the two.
 // group_sums: four int32 per block unit -- the sums of the DC differences of its MCUs, per component (what the DC pass needs
 // from the groups in front of a group).
 // dc_only: the pixel kernels decode the blocks themselves (decode_kernels.hip FUSED builds); only the DC differences are read here.
 int launch_huff_write(HuffImage* images, const HuffUnit* sync_units, int nsync_units, const HuffUnit* block_units, int nblock_units,
-                      const unsigned long long* states, const uint32_t* first_block, int32_t* group_sums, unsigned pool_bytes, void* stream,
-                      bool dc_only = false);
+                      const unsigned long long* states, const uint32_t* first_block, const uint16_t* records, uint32_t* walkers,
+                      int32_t* group_sums, unsigned pool_bytes, void* stream, bool dc_only = false);
 // DC differences -> DC planes.  Images without restart intervals: one workgroup per block unit (its base = the sums of the
 // units in front of it); images with restart intervals: one workgroup per (image, component) in rst_units.
 int launch_huff_dc(const HuffImage* images, const HuffUnit* rst_units, int nrst_units, const HuffUnit* block_units, int nblock_units,

@@ -16,7 +16,8 @@
 //   huff_sync_kernel   pass 0 + workgroup-local synchronisation loop in LDS; publishes end states; counts the workgroups
 //                      whose LAST end state moved (the only state another workgroup consumes)
 //   huff_scan_kernel   per image: exclusive scan of completed-block counts -> first block index of every subsequence
-//   huff_pos_kernel    where every block starts (walk from the converged states)
+//   huff_copy_records_kernel  where every block starts: copies the records the last synchronisation decodes took
+//   huff_pos_kernel    walks from the converged states the subsequences without a usable record
 //   huff_blocks_kernel one lane per block: decode into LDS, store whole 128-byte lines (DC differences to a compact array)
 //   huff_dc_kernel     per (image, component): DC differences -> DC values, stored into the blocks
 #include <hip/hip_runtime.h>
@@ -104,12 +105,41 @@ __device__ __forceinline__ uint32_t boundary0_of(const HuffImage& im, uint32_t s
 {
     return im.restart_interval ? ((const HJ_GLOBAL uint32_t*)im.sub_boundary)[subseq] : 0u;
 }
-// decode_subsequence with or without restart handling (wave-uniform choice: one image per workgroup)
-template <class Env>
-__device__ __forceinline__ SubseqState walk_subsequence(bool rst, const HuffGeom& geom, const Env& env, uint32_t begin, uint32_t limit, int z, int k,
-                                                        uint32_t boundary0)
+// Block-start records (huffman_gpu_core.h) in global memory: fire-and-forget 16-bit stores from the walk's end-of-block branch.
+// The records' base is uniform, the offset a 32-bit byte count (SGPR base + VGPR offset addressing).
+struct SlotRecorder {
+    HJ_GLOBAL char* records;  // the batch's records
+    uint32_t off;             // byte offset of this subsequence's record
+    uint32_t bit0;            // first bit of the subsequence
+    // reports behind the last slot go to the scratch slot (the mark then says "overflow", or does not count them)
+    __device__ __forceinline__ void operator()(uint32_t i, uint32_t pos) const
+    {
+        *(HJ_GLOBAL uint16_t*)(records + (off + 2 * min(i, (uint32_t)kRecSlots))) = (uint16_t)(pos - bit0);
+    }
+};
+// subsequence j of the image
+__device__ __forceinline__ SlotRecorder slot_recorder(uint16_t* records, const HuffImage& im, uint32_t j)
 {
-    return rst ? decode_subsequence<true>(geom, env, begin, limit, z, k, boundary0) : decode_subsequence<false>(geom, env, begin, limit, z, k);
+    SlotRecorder r;
+    r.records = (HJ_GLOBAL char*)records;
+    r.off = (im.first_subseq + j) * (uint32_t)(2 * kRecShorts);
+    r.bit0 = j * kSubseqBits;
+    return r;
+}
+// the mark of the subsequence after a recording decode from (begin, z0) that ended in `st`
+__device__ __forceinline__ void put_mark(const SlotRecorder& r, uint32_t begin, uint32_t limit, uint32_t total_bits, uint32_t z0, const SubseqState& st)
+{
+    *(HJ_GLOBAL uint16_t*)(r.records + (r.off + 2 * kRecMark)) = (uint16_t)record_mark(begin, min(limit, total_bits), z0, st);
+}
+
+// decode_subsequence with or without restart handling (wave-uniform choice: one image per workgroup), with or without records
+// (uniform too; never across restart boundaries)
+template <class Env>
+__device__ __forceinline__ SubseqState walk_subsequence(bool rst, bool record, const HuffGeom& geom, const Env& env, uint32_t begin, uint32_t limit, int z,
+                                                        int k, uint32_t boundary0, const SlotRecorder& rec)
+{
+    if (rst) return decode_subsequence<true>(geom, env, begin, limit, z, k, boundary0);
+    return record ? decode_subsequence<false>(geom, env, begin, limit, z, k, 0, rec) : decode_subsequence<false>(geom, env, begin, limit, z, k);
 }
 
 // Cooperative staging of stream words: lane t brings in row t = subsequence first_row + t of the image (first_row may be -1:
@@ -461,7 +491,7 @@ __global__ __launch_bounds__(kThreads) void destuff_compact_kernel(HuffImage* __
 __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
                                                              unsigned long long* __restrict__ states, unsigned long long* __restrict__ incoming,
                                                              unsigned int* __restrict__ counters, int first_pass, int max_rounds,
-                                                             uint16_t* __restrict__ tail_tasks, uint32_t* __restrict__ tail_count)
+                                                             uint16_t* __restrict__ tail_tasks, uint32_t* __restrict__ tail_count, uint16_t* records)
 {
     __shared__ WgShared sh;
     extern __shared__ uint16_t dyn_pool[];
@@ -490,17 +520,22 @@ __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage
     const bool rst = im.restart_interval != 0;
     unsigned long long old_global = ~0ull;
     int task = -1;
+    // block-start records: every correction decode takes them (not across restart boundaries)
+    const bool recording = !rst;
     if (first_pass) {
         const unsigned long long assumed = (unsigned long long)j * kSubseqBits;
         unsigned long long mine = 0;  // first workgroup of an image, lane 0: the exact initial state (bit 0, z 0, k 0)
         if (owner || (t == 0 && u.first > 0)) {
             const uint32_t bidx0 = boundary0_of(im, j);
             env.set_row(t);
-            mine = pack_state(walk_subsequence(rst, geom, env, j * kSubseqBits, (j + 1) * kSubseqBits, 0, 0, bidx0));
+            mine = pack_state(walk_subsequence(rst, false, geom, env, j * kSubseqBits, (j + 1) * kSubseqBits, 0, 0, bidx0, SlotRecorder()));
         }
         sh.end[t] = mine;
         __syncthreads();
-        if (owner && (sh.end[t - 1] & kSyncMask) != assumed) task = t;
+        // A wrong guess is decoded again.  With records, so is every other subsequence: pass 0 records nothing (its guesses are
+        // throughput-bound work, and almost all of them are wrong), and round 1 keeps almost every lane busy anyway -- the ones
+        // that guessed right (about one in 300, and subsequence 0) are decoded again from the same state, record, and stop there.
+        if (owner && ((sh.end[t - 1] & kSyncMask) != assumed || recording)) task = t;
     } else {
         if (owner) old_global = gstate[j];
         sh.end[t] = t == 0 ? in_state : old_global;
@@ -515,7 +550,11 @@ __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage
         if (task >= 0) {
             const SubseqState p = unpack_state(sh.end[task - 1]);
             env.set_row(task);  // the predecessor's walk ended on a symbol that starts in this row
-            now = pack_state(walk_subsequence(rst, geom, env, p.end_bit, (u.first + task) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, u.first - 1 + task)));
+            const uint32_t jt = u.first - 1 + task;
+            const SlotRecorder rec = slot_recorder(records, im, jt);
+            const SubseqState st = walk_subsequence(rst, recording, geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
+            if (recording) put_mark(rec, p.end_bit, (jt + 1) * kSubseqBits, geom.total_bits, p.zk & 255, st);
+            now = pack_state(st);
             moved = ((now ^ sh.end[task]) & kSyncMask) != 0;
         }
         __syncthreads();  // every start state has been read before any end state is replaced
@@ -676,7 +715,7 @@ template <bool RIPPLE>
 __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage& im, const HuffUnit u, uint32_t ui, int lane,
                                            unsigned long long* __restrict__ states, unsigned long long* __restrict__ incoming,
                                            unsigned int* __restrict__ counters, const uint16_t* __restrict__ tail_tasks, uint32_t pending,
-                                           uint32_t pass_id)
+                                           uint32_t pass_id, uint16_t* records)
 {
     const HuffGeom geom = make_geom(im);
     const uint32_t nsub = (geom.total_bits + kSubseqBits - 1) / kSubseqBits;
@@ -697,6 +736,7 @@ __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage&
     if (lane == 0) ws.count[0] = pending;
     wave_sync();
     const bool rst = im.restart_interval != 0;
+    const bool recording = !rst;  // every decode here can be a subsequence's last one
     bool out_moved = false;  // the group's last end state changed
     const HJ_GLOBAL uint32_t* g = (const HJ_GLOBAL uint32_t*)im.stream;
     const uint32_t gwords = im.stream_words;
@@ -741,8 +781,12 @@ __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage&
                     wave_sync();
                     const SubseqState p = unpack_state(before);
                     win.row_bit0 = word0 * 32u;
-                    const unsigned long long now =
-                        pack_state(cooperative_subsequence(geom, win, changes, p.end_bit, (u.first + task) * kSubseqBits, p.zk & 255u, p.zk >> 8));
+                    const uint32_t jt = u.first - 1 + task;
+                    // (every lane stores the same value to the same address: one write)
+                    const SlotRecorder rec = slot_recorder(records, im, jt);
+                    const SubseqState st = cooperative_subsequence(geom, win, changes, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255u, p.zk >> 8, rec);
+                    if (lane == 0) put_mark(rec, p.end_bit, (jt + 1) * kSubseqBits, geom.total_bits, p.zk & 255u, st);
+                    const unsigned long long now = pack_state(st);
                     const bool moved = ((now ^ old) & kSyncMask) != 0;
                     if (lane == 0) __hip_atomic_store(&gstate[u.first - 1 + task], now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     wave_sync();
@@ -779,7 +823,11 @@ __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage&
                     row[(4 * i + 3) * kTailSlots] = ok ? __builtin_bswap32(x.w) : ~0u;
                 }
                 const SubseqState p = unpack_state(before);
-                now = pack_state(walk_subsequence(rst, geom, env, p.end_bit, (u.first + task) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, u.first - 1 + task)));
+                const uint32_t jt = u.first - 1 + task;
+                const SlotRecorder rec = slot_recorder(records, im, jt);
+                const SubseqState st = walk_subsequence(rst, recording, geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
+                if (recording) put_mark(rec, p.end_bit, (jt + 1) * kSubseqBits, geom.total_bits, p.zk & 255, st);
+                now = pack_state(st);
                 moved = ((now ^ old) & kSyncMask) != 0;
             }
             wave_sync();  // all start states have been read
@@ -808,11 +856,12 @@ __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage&
     }
 }
 
+// (at least 5 waves per SIMD, i.e. at most 96 VGPRs: what "every group of the batch resident at once" rests on)
 template <bool RIPPLE>
-__global__ __launch_bounds__(kTailThreads) void huff_tail_kernel(HuffImage* __restrict__ images, const HuffUnit* __restrict__ units, int nunits,
+__global__ __launch_bounds__(kTailThreads, 5) void huff_tail_kernel(HuffImage* __restrict__ images, const HuffUnit* __restrict__ units, int nunits,
                                                                  unsigned long long* __restrict__ states, unsigned long long* __restrict__ incoming,
                                                                  unsigned int* __restrict__ counters, const uint16_t* __restrict__ tail_tasks,
-                                                                 const uint32_t* __restrict__ tail_count, uint32_t pass_id)
+                                                                 const uint32_t* __restrict__ tail_count, uint32_t pass_id, uint16_t* records)
 {
     __shared__ TailShared sh;
     extern __shared__ uint16_t dyn_pool[];
@@ -864,7 +913,7 @@ __global__ __launch_bounds__(kTailThreads) void huff_tail_kernel(HuffImage* __re
             env.tsel = (const HJ_LDS uint32_t*)sh.tsel;
             env.boundaries = im.boundaries;
             env.num_boundaries = im.num_boundaries;
-            tail_group<RIPPLE>(sh.wave[wave], env, im, u, ui, lane, states, incoming, counters, tail_tasks, pending, pass_id);
+            tail_group<RIPPLE>(sh.wave[wave], env, im, u, ui, lane, states, incoming, counters, tail_tasks, pending, pass_id, records);
         }
     }
 }
@@ -910,10 +959,77 @@ __global__ __launch_bounds__(kThreads) void huff_scan_kernel(HuffImage* __restri
 }
 
 // ---- write pass, step 1: where the blocks start -----------------------------------------------------------------------------
-// Same workgroup shape as the sync kernel (lane 0 idles): every lane walks its subsequence from the converged start state
-// and records the bit position of each block that starts inside it.
+// Records first: one lane per subsequence (the sync units, lane 0 idles) takes its usable record -- the last synchronisation
+// decode took it, from the converged start state; walkers[unit] = how many lanes of the unit have none (overflow, or an image
+// with restart intervals: their damage check is in the walk).  When every lane has one, the records of the unit name one
+// contiguous run of blocks: they are gathered in LDS and leave as consecutive dwords (stored straight from the lanes, a wave's
+// stores would touch a cache line per lane).
+constexpr int kCopyCapacity = kHuffOwn * kRecSlots;  // blocks the records of a unit can name
+__global__ __launch_bounds__(kSyncThreads) void huff_copy_records_kernel(HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
+                                                                     const uint32_t* __restrict__ first_block, const uint16_t* __restrict__ records,
+                                                                     uint32_t* __restrict__ walkers)
+{
+    __shared__ uint32_t s_pos[kCopyCapacity];
+    __shared__ uint32_t s_range[2];  // first block of the run, block behind it
+    const HuffUnit u = units[blockIdx.x];
+    HuffImage& im = images[u.image];
+    const uint32_t nsub = (im.total_bits + kSubseqBits - 1) / kSubseqBits;
+    const int t = threadIdx.x;
+    const uint32_t j = u.first - 1 + t;
+    const bool owner = t != 0 && j < nsub;
+    bool walk = owner;
+    uint32_t n = 0, b0 = 0;
+    u32x4 v[kRecShorts / 8];
+    if (owner && im.restart_interval == 0) {
+        // the whole record in one go (64 bytes: four 16-byte loads in flight together), the mark last
+        const uint32_t g = im.first_subseq + j;
+        const HJ_GLOBAL u32x4* src = (const HJ_GLOBAL u32x4*)records + (size_t)g * (kRecShorts / 8);
+#pragma unroll
+        for (int q = 0; q < kRecShorts / 8; q++) v[q] = src[q];
+        const uint32_t mark = v[kRecShorts / 8 - 1].w >> 16;
+        if (mark_valid(mark)) {
+            // the record's blocks are consecutive: the one in progress at the start (first_block) if fresh, else the next one
+            walk = false;
+            n = mark & (kRecFresh - 1u);
+            b0 = first_block[g] + ((mark & kRecFresh) ? 0u : 1u);
+        }
+    }
+    const int n_walk = __syncthreads_count(walk);
+    if (t == 0) walkers[blockIdx.x] = (uint32_t)n_walk;
+    if (u.first >= nsub) return;  // uniform: no subsequence here
+    HJ_GLOBAL uint32_t* out = (HJ_GLOBAL uint32_t*)im.block_pos;
+    const uint32_t total_blocks = im.total_blocks, bit0 = j * kSubseqBits;
+    auto slot = [&](int i) { return bit0 + ((v[i >> 3][(i >> 1) & 3] >> (16 * (i & 1))) & 0xFFFFu); };
+    if (n_walk == 0) {
+        // uniform: lane 1 holds the first block of the run, the last owner the block behind it (unsettled streams -- the host
+        // decoder takes them -- can have anything here: the run is clipped to the buffer)
+        const int last = (int)min((uint32_t)kSyncThreads, nsub - u.first + 1) - 1;
+        if (t == 1) s_range[0] = b0;
+        if (t == last) s_range[1] = b0 + n;
+        __syncthreads();
+        const uint32_t base = s_range[0];
+#pragma unroll
+        for (int i = 0; i < kRecSlots; i++) {
+            const uint32_t at = b0 - base + (uint32_t)i;
+            if ((uint32_t)i < n && at < (uint32_t)kCopyCapacity) s_pos[at] = slot(i);
+        }
+        __syncthreads();
+        const uint32_t count = min(s_range[1] - base, (uint32_t)kCopyCapacity);
+        for (uint32_t i = t; i < count; i += kSyncThreads)
+            if (base + i < total_blocks) out[base + i] = s_pos[i];
+    } else if (!walk) {
+#pragma unroll
+        for (int i = 0; i < kRecSlots; i++)
+            if ((uint32_t)i < n && b0 + i < total_blocks) out[b0 + i] = slot(i);
+    }
+}
+
+// Then the walks, same workgroup shape: every lane whose subsequence has no usable record walks it from the converged start state
+// and records the bit position of each block that starts inside it.  A workgroup without such lanes leaves at once.
+// records == nullptr: every subsequence is walked (HIPJPEG_POSITION_PASS=1).
 __global__ __launch_bounds__(kSyncThreads) void huff_pos_kernel(HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
-                                                            const unsigned long long* __restrict__ states, const uint32_t* __restrict__ first_block)
+                                                            const unsigned long long* __restrict__ states, const uint32_t* __restrict__ first_block,
+                                                            const uint16_t* __restrict__ records, const uint32_t* __restrict__ walkers)
 {
     __shared__ WgShared sh;
     extern __shared__ uint16_t dyn_pool[];
@@ -923,16 +1039,19 @@ __global__ __launch_bounds__(kSyncThreads) void huff_pos_kernel(HuffImage* __res
     const HuffGeom geom = make_geom(im);
     const uint32_t nsub = (geom.total_bits + kSubseqBits - 1) / kSubseqBits;
     if (u.first >= nsub) return;
+    if (records && walkers[blockIdx.x] == 0) return;  // uniform: every record of the workgroup was usable
+    const int t = threadIdx.x;
+    const uint32_t j = u.first - 1 + t;
+    const bool rst = im.restart_interval != 0;
+    bool walk = t != 0 && j < nsub;
+    if (walk && records && !rst) walk = !mark_valid(records[(size_t)(im.first_subseq + j) * kRecShorts + kRecMark]);
     stage_rows<kSyncThreads>(sh.stream, im, (int)u.first - 1);
     stage_pool<kSyncThreads>(pool, im);
     stage_constants(sh.tsel, nullptr, nullptr, im, false);
     __syncthreads();
-    const int t = threadIdx.x;
-    const uint32_t j = u.first - 1 + t;
-    if (t == 0 || j >= nsub) return;
+    if (!walk) return;
     DevEnv env = make_env(sh, pool, u.first, geom);
     env.set_row(t);
-    const bool rst = im.restart_interval != 0;
     const unsigned long long* st = states + im.first_subseq;
     uint32_t begin = 0;
     int z = 0, k = 0;
@@ -1364,8 +1483,8 @@ static bool ripple_in_tail_kernel()
 }
 
 int launch_huff_sync(HuffImage* images, const HuffUnit* units, int nunits, unsigned long long* states, unsigned long long* incoming,
-                     unsigned int* changed, int first_pass, int max_rounds, uint16_t* tail_tasks, uint32_t* tail_count, unsigned pool_bytes, void* stream,
-                     unsigned pass_id)
+                     unsigned int* changed, int first_pass, int max_rounds, uint16_t* tail_tasks, uint32_t* tail_count, uint16_t* records,
+                     unsigned pool_bytes, void* stream, unsigned pass_id)
 {
     if (nunits <= 0) return 0;
     const dim3 tail_grid((nunits + kTailWaves - 1) / kTailWaves);
@@ -1373,14 +1492,14 @@ int launch_huff_sync(HuffImage* images, const HuffUnit* units, int nunits, unsig
         // corrections across group borders: the tail kernel's workgroups (little LDS, a row staged per decode) instead of the
         // sync kernel's, which would stage 255 rows to decode one or two
         hipLaunchKernelGGL(huff_tail_kernel<true>, tail_grid, dim3(kTailThreads), pool_bytes, (hipStream_t)stream, images, units, nunits, states, incoming,
-                           changed, nullptr, nullptr, pass_id);
+                           changed, nullptr, nullptr, pass_id, records);
         return (int)hipGetLastError();
     }
     hipLaunchKernelGGL(huff_sync_kernel, dim3(nunits), dim3(kSyncThreads), pool_bytes, (hipStream_t)stream, images, units, states, incoming, changed,
-                       first_pass, max_rounds, tail_tasks, tail_count);
+                       first_pass, max_rounds, tail_tasks, tail_count, records);
     if (tail_count)
         hipLaunchKernelGGL(huff_tail_kernel<false>, tail_grid, dim3(kTailThreads), pool_bytes, (hipStream_t)stream, images, units, nunits, states, incoming,
-                           changed, tail_tasks, tail_count, 0u);
+                           changed, tail_tasks, tail_count, 0u, records);
     return (int)hipGetLastError();
 }
 
@@ -1392,11 +1511,15 @@ int launch_huff_scan(HuffImage* images, const uint32_t* image_list, int nimages,
 }
 
 int launch_huff_write(HuffImage* images, const HuffUnit* sync_units, int nsync_units, const HuffUnit* block_units, int nblock_units,
-                      const unsigned long long* states, const uint32_t* first_block, int32_t* group_sums, unsigned pool_bytes, void* stream,
-                      bool dc_only)
+                      const unsigned long long* states, const uint32_t* first_block, const uint16_t* records, uint32_t* walkers, int32_t* group_sums,
+                      unsigned pool_bytes, void* stream, bool dc_only)
 {
     if (nsync_units <= 0) return 0;
-    hipLaunchKernelGGL(huff_pos_kernel, dim3(nsync_units), dim3(kSyncThreads), pool_bytes, (hipStream_t)stream, images, sync_units, states, first_block);
+    if (records)
+        hipLaunchKernelGGL(huff_copy_records_kernel, dim3(nsync_units), dim3(kSyncThreads), 0, (hipStream_t)stream, images, sync_units, first_block, records,
+                           walkers);
+    hipLaunchKernelGGL(huff_pos_kernel, dim3(nsync_units), dim3(kSyncThreads), pool_bytes, (hipStream_t)stream, images, sync_units, states, first_block,
+                       records, walkers);
     if (nblock_units > 0) {
         if (dc_only)
             hipLaunchKernelGGL(huff_dcdiff_kernel, dim3(nblock_units), dim3(kThreads), 0, (hipStream_t)stream, images, block_units, group_sums);

@@ -277,6 +277,16 @@ struct HostWindow {
     uint32_t dc(uint32_t rel) const { return edc[rel]; }
     uint32_t ac(uint32_t rel) const { return eac[rel]; }
 };
+
+// Block-start records as the kernels keep them (huffman_gpu_core.h): kRecShorts uint16 per subsequence, the mark last.
+struct HostRecorder {
+    uint16_t* rec;  // the subsequence's record
+    uint32_t bit0;  // its first bit
+    void operator()(uint32_t i, uint32_t pos) const
+    {
+        rec[i < (uint32_t)kRecSlots ? i : (uint32_t)kRecSlots] = (uint16_t)(pos - bit0);
+    }
+};
 }  // namespace
 
 int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4], int* sync_passes)
@@ -309,18 +319,31 @@ int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, in
     const uint32_t ns = im.num_subseq;
     std::vector<SubseqState> cur(ns), nxt(ns);
     uint32_t err = 0;
-    // pass 0
-    auto walk = [&](uint32_t begin, uint32_t limit, int z, int k) {
-        return rst ? decode_subsequence<true>(geom, env, begin, limit, z, k, 0) : decode_subsequence<false>(geom, env, begin, limit, z, k);
+    // Block-start records, as the kernels take them: every decode from a start state that can be final records and writes the mark
+    // (in pass 0 only subsequence 0, whose start state is exact: the kernels decode it once more in round 1, from the same state).
+    // Not for restart intervals.
+    std::vector<uint16_t> records((size_t)ns * kRecShorts, 0);
+    auto walk = [&](uint32_t i, uint32_t begin, int z, int k, bool record) {
+        const uint32_t limit = (i + 1) * kSubseqBits;
+        uint16_t* rec = &records[(size_t)i * kRecShorts];
+        if (rst) {
+            rec[kRecMark] = (uint16_t)kRecInvalid;
+            return decode_subsequence<true>(geom, env, begin, limit, z, k, 0);
+        }
+        const SubseqState st = record ? decode_subsequence<false>(geom, env, begin, limit, z, k, 0, HostRecorder{rec, i * kSubseqBits})
+                                      : decode_subsequence<false>(geom, env, begin, limit, z, k);
+        rec[kRecMark] = (uint16_t)(record ? record_mark(begin, limit < geom.total_bits ? limit : geom.total_bits, (uint32_t)z, st) : kRecInvalid);
+        return st;
     };
-    for (uint32_t i = 0; i < ns; i++) cur[i] = walk(i * kSubseqBits, (i + 1) * kSubseqBits, 0, 0);
+    // pass 0
+    for (uint32_t i = 0; i < ns; i++) cur[i] = walk(i, i * kSubseqBits, 0, 0, i == 0);
     int passes = 0;
     for (;;) {
         bool changed = false;
         if (ns) nxt[0] = cur[0];
         for (uint32_t i = 1; i < ns; i++) {
             const SubseqState& prev = cur[i - 1];
-            nxt[i] = walk(prev.end_bit, (i + 1) * kSubseqBits, prev.zk & 255, prev.zk >> 8);
+            nxt[i] = walk(i, prev.end_bit, prev.zk & 255, prev.zk >> 8, true);
             if (pack_state(nxt[i]) != pack_state(cur[i])) changed = true;
         }
         cur.swap(nxt);
@@ -332,16 +355,25 @@ int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, in
     if (!rst) {
         // The kernels follow the last links of a correction chain with the whole wave on one subsequence (cooperative_subsequence):
         // the same routine, here, must reproduce the lane decoder's end state for every subsequence -- from its true start state and
-        // from the state pass 0 assumes (a trajectory through garbage).
+        // from the state pass 0 assumes (a trajectory through garbage).  Its records must be the lane decoder's (return 5).
         HostWindow win;
         win.env = &env;
         const uint32_t changes = cooperative_table_changes(win, geom.blocks_per_mcu);
+        std::vector<uint16_t> coop(kRecShorts), lane(kRecShorts);
         for (uint32_t i = 0; i < ns; i++) {
             const uint32_t begin = i ? cur[i - 1].end_bit : 0u, z = i ? (cur[i - 1].zk & 255u) : 0u, k = i ? (uint32_t)(cur[i - 1].zk >> 8) : 0u;
-            if (pack_state(cooperative_subsequence(geom, win, changes, begin, (i + 1) * kSubseqBits, z, k)) != pack_state(cur[i])) return 4;
-            if (pack_state(cooperative_subsequence(geom, win, changes, i * kSubseqBits, (i + 1) * kSubseqBits, 0, 0)) !=
-                pack_state(walk(i * kSubseqBits, (i + 1) * kSubseqBits, 0, 0)))
-                return 4;
+            const uint32_t limit = (i + 1) * kSubseqBits, end = limit < geom.total_bits ? limit : geom.total_bits;
+            const uint16_t* final_rec = &records[(size_t)i * kRecShorts];
+            const SubseqState cs = cooperative_subsequence(geom, win, changes, begin, limit, z, k, HostRecorder{coop.data(), i * kSubseqBits});
+            if (pack_state(cs) != pack_state(cur[i])) return 4;
+            const uint32_t final_mark = final_rec[kRecMark];
+            if (record_mark(begin, end, z, cs) != final_mark) return 5;
+            if (mark_valid(final_mark) && memcmp(coop.data(), final_rec, 2 * (final_mark & (kRecFresh - 1))) != 0) return 5;
+            const SubseqState cg = cooperative_subsequence(geom, win, changes, i * kSubseqBits, limit, 0, 0, HostRecorder{coop.data(), i * kSubseqBits});
+            const SubseqState lg = decode_subsequence<false>(geom, env, i * kSubseqBits, limit, 0, 0, 0, HostRecorder{lane.data(), i * kSubseqBits});
+            if (pack_state(cg) != pack_state(lg)) return 4;
+            const uint32_t mark = record_mark(i * kSubseqBits, end, 0, lg);
+            if (mark_valid(mark) && memcmp(coop.data(), lane.data(), 2 * (mark & (kRecFresh - 1))) != 0) return 5;
         }
     }
     // block index of each subsequence's first symbol
@@ -352,12 +384,18 @@ int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, in
         acc += cur[i].nblocks;
     }
     if (acc < im.total_blocks) return 2;
-    // write pass, step 1: block start positions
+    // write pass, step 1: block start positions.  A usable record must name exactly the blocks the position walk finds, at the
+    // same positions (the kernels copy it instead of walking: huff_pos_kernel); else return 5.
     std::vector<uint32_t> block_pos(im.total_blocks, 0xFFFFFFFFu);
+    std::vector<uint32_t> found_block, found_pos;
     for (uint32_t i = 0; i < ns; i++) {
         const uint32_t begin = i == 0 ? 0 : cur[i - 1].end_bit;
         const int z = i == 0 ? 0 : (cur[i - 1].zk & 255), k = i == 0 ? 0 : (cur[i - 1].zk >> 8);
+        found_block.clear();
+        found_pos.clear();
         auto rec = [&](uint32_t block, uint32_t pos) {
+            found_block.push_back(block);
+            found_pos.push_back(pos);
             if (block < im.total_blocks) block_pos[block] = pos;
         };
         if (rst) {
@@ -366,6 +404,17 @@ int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, in
             if (fault) return 1;
         } else
             position_subsequence<false>(geom, env, begin, (i + 1) * kSubseqBits, z, k, first_block[i], rec);
+        const uint16_t* r = &records[(size_t)i * kRecShorts];
+        const uint32_t mark = r[kRecMark];
+        if (rst || !mark_valid(mark)) {
+            if (!rst && mark != kRecOverflow) return 5;  // every decode that can be final records
+            if (mark == kRecOverflow && found_block.size() <= (size_t)kRecSlots) return 5;
+            continue;
+        }
+        const uint32_t n = mark & (kRecFresh - 1), b0 = first_block[i] + ((mark & kRecFresh) ? 0u : 1u);
+        if (n != found_block.size()) return 5;
+        for (uint32_t s = 0; s < n; s++)
+            if (found_block[s] != b0 + s || found_pos[s] != i * kSubseqBits + r[s]) return 5;
     }
     // restart intervals: the first block of interval j+1 starts exactly at boundary j (see huff_blocks_kernel)
     if (geom.interval_blocks)

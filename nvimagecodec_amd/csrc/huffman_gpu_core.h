@@ -15,7 +15,9 @@
 //              is exact).
 //   count      each pass also counts the blocks completed in the subsequence; an exclusive scan gives every lane the
 //              index of its first block.
-//   write      step 1: the lanes walk their subsequences once more and record where every block starts; step 2: one lane
+//   write      step 1: where every block starts.  The synchronisation decodes record it as they go (block-start records
+//              below); the last decode of a subsequence is the one from its converged start state, so its record is final
+//              and is copied into place.  Only subsequences without a usable record are walked once more.  step 2: one lane
 //              per BLOCK decodes it from its start position into a buffer and the blocks are stored whole (column-major
 //              block layout, DC position left zero); DC differences go to a compact per-image array in scan order.
 //   dc         a per-component scan in MCU order turns DC differences into DC values, stored as one compact plane per
@@ -23,6 +25,7 @@
 // All decisions are integer/bit exact; the result is compared with the host entropy decoder and the oracle in tests/.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -272,8 +275,46 @@ struct RestartCursor {
     }
 };
 
+// Block-start records.  A synchronisation decode can note where the blocks of its subsequence start, at no more cost than a store
+// in its rare end-of-block branch: rec(i, pos) = the i-th block that starts in [begin, end) starts at bit `pos` -- the same blocks,
+// in the same order, that position_subsequence reports (the block in progress at `begin` first, when it is fresh there).  The walk
+// also reports the block that starts behind `end` (where its last symbol completes a block): no test in the branch, and that
+// report is not counted.  The record of a subsequence is kRecShorts uint16 (64 bytes): the bit offsets (from j * kSubseqBits) of
+// up to kRecSlots blocks, a scratch slot that takes every report behind those, and last the MARK, which says whether the record
+// can be used.  Every decode that can be a subsequence's last one records and
+// writes the mark: the count (recorded_blocks) or kRecOverflow; the last one wins.  kRecInvalid: no record (the host emulation's
+// pass-0 guesses and restart-interval streams).  kRecFresh: the first recorded block is the one in progress at `begin` (index
+// first_block[j]); else it is the next one.  (In the bench's q90 photographs 13 blocks start in a subsequence on average, 25 at
+// most; flat pictures overflow and take the position pass.)
+constexpr int kRecShorts = 32;
+constexpr int kRecSlots = kRecShorts - 2;  // slot kRecSlots is the scratch slot
+constexpr int kRecMark = kRecShorts - 1;
+constexpr uint32_t kRecFresh = 0x40, kRecOverflow = 0xFE, kRecInvalid = 0xFF;
+static_assert(kRecSlots < (int)kRecFresh, "counts below kRecFresh");
+HJ_HD bool mark_valid(uint32_t mark) { return mark < kRecOverflow; }
+
+// The no-op recorder: the walks compile to the code without records.
+struct NoRecord {
+    HJ_HD void operator()(uint32_t, uint32_t) const {}
+};
+
+// Blocks a walk from (begin, z0) recorded, from the state it ended in (end = min(limit, total_bits)): every completed block, plus
+// the one in progress at `begin` if it was fresh there, minus the one completed by the last symbol (it starts at or behind `end`;
+// any other step leaves z >= 1).
+HJ_HD uint32_t recorded_blocks(uint32_t begin, uint32_t end, uint32_t z0, const SubseqState& st)
+{
+    if (begin >= end) return 0;
+    return (uint32_t)st.nblocks + (z0 == 0 ? 1u : 0u) - ((st.zk & 255u) == 0 ? 1u : 0u);
+}
+HJ_HD uint32_t record_mark(uint32_t begin, uint32_t end, uint32_t z0, const SubseqState& st)
+{
+    const uint32_t n = recorded_blocks(begin, end, z0, st);
+    return n > (uint32_t)kRecSlots ? kRecOverflow : n | (z0 == 0 ? kRecFresh : 0u);
+}
+
 // Synchronisation decode: the symbols that START in [begin, limit) (and before total_bits), beginning in state (z, k).
-// Tracks the decoder state and counts the blocks completed; nothing is stored.
+// Tracks the decoder state and counts the blocks completed; rec(i, pos) is told where each block starts (see the block-start records
+// above -- not for restart intervals, whose positions the position pass finds together with the damage check).
 // Env supplies the memory accessors:
 //   uint32_t cursor(uint32_t i), fetch(cursor), kCursorStep   32-bit word i of the stream, first byte in the most significant
 //                                        position, through a cursor (see BitReader)
@@ -283,9 +324,11 @@ struct RestartCursor {
 //   uint32_t lookup2(uint32_t e, w)      second-level entry behind first-level entry e (index = next kHuffSubBits bits)
 //   uint32_t lookup_pair(uint32_t t, w)  pair-table entry of table t for window w (same index as lookup1, kPairOffset entries on)
 // RST: the scan has restart intervals; boundary0 = index of the first boundary at or behind the subsequence's first bit.
-template <bool RST, class Env>
-HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_t begin, uint32_t limit, int z, int k, uint32_t boundary0 = 0)
+template <bool RST, class Env, class Rec = NoRecord>
+HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_t begin, uint32_t limit, int z, int k, uint32_t boundary0 = 0,
+                                     Rec rec = Rec())
 {
+    static_assert(!RST || std::is_same<Rec, NoRecord>::value, "records are not taken across restart boundaries");
     uint32_t pos = begin, nblocks = 0;
     const uint32_t end = limit < im.total_bits ? limit : im.total_bits;
     // a pair's first symbol has at most kHuffFastBits - 2 bits: from here on the second one might start outside the range
@@ -305,6 +348,8 @@ HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_
             br.start(env, pos);
         }
     }
+    const uint32_t fresh = z == 0 ? 1u : 0u;  // records: index of the next block to start = nblocks + fresh
+    if (fresh && pos < end) rec(0u, pos);
     while (pos < end) {
         const uint32_t fetched = env.fetch(br.next);
         uint32_t e = env.lookup1(tcur, br.hi);
@@ -322,6 +367,7 @@ HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_
             }
             if (z >= 64) {
                 z = 0;
+                rec(nblocks + fresh, pos + tot);
                 nblocks++;
                 if (++k == bpm) k = 0;
                 tsel = env.tables(k);
@@ -367,14 +413,18 @@ HJ_HD uint32_t cooperative_table_changes(const Win& win, uint32_t blocks_per_mcu
         changes |= (HJ_UNIFORM(win.tables(q)) != HJ_UNIFORM(win.tables(q + 1 == blocks_per_mcu ? 0 : q + 1)) ? 1u : 0u) << q;
     return changes;
 }
-template <class Win>
-HJ_HD SubseqState cooperative_subsequence(const HuffGeom& im, Win& win, uint32_t changes, uint32_t begin, uint32_t limit, uint32_t z, uint32_t k)
+// rec: as decode_subsequence's (called with wave-uniform arguments).
+template <class Win, class Rec = NoRecord>
+HJ_HD SubseqState cooperative_subsequence(const HuffGeom& im, Win& win, uint32_t changes, uint32_t begin, uint32_t limit, uint32_t z, uint32_t k,
+                                          Rec rec = Rec())
 {
     const uint32_t end = HJ_UNIFORM(limit < im.total_bits ? limit : im.total_bits);
     const uint32_t bpm = HJ_UNIFORM(im.blocks_per_mcu);
     uint32_t pos = HJ_UNIFORM(begin), nblocks = 0;
     z = HJ_UNIFORM(z);
     k = HJ_UNIFORM(k);
+    const uint32_t fresh = z == 0 ? 1u : 0u;
+    if (fresh && pos < end) rec(0u, pos);
     uint32_t ts = HJ_UNIFORM(win.tables(k));  // read again only where the tables change
     while (pos < end) {
         win.open(pos, ts);
@@ -393,6 +443,7 @@ HJ_HD SubseqState cooperative_subsequence(const HuffGeom& im, Win& win, uint32_t
             z += e >> 9;
             if (z >= 64) {
                 z = 0;
+                rec(nblocks + fresh, pos + rel);
                 nblocks++;
                 const bool other_tables = (changes >> k) & 1u;
                 k = k + 1 == bpm ? 0 : k + 1;
