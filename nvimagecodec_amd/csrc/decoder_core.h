@@ -5,6 +5,7 @@
 // MI355X counterpart of the reference's per-thread {pinned buffer, device buffer, stream} resources
 // (extensions/nvjpeg/cuda_decoder.h:54-75), but sized for a whole batch so the device stage is one launch per kernel.
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <cstddef>
 #include <cstdint>
@@ -54,6 +55,22 @@ private:
 
 enum KernelVariant { kVarGray = 0, kVar11 = 1, kVar21 = 2, kVar22 = 3, kVar12 = 4, kNumLumaVariants = 5 };
 
+// Bump allocator over one arena: every region starts at the next multiple of `align` behind the one taken before it.
+struct Carve {
+    size_t end = 0;
+    size_t take(size_t bytes, size_t align = 256)
+    {
+        end = (end + align - 1) / align * align + bytes;
+        return end - bytes;
+    }
+};
+
+// A work-unit table and the byte offset it was staged at (the kernels read it from the device mirror there).
+struct UnitList {
+    std::vector<WorkUnit> units;
+    size_t offset = 0;
+};
+
 struct PlannedImage {
     FrameInfo frame;
     hipjpegStatus_t status = HIPJPEG_STATUS_SUCCESS;
@@ -77,8 +94,8 @@ struct PlannedImage {
     size_t boundary_offset = 0;   // restart boundaries + per-subsequence boundary index (staging area)
     uint32_t num_boundaries = 0;
     size_t block_pos_offset = 0;  // bytes into the block-position scratch
-    size_t dc_diff_offset = 0;
-    size_t dc_plane_offset[4] = {0, 0, 0, 0};  // bytes into the same scratch: compact DC planes per component  // bytes into the DC-difference scratch
+    size_t dc_diff_offset = 0;    // bytes into the DC-difference scratch
+    size_t dc_plane_offset[4] = {0, 0, 0, 0};  // bytes into the same scratch: compact DC planes per component
     uint32_t stream_bytes = 0;
     // progressive scans on the GPU entropy stage (progressive_gpu_core.h): gpu_entropy is set as well (device-only coefficient
     // arena, compact DC planes); every scan has a HuffImage of its own for the destuff kernels
@@ -141,70 +158,87 @@ public:
     int host_fallback_images() const { return host_fallback_images_; }  // GPU-entropy images the host decoder took over in resolve()
     bool has_progressive() const { return !prog_to_image_.empty(); }
     uint64_t stream_bytes() const { return stream_bytes_total_; }
+    // images of the current batch whose bitstream went to the device from the caller's own (pinned) memory
     int zero_copy_images() const { return zero_copy_images_; }
     uint64_t h2d_bytes() const { return h2d_used_; }  // bytes the current batch's transfer() copies to the device
-    int sparse_images() const
-    {
-        int n = 0;
-        for (const PlannedImage& im : images_) n += im.sparse ? 1 : 0;
-        return n;
-    }  // images of the current batch whose bitstream went to the device from the caller's own (pinned) memory
-    void flavour_units(int32_t* plane_units, int32_t luma_units[kNumLumaLayouts]) const
-    {
-        *plane_units = (int32_t)(plane_units_.size() + fused_plane_units_.size());
-        for (int e = 0; e < kNumLumaLayouts; e++) {
-            luma_units[e] = 0;
-            for (const auto& v : luma_units_[e]) luma_units[e] += (int32_t)v.size();
-            for (const auto& v : fused_luma_units_[e]) luma_units[e] += (int32_t)v.size();
-        }
-    }
-    int fused_units() const  // work units of the FUSED kernel builds (blocks decoded inside the pixel kernels) in the current batch
-    {
-        size_t n = fused_plane_units_.size();
-        for (int e = 0; e < kNumLumaLayouts; e++)
-            for (const auto& v : fused_luma_units_[e]) n += v.size();
-        return (int)n;
-    }
+    int sparse_images() const { return (int)std::count_if(images_.begin(), images_.end(), [](const PlannedImage& im) { return im.sparse; }); }
+    void flavour_units(int32_t* plane_units, int32_t luma_units[kNumLumaLayouts]) const { unit_counts(true, plane_units, luma_units); }
+    int fused_units() const;  // work units of the FUSED kernel builds (blocks decoded inside the pixel kernels) in the current batch
 
     int size() const { return (int)images_.size(); }
     const PlannedImage& image(int i) const { return images_[i]; }
     void stats(int32_t num_units[3], uint64_t* coef_bytes, uint64_t* output_bytes) const;
 
 private:
-    hipjpegStatus_t plan_once(const uint8_t* const* data, const size_t* lengths, int n, const hipjpegOutput_t* outputs,
-                              hipjpegOutputFormat_t format, unsigned flags, hipjpegStatus_t* statuses, const hipjpegOutputFormat_t* formats,
-                              ForkJoinPool* pool, const hipjpegTransform_t* transforms, const std::vector<char>& give_up);
     int device_id_;
+    ForkJoinPool* pool_ = nullptr;  // the pool plan() was given (resolve() decodes handed-over images on it)
+    uint64_t gpu_entropy_min_pixels_ = 0;
+
+    // ---- plan(): per-image checks and descriptors, sizes, layout of the arenas, device pointers
+    struct PlanArgs;  // plan()'s arguments as prepare() reads them
+    struct Sizing;    // what the per-image sizing adds up
+    hipjpegStatus_t plan_once(const PlanArgs& a, int n, hipjpegStatus_t* statuses);
+    void prepare(int i, const PlanArgs& a);
+    bool pitch_ok(int i, const hipjpegOutput_t& out, OutFormat fmt) const;
+    void demote_progressive_lds();
+    void size_image(int i, Sizing& s);
+    void layout(const Sizing& s);
+    hipjpegStatus_t reserve(const Sizing& s);
+    void bind_pointers(const Sizing& s);
     Buffer pinned_, device_, planes_;
+    // Staging area, pinned and mirrored on the device at the same offsets:  descriptors | work units | entropy descriptors, units,
+    // tables | staged bitstreams [streams, coef) | coefficients of host-decoded images  ||  (device only from h2d_bytes) coefficients of
+    // GPU-decoded images.  The pinned side keeps 256 spare bytes behind h2d_bytes (entropy_launch_args).
+    struct StagingLayout {
+        size_t desc, units, huff_desc, huff_units, huff_wunits, huff_dc_units, huff_list, huff_chunk_units, huff_drops, xform_desc, xform_units,
+            prog_desc, prog_units, tables, boundaries, streams, coef, h2d_bytes, gpu_coef_begin, total;
+    } staging_{};
+    // Device-only scratch of the entropy kernels (work_): subsequence states (at 0) | first block indices | change counters | ...
+    struct WorkLayout {
+        size_t first_block, changed, incoming, tail, dc_diff, block_pos, records, walkers, drops, prog_pos, group_sums, streams, total;
+    } scratch_{};
+    Buffer work_;
     std::vector<PlannedImage> images_;
     std::vector<DecodeImage> desc_;  // host copy (device pointers inside)
-    std::vector<WorkUnit> plane_units_, luma_units_[kNumLumaLayouts][kNumLumaVariants], generic_units_, cmyk_units_;  // luma: [layout of K2][sampling]
-    size_t desc_offset_ = 0, units_offset_ = 0, coef_offset_ = 0, staging_bytes_ = 0, plane_bytes_ = 0;
-    size_t unit_off_plane_ = 0, unit_off_luma_[kNumLumaLayouts][kNumLumaVariants] = {{0}}, unit_off_generic_ = 0, unit_off_cmyk_ = 0;
-    // Images of the GPU entropy stage (baseline): their K1 / K2 units go to the FUSED kernel builds, which Huffman-decode the blocks
-    // themselves (decode_kernels.hip) -- same unit geometry.  host_taken_: such images the host entropy decoder took over in resolve()
-    // (damaged / periodic streams): their coefficients then lie in HBM and the plain builds run for them (launch_taken_pixels).
-    std::vector<WorkUnit> fused_plane_units_, fused_luma_units_[kNumLumaLayouts][kNumLumaVariants];
-    size_t unit_off_fused_plane_ = 0, unit_off_fused_luma_[kNumLumaLayouts][kNumLumaVariants] = {{0}};
-    bool fused_ = false;
     // HIPJPEG_FLAG_FAST_IDCT of the batch being planned: the descriptors' qpk hold IFAST multiplier tables and K1 / K2 launch their
     // fast-IDCT flavour; such a batch never takes the FUSED builds (they have no IFAST flavour).  Set by every plan().
     bool fast_idct_ = false;
-    uint64_t gpu_entropy_min_pixels_ = 0;
-    size_t raw_region_begin_ = 0, raw_region_end_ = 0;  // the staged bitstreams inside the H2D part of the staging area
-    // Host-decoded coefficients are handed out of their region [coef_offset_, h2d_bytes_) first come first served while the pool threads
-    // decode (a sparse stream's size is known only then): h2d_used_ = what transfer() actually has to copy.
+    uint64_t coef_bytes_ = 0, output_bytes_ = 0;
+    // Host-decoded coefficients are handed out of their region [staging_.coef, staging_.h2d_bytes) first come first served while the
+    // pool threads decode (a sparse stream's size is known only then): h2d_used_ = what transfer() actually has to copy.
     bool sparse_mode_ = false;
     std::atomic<size_t> host_coef_used_{0};
     size_t h2d_used_ = 0;
-    int zero_copy_images_ = 0;
-    std::vector<int> host_taken_;
-    void* taken_units_dev_ = nullptr;
-    size_t taken_units_cap_ = 0;
-    int launch_taken_pixels(void* stream, int which);
-    uint64_t coef_bytes_ = 0, output_bytes_ = 0;
+    // ---- entropy_stage(), finalize(): unit tables, entropy descriptors, staging of the tables
+    void stage_chunk_drops(const ScanHeader& sc, uint32_t first_chunk);
+    void build_pixel_units();
+    void build_entropy_units();
+    void stage_tables();
+    void unit_counts(bool plain, int32_t* plane, int32_t luma[kNumLumaLayouts]) const;
+    UnitList plane_units_, luma_units_[kNumLumaLayouts][kNumLumaVariants], generic_units_, cmyk_units_, xform_units_;  // luma: [layout of K2][sampling]
+    // Images of the GPU entropy stage (baseline): their K1 / K2 units go to the FUSED kernel builds, which Huffman-decode the blocks
+    // themselves (decode_kernels.hip) -- same unit geometry.  host_taken_: such images the host entropy decoder took over in resolve()
+    // (damaged / periodic streams): their coefficients then lie in HBM and the plain builds run for them (launch_taken_pixels).
+    UnitList fused_plane_units_, fused_luma_units_[kNumLumaLayouts][kNumLumaVariants];
+    bool fused_ = false;
     bool finalized_ = false;
-    // ---- GPU entropy stage
+    std::vector<TransformImage> xform_desc_;
+    // GPU entropy stage: baseline images first, then one HuffImage per scan of the progressive images
+    std::vector<HuffImage> huff_images_;
+    std::vector<HuffUnit> huff_units_, huff_dc_units_;
+    std::vector<uint32_t> huff_list_;
+    std::vector<int> huff_to_image_;
+    std::vector<HuffUnit> huff_wunits_;       // block kernel: kHuffMcusPerWg MCUs per workgroup
+    std::vector<HuffUnit> huff_chunk_units_;  // destuff kernels: one per kDestuffChunk bytes of a scan
+    size_t total_subseq_ = 0, max_huff_units_ = 0, max_pool_words_ = 0;
+    std::atomic<bool> host_drops_missing_{false};  // set by a host task that found a scan without counts: the device counts instead
+    // progressive images of the batch
+    std::vector<ProgImage> prog_images_;
+    std::vector<int> prog_to_image_;
+    std::vector<HuffUnit> prog_units_;  // replay kernel: {ProgImage index, component << 28 | first block}
+    unsigned prog_slot_words_ = 0;
+    uint64_t stream_bytes_total_ = 0;
+    // ---- transfer(), launch(), resolve()
     struct EntropyLaunch {
         HuffImage* dimg;
         const HuffUnit *dunits, *dwunits, *ddc;
@@ -222,43 +256,23 @@ private:
     };
     EntropyLaunch entropy_launch_args();
     bool entropy_write_passes(const EntropyLaunch& L, void* stream);
-    void stage_chunk_drops(const ScanHeader& sc, uint32_t first_chunk);
     hipjpegStatus_t enqueue_gpu_entropy(void* stream);
-    int launch_pixel_kernels(void* stream, int which);
-    bool entropy_pending_ = false, pixels_launched_ = false, copy_pending_ = false;
-    void* last_stream_ = nullptr;  // stream of the last launch()
-    void* copied_event_ = nullptr;
-    void* entropy_event_ = nullptr;  // hipEvent_t: entropy stage finished on its own stream  // hipEvent_t: H2D copy issued on a stream other than the kernels' 
-    Buffer work_;  // device only: subsequence states, first-block indices, change counter
-    std::vector<HuffImage> huff_images_;
-    std::vector<HuffUnit> huff_units_, huff_dc_units_;
-    std::vector<uint32_t> huff_list_;
-    std::vector<int> huff_to_image_;
-    size_t huff_desc_offset_ = 0, huff_units_offset_ = 0, huff_dc_units_offset_ = 0, huff_list_offset_ = 0, h2d_bytes_ = 0;
-    size_t gpu_coef_begin_ = 0, gpu_coef_bytes_ = 0, total_subseq_ = 0, max_huff_units_ = 0, max_pool_words_ = 0;
-    size_t work_first_block_ = 0, work_changed_ = 0, work_incoming_ = 0, work_tail_ = 0, work_dc_diff_ = 0, work_block_pos_ = 0, work_records_ = 0, work_walkers_ = 0, work_drops_ = 0, work_streams_ = 0, work_group_sums_ = 0;
-    size_t huff_chunk_units_offset_ = 0, huff_wunits_offset_ = 0, max_huff_wunits_ = 0;
-    size_t huff_drops_offset_ = 0;  // per destuff chunk: bytes to drop, counted by the parser's marker walk (ScanHeader::chunk_drops)
-    std::atomic<bool> host_drops_missing_{false};  // set by a host task that found a scan without counts: the device counts instead
-    std::vector<TransformImage> xform_desc_;
-    std::vector<WorkUnit> xform_units_;
-    size_t xform_desc_offset_ = 0, xform_units_offset_ = 0;
-    std::vector<HuffUnit> huff_wunits_;  // block kernel: kHuffMcusPerWg MCUs per workgroup
-    std::vector<HuffUnit> huff_chunk_units_;  // offsets into work_
-    // progressive images of the batch
-    std::vector<ProgImage> prog_images_;
-    std::vector<int> prog_to_image_;
-    std::vector<HuffUnit> prog_units_;  // replay kernel: {ProgImage index, component << 28 | first block}
-    size_t prog_desc_offset_ = 0, prog_units_offset_ = 0, max_prog_units_ = 0, prog_scan_total_ = 0, work_prog_pos_ = 0;
-    unsigned prog_slot_words_ = 0;
     hipjpegStatus_t enqueue_progressive(void* stream);
-    uint64_t stream_bytes_total_ = 0;
-    int last_sync_launches_ = 0, host_fallback_images_ = 0;
-    ForkJoinPool* pool_ = nullptr;  // the pool plan() was given (resolve() decodes handed-over images on it)
-    unsigned sync_rounds_total_ = 0, sync_rounds_max_ = 0;  // correction rounds of the first sync launch (sum over workgroups, maximum)
-    bool entropy_done_ = false;
-    void* done_event_ = nullptr;  // hipEvent_t recorded after the last launch that reads this batch's buffers
+    int launch_pixel_kernels(void* stream, int which);
+    int launch_taken_pixels(void* stream, int which);
+    void print_progressive_timing(const ProgImage* hprog) const;
+    hipjpegStatus_t take_over_on_host(const std::vector<int>& takeover, bool* redo_pixels);
+    int zero_copy_images_ = 0;
+    std::vector<int> host_taken_;
+    void* taken_units_dev_ = nullptr;
+    size_t taken_units_cap_ = 0;
+    bool entropy_pending_ = false, pixels_launched_ = false, copy_pending_ = false, entropy_done_ = false;
+    void* last_stream_ = nullptr;    // stream of the last launch()
+    void* copied_event_ = nullptr;   // hipEvent_t: H2D copy issued on a stream other than the kernels'
+    void* entropy_event_ = nullptr;  // hipEvent_t: entropy stage finished on its own stream
+    void* done_event_ = nullptr;     // hipEvent_t recorded after the last launch that reads this batch's buffers
     bool in_flight_ = false;
+    int last_sync_launches_ = 0, host_fallback_images_ = 0;
 };
 
 // status helpers

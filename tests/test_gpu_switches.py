@@ -12,8 +12,9 @@ HELPER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers", "de
 
 
 @pytest.mark.parametrize("switches", [{"HIPJPEG_DEVICE_DESTUFF_COUNT": "1"}, {"HIPJPEG_TAIL_AFTER": "1"}, {"HIPJPEG_FUSED_DECODE": "1"}, {"HIPJPEG_DENSE_STAGING": "1"},
-                                      {"HIPJPEG_DEVICE_DESTUFF_COUNT": "1", "HIPJPEG_TAIL_AFTER": "3", "HIPJPEG_FUSED_DECODE": "1"}],
-                         ids=["device_destuff_count", "tail_after_1", "fused_decode", "dense_staging", "all"])
+                                      {"HIPJPEG_DEVICE_DESTUFF_COUNT": "1", "HIPJPEG_TAIL_AFTER": "3", "HIPJPEG_FUSED_DECODE": "1"},
+                                      {"HIPJPEG_PROG_LDS_LIMIT": "1"}],
+                         ids=["device_destuff_count", "tail_after_1", "fused_decode", "dense_staging", "all", "prog_lds_limit"])
 def test_goldens_under_switch(switches):
     env = dict(os.environ)
     env.update(switches)
