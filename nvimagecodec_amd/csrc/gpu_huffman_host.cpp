@@ -311,7 +311,12 @@ int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, in
     const bool rst = sc.restart_interval != 0;
     for (int c = 0; c < f.ncomp; c++) {
         im.coef[c] = coef[c];
-        memset(coef[c], 0x5A, (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 128);  // every block must be written by the write pass
+        // every coded block must be written by the write pass; a one-component scan codes the real blocks only (T.81 A.2.2), the
+        // padding blocks of its MCU-padded grid stay zero as in the host decoder
+        const size_t bw = (size_t)f.comp[c].blocks_w, rows = f.ncomp == 1 ? im.mcus_y : (size_t)f.comp[c].blocks_h;
+        const size_t cols = f.ncomp == 1 ? im.mcus_x : bw;
+        memset(coef[c], 0, bw * f.comp[c].blocks_h * 128);
+        for (size_t y = 0; y < rows; y++) memset(coef[c] + y * bw * 64, 0x5A, cols * 128);
     }
     int16_t block_buffer[64] = {0};
     const HostEnv env{&im, block_buffer};

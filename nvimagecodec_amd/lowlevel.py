@@ -158,9 +158,9 @@ class BatchDecoder:
                 outs.append(torch.empty((3, h, w), dtype=torch.uint8, device=dev))
             elif fmt == "y":
                 outs.append(torch.empty((h, w), dtype=torch.uint8, device=dev))
-            else:
+            else:  # (hipjpegOutput_t holds three planes: four-component frames have no raw planes and are declined)
                 outs.append([torch.empty((info["samp_h"][c], info["samp_w"][c]), dtype=torch.uint8, device=dev)
-                             for c in range(info["num_components"])])
+                             for c in range(min(info["num_components"], 3))])
         return outs
 
     def _marshal(self, jpegs, outs, fmt):

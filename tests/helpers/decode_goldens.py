@@ -1,6 +1,6 @@
 """Test helper (run as a child process): decodes every golden bitstream in one batch through the GPU entropy stage and the host one and
-compares with the manifest's hashes -- so that a test can run it under the library's measurement switches, which are read once per
-process (HIPJPEG_DEVICE_DESTUFF_COUNT, HIPJPEG_NO_PK16, HIPJPEG_SINGLE_STREAM ...)."""
+compares with the manifest's hashes, then the sampling-layout goldens with libjpeg-turbo's hashes -- so that a test can run it under the
+library's measurement switches, which are read once per process (HIPJPEG_DEVICE_DESTUFF_COUNT, HIPJPEG_NO_PK16, HIPJPEG_SINGLE_STREAM ...)."""
 import hashlib
 import json
 import os
@@ -28,6 +28,25 @@ def main():
             got = hashlib.sha256(np.ascontiguousarray(o.cpu().numpy()).tobytes()).hexdigest()
             assert got == e["rgb_sha256"], (e["name"], gh)
     plane, luma = dec.kernel_flavours()
+    # the sampling-layout goldens (tests/helpers/sampling_goldens.py): libjpeg-turbo's pixels, or a decline where the restatement of
+    # its upsampler choice says the decoder cannot match them
+    import oracle
+    from helpers import sampling_goldens as G
+    from test_cmyk import _reference_rgb
+    sampling = [G.jpeg(e) for e in G.ENTRIES]
+    for gh in (True, False):
+        outs, st = dec.decode(sampling, fmt="rgb", gpu_huffman=gh, check=False)
+        torch.cuda.synchronize()
+        for e, j, o, s in zip(G.ENTRIES, sampling, outs, st):
+            assert s == (3 if G.expected_unsupported(e, "rgb", True) else 0), (e["name"], gh, s)
+            if s:
+                continue
+            got, n = o.cpu().numpy(), len(e["sampling"])
+            if n == 4:  # the reference's CMYK -> RGB step on libjpeg-turbo's samples
+                samples = oracle.decode_cmyk(j)
+                assert G.sha(samples) == e["sha256"] and np.array_equal(got, _reference_rgb(samples, e["kind"] != "plain")), (e["name"], gh)
+            else:  # (a gray frame: the luma three times)
+                assert G.sha(got if n == 3 else got[:, :, 0]) == e["sha256"] and (n == 3 or (got == got[:, :, :1]).all()), (e["name"], gh)
     if os.environ.get("HIPJPEG_FUSED_DECODE"):
         # the pixel kernels decode the blocks themselves: damaged streams are flagged THERE, the host decoder takes them over and the
         # plain kernels finish them (DecodeBatch::launch_taken_pixels) -- same statuses and pixels as with Huffman decoding on the host

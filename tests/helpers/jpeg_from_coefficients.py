@@ -68,16 +68,26 @@ def _magnitude(v):
     return nb, (int(v) if v >= 0 else int(v) - 1) & ((1 << nb) - 1)
 
 
-def write_baseline(width, height, sampling, coefficients, qtables):
+def _adobe_segment(transform):
+    """APP14 "Adobe" segment (version 100, no flags) with the given colour transform: 0 = none (RGB / CMYK), 1 = YCbCr, 2 = YCCK."""
+    return b"\xff\xee" + (14).to_bytes(2, "big") + b"Adobe" + (100).to_bytes(2, "big") + bytes(4) + bytes([transform])
+
+
+def write_baseline(width, height, sampling, coefficients, qtables, adobe=None, restart_interval=0):
     """sampling: [(h, v)] per component; coefficients[c]: int array [blocks_h][blocks_w][64] in natural (row-major) order over the
     MCU-padded block grid, DC values absolute; qtables[c]: 64 quantizers in natural order (values 1..255; any value above 255 in a
     table makes it a 16-bit table and the frame an extended-sequential one, SOF1).  Component 0 uses the luminance Huffman tables,
     the others the chrominance ones.  DC values may leave int16 as long as successive differences fit 11 bits: libjpeg keeps the
-    predictor in an int and stores its low 16 bits in the block.  Returns the file as bytes."""
+    predictor in an int and stores its low 16 bits in the block.  A one-component frame is coded non-interleaved whatever its
+    factors (T.81 A.2.2): one block per MCU, its REAL blocks (ceil(samples / 8) each way) in raster order; the padding blocks of the
+    grid are not coded.  adobe: None, or the transform byte of an APP14 Adobe segment (0, 1, 2).  restart_interval: MCUs between
+    RSTn markers (0: none).  Returns the file as bytes."""
     ncomp = len(sampling)
     hmax, vmax = max(h for h, _ in sampling), max(v for _, v in sampling)
     mcus_x, mcus_y = -(-width // (8 * hmax)), -(-height // (8 * vmax))
     out = bytearray(b"\xff\xd8")
+    if adobe is not None:
+        out += _adobe_segment(adobe)
     wide = False
     for c in range(ncomp):
         q = [int(qtables[c][ZIGZAG[k]]) for k in range(64)]
@@ -93,43 +103,51 @@ def write_baseline(width, height, sampling, coefficients, qtables):
     tables = [(0x00, DC_LUMA), (0x10, AC_LUMA)] + ([(0x01, DC_CHROMA), (0x11, AC_CHROMA)] if ncomp > 1 else [])
     for ident, (bits, vals) in tables:
         out += b"\xff\xc4" + (19 + len(vals)).to_bytes(2, "big") + bytes([ident]) + bytes(bits) + bytes(vals)
+    if restart_interval:
+        out += b"\xff\xdd" + (4).to_bytes(2, "big") + int(restart_interval).to_bytes(2, "big")
     out += b"\xff\xda" + (6 + 2 * ncomp).to_bytes(2, "big") + bytes([ncomp])
     for c in range(ncomp):
         out += bytes([c + 1, 0x00 if c == 0 else 0x11])
     out += b"\x00\x3f\x00"
     dc_codes = [_codes(*DC_LUMA)] + [_codes(*DC_CHROMA)] * (ncomp - 1)
     ac_codes = [_codes(*AC_LUMA)] + [_codes(*AC_CHROMA)] * (ncomp - 1)
+    if ncomp == 1:  # non-interleaved: an MCU is one real block
+        mcus = [[(0, y, x)] for y in range(-(-height // 8)) for x in range(-(-width // 8))]
+    else:
+        mcus = [[(c, my * v + by, mx * h + bx) for c, (h, v) in enumerate(sampling) for by in range(v) for bx in range(h)]
+                for my in range(mcus_y) for mx in range(mcus_x)]
     bw = _Bits()
     pred = [0] * ncomp
-    for my in range(mcus_y):
-        for mx in range(mcus_x):
-            for c, (h, v) in enumerate(sampling):
-                for by in range(v):
-                    for bx in range(h):
-                        blk = coefficients[c][my * v + by][mx * h + bx]
-                        diff = int(blk[0]) - pred[c]
-                        pred[c] = int(blk[0])
-                        nb, bits = _magnitude(diff)
-                        assert nb <= 11, "DC difference beyond category 11"
-                        bw.put(*dc_codes[c][nb])
-                        if nb:
-                            bw.put(bits, nb)
-                        run = 0
-                        for k in range(1, 64):
-                            val = int(blk[ZIGZAG[k]])
-                            if val == 0:
-                                run += 1
-                                continue
-                            while run > 15:
-                                bw.put(*ac_codes[c][0xF0])
-                                run -= 16
-                            nb, bits = _magnitude(val)
-                            assert nb <= 10
-                            bw.put(*ac_codes[c][(run << 4) | nb])
-                            bw.put(bits, nb)
-                            run = 0
-                        if run:
-                            bw.put(*ac_codes[c][0x00])
+    for m, mcu in enumerate(mcus):
+        if restart_interval and m and m % restart_interval == 0:  # byte-align with 1-bits, RSTn, predictors back to 0
+            bw.flush()
+            bw.out += bytes([0xFF, 0xD0 + (m // restart_interval - 1) % 8])
+            pred = [0] * ncomp
+        for c, y, x in mcu:
+            blk = coefficients[c][y][x]
+            diff = int(blk[0]) - pred[c]
+            pred[c] = int(blk[0])
+            nb, bits = _magnitude(diff)
+            assert nb <= 11, "DC difference beyond category 11"
+            bw.put(*dc_codes[c][nb])
+            if nb:
+                bw.put(bits, nb)
+            run = 0
+            for k in range(1, 64):
+                val = int(blk[ZIGZAG[k]])
+                if val == 0:
+                    run += 1
+                    continue
+                while run > 15:
+                    bw.put(*ac_codes[c][0xF0])
+                    run -= 16
+                nb, bits = _magnitude(val)
+                assert nb <= 10
+                bw.put(*ac_codes[c][(run << 4) | nb])
+                bw.put(bits, nb)
+                run = 0
+            if run:
+                bw.put(*ac_codes[c][0x00])
     bw.flush()
     out += bw.out + b"\xff\xd9"
     return bytes(out)
