@@ -255,15 +255,7 @@ __device__ __forceinline__ void fetch_half_block(const DecodeComponent& cd, int 
     for (int k = 0; k < 4; k++) {
         const int g = k * 64 + lane;
         u32x4 v = {0u, 0u, 0u, 0u};
-#ifdef HJ_ABLATE_COEF
-        if (g < nchunks) v = u32x4{(unsigned)g, 1u, 0u, 0u};
-#else
-#ifdef HJ_DEC_PLAIN_LOADS
-        if (g < nchunks) v = *((const HJ_GLOBAL u32x4*)src + g);
-#else
         if (g < nchunks) v = __builtin_nontemporal_load((const HJ_GLOBAL u32x4*)src + g);
-#endif
-#endif
         *reinterpret_cast<u32x4*>(lds_wave + (g >> 3) * kLdsBlockStride + (g & 7) * 16) = v;
     }
     wave_lds_fence();
@@ -298,11 +290,7 @@ __device__ __forceinline__ void fetch_tile_half_block(const DecodeComponent& cd,
         u32x4 v = {0u, 0u, 0u, 0u};
         // byte offset in 32 bits (a component's blocks are far below 4 GB): SGPR base + VGPR offset addressing
         if (row < bh && col < bw)
-#ifdef HJ_DEC_PLAIN_LOADS
-            v = *(const HJ_GLOBAL u32x4*)((const HJ_GLOBAL char*)src + ((unsigned)(row * bw + col) * 128u + (unsigned)(g & 7) * 16u));
-#else
             v = __builtin_nontemporal_load((const HJ_GLOBAL u32x4*)((const HJ_GLOBAL char*)src + ((unsigned)(row * bw + col) * 128u + (unsigned)(g & 7) * 16u)));
-#endif
         *reinterpret_cast<u32x4*>(lds_wave + j * kLdsBlockStride + (g & 7) * 16) = v;
     }
     wave_lds_fence();
@@ -730,15 +718,11 @@ __device__ __forceinline__ void load_chroma_rows(const uint8_t* __restrict__ pla
         const uint8_t* src = plane + (__umul24((unsigned)y, pitch) + (unsigned)base);  // planes are far smaller than 4 GB
         // planes are allocated with >= 16 bytes of slack per row, so an 8-byte read starting inside the row is in bounds
         uint2 v;
-#ifdef HJ_ABLATE_CHROMA
-        v = make_uint2(0x80808080u + (unsigned)(uintptr_t)src, 0x80808080u);
-#else
         {
             typedef u32x2 __attribute__((aligned(1))) u32x2_unaligned;  // the window starts at any byte; gfx950 loads it in one go
             const u32x2 t = *(const HJ_GLOBAL u32x2_unaligned*)src;
             v = make_uint2(t.x, t.y);
         }
-#endif
         rows[k] = v;
     }
     if (__builtin_amdgcn_ballot_w64(edge) != 0) {
@@ -1045,15 +1029,8 @@ __device__ __forceinline__ void luma_color_body(const DecodeImage& im, const Wor
             const u32x4 v = *reinterpret_cast<const u32x4*>(lds_wave + r * lds_row_bytes + off);
             uint8_t* dst = out_base + (__umul24((unsigned)r, im.out_pitch[0]) + (unsigned)off);
             if (off + 16 <= row_bytes) {
-#ifdef HJ_ABLATE_STORE
-                if (v.x == 0x12345678u && v.y == 0x9abcdef0u)  // practically never: keeps the value live, drops the traffic
-#endif
                 typedef u32x4 __attribute__((aligned(1))) u32x4_unaligned;
-#ifdef HJ_DEC_PLAIN_STORES
-                *(HJ_GLOBAL u32x4_unaligned*)dst = v;
-#else
                 __builtin_nontemporal_store(v, (HJ_GLOBAL u32x4_unaligned*)dst);
-#endif
             } else {
                 const unsigned w[4] = {v.x, v.y, v.z, v.w};
                 for (int j = 0; j < row_bytes - off; j++) dst[j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));

@@ -950,11 +950,10 @@ void DecodeBatch::build_entropy_units()
 // The luma tiles of a tile row share chroma lines at their seams (fancy upsampling reads a sample to the left and to the right of a
 // tile: one more 128-byte line on either side), and the hardware deals workgroups to the eight XCDs -- eight L2 caches -- in turn.  So the
 // rows are dealt to eight queues and the list takes one tile of every queue in turn: position p goes to XCD p % 8, a row's tiles follow
-// each other on ONE XCD and find their neighbour's lines in its L2.  (HIPJPEG_ROW_MAJOR_TILES=1: the plain order, for A/B runs.)
+// each other on ONE XCD and find their neighbour's lines in its L2.
 static void deal_rows_to_xcds(std::vector<WorkUnit>& v)
 {
-    static const bool row_major = getenv("HIPJPEG_ROW_MAJOR_TILES") != nullptr;
-    if (row_major || v.size() < 64) return;
+    if (v.size() < 64) return;
     constexpr size_t kXcds = 8;
     std::vector<WorkUnit> queue[kXcds], rest, out;
     out.reserve(v.size());
@@ -1287,11 +1286,6 @@ void DecodeBatch::print_progressive_timing(const ProgImage* hprog) const
                 "all %u images: %.3f / %.3f / %.3f ms\n",
                 k, q0.scan[k].ss, q0.scan[k].se, q0.scan[k].ah, q0.scan[k].al, q0.scan[k].walk_ticks * 1e-5, q0.scan[k].wait_ticks * 1e-5, (hw >> 13) & 7u,
                 (hw >> 8) & 15u, (hw >> 4) & 3u, cnt, lo * 1e-5, cnt ? sum / cnt * 1e-5 : 0.0, hi * 1e-5);
-        if (getenv("HIPJPEG_WALK_LAPS"))  // a library built with -DHJ_WALK_PROFILE (tools/walk_laps.sh): the packed lap timers
-            fprintf(stderr, "[hipjpeg]   laps (cycles / count): fast %u / %u, event %u / %u, window %u / %u, block %u / %u\n",
-                    (q0.scan[k].wait_ticks & 0xFFFFu) << 12, (q0.scan[k].pad_ticks[1] & 0xFFFFu) << 4, (q0.scan[k].wait_ticks >> 16) << 12,
-                    (q0.scan[k].pad_ticks[1] >> 16) << 4, (q0.scan[k].pad_ticks[0] & 0xFFFFu) << 12, (q0.scan[k].pad_ticks[2] & 0xFFFFu) << 4,
-                    (q0.scan[k].pad_ticks[0] >> 16) << 12, (q0.scan[k].pad_ticks[2] >> 16) << 4);
     }
 }
 
@@ -1398,29 +1392,6 @@ int DecodeBatch::launch_pixel_kernels(void* stream, int which)
     auto dev = [&](const UnitList& l) { return at<const WorkUnit>(device_, l.offset); };
     auto count = [](const UnitList& l) { return (int)l.units.size(); };
     int rc = 0;
-    if (which == 7) {
-        // measurement aid: K1 and K2 alternate over slices of HIPJPEG_PIXEL_CHUNK images, so that a slice's chroma
-        // planes are still in the 256 MB Infinity Cache when its K2 reads them -- DESIGN.md 3.1 has what it measured
-        static const int chunk = getenv("HIPJPEG_PIXEL_CHUNK") ? std::max(1, atoi(getenv("HIPJPEG_PIXEL_CHUNK"))) : 16;
-        auto slice = [](const std::vector<WorkUnit>& v, uint32_t a, uint32_t b, size_t* first) {
-            auto lo = std::lower_bound(v.begin(), v.end(), a, [](const WorkUnit& u, uint32_t x) { return u.image < x; });
-            auto hi = std::lower_bound(lo, v.end(), b, [](const WorkUnit& u, uint32_t x) { return u.image < x; });
-            *first = (size_t)(lo - v.begin());
-            return (int)(hi - lo);
-        };
-        const uint32_t n = (uint32_t)images_.size();
-        for (uint32_t a = 0; a < n && rc == 0; a += (uint32_t)chunk) {
-            size_t first = 0;
-            const int cnt = slice(plane_units_.units, a, a + chunk, &first);
-            rc = launch_idct_plane(dimg, dev(plane_units_) + first, cnt, stream, fast_idct_);
-            for (int e = 0; e < kNumLumaLayouts; e++)
-                for (int k = 0; k < kNumLumaVariants && rc == 0; k++) {
-                    const int cnt = slice(luma_units_[e][k].units, a, a + chunk, &first);
-                    rc = launch_luma_color(e, kLumaHs[k], kLumaVs[k], dimg, dev(luma_units_[e][k]) + first, cnt, stream, fast_idct_);
-                }
-        }
-        return rc;
-    }
     HuffImage* himg = at<HuffImage>(device_, staging_.huff_desc);
     const unsigned pool_bytes = (unsigned)align_up(max_pool_words_ * 2, 256);
     if (rc == 0 && (which < 0 || which == 0)) {

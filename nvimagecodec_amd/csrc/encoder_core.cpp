@@ -221,9 +221,7 @@ hipjpegStatus_t EncodeBatch::gpu_entropy_stage(std::vector<char>* todo)
         im.gpu_bitstream = nullptr;
         im.gpu_bitstream_len = 0;
         if (im.status != HIPJPEG_STATUS_SUCCESS) continue;
-        // HIPJPEG_NO_GPU_OPTIMIZED_HUFFMAN=1: per-image tables on the host coder as in round 2 (A/B and cross-check aid)
-        static const bool gpu_optimized = getenv("HIPJPEG_NO_GPU_OPTIMIZED_HUFFMAN") == nullptr;
-        if (im.params.restart_interval == 0 && !im.params.progressive && (gpu_optimized || !im.params.optimized_huffman))
+        if (im.params.restart_interval == 0 && !im.params.progressive)
             idx.push_back(i);
         else
             (*todo)[i] = 1;  // restart markers / progressive scans: the host coder
@@ -379,8 +377,7 @@ hipjpegStatus_t EncodeBatch::gpu_entropy_stage(std::vector<char>* todo)
     // The finished files go straight into pinned host memory when it is ours (hipHostMalloc: mapped into the device's address
     // space): the expand kernel's stores cross PCIe themselves and no copy follows.  With a caller-supplied pinned allocator
     // the mapping is unknown, so the files are assembled in HBM and copied.
-    static const bool no_direct = getenv("HIPJPEG_ENCODE_STAGED_OUTPUT") != nullptr;
-    bool direct = !no_direct && henc_out_.reserve(arena_cap + 256) == HIPJPEG_STATUS_SUCCESS && !henc_out_.custom();
+    bool direct = henc_out_.reserve(arena_cap + 256) == HIPJPEG_STATUS_SUCCESS && !henc_out_.custom();
     uint8_t* arena = direct ? henc_out_.data() : dev2 + q_arena;
     if (hipMemcpyAsync(dev2, pin + p_up2, up2, hipMemcpyHostToDevice, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
     if (launch_henc_zero(dev2 + q_raw, raw_total, stream_) != 0) return HIPJPEG_STATUS_HIP_ERROR;

@@ -3,8 +3,6 @@
 // goldens): jchuff.c encode_one_block for the symbols, jccoefct.c compress_data for the dummy blocks of the MCU padding.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "gpu_huffman_encode.h"
 
 namespace hipjpeg {
@@ -607,8 +605,7 @@ int launch_henc_expand(const HencImage* images, const HencUnit* chunk_units, int
                        const unsigned long long* final_off, uint8_t* arena, void* stream)
 {
     if (nchunks <= 0) return 0;
-    static const int tuned = getenv("HIPJPEG_EXPAND_GRID") ? atoi(getenv("HIPJPEG_EXPAND_GRID")) : kExpandGrid;  // dev aid
-    const int grid = nchunks < tuned ? nchunks : (tuned > 0 ? tuned : kExpandGrid);
+    const int grid = nchunks < kExpandGrid ? nchunks : kExpandGrid;
     hipLaunchKernelGGL(henc_expand_kernel, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, images, chunk_units, chunk_out, final_len, final_off,
                        arena, nchunks);
     return (int)hipGetLastError();

@@ -347,7 +347,7 @@ hipjpegStatus_t hipjpegDecodeBatchDevice(hipjpegHandle_t handle, void* stream)
 hipjpegStatus_t hipjpegDecodeBatchDeviceKernel(hipjpegHandle_t handle, int which, void* stream)
 {
     return guarded([&]() -> hipjpegStatus_t {
-    if (!handle) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (!handle || which < 0 || which > 6 || which == 5) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     return handle->cur().launch(stream, which);
     });
 }
@@ -387,8 +387,7 @@ hipjpegStatus_t hipjpegDecodeBatchSubmit(hipjpegHandle_t handle, const uint8_t* 
     if (handle->num_submitted >= handle->pages) return HIPJPEG_STATUS_INVALID_ARGUMENT;  // every page in flight: Wait first
     if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
     if (!handle->copy_stream && hipStreamCreateWithFlags(&handle->copy_stream, hipStreamNonBlocking) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-    static const bool two_streams = getenv("HIPJPEG_SINGLE_STREAM") == nullptr;  // HIPJPEG_SINGLE_STREAM=1: measurement aid
-    if (two_streams && !handle->entropy_stream && hipStreamCreateWithFlags(&handle->entropy_stream, hipStreamNonBlocking) != hipSuccess)
+    if (!handle->entropy_stream && hipStreamCreateWithFlags(&handle->entropy_stream, hipStreamNonBlocking) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;
     hipjpegStatus_t st = hipjpegDecodeBatchHost(handle, data, lengths, batch_size, outputs, format, flags, nullptr);
     if (st != HIPJPEG_STATUS_SUCCESS) return st;
@@ -406,7 +405,7 @@ hipjpegStatus_t hipjpegDecodeBatchSubmit(hipjpegHandle_t handle, const uint8_t* 
     };
     try {
         if ((st = b.transfer(handle->copy_stream, true)) == HIPJPEG_STATUS_SUCCESS) {
-            if (two_streams && b.has_progressive()) {
+            if (b.has_progressive()) {
                 hipStream_t& ps = handle->page_entropy_stream[handle->current];
                 if (!ps && hipStreamCreateWithFlags(&ps, hipStreamNonBlocking) != hipSuccess) st = HIPJPEG_STATUS_HIP_ERROR;
                 es = ps;

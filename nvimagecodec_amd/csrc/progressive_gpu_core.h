@@ -106,15 +106,6 @@ HJ_HD int prog_popc64(uint64_t v)
 // a PLAIN coefficient symbol -- first scans: any size s > 0; refinement scans: s == 1 -- becomes (run r + 1) << 16 | bits the symbol
 // takes (code + value bits, resp. code + sign bit); everything else (no such code, end of band, run of sixteen, a size a refinement scan
 // may not carry) becomes a run no band can hold, so the ONE bound check of the inner loop also sorts those out.
-// development aid (tools/walk_laps.sh): where a walking wave's time goes -- lap timers around the parts of prog_walk_scan
-#if defined(HJ_WALK_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
-#define HJ_WALK_LAP(w, id) (w).lap(id)
-#define HJ_WALK_COUNT(n) ((n)++)
-#else
-#define HJ_WALK_LAP(w, id) ((void)0)
-#define HJ_WALK_COUNT(n) ((void)0)
-#endif
-
 // The one non-plain symbol that is common -- "end of band, no run": how most blocks end -- keeps a tag of its own and its length, so that the
 // walk recognises it by the fast view alone.
 constexpr uint32_t kProgNotPlain = 64u << 16;
@@ -235,14 +226,12 @@ HJ_HD bool prog_walk_scan(W& w, int ss, int se, uint32_t nblocks, uint32_t total
                     f = w.fast_at(d);
                     uint32_t kk = c + (f >> 16) + (d & ~63u);
                     while (HJ_LIKELY(kk <= last)) {  // (two symbols per turn: every second one saves the taken branch back to the top)
-                        HJ_WALK_COUNT(w.lap_syms);
                         if (TRACK) h = prog_bit_set(h, kk);
                         d += f & 0xFFFFu;
                         c = kk;
                         f = w.fast_at(d);
                         kk = c + (f >> 16) + (d & ~63u);
                         if (HJ_UNLIKELY(kk > last)) break;
-                        HJ_WALK_COUNT(w.lap_syms);
                         if (TRACK) h = prog_bit_set(h, kk);
                         d += f & 0xFFFFu;
                         c = kk;
@@ -257,7 +246,6 @@ HJ_HD bool prog_walk_scan(W& w, int ss, int se, uint32_t nblocks, uint32_t total
                     f = w.fast_at(d);
                     uint32_t t = zr + (f >> 16) + (d & ~63u);
                     while (HJ_LIKELY(t <= nz)) {  // (two symbols per turn: every second one saves the taken branch back to the top)
-                        HJ_WALK_COUNT(w.lap_syms);
                         gprev = w.zero_at(t);
                         q += f & 0xFFFFu;
                         d = q + gprev;
@@ -266,7 +254,6 @@ HJ_HD bool prog_walk_scan(W& w, int ss, int se, uint32_t nblocks, uint32_t total
                         f = w.fast_at(d);
                         t = zr + (f >> 16) + (d & ~63u);
                         if (HJ_UNLIKELY(t > nz)) break;
-                        HJ_WALK_COUNT(w.lap_syms);
                         gprev = w.zero_at(t);
                         q += f & 0xFFFFu;
                         d = q + gprev;
@@ -277,7 +264,6 @@ HJ_HD bool prog_walk_scan(W& w, int ss, int se, uint32_t nblocks, uint32_t total
                     }
                     placed = gprev + zr;
                 }
-                HJ_WALK_LAP(w, 0);
                 if (placed >= last) {
                     // the band is complete
                 } else if (d >= 64u) {
@@ -286,7 +272,6 @@ HJ_HD bool prog_walk_scan(W& w, int ss, int se, uint32_t nblocks, uint32_t total
                     d = base + d - nb;
                     base = nb;
                     next = false;
-                    HJ_WALK_LAP(w, 2);
                 } else if (HJ_LIKELY((f >> 16) == kProgEndOfBandTag)) {
                     // end of band, no run -- how most blocks end.  Refinement scans: + a correction bit for every non-zero-history
                     // coefficient in the rest of the band (the band has se - ss + 1 - nz of them, gprev + 1 - ss lie in front of the position)
@@ -326,7 +311,6 @@ HJ_HD bool prog_walk_scan(W& w, int ss, int se, uint32_t nblocks, uint32_t total
                     }
                 }
                 if (TRACK && next) w.set_hist((int)j, h);
-                HJ_WALK_LAP(w, 1);
             }
             if (next) {
                 j++;
@@ -334,7 +318,6 @@ HJ_HD bool prog_walk_scan(W& w, int ss, int se, uint32_t nblocks, uint32_t total
                     run = 0;
                 else
                     block_start();
-                HJ_WALK_LAP(w, 3);
             }
         } while (run == 1);
         w.group_end(g);

@@ -302,7 +302,8 @@ class BatchDecoder:
             raise N.HipJpegError(st, "hipjpegDecodeBatchTransfer")
 
     def device_stage(self, stream=None, which=None):
-        """which=None: all kernels; 0 idct_plane, 1 luma_color, 2 generic_color."""
+        """which=None: all kernels; 0 idct_plane, 1 luma_color, 2 generic_color, 3 GPU entropy stage and the read-back of its
+        verdicts, 4 geometry pass, 6 GPU entropy stage enqueued only.  Any other value raises HipJpegError."""
         if which is None:
             st = N.load().hipjpegDecodeBatchDevice(self._h, self._stream_ptr(stream))
         else:

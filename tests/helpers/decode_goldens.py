@@ -1,6 +1,6 @@
 """Test helper (run as a child process): decodes every golden bitstream in one batch through the GPU entropy stage and the host one and
 compares with the manifest's hashes, then the sampling-layout goldens with libjpeg-turbo's hashes -- so that a test can run it under the
-library's measurement switches, which are read once per process (HIPJPEG_DEVICE_DESTUFF_COUNT, HIPJPEG_NO_PK16, HIPJPEG_SINGLE_STREAM ...)."""
+library's measurement switches, which are read once per process (HIPJPEG_DEVICE_DESTUFF_COUNT, HIPJPEG_DENSE_STAGING, HIPJPEG_TAIL_AFTER ...)."""
 import hashlib
 import json
 import os

@@ -145,6 +145,12 @@ def test_bad_images_in_a_batch_do_not_poison_neighbours(dec):
     assert statuses[2] in (4, 5)      # TRUNCATED / CORRUPT
     assert np.array_equal(outs[0].cpu().numpy(), good[0][1])
     assert np.array_equal(outs[3].cpu().numpy(), good[1][1])
+    # a kernel family the device stage does not have is refused, not skipped
+    from nvimagecodec_amd._native import HipJpegError
+    for which in (-1, 5, 7):
+        with pytest.raises(HipJpegError) as err:
+            dec.device_stage(which=which)
+        assert err.value.status == 1, which  # INVALID_ARGUMENT
 
 
 def _encode_inputs(shapes_subs, quality=90):
