@@ -68,9 +68,10 @@ typedef enum {
 } hipjpegChromaSubsampling_t;
 
 #define HIPJPEG_FLAG_FANCY_UPSAMPLING 1u /* libjpeg do_fancy_upsampling (plugin option fancy_upsampling, default on) */
-#define HIPJPEG_FLAG_GPU_HUFFMAN 2u      /* entropy-decode eligible streams on the GPU (sequential Huffman with one interleaved scan, with or
-                                            without restart intervals; progressive SOF2 with up to 24 scans); the host then only finds the
-                                            scans.  Other streams keep the host entropy stage. */
+#define HIPJPEG_FLAG_GPU_HUFFMAN 2u      /* entropy-decode eligible streams on the GPU (sequential Huffman in up to 4 scans that code every
+                                            component once, in any component order, each scan a stream of its own, with or without restart
+                                            intervals; progressive SOF2 with up to 24 scans); the host then only finds the scans.  Other
+                                            streams keep the host entropy stage. */
 #define HIPJPEG_FLAG_FAST_IDCT 4u        /* the fast integer IDCT (plugin option hipjpeg_decoder:fast_idct=1; the reference's fast_idct, which
                                             selects JDCT_IFAST): the pixels are those of libjpeg-turbo's x86-64 SIMD routine
                                             jsimd_idct_ifast_sse2, which differs from jidctfst.c only on streams whose samples leave the
@@ -153,7 +154,8 @@ HIPJPEG_API hipjpegStatus_t hipjpegEntropyDecodeHostSparse(const uint8_t* data, 
 /* The GPU entropy decoder's algorithm (self-synchronizing subsequence decoding, csrc/huffman_gpu_core.h) executed on the
  * host, lane by lane, with the very code the kernels run: lets the algorithm be verified without a GPU.  Same output
  * layout as hipjpegEntropyDecodeHost; returns HIPJPEG_STATUS_UNSUPPORTED for streams the GPU entropy path does not take
- * (sequential streams in several scans, arithmetic coding, progressive scripts beyond the walker's limits), and
+ * (sequential streams in more than 4 scans or with a component that no scan or two scans code, arithmetic coding, progressive
+ * scripts beyond the walker's limits), and
  * HIPJPEG_STATUS_INTERNAL_ERROR when one of its self-checks fails (a block-start record of the synchronisation decodes that
  * disagrees with the position walk). */
 HIPJPEG_API hipjpegStatus_t hipjpegEntropyDecodeGpuAlgorithmHost(const uint8_t* data, size_t length, int16_t* coef,

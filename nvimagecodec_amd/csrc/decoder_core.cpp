@@ -310,6 +310,7 @@ hipjpegStatus_t DecodeBatch::plan_once(const PlanArgs& a, int n, hipjpegStatus_t
     entropy_pending_ = false;  // a caller that re-plans without resolve() gives up the statuses of the previous batch
     huff_images_.clear();
     huff_to_image_.clear();
+    seq_gpu_images_ = 0;
     prog_images_.clear();
     prog_to_image_.clear();
     xform_desc_.clear();
@@ -361,7 +362,9 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
     const bool big_enough = (uint64_t)f.width * (uint64_t)f.height > gpu_entropy_min_pixels_ || gpu_entropy_min_pixels_ == 0;
     if (im.status == HIPJPEG_STATUS_SUCCESS && want_gpu_entropy && big_enough && gpu_entropy_eligible(f)) {
         im.gpu_entropy = true;
-        im.pool_words = gpu_pool_words(f.scans[0]);
+        for (const ScanHeader& sc : f.scans) im.pool_words = std::max(im.pool_words, gpu_pool_words(sc));
+        im.fused_layout = f.scans.size() == 1;
+        for (int c = 0; c < f.scans[0].ncomp; c++) im.fused_layout = im.fused_layout && f.scans[0].comp_index[c] == c;
         // Zero-copy input: page-locked caller memory (hipHostMalloc / hipHostRegister, a pinned torch tensor) can
         // be read by the copy engine directly, so the scan's bytes skip the staging copy -- per rank one pass over host DRAM instead
         // of three (read, non-temporal store into the staging area, the engine's read).  HIPJPEG_NO_ZERO_COPY=1 switches it off.
@@ -508,8 +511,13 @@ void DecodeBatch::size_image(int i, Sizing& s)
         output_bytes_ += (uint64_t)f.width * f.height * (fmt == kOutY ? 1 : 3);
     if (!im.gpu_entropy) return;
     // the GPU entropy stage's share; offsets into the staging area are relative to their region here, layout() rebases them
-    im.tables_offset = s.pools.take(align_up(im.pool_words * 2, 64), 1);
-    if (!im.gpu_prog) im.dc_diff_offset = s.blocks.take(((f.total_blocks() + 31) & ~(size_t)31) * 2, 1);
+    if (im.gpu_prog) im.tables_offset = s.pools.take(align_up(im.pool_words * 2, 64), 1);
+    if (!im.gpu_prog)
+        for (size_t sidx = 0; sidx < f.scans.size(); sidx++) {
+            const ScanHeader& sc = f.scans[sidx];
+            const size_t blocks = (size_t)scan_mcus_x(f, sc) * scan_mcus_y(f, sc) * scan_blocks_per_mcu(f, sc);
+            im.seq[sidx].dc_diff_offset = s.blocks.take(((blocks + 31) & ~(size_t)31) * 2, 1);
+        }
     for (int c = 0; c < f.ncomp; c++) {  // compact DC planes, in the same scratch (behind the differences of a baseline image)
         const size_t nblk = (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h;
         im.dc_plane_offset[c] = s.blocks.take(((nblk + 31) & ~(size_t)31) * 2, 1);
@@ -536,17 +544,27 @@ void DecodeBatch::size_image(int i, Sizing& s)
         }
         return;
     }
+    // sequential: every scan is a stream of its own (one HuffImage each)
+    static_assert(sizeof(im.seq) / sizeof(im.seq[0]) == (size_t)kMaxSeqScans, "one SeqScan per scan gpu_entropy_eligible() admits");
     im.huff_index = (int)huff_to_image_.size();
-    huff_to_image_.push_back(i);
-    const ScanHeader& sc = f.scans[0];
-    const size_t nsub = (s.scan(sc, &im.raw_offset, &im.stream_offset, &im.first_chunk) * 8 + kSubseqBits - 1) / kSubseqBits;
-    s.subseq += nsub;
-    max_huff_units_ += (nsub + kHuffOwn - 1) / kHuffOwn;
-    max_pool_words_ = std::max(max_pool_words_, im.pool_words);
-    s.huff_wunits += ((size_t)f.mcus_x * f.mcus_y + kHuffMcusPerWg - 1) / kHuffMcusPerWg + 1;
-    im.num_boundaries = (uint32_t)sc.rst_after.size();  // restart boundaries + per-subsequence index
-    im.boundary_offset = s.boundaries.take(sc.restart_interval ? align_up(((size_t)im.num_boundaries + nsub + 1) * 4, 64) : 0, 1);
-    im.block_pos_offset = s.block_pos.take(((f.total_blocks() + 63) & ~(size_t)63) * 4, 1);
+    im.huff_count = (int)f.scans.size();
+    seq_gpu_images_++;
+    for (size_t sidx = 0; sidx < f.scans.size(); sidx++) {
+        const ScanHeader& sc = f.scans[sidx];
+        PlannedImage::SeqScan& q = im.seq[sidx];
+        huff_to_image_.push_back(i);
+        const size_t nsub = (s.scan(sc, &q.raw_offset, &q.stream_offset, &q.first_chunk) * 8 + kSubseqBits - 1) / kSubseqBits;
+        const size_t mcus = (size_t)scan_mcus_x(f, sc) * scan_mcus_y(f, sc);
+        s.subseq += nsub;
+        max_huff_units_ += (nsub + kHuffOwn - 1) / kHuffOwn;
+        q.pool_words = gpu_pool_words(sc);
+        q.tables_offset = s.pools.take(align_up(q.pool_words * 2, 64), 1);
+        max_pool_words_ = std::max(max_pool_words_, q.pool_words);
+        s.huff_wunits += (mcus + kHuffMcusPerWg - 1) / kHuffMcusPerWg + 1;
+        q.num_boundaries = (uint32_t)sc.rst_after.size();  // restart boundaries + per-subsequence index
+        q.boundary_offset = s.boundaries.take(sc.restart_interval ? align_up(((size_t)q.num_boundaries + nsub + 1) * 4, 64) : 0, 1);
+        q.block_pos_offset = s.block_pos.take(((mcus * scan_blocks_per_mcu(f, sc) + 63) & ~(size_t)63) * 4, 1);
+    }
 }
 
 // Offsets of every region of the staging area and of the entropy scratch, and the coefficient placement.
@@ -586,11 +604,16 @@ void DecodeBatch::layout(const Sizing& s)
             if (pass == 0 && sparse_mode_) c.end += 256;  // (host-decoded pictures are placed while they are decoded: room for alignment)
             for (int k = 0; k < im.frame.ncomp; k++) im.coef_offset[k] = c.take((size_t)im.frame.comp[k].blocks_w * im.frame.comp[k].blocks_h * 128, 1);
             if (!im.gpu_entropy) continue;
-            im.raw_offset += L.streams;
-            im.boundary_offset += L.boundaries;
-            im.tables_offset += L.tables;
-            if (im.gpu_prog)
+            if (im.gpu_prog) {
+                im.tables_offset += L.tables;
                 for (size_t sidx = 0; sidx < im.frame.scans.size(); sidx++) im.prog_raw_offset[sidx] += L.streams;
+            } else {
+                for (int sidx = 0; sidx < im.huff_count; sidx++) {
+                    im.seq[sidx].raw_offset += L.streams;
+                    im.seq[sidx].boundary_offset += L.boundaries;
+                    im.seq[sidx].tables_offset += L.tables;
+                }
+            }
         }
     }
     L.total = c.end;
@@ -693,42 +716,49 @@ void DecodeBatch::entropy_stage(int i)
         return;
     }
     if (im.gpu_entropy) {
-        // host part of the GPU entropy path: stage the scan's bytes as they are (the device removes the byte stuffing),
-        // expand the Huffman tables, describe the scan
-        const ScanHeader& sc = im.frame.scans[0];
-        im.stream_bytes = (uint32_t)(sc.data_end - sc.data_begin);
-        uint8_t* raw = pinned_.data() + im.raw_offset;
-        if (!im.input_pinned) {  // (else: transfer() sends the bytes from where they are)
-            copy_to_staging(raw, im.data + sc.data_begin, im.stream_bytes);
-            memset(raw + im.stream_bytes, 0x01, align_up((size_t)im.stream_bytes, 16) + 16 - im.stream_bytes);  // neither FF nor 00
-        }
-        stage_chunk_drops(sc, im.first_chunk);
-        HuffImage& h = huff_images_[im.huff_index];
-        fill_huff_image(im.frame, im.stream_bytes, &h);
-        build_gpu_pool(sc, &h, at<uint16_t>(pinned_, im.tables_offset));
-        if (sc.restart_interval) {
-            // restart boundaries in bits, and for every subsequence the first boundary at or behind its first bit
-            uint32_t* bnd = at<uint32_t>(pinned_, im.boundary_offset);
-            uint32_t* sub = bnd + im.num_boundaries;
-            for (uint32_t b = 0; b < im.num_boundaries; b++) bnd[b] = sc.rst_after[b] * 8u;
-            uint32_t idx = 0;
-            for (uint32_t j = 0; j <= h.num_subseq; j++) {
-                while (idx < im.num_boundaries && bnd[idx] < j * (uint32_t)kSubseqBits) idx++;
-                sub[j] = idx;
+        // host part of the GPU entropy path, scan by scan: stage the scan's bytes as they are (the device removes the byte stuffing),
+        // expand its Huffman tables, describe it
+        const FrameInfo& f = im.frame;
+        im.stream_bytes = 0;
+        for (int sidx = 0; sidx < im.huff_count; sidx++) {
+            const ScanHeader& sc = f.scans[sidx];
+            PlannedImage::SeqScan& q = im.seq[sidx];
+            q.stream_bytes = (uint32_t)(sc.data_end - sc.data_begin);
+            im.stream_bytes += q.stream_bytes;
+            uint8_t* raw = pinned_.data() + q.raw_offset;
+            if (!im.input_pinned) {  // (else: transfer() sends the bytes from where they are)
+                copy_to_staging(raw, im.data + sc.data_begin, q.stream_bytes);
+                memset(raw + q.stream_bytes, 0x01, align_up((size_t)q.stream_bytes, 16) + 16 - q.stream_bytes);  // neither FF nor 00
             }
-            h.restart_interval = (uint32_t)sc.restart_interval;
-            h.num_boundaries = im.num_boundaries;
-        }
-        // magnitude bound for the 24-bit multiplier decision without seeing the coefficients: DC values live in int16,
-        // AC magnitudes are below 2^(largest size category any AC table of the scan can code)
-        for (int c = 0; c < im.frame.ncomp; c++) {
-            int maxcat = 0;
-            const HuffSpec& t = sc.ac[sc.ta[c]];
-            int nv = 0;
-            for (int l = 1; l <= 16; l++) nv += t.bits[l];
-            for (int v = 0; v < nv; v++) maxcat = std::max(maxcat, t.vals[v] & 15);
-            im.coef_or[c] = 32767u | ((1u << maxcat) - 1);
-            im.ac_bound[c] = (1u << maxcat) - 1;
+            stage_chunk_drops(sc, q.first_chunk);
+            HuffImage& h = huff_images_[(size_t)im.huff_index + sidx];
+            fill_huff_image(f, sc, q.stream_bytes, &h);
+            build_gpu_pool(sc, &h, at<uint16_t>(pinned_, q.tables_offset));
+            if (sc.restart_interval) {
+                // restart boundaries in bits, and for every subsequence the first boundary at or behind its first bit
+                uint32_t* bnd = at<uint32_t>(pinned_, q.boundary_offset);
+                uint32_t* sub = bnd + q.num_boundaries;
+                for (uint32_t b = 0; b < q.num_boundaries; b++) bnd[b] = sc.rst_after[b] * 8u;
+                uint32_t idx = 0;
+                for (uint32_t j = 0; j <= h.num_subseq; j++) {
+                    while (idx < q.num_boundaries && bnd[idx] < j * (uint32_t)kSubseqBits) idx++;
+                    sub[j] = idx;
+                }
+                h.restart_interval = (uint32_t)sc.restart_interval;
+                h.num_boundaries = q.num_boundaries;
+            }
+            // magnitude bound for the 24-bit multiplier decision without seeing the coefficients: DC values live in int16,
+            // AC magnitudes are below 2^(largest size category any AC table of the scan can code)
+            for (int i = 0; i < sc.ncomp; i++) {
+                int maxcat = 0;
+                const HuffSpec& t = sc.ac[sc.ta[i]];
+                int nv = 0;
+                for (int l = 1; l <= 16; l++) nv += t.bits[l];
+                for (int v = 0; v < nv; v++) maxcat = std::max(maxcat, t.vals[v] & 15);
+                const int c = sc.comp_index[i];
+                im.coef_or[c] = 32767u | ((1u << maxcat) - 1);
+                im.ac_bound[c] = (1u << maxcat) - 1;
+            }
         }
         return;
     }
@@ -790,6 +820,9 @@ void DecodeBatch::finalize(hipjpegStatus_t* statuses)
     // unchecked
     for (const PlannedImage& im : images_)
         if (im.status == HIPJPEG_STATUS_SUCCESS && im.gpu_entropy && !im.gpu_prog && im.has_transform) fused_ = false;
+    // likewise a picture the FUSED builds cannot decode from one HuffImage: several scans, or one scan in another component order
+    for (const PlannedImage& im : images_)
+        if (im.status == HIPJPEG_STATUS_SUCCESS && im.gpu_entropy && !im.gpu_prog && !im.fused_layout) fused_ = false;
     if (statuses)
         for (size_t i = 0; i < images_.size(); i++) statuses[i] = images_[i].status;
     host_taken_.clear();
@@ -882,6 +915,7 @@ void DecodeBatch::build_entropy_units()
     huff_list_.clear();
     uint32_t first_subseq = 0;
     stream_bytes_total_ = 0;
+    huff_zero_.clear();
     for (size_t g = 0; g < huff_to_image_.size(); g++) {
         const PlannedImage& im = images_[huff_to_image_[g]];
         HuffImage& h = huff_images_[g];
@@ -889,30 +923,46 @@ void DecodeBatch::build_entropy_units()
             h.num_subseq = 0;
             continue;
         }
-        h.stream = work_.data() + scratch_.streams + im.stream_offset;
-        h.raw = device_.data() + im.raw_offset;
-        h.raw_src = im.input_pinned ? im.input_device_view + im.frame.scans[0].data_begin : nullptr;
+        const int sidx = (int)g - im.huff_index;
+        const ScanHeader& sc = im.frame.scans[sidx];
+        const PlannedImage::SeqScan& q = im.seq[sidx];
+        h.stream = work_.data() + scratch_.streams + q.stream_offset;
+        h.raw = device_.data() + q.raw_offset;
+        h.raw_src = im.input_pinned ? im.input_device_view + sc.data_begin : nullptr;
         if (h.restart_interval) {
-            h.boundaries = at<const uint32_t>(device_, im.boundary_offset);
+            h.boundaries = at<const uint32_t>(device_, q.boundary_offset);
             h.sub_boundary = h.boundaries + h.num_boundaries;
         }
-        h.raw_bytes = im.stream_bytes;
-        h.first_chunk = im.first_chunk;
-        for (uint32_t c = 0; c * (uint32_t)kDestuffChunk < im.stream_bytes; c++) huff_chunk_units_.push_back(HuffUnit{(uint32_t)g, c});
-        h.pool = at<const uint16_t>(device_, im.tables_offset);
-        h.dc_diff = at<int16_t>(work_, scratch_.dc_diff + im.dc_diff_offset);
-        for (int c = 0; c < im.frame.ncomp; c++) h.dc_plane[c] = at<int16_t>(work_, scratch_.dc_diff + im.dc_plane_offset[c]);
-        h.block_pos = at<uint32_t>(work_, scratch_.block_pos + im.block_pos_offset);
+        h.raw_bytes = q.stream_bytes;
+        h.first_chunk = q.first_chunk;
+        for (uint32_t c = 0; c * (uint32_t)kDestuffChunk < q.stream_bytes; c++) huff_chunk_units_.push_back(HuffUnit{(uint32_t)g, c});
+        h.pool = at<const uint16_t>(device_, q.tables_offset);
+        h.dc_diff = at<int16_t>(work_, scratch_.dc_diff + q.dc_diff_offset);
+        h.block_pos = at<uint32_t>(work_, scratch_.block_pos + q.block_pos_offset);
         for (uint32_t m = 0; m < h.mcus_x * h.mcus_y; m += kHuffMcusPerWg) huff_wunits_.push_back(HuffUnit{(uint32_t)g, m});
-        for (int c = 0; c < im.frame.ncomp; c++) h.coef[c] = at<int16_t>(device_, im.coef_offset[c]);
+        for (int i = 0; i < sc.ncomp; i++) {  // slot i: frame component sc.comp_index[i]
+            const int c = sc.comp_index[i];
+            const Component& fc = im.frame.comp[c];
+            h.coef[i] = at<int16_t>(device_, im.coef_offset[c]);
+            h.dc_plane[i] = at<int16_t>(work_, scratch_.dc_diff + im.dc_plane_offset[c]);
+            // a one-component scan codes the real blocks only: the padding of the grid is zeroed (the bottom rows alone when the
+            // real blocks fill whole rows, else the whole component)
+            const size_t bw = (size_t)fc.blocks_w, bh = (size_t)fc.blocks_h;
+            if (sc.ncomp == 1 && (h.mcus_x < bw || h.mcus_y < bh)) {
+                const size_t first = h.mcus_x < bw ? 0 : (size_t)h.mcus_y * bw, n = bw * bh - first;
+                huff_zero_.push_back(ZeroFill{reinterpret_cast<uint8_t*>(h.coef[i] + first * 64), n * 128, 1, 0});
+                huff_zero_.push_back(ZeroFill{reinterpret_cast<uint8_t*>(h.dc_plane[i] + first), n * 2, 1, 0});
+            }
+        }
         h.first_subseq = first_subseq;
         first_subseq += h.num_subseq;
         for (uint32_t j = 0; j < h.num_subseq; j += kHuffOwn) huff_units_.push_back(HuffUnit{(uint32_t)g, j});
-        if (h.restart_interval)  // the predictor starts over inside the image: the per-component scan (everything else: per MCU group)
-            for (int c = 0; c < im.frame.ncomp; c++) huff_dc_units_.push_back(HuffUnit{(uint32_t)g, (uint32_t)c});
+        if (h.restart_interval)  // the predictor starts over inside the scan: the per-component scan (everything else: per MCU group)
+            for (uint32_t i = 0; i < h.ncomp; i++) huff_dc_units_.push_back(HuffUnit{(uint32_t)g, i});
         huff_list_.push_back((uint32_t)g);
-        stream_bytes_total_ += im.stream_bytes;
+        stream_bytes_total_ += q.stream_bytes;
     }
+    merge_zero_fills();
     total_subseq_ = first_subseq;
     for (size_t q = 0; q < prog_images_.size(); q++) {
         const PlannedImage& im = images_[prog_to_image_[q]];
@@ -945,6 +995,30 @@ void DecodeBatch::build_entropy_units()
         }
         stream_bytes_total_ += im.stream_bytes;
     }
+}
+
+// The padding fills of a batch of pictures alike are evenly spaced, in two interleaved series (coefficients, DC planes): each series
+// becomes one 2D fill, so that the whole batch costs a handful of launches instead of two per picture.
+void DecodeBatch::merge_zero_fills()
+{
+    std::vector<ZeroFill> in, out;
+    in.swap(huff_zero_);
+    for (int series = 0; series < 2; series++) {
+        for (size_t a = (size_t)series; a < in.size();) {
+            ZeroFill z = in[a];
+            size_t b = a + 2;
+            if (b < in.size() && in[b].bytes == z.bytes && in[b].ptr > z.ptr && (size_t)(in[b].ptr - z.ptr) >= z.bytes) {
+                z.pitch = (size_t)(in[b].ptr - z.ptr);
+                while (b < in.size() && in[b].bytes == z.bytes && in[b].ptr == z.ptr + z.count * z.pitch) {
+                    z.count++;
+                    b += 2;
+                }
+            }
+            out.push_back(z);
+            a += 2 * z.count;
+        }
+    }
+    huff_zero_.swap(out);
 }
 
 // The luma tiles of a tile row share chroma lines at their seams (fancy upsampling reads a sample to the left and to the right of a
@@ -1058,8 +1132,10 @@ hipjpegStatus_t DecodeBatch::transfer(void* stream, bool kernels_on_other_stream
                 }
                 continue;
             }
-            if (!im.input_pinned)  // (the pinned ones: one kernel for all of them, below)
-                e = hipMemcpyAsync(device_.data() + im.raw_offset, pinned_.data() + im.raw_offset, align_up((size_t)im.stream_bytes, 16) + 16, hipMemcpyHostToDevice, s);
+            for (int sidx = 0; sidx < im.huff_count && e == hipSuccess && !im.input_pinned; sidx++) {  // (the pinned ones: one kernel for all of them, below)
+                const PlannedImage::SeqScan& q = im.seq[sidx];
+                e = hipMemcpyAsync(device_.data() + q.raw_offset, pinned_.data() + q.raw_offset, align_up((size_t)q.stream_bytes, 16) + 16, hipMemcpyHostToDevice, s);
+            }
         }
         if (e == hipSuccess && launch_gather_raw(at<const HuffImage>(device_, staging_.huff_desc), at<const HuffUnit>(device_, staging_.huff_chunk_units),
                                                  (int)huff_chunk_units_.size(), stream) != 0) e = hipErrorLaunchFailure;
@@ -1087,6 +1163,9 @@ hipjpegStatus_t DecodeBatch::enqueue_gpu_entropy(void* stream)
     if (huff_units_.empty() && prog_units_.empty()) return HIPJPEG_STATUS_SUCCESS;
     EntropyLaunch L = entropy_launch_args();
     if (huff_chunk_units_.empty() && hipMemsetAsync(L.changed, 0, 256, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;  // (else: the compact kernel clears them)
+    for (const ZeroFill& z : huff_zero_)
+        if ((z.count == 1 ? hipMemsetAsync(z.ptr, 0, z.bytes, s) : hipMemset2DAsync(z.ptr, z.pitch, 0, z.bytes, z.count, s)) != hipSuccess)
+            return HIPJPEG_STATUS_HIP_ERROR;
     // the per-chunk counts of bytes to drop came up with the bitstreams (the parser's marker walk sees every FF anyway);
     // HIPJPEG_DEVICE_DESTUFF_COUNT=1 counts them on the device as round 1 did (A/B and cross-check aid)
     static const bool force_device_count = getenv("HIPJPEG_DEVICE_DESTUFF_COUNT") != nullptr;
@@ -1247,9 +1326,13 @@ hipjpegStatus_t DecodeBatch::resolve(void* stream)
     }
     // The kernels could not vouch for a stream (corrupt / truncated data, a periodic stream): the host entropy decoder produces
     // either the coefficients or the precise error.
+    // A picture in several scans is taken over when any of them is flagged, once.
     std::vector<int> takeover;
-    for (size_t g = 0; g < huff_to_image_.size(); g++)
-        if (images_[huff_to_image_[g]].status == HIPJPEG_STATUS_SUCCESS && (L.himg[g].status != 0 || unsettled[g])) takeover.push_back(huff_to_image_[g]);
+    for (size_t g = 0; g < huff_to_image_.size(); g++) {
+        const int i = huff_to_image_[g];
+        if (images_[i].status == HIPJPEG_STATUS_SUCCESS && (L.himg[g].status != 0 || unsettled[g]) && (takeover.empty() || takeover.back() != i))
+            takeover.push_back(i);
+    }
     host_fallback_images_ = (int)takeover.size();
     const ProgImage* hprog = at<const ProgImage>(pinned_, staging_.prog_desc);
     if (debug_stats && !prog_to_image_.empty()) print_progressive_timing(hprog);

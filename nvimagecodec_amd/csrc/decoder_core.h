@@ -80,23 +80,31 @@ struct PlannedImage {
     int variant = -1;                      // KernelVariant, or -1 = generic colour path, -2 = planes-to-output only, -3 = CMYK / YCCK
     uint32_t coef_or[4] = {0, 0, 0, 0};    // OR of |coefficient| per component (from the entropy stage)
     uint32_t ac_bound[4] = {32768, 32768, 32768, 32768};  // upper bound of |AC coefficient| per component (packed IDCT pass 1 decision); default: any int16, -32768 included
-    // GPU entropy decoding (flag HIPJPEG_FLAG_GPU_HUFFMAN and an eligible stream): the host only destuffs the scan
+    // GPU entropy decoding (flag HIPJPEG_FLAG_GPU_HUFFMAN and an eligible stream): the host only stages the scans
     bool gpu_entropy = false;
-    int huff_index = -1;          // index into the HuffImage array
-    size_t stream_offset = 0;     // staging offsets of the destuffed stream and the 8 expanded tables
-    size_t tables_offset = 0;
+    // sequential: every scan is a HuffImage of its own, huff_index .. huff_index + huff_count - 1 (scan order)
+    int huff_index = -1, huff_count = 0;
+    size_t tables_offset = 0;    // staging offset of the expanded tables (progressive: all scans' tables)
     bool has_transform = false;  // region of interest and/or EXIF orientation (geometry pass)
     hipjpegTransform_t transform = {0, 0, 0, 0, 1};
     int xform_index = -1;
-    size_t pool_words = 0;      // lookup-table entries of the scan (GPU entropy path)
-    size_t raw_offset = 0;      // staged copy of the scan's entropy-coded bytes
-    uint32_t first_chunk = 0;   // first destuff chunk (batch-wide numbering)
-    size_t boundary_offset = 0;   // restart boundaries + per-subsequence boundary index (staging area)
-    uint32_t num_boundaries = 0;
-    size_t block_pos_offset = 0;  // bytes into the block-position scratch
-    size_t dc_diff_offset = 0;    // bytes into the DC-difference scratch
-    size_t dc_plane_offset[4] = {0, 0, 0, 0};  // bytes into the same scratch: compact DC planes per component
-    uint32_t stream_bytes = 0;
+    size_t pool_words = 0;      // lookup-table entries of the picture (GPU entropy path; sequential: the largest scan's)
+    struct SeqScan {             // one scan of a sequential picture on the GPU entropy stage
+        size_t raw_offset = 0;       // staged copy of the scan's entropy-coded bytes
+        size_t stream_offset = 0;    // destuffed stream (device-only scratch)
+        size_t tables_offset = 0;    // the scan's expanded tables (staging area)
+        size_t pool_words = 0;
+        uint32_t first_chunk = 0;    // first destuff chunk (batch-wide numbering)
+        size_t boundary_offset = 0;  // restart boundaries + per-subsequence boundary index (staging area)
+        uint32_t num_boundaries = 0;
+        size_t block_pos_offset = 0;  // bytes into the block-position scratch
+        size_t dc_diff_offset = 0;    // bytes into the DC-difference scratch
+        uint32_t stream_bytes = 0;
+    } seq[4];
+    size_t dc_plane_offset[4] = {0, 0, 0, 0};  // bytes into the DC-difference scratch: compact DC planes per component
+    uint32_t stream_bytes = 0;   // entropy-coded bytes of all scans
+    // the FUSED kernel builds decode a picture from one HuffImage whose slots are the frame's components (one scan, frame order)
+    bool fused_layout = true;
     // progressive scans on the GPU entropy stage (progressive_gpu_core.h): gpu_entropy is set as well (device-only coefficient
     // arena, compact DC planes); every scan has a HuffImage of its own for the destuff kernels
     bool gpu_prog = false;
@@ -153,7 +161,7 @@ public:
     // Blocks until the kernels of the last launch() have finished (the event recorded behind them).
     hipjpegStatus_t wait_done();
     void* last_stream() const { return last_stream_; }
-    int gpu_entropy_images() const { return (int)(huff_to_image_.size() + prog_to_image_.size()); }
+    int gpu_entropy_images() const { return seq_gpu_images_ + (int)prog_to_image_.size(); }
     int last_sync_launches() const { return last_sync_launches_; }
     int host_fallback_images() const { return host_fallback_images_; }  // GPU-entropy images the host decoder took over in resolve()
     bool has_progressive() const { return !prog_to_image_.empty(); }
@@ -214,6 +222,7 @@ private:
     void build_pixel_units();
     void build_entropy_units();
     void stage_tables();
+    void merge_zero_fills();
     void unit_counts(bool plain, int32_t* plane, int32_t luma[kNumLumaLayouts]) const;
     UnitList plane_units_, luma_units_[kNumLumaLayouts][kNumLumaVariants], generic_units_, cmyk_units_, xform_units_;  // luma: [layout of K2][sampling]
     // Images of the GPU entropy stage (baseline): their K1 / K2 units go to the FUSED kernel builds, which Huffman-decode the blocks
@@ -223,11 +232,19 @@ private:
     bool fused_ = false;
     bool finalized_ = false;
     std::vector<TransformImage> xform_desc_;
-    // GPU entropy stage: baseline images first, then one HuffImage per scan of the progressive images
+    // GPU entropy stage: one HuffImage per scan of the sequential images first, then one per scan of the progressive images
     std::vector<HuffImage> huff_images_;
     std::vector<HuffUnit> huff_units_, huff_dc_units_;
     std::vector<uint32_t> huff_list_;
-    std::vector<int> huff_to_image_;
+    std::vector<int> huff_to_image_;  // sequential HuffImage -> image
+    int seq_gpu_images_ = 0;          // sequential images among them
+    // blocks of GPU-decoded sequential pictures that no scan codes (padding of a one-component scan's grid): zeroed before the
+    // entropy kernels run, as the host decoder leaves them -- {device address, bytes, count, pitch} (count > 1: a 2D fill)
+    struct ZeroFill {
+        uint8_t* ptr;
+        size_t bytes, count, pitch;
+    };
+    std::vector<ZeroFill> huff_zero_;
     std::vector<HuffUnit> huff_wunits_;       // block kernel: kHuffMcusPerWg MCUs per workgroup
     std::vector<HuffUnit> huff_chunk_units_;  // destuff kernels: one per kDestuffChunk bytes of a scan
     size_t total_subseq_ = 0, max_huff_units_ = 0, max_pool_words_ = 0;

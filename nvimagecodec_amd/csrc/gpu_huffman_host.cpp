@@ -1,31 +1,63 @@
 // gpu_huffman_host.cpp -- see gpu_huffman_host.h
 #include "gpu_huffman_host.h"
 
+#include <algorithm>
 #include <cstring>
 
 namespace hipjpeg {
 
-bool gpu_entropy_eligible(const FrameInfo& f)
+uint32_t scan_mcus_x(const FrameInfo& f, const ScanHeader& sc)
 {
-    if (f.progressive() || f.scans.size() != 1) return false;
-    const ScanHeader& sc = f.scans[0];
-    if (sc.ncomp != f.ncomp || !sc.plain_stuffing) return false;
+    return (uint32_t)(sc.ncomp == 1 ? (f.comp[sc.comp_index[0]].samp_w + 7) / 8 : f.mcus_x);
+}
+
+uint32_t scan_mcus_y(const FrameInfo& f, const ScanHeader& sc)
+{
+    return (uint32_t)(sc.ncomp == 1 ? (f.comp[sc.comp_index[0]].samp_h + 7) / 8 : f.mcus_y);
+}
+
+uint32_t scan_blocks_per_mcu(const FrameInfo& f, const ScanHeader& sc)
+{
+    if (sc.ncomp == 1) return 1;
+    uint32_t n = 0;
+    for (int i = 0; i < sc.ncomp; i++) n += (uint32_t)(f.comp[sc.comp_index[i]].h * f.comp[sc.comp_index[i]].v);
+    return n;
+}
+
+namespace {
+// One scan of a sequential frame: plain stuffing, every restart interval closed by its marker, tables present and expandable, at
+// most 10 blocks per MCU, bit positions that fit 32 bits.
+bool gpu_scan_eligible(const FrameInfo& f, const ScanHeader& sc)
+{
+    if (sc.ncomp < 1 || !sc.plain_stuffing) return false;
     {
         // restart intervals: every interval but the last must be closed by its marker (RST0..7 in order: plain_stuffing)
-        const size_t mcus = (size_t)(f.ncomp == 1 ? ((f.comp[0].samp_w + 7) / 8) * ((f.comp[0].samp_h + 7) / 8) : f.mcus_x * f.mcus_y);
+        const size_t mcus = (size_t)scan_mcus_x(f, sc) * scan_mcus_y(f, sc);
         const size_t expect = sc.restart_interval ? (mcus + sc.restart_interval - 1) / sc.restart_interval - 1 : 0;
         if (sc.rst_after.size() != expect) return false;
     }
-    int bpm = 0;
-    for (int i = 0; i < sc.ncomp; i++) {
-        if (sc.comp_index[i] != i) return false;  // keep the MCU layout simple: components in frame order
+    for (int i = 0; i < sc.ncomp; i++)
         if (!sc.dc[sc.td[i]].present || !sc.ac[sc.ta[i]].present) return false;
-        bpm += f.ncomp == 1 ? 1 : f.comp[i].h * f.comp[i].v;
-    }
-    if (bpm > 10) return false;
+    if (scan_blocks_per_mcu(f, sc) > 10) return false;
     if ((sc.data_end - sc.data_begin) >= (1ull << 28)) return false;  // bit positions are 32-bit
     const size_t words = gpu_pool_words(sc);
     return words != 0 && words <= (size_t)kMaxPoolWords;
+}
+}  // namespace
+
+bool gpu_entropy_eligible(const FrameInfo& f)
+{
+    if (f.progressive() || f.scans.empty() || f.scans.size() > (size_t)kMaxSeqScans) return false;
+    // every component in exactly one scan: the scans then write disjoint components and each starts its own DC prediction, so they
+    // are independent streams (a component no scan codes, or one coded twice, keeps the host decoder's verdict)
+    int coded[4] = {0, 0, 0, 0};
+    for (const ScanHeader& sc : f.scans) {
+        if (!gpu_scan_eligible(f, sc)) return false;
+        for (int i = 0; i < sc.ncomp; i++) coded[sc.comp_index[i]]++;
+    }
+    for (int c = 0; c < f.ncomp; c++)
+        if (coded[c] != 1) return false;
+    return true;
 }
 
 size_t destuff_scan(const uint8_t* data, const ScanHeader& sc, uint8_t* out)
@@ -193,28 +225,30 @@ void build_gpu_pool(const ScanHeader& sc, HuffImage* im, uint16_t* pool)
     }
 }
 
-void fill_huff_image(const FrameInfo& f, uint32_t stream_bytes, HuffImage* im)
+void fill_huff_image(const FrameInfo& f, const ScanHeader& sc, uint32_t stream_bytes, HuffImage* im)
 {
     memset(im, 0, sizeof *im);
     im->total_bits = stream_bytes * 8u;
     im->num_subseq = (im->total_bits + kSubseqBits - 1) / kSubseqBits;
     im->stream_words = (uint32_t)((((size_t)stream_bytes + 3) & ~(size_t)3) + kStreamSlackBytes) / 4;
-    im->mcus_x = (uint32_t)(f.ncomp == 1 ? (f.comp[0].samp_w + 7) / 8 : f.mcus_x);
-    im->mcus_y = (uint32_t)(f.ncomp == 1 ? (f.comp[0].samp_h + 7) / 8 : f.mcus_y);
-    im->ncomp = (uint32_t)f.ncomp;
+    // a one-component scan: one block per MCU over the component's real blocks (T.81 A.2.2), addressed through its padded grid
+    im->mcus_x = scan_mcus_x(f, sc);
+    im->mcus_y = scan_mcus_y(f, sc);
+    im->ncomp = (uint32_t)sc.ncomp;
     int k = 0;
-    for (int c = 0; c < f.ncomp; c++) {
-        const int h = f.ncomp == 1 ? 1 : f.comp[c].h, v = f.ncomp == 1 ? 1 : f.comp[c].v;
-        im->comp_h[c] = (uint8_t)h;
-        im->comp_v[c] = (uint8_t)v;
-        im->comp_k0[c] = (uint8_t)k;
-        im->blocks_w[c] = (uint32_t)f.comp[c].blocks_w;
+    for (int i = 0; i < sc.ncomp; i++) {  // slot i of the scan = frame component sc.comp_index[i]
+        const Component& fc = f.comp[sc.comp_index[i]];
+        const int h = sc.ncomp == 1 ? 1 : fc.h, v = sc.ncomp == 1 ? 1 : fc.v;
+        im->comp_h[i] = (uint8_t)h;
+        im->comp_v[i] = (uint8_t)v;
+        im->comp_k0[i] = (uint8_t)k;
+        im->blocks_w[i] = (uint32_t)fc.blocks_w;
         for (int dy = 0; dy < v; dy++)
             for (int dx = 0; dx < h; dx++, k++) {
                 HuffK& hk = im->k[k];
-                hk.comp = (uint8_t)c;
-                hk.blk0 = (uint32_t)(dy * f.comp[c].blocks_w + dx);
-                hk.stride_y = (uint32_t)(v * f.comp[c].blocks_w);
+                hk.comp = (uint8_t)i;
+                hk.blk0 = (uint32_t)(dy * fc.blocks_w + dx);
+                hk.stride_y = (uint32_t)(v * fc.blocks_w);
                 hk.stride_x = (uint8_t)h;
             }
     }
@@ -289,15 +323,15 @@ struct HostRecorder {
 };
 }  // namespace
 
-int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4], int* sync_passes)
+namespace {
+// One scan of the frame, as the kernels decode it from its own HuffImage.  Returns 0 or the status the kernels would report.
+int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, int16_t* const frame_coef[4], int* sync_passes)
 {
-    (void)size;
-    const ScanHeader& sc = f.scans[0];
     std::vector<uint8_t> stream(destuffed_capacity(sc));
     const size_t n = destuff_scan(data, sc, stream.data());
     std::vector<uint16_t> pool(gpu_pool_words(sc));
     HuffImage im;
-    fill_huff_image(f, (uint32_t)n, &im);
+    fill_huff_image(f, sc, (uint32_t)n, &im);
     build_gpu_pool(sc, &im, pool.data());
     std::vector<int16_t> dc_diff(im.total_blocks);
     std::vector<uint32_t> boundaries;
@@ -309,14 +343,15 @@ int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, in
     im.num_boundaries = (uint32_t)boundaries.size();
     im.restart_interval = (uint32_t)sc.restart_interval;
     const bool rst = sc.restart_interval != 0;
-    for (int c = 0; c < f.ncomp; c++) {
-        im.coef[c] = coef[c];
+    for (int i = 0; i < sc.ncomp; i++) {
+        const int c = sc.comp_index[i];
+        int16_t* const coef = frame_coef[c];
+        im.coef[i] = coef;
         // every coded block must be written by the write pass; a one-component scan codes the real blocks only (T.81 A.2.2), the
         // padding blocks of its MCU-padded grid stay zero as in the host decoder
-        const size_t bw = (size_t)f.comp[c].blocks_w, rows = f.ncomp == 1 ? im.mcus_y : (size_t)f.comp[c].blocks_h;
-        const size_t cols = f.ncomp == 1 ? im.mcus_x : bw;
-        memset(coef[c], 0, bw * f.comp[c].blocks_h * 128);
-        for (size_t y = 0; y < rows; y++) memset(coef[c] + y * bw * 64, 0x5A, cols * 128);
+        const size_t bw = (size_t)f.comp[c].blocks_w, rows = sc.ncomp == 1 ? im.mcus_y : (size_t)f.comp[c].blocks_h;
+        const size_t cols = sc.ncomp == 1 ? im.mcus_x : bw;
+        for (size_t y = 0; y < rows; y++) memset(coef + y * bw * 64, 0x5A, cols * 128);
     }
     int16_t block_buffer[64] = {0};
     const HostEnv env{&im, block_buffer};
@@ -447,6 +482,23 @@ int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, in
                 env.block_ptr((int)k, mx, my)[0] = (int16_t)pred[c];
             }
         }
+    return 0;
+}
+}  // namespace
+
+int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4], int* sync_passes)
+{
+    (void)size;
+    // the blocks no scan codes (padding of a one-component scan's grid) stay zero
+    for (int c = 0; c < f.ncomp; c++) memset(coef[c], 0, (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 128);
+    int passes = 0;
+    for (const ScanHeader& sc : f.scans) {  // the scans are independent: each on its own, as the batched launches take them
+        int p = 0;
+        const int rc = emulate_scan(data, f, sc, coef, &p);
+        passes = std::max(passes, p);
+        if (rc != 0) return rc;
+    }
+    if (sync_passes) *sync_passes = passes;
     return 0;
 }
 

@@ -10,9 +10,17 @@
 
 namespace hipjpeg {
 
-// Baseline/extended sequential frames with ONE scan that interleaves every component (or a single-component frame), no
-// restart markers, lookup tables that fit kMaxPoolWords.  Everything else takes the host entropy stage.
+// Baseline/extended sequential frames in at most kMaxSeqScans scans (any component order inside a scan) that code every component
+// exactly once; every scan with plain byte stuffing, every restart interval closed by its marker, at most 10 blocks per MCU and lookup
+// tables that fit kMaxPoolWords.  Every scan is a stream of its own on the GPU (one HuffImage each).  Everything else takes the host
+// entropy stage.
+constexpr int kMaxSeqScans = 4;
 bool gpu_entropy_eligible(const FrameInfo& f);
+
+// MCU grid of a scan: a one-component scan has one block per MCU over the component's real blocks, any other the frame's MCU grid.
+uint32_t scan_mcus_x(const FrameInfo& f, const ScanHeader& sc);
+uint32_t scan_mcus_y(const FrameInfo& f, const ScanHeader& sc);
+uint32_t scan_blocks_per_mcu(const FrameInfo& f, const ScanHeader& sc);
 
 // Upper bound of the destuffed size (+ slack) for staging allocation.
 inline size_t destuffed_capacity(const ScanHeader& sc) { return (((sc.data_end - sc.data_begin) + 3) & ~(size_t)3) + kStreamSlackBytes; }
@@ -30,11 +38,13 @@ size_t gpu_pool_words(const ScanHeader& sc);
 // Call after fill_huff_image().
 void build_gpu_pool(const ScanHeader& sc, HuffImage* im, uint16_t* pool);
 
-// Fills every field except the pointers (stream, pool, coef, dc_diff), first_subseq and the table offsets.
-void fill_huff_image(const FrameInfo& f, uint32_t stream_bytes, HuffImage* im);
+// Describes scan `sc` of frame `f`: every field except the pointers (stream, pool, coef, dc_diff, dc_plane), first_subseq and the
+// table offsets.  Slot i of the per-component arrays (coef, dc_plane, blocks_w, comp_h/v/k0, HuffK::comp) is the scan's i-th
+// component, frame component sc.comp_index[i].
+void fill_huff_image(const FrameInfo& f, const ScanHeader& sc, uint32_t stream_bytes, HuffImage* im);
 
 // Runs pass 0, the synchronisation passes, the block-count scan, the write pass and the DC integration on the host, one
-// "lane" after the other.  coef[c] = device-layout blocks (as entropy_decode.h).  Returns 0 on success, else the status the
+// "lane" after the other, scan by scan (blocks no scan codes are left zero).  coef[c] = device-layout blocks (as entropy_decode.h).  Returns 0 on success, else the status the
 // kernels would report; *sync_passes receives the number of passes until the fixpoint.  Self-checks: 4 = the cooperative walk
 // disagrees with the lane walk, 5 = a block-start record disagrees with the position walk.
 int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4], int* sync_passes);
