@@ -19,14 +19,6 @@
 namespace hipjpeg {
 
 namespace {
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// The arenas hold every table at a byte offset: this is the one typed view of such a table.
-template <class T>
-T* at(const Buffer& b, size_t offset) { return reinterpret_cast<T*>(b.data() + offset); }
-template <class T>
-void copy_table(const Buffer& b, size_t offset, const std::vector<T>& v) { if (!v.empty()) memcpy(b.data() + offset, v.data(), v.size() * sizeof(T)); }
-
 // Planes of the caller's buffer and bytes per pixel in each (full-resolution formats; kOutPlanarYUV writes one plane per component).
 int out_planes(OutFormat fmt) { return (fmt == kOutInterleavedRGB || fmt == kOutInterleavedBGR || fmt == kOutY) ? 1 : 3; }
 int out_bpp(OutFormat fmt) { return (fmt == kOutInterleavedRGB || fmt == kOutInterleavedBGR) ? 3 : 1; }
@@ -61,6 +53,7 @@ bool ensure_event(void** ev)  // a timing-free event, created on first use
 }
 }  // namespace
 
+// Same classification the framework's parser applies (reference src/parsers/jpeg.cpp:70-114).
 hipjpegStatus_t status_from_parse(ParseStatus s)
 {
     switch (s) {
@@ -69,47 +62,6 @@ hipjpegStatus_t status_from_parse(ParseStatus s)
     case kParseTruncated: return HIPJPEG_STATUS_TRUNCATED;
     default: return HIPJPEG_STATUS_BAD_JPEG;
     }
-}
-
-// Same classification the framework's parser applies (reference src/parsers/jpeg.cpp:70-114).
-// ---------------------------------------------------------------- Buffer
-hipjpegStatus_t Buffer::reserve(size_t bytes)
-{
-    if (bytes <= cap_) return HIPJPEG_STATUS_SUCCESS;
-    release();
-    size_t want = align_up(bytes + bytes / 8, 1 << 20);  // headroom so a slightly bigger next batch does not reallocate
-    void* p = nullptr;
-    if (kind_ == kDevice && hooks_ && hooks_->device_malloc) {
-        if (hooks_->device_malloc(hooks_->device_ctx, &p, want, nullptr) != 0 || !p) return HIPJPEG_STATUS_ALLOC_FAILED;
-        custom_ = true;
-    } else if (kind_ == kPinned && hooks_ && hooks_->pinned_malloc) {
-        if (hooks_->pinned_malloc(hooks_->pinned_ctx, &p, want, nullptr) != 0 || !p) return HIPJPEG_STATUS_ALLOC_FAILED;
-        custom_ = true;
-    } else {
-        hipError_t e = kind_ == kDevice ? hipMalloc(&p, want) : hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) return HIPJPEG_STATUS_ALLOC_FAILED;
-        custom_ = false;
-    }
-    ptr_ = static_cast<uint8_t*>(p);
-    cap_ = want;
-    return HIPJPEG_STATUS_SUCCESS;
-}
-
-void Buffer::release()
-{
-    if (!ptr_) return;
-    if (custom_) {
-        if (kind_ == kDevice)
-            hooks_->device_free(hooks_->device_ctx, ptr_, cap_, nullptr);
-        else
-            hooks_->pinned_free(hooks_->pinned_ctx, ptr_, cap_, nullptr);
-    } else if (kind_ == kDevice) {
-        (void)hipFree(ptr_);
-    } else {
-        (void)hipHostFree(ptr_);
-    }
-    ptr_ = nullptr;
-    cap_ = 0;
 }
 
 // ---------------------------------------------------------------- DecodeBatch

@@ -17,53 +17,12 @@
 #include "gpu_huffman.h"
 #include "progressive_gpu.h"
 #include "jpeg_syntax.h"
+#include "staging.h"
 #include "thread_pool.h"
 
 namespace hipjpeg {
 
-// Custom allocation hooks (the plugin forwards nvimgcodecDeviceAllocator_t / nvimgcodecPinnedAllocator_t here).
-struct MemoryHooks {
-    int (*device_malloc)(void* ctx, void** ptr, size_t size, void* stream) = nullptr;
-    int (*device_free)(void* ctx, void* ptr, size_t size, void* stream) = nullptr;
-    void* device_ctx = nullptr;
-    int (*pinned_malloc)(void* ctx, void** ptr, size_t size, void* stream) = nullptr;
-    int (*pinned_free)(void* ctx, void* ptr, size_t size, void* stream) = nullptr;
-    void* pinned_ctx = nullptr;
-};
-
-class Buffer {
-public:
-    enum Kind { kDevice, kPinned };
-    Buffer(Kind kind, const MemoryHooks* hooks) : kind_(kind), hooks_(hooks) {}
-    ~Buffer() { release(); }
-    Buffer(const Buffer&) = delete;
-    Buffer& operator=(const Buffer&) = delete;
-    // grow-only; contents are NOT preserved
-    hipjpegStatus_t reserve(size_t bytes);
-    void release();
-    uint8_t* data() const { return ptr_; }
-    size_t capacity() const { return cap_; }
-    bool custom() const { return custom_; }  // allocated through the caller's hooks
-
-private:
-    Kind kind_;
-    const MemoryHooks* hooks_;
-    uint8_t* ptr_ = nullptr;
-    size_t cap_ = 0;
-    bool custom_ = false;
-};
-
 enum KernelVariant { kVarGray = 0, kVar11 = 1, kVar21 = 2, kVar22 = 3, kVar12 = 4, kNumLumaVariants = 5 };
-
-// Bump allocator over one arena: every region starts at the next multiple of `align` behind the one taken before it.
-struct Carve {
-    size_t end = 0;
-    size_t take(size_t bytes, size_t align = 256)
-    {
-        end = (end + align - 1) / align * align + bytes;
-        return end - bytes;
-    }
-};
 
 // A work-unit table and the byte offset it was staged at (the kernels read it from the device mirror there).
 struct UnitList {

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -12,8 +13,24 @@
 namespace hipjpeg {
 
 namespace {
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr int kTileBX = 32, kTileBY = 8;
+constexpr size_t kHistBytes = 2 * 2 * 256 * sizeof(uint32_t);  // one image's symbol counts: [table][DC / AC][symbol]
+
+// forward_pair_kernel's chroma sampling and input layout per flavour (hs = 0: not a pair flavour)
+struct PairFlavour { int hs, vs; bool planar; };
+constexpr PairFlavour kPair[kNumFwdFlavours] = {{0, 0, false}, {2, 2, false}, {2, 1, false}, {1, 1, false},
+                                                {0, 0, false}, {2, 2, true},  {2, 1, true},  {1, 1, true}};
+// launch order on the stream
+constexpr EncodeFlavour kLaunchOrder[kNumFwdFlavours] = {kFwdOneLane,       kFwdPair420,       kFwdPair422,       kFwdPair444,
+                                                         kFwdPlanarPair420, kFwdPlanarPair422, kFwdPlanarPair444, kFwdPlanes};
+
+// The pair flavour of RGB / BGR input in (hs, vs) sampling, or the one-lane kernel when the pair kernel has no such flavour.
+EncodeFlavour pair_flavour(int hs, int vs, bool planar)
+{
+    for (int f = 0; f < kNumFwdFlavours; f++)
+        if (kPair[f].hs == hs && kPair[f].vs == vs && kPair[f].planar == planar) return (EncodeFlavour)f;
+    return kFwdOneLane;
+}
 }  // namespace
 
 hipjpegStatus_t subsampling_factors(int subsampling, int* ncomp, int* hs, int* vs)
@@ -32,6 +49,23 @@ hipjpegStatus_t subsampling_factors(int subsampling, int* ncomp, int* hs, int* v
     return HIPJPEG_STATUS_SUCCESS;
 }
 
+hipjpegStatus_t picture_setup(const hipjpegEncodeParams_t& p, int width, int height, EncodeGeometry* g, uint16_t qlum[64], uint16_t qchr[64])
+{
+    g->width = width;
+    g->height = height;
+    const hipjpegStatus_t st = subsampling_factors(p.subsampling, &g->ncomp, &g->hs, &g->vs);
+    if (st != HIPJPEG_STATUS_SUCCESS) return st;
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    compute_geometry(g);
+    quality_tables(p.quality, qlum, qchr);
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+EntropyEncodeOptions entropy_options(const hipjpegEncodeParams_t& p)
+{
+    return EntropyEncodeOptions{p.restart_interval, p.optimized_huffman != 0, p.progressive != 0};
+}
+
 EncodeBatch::EncodeBatch(int device_id, const MemoryHooks* hooks)
     : device_id_(device_id), pinned_desc_(Buffer::kPinned, hooks), device_(Buffer::kDevice, hooks), pinned_coef_(Buffer::kPinned, hooks),
       henc_dev_(Buffer::kDevice, hooks), henc_dev2_(Buffer::kDevice, hooks), henc_pinned_(Buffer::kPinned, hooks), henc_out_(Buffer::kPinned, hooks)
@@ -46,11 +80,9 @@ EncodeBatch::~EncodeBatch()
     }
 }
 
-const int16_t* EncodeBatch::host_coef(int i, int c) const
-{
-    return reinterpret_cast<const int16_t*>(pinned_coef_.data() + images_[i].coef_offset[c]);
-}
+const int16_t* EncodeBatch::host_coef(int i, int c) const { return at<const int16_t>(pinned_coef_, images_[i].coef_offset[c]); }
 
+// ---------------------------------------------------------------- device_stage
 hipjpegStatus_t EncodeBatch::device_stage(const hipjpegEncodeInput_t* inputs, const hipjpegEncodeParams_t* params, int n,
                                           hipjpegStatus_t* statuses, void* stream)
 {
@@ -60,124 +92,149 @@ hipjpegStatus_t EncodeBatch::device_stage(const hipjpegEncodeInput_t* inputs, co
     launched_ = fetched_ = false;
     images_.assign(n, PlannedEncode());
     desc_.assign(n, EncodeImage());
+    host_coder_.assign(n, 0);
     units_.clear();
     for (auto& v : unit_lists_) v.clear();
     coef_total_ = 0;
     pixel_bytes_ = coef_bytes_ = 0;
-    for (int i = 0; i < n; i++) {
-        PlannedEncode& im = images_[i];
-        im.params = params[i];
-        const hipjpegEncodeInput_t& in = inputs[i];
-        EncodeGeometry& g = im.geom;
-        g.width = in.width;
-        g.height = in.height;
-        im.status = subsampling_factors(params[i].subsampling, &g.ncomp, &g.hs, &g.vs);
-        const int fmt = params[i].input_format;
-        if (im.status == HIPJPEG_STATUS_SUCCESS) {
-            if (in.width < 1 || in.height < 1 || in.width > 65535 || in.height > 65535) im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
-            if (fmt != HIPJPEG_OUTPUT_RGBI && fmt != HIPJPEG_OUTPUT_BGRI && fmt != HIPJPEG_OUTPUT_RGB_PLANAR && fmt != HIPJPEG_OUTPUT_BGR_PLANAR &&
-                fmt != HIPJPEG_OUTPUT_Y && fmt != HIPJPEG_OUTPUT_YUV_PLANAR)
-                im.status = HIPJPEG_STATUS_UNSUPPORTED;
-            if (fmt == HIPJPEG_OUTPUT_Y && g.ncomp != 1) im.status = HIPJPEG_STATUS_UNSUPPORTED;  // gray pixels carry no chroma
-            if (fmt == HIPJPEG_OUTPUT_YUV_PLANAR && g.ncomp != 3) im.status = HIPJPEG_STATUS_UNSUPPORTED;
-            const int nplanes = (fmt == HIPJPEG_OUTPUT_RGB_PLANAR || fmt == HIPJPEG_OUTPUT_BGR_PLANAR || fmt == HIPJPEG_OUTPUT_YUV_PLANAR) ? 3 : 1;
-            for (int p = 0; p < nplanes; p++)
-                if (!in.plane[p]) im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
-            if (params[i].restart_interval < 0 || params[i].restart_interval > 65535) im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
-        }
-        if (im.status != HIPJPEG_STATUS_SUCCESS) continue;
-        compute_geometry(&g);
-        quality_tables(params[i].quality, im.qlum, im.qchr);
-        EncodeImage& d = desc_[i];
-        memset(&d, 0, sizeof d);
-        d.width = (uint32_t)g.width;
-        d.height = (uint32_t)g.height;
-        d.ncomp = (uint32_t)g.ncomp;
-        d.hs = (uint32_t)g.hs;
-        d.vs = (uint32_t)g.vs;
-        d.in_format = fmt == HIPJPEG_OUTPUT_Y ? (uint32_t)kInGray : (uint32_t)fmt;  // RGBI/BGRI/planar/YUV values coincide with InFormat
-        for (int p = 0; p < 3; p++) {
-            d.in[p] = static_cast<const uint8_t*>(in.plane[p]);
-            d.in_pitch[p] = in.pitch[p];
-        }
-        for (int c = 0; c < g.ncomp; c++) {
-            d.blocks_w[c] = (uint32_t)g.blocks_w[c];
-            d.blocks_h[c] = (uint32_t)g.blocks_h[c];
-            d.real_w[c] = (uint32_t)g.real_w[c];
-            d.real_h[c] = (uint32_t)g.real_h[c];
-            im.coef_offset[c] = coef_total_;
-            coef_total_ += (size_t)g.blocks_w[c] * g.blocks_h[c] * 128;
-        }
-        for (int t = 0; t < 2; t++) {
-            const uint16_t* q = t ? im.qchr : im.qlum;
-            for (int k = 0; k < 64; k++) {
-                const uint32_t div = 8u * q[kZigzagNatural[k]];
-                d.quant[t].magic[k] = (1u << 28) / div + 1;
-                d.quant[t].half[k] = div >> 1;
-                const int nat = kZigzagNatural[k], tr = (nat & 7) * 8 + (nat >> 3);
-                d.qnat[t].magic[tr] = d.quant[t].magic[k];
-                d.qnat[t].half16[tr] = (div >> 1) << 4;
-            }
-        }
-        // tiles cover the real luma blocks only
-        const int tiles_x = (g.real_w[0] + kTileBX - 1) / kTileBX, tiles_y = (g.real_h[0] + kTileBY - 1) / kTileBY;
-        // interleaved RGB/BGR (any base address and pitch) into 4:2:0 / 4:2:2 / 4:4:4 has a kernel of its own (encode_kernels.hip
-        // forward_pair_kernel).  HIPJPEG_ENCODE_ONE_LANE_KERNEL (read per batch) sends everything to the one-lane-per-block kernel:
-        // the cross-check campaigns compare the two on the same pixels.
-        int flavour = 0;
-        const bool interleaved = fmt == HIPJPEG_OUTPUT_RGBI || fmt == HIPJPEG_OUTPUT_BGRI;
-        const bool planar_rgb = fmt == HIPJPEG_OUTPUT_RGB_PLANAR || fmt == HIPJPEG_OUTPUT_BGR_PLANAR;
-        if (g.ncomp == 3 && (interleaved || planar_rgb) && getenv("HIPJPEG_ENCODE_ONE_LANE_KERNEL") == nullptr) {
-            flavour = (g.hs == 2 && g.vs == 2) ? 1 : (g.hs == 2 && g.vs == 1) ? 2 : (g.hs == 1 && g.vs == 1) ? 3 : 0;
-            if (flavour != 0 && planar_rgb) flavour += 4;
-        }
-        if (fmt == HIPJPEG_OUTPUT_YUV_PLANAR) {
-            // planes that are components already: one lane per real block of each component
-            for (int c = 0; c < 3; c++)
-                for (int b = 0; b < g.real_w[c] * g.real_h[c]; b += 256) unit_lists_[4].push_back(EncodeUnit{(uint32_t)i, (uint32_t)b, 0u, (uint32_t)c});
-        } else {
-            for (int ty = 0; ty < tiles_y; ty++)
-                for (int tx = 0; tx < tiles_x; tx++) unit_lists_[flavour].push_back(EncodeUnit{(uint32_t)i, (uint32_t)tx, (uint32_t)ty, 0u});
-        }
-        pixel_bytes_ += (uint64_t)g.width * g.height * (g.ncomp == 1 ? 1 : 3);
-        for (int c = 0; c < g.ncomp; c++) coef_bytes_ += (uint64_t)g.real_w[c] * g.real_h[c] * 128;
-    }
-    for (int f = 0; f < kUnitLists; f++) {  // one table, the flavours back to back
-        unit_first_[f] = units_.size();
-        units_.insert(units_.end(), unit_lists_[f].begin(), unit_lists_[f].end());
-    }
-    units_offset_ = align_up(sizeof(EncodeImage) * (size_t)n, 256);
-    desc_bytes_ = align_up(units_offset_ + sizeof(EncodeUnit) * units_.size(), 256);
-    coef_offset_ = desc_bytes_;
+    for (int i = 0; i < n; i++) prepare(i, inputs[i], params[i]);
+    layout();
     hipjpegStatus_t st;
-    if ((st = pinned_desc_.reserve(desc_bytes_ + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
-    if ((st = device_.reserve(desc_bytes_ + coef_total_ + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
-    if ((st = pinned_coef_.reserve(coef_total_ + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
-    for (int i = 0; i < n; i++) {
-        if (images_[i].status != HIPJPEG_STATUS_SUCCESS) continue;
-        for (int c = 0; c < images_[i].geom.ncomp; c++)
-            desc_[i].coef[c] = reinterpret_cast<int16_t*>(device_.data() + coef_offset_ + images_[i].coef_offset[c]);
-    }
-    if (n) memcpy(pinned_desc_.data(), desc_.data(), sizeof(EncodeImage) * (size_t)n);
-    if (!units_.empty()) memcpy(pinned_desc_.data() + units_offset_, units_.data(), sizeof(EncodeUnit) * units_.size());
+    if ((st = reserve()) != HIPJPEG_STATUS_SUCCESS) return st;
+    bind_pointers();
     if (statuses)
         for (int i = 0; i < n; i++) statuses[i] = images_[i].status;
     stream_ = stream;
-    if (desc_bytes_ && hipMemcpyAsync(device_.data(), pinned_desc_.data(), desc_bytes_, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
+    if (staging_.coef && hipMemcpyAsync(device_.data(), pinned_desc_.data(), staging_.coef, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;
     return relaunch(stream);
 }
 
+// Checks, geometry, quantiser tables, descriptor and work units of image i.
+void EncodeBatch::prepare(int i, const hipjpegEncodeInput_t& in, const hipjpegEncodeParams_t& p)
+{
+    PlannedEncode& im = images_[i];
+    im.params = p;
+    const EncodeGeometry& g = im.geom;
+    const int fmt = p.input_format;
+    // An unknown subsampling ends the checks.  After it every failing check overwrites the status: of several problems the
+    // last one checked is reported.
+    im.status = picture_setup(p, in.width, in.height, &im.geom, im.qlum, im.qchr);
+    if (im.status == HIPJPEG_STATUS_UNSUPPORTED) return;
+    if (fmt != HIPJPEG_OUTPUT_RGBI && fmt != HIPJPEG_OUTPUT_BGRI && fmt != HIPJPEG_OUTPUT_RGB_PLANAR && fmt != HIPJPEG_OUTPUT_BGR_PLANAR &&
+        fmt != HIPJPEG_OUTPUT_Y && fmt != HIPJPEG_OUTPUT_YUV_PLANAR)
+        im.status = HIPJPEG_STATUS_UNSUPPORTED;
+    if (fmt == HIPJPEG_OUTPUT_Y && g.ncomp != 1) im.status = HIPJPEG_STATUS_UNSUPPORTED;  // gray pixels carry no chroma
+    if (fmt == HIPJPEG_OUTPUT_YUV_PLANAR && g.ncomp != 3) im.status = HIPJPEG_STATUS_UNSUPPORTED;
+    const int nplanes = (fmt == HIPJPEG_OUTPUT_RGB_PLANAR || fmt == HIPJPEG_OUTPUT_BGR_PLANAR || fmt == HIPJPEG_OUTPUT_YUV_PLANAR) ? 3 : 1;
+    for (int c = 0; c < nplanes; c++)
+        if (!in.plane[c]) im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (p.restart_interval < 0 || p.restart_interval > 65535) im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (im.status != HIPJPEG_STATUS_SUCCESS) return;
+
+    EncodeImage& d = desc_[i];
+    memset(&d, 0, sizeof d);
+    d.width = (uint32_t)g.width;
+    d.height = (uint32_t)g.height;
+    d.ncomp = (uint32_t)g.ncomp;
+    d.hs = (uint32_t)g.hs;
+    d.vs = (uint32_t)g.vs;
+    d.in_format = fmt == HIPJPEG_OUTPUT_Y ? (uint32_t)kInGray : (uint32_t)fmt;  // RGBI/BGRI/planar/YUV values coincide with InFormat
+    for (int c = 0; c < 3; c++) {
+        d.in[c] = static_cast<const uint8_t*>(in.plane[c]);
+        d.in_pitch[c] = in.pitch[c];
+    }
+    for (int c = 0; c < g.ncomp; c++) {
+        d.blocks_w[c] = (uint32_t)g.blocks_w[c];
+        d.blocks_h[c] = (uint32_t)g.blocks_h[c];
+        d.real_w[c] = (uint32_t)g.real_w[c];
+        d.real_h[c] = (uint32_t)g.real_h[c];
+        im.coef_offset[c] = coef_total_;
+        coef_total_ += (size_t)g.blocks_w[c] * g.blocks_h[c] * 128;
+    }
+    for (int t = 0; t < 2; t++) {
+        const uint16_t* q = t ? im.qchr : im.qlum;
+        for (int k = 0; k < 64; k++) {
+            const uint32_t div = 8u * q[kZigzagNatural[k]];
+            d.quant[t].magic[k] = (1u << 28) / div + 1;
+            d.quant[t].half[k] = div >> 1;
+            const int nat = kZigzagNatural[k], tr = (nat & 7) * 8 + (nat >> 3);
+            d.qnat[t].magic[tr] = d.quant[t].magic[k];
+            d.qnat[t].half16[tr] = (div >> 1) << 4;
+        }
+    }
+    add_units(i, fmt);
+    pixel_bytes_ += (uint64_t)g.width * g.height * (g.ncomp == 1 ? 1 : 3);
+    for (int c = 0; c < g.ncomp; c++) coef_bytes_ += (uint64_t)g.real_w[c] * g.real_h[c] * 128;
+}
+
+// Work units of image i on the list of its flavour.
+void EncodeBatch::add_units(int i, int fmt)
+{
+    const EncodeGeometry& g = images_[i].geom;
+    if (fmt == HIPJPEG_OUTPUT_YUV_PLANAR) {
+        // planes that are components already: one lane per real block of each component
+        for (int c = 0; c < 3; c++)
+            for (int b = 0; b < g.real_w[c] * g.real_h[c]; b += 256) unit_lists_[kFwdPlanes].push_back(EncodeUnit{(uint32_t)i, (uint32_t)b, 0u, (uint32_t)c});
+        return;
+    }
+    // Interleaved or planar RGB / BGR into 4:2:0 / 4:2:2 / 4:4:4 has a kernel of its own (encode_kernels.hip forward_pair_kernel).
+    // HIPJPEG_ENCODE_ONE_LANE_KERNEL (read per batch) sends everything to the one-lane-per-block kernel: the cross-check
+    // campaigns compare the two on the same pixels.
+    EncodeFlavour flavour = kFwdOneLane;
+    const bool interleaved = fmt == HIPJPEG_OUTPUT_RGBI || fmt == HIPJPEG_OUTPUT_BGRI;
+    const bool planar_rgb = fmt == HIPJPEG_OUTPUT_RGB_PLANAR || fmt == HIPJPEG_OUTPUT_BGR_PLANAR;
+    if (g.ncomp == 3 && (interleaved || planar_rgb) && getenv("HIPJPEG_ENCODE_ONE_LANE_KERNEL") == nullptr) flavour = pair_flavour(g.hs, g.vs, planar_rgb);
+    // tiles cover the real luma blocks only
+    const int tiles_x = (g.real_w[0] + kTileBX - 1) / kTileBX, tiles_y = (g.real_h[0] + kTileBY - 1) / kTileBY;
+    for (int ty = 0; ty < tiles_y; ty++)
+        for (int tx = 0; tx < tiles_x; tx++) unit_lists_[flavour].push_back(EncodeUnit{(uint32_t)i, (uint32_t)tx, (uint32_t)ty, 0u});
+}
+
+// One units table, the flavours back to back, and the descriptor arena around it.
+void EncodeBatch::layout()
+{
+    for (int f = 0; f < kNumFwdFlavours; f++) {
+        unit_first_[f] = units_.size();
+        units_.insert(units_.end(), unit_lists_[f].begin(), unit_lists_[f].end());
+    }
+    Carve c;
+    staging_.desc = c.take(sizeof(EncodeImage) * desc_.size());
+    staging_.units = c.take(sizeof(EncodeUnit) * units_.size());
+    staging_.coef = c.take(coef_total_);
+    staging_.total = c.end;
+}
+
+hipjpegStatus_t EncodeBatch::reserve()
+{
+    hipjpegStatus_t st;
+    if ((st = pinned_desc_.reserve(staging_.coef + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
+    if ((st = device_.reserve(staging_.total + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
+    return pinned_coef_.reserve(coef_total_ + 256);
+}
+
+void EncodeBatch::bind_pointers()
+{
+    for (int i = 0; i < (int)images_.size(); i++) {
+        if (images_[i].status != HIPJPEG_STATUS_SUCCESS) continue;
+        for (int c = 0; c < images_[i].geom.ncomp; c++) desc_[i].coef[c] = at<int16_t>(device_, staging_.coef + images_[i].coef_offset[c]);
+    }
+    copy_table(pinned_desc_, staging_.desc, desc_);
+    copy_table(pinned_desc_, staging_.units, units_);
+}
+
 hipjpegStatus_t EncodeBatch::relaunch(void* stream)
 {
-    const EncodeImage* dimg = reinterpret_cast<const EncodeImage*>(device_.data());
-    const EncodeUnit* dunits = reinterpret_cast<const EncodeUnit*>(device_.data() + units_offset_);
-    static const int pair_hs[4] = {0, 2, 2, 1}, pair_vs[4] = {0, 2, 1, 1};
-    int rc = launch_forward(dimg, dunits + unit_first_[0], (int)unit_lists_[0].size(), stream);
-    for (int f = 1; f < 4 && rc == 0; f++) rc = launch_forward_pair(pair_hs[f], pair_vs[f], false, dimg, dunits + unit_first_[f], (int)unit_lists_[f].size(), stream);
-    for (int f = 1; f < 4 && rc == 0; f++)
-        rc = launch_forward_pair(pair_hs[f], pair_vs[f], true, dimg, dunits + unit_first_[4 + f], (int)unit_lists_[4 + f].size(), stream);
-    if (rc == 0) rc = launch_forward_planes(dimg, dunits + unit_first_[4], (int)unit_lists_[4].size(), stream);
+    const EncodeImage* dimg = at<const EncodeImage>(device_, staging_.desc);
+    int rc = 0;
+    for (int k = 0; k < kNumFwdFlavours && rc == 0; k++) {
+        const EncodeFlavour f = kLaunchOrder[k];
+        const EncodeUnit* u = at<const EncodeUnit>(device_, staging_.units) + unit_first_[f];
+        const int nu = (int)unit_lists_[f].size();
+        rc = f == kFwdOneLane ? launch_forward(dimg, u, nu, stream)
+           : f == kFwdPlanes  ? launch_forward_planes(dimg, u, nu, stream)
+                              : launch_forward_pair(kPair[f].hs, kPair[f].vs, kPair[f].planar, dimg, u, nu, stream);
+    }
     if (rc != 0) return HIPJPEG_STATUS_HIP_ERROR;
     if (!event_) {
         hipEvent_t ev;
@@ -197,7 +254,7 @@ hipjpegStatus_t EncodeBatch::fetch_coefficients()
     if (fetched_) return HIPJPEG_STATUS_SUCCESS;
     if (hipSetDevice(device_id_) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
     if (coef_total_ &&
-        hipMemcpyAsync(pinned_coef_.data(), device_.data() + coef_offset_, coef_total_, hipMemcpyDeviceToHost, (hipStream_t)stream_) != hipSuccess)
+        hipMemcpyAsync(pinned_coef_.data(), device_.data() + staging_.coef, coef_total_, hipMemcpyDeviceToHost, (hipStream_t)stream_) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;
     if (hipEventRecord((hipEvent_t)event_, (hipStream_t)stream_) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
     if (hipEventSynchronize((hipEvent_t)event_) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
@@ -205,41 +262,122 @@ hipjpegStatus_t EncodeBatch::fetch_coefficients()
     return HIPJPEG_STATUS_SUCCESS;
 }
 
-// GPU entropy coder.  Two short host round trips: after the length scan (the bit-buffer sizes) and after the layout (the
-// file sizes); everything else is queued on the stream the forward kernel ran on.
-hipjpegStatus_t EncodeBatch::gpu_entropy_stage(std::vector<char>* todo)
+// ---------------------------------------------------------------- entropy coding
+hipjpegStatus_t EncodeBatch::route_entropy(bool gpu_huffman)
 {
-    const int n = (int)images_.size();
-    todo->assign(n, 0);
+    for (size_t i = 0; i < images_.size(); i++) host_coder_[i] = images_[i].status == HIPJPEG_STATUS_SUCCESS;
+    hipjpegStatus_t st;
+    if (gpu_huffman && (st = gpu_entropy_stage()) != HIPJPEG_STATUS_SUCCESS) return st;
+    host_images_ = (int)std::count(host_coder_.begin(), host_coder_.end(), 1);
+    // the host coder needs the coefficients on its side of PCIe
+    return host_images_ ? fetch_coefficients() : HIPJPEG_STATUS_SUCCESS;
+}
+
+void EncodeBatch::entropy_stage(int i)
+{
+    PlannedEncode& im = images_[i];
+    if (!host_coder_[i] || im.status != HIPJPEG_STATUS_SUCCESS) return;
+    const int16_t* coef[3] = {nullptr, nullptr, nullptr};
+    for (int c = 0; c < im.geom.ncomp; c++) coef[c] = host_coef(i, c);
+    im.bitstream.clear();
+    im.gpu_bitstream = nullptr;
+    im.gpu_bitstream_len = 0;
+    encode_jfif(im.geom, im.qlum, im.qchr, coef, entropy_options(im.params), &im.bitstream);
+}
+
+// ---------------------------------------------------------------- GPU entropy coder
+namespace {
+// Phase-1 device arena (henc_dev_): descriptors | length units | standard tables | optimized tables [the upload, staged at the same
+// offsets at the start of henc_pinned_) | block bit lengths | block bit offsets | total bits | histograms
+struct HencLayout1 {
+    size_t desc, units, tables, opt_tables, bits, off, totals, hist, end;
+    size_t upload() const { return bits; }
+};
+// henc_pinned_ behind the phase-1 upload: total bits | histograms | phase-2 upload (at the phase-2 arena's offsets) | lengths | offsets
+struct HencPinnedLayout { size_t totals, hist, up2, len, foff, end; };
+// Phase-2 device arena (henc_dev2_): descriptors | chunk units | headers [the upload) | 0xFF counts per chunk | chunk outputs | file
+// lengths | file offsets | bit buffers | files (unused when they go straight to henc_out_)
+struct HencLayout2 {
+    size_t desc, units, headers, ff, out, len, foff, raw, arena, end;
+    size_t upload() const { return ff; }
+};
+
+// From `len` on the pinned tail depends on the phase-2 upload: phase 1 lays it out with upload2 = 0 and reads totals, hist, up2.
+HencPinnedLayout henc_pinned_layout(const HencLayout1& d1, int ng, int nopt, size_t upload2)
+{
+    Carve c{d1.upload()};
+    HencPinnedLayout p;
+    p.totals = c.take((size_t)ng * 4);
+    p.hist = c.take(kHistBytes * (size_t)nopt);
+    p.up2 = c.take(upload2);
+    p.len = c.take((size_t)ng * 4);
+    p.foff = c.take((size_t)ng * 8);
+    p.end = c.end;
+    return p;
+}
+}  // namespace
+
+struct EncodeBatch::HencPlan {
+    std::vector<int> idx;                      // images taken, in batch order
+    std::vector<HencImage> desc;               // their descriptors (device pointers inside)
+    std::vector<HencUnit> units, chunk_units;  // length / write units (256 blocks each); count / expand units (kHencChunk bytes each)
+    std::vector<int> opt_slot;                 // slot among the images with tables of their own (optimized_huffman), or -1
+    int nopt = 0;
+    size_t total_blocks = 0;                    // entries of the per-block arrays
+    std::vector<std::vector<uint8_t>> headers;  // SOI .. SOS of every file
+    std::vector<size_t> raw_off, hdr_off;       // offsets inside the bit-buffer area and the header area
+    size_t raw_total = 0, hdr_total = 0, arena_cap = 0;
+    HencLayout1 d1{};
+    HencPinnedLayout pin{};
+    HencLayout2 d2{};
+};
+
+hipjpegStatus_t EncodeBatch::gpu_entropy_stage()
+{
     gpu_entropy_images_ = 0;
     if (!launched_) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (hipSetDevice(device_id_) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
-    hipStream_t s = (hipStream_t)stream_;
-    std::vector<int> idx;  // images taken here
-    for (int i = 0; i < n; i++) {
+    HencPlan p;
+    henc_choose(p);
+    if (p.idx.empty()) return HIPJPEG_STATUS_SUCCESS;
+    henc_describe(p);
+    hipjpegStatus_t st;
+    if ((st = henc_stage_phase1(p)) != HIPJPEG_STATUS_SUCCESS || (p.nopt > 0 && (st = henc_histograms(p)) != HIPJPEG_STATUS_SUCCESS) ||
+        (st = henc_lengths(p)) != HIPJPEG_STATUS_SUCCESS)
+        return st;
+    henc_chunks(p);
+    bool direct = false;
+    if ((st = henc_assemble(p, &direct)) != HIPJPEG_STATUS_SUCCESS) return st;
+    return henc_collect(p, direct);
+}
+
+// Every image the host coder would code except those with restart markers or progressive scans.
+void EncodeBatch::henc_choose(HencPlan& p)
+{
+    for (int i = 0; i < (int)images_.size(); i++) {
         PlannedEncode& im = images_[i];
         im.gpu_bitstream = nullptr;
         im.gpu_bitstream_len = 0;
-        if (im.status != HIPJPEG_STATUS_SUCCESS) continue;
-        if (im.params.restart_interval == 0 && !im.params.progressive)
-            idx.push_back(i);
-        else
-            (*todo)[i] = 1;  // restart markers / progressive scans: the host coder
+        if (!host_coder_[i] || im.params.restart_interval != 0 || im.params.progressive) continue;
+        host_coder_[i] = 0;
+        p.idx.push_back(i);
     }
-    const int ng = (int)idx.size();
-    if (ng == 0) return HIPJPEG_STATUS_SUCCESS;
+}
 
-    // ---- phase 1: descriptors, work units, code tables up; block lengths and their prefix sums
-    std::vector<HencImage> desc(ng);
-    std::vector<HencUnit> units;
-    size_t total_blocks = 0;
+// Descriptors, length units, table slots and the standard headers of the images taken.
+void EncodeBatch::henc_describe(HencPlan& p)
+{
+    const int ng = (int)p.idx.size();
+    p.desc.resize(ng);
+    p.opt_slot.assign(ng, -1);
+    p.headers.resize(ng);
     for (int g = 0; g < ng; g++) {
-        const PlannedEncode& im = images_[idx[g]];
+        const PlannedEncode& im = images_[p.idx[g]];
         const EncodeGeometry& eg = im.geom;
-        HencImage& h = desc[g];
+        HencImage& h = p.desc[g];
         memset(&h, 0, sizeof h);
         for (int c = 0; c < eg.ncomp; c++) {
-            h.coef[c] = desc_[idx[g]].coef[c];
+            h.coef[c] = desc_[p.idx[g]].coef[c];
             h.blocks_w[c] = (uint32_t)eg.blocks_w[c];
             h.real_w[c] = (uint32_t)eg.real_w[c];
             h.real_h[c] = (uint32_t)eg.real_h[c];
@@ -251,176 +389,182 @@ hipjpegStatus_t EncodeBatch::gpu_entropy_stage(std::vector<char>* todo)
         h.vs = (uint32_t)eg.vs;
         h.bpm = eg.ncomp == 3 ? (uint32_t)(eg.hs * eg.vs + 2) : 1u;
         h.total_blocks = h.mcus_x * h.mcus_y * h.bpm;
-        h.first_block = (uint32_t)total_blocks;
-        for (uint32_t b = 0; b < h.total_blocks; b += 256) units.push_back(HencUnit{(uint32_t)g, b});
-        total_blocks += (h.total_blocks + 63) & ~(size_t)63;
+        h.first_block = (uint32_t)p.total_blocks;
+        for (uint32_t b = 0; b < h.total_blocks; b += 256) p.units.push_back(HencUnit{(uint32_t)g, b});
+        p.total_blocks += (h.total_blocks + 63) & ~(size_t)63;
+        if (im.params.optimized_huffman) p.opt_slot[g] = p.nopt++;
+        write_standard_headers(eg, im.qlum, im.qchr, &p.headers[g]);
     }
-    // images that want tables of their own (optimized_huffman): slot k of the per-image histogram / code-table arrays
-    std::vector<int> opt_slot(ng, -1);
-    int nopt = 0;
-    for (int g = 0; g < ng; g++)
-        if (images_[idx[g]].params.optimized_huffman) opt_slot[g] = nopt++;
-    constexpr size_t kHistBytes = 2 * 2 * 256 * sizeof(uint32_t);
-    const size_t o_units = align_up(sizeof(HencImage) * (size_t)ng, 256);
-    const size_t o_tables = align_up(o_units + sizeof(HencUnit) * units.size(), 256);
-    const size_t o_opt_tables = align_up(o_tables + sizeof(StandardCodeTables), 256);
-    const size_t up1 = align_up(o_opt_tables + sizeof(StandardCodeTables) * (size_t)nopt, 256);  // uploaded part
-    const size_t o_bits = up1;
-    const size_t o_off = align_up(o_bits + total_blocks * 2, 256);
-    const size_t o_total = align_up(o_off + total_blocks * 4, 256);
-    const size_t o_hist = align_up(o_total + (size_t)ng * 4, 256);
-    const size_t dev1 = o_hist + align_up(kHistBytes * (size_t)nopt, 256);
-    hipjpegStatus_t st;
-    if ((st = henc_dev_.reserve(dev1 + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
-    // pinned staging: phase-1 upload | totals | phase-2 upload (descriptors again, chunk units, headers) | lengths, offsets
-    std::vector<std::vector<uint8_t>> headers(ng);
-    for (int g = 0; g < ng; g++) {
-        const PlannedEncode& im = images_[idx[g]];
-        write_standard_headers(im.geom, im.qlum, im.qchr, &headers[g]);
-    }
-    const size_t p_totals = up1;
-    const size_t p_hist = align_up(p_totals + (size_t)ng * 4, 256);
-    const size_t p_up2 = align_up(p_hist + kHistBytes * (size_t)nopt, 256);
-    // worst case for the chunk count: sized after the totals are known -> reserve generously from the block count
-    // (a block codes to at most 64 * (16 + 15) bits; in practice ~10 bytes) -- the exact size is re-checked below
-    if ((st = henc_pinned_.reserve(p_up2 + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
-    uint8_t* pin = henc_pinned_.data();
-    memcpy(pin, desc.data(), sizeof(HencImage) * (size_t)ng);
-    memcpy(pin + o_units, units.data(), sizeof(HencUnit) * units.size());
-    standard_code_tables(reinterpret_cast<StandardCodeTables*>(pin + o_tables));
-    uint8_t* dev = henc_dev_.data();
-    const HencImage* dimg = reinterpret_cast<const HencImage*>(dev);
-    const HencUnit* dunits = reinterpret_cast<const HencUnit*>(dev + o_units);
-    const StandardCodeTables* dtables = reinterpret_cast<const StandardCodeTables*>(dev + o_tables);
-    uint16_t* block_bits = reinterpret_cast<uint16_t*>(dev + o_bits);
-    uint32_t* block_off = reinterpret_cast<uint32_t*>(dev + o_off);
-    uint32_t* total_bits = reinterpret_cast<uint32_t*>(dev + o_total);
-    if (nopt > 0) {
-        // ---- phase 0: symbol statistics on the device, optimal tables on the host (a few dozen microseconds per image), tables back up.
-        // The coefficients never leave HBM; what crosses PCIe is 4 KB of counts and 1.6 KB of tables per image.
-        for (int g = 0; g < ng; g++)
-            if (opt_slot[g] >= 0) desc[g].hist = reinterpret_cast<uint32_t*>(dev + o_hist + kHistBytes * (size_t)opt_slot[g]);
-        memcpy(pin, desc.data(), sizeof(HencImage) * (size_t)ng);
-        if (hipMemcpyAsync(dev, pin, o_opt_tables, hipMemcpyHostToDevice, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-        if (hipMemsetAsync(dev + o_hist, 0, kHistBytes * (size_t)nopt, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-        if (launch_henc_hist(dimg, dunits, (int)units.size(), stream_) != 0) return HIPJPEG_STATUS_HIP_ERROR;
-        if (hipMemcpyAsync(pin + p_hist, dev + o_hist, kHistBytes * (size_t)nopt, hipMemcpyDeviceToHost, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-        if (hipStreamSynchronize(s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-        for (int g = 0; g < ng; g++) {
-            if (opt_slot[g] < 0) continue;
-            const PlannedEncode& im = images_[idx[g]];
-            const auto* counts = reinterpret_cast<const uint32_t(*)[2][256]>(pin + p_hist + kHistBytes * (size_t)opt_slot[g]);
-            headers[g].clear();
-            optimal_code_tables(counts, im.geom, im.qlum, im.qchr,
-                                reinterpret_cast<StandardCodeTables*>(pin + o_opt_tables + sizeof(StandardCodeTables) * (size_t)opt_slot[g]), &headers[g]);
-            desc[g].hist = nullptr;
-            desc[g].tables = reinterpret_cast<const StandardCodeTables*>(dev + o_opt_tables + sizeof(StandardCodeTables) * (size_t)opt_slot[g]);
-        }
-        memcpy(pin, desc.data(), sizeof(HencImage) * (size_t)ng);
-    }
-    if (hipMemcpyAsync(dev, pin, up1, hipMemcpyHostToDevice, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-    if (launch_henc_length(dimg, dunits, (int)units.size(), dtables, block_bits, stream_) != 0) return HIPJPEG_STATUS_HIP_ERROR;
-    if (launch_henc_scan(dimg, ng, block_bits, block_off, total_bits, stream_) != 0) return HIPJPEG_STATUS_HIP_ERROR;
-    uint32_t* h_totals = reinterpret_cast<uint32_t*>(pin + p_totals);
-    if (hipMemcpyAsync(h_totals, total_bits, (size_t)ng * 4, hipMemcpyDeviceToHost, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-    if (hipStreamSynchronize(s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+}
 
-    // ---- phase 2: bit buffers, stuffing, file assembly
-    std::vector<HencUnit> chunk_units;
-    size_t raw_total = 0, arena_cap = 0, nchunks = 0;
-    std::vector<size_t> raw_off(ng), hdr_off(ng);
-    size_t hdr_total = 0;
-    for (int g = 0; g < ng; g++) {
-        HencImage& h = desc[g];
-        const uint32_t pad = (8 - (h_totals[g] & 7)) & 7;
-        h.raw_bytes = (h_totals[g] + pad) / 8;
-        h.first_chunk = (uint32_t)nchunks;
-        h.num_chunks = (h.raw_bytes + kHencChunk - 1) / kHencChunk;
-        for (uint32_t c = 0; c < h.num_chunks; c++) chunk_units.push_back(HencUnit{(uint32_t)g, c});
-        nchunks += h.num_chunks;
-        raw_off[g] = raw_total;
-        raw_total += align_up((size_t)h.raw_bytes + 16, 256);
-        h.header_bytes = (uint32_t)headers[g].size();
-        hdr_off[g] = hdr_total;
-        hdr_total += align_up(headers[g].size(), 16);
-        arena_cap += align_up((size_t)h.header_bytes + 2 * (size_t)h.raw_bytes + 2, 16);  // every byte could be 0xFF
-    }
-    const size_t q_units = align_up(sizeof(HencImage) * (size_t)ng, 256);
-    const size_t q_headers = align_up(q_units + sizeof(HencUnit) * chunk_units.size(), 256);
-    const size_t up2 = align_up(q_headers + hdr_total, 256);
-    const size_t q_ff = up2;
-    const size_t q_out = align_up(q_ff + nchunks * 4, 256);
-    const size_t q_len = align_up(q_out + nchunks * 4, 256);
-    const size_t q_foff = align_up(q_len + (size_t)ng * 4, 256);
-    const size_t q_raw = align_up(q_foff + (size_t)ng * 8, 256);
-    const size_t q_arena = align_up(q_raw + raw_total, 256);
-    if ((st = henc_dev2_.reserve(q_arena + arena_cap + 256)) != HIPJPEG_STATUS_SUCCESS) return st;  // (arena unused when the files go to the host directly)
-    // the pinned buffer is about to grow: keep what is still needed
-    const size_t p_len = align_up(p_up2 + up2, 256);
-    const size_t p_foff = align_up(p_len + (size_t)ng * 4, 256);
-    if ((st = henc_pinned_.reserve(p_foff + (size_t)ng * 8 + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
-    pin = henc_pinned_.data();
-    uint8_t* dev2 = henc_dev2_.data();
-    for (int g = 0; g < ng; g++) {
-        desc[g].raw = dev2 + q_raw + raw_off[g];
-        desc[g].header = dev2 + q_headers + hdr_off[g];
-        memcpy(pin + p_up2 + q_headers + hdr_off[g], headers[g].data(), headers[g].size());
-    }
-    memcpy(pin + p_up2, desc.data(), sizeof(HencImage) * (size_t)ng);
-    memcpy(pin + p_up2 + q_units, chunk_units.data(), sizeof(HencUnit) * chunk_units.size());
-    const HencImage* dimg2 = reinterpret_cast<const HencImage*>(dev2);
-    const HencUnit* dchunks = reinterpret_cast<const HencUnit*>(dev2 + q_units);
-    uint32_t* chunk_ff = reinterpret_cast<uint32_t*>(dev2 + q_ff);
-    uint32_t* chunk_out = reinterpret_cast<uint32_t*>(dev2 + q_out);
-    uint32_t* final_len = reinterpret_cast<uint32_t*>(dev2 + q_len);
-    unsigned long long* final_off = reinterpret_cast<unsigned long long*>(dev2 + q_foff);
-    // The finished files go straight into pinned host memory when it is ours (hipHostMalloc: mapped into the device's address
-    // space): the expand kernel's stores cross PCIe themselves and no copy follows.  With a caller-supplied pinned allocator
-    // the mapping is unknown, so the files are assembled in HBM and copied.
-    bool direct = henc_out_.reserve(arena_cap + 256) == HIPJPEG_STATUS_SUCCESS && !henc_out_.custom();
-    uint8_t* arena = direct ? henc_out_.data() : dev2 + q_arena;
-    if (hipMemcpyAsync(dev2, pin + p_up2, up2, hipMemcpyHostToDevice, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-    if (launch_henc_zero(dev2 + q_raw, raw_total, stream_) != 0) return HIPJPEG_STATUS_HIP_ERROR;
-    if (launch_henc_write(dimg2, dunits, (int)units.size(), dtables, block_off, block_bits, stream_) != 0) return HIPJPEG_STATUS_HIP_ERROR;
-    if (launch_henc_count(dimg2, dchunks, (int)nchunks, chunk_ff, stream_) != 0) return HIPJPEG_STATUS_HIP_ERROR;
-    if (launch_henc_layout(dimg2, ng, chunk_ff, chunk_out, final_len, final_off, stream_) != 0) return HIPJPEG_STATUS_HIP_ERROR;
-    if (launch_henc_expand(dimg2, dchunks, (int)nchunks, chunk_out, final_len, final_off, arena, stream_) != 0) return HIPJPEG_STATUS_HIP_ERROR;
-    uint32_t* h_len = reinterpret_cast<uint32_t*>(pin + p_len);
-    unsigned long long* h_foff = reinterpret_cast<unsigned long long*>(pin + p_foff);
-    if (hipMemcpyAsync(h_len, final_len, (size_t)ng * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(h_foff, final_off, (size_t)ng * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
-        return HIPJPEG_STATUS_HIP_ERROR;
-    if (hipStreamSynchronize(s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-    const size_t used = (size_t)h_foff[ng - 1] + align_up((size_t)h_len[ng - 1], 16);
-    if (used > arena_cap) return HIPJPEG_STATUS_HIP_ERROR;  // cannot happen: the capacity assumes every byte is stuffed
-    if (!direct) {
-        if ((st = henc_out_.reserve(used + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
-        if (hipMemcpyAsync(henc_out_.data(), arena, used, hipMemcpyDeviceToHost, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-        if (hipStreamSynchronize(s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-    }
-    for (int g = 0; g < ng; g++) {
-        PlannedEncode& im = images_[idx[g]];
-        im.gpu_bitstream = henc_out_.data() + h_foff[g];
-        im.gpu_bitstream_len = h_len[g];
-    }
-    gpu_entropy_images_ = (uint64_t)ng;
+// Lays out the phase-1 device arena and the start of henc_pinned_; stages descriptors, units and standard tables.
+hipjpegStatus_t EncodeBatch::henc_stage_phase1(HencPlan& p)
+{
+    const int ng = (int)p.idx.size();
+    HencLayout1& d1 = p.d1;
+    Carve c;
+    d1.desc = c.take(sizeof(HencImage) * (size_t)ng);
+    d1.units = c.take(sizeof(HencUnit) * p.units.size());
+    d1.tables = c.take(sizeof(StandardCodeTables));
+    d1.opt_tables = c.take(sizeof(StandardCodeTables) * (size_t)p.nopt);
+    d1.bits = c.take(p.total_blocks * 2);
+    d1.off = c.take(p.total_blocks * 4);
+    d1.totals = c.take((size_t)ng * 4);
+    d1.hist = c.take(kHistBytes * (size_t)p.nopt);
+    d1.end = c.take(0);
+    p.pin = henc_pinned_layout(d1, ng, p.nopt, 0);
+    // henc_pinned_ grows again in phase 2, after the totals have been read (reserve() keeps no contents)
+    hipjpegStatus_t st;
+    if ((st = henc_dev_.reserve(d1.end + 256)) != HIPJPEG_STATUS_SUCCESS || (st = henc_pinned_.reserve(p.pin.up2 + 256)) != HIPJPEG_STATUS_SUCCESS)
+        return st;
+    copy_table(henc_pinned_, d1.desc, p.desc);
+    copy_table(henc_pinned_, d1.units, p.units);
+    standard_code_tables(at<StandardCodeTables>(henc_pinned_, d1.tables));
     return HIPJPEG_STATUS_SUCCESS;
 }
 
-void EncodeBatch::entropy_stage(int i)
+// Phase 0: symbol statistics on the device, optimal tables on the host (a few dozen microseconds per image); the tables go up
+// with phase 1.  The coefficients never leave HBM; what crosses PCIe is 4 KB of counts and 1.6 KB of tables per image.
+hipjpegStatus_t EncodeBatch::henc_histograms(HencPlan& p)
 {
-    PlannedEncode& im = images_[i];
-    if (im.status != HIPJPEG_STATUS_SUCCESS) return;
-    const int16_t* coef[3] = {nullptr, nullptr, nullptr};
-    for (int c = 0; c < im.geom.ncomp; c++) coef[c] = host_coef(i, c);
-    EntropyEncodeOptions opt;
-    opt.restart_interval = im.params.restart_interval;
-    opt.optimized_huffman = im.params.optimized_huffman != 0;
-    opt.progressive = im.params.progressive != 0;
-    im.bitstream.clear();
-    im.gpu_bitstream = nullptr;
-    im.gpu_bitstream_len = 0;
-    encode_jfif(im.geom, im.qlum, im.qchr, coef, opt, &im.bitstream);
+    const HencLayout1& d1 = p.d1;
+    const size_t hist_bytes = kHistBytes * (size_t)p.nopt;
+    hipStream_t s = (hipStream_t)stream_;
+    for (size_t g = 0; g < p.idx.size(); g++)
+        if (p.opt_slot[g] >= 0) p.desc[g].hist = at<uint32_t>(henc_dev_, d1.hist + kHistBytes * (size_t)p.opt_slot[g]);
+    copy_table(henc_pinned_, d1.desc, p.desc);
+    if (hipMemcpyAsync(henc_dev_.data(), henc_pinned_.data(), d1.opt_tables, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemsetAsync(henc_dev_.data() + d1.hist, 0, hist_bytes, s) != hipSuccess ||
+        launch_henc_hist(at<const HencImage>(henc_dev_, d1.desc), at<const HencUnit>(henc_dev_, d1.units), (int)p.units.size(), stream_) != 0 ||
+        hipMemcpyAsync(henc_pinned_.data() + p.pin.hist, henc_dev_.data() + d1.hist, hist_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    for (size_t g = 0; g < p.idx.size(); g++) {
+        const int k = p.opt_slot[g];
+        if (k < 0) continue;
+        const PlannedEncode& im = images_[p.idx[g]];
+        const auto* counts = at<const uint32_t[2][256]>(henc_pinned_, p.pin.hist + kHistBytes * (size_t)k);
+        const size_t tables = d1.opt_tables + sizeof(StandardCodeTables) * (size_t)k;
+        p.headers[g].clear();
+        optimal_code_tables(counts, im.geom, im.qlum, im.qchr, at<StandardCodeTables>(henc_pinned_, tables), &p.headers[g]);
+        p.desc[g].hist = nullptr;
+        p.desc[g].tables = at<const StandardCodeTables>(henc_dev_, tables);
+    }
+    copy_table(henc_pinned_, d1.desc, p.desc);
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+// Phase 1: descriptors, units and tables up; block lengths, their prefix sums, and every image's total bits back.
+hipjpegStatus_t EncodeBatch::henc_lengths(HencPlan& p)
+{
+    const HencLayout1& d1 = p.d1;
+    const int ng = (int)p.idx.size();
+    const HencImage* dimg = at<const HencImage>(henc_dev_, d1.desc);
+    hipStream_t s = (hipStream_t)stream_;
+    if (hipMemcpyAsync(henc_dev_.data(), henc_pinned_.data(), d1.upload(), hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_henc_length(dimg, at<const HencUnit>(henc_dev_, d1.units), (int)p.units.size(), at<const StandardCodeTables>(henc_dev_, d1.tables),
+                           at<uint16_t>(henc_dev_, d1.bits), stream_) != 0 ||
+        launch_henc_scan(dimg, ng, at<const uint16_t>(henc_dev_, d1.bits), at<uint32_t>(henc_dev_, d1.off), at<uint32_t>(henc_dev_, d1.totals), stream_) != 0 ||
+        hipMemcpyAsync(henc_pinned_.data() + p.pin.totals, henc_dev_.data() + d1.totals, (size_t)ng * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+// From the total bits: every image's bit buffer, stuffing chunks, header slot and worst-case file size.
+void EncodeBatch::henc_chunks(HencPlan& p)
+{
+    const int ng = (int)p.idx.size();
+    const uint32_t* totals = at<const uint32_t>(henc_pinned_, p.pin.totals);
+    Carve raw, hdr;  // the bit-buffer area and the header area of the phase-2 arena
+    p.raw_off.resize(ng);
+    p.hdr_off.resize(ng);
+    for (int g = 0; g < ng; g++) {
+        HencImage& h = p.desc[g];
+        h.raw_bytes = (totals[g] + ((8 - (totals[g] & 7)) & 7)) / 8;
+        h.first_chunk = (uint32_t)p.chunk_units.size();
+        h.num_chunks = (h.raw_bytes + kHencChunk - 1) / kHencChunk;
+        for (uint32_t c = 0; c < h.num_chunks; c++) p.chunk_units.push_back(HencUnit{(uint32_t)g, c});
+        h.header_bytes = (uint32_t)p.headers[g].size();
+        p.raw_off[g] = raw.take((size_t)h.raw_bytes + 16);
+        p.hdr_off[g] = hdr.take(p.headers[g].size(), 16);
+        p.arena_cap += align_up((size_t)h.header_bytes + 2 * (size_t)h.raw_bytes + 2, 16);  // every byte could be 0xFF
+    }
+    p.raw_total = raw.take(0);
+    p.hdr_total = hdr.take(0, 16);
+}
+
+// Phase 2: bit buffers, stuffing, file assembly; file lengths and offsets back.  The finished files go straight into pinned host
+// memory when it is ours (hipHostMalloc: mapped into the device's address space): the expand kernel's stores cross PCIe themselves
+// and no copy follows.  With a caller-supplied pinned allocator the mapping is unknown, so the files are assembled in HBM.
+hipjpegStatus_t EncodeBatch::henc_assemble(HencPlan& p, bool* direct)
+{
+    const int ng = (int)p.idx.size();
+    const size_t nchunks = p.chunk_units.size();
+    HencLayout2& d2 = p.d2;
+    Carve c;
+    d2.desc = c.take(sizeof(HencImage) * (size_t)ng);
+    d2.units = c.take(sizeof(HencUnit) * nchunks);
+    d2.headers = c.take(p.hdr_total);
+    d2.ff = c.take(nchunks * 4);
+    d2.out = c.take(nchunks * 4);
+    d2.len = c.take((size_t)ng * 4);
+    d2.foff = c.take((size_t)ng * 8);
+    d2.raw = c.take(p.raw_total);
+    d2.arena = c.take(p.arena_cap);
+    d2.end = c.end;
+    p.pin = henc_pinned_layout(p.d1, ng, p.nopt, d2.upload());
+    hipjpegStatus_t st;
+    if ((st = henc_dev2_.reserve(d2.end + 256)) != HIPJPEG_STATUS_SUCCESS || (st = henc_pinned_.reserve(p.pin.end + 256)) != HIPJPEG_STATUS_SUCCESS)
+        return st;
+    for (int g = 0; g < ng; g++) {
+        p.desc[g].raw = henc_dev2_.data() + d2.raw + p.raw_off[g];
+        p.desc[g].header = henc_dev2_.data() + d2.headers + p.hdr_off[g];
+        copy_table(henc_pinned_, p.pin.up2 + d2.headers + p.hdr_off[g], p.headers[g]);
+    }
+    copy_table(henc_pinned_, p.pin.up2 + d2.desc, p.desc);
+    copy_table(henc_pinned_, p.pin.up2 + d2.units, p.chunk_units);
+    *direct = henc_out_.reserve(p.arena_cap + 256) == HIPJPEG_STATUS_SUCCESS && !henc_out_.custom();
+    const HencImage* dimg = at<const HencImage>(henc_dev2_, d2.desc);
+    const HencUnit* dchunks = at<const HencUnit>(henc_dev2_, d2.units);
+    uint32_t *chunk_ff = at<uint32_t>(henc_dev2_, d2.ff), *chunk_out = at<uint32_t>(henc_dev2_, d2.out), *len = at<uint32_t>(henc_dev2_, d2.len);
+    unsigned long long* foff = at<unsigned long long>(henc_dev2_, d2.foff);
+    hipStream_t s = (hipStream_t)stream_;
+    if (hipMemcpyAsync(henc_dev2_.data(), henc_pinned_.data() + p.pin.up2, d2.upload(), hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_henc_zero(henc_dev2_.data() + d2.raw, p.raw_total, stream_) != 0 ||
+        launch_henc_write(dimg, at<const HencUnit>(henc_dev_, p.d1.units), (int)p.units.size(), at<const StandardCodeTables>(henc_dev_, p.d1.tables),
+                          at<const uint32_t>(henc_dev_, p.d1.off), at<const uint16_t>(henc_dev_, p.d1.bits), stream_) != 0 ||
+        launch_henc_count(dimg, dchunks, (int)nchunks, chunk_ff, stream_) != 0 ||
+        launch_henc_layout(dimg, ng, chunk_ff, chunk_out, len, foff, stream_) != 0 ||
+        launch_henc_expand(dimg, dchunks, (int)nchunks, chunk_out, len, foff, *direct ? henc_out_.data() : henc_dev2_.data() + d2.arena, stream_) != 0 ||
+        hipMemcpyAsync(henc_pinned_.data() + p.pin.len, len, (size_t)ng * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(henc_pinned_.data() + p.pin.foff, foff, (size_t)ng * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+// The files' places in henc_out_ (copied down first when they were assembled in HBM).
+hipjpegStatus_t EncodeBatch::henc_collect(HencPlan& p, bool direct)
+{
+    const int ng = (int)p.idx.size();
+    const uint32_t* len = at<const uint32_t>(henc_pinned_, p.pin.len);
+    const unsigned long long* foff = at<const unsigned long long>(henc_pinned_, p.pin.foff);
+    const size_t used = (size_t)foff[ng - 1] + align_up((size_t)len[ng - 1], 16);
+    if (used > p.arena_cap) return HIPJPEG_STATUS_HIP_ERROR;  // cannot happen: the capacity assumes every byte is stuffed
+    if (!direct) {
+        hipjpegStatus_t st;
+        if ((st = henc_out_.reserve(used + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
+        if (hipMemcpyAsync(henc_out_.data(), henc_dev2_.data() + p.d2.arena, used, hipMemcpyDeviceToHost, (hipStream_t)stream_) != hipSuccess ||
+            hipStreamSynchronize((hipStream_t)stream_) != hipSuccess)
+            return HIPJPEG_STATUS_HIP_ERROR;
+    }
+    for (int g = 0; g < ng; g++) {
+        images_[p.idx[g]].gpu_bitstream = henc_out_.data() + foff[g];
+        images_[p.idx[g]].gpu_bitstream_len = len[g];
+    }
+    gpu_entropy_images_ = (uint64_t)ng;
+    return HIPJPEG_STATUS_SUCCESS;
 }
 
 }  // namespace hipjpeg

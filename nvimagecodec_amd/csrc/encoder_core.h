@@ -6,10 +6,10 @@
 #include <vector>
 
 #include "../../include/hipjpeg.h"
-#include "decoder_core.h"
 #include "encode_layout.h"
 #include "entropy_encode.h"
 #include "gpu_huffman_encode.h"
+#include "staging.h"
 
 namespace hipjpeg {
 
@@ -26,6 +26,15 @@ struct PlannedEncode {
     size_t file_size() const { return gpu_bitstream ? gpu_bitstream_len : bitstream.size(); }
 };
 
+// Flavours of the forward kernel, in the order their unit lists lie in the units table.
+enum EncodeFlavour {
+    kFwdOneLane,                                              // one lane per block, any input (forward_kernel)
+    kFwdPair420, kFwdPair422, kFwdPair444,                    // forward_pair_kernel on interleaved RGB / BGR
+    kFwdPlanes,                                               // planar YCbCr: one lane per real block of each component
+    kFwdPlanarPair420, kFwdPlanarPair422, kFwdPlanarPair444,  // forward_pair_kernel on planar RGB / BGR
+    kNumFwdFlavours
+};
+
 class EncodeBatch {
 public:
     EncodeBatch(int device_id, const MemoryHooks* hooks);
@@ -34,12 +43,15 @@ public:
     hipjpegStatus_t device_stage(const hipjpegEncodeInput_t* inputs, const hipjpegEncodeParams_t* params, int n, hipjpegStatus_t* statuses,
                                  void* stream);
     hipjpegStatus_t relaunch(void* stream);
-    // Coefficients D2H (on the stream used by device_stage), wait, then Huffman + markers for image i.
+    // Coefficients D2H (on the stream used by device_stage), wait.
     hipjpegStatus_t fetch_coefficients();
+    // Decides who entropy-codes each planned image: with gpu_huffman the GPU coder (blocking) takes every image it can -- Annex-K
+    // or optimized tables, no restart markers, no progressive scans -- and the rest is flagged for the host coder (every planned
+    // image without gpu_huffman).  Fetches the coefficients when the host coder has anything to do.
+    hipjpegStatus_t route_entropy(bool gpu_huffman);
+    // Host coder: Huffman + markers for image i when route_entropy() left it to the host; otherwise nothing.  Thread-safe for distinct i.
     void entropy_stage(int i);
-    // GPU entropy coder (gpu_huffman_encode.h) for every image it can take -- Annex-K tables, no restart markers; blocking.
-    // todo[i] = true afterwards for the images that still need the host coder (entropy_stage).
-    hipjpegStatus_t gpu_entropy_stage(std::vector<char>* todo);
+    int host_images() const { return host_images_; }  // images route_entropy() left to the host coder
     uint64_t gpu_entropy_images() const { return gpu_entropy_images_; }
     int size() const { return (int)images_.size(); }
     PlannedEncode& image(int i) { return images_[i]; }
@@ -50,24 +62,53 @@ public:
 
 private:
     int device_id_;
+    // ---- device_stage(): per-image checks and descriptors, unit lists, layout of the descriptor arena, device pointers
+    void prepare(int i, const hipjpegEncodeInput_t& in, const hipjpegEncodeParams_t& p);
+    void add_units(int i, int fmt);
+    void layout();
+    hipjpegStatus_t reserve();
+    void bind_pointers();
     Buffer pinned_desc_, device_, pinned_coef_;
     std::vector<PlannedEncode> images_;
     std::vector<EncodeImage> desc_;
-    std::vector<EncodeUnit> units_;            // every tile of the batch, grouped by kernel flavour
-    // [0] one-lane-per-block kernel, [1..3] forward_pair_kernel 4:2:0 / 4:2:2 / 4:4:4 on interleaved input, [4] planar YCbCr,
-    // [5..7] forward_pair_kernel on planar RGB / BGR input
-    static constexpr int kUnitLists = 8;
-    std::vector<EncodeUnit> unit_lists_[kUnitLists];
-    size_t unit_first_[kUnitLists] = {0, 0, 0, 0, 0, 0, 0, 0};
-    size_t units_offset_ = 0, coef_offset_ = 0, desc_bytes_ = 0, coef_total_ = 0;
+    std::vector<EncodeUnit> units_;  // every tile of the batch, grouped by flavour
+    std::vector<EncodeUnit> unit_lists_[kNumFwdFlavours];
+    size_t unit_first_[kNumFwdFlavours] = {};
+    // Descriptor arena, pinned and mirrored on the device at the same offsets: EncodeImage[] | EncodeUnit[] (the upload, [0, coef))
+    // || (device only) the coefficients, which pinned_coef_ receives at offset 0.
+    struct EncodeStaging {
+        size_t desc, units, coef, total;
+    } staging_{};
+    size_t coef_total_ = 0;
     uint64_t pixel_bytes_ = 0, coef_bytes_ = 0;
     void* stream_ = nullptr;
     void* event_ = nullptr;
     bool launched_ = false, fetched_ = false;
+    // route_entropy(): per image, the host coder still has to code it.  Not a PlannedEncode field: the host coder's threads append
+    // to their own record's bitstream next to the neighbouring record's geometry, and a record that grows slows them down.
+    std::vector<char> host_coder_;
+    int host_images_ = 0;
+
+    // ---- gpu_entropy_stage(): two short host round trips (after the length scan: the bit-buffer sizes; after the layout: the
+    // file sizes), everything else queued on the stream the forward kernel ran on
+    struct HencPlan;  // what the phases hand on
+    hipjpegStatus_t gpu_entropy_stage();
+    void henc_choose(HencPlan& p);
+    void henc_describe(HencPlan& p);
+    hipjpegStatus_t henc_stage_phase1(HencPlan& p);
+    hipjpegStatus_t henc_histograms(HencPlan& p);
+    hipjpegStatus_t henc_lengths(HencPlan& p);
+    void henc_chunks(HencPlan& p);
+    hipjpegStatus_t henc_assemble(HencPlan& p, bool* direct);
+    hipjpegStatus_t henc_collect(HencPlan& p, bool direct);
     Buffer henc_dev_, henc_dev2_, henc_pinned_, henc_out_;
     uint64_t gpu_entropy_images_ = 0;
 };
 
 hipjpegStatus_t subsampling_factors(int subsampling, int* ncomp, int* hs, int* vs);
+// Geometry (subsampling factors, block grid) and quantiser tables of a width x height picture coded with `p`: UNSUPPORTED for an
+// unknown subsampling, INVALID_ARGUMENT for a size outside 1..65535 (then neither grid nor tables are filled).
+hipjpegStatus_t picture_setup(const hipjpegEncodeParams_t& p, int width, int height, EncodeGeometry* g, uint16_t qlum[64], uint16_t qchr[64]);
+EntropyEncodeOptions entropy_options(const hipjpegEncodeParams_t& p);
 
 }  // namespace hipjpeg

@@ -557,20 +557,9 @@ hipjpegStatus_t hipjpegEncodeBatchEntropy(hipjpegHandle_t handle, unsigned flags
     return guarded([&]() -> hipjpegStatus_t {
     if (!handle) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     EncodeBatch& b = *handle->encode;
-    std::vector<char> todo(b.size(), 1);
-    hipjpegStatus_t st;
-    if (flags & HIPJPEG_FLAG_GPU_HUFFMAN) {
-        if ((st = b.gpu_entropy_stage(&todo)) != HIPJPEG_STATUS_SUCCESS) return st;
-    }
-    bool any = false;
-    for (int i = 0; i < b.size(); i++) any = any || (todo[i] && b.image(i).status == HIPJPEG_STATUS_SUCCESS);
-    if (any) {
-        // the host coder needs the coefficients on its side of PCIe
-        if ((st = b.fetch_coefficients()) != HIPJPEG_STATUS_SUCCESS) return st;
-        handle->pool->parallel_for(b.size(), [&](int i, int) {
-            if (todo[i]) b.entropy_stage(i);
-        });
-    }
+    const hipjpegStatus_t st = b.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0);
+    if (st != HIPJPEG_STATUS_SUCCESS) return st;
+    if (b.host_images()) handle->pool->parallel_for(b.size(), [&](int i, int) { b.entropy_stage(i); });
     if (statuses)
         for (int i = 0; i < b.size(); i++) statuses[i] = b.image(i).status;
     return HIPJPEG_STATUS_SUCCESS;
@@ -615,15 +604,8 @@ hipjpegStatus_t hipjpegEncodeBatchSubmit(hipjpegHandle_t handle, const hipjpegEn
         EncodeBatch& b = *page->batch;
         hipjpegStatus_t st = b.device_stage(page->inputs.data(), page->params.data(), (int)page->inputs.size(), nullptr, page->stream);
         if (st != HIPJPEG_STATUS_SUCCESS) return st;
-        std::vector<char> todo(b.size(), 1);
-        if ((flags & HIPJPEG_FLAG_GPU_HUFFMAN) && (st = b.gpu_entropy_stage(&todo)) != HIPJPEG_STATUS_SUCCESS) return st;
-        bool any = false;
-        for (int i = 0; i < b.size(); i++) any = any || (todo[i] && b.image(i).status == HIPJPEG_STATUS_SUCCESS);
-        if (any) {
-            if ((st = b.fetch_coefficients()) != HIPJPEG_STATUS_SUCCESS) return st;
-            for (int i = 0; i < b.size(); i++)
-                if (todo[i]) b.entropy_stage(i);
-        }
+        if ((st = b.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0)) != HIPJPEG_STATUS_SUCCESS) return st;
+        for (int i = 0; i < b.size(); i++) b.entropy_stage(i);
         return HIPJPEG_STATUS_SUCCESS;
     });
     handle->encode_next = (handle->encode_next + 1) % hipjpegHandle::kEncodePages;
@@ -701,21 +683,13 @@ hipjpegStatus_t hipjpegEncodeFromCoefficientsHost(int32_t width, int32_t height,
     return guarded([&]() -> hipjpegStatus_t {
     if (!params || !coef || !length || width < 1 || height < 1 || width > 65535 || height > 65535) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     EncodeGeometry g;
-    g.width = width;
-    g.height = height;
-    hipjpegStatus_t st = subsampling_factors(params->subsampling, &g.ncomp, &g.hs, &g.vs);
+    uint16_t ql[64], qc[64];
+    hipjpegStatus_t st = picture_setup(*params, width, height, &g, ql, qc);
     if (st != HIPJPEG_STATUS_SUCCESS) return st;
-    compute_geometry(&g);
     for (int c = 0; c < g.ncomp; c++)
         if (!coef[c]) return HIPJPEG_STATUS_INVALID_ARGUMENT;
-    uint16_t ql[64], qc[64];
-    quality_tables(params->quality, ql, qc);
-    EntropyEncodeOptions opt;
-    opt.restart_interval = params->restart_interval;
-    opt.optimized_huffman = params->optimized_huffman != 0;
-    opt.progressive = params->progressive != 0;
     std::vector<uint8_t> bytes;
-    encode_jfif(g, ql, qc, coef, opt, &bytes);
+    encode_jfif(g, ql, qc, coef, entropy_options(*params), &bytes);
     *length = bytes.size();
     if (!out || capacity < bytes.size()) return HIPJPEG_STATUS_BUFFER_TOO_SMALL;
     memcpy(out, bytes.data(), bytes.size());

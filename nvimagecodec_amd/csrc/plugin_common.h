@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/nvimgcodec_abi.h"
+#include "staging.h"
 
 namespace hipjpeg_ext {
 
@@ -50,6 +51,23 @@ inline void for_each_option(const char* options, const char* module_name, F&& fn
         if (addressed && !module.empty()) addressed->push_back(token.substr(colon + 1, equal - colon - 1));  // named this very module
         fn(token.substr(colon + 1, equal - colon - 1), token.substr(equal + 1));
     }
+}
+
+// The execution parameters' device / pinned allocators as allocation hooks of the batches (an allocator needs both functions).
+inline hipjpeg::MemoryHooks memory_hooks(const nvimgcodecExecutionParams_t* ep)
+{
+    hipjpeg::MemoryHooks hooks;
+    if (ep->device_allocator && ep->device_allocator->device_malloc && ep->device_allocator->device_free) {
+        hooks.device_malloc = reinterpret_cast<int (*)(void*, void**, size_t, void*)>(ep->device_allocator->device_malloc);
+        hooks.device_free = reinterpret_cast<int (*)(void*, void*, size_t, void*)>(ep->device_allocator->device_free);
+        hooks.device_ctx = ep->device_allocator->device_ctx;
+    }
+    if (ep->pinned_allocator && ep->pinned_allocator->pinned_malloc && ep->pinned_allocator->pinned_free) {
+        hooks.pinned_malloc = reinterpret_cast<int (*)(void*, void**, size_t, void*)>(ep->pinned_allocator->pinned_malloc);
+        hooks.pinned_free = reinterpret_cast<int (*)(void*, void*, size_t, void*)>(ep->pinned_allocator->pinned_free);
+        hooks.pinned_ctx = ep->pinned_allocator->pinned_ctx;
+    }
+    return hooks;
 }
 
 // Walks a struct_next chain looking for a given structure type.

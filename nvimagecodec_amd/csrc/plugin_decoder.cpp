@@ -156,7 +156,7 @@ private:
 };
 
 HipJpegDecoder::HipJpegDecoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgcodecExecutionParams_t* ep, const char* options)
-    : fw_(fw), ep_(ep), device_(ep->device_id)
+    : fw_(fw), ep_(ep), hooks_(memory_hooks(ep)), device_(ep->device_id)
 {
     bool chain_fast_idct = false, named_fast_idct = false, named_fast_idct_given = false;
     size_t named_seen = 0;
@@ -189,16 +189,6 @@ HipJpegDecoder::HipJpegDecoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgc
         int threads = 0;
         if (ep->executor && ep->executor->getNumThreads) threads = ep->executor->getNumThreads(ep->executor->instance);
         parse_pool_.reset(new hipjpeg::ForkJoinPool(threads > 0 ? threads : 0));
-    }
-    if (ep->device_allocator && ep->device_allocator->device_malloc && ep->device_allocator->device_free) {
-        hooks_.device_malloc = reinterpret_cast<int (*)(void*, void**, size_t, void*)>(ep->device_allocator->device_malloc);
-        hooks_.device_free = reinterpret_cast<int (*)(void*, void*, size_t, void*)>(ep->device_allocator->device_free);
-        hooks_.device_ctx = ep->device_allocator->device_ctx;
-    }
-    if (ep->pinned_allocator && ep->pinned_allocator->pinned_malloc && ep->pinned_allocator->pinned_free) {
-        hooks_.pinned_malloc = reinterpret_cast<int (*)(void*, void**, size_t, void*)>(ep->pinned_allocator->pinned_malloc);
-        hooks_.pinned_free = reinterpret_cast<int (*)(void*, void*, size_t, void*)>(ep->pinned_allocator->pinned_free);
-        hooks_.pinned_ctx = ep->pinned_allocator->pinned_ctx;
     }
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device_ < 0 || device_ >= count) {

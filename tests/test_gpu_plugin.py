@@ -331,6 +331,66 @@ def test_python_encoder_mirror_through_plugin(torch_mod):
                                                         oracle.decode_coefficients(oracle.encode(imgs[0], "420", 90))[0]))
 
 
+def test_encoder_with_custom_allocators_assembles_files_in_hbm(torch_mod):
+    """A caller-supplied pinned allocator: the GPU entropy coder cannot write the files into memory whose device mapping it does
+    not know, so it assembles them in HBM and copies them down.  Same bytes as the oracle, the caller's allocators are used,
+    and every allocation is handed back when the encoder is destroyed."""
+    from nvimagecodec_amd import api
+    from nvimagecodec_amd.api import _api, _check
+    from nvimagecodec_amd.synth import synth_image
+    torch = torch_mod
+    lib, inst = _api()
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipHostMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_uint]
+    hip.hipFree.argtypes = [C.c_void_p]
+    hip.hipHostFree.argtypes = [C.c_void_p]
+    calls = {"dev": 0, "pin": 0, "devfree": 0, "pinfree": 0}
+
+    def dmalloc(ctx, pp, size, stream):
+        calls["dev"] += 1
+        return hip.hipMalloc(pp, size)
+
+    def dfree(ctx, p, size, stream):
+        calls["devfree"] += 1
+        return hip.hipFree(p)
+
+    def pmalloc(ctx, pp, size, stream):
+        calls["pin"] += 1
+        return hip.hipHostMalloc(pp, size, 0)
+
+    def pfree(ctx, p, size, stream):
+        calls["pinfree"] += 1
+        return hip.hipHostFree(p)
+
+    cbs = [A.DeviceMalloc(dmalloc), A.DeviceFree(dfree), A.DeviceMalloc(pmalloc), A.DeviceFree(pfree)]
+    da = A.init(A.DeviceAllocator, A.ST_DEVICE_ALLOCATOR, device_malloc=cbs[0], device_free=cbs[1])
+    pa = A.init(A.PinnedAllocator, A.ST_PINNED_ALLOCATOR, pinned_malloc=cbs[2], pinned_free=cbs[3])
+    device = torch.cuda.current_device()
+    ep = A.init(A.ExecutionParams, A.ST_EXECUTION_PARAMS, device_id=device, max_num_cpu_threads=2)
+    ep.device_allocator, ep.pinned_allocator = C.pointer(da), C.pointer(pa)
+    # the Python encoder's marshalling over an encoder handle created with the allocators (GPU entropy coder: the plugin's default)
+    enc = api.Encoder.__new__(api.Encoder)
+    enc._torch, enc.device_id, enc._h = torch, device, C.c_void_p()
+    _check(lib.nvimgcodecEncoderCreate(inst, C.byref(enc._h), C.byref(ep), b""), "nvimgcodecEncoderCreate")
+    imgs = [synth_image(w, h, seed=w) for (w, h) in ((64, 48), (131, 77), (320, 240))]
+    dev = [torch.from_numpy(i).cuda() for i in imgs]
+    std = api.EncodeParams(quality=90, chroma_subsampling=api.ChromaSubsampling.CSS_420)
+    opt = api.EncodeParams(quality=90, chroma_subsampling=api.ChromaSubsampling.CSS_420,
+                           jpeg_encode_params=api.JpegEncodeParams(optimized_huffman=True))
+    out = enc.encode([api.as_image(d) for d in dev], "jpeg", std)
+    assert out == [oracle.encode(im, "420", 90) for im in imgs]
+    # optimized tables: the files the default route (assembled straight into the encoder's own pinned memory) writes
+    out = enc.encode([api.as_image(d) for d in dev], "jpeg", opt)
+    with api.Encoder(max_num_cpu_threads=2) as plain:
+        want = plain.encode([api.as_image(d) for d in dev], "jpeg", opt)
+    assert all(b is not None and len(b) < len(oracle.encode(im, "420", 90)) for im, b in zip(imgs, out))
+    assert out == want
+    assert calls["dev"] >= 1 and calls["pin"] >= 1
+    enc.close()
+    assert calls["devfree"] == calls["dev"] and calls["pinfree"] == calls["pin"]
+
+
 def test_transcode_roundtrip_through_both_plugins(torch_mod, tmp_path):
     """decode -> encode -> decode through the nvImageCodec API route (the nvimtrans use case, example/nvimtrans/main.cpp)."""
     from nvimagecodec_amd import api
