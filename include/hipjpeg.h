@@ -71,7 +71,9 @@ typedef enum {
 #define HIPJPEG_FLAG_GPU_HUFFMAN 2u      /* entropy-decode eligible streams on the GPU (sequential Huffman in up to 4 scans that code every
                                             component once, in any component order, each scan a stream of its own, with or without restart
                                             intervals; progressive SOF2 with up to 24 scans); the host then only finds the scans.  Other
-                                            streams keep the host entropy stage. */
+                                            streams keep the host entropy stage.  Encoding: entropy-code on the GPU every image without a
+                                            restart interval -- baseline with Annex-K or optimized tables, or progressive output -- see
+                                            hipjpegEncodeBatchEntropy. */
 #define HIPJPEG_FLAG_FAST_IDCT 4u        /* the fast integer IDCT (plugin option hipjpeg_decoder:fast_idct=1; the reference's fast_idct, which
                                             selects JDCT_IFAST): the pixels are those of libjpeg-turbo's x86-64 SIMD routine
                                             jsimd_idct_ifast_sse2, which differs from jidctfst.c only on streams whose samples leave the
@@ -253,11 +255,12 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchDevice(hipjpegHandle_t handle, con
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchRelaunch(hipjpegHandle_t handle, void* stream);
 /* D2H of the quantized coefficients, then Huffman coding + marker writing on the host thread pool (blocking). */
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchHost(hipjpegHandle_t handle, hipjpegStatus_t* statuses);
-/* Entropy stage with a choice: flags = HIPJPEG_FLAG_GPU_HUFFMAN codes every baseline image without restart markers on the GPU
- * (Annex-K tables, or optimized ones: histograms on the device, jpeg_gen_optimal_table on the host, second pass on the device; then
- * lengths, prefix sums, bit packing, byte stuffing, file assembly -- only finished JPEG files cross PCIe); progressive output and restart
- * intervals (which the reference's encode parameters do not have), and everything when flags = 0, go through the host coder as in
- * hipjpegEncodeBatchHost.  Blocking. */
+/* Entropy stage with a choice: flags = HIPJPEG_FLAG_GPU_HUFFMAN codes every image without restart markers on the GPU: baseline with
+ * Annex-K tables, or optimized ones (histograms on the device, jpeg_gen_optimal_table on the host, second pass on the device), and
+ * progressive output (per-block summaries and the EOB-run resolution on the device, per-scan optimal tables on the host, then one
+ * segment per scan; byte-identical to the host coder's SOF2 files); then lengths, prefix sums, bit packing, byte stuffing, file
+ * assembly -- only finished JPEG files cross PCIe.  Restart intervals (which the reference's encode parameters do not have), and
+ * everything when flags = 0, go through the host coder as in hipjpegEncodeBatchHost.  Blocking. */
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchEntropy(hipjpegHandle_t handle, unsigned flags, hipjpegStatus_t* statuses);
 /* Both of the above. */
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatch(hipjpegHandle_t handle, const hipjpegEncodeInput_t* inputs, const hipjpegEncodeParams_t* params,
@@ -279,13 +282,20 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeGetBitstream(hipjpegHandle_t handle, in
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeGetCoefficients(hipjpegHandle_t handle, int index, int component, const int16_t** coef,
                                                          int32_t grid[4] /* blocks_w, blocks_h, real_w, real_h */);
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchStats(hipjpegHandle_t handle, int32_t* num_units, uint64_t* pixel_bytes, uint64_t* coef_bytes);
-/* How many images of the handle's last entropy stage the GPU entropy coder took (Annex-K or optimized tables, no restart intervals, baseline);
- * the others were coded by the host coder. */
+/* How many images of the handle's last entropy stage the GPU entropy coder took (no restart intervals: baseline with Annex-K or optimized
+ * tables, and progressive output); the others were coded by the host coder. */
 HIPJPEG_API int32_t hipjpegEncodeBatchGpuEntropyImages(hipjpegHandle_t handle);
 /* Host-only: entropy-code given coefficient grids (zigzag order, MCU-padded grids as above) into a JFIF file.
  * Returns HIPJPEG_STATUS_BUFFER_TOO_SMALL with *length = needed size if capacity is insufficient. */
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeFromCoefficientsHost(int32_t width, int32_t height, const hipjpegEncodeParams_t* params,
                                                               const int16_t* const coef[3], uint8_t* out, size_t capacity, size_t* length);
+/* The GPU entropy coder's progressive algorithm (csrc/progressive_encode_core.h: block summaries, EOB-run resolution, lengths, bit
+ * emission) executed on the host, block by block, with the very code the kernels run: lets the algorithm be verified without a GPU.
+ * Same signature and output as hipjpegEncodeFromCoefficientsHost; HIPJPEG_STATUS_UNSUPPORTED for what the GPU coder's progressive path
+ * does not take (baseline output, restart intervals). */
+HIPJPEG_API hipjpegStatus_t hipjpegEncodeFromCoefficientsGpuAlgorithmHost(int32_t width, int32_t height, const hipjpegEncodeParams_t* params,
+                                                                          const int16_t* const coef[3], uint8_t* out, size_t capacity,
+                                                                          size_t* length);
 
 #ifdef __cplusplus
 }

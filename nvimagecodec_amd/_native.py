@@ -125,5 +125,6 @@ def load():
     L.hipjpegEncodeBatchGpuEntropyImages.argtypes = [vp]
     L.hipjpegEncodeBatchGpuEntropyImages.restype = i32
     L.hipjpegEncodeFromCoefficientsHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
+    L.hipjpegEncodeFromCoefficientsGpuAlgorithmHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
     _lib = L
     return L

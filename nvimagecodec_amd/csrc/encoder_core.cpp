@@ -9,6 +9,7 @@
 
 #include "encode_kernels.h"
 #include "jpeg_syntax.h"
+#include "progressive_encode.h"
 
 namespace hipjpeg {
 
@@ -68,7 +69,8 @@ EntropyEncodeOptions entropy_options(const hipjpegEncodeParams_t& p)
 
 EncodeBatch::EncodeBatch(int device_id, const MemoryHooks* hooks)
     : device_id_(device_id), pinned_desc_(Buffer::kPinned, hooks), device_(Buffer::kDevice, hooks), pinned_coef_(Buffer::kPinned, hooks),
-      henc_dev_(Buffer::kDevice, hooks), henc_dev2_(Buffer::kDevice, hooks), henc_pinned_(Buffer::kPinned, hooks), henc_out_(Buffer::kPinned, hooks)
+      henc_dev_(Buffer::kDevice, hooks), henc_dev2_(Buffer::kDevice, hooks), henc_pinned_(Buffer::kPinned, hooks), henc_out_(Buffer::kPinned, hooks),
+      penc_dev_(Buffer::kDevice, hooks), penc_dev2_(Buffer::kDevice, hooks), penc_pinned_(Buffer::kPinned, hooks), penc_out_(Buffer::kPinned, hooks)
 {
 }
 
@@ -332,35 +334,82 @@ struct EncodeBatch::HencPlan {
     HencLayout2 d2{};
 };
 
+namespace {
+// Progressive output (progressive_encode.h).  Phase-1 device arena (penc_dev_): scans | length units | AC scans | segment descriptors
+// [the upload, staged at the same offsets at the start of penc_pinned_) | code tables [uploaded after the statistics] | symbol counts |
+// per block: summaries, pre / post flushes, pieces, flushers, rel, own bits, bits, offsets | total bits per scan.
+struct PencLayout1 {
+    size_t scans, units, ac, segs, codes, hist, sum, pre, post, piece, flusher, rel, own, bits, off, totals, end;
+};
+// penc_pinned_ behind the code tables: symbol counts | total bits | phase-2 upload (at the phase-2 arena's offsets) | lengths | offsets
+struct PencPinnedLayout { size_t hist, totals, up2, len, foff, end; };
+
+PencPinnedLayout penc_pinned_layout(const PencLayout1& d1, int nscans, size_t upload2)
+{
+    Carve c{d1.hist};
+    PencPinnedLayout p;
+    p.hist = c.take((size_t)nscans * 1024);
+    p.totals = c.take((size_t)nscans * 4);
+    p.up2 = c.take(upload2);
+    p.len = c.take((size_t)nscans * 4);
+    p.foff = c.take((size_t)nscans * 8);
+    p.end = c.end;
+    return p;
+}
+}  // namespace
+
+struct EncodeBatch::PencPlan {
+    std::vector<int> idx;                      // images taken, in batch order
+    std::vector<int> first_scan;               // per image: index of its first scan (one more entry: the end)
+    std::vector<PencScan> scans;               // every scan of those images (device pointers inside)
+    std::vector<HencUnit> units, chunk_units;  // length / write units (256 blocks of one scan, image = scan); count / expand units
+    std::vector<uint32_t> ac_scans;            // scans with end-of-band runs
+    std::vector<HencImage> segs;               // one file segment per scan: the count / layout / expand kernels' descriptors
+    std::vector<std::vector<uint8_t>> headers;  // per scan: [frame header] DHT.. SOS
+    std::vector<size_t> raw_off, hdr_off;
+    size_t total_blocks = 0, raw_total = 0, hdr_total = 0, arena_cap = 0;
+    PencLayout1 d1{};
+    PencPinnedLayout pin{};
+    HencLayout2 d2{};
+};
+
 hipjpegStatus_t EncodeBatch::gpu_entropy_stage()
 {
     gpu_entropy_images_ = 0;
     if (!launched_) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (hipSetDevice(device_id_) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
     HencPlan p;
-    henc_choose(p);
-    if (p.idx.empty()) return HIPJPEG_STATUS_SUCCESS;
-    henc_describe(p);
+    PencPlan q;
+    henc_choose(p, q);
     hipjpegStatus_t st;
-    if ((st = henc_stage_phase1(p)) != HIPJPEG_STATUS_SUCCESS || (p.nopt > 0 && (st = henc_histograms(p)) != HIPJPEG_STATUS_SUCCESS) ||
-        (st = henc_lengths(p)) != HIPJPEG_STATUS_SUCCESS)
-        return st;
-    henc_chunks(p);
     bool direct = false;
-    if ((st = henc_assemble(p, &direct)) != HIPJPEG_STATUS_SUCCESS) return st;
-    return henc_collect(p, direct);
+    if (!p.idx.empty()) {
+        henc_describe(p);
+        if ((st = henc_stage_phase1(p)) != HIPJPEG_STATUS_SUCCESS || (p.nopt > 0 && (st = henc_histograms(p)) != HIPJPEG_STATUS_SUCCESS) ||
+            (st = henc_lengths(p)) != HIPJPEG_STATUS_SUCCESS)
+            return st;
+        henc_chunks(p);
+        if ((st = henc_assemble(p, &direct)) != HIPJPEG_STATUS_SUCCESS || (st = henc_collect(p, direct)) != HIPJPEG_STATUS_SUCCESS) return st;
+    }
+    if (!q.idx.empty()) {
+        penc_describe(q);
+        if ((st = penc_statistics(q)) != HIPJPEG_STATUS_SUCCESS || (st = penc_lengths(q)) != HIPJPEG_STATUS_SUCCESS) return st;
+        penc_chunks(q);
+        if ((st = penc_assemble(q, &direct)) != HIPJPEG_STATUS_SUCCESS || (st = penc_collect(q, direct)) != HIPJPEG_STATUS_SUCCESS) return st;
+    }
+    return HIPJPEG_STATUS_SUCCESS;
 }
 
-// Every image the host coder would code except those with restart markers or progressive scans.
-void EncodeBatch::henc_choose(HencPlan& p)
+// Every image the host coder would code except those with restart markers: baseline ones into p, progressive ones into q.
+void EncodeBatch::henc_choose(HencPlan& p, PencPlan& q)
 {
     for (int i = 0; i < (int)images_.size(); i++) {
         PlannedEncode& im = images_[i];
         im.gpu_bitstream = nullptr;
         im.gpu_bitstream_len = 0;
-        if (!host_coder_[i] || im.params.restart_interval != 0 || im.params.progressive) continue;
+        if (!host_coder_[i] || im.params.restart_interval != 0) continue;
         host_coder_[i] = 0;
-        p.idx.push_back(i);
+        (im.params.progressive ? q.idx : p.idx).push_back(i);
     }
 }
 
@@ -486,6 +535,8 @@ void EncodeBatch::henc_chunks(HencPlan& p)
         h.num_chunks = (h.raw_bytes + kHencChunk - 1) / kHencChunk;
         for (uint32_t c = 0; c < h.num_chunks; c++) p.chunk_units.push_back(HencUnit{(uint32_t)g, c});
         h.header_bytes = (uint32_t)p.headers[g].size();
+        h.nseg = 1;  // a baseline file is one segment
+        h.last_seg = 1;
         p.raw_off[g] = raw.take((size_t)h.raw_bytes + 16);
         p.hdr_off[g] = hdr.take(p.headers[g].size(), 16);
         p.arena_cap += align_up((size_t)h.header_bytes + 2 * (size_t)h.raw_bytes + 2, 16);  // every byte could be 0xFF
@@ -563,7 +614,211 @@ hipjpegStatus_t EncodeBatch::henc_collect(HencPlan& p, bool direct)
         images_[p.idx[g]].gpu_bitstream = henc_out_.data() + foff[g];
         images_[p.idx[g]].gpu_bitstream_len = len[g];
     }
-    gpu_entropy_images_ = (uint64_t)ng;
+    gpu_entropy_images_ += (uint64_t)ng;
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+// ---------------------------------------------------------------- GPU entropy coder, progressive output
+// Scans, units, segments and the frame headers of the progressive images taken.
+void EncodeBatch::penc_describe(PencPlan& q)
+{
+    const int ng = (int)q.idx.size();
+    for (int g = 0; g < ng; g++) {
+        const PlannedEncode& im = images_[q.idx[g]];
+        const int16_t* coef[3] = {desc_[q.idx[g]].coef[0], desc_[q.idx[g]].coef[1], desc_[q.idx[g]].coef[2]};
+        const size_t s0 = q.scans.size();
+        q.first_scan.push_back((int)s0);
+        q.total_blocks += hipjpeg::penc_describe(im.geom, coef, q.total_blocks, &q.scans);
+        for (size_t k = s0; k < q.scans.size(); k++) {
+            const PencScan& sc = q.scans[k];
+            for (uint32_t b = 0; b < sc.nblocks; b += 256) q.units.push_back(HencUnit{(uint32_t)k, b});
+            if (sc.kind >= kPencAcFirst) q.ac_scans.push_back((uint32_t)k);
+            HencImage h;
+            memset(&h, 0, sizeof h);
+            h.total_blocks = sc.nblocks;  // what henc_scan reads
+            h.first_block = sc.first_block;
+            h.nseg = k == s0 ? (uint32_t)(q.scans.size() - s0) : 0u;
+            h.last_seg = k + 1 == q.scans.size() ? 1u : 0u;
+            q.segs.push_back(h);
+            q.headers.emplace_back();
+        }
+        write_progressive_frame_header(im.geom, im.qlum, im.qchr, &q.headers[s0]);
+    }
+    q.first_scan.push_back((int)q.scans.size());
+}
+
+// Phase 0: descriptors up; block summaries, run resolution and the symbol counts of every scan on the device; the counts back in one
+// copy (1 KB per scan); optimal tables, DHT and SOS per scan on the host.
+hipjpegStatus_t EncodeBatch::penc_statistics(PencPlan& q)
+{
+    const size_t ns = q.scans.size(), nb = q.total_blocks;
+    PencLayout1& d1 = q.d1;
+    Carve c;
+    d1.scans = c.take(sizeof(PencScan) * ns);
+    d1.units = c.take(sizeof(HencUnit) * q.units.size());
+    d1.ac = c.take(4 * q.ac_scans.size());
+    d1.segs = c.take(sizeof(HencImage) * ns);
+    d1.codes = c.take(1024 * ns);
+    d1.hist = c.take(1024 * ns);
+    d1.sum = c.take(nb);
+    d1.pre = c.take(4 * nb);
+    d1.post = c.take(4 * nb);
+    d1.piece = c.take(4 * nb);
+    d1.flusher = c.take(4 * nb);
+    d1.rel = c.take(2 * nb);
+    d1.own = c.take(2 * nb);
+    d1.bits = c.take(2 * nb);
+    d1.off = c.take(4 * nb);
+    d1.totals = c.take(4 * ns);
+    d1.end = c.take(0);
+    q.pin = penc_pinned_layout(d1, (int)ns, 0);
+    hipjpegStatus_t st;
+    if ((st = penc_dev_.reserve(d1.end + 256)) != HIPJPEG_STATUS_SUCCESS || (st = penc_pinned_.reserve(q.pin.up2 + 256)) != HIPJPEG_STATUS_SUCCESS)
+        return st;
+    for (size_t k = 0; k < ns; k++) {
+        PencScan& sc = q.scans[k];
+        sc.hist = sc.kind == kPencDcRefine ? nullptr : at<uint32_t>(penc_dev_, d1.hist + 1024 * k);
+        sc.codes = at<const uint32_t>(penc_dev_, d1.codes + 1024 * k);
+    }
+    copy_table(penc_pinned_, d1.scans, q.scans);
+    copy_table(penc_pinned_, d1.units, q.units);
+    copy_table(penc_pinned_, d1.ac, q.ac_scans);
+    copy_table(penc_pinned_, d1.segs, q.segs);
+    const PencScan* dscans = at<const PencScan>(penc_dev_, d1.scans);
+    uint8_t* dev = penc_dev_.data();
+    hipStream_t s = (hipStream_t)stream_;
+    if (hipMemcpyAsync(dev, penc_pinned_.data(), d1.codes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemsetAsync(dev + d1.hist, 0, 1024 * ns, s) != hipSuccess || hipMemsetAsync(dev + d1.pre, 0, 4 * nb, s) != hipSuccess ||
+        hipMemsetAsync(dev + d1.post, 0, 4 * nb, s) != hipSuccess ||
+        launch_penc_summary(dscans, at<const HencUnit>(penc_dev_, d1.units), (int)q.units.size(), dev + d1.sum, stream_) != 0 ||
+        launch_penc_runs(dscans, at<const uint32_t>(penc_dev_, d1.ac), (int)q.ac_scans.size(), dev + d1.sum, at<uint32_t>(penc_dev_, d1.pre),
+                         at<uint32_t>(penc_dev_, d1.post), at<uint32_t>(penc_dev_, d1.piece), at<uint32_t>(penc_dev_, d1.flusher),
+                         at<uint16_t>(penc_dev_, d1.rel), stream_) != 0 ||
+        hipMemcpyAsync(penc_pinned_.data() + q.pin.hist, dev + d1.hist, 1024 * ns, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    for (size_t g = 0; g + 1 < q.first_scan.size(); g++) {
+        const std::vector<ScanSpec> script = simple_progression(images_[q.idx[g]].geom.ncomp);
+        for (int k = q.first_scan[g]; k < q.first_scan[g + 1]; k++)
+            progressive_scan_header(script[k - q.first_scan[g]], at<const uint32_t>(penc_pinned_, q.pin.hist + 1024 * (size_t)k),
+                                    at<uint32_t>(penc_pinned_, d1.codes + 1024 * (size_t)k), &q.headers[k]);
+    }
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+// Phase 1: the code tables up; block lengths, their prefix sums per scan, and every scan's total bits back.
+hipjpegStatus_t EncodeBatch::penc_lengths(PencPlan& q)
+{
+    const PencLayout1& d1 = q.d1;
+    const int ns = (int)q.scans.size();
+    hipStream_t s = (hipStream_t)stream_;
+    if (hipMemcpyAsync(penc_dev_.data() + d1.codes, penc_pinned_.data() + d1.codes, d1.hist - d1.codes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_penc_length(at<const PencScan>(penc_dev_, d1.scans), at<const HencUnit>(penc_dev_, d1.units), (int)q.units.size(),
+                           at<const uint32_t>(penc_dev_, d1.pre), at<const uint32_t>(penc_dev_, d1.post), at<uint16_t>(penc_dev_, d1.own),
+                           at<uint16_t>(penc_dev_, d1.bits), stream_) != 0 ||
+        launch_henc_scan(at<const HencImage>(penc_dev_, d1.segs), ns, at<const uint16_t>(penc_dev_, d1.bits), at<uint32_t>(penc_dev_, d1.off),
+                         at<uint32_t>(penc_dev_, d1.totals), stream_) != 0 ||
+        hipMemcpyAsync(penc_pinned_.data() + q.pin.totals, penc_dev_.data() + d1.totals, (size_t)ns * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+// From the total bits: every segment's bit buffer, stuffing chunks, header slot; worst-case file sizes.
+void EncodeBatch::penc_chunks(PencPlan& q)
+{
+    const size_t ns = q.scans.size();
+    const uint32_t* totals = at<const uint32_t>(penc_pinned_, q.pin.totals);
+    Carve raw, hdr;
+    q.raw_off.resize(ns);
+    q.hdr_off.resize(ns);
+    for (size_t k = 0; k < ns; k++) {
+        HencImage& h = q.segs[k];
+        h.raw_bytes = (totals[k] + 7) / 8;
+        h.first_chunk = (uint32_t)q.chunk_units.size();
+        h.num_chunks = (h.raw_bytes + kHencChunk - 1) / kHencChunk;
+        for (uint32_t c = 0; c < h.num_chunks; c++) q.chunk_units.push_back(HencUnit{(uint32_t)k, c});
+        h.header_bytes = (uint32_t)q.headers[k].size();
+        q.raw_off[k] = raw.take((size_t)h.raw_bytes + 16);
+        q.hdr_off[k] = hdr.take(q.headers[k].size(), 16);
+        q.arena_cap += (size_t)h.header_bytes + 2 * (size_t)h.raw_bytes + (h.last_seg ? 2 + 15 : 0);  // every byte could be 0xFF
+    }
+    q.raw_total = raw.take(0);
+    q.hdr_total = hdr.take(0, 16);
+}
+
+// Phase 2: bit buffers, stuffing and assembly of the segments into files, as henc_assemble does for baseline files.
+hipjpegStatus_t EncodeBatch::penc_assemble(PencPlan& q, bool* direct)
+{
+    const int ns = (int)q.scans.size();
+    const size_t nchunks = q.chunk_units.size();
+    HencLayout2& d2 = q.d2;
+    const PencLayout1& d1 = q.d1;
+    Carve c;
+    d2.desc = c.take(sizeof(HencImage) * (size_t)ns);
+    d2.units = c.take(sizeof(HencUnit) * nchunks);
+    d2.headers = c.take(q.hdr_total);
+    d2.ff = c.take(nchunks * 4);
+    d2.out = c.take(nchunks * 4);
+    d2.len = c.take((size_t)ns * 4);
+    d2.foff = c.take((size_t)ns * 8);
+    d2.raw = c.take(q.raw_total);
+    d2.arena = c.take(q.arena_cap);
+    d2.end = c.end;
+    q.pin = penc_pinned_layout(d1, ns, d2.upload());
+    hipjpegStatus_t st;
+    if ((st = penc_dev2_.reserve(d2.end + 256)) != HIPJPEG_STATUS_SUCCESS || (st = penc_pinned_.reserve(q.pin.end + 256)) != HIPJPEG_STATUS_SUCCESS)
+        return st;
+    for (int k = 0; k < ns; k++) {
+        q.segs[k].raw = penc_dev2_.data() + d2.raw + q.raw_off[k];
+        q.segs[k].header = penc_dev2_.data() + d2.headers + q.hdr_off[k];
+        copy_table(penc_pinned_, q.pin.up2 + d2.headers + q.hdr_off[k], q.headers[k]);
+    }
+    copy_table(penc_pinned_, q.pin.up2 + d2.desc, q.segs);
+    copy_table(penc_pinned_, q.pin.up2 + d2.units, q.chunk_units);
+    *direct = penc_out_.reserve(q.arena_cap + 256) == HIPJPEG_STATUS_SUCCESS && !penc_out_.custom();
+    const HencImage* dsegs = at<const HencImage>(penc_dev2_, d2.desc);
+    const HencUnit* dchunks = at<const HencUnit>(penc_dev2_, d2.units);
+    uint32_t *chunk_ff = at<uint32_t>(penc_dev2_, d2.ff), *chunk_out = at<uint32_t>(penc_dev2_, d2.out), *len = at<uint32_t>(penc_dev2_, d2.len);
+    unsigned long long* foff = at<unsigned long long>(penc_dev2_, d2.foff);
+    const PencBlockArrays a{at<const uint8_t>(penc_dev_, d1.sum),     at<const uint32_t>(penc_dev_, d1.pre),     at<const uint32_t>(penc_dev_, d1.post),
+                            at<const uint32_t>(penc_dev_, d1.piece),  at<const uint32_t>(penc_dev_, d1.flusher), at<const uint16_t>(penc_dev_, d1.rel),
+                            at<const uint16_t>(penc_dev_, d1.own),    at<const uint16_t>(penc_dev_, d1.bits),    at<const uint32_t>(penc_dev_, d1.off)};
+    hipStream_t s = (hipStream_t)stream_;
+    if (hipMemcpyAsync(penc_dev2_.data(), penc_pinned_.data() + q.pin.up2, d2.upload(), hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_henc_zero(penc_dev2_.data() + d2.raw, q.raw_total, stream_) != 0 ||
+        launch_penc_write(at<const PencScan>(penc_dev_, d1.scans), dsegs, at<const HencUnit>(penc_dev_, d1.units), (int)q.units.size(), a, stream_) != 0 ||
+        launch_henc_count(dsegs, dchunks, (int)nchunks, chunk_ff, stream_) != 0 || launch_henc_layout(dsegs, ns, chunk_ff, chunk_out, len, foff, stream_) != 0 ||
+        launch_henc_expand(dsegs, dchunks, (int)nchunks, chunk_out, len, foff, *direct ? penc_out_.data() : penc_dev2_.data() + d2.arena, stream_) != 0 ||
+        hipMemcpyAsync(penc_pinned_.data() + q.pin.len, len, (size_t)ns * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(penc_pinned_.data() + q.pin.foff, foff, (size_t)ns * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+// The files' places in penc_out_: a file starts at its first segment and runs over all of them.
+hipjpegStatus_t EncodeBatch::penc_collect(PencPlan& q, bool direct)
+{
+    const int ns = (int)q.scans.size();
+    const uint32_t* len = at<const uint32_t>(penc_pinned_, q.pin.len);
+    const unsigned long long* foff = at<const unsigned long long>(penc_pinned_, q.pin.foff);
+    const size_t used = (size_t)foff[ns - 1] + align_up((size_t)len[ns - 1], 16);
+    if (used > q.arena_cap) return HIPJPEG_STATUS_HIP_ERROR;  // cannot happen: the capacity assumes every byte is stuffed
+    if (!direct) {
+        hipjpegStatus_t st;
+        if ((st = penc_out_.reserve(used + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
+        if (hipMemcpyAsync(penc_out_.data(), penc_dev2_.data() + q.d2.arena, used, hipMemcpyDeviceToHost, (hipStream_t)stream_) != hipSuccess ||
+            hipStreamSynchronize((hipStream_t)stream_) != hipSuccess)
+            return HIPJPEG_STATUS_HIP_ERROR;
+    }
+    for (size_t g = 0; g < q.idx.size(); g++) {
+        size_t flen = 0;
+        for (int k = q.first_scan[g]; k < q.first_scan[g + 1]; k++) flen += len[k];
+        images_[q.idx[g]].gpu_bitstream = penc_out_.data() + foff[q.first_scan[g]];
+        images_[q.idx[g]].gpu_bitstream_len = flen;
+    }
+    gpu_entropy_images_ += (uint64_t)q.idx.size();
     return HIPJPEG_STATUS_SUCCESS;
 }
 

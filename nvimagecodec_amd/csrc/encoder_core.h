@@ -46,7 +46,7 @@ public:
     // Coefficients D2H (on the stream used by device_stage), wait.
     hipjpegStatus_t fetch_coefficients();
     // Decides who entropy-codes each planned image: with gpu_huffman the GPU coder (blocking) takes every image it can -- Annex-K
-    // or optimized tables, no restart markers, no progressive scans -- and the rest is flagged for the host coder (every planned
+    // or optimized tables or progressive output, no restart markers -- and the rest is flagged for the host coder (every planned
     // image without gpu_huffman).  Fetches the coefficients when the host coder has anything to do.
     hipjpegStatus_t route_entropy(bool gpu_huffman);
     // Host coder: Huffman + markers for image i when route_entropy() left it to the host; otherwise nothing.  Thread-safe for distinct i.
@@ -92,8 +92,9 @@ private:
     // ---- gpu_entropy_stage(): two short host round trips (after the length scan: the bit-buffer sizes; after the layout: the
     // file sizes), everything else queued on the stream the forward kernel ran on
     struct HencPlan;  // what the phases hand on
+    struct PencPlan;  // the same for progressive output
     hipjpegStatus_t gpu_entropy_stage();
-    void henc_choose(HencPlan& p);
+    void henc_choose(HencPlan& p, PencPlan& q);
     void henc_describe(HencPlan& p);
     hipjpegStatus_t henc_stage_phase1(HencPlan& p);
     hipjpegStatus_t henc_histograms(HencPlan& p);
@@ -102,6 +103,15 @@ private:
     hipjpegStatus_t henc_assemble(HencPlan& p, bool* direct);
     hipjpegStatus_t henc_collect(HencPlan& p, bool direct);
     Buffer henc_dev_, henc_dev2_, henc_pinned_, henc_out_;
+    // progressive output (progressive_encode.h): one more host round trip than baseline -- the symbol counts of every scan, for
+    // the per-scan optimal tables -- and one segment (tables, SOS, data) per scan in the files
+    void penc_describe(PencPlan& q);
+    hipjpegStatus_t penc_statistics(PencPlan& q);
+    hipjpegStatus_t penc_lengths(PencPlan& q);
+    void penc_chunks(PencPlan& q);
+    hipjpegStatus_t penc_assemble(PencPlan& q, bool* direct);
+    hipjpegStatus_t penc_collect(PencPlan& q, bool direct);
+    Buffer penc_dev_, penc_dev2_, penc_pinned_, penc_out_;
     uint64_t gpu_entropy_images_ = 0;
 };
 

@@ -395,10 +395,7 @@ namespace {
 // libjpeg's progressive Huffman coder (jcphuff.c) over the scan script of jcparam.c jpeg_simple_progression, with the
 // per-scan optimal tables libjpeg forces in progressive mode (jcmaster.c: optimize_coding = TRUE).
 
-struct ScanSpec {
-    int ncomp, comp[3];
-    int ss, se, ah, al;
-};
+}  // namespace
 
 // jcparam.c jpeg_simple_progression: the 10-scan script for YCbCr, the all-purpose 6-scan script for one component
 std::vector<ScanSpec> simple_progression(int ncomp)
@@ -433,6 +430,8 @@ std::vector<ScanSpec> simple_progression(int ncomp)
     }
     return v;
 }
+
+namespace {
 
 // One scan, either counting symbols (bw == null) or emitting them.  State and routine names follow jcphuff.c.
 class ProgressiveScanCoder {
@@ -641,6 +640,40 @@ private:
     uint8_t corr_[kMaxCorrBits];
 };
 
+// Optimal tables of the scan's table slots from their counts, and their DHT segments (jcmarker.c write_scan_header: the tables this
+// scan uses, in component order, each once).  Not for DC refinement scans, which use no table.
+void scan_tables(const ScanSpec& sc, long counts[2][257], HuffTable tables[2], std::vector<uint8_t>* o)
+{
+    bool used[2] = {false, false};
+    for (int k = 0; k < sc.ncomp; k++) used[sc.comp[k] == 0 ? 0 : 1] = true;
+    for (int t = 0; t < 2; t++)
+        if (used[t]) gen_optimal_table(counts[t], &tables[t]);
+    bool sent[2] = {false, false};
+    for (int k = 0; k < sc.ncomp; k++) {
+        const int t = sc.comp[k] == 0 ? 0 : 1;
+        if (sent[t]) continue;
+        sent[t] = true;
+        write_dht(o, (sc.ss == 0 ? 0x00 : 0x10) | t, tables[t]);
+    }
+}
+
+void write_sos(const ScanSpec& sc, std::vector<uint8_t>* o)
+{
+    const bool dc_scan = sc.ss == 0;
+    put16(o, 0xFFDA);
+    put16(o, 6 + 2 * sc.ncomp);
+    o->push_back((uint8_t)sc.ncomp);
+    for (int k = 0; k < sc.ncomp; k++) {
+        const int c = sc.comp[k], t = c == 0 ? 0 : 1;
+        o->push_back((uint8_t)(c + 1));
+        // only the table a scan uses is named: DC first scans Td, AC scans Ta, DC refinement neither
+        o->push_back((uint8_t)(dc_scan ? (sc.ah == 0 ? t << 4 : 0) : t));
+    }
+    o->push_back((uint8_t)sc.ss);
+    o->push_back((uint8_t)sc.se);
+    o->push_back((uint8_t)((sc.ah << 4) | sc.al));
+}
+
 void encode_progressive(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], const int16_t* const coef[3],
                         int restart_interval, std::vector<uint8_t>* o)
 {
@@ -648,25 +681,13 @@ void encode_progressive(const EncodeGeometry& g, const uint16_t qlum[64], const 
     BlockSource src{g, coef};
     write_frame_header(g, qlum, qchr, 0xFFC2, o);
     for (const ScanSpec& sc : simple_progression(g.ncomp)) {
-        const bool dc_scan = sc.ss == 0;
-        const bool needs_table = !(dc_scan && sc.ah != 0);
+        const bool needs_table = !(sc.ss == 0 && sc.ah != 0);
         HuffTable tables[2];
-        bool used[2] = {false, false};
         if (needs_table) {
             long counts[2][257];
             memset(counts, 0, sizeof counts);
             ProgressiveScanCoder(g, src, sc, restart_interval, nullptr, nullptr, counts).run();
-            for (int k = 0; k < sc.ncomp; k++) used[sc.comp[k] == 0 ? 0 : 1] = true;
-            for (int t = 0; t < 2; t++)
-                if (used[t]) gen_optimal_table(counts[t], &tables[t]);
-            // jcmarker.c write_scan_header: the tables this scan uses, in component order, each once
-            bool sent[2] = {false, false};
-            for (int k = 0; k < sc.ncomp; k++) {
-                const int t = sc.comp[k] == 0 ? 0 : 1;
-                if (sent[t]) continue;
-                sent[t] = true;
-                write_dht(o, (dc_scan ? 0x00 : 0x10) | t, tables[t]);
-            }
+            scan_tables(sc, counts, tables, o);
         }
         if (restart_interval && !dri_sent) {  // write_scan_header: DRI whenever the interval changes, i.e. once
             put16(o, 0xFFDD);
@@ -674,18 +695,7 @@ void encode_progressive(const EncodeGeometry& g, const uint16_t qlum[64], const 
             put16(o, restart_interval);
             dri_sent = true;
         }
-        put16(o, 0xFFDA);
-        put16(o, 6 + 2 * sc.ncomp);
-        o->push_back((uint8_t)sc.ncomp);
-        for (int k = 0; k < sc.ncomp; k++) {
-            const int c = sc.comp[k], t = c == 0 ? 0 : 1;
-            o->push_back((uint8_t)(c + 1));
-            // only the table a scan uses is named: DC first scans Td, AC scans Ta, DC refinement neither
-            o->push_back((uint8_t)(dc_scan ? (sc.ah == 0 ? t << 4 : 0) : t));
-        }
-        o->push_back((uint8_t)sc.ss);
-        o->push_back((uint8_t)sc.se);
-        o->push_back((uint8_t)((sc.ah << 4) | sc.al));
+        write_sos(sc, o);
         BitWriter bw(o);
         ProgressiveScanCoder(g, src, sc, restart_interval, &bw, tables, nullptr).run();
     }
@@ -693,6 +703,32 @@ void encode_progressive(const EncodeGeometry& g, const uint16_t qlum[64], const 
 }
 
 }  // namespace
+
+void write_progressive_frame_header(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out)
+{
+    write_frame_header(g, qlum, qchr, 0xFFC2, out);
+}
+
+void progressive_scan_header(const ScanSpec& sc, const uint32_t counts[256], uint32_t codes[256], std::vector<uint8_t>* out)
+{
+    if (sc.ss != 0 || sc.ah == 0) {
+        const bool dc_scan = sc.ss == 0;
+        long freq[2][257];
+        memset(freq, 0, sizeof freq);
+        for (int t = 0; t < 2; t++)
+            for (int s = 0; s < (dc_scan ? 16 : 256); s++) freq[t][s] = (long)counts[dc_scan ? t * 16 + s : s];
+        if (!dc_scan)  // an AC scan holds one component: its counts belong to that component's slot
+            for (int s = 0; s < 256; s++) freq[sc.comp[0] == 0 ? 1 : 0][s] = 0;
+        HuffTable tables[2];
+        scan_tables(sc, freq, tables, out);
+        for (int t = 0; t < 2; t++)
+            for (int s = 0; s < (dc_scan ? 16 : 256); s++) {
+                const int k = dc_scan ? t * 16 + s : s;
+                if (dc_scan || t == (sc.comp[0] == 0 ? 0 : 1)) codes[k] = tables[t].code[s] | ((uint32_t)tables[t].size[s] << 16);
+            }
+    }
+    write_sos(sc, out);
+}
 
 void write_standard_headers(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out)
 {

@@ -50,4 +50,19 @@ void optimal_code_tables(const uint32_t counts[2][2][256], const EncodeGeometry&
                          StandardCodeTables* t, std::vector<uint8_t>* headers);
 void write_standard_headers(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out);
 
+// ---- progressive output on the GPU coder (progressive_encode.hip): the host coder's scan script, frame header and per-scan tables
+// One scan of a progressive script: components (indices), spectral band ss..se, successive approximation ah / al.
+struct ScanSpec {
+    int ncomp, comp[3];
+    int ss, se, ah, al;
+};
+// jcparam.c jpeg_simple_progression: the 10-scan script for YCbCr, the all-purpose 6-scan script for one component.
+std::vector<ScanSpec> simple_progression(int ncomp);
+// SOI, APP0, DQT.., SOF2 -- what precedes the first scan's tables.
+void write_progressive_frame_header(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out);
+// One scan's optimal table(s) from its symbol counts, and its DHT segments and SOS as the host coder writes them (no DRI).  Layout of
+// `counts` and `codes` (code | length << 16): DC first scans [t * 16 + category] (t = 0 luma, 1 chroma); AC scans [run/size symbol].
+// DC refinement scans use no table: counts are ignored and `codes` is left alone.
+void progressive_scan_header(const ScanSpec& sc, const uint32_t counts[256], uint32_t codes[256], std::vector<uint8_t>* out);
+
 }  // namespace hipjpeg

@@ -36,6 +36,10 @@ struct alignas(16) HencImage {
     uint32_t raw_bytes, header_bytes;
     uint32_t first_chunk;    // index of the image's first chunk in the batch-wide per-chunk arrays
     uint32_t num_chunks;
+    // A file is a list of segments (header + stuffed bit buffer), consecutive descriptors laid out back to back: baseline output has
+    // one, progressive output one per scan.  nseg = the number of segments of the file this descriptor starts (0: a later segment of
+    // a file); last_seg = 1 for the file's last segment, which EOI follows.
+    uint32_t nseg, last_seg;
     // optimized Huffman tables (nvimgcodecJpegEncodeParams_t::optimized_huffman, reference extensions/nvjpeg/cuda_encoder.cpp:348-357):
     // hist = where the histogram kernel adds this image's symbol counts ([2][2][256] uint32: table, DC / AC, symbol), null for images
     // coded with the Annex-K tables; tables = the image's own code tables once the host has built them from the counts (null: the

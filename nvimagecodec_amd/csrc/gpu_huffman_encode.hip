@@ -443,8 +443,9 @@ __global__ __launch_bounds__(kThreads) void henc_count_kernel(const HencImage* _
     if (threadIdx.x == 0) chunk_ff[im.first_chunk + u.first] = total;
 }
 
-// One workgroup in total.  Per image: chunk_out[c] = 0xFF bytes in the chunks before c; final_len = header + data + stuffed
-// zeros + EOI; final_off = files packed back to back at 16-byte boundaries.
+// One workgroup in total.  Per segment: chunk_out[c] = 0xFF bytes in the chunks before c; final_len = header + data + stuffed
+// zeros (+ EOI behind a file's last segment); final_off = the segments of a file back to back, files at 16-byte boundaries.  A lane
+// lays out the files that start in its range of descriptors.
 __global__ __launch_bounds__(kThreads) void henc_layout_kernel(const HencImage* __restrict__ images, int nimages, const uint32_t* __restrict__ chunk_ff,
                                                                uint32_t* __restrict__ chunk_out, uint32_t* __restrict__ final_len,
                                                                unsigned long long* __restrict__ final_off)
@@ -453,16 +454,20 @@ __global__ __launch_bounds__(kThreads) void henc_layout_kernel(const HencImage* 
     const int per = (nimages + kThreads - 1) / kThreads;
     const int lo = min(nimages, (int)threadIdx.x * per), hi = min(nimages, lo + per);
     unsigned long long sum = 0;
-    for (int i = lo; i < hi; i++) {
-        const HencImage& im = images[i];
-        uint32_t ff = 0;
-        for (uint32_t c = 0; c < im.num_chunks; c++) {
-            chunk_out[im.first_chunk + c] = ff;
-            ff += chunk_ff[im.first_chunk + c];
+    for (int f = lo; f < hi; f++) {
+        uint32_t flen = 0;
+        for (int i = f; i < f + (int)images[f].nseg; i++) {
+            const HencImage& im = images[i];
+            uint32_t ff = 0;
+            for (uint32_t c = 0; c < im.num_chunks; c++) {
+                chunk_out[im.first_chunk + c] = ff;
+                ff += chunk_ff[im.first_chunk + c];
+            }
+            const uint32_t len = im.header_bytes + im.raw_bytes + ff + (im.last_seg ? 2u : 0u);
+            final_len[i] = len;
+            flen += len;
         }
-        const uint32_t len = im.header_bytes + im.raw_bytes + ff + 2;
-        final_len[i] = len;
-        sum += (len + 15) & ~15u;
+        sum += (flen + 15) & ~15u;
     }
     s_sum[threadIdx.x] = sum;
     __syncthreads();
@@ -473,9 +478,13 @@ __global__ __launch_bounds__(kThreads) void henc_layout_kernel(const HencImage* 
         __syncthreads();
     }
     unsigned long long run = threadIdx.x ? s_sum[threadIdx.x - 1] : 0;
-    for (int i = lo; i < hi; i++) {
-        final_off[i] = run;
-        run += (final_len[i] + 15) & ~15u;
+    for (int f = lo; f < hi; f++) {
+        uint32_t flen = 0;
+        for (int i = f; i < f + (int)images[f].nseg; i++) {
+            final_off[i] = run + flen;
+            flen += final_len[i];
+        }
+        run += (flen + 15) & ~15u;
     }
 }
 
@@ -536,7 +545,7 @@ __global__ __launch_bounds__(kThreads) void henc_expand_kernel(const HencImage* 
     }
     if (u.first == 0)
         for (uint32_t i = t; i < im.header_bytes; i += kThreads) file[i] = im.header[i];
-    if (u.first + 1 == im.num_chunks && t == 0) {
+    if (im.last_seg && u.first + 1 == im.num_chunks && t == 0) {
         const uint32_t flen = final_len[u.image];
         file[flen - 2] = 0xFF;
         file[flen - 1] = 0xD9;

@@ -12,6 +12,7 @@
 #include "encoder_core.h"
 #include "entropy_decode.h"
 #include "gpu_huffman_host.h"
+#include "progressive_encode.h"
 #include "progressive_gpu_host.h"
 #include "thread_pool.h"
 
@@ -690,6 +691,27 @@ hipjpegStatus_t hipjpegEncodeFromCoefficientsHost(int32_t width, int32_t height,
         if (!coef[c]) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     std::vector<uint8_t> bytes;
     encode_jfif(g, ql, qc, coef, entropy_options(*params), &bytes);
+    *length = bytes.size();
+    if (!out || capacity < bytes.size()) return HIPJPEG_STATUS_BUFFER_TOO_SMALL;
+    memcpy(out, bytes.data(), bytes.size());
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+hipjpegStatus_t hipjpegEncodeFromCoefficientsGpuAlgorithmHost(int32_t width, int32_t height, const hipjpegEncodeParams_t* params,
+                                                              const int16_t* const coef[3], uint8_t* out, size_t capacity, size_t* length)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!params || !coef || !length || width < 1 || height < 1 || width > 65535 || height > 65535) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    EncodeGeometry g;
+    uint16_t ql[64], qc[64];
+    hipjpegStatus_t st = picture_setup(*params, width, height, &g, ql, qc);
+    if (st != HIPJPEG_STATUS_SUCCESS) return st;
+    for (int c = 0; c < g.ncomp; c++)
+        if (!coef[c]) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (!params->progressive || params->restart_interval != 0) return HIPJPEG_STATUS_UNSUPPORTED;  // what the GPU coder's progressive path takes
+    std::vector<uint8_t> bytes;
+    encode_progressive_gpu_algorithm(g, ql, qc, coef, &bytes);
     *length = bytes.size();
     if (!out || capacity < bytes.size()) return HIPJPEG_STATUS_BUFFER_TOO_SMALL;
     memcpy(out, bytes.data(), bytes.size());

@@ -127,7 +127,7 @@ private:
     MemoryHooks hooks_;
     int device_;
     bool ok_ = false;
-    bool gpu_huffman_ = true;       // entropy-code on the GPU what it can take (Annex-K tables, no restart markers)
+    bool gpu_huffman_ = true;       // entropy-code on the GPU what it can take (Annex-K or optimized tables, or progressive output; no restart markers)
     hipStream_t stream_ = nullptr;
     hipEvent_t event_ = nullptr;
     std::unique_ptr<EncodeBatch> batch_;

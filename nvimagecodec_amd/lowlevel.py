@@ -341,20 +341,34 @@ def _enc_params(subsampling, quality, input_format="rgb", restart_interval=0, op
                           int(bool(progressive)))
 
 
-def encode_from_coefficients_host(width, height, coefs_natural, subsampling="420", quality=90, restart_interval=0, optimized_huffman=False,
-                                  progressive=False):
-    """Host-only entropy coding (no GPU).  coefs_natural: per component int16 [blocks_h, blocks_w, 64] in natural order over the
-    MCU-padded grid (what oracle.forward returns); converted to the zigzag layout the C-ABI takes."""
+def _encode_coefficients(entry, width, height, coefs_natural, subsampling, quality, restart_interval, optimized_huffman, progressive):
     zz = [np.ascontiguousarray(c[:, :, _ZIGZAG]) for c in coefs_natural]
     ptrs = (ctypes.c_void_p * 3)(*([z.ctypes.data for z in zz] + [None] * (3 - len(zz))))
     p = _enc_params(subsampling, quality, "rgb", restart_interval, optimized_huffman, progressive)
     cap = width * height * 3 + 65536
     out = np.zeros(cap, dtype=np.uint8)
     n = ctypes.c_size_t()
-    st = N.load().hipjpegEncodeFromCoefficientsHost(width, height, ctypes.byref(p), ptrs, out.ctypes.data, cap, ctypes.byref(n))
+    st = getattr(N.load(), entry)(width, height, ctypes.byref(p), ptrs, out.ctypes.data, cap, ctypes.byref(n))
     if st:
-        raise N.HipJpegError(st, "hipjpegEncodeFromCoefficientsHost")
+        raise N.HipJpegError(st, entry)
     return out[: n.value].tobytes()
+
+
+def encode_from_coefficients_host(width, height, coefs_natural, subsampling="420", quality=90, restart_interval=0, optimized_huffman=False,
+                                  progressive=False):
+    """Host-only entropy coding (no GPU).  coefs_natural: per component int16 [blocks_h, blocks_w, 64] in natural order over the
+    MCU-padded grid (what oracle.forward returns); converted to the zigzag layout the C-ABI takes."""
+    return _encode_coefficients("hipjpegEncodeFromCoefficientsHost", width, height, coefs_natural, subsampling, quality, restart_interval,
+                                optimized_huffman, progressive)
+
+
+def encode_from_coefficients_gpu_algorithm_host(width, height, coefs_natural, subsampling="420", quality=90, restart_interval=0,
+                                                progressive=True):
+    """The GPU entropy coder's progressive algorithm run on the host with the kernels' per-block code (no GPU): the file
+    encode_from_coefficients_host(..., progressive=True) writes.  Raises HipJpegError (UNSUPPORTED) for baseline output and restart
+    intervals, which the GPU coder's progressive path does not take."""
+    return _encode_coefficients("hipjpegEncodeFromCoefficientsGpuAlgorithmHost", width, height, coefs_natural, subsampling, quality,
+                                restart_interval, False, progressive)
 
 
 class BatchEncoder:
