@@ -394,13 +394,23 @@ __global__ __launch_bounds__(kThreads) void destuff_compact_kernel(HuffImage* __
     const uint32_t a = gout & 3;                 // the LDS image shares the destination's misalignment
 
     // raw chunk -> LDS (the raw copy is padded to 16 bytes with a neutral value and 16 more: whole 16-byte pieces are readable)
+    // The loads go out unconditionally from clamped indices, all of a lane's four in flight together, and the pieces behind the
+    // chunk's end are replaced afterwards (a test around each load made every one of them wait for its own latency).
     {
-        const uint32_t readable = (chunk_len + 15) / 16 * 4;  // dwords
-        const HJ_GLOBAL uint32_t* src = (const HJ_GLOBAL uint32_t*)(im.raw + chunk_begin);
+        const uint32_t pieces = (chunk_len + 15) / 16;  // chunk_len >= 1: 16-byte pieces, at raw offsets that are multiples of 16
+        const HJ_GLOBAL u32x4* src = (const HJ_GLOBAL u32x4*)(im.raw + chunk_begin);
+        constexpr uint32_t kPiecesPerLane = kDestuffChunk / 16 / kThreads;
+        u32x4 v[kPiecesPerLane];
 #pragma unroll
-        for (uint32_t i = 0; i < kDestuffChunk / 4 / kThreads; i++) {
-            const uint32_t g = i * kThreads + t;
-            buf[g + (g >> 4)] = g < readable ? src[g] : 0x01010101u;
+        for (uint32_t i = 0; i < kPiecesPerLane; i++) v[i] = src[min(i * kThreads + t, pieces - 1)];
+#pragma unroll
+        for (uint32_t i = 0; i < kPiecesPerLane; i++) {
+            const uint32_t q = i * kThreads + t, g = q * 4 + (q >> 2);  // dwords 4q .. 4q + 3 share their padding
+            const u32x4 x = q < pieces ? v[i] : u32x4{0x01010101u, 0x01010101u, 0x01010101u, 0x01010101u};
+            buf[g] = x.x;
+            buf[g + 1] = x.y;
+            buf[g + 2] = x.z;
+            buf[g + 3] = x.w;
         }
     }
     const uint32_t before_chunk = chunk_begin > 0 ? im.raw[chunk_begin - 1] : 0u;                    // (lane 0's predecessor byte)
@@ -1078,7 +1088,9 @@ __global__ __launch_bounds__(kSyncThreads) void huff_pos_kernel(HuffImage* __res
 // kHuffMcusPerWg consecutive MCUs (scan order) of one image per workgroup, 256 blocks per round.  Every lane decodes
 // its block into a 128-byte LDS buffer, and the finished blocks leave as whole 128-byte lines, eight lanes per block --
 // each line written once, no memset, no partial-line traffic.  Lanes idle once their block is done: chroma blocks are
-// short, luma blocks long; the wave runs as long as its longest block.
+// short, luma blocks long; the wave runs as long as its longest block.  Block buffers, destination slots and the flush are a wave's
+// own (lane t flushes buffers of lanes t & ~63 ...), so between the rounds a wave only has to order its own LDS traffic: the waves
+// of a workgroup do not wait for each other's longest block.
 constexpr int kBThreads = kHuffBlocksPerWg;
 // Words of the bitstream a workgroup may stage in LDS.  0 (shipped): the lanes read the stream through the vector cache instead
 // -- a workgroup's span is ~7 KB and every word is needed by one or two neighbouring lanes, the prefetch in the bit reader covers
@@ -1198,11 +1210,20 @@ __global__ __launch_bounds__(kBThreads) void huff_blocks_kernel(HuffImage* __res
     env.kslot = (const HJ_LDS KSlot*)sh.kslot;
     env.zz = (const HJ_LDS uint8_t*)sh.zz;
     uint32_t err = 0;
+    // Between the steps of a round a wave waits for its own lanes only (wave_sync: LDS operations of a wave complete in order) --
+    // unless the stream is staged in LDS, which the whole workgroup fills and reads.
+    static_assert(kBThreads % 64 == 0, "whole waves: lane t flushes the buffers of lanes (t & ~63) ...");
+    auto round_sync = [] {
+        if (kBStreamWords == 0)
+            wave_sync();
+        else
+            __syncthreads();
+    };
     // Work items are ordered by MCU position first: item i is position i / mcus of MCU i % mcus, so that the 256 lanes of
     // a round hold blocks of the same component -- luma blocks run ~4x longer than chroma blocks, and a wave takes as long
     // as its longest block.
     for (uint32_t base = 0; base < items; base += kBThreads) {
-        __syncthreads();  // staged stream (first round) / zeroed buffers (later rounds) are in place
+        round_sync();  // staged stream (first round) / zeroed buffers (later rounds) are in place
         const uint32_t item = base + t;
         int16_t* dst = nullptr;
         if (item < items) {
@@ -1223,7 +1244,7 @@ __global__ __launch_bounds__(kBThreads) void huff_blocks_kernel(HuffImage* __res
             }
         }
         sh.dst[t] = dst;
-        __syncthreads();
+        round_sync();
         // eight lanes per block, 16 bytes each: every store instruction writes eight whole lines
 #pragma unroll
         for (int i = 0; i < 8; i++) {
@@ -1235,7 +1256,7 @@ __global__ __launch_bounds__(kBThreads) void huff_blocks_kernel(HuffImage* __res
             }
         }
         if (base + kBThreads < items) {
-            __syncthreads();
+            round_sync();
 #pragma unroll
             for (int i = 0; i < 8; i++) my_buf[i] = u32x4{0u, 0u, 0u, 0u};
         }
