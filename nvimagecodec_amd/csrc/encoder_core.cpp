@@ -69,8 +69,7 @@ EntropyEncodeOptions entropy_options(const hipjpegEncodeParams_t& p)
 
 EncodeBatch::EncodeBatch(int device_id, const MemoryHooks* hooks)
     : device_id_(device_id), pinned_desc_(Buffer::kPinned, hooks), device_(Buffer::kDevice, hooks), pinned_coef_(Buffer::kPinned, hooks),
-      henc_dev_(Buffer::kDevice, hooks), henc_dev2_(Buffer::kDevice, hooks), henc_pinned_(Buffer::kPinned, hooks), henc_out_(Buffer::kPinned, hooks),
-      penc_dev_(Buffer::kDevice, hooks), penc_dev2_(Buffer::kDevice, hooks), penc_pinned_(Buffer::kPinned, hooks), penc_out_(Buffer::kPinned, hooks)
+      henc_(hooks), penc_(hooks)
 {
 }
 
@@ -289,88 +288,67 @@ void EncodeBatch::entropy_stage(int i)
 
 // ---------------------------------------------------------------- GPU entropy coder
 namespace {
-// Phase-1 device arena (henc_dev_): descriptors | length units | standard tables | optimized tables [the upload, staged at the same
-// offsets at the start of henc_pinned_) | block bit lengths | block bit offsets | total bits | histograms
+// Baseline output.  Phase-1 device arena (henc_.dev): descriptors | length units | standard tables | optimized tables [the upload,
+// staged at the same offsets at the start of henc_.pinned) | block bit lengths | block bit offsets | total bits | histograms
 struct HencLayout1 {
     size_t desc, units, tables, opt_tables, bits, off, totals, hist, end;
     size_t upload() const { return bits; }
 };
-// henc_pinned_ behind the phase-1 upload: total bits | histograms | phase-2 upload (at the phase-2 arena's offsets) | lengths | offsets
-struct HencPinnedLayout { size_t totals, hist, up2, len, foff, end; };
-// Phase-2 device arena (henc_dev2_): descriptors | chunk units | headers [the upload) | 0xFF counts per chunk | chunk outputs | file
-// lengths | file offsets | bit buffers | files (unused when they go straight to henc_out_)
+// Progressive output (progressive_encode.h).  Phase-1 device arena (penc_.dev): scans | length units | AC scans | segment descriptors
+// [the upload, staged at the same offsets at the start of penc_.pinned) | code tables [uploaded after the statistics] | symbol counts |
+// per block: summaries, pre / post flushes, pieces, flushers, rel, own bits, bits, offsets | total bits per scan.
+struct PencLayout1 {
+    size_t scans, units, ac, segs, codes, hist, sum, pre, post, piece, flusher, rel, own, bits, off, totals, end;
+};
+// Either flavour's pinned arena behind what phase 1 stages in it: symbol counts | total bits per segment | segment lengths | segment
+// offsets | phase-2 upload (at the phase-2 arena's offsets; last, because its size follows from the total bits: `end` is set then)
+struct HencPinnedLayout { size_t hist, totals, len, foff, up2, end; };
+// Phase-2 device arena (dev2): segment descriptors | chunk units | headers [the upload) | 0xFF counts per chunk | chunk outputs |
+// segment lengths | segment offsets | bit buffers | files (unused when they go straight to `out`)
 struct HencLayout2 {
     size_t desc, units, headers, ff, out, len, foff, raw, arena, end;
     size_t upload() const { return ff; }
 };
 
-// From `len` on the pinned tail depends on the phase-2 upload: phase 1 lays it out with upload2 = 0 and reads totals, hist, up2.
-HencPinnedLayout henc_pinned_layout(const HencLayout1& d1, int ng, int nopt, size_t upload2)
+HencPinnedLayout henc_pinned_layout(size_t start, size_t hist_bytes, size_t nseg)
 {
-    Carve c{d1.upload()};
+    Carve c{start};
     HencPinnedLayout p;
-    p.totals = c.take((size_t)ng * 4);
-    p.hist = c.take(kHistBytes * (size_t)nopt);
-    p.up2 = c.take(upload2);
-    p.len = c.take((size_t)ng * 4);
-    p.foff = c.take((size_t)ng * 8);
-    p.end = c.end;
+    p.hist = c.take(hist_bytes);
+    p.totals = c.take(nseg * 4);
+    p.len = c.take(nseg * 4);
+    p.foff = c.take(nseg * 8);
+    p.up2 = p.end = c.take(0);
     return p;
 }
 }  // namespace
 
-struct EncodeBatch::HencPlan {
-    std::vector<int> idx;                      // images taken, in batch order
-    std::vector<HencImage> desc;               // their descriptors (device pointers inside)
-    std::vector<HencUnit> units, chunk_units;  // length / write units (256 blocks each); count / expand units (kHencChunk bytes each)
-    std::vector<int> opt_slot;                 // slot among the images with tables of their own (optimized_huffman), or -1
-    int nopt = 0;
-    size_t total_blocks = 0;                    // entries of the per-block arrays
-    std::vector<std::vector<uint8_t>> headers;  // SOI .. SOS of every file
-    std::vector<size_t> raw_off, hdr_off;       // offsets inside the bit-buffer area and the header area
+struct EncodeBatch::SegmentPlan {
+    std::vector<int> idx;                       // images taken, in batch order: one file each
+    std::vector<int> first_seg;                 // per file: index of its first segment (one more entry: the end)
+    std::vector<HencImage> segs;                // every segment of those files: the scan / count / layout / expand kernels' descriptors
+    std::vector<std::vector<uint8_t>> headers;  // per segment: baseline SOI .. SOS; progressive [frame header] DHT.. SOS
+    std::vector<HencUnit> chunk_units;          // count / expand units (kHencChunk bytes of one segment each)
+    std::vector<size_t> raw_off, hdr_off;       // per segment: offsets inside the bit-buffer area and the header area
     size_t raw_total = 0, hdr_total = 0, arena_cap = 0;
-    HencLayout1 d1{};
     HencPinnedLayout pin{};
     HencLayout2 d2{};
 };
 
-namespace {
-// Progressive output (progressive_encode.h).  Phase-1 device arena (penc_dev_): scans | length units | AC scans | segment descriptors
-// [the upload, staged at the same offsets at the start of penc_pinned_) | code tables [uploaded after the statistics] | symbol counts |
-// per block: summaries, pre / post flushes, pieces, flushers, rel, own bits, bits, offsets | total bits per scan.
-struct PencLayout1 {
-    size_t scans, units, ac, segs, codes, hist, sum, pre, post, piece, flusher, rel, own, bits, off, totals, end;
+struct EncodeBatch::HencPlan : SegmentPlan {
+    std::vector<HencUnit> units;  // length / write units (256 blocks each)
+    std::vector<int> opt_slot;    // slot among the images with tables of their own (optimized_huffman), or -1
+    int nopt = 0;
+    size_t total_blocks = 0;  // entries of the per-block arrays
+    HencLayout1 d1{};
 };
-// penc_pinned_ behind the code tables: symbol counts | total bits | phase-2 upload (at the phase-2 arena's offsets) | lengths | offsets
-struct PencPinnedLayout { size_t hist, totals, up2, len, foff, end; };
 
-PencPinnedLayout penc_pinned_layout(const PencLayout1& d1, int nscans, size_t upload2)
-{
-    Carve c{d1.hist};
-    PencPinnedLayout p;
-    p.hist = c.take((size_t)nscans * 1024);
-    p.totals = c.take((size_t)nscans * 4);
-    p.up2 = c.take(upload2);
-    p.len = c.take((size_t)nscans * 4);
-    p.foff = c.take((size_t)nscans * 8);
-    p.end = c.end;
-    return p;
-}
-}  // namespace
-
-struct EncodeBatch::PencPlan {
-    std::vector<int> idx;                      // images taken, in batch order
-    std::vector<int> first_scan;               // per image: index of its first scan (one more entry: the end)
-    std::vector<PencScan> scans;               // every scan of those images (device pointers inside)
-    std::vector<HencUnit> units, chunk_units;  // length / write units (256 blocks of one scan, image = scan); count / expand units
-    std::vector<uint32_t> ac_scans;            // scans with end-of-band runs
-    std::vector<HencImage> segs;               // one file segment per scan: the count / layout / expand kernels' descriptors
-    std::vector<std::vector<uint8_t>> headers;  // per scan: [frame header] DHT.. SOS
-    std::vector<size_t> raw_off, hdr_off;
-    size_t total_blocks = 0, raw_total = 0, hdr_total = 0, arena_cap = 0;
+struct EncodeBatch::PencPlan : SegmentPlan {
+    std::vector<PencScan> scans;     // every scan of the images taken, one per segment (device pointers inside)
+    std::vector<HencUnit> units;     // length / write units (256 blocks of one scan, image = scan)
+    std::vector<uint32_t> ac_scans;  // scans with end-of-band runs
+    size_t total_blocks = 0;
     PencLayout1 d1{};
-    PencPinnedLayout pin{};
-    HencLayout2 d2{};
 };
 
 hipjpegStatus_t EncodeBatch::gpu_entropy_stage()
@@ -382,20 +360,34 @@ hipjpegStatus_t EncodeBatch::gpu_entropy_stage()
     PencPlan q;
     henc_choose(p, q);
     hipjpegStatus_t st;
-    bool direct = false;
     if (!p.idx.empty()) {
+        const HencLayout1& d1 = p.d1;
+        const auto write = [&](const HencImage* dsegs) {
+            return launch_henc_write(dsegs, at<const HencUnit>(henc_.dev, d1.units), (int)p.units.size(), at<const StandardCodeTables>(henc_.dev, d1.tables),
+                                     at<const uint32_t>(henc_.dev, d1.off), at<const uint16_t>(henc_.dev, d1.bits), stream_);
+        };
+        bool direct = false;
         henc_describe(p);
         if ((st = henc_stage_phase1(p)) != HIPJPEG_STATUS_SUCCESS || (p.nopt > 0 && (st = henc_histograms(p)) != HIPJPEG_STATUS_SUCCESS) ||
             (st = henc_lengths(p)) != HIPJPEG_STATUS_SUCCESS)
             return st;
-        henc_chunks(p);
-        if ((st = henc_assemble(p, &direct)) != HIPJPEG_STATUS_SUCCESS || (st = henc_collect(p, direct)) != HIPJPEG_STATUS_SUCCESS) return st;
+        henc_chunks(p, henc_);
+        if ((st = henc_assemble(p, henc_, write, &direct)) != HIPJPEG_STATUS_SUCCESS || (st = henc_collect(p, henc_, direct)) != HIPJPEG_STATUS_SUCCESS) return st;
     }
     if (!q.idx.empty()) {
+        const PencLayout1& d1 = q.d1;
+        const auto write = [&](const HencImage* dsegs) {
+            const Buffer& dev = penc_.dev;
+            const PencBlockArrays a{at<const uint8_t>(dev, d1.sum),    at<const uint32_t>(dev, d1.pre),     at<const uint32_t>(dev, d1.post),
+                                    at<const uint32_t>(dev, d1.piece), at<const uint32_t>(dev, d1.flusher), at<const uint16_t>(dev, d1.rel),
+                                    at<const uint16_t>(dev, d1.own),   at<const uint16_t>(dev, d1.bits),    at<const uint32_t>(dev, d1.off)};
+            return launch_penc_write(at<const PencScan>(dev, d1.scans), dsegs, at<const HencUnit>(dev, d1.units), (int)q.units.size(), a, stream_);
+        };
+        bool direct = false;
         penc_describe(q);
         if ((st = penc_statistics(q)) != HIPJPEG_STATUS_SUCCESS || (st = penc_lengths(q)) != HIPJPEG_STATUS_SUCCESS) return st;
-        penc_chunks(q);
-        if ((st = penc_assemble(q, &direct)) != HIPJPEG_STATUS_SUCCESS || (st = penc_collect(q, direct)) != HIPJPEG_STATUS_SUCCESS) return st;
+        henc_chunks(q, penc_);
+        if ((st = henc_assemble(q, penc_, write, &direct)) != HIPJPEG_STATUS_SUCCESS || (st = henc_collect(q, penc_, direct)) != HIPJPEG_STATUS_SUCCESS) return st;
     }
     return HIPJPEG_STATUS_SUCCESS;
 }
@@ -417,13 +409,13 @@ void EncodeBatch::henc_choose(HencPlan& p, PencPlan& q)
 void EncodeBatch::henc_describe(HencPlan& p)
 {
     const int ng = (int)p.idx.size();
-    p.desc.resize(ng);
+    p.segs.resize(ng);
     p.opt_slot.assign(ng, -1);
     p.headers.resize(ng);
     for (int g = 0; g < ng; g++) {
         const PlannedEncode& im = images_[p.idx[g]];
         const EncodeGeometry& eg = im.geom;
-        HencImage& h = p.desc[g];
+        HencImage& h = p.segs[g];
         memset(&h, 0, sizeof h);
         for (int c = 0; c < eg.ncomp; c++) {
             h.coef[c] = desc_[p.idx[g]].coef[c];
@@ -439,14 +431,18 @@ void EncodeBatch::henc_describe(HencPlan& p)
         h.bpm = eg.ncomp == 3 ? (uint32_t)(eg.hs * eg.vs + 2) : 1u;
         h.total_blocks = h.mcus_x * h.mcus_y * h.bpm;
         h.first_block = (uint32_t)p.total_blocks;
+        h.nseg = 1;  // a baseline file is one segment
+        h.last_seg = 1;
+        p.first_seg.push_back(g);
         for (uint32_t b = 0; b < h.total_blocks; b += 256) p.units.push_back(HencUnit{(uint32_t)g, b});
         p.total_blocks += (h.total_blocks + 63) & ~(size_t)63;
         if (im.params.optimized_huffman) p.opt_slot[g] = p.nopt++;
         write_standard_headers(eg, im.qlum, im.qchr, &p.headers[g]);
     }
+    p.first_seg.push_back(ng);
 }
 
-// Lays out the phase-1 device arena and the start of henc_pinned_; stages descriptors, units and standard tables.
+// Lays out the phase-1 device arena and the start of henc_.pinned; stages descriptors, units and standard tables.
 hipjpegStatus_t EncodeBatch::henc_stage_phase1(HencPlan& p)
 {
     const int ng = (int)p.idx.size();
@@ -461,14 +457,14 @@ hipjpegStatus_t EncodeBatch::henc_stage_phase1(HencPlan& p)
     d1.totals = c.take((size_t)ng * 4);
     d1.hist = c.take(kHistBytes * (size_t)p.nopt);
     d1.end = c.take(0);
-    p.pin = henc_pinned_layout(d1, ng, p.nopt, 0);
-    // henc_pinned_ grows again in phase 2, after the totals have been read (reserve() keeps no contents)
+    p.pin = henc_pinned_layout(d1.upload(), kHistBytes * (size_t)p.nopt, (size_t)ng);
+    // henc_.pinned grows again in phase 2, after the totals have been read (reserve() keeps no contents)
     hipjpegStatus_t st;
-    if ((st = henc_dev_.reserve(d1.end + 256)) != HIPJPEG_STATUS_SUCCESS || (st = henc_pinned_.reserve(p.pin.up2 + 256)) != HIPJPEG_STATUS_SUCCESS)
+    if ((st = henc_.dev.reserve(d1.end + 256)) != HIPJPEG_STATUS_SUCCESS || (st = henc_.pinned.reserve(p.pin.up2 + 256)) != HIPJPEG_STATUS_SUCCESS)
         return st;
-    copy_table(henc_pinned_, d1.desc, p.desc);
-    copy_table(henc_pinned_, d1.units, p.units);
-    standard_code_tables(at<StandardCodeTables>(henc_pinned_, d1.tables));
+    copy_table(henc_.pinned, d1.desc, p.segs);
+    copy_table(henc_.pinned, d1.units, p.units);
+    standard_code_tables(at<StandardCodeTables>(henc_.pinned, d1.tables));
     return HIPJPEG_STATUS_SUCCESS;
 }
 
@@ -480,26 +476,26 @@ hipjpegStatus_t EncodeBatch::henc_histograms(HencPlan& p)
     const size_t hist_bytes = kHistBytes * (size_t)p.nopt;
     hipStream_t s = (hipStream_t)stream_;
     for (size_t g = 0; g < p.idx.size(); g++)
-        if (p.opt_slot[g] >= 0) p.desc[g].hist = at<uint32_t>(henc_dev_, d1.hist + kHistBytes * (size_t)p.opt_slot[g]);
-    copy_table(henc_pinned_, d1.desc, p.desc);
-    if (hipMemcpyAsync(henc_dev_.data(), henc_pinned_.data(), d1.opt_tables, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemsetAsync(henc_dev_.data() + d1.hist, 0, hist_bytes, s) != hipSuccess ||
-        launch_henc_hist(at<const HencImage>(henc_dev_, d1.desc), at<const HencUnit>(henc_dev_, d1.units), (int)p.units.size(), stream_) != 0 ||
-        hipMemcpyAsync(henc_pinned_.data() + p.pin.hist, henc_dev_.data() + d1.hist, hist_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        if (p.opt_slot[g] >= 0) p.segs[g].hist = at<uint32_t>(henc_.dev, d1.hist + kHistBytes * (size_t)p.opt_slot[g]);
+    copy_table(henc_.pinned, d1.desc, p.segs);
+    if (hipMemcpyAsync(henc_.dev.data(), henc_.pinned.data(), d1.opt_tables, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemsetAsync(henc_.dev.data() + d1.hist, 0, hist_bytes, s) != hipSuccess ||
+        launch_henc_hist(at<const HencImage>(henc_.dev, d1.desc), at<const HencUnit>(henc_.dev, d1.units), (int)p.units.size(), stream_) != 0 ||
+        hipMemcpyAsync(henc_.pinned.data() + p.pin.hist, henc_.dev.data() + d1.hist, hist_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;
     for (size_t g = 0; g < p.idx.size(); g++) {
         const int k = p.opt_slot[g];
         if (k < 0) continue;
         const PlannedEncode& im = images_[p.idx[g]];
-        const auto* counts = at<const uint32_t[2][256]>(henc_pinned_, p.pin.hist + kHistBytes * (size_t)k);
+        const auto* counts = at<const uint32_t[2][256]>(henc_.pinned, p.pin.hist + kHistBytes * (size_t)k);
         const size_t tables = d1.opt_tables + sizeof(StandardCodeTables) * (size_t)k;
         p.headers[g].clear();
-        optimal_code_tables(counts, im.geom, im.qlum, im.qchr, at<StandardCodeTables>(henc_pinned_, tables), &p.headers[g]);
-        p.desc[g].hist = nullptr;
-        p.desc[g].tables = at<const StandardCodeTables>(henc_dev_, tables);
+        optimal_code_tables(counts, im.geom, im.qlum, im.qchr, at<StandardCodeTables>(henc_.pinned, tables), &p.headers[g]);
+        p.segs[g].hist = nullptr;
+        p.segs[g].tables = at<const StandardCodeTables>(henc_.dev, tables);
     }
-    copy_table(henc_pinned_, d1.desc, p.desc);
+    copy_table(henc_.pinned, d1.desc, p.segs);
     return HIPJPEG_STATUS_SUCCESS;
 }
 
@@ -508,113 +504,15 @@ hipjpegStatus_t EncodeBatch::henc_lengths(HencPlan& p)
 {
     const HencLayout1& d1 = p.d1;
     const int ng = (int)p.idx.size();
-    const HencImage* dimg = at<const HencImage>(henc_dev_, d1.desc);
+    const HencImage* dimg = at<const HencImage>(henc_.dev, d1.desc);
     hipStream_t s = (hipStream_t)stream_;
-    if (hipMemcpyAsync(henc_dev_.data(), henc_pinned_.data(), d1.upload(), hipMemcpyHostToDevice, s) != hipSuccess ||
-        launch_henc_length(dimg, at<const HencUnit>(henc_dev_, d1.units), (int)p.units.size(), at<const StandardCodeTables>(henc_dev_, d1.tables),
-                           at<uint16_t>(henc_dev_, d1.bits), stream_) != 0 ||
-        launch_henc_scan(dimg, ng, at<const uint16_t>(henc_dev_, d1.bits), at<uint32_t>(henc_dev_, d1.off), at<uint32_t>(henc_dev_, d1.totals), stream_) != 0 ||
-        hipMemcpyAsync(henc_pinned_.data() + p.pin.totals, henc_dev_.data() + d1.totals, (size_t)ng * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+    if (hipMemcpyAsync(henc_.dev.data(), henc_.pinned.data(), d1.upload(), hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_henc_length(dimg, at<const HencUnit>(henc_.dev, d1.units), (int)p.units.size(), at<const StandardCodeTables>(henc_.dev, d1.tables),
+                           at<uint16_t>(henc_.dev, d1.bits), stream_) != 0 ||
+        launch_henc_scan(dimg, ng, at<const uint16_t>(henc_.dev, d1.bits), at<uint32_t>(henc_.dev, d1.off), at<uint32_t>(henc_.dev, d1.totals), stream_) != 0 ||
+        hipMemcpyAsync(henc_.pinned.data() + p.pin.totals, henc_.dev.data() + d1.totals, (size_t)ng * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;
-    return HIPJPEG_STATUS_SUCCESS;
-}
-
-// From the total bits: every image's bit buffer, stuffing chunks, header slot and worst-case file size.
-void EncodeBatch::henc_chunks(HencPlan& p)
-{
-    const int ng = (int)p.idx.size();
-    const uint32_t* totals = at<const uint32_t>(henc_pinned_, p.pin.totals);
-    Carve raw, hdr;  // the bit-buffer area and the header area of the phase-2 arena
-    p.raw_off.resize(ng);
-    p.hdr_off.resize(ng);
-    for (int g = 0; g < ng; g++) {
-        HencImage& h = p.desc[g];
-        h.raw_bytes = (totals[g] + ((8 - (totals[g] & 7)) & 7)) / 8;
-        h.first_chunk = (uint32_t)p.chunk_units.size();
-        h.num_chunks = (h.raw_bytes + kHencChunk - 1) / kHencChunk;
-        for (uint32_t c = 0; c < h.num_chunks; c++) p.chunk_units.push_back(HencUnit{(uint32_t)g, c});
-        h.header_bytes = (uint32_t)p.headers[g].size();
-        h.nseg = 1;  // a baseline file is one segment
-        h.last_seg = 1;
-        p.raw_off[g] = raw.take((size_t)h.raw_bytes + 16);
-        p.hdr_off[g] = hdr.take(p.headers[g].size(), 16);
-        p.arena_cap += align_up((size_t)h.header_bytes + 2 * (size_t)h.raw_bytes + 2, 16);  // every byte could be 0xFF
-    }
-    p.raw_total = raw.take(0);
-    p.hdr_total = hdr.take(0, 16);
-}
-
-// Phase 2: bit buffers, stuffing, file assembly; file lengths and offsets back.  The finished files go straight into pinned host
-// memory when it is ours (hipHostMalloc: mapped into the device's address space): the expand kernel's stores cross PCIe themselves
-// and no copy follows.  With a caller-supplied pinned allocator the mapping is unknown, so the files are assembled in HBM.
-hipjpegStatus_t EncodeBatch::henc_assemble(HencPlan& p, bool* direct)
-{
-    const int ng = (int)p.idx.size();
-    const size_t nchunks = p.chunk_units.size();
-    HencLayout2& d2 = p.d2;
-    Carve c;
-    d2.desc = c.take(sizeof(HencImage) * (size_t)ng);
-    d2.units = c.take(sizeof(HencUnit) * nchunks);
-    d2.headers = c.take(p.hdr_total);
-    d2.ff = c.take(nchunks * 4);
-    d2.out = c.take(nchunks * 4);
-    d2.len = c.take((size_t)ng * 4);
-    d2.foff = c.take((size_t)ng * 8);
-    d2.raw = c.take(p.raw_total);
-    d2.arena = c.take(p.arena_cap);
-    d2.end = c.end;
-    p.pin = henc_pinned_layout(p.d1, ng, p.nopt, d2.upload());
-    hipjpegStatus_t st;
-    if ((st = henc_dev2_.reserve(d2.end + 256)) != HIPJPEG_STATUS_SUCCESS || (st = henc_pinned_.reserve(p.pin.end + 256)) != HIPJPEG_STATUS_SUCCESS)
-        return st;
-    for (int g = 0; g < ng; g++) {
-        p.desc[g].raw = henc_dev2_.data() + d2.raw + p.raw_off[g];
-        p.desc[g].header = henc_dev2_.data() + d2.headers + p.hdr_off[g];
-        copy_table(henc_pinned_, p.pin.up2 + d2.headers + p.hdr_off[g], p.headers[g]);
-    }
-    copy_table(henc_pinned_, p.pin.up2 + d2.desc, p.desc);
-    copy_table(henc_pinned_, p.pin.up2 + d2.units, p.chunk_units);
-    *direct = henc_out_.reserve(p.arena_cap + 256) == HIPJPEG_STATUS_SUCCESS && !henc_out_.custom();
-    const HencImage* dimg = at<const HencImage>(henc_dev2_, d2.desc);
-    const HencUnit* dchunks = at<const HencUnit>(henc_dev2_, d2.units);
-    uint32_t *chunk_ff = at<uint32_t>(henc_dev2_, d2.ff), *chunk_out = at<uint32_t>(henc_dev2_, d2.out), *len = at<uint32_t>(henc_dev2_, d2.len);
-    unsigned long long* foff = at<unsigned long long>(henc_dev2_, d2.foff);
-    hipStream_t s = (hipStream_t)stream_;
-    if (hipMemcpyAsync(henc_dev2_.data(), henc_pinned_.data() + p.pin.up2, d2.upload(), hipMemcpyHostToDevice, s) != hipSuccess ||
-        launch_henc_zero(henc_dev2_.data() + d2.raw, p.raw_total, stream_) != 0 ||
-        launch_henc_write(dimg, at<const HencUnit>(henc_dev_, p.d1.units), (int)p.units.size(), at<const StandardCodeTables>(henc_dev_, p.d1.tables),
-                          at<const uint32_t>(henc_dev_, p.d1.off), at<const uint16_t>(henc_dev_, p.d1.bits), stream_) != 0 ||
-        launch_henc_count(dimg, dchunks, (int)nchunks, chunk_ff, stream_) != 0 ||
-        launch_henc_layout(dimg, ng, chunk_ff, chunk_out, len, foff, stream_) != 0 ||
-        launch_henc_expand(dimg, dchunks, (int)nchunks, chunk_out, len, foff, *direct ? henc_out_.data() : henc_dev2_.data() + d2.arena, stream_) != 0 ||
-        hipMemcpyAsync(henc_pinned_.data() + p.pin.len, len, (size_t)ng * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(henc_pinned_.data() + p.pin.foff, foff, (size_t)ng * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return HIPJPEG_STATUS_HIP_ERROR;
-    return HIPJPEG_STATUS_SUCCESS;
-}
-
-// The files' places in henc_out_ (copied down first when they were assembled in HBM).
-hipjpegStatus_t EncodeBatch::henc_collect(HencPlan& p, bool direct)
-{
-    const int ng = (int)p.idx.size();
-    const uint32_t* len = at<const uint32_t>(henc_pinned_, p.pin.len);
-    const unsigned long long* foff = at<const unsigned long long>(henc_pinned_, p.pin.foff);
-    const size_t used = (size_t)foff[ng - 1] + align_up((size_t)len[ng - 1], 16);
-    if (used > p.arena_cap) return HIPJPEG_STATUS_HIP_ERROR;  // cannot happen: the capacity assumes every byte is stuffed
-    if (!direct) {
-        hipjpegStatus_t st;
-        if ((st = henc_out_.reserve(used + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
-        if (hipMemcpyAsync(henc_out_.data(), henc_dev2_.data() + p.d2.arena, used, hipMemcpyDeviceToHost, (hipStream_t)stream_) != hipSuccess ||
-            hipStreamSynchronize((hipStream_t)stream_) != hipSuccess)
-            return HIPJPEG_STATUS_HIP_ERROR;
-    }
-    for (int g = 0; g < ng; g++) {
-        images_[p.idx[g]].gpu_bitstream = henc_out_.data() + foff[g];
-        images_[p.idx[g]].gpu_bitstream_len = len[g];
-    }
-    gpu_entropy_images_ += (uint64_t)ng;
     return HIPJPEG_STATUS_SUCCESS;
 }
 
@@ -627,7 +525,7 @@ void EncodeBatch::penc_describe(PencPlan& q)
         const PlannedEncode& im = images_[q.idx[g]];
         const int16_t* coef[3] = {desc_[q.idx[g]].coef[0], desc_[q.idx[g]].coef[1], desc_[q.idx[g]].coef[2]};
         const size_t s0 = q.scans.size();
-        q.first_scan.push_back((int)s0);
+        q.first_seg.push_back((int)s0);
         q.total_blocks += hipjpeg::penc_describe(im.geom, coef, q.total_blocks, &q.scans);
         for (size_t k = s0; k < q.scans.size(); k++) {
             const PencScan& sc = q.scans[k];
@@ -644,7 +542,7 @@ void EncodeBatch::penc_describe(PencPlan& q)
         }
         write_progressive_frame_header(im.geom, im.qlum, im.qchr, &q.headers[s0]);
     }
-    q.first_scan.push_back((int)q.scans.size());
+    q.first_seg.push_back((int)q.scans.size());
 }
 
 // Phase 0: descriptors up; block summaries, run resolution and the symbol counts of every scan on the device; the counts back in one
@@ -671,37 +569,37 @@ hipjpegStatus_t EncodeBatch::penc_statistics(PencPlan& q)
     d1.off = c.take(4 * nb);
     d1.totals = c.take(4 * ns);
     d1.end = c.take(0);
-    q.pin = penc_pinned_layout(d1, (int)ns, 0);
+    q.pin = henc_pinned_layout(d1.hist, 1024 * ns, ns);
     hipjpegStatus_t st;
-    if ((st = penc_dev_.reserve(d1.end + 256)) != HIPJPEG_STATUS_SUCCESS || (st = penc_pinned_.reserve(q.pin.up2 + 256)) != HIPJPEG_STATUS_SUCCESS)
+    if ((st = penc_.dev.reserve(d1.end + 256)) != HIPJPEG_STATUS_SUCCESS || (st = penc_.pinned.reserve(q.pin.up2 + 256)) != HIPJPEG_STATUS_SUCCESS)
         return st;
     for (size_t k = 0; k < ns; k++) {
         PencScan& sc = q.scans[k];
-        sc.hist = sc.kind == kPencDcRefine ? nullptr : at<uint32_t>(penc_dev_, d1.hist + 1024 * k);
-        sc.codes = at<const uint32_t>(penc_dev_, d1.codes + 1024 * k);
+        sc.hist = sc.kind == kPencDcRefine ? nullptr : at<uint32_t>(penc_.dev, d1.hist + 1024 * k);
+        sc.codes = at<const uint32_t>(penc_.dev, d1.codes + 1024 * k);
     }
-    copy_table(penc_pinned_, d1.scans, q.scans);
-    copy_table(penc_pinned_, d1.units, q.units);
-    copy_table(penc_pinned_, d1.ac, q.ac_scans);
-    copy_table(penc_pinned_, d1.segs, q.segs);
-    const PencScan* dscans = at<const PencScan>(penc_dev_, d1.scans);
-    uint8_t* dev = penc_dev_.data();
+    copy_table(penc_.pinned, d1.scans, q.scans);
+    copy_table(penc_.pinned, d1.units, q.units);
+    copy_table(penc_.pinned, d1.ac, q.ac_scans);
+    copy_table(penc_.pinned, d1.segs, q.segs);
+    const PencScan* dscans = at<const PencScan>(penc_.dev, d1.scans);
+    uint8_t* dev = penc_.dev.data();
     hipStream_t s = (hipStream_t)stream_;
-    if (hipMemcpyAsync(dev, penc_pinned_.data(), d1.codes, hipMemcpyHostToDevice, s) != hipSuccess ||
+    if (hipMemcpyAsync(dev, penc_.pinned.data(), d1.codes, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemsetAsync(dev + d1.hist, 0, 1024 * ns, s) != hipSuccess || hipMemsetAsync(dev + d1.pre, 0, 4 * nb, s) != hipSuccess ||
         hipMemsetAsync(dev + d1.post, 0, 4 * nb, s) != hipSuccess ||
-        launch_penc_summary(dscans, at<const HencUnit>(penc_dev_, d1.units), (int)q.units.size(), dev + d1.sum, stream_) != 0 ||
-        launch_penc_runs(dscans, at<const uint32_t>(penc_dev_, d1.ac), (int)q.ac_scans.size(), dev + d1.sum, at<uint32_t>(penc_dev_, d1.pre),
-                         at<uint32_t>(penc_dev_, d1.post), at<uint32_t>(penc_dev_, d1.piece), at<uint32_t>(penc_dev_, d1.flusher),
-                         at<uint16_t>(penc_dev_, d1.rel), stream_) != 0 ||
-        hipMemcpyAsync(penc_pinned_.data() + q.pin.hist, dev + d1.hist, 1024 * ns, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        launch_penc_summary(dscans, at<const HencUnit>(penc_.dev, d1.units), (int)q.units.size(), dev + d1.sum, stream_) != 0 ||
+        launch_penc_runs(dscans, at<const uint32_t>(penc_.dev, d1.ac), (int)q.ac_scans.size(), dev + d1.sum, at<uint32_t>(penc_.dev, d1.pre),
+                         at<uint32_t>(penc_.dev, d1.post), at<uint32_t>(penc_.dev, d1.piece), at<uint32_t>(penc_.dev, d1.flusher),
+                         at<uint16_t>(penc_.dev, d1.rel), stream_) != 0 ||
+        hipMemcpyAsync(penc_.pinned.data() + q.pin.hist, dev + d1.hist, 1024 * ns, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;
-    for (size_t g = 0; g + 1 < q.first_scan.size(); g++) {
+    for (size_t g = 0; g + 1 < q.first_seg.size(); g++) {
         const std::vector<ScanSpec> script = simple_progression(images_[q.idx[g]].geom.ncomp);
-        for (int k = q.first_scan[g]; k < q.first_scan[g + 1]; k++)
-            progressive_scan_header(script[k - q.first_scan[g]], at<const uint32_t>(penc_pinned_, q.pin.hist + 1024 * (size_t)k),
-                                    at<uint32_t>(penc_pinned_, d1.codes + 1024 * (size_t)k), &q.headers[k]);
+        for (int k = q.first_seg[g]; k < q.first_seg[g + 1]; k++)
+            progressive_scan_header(script[k - q.first_seg[g]], at<const uint32_t>(penc_.pinned, q.pin.hist + 1024 * (size_t)k),
+                                    at<uint32_t>(penc_.pinned, d1.codes + 1024 * (size_t)k), &q.headers[k]);
     }
     return HIPJPEG_STATUS_SUCCESS;
 }
@@ -712,113 +610,118 @@ hipjpegStatus_t EncodeBatch::penc_lengths(PencPlan& q)
     const PencLayout1& d1 = q.d1;
     const int ns = (int)q.scans.size();
     hipStream_t s = (hipStream_t)stream_;
-    if (hipMemcpyAsync(penc_dev_.data() + d1.codes, penc_pinned_.data() + d1.codes, d1.hist - d1.codes, hipMemcpyHostToDevice, s) != hipSuccess ||
-        launch_penc_length(at<const PencScan>(penc_dev_, d1.scans), at<const HencUnit>(penc_dev_, d1.units), (int)q.units.size(),
-                           at<const uint32_t>(penc_dev_, d1.pre), at<const uint32_t>(penc_dev_, d1.post), at<uint16_t>(penc_dev_, d1.own),
-                           at<uint16_t>(penc_dev_, d1.bits), stream_) != 0 ||
-        launch_henc_scan(at<const HencImage>(penc_dev_, d1.segs), ns, at<const uint16_t>(penc_dev_, d1.bits), at<uint32_t>(penc_dev_, d1.off),
-                         at<uint32_t>(penc_dev_, d1.totals), stream_) != 0 ||
-        hipMemcpyAsync(penc_pinned_.data() + q.pin.totals, penc_dev_.data() + d1.totals, (size_t)ns * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+    if (hipMemcpyAsync(penc_.dev.data() + d1.codes, penc_.pinned.data() + d1.codes, d1.hist - d1.codes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_penc_length(at<const PencScan>(penc_.dev, d1.scans), at<const HencUnit>(penc_.dev, d1.units), (int)q.units.size(),
+                           at<const uint32_t>(penc_.dev, d1.pre), at<const uint32_t>(penc_.dev, d1.post), at<uint16_t>(penc_.dev, d1.own),
+                           at<uint16_t>(penc_.dev, d1.bits), stream_) != 0 ||
+        launch_henc_scan(at<const HencImage>(penc_.dev, d1.segs), ns, at<const uint16_t>(penc_.dev, d1.bits), at<uint32_t>(penc_.dev, d1.off),
+                         at<uint32_t>(penc_.dev, d1.totals), stream_) != 0 ||
+        hipMemcpyAsync(penc_.pinned.data() + q.pin.totals, penc_.dev.data() + d1.totals, (size_t)ns * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;
     return HIPJPEG_STATUS_SUCCESS;
 }
 
-// From the total bits: every segment's bit buffer, stuffing chunks, header slot; worst-case file sizes.
-void EncodeBatch::penc_chunks(PencPlan& q)
+// ---------------------------------------------------------------- GPU entropy coder, phase 2 of either flavour
+// From the total bits: every segment's bit buffer, stuffing chunks and header slot, and the capacity of the file arena.
+void EncodeBatch::henc_chunks(SegmentPlan& p, const HencArenas& a)
 {
-    const size_t ns = q.scans.size();
-    const uint32_t* totals = at<const uint32_t>(penc_pinned_, q.pin.totals);
-    Carve raw, hdr;
-    q.raw_off.resize(ns);
-    q.hdr_off.resize(ns);
-    for (size_t k = 0; k < ns; k++) {
-        HencImage& h = q.segs[k];
-        h.raw_bytes = (totals[k] + 7) / 8;
-        h.first_chunk = (uint32_t)q.chunk_units.size();
-        h.num_chunks = (h.raw_bytes + kHencChunk - 1) / kHencChunk;
-        for (uint32_t c = 0; c < h.num_chunks; c++) q.chunk_units.push_back(HencUnit{(uint32_t)k, c});
-        h.header_bytes = (uint32_t)q.headers[k].size();
-        q.raw_off[k] = raw.take((size_t)h.raw_bytes + 16);
-        q.hdr_off[k] = hdr.take(q.headers[k].size(), 16);
-        q.arena_cap += (size_t)h.header_bytes + 2 * (size_t)h.raw_bytes + (h.last_seg ? 2 + 15 : 0);  // every byte could be 0xFF
+    const uint32_t* totals = at<const uint32_t>(a.pinned, p.pin.totals);
+    Carve raw, hdr;  // the bit-buffer area and the header area of the phase-2 arena
+    p.raw_off.resize(p.segs.size());
+    p.hdr_off.resize(p.segs.size());
+    for (size_t f = 0; f < p.idx.size(); f++) {
+        size_t file_bytes = 2;  // EOI
+        for (int k = p.first_seg[f]; k < p.first_seg[f + 1]; k++) {
+            HencImage& h = p.segs[k];
+            h.raw_bytes = (totals[k] + 7) / 8;
+            h.first_chunk = (uint32_t)p.chunk_units.size();
+            h.num_chunks = (h.raw_bytes + kHencChunk - 1) / kHencChunk;
+            for (uint32_t c = 0; c < h.num_chunks; c++) p.chunk_units.push_back(HencUnit{(uint32_t)k, c});
+            h.header_bytes = (uint32_t)p.headers[k].size();
+            p.raw_off[k] = raw.take((size_t)h.raw_bytes + 16);
+            p.hdr_off[k] = hdr.take(p.headers[k].size(), 16);
+            file_bytes += (size_t)h.header_bytes + 2 * (size_t)h.raw_bytes;  // every byte could be 0xFF
+        }
+        // as henc_layout_kernel places them: a file's segments back to back, every file at a 16-byte boundary
+        p.arena_cap += align_up(file_bytes, 16);
     }
-    q.raw_total = raw.take(0);
-    q.hdr_total = hdr.take(0, 16);
+    p.raw_total = raw.take(0);
+    p.hdr_total = hdr.take(0, 16);
 }
 
-// Phase 2: bit buffers, stuffing and assembly of the segments into files, as henc_assemble does for baseline files.
-hipjpegStatus_t EncodeBatch::penc_assemble(PencPlan& q, bool* direct)
+// Phase 2: bit buffers (`write`: the flavour's kernel that fills them), stuffing, assembly of the segments into files; segment
+// lengths and offsets back.  The finished files go straight into pinned host memory when it is ours (hipHostMalloc: mapped into the
+// device's address space): the expand kernel's stores cross PCIe themselves and no copy follows.  With a caller-supplied pinned
+// allocator the mapping is unknown, so the files are assembled in HBM.
+template <class Write>
+hipjpegStatus_t EncodeBatch::henc_assemble(SegmentPlan& p, HencArenas& a, Write write, bool* direct)
 {
-    const int ns = (int)q.scans.size();
-    const size_t nchunks = q.chunk_units.size();
-    HencLayout2& d2 = q.d2;
-    const PencLayout1& d1 = q.d1;
+    const int ns = (int)p.segs.size();
+    const size_t nchunks = p.chunk_units.size();
+    HencLayout2& d2 = p.d2;
     Carve c;
     d2.desc = c.take(sizeof(HencImage) * (size_t)ns);
     d2.units = c.take(sizeof(HencUnit) * nchunks);
-    d2.headers = c.take(q.hdr_total);
+    d2.headers = c.take(p.hdr_total);
     d2.ff = c.take(nchunks * 4);
     d2.out = c.take(nchunks * 4);
     d2.len = c.take((size_t)ns * 4);
     d2.foff = c.take((size_t)ns * 8);
-    d2.raw = c.take(q.raw_total);
-    d2.arena = c.take(q.arena_cap);
+    d2.raw = c.take(p.raw_total);
+    d2.arena = c.take(p.arena_cap);
     d2.end = c.end;
-    q.pin = penc_pinned_layout(d1, ns, d2.upload());
+    p.pin.end = p.pin.up2 + d2.upload();
     hipjpegStatus_t st;
-    if ((st = penc_dev2_.reserve(d2.end + 256)) != HIPJPEG_STATUS_SUCCESS || (st = penc_pinned_.reserve(q.pin.end + 256)) != HIPJPEG_STATUS_SUCCESS)
-        return st;
+    if ((st = a.dev2.reserve(d2.end + 256)) != HIPJPEG_STATUS_SUCCESS || (st = a.pinned.reserve(p.pin.end + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
     for (int k = 0; k < ns; k++) {
-        q.segs[k].raw = penc_dev2_.data() + d2.raw + q.raw_off[k];
-        q.segs[k].header = penc_dev2_.data() + d2.headers + q.hdr_off[k];
-        copy_table(penc_pinned_, q.pin.up2 + d2.headers + q.hdr_off[k], q.headers[k]);
+        p.segs[k].raw = a.dev2.data() + d2.raw + p.raw_off[k];
+        p.segs[k].header = a.dev2.data() + d2.headers + p.hdr_off[k];
+        copy_table(a.pinned, p.pin.up2 + d2.headers + p.hdr_off[k], p.headers[k]);
     }
-    copy_table(penc_pinned_, q.pin.up2 + d2.desc, q.segs);
-    copy_table(penc_pinned_, q.pin.up2 + d2.units, q.chunk_units);
-    *direct = penc_out_.reserve(q.arena_cap + 256) == HIPJPEG_STATUS_SUCCESS && !penc_out_.custom();
-    const HencImage* dsegs = at<const HencImage>(penc_dev2_, d2.desc);
-    const HencUnit* dchunks = at<const HencUnit>(penc_dev2_, d2.units);
-    uint32_t *chunk_ff = at<uint32_t>(penc_dev2_, d2.ff), *chunk_out = at<uint32_t>(penc_dev2_, d2.out), *len = at<uint32_t>(penc_dev2_, d2.len);
-    unsigned long long* foff = at<unsigned long long>(penc_dev2_, d2.foff);
-    const PencBlockArrays a{at<const uint8_t>(penc_dev_, d1.sum),     at<const uint32_t>(penc_dev_, d1.pre),     at<const uint32_t>(penc_dev_, d1.post),
-                            at<const uint32_t>(penc_dev_, d1.piece),  at<const uint32_t>(penc_dev_, d1.flusher), at<const uint16_t>(penc_dev_, d1.rel),
-                            at<const uint16_t>(penc_dev_, d1.own),    at<const uint16_t>(penc_dev_, d1.bits),    at<const uint32_t>(penc_dev_, d1.off)};
+    copy_table(a.pinned, p.pin.up2 + d2.desc, p.segs);
+    copy_table(a.pinned, p.pin.up2 + d2.units, p.chunk_units);
+    *direct = a.out.reserve(p.arena_cap + 256) == HIPJPEG_STATUS_SUCCESS && !a.out.custom();
+    const HencImage* dsegs = at<const HencImage>(a.dev2, d2.desc);
+    const HencUnit* dchunks = at<const HencUnit>(a.dev2, d2.units);
+    uint32_t *chunk_ff = at<uint32_t>(a.dev2, d2.ff), *chunk_out = at<uint32_t>(a.dev2, d2.out), *len = at<uint32_t>(a.dev2, d2.len);
+    unsigned long long* foff = at<unsigned long long>(a.dev2, d2.foff);
     hipStream_t s = (hipStream_t)stream_;
-    if (hipMemcpyAsync(penc_dev2_.data(), penc_pinned_.data() + q.pin.up2, d2.upload(), hipMemcpyHostToDevice, s) != hipSuccess ||
-        launch_henc_zero(penc_dev2_.data() + d2.raw, q.raw_total, stream_) != 0 ||
-        launch_penc_write(at<const PencScan>(penc_dev_, d1.scans), dsegs, at<const HencUnit>(penc_dev_, d1.units), (int)q.units.size(), a, stream_) != 0 ||
-        launch_henc_count(dsegs, dchunks, (int)nchunks, chunk_ff, stream_) != 0 || launch_henc_layout(dsegs, ns, chunk_ff, chunk_out, len, foff, stream_) != 0 ||
-        launch_henc_expand(dsegs, dchunks, (int)nchunks, chunk_out, len, foff, *direct ? penc_out_.data() : penc_dev2_.data() + d2.arena, stream_) != 0 ||
-        hipMemcpyAsync(penc_pinned_.data() + q.pin.len, len, (size_t)ns * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(penc_pinned_.data() + q.pin.foff, foff, (size_t)ns * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+    if (hipMemcpyAsync(a.dev2.data(), a.pinned.data() + p.pin.up2, d2.upload(), hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_henc_zero(a.dev2.data() + d2.raw, p.raw_total, stream_) != 0 || write(dsegs) != 0 ||
+        launch_henc_count(dsegs, dchunks, (int)nchunks, chunk_ff, stream_) != 0 ||
+        launch_henc_layout(dsegs, ns, chunk_ff, chunk_out, len, foff, stream_) != 0 ||
+        launch_henc_expand(dsegs, dchunks, (int)nchunks, chunk_out, len, foff, *direct ? a.out.data() : a.dev2.data() + d2.arena, stream_) != 0 ||
+        hipMemcpyAsync(a.pinned.data() + p.pin.len, len, (size_t)ns * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(a.pinned.data() + p.pin.foff, foff, (size_t)ns * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;
     return HIPJPEG_STATUS_SUCCESS;
 }
 
-// The files' places in penc_out_: a file starts at its first segment and runs over all of them.
-hipjpegStatus_t EncodeBatch::penc_collect(PencPlan& q, bool direct)
+// The files' places in `out` (copied down first when they were assembled in HBM): a file starts at its first segment and runs
+// over all of them.
+hipjpegStatus_t EncodeBatch::henc_collect(SegmentPlan& p, HencArenas& a, bool direct)
 {
-    const int ns = (int)q.scans.size();
-    const uint32_t* len = at<const uint32_t>(penc_pinned_, q.pin.len);
-    const unsigned long long* foff = at<const unsigned long long>(penc_pinned_, q.pin.foff);
-    const size_t used = (size_t)foff[ns - 1] + align_up((size_t)len[ns - 1], 16);
-    if (used > q.arena_cap) return HIPJPEG_STATUS_HIP_ERROR;  // cannot happen: the capacity assumes every byte is stuffed
+    const uint32_t* len = at<const uint32_t>(a.pinned, p.pin.len);
+    const unsigned long long* foff = at<const unsigned long long>(a.pinned, p.pin.foff);
+    size_t used = 0;  // the end of the last file, padded as henc_layout_kernel pads it
+    for (size_t f = 0; f < p.idx.size(); f++) {
+        PlannedEncode& im = images_[p.idx[f]];
+        im.gpu_bitstream_len = 0;
+        for (int k = p.first_seg[f]; k < p.first_seg[f + 1]; k++) im.gpu_bitstream_len += len[k];
+        used = (size_t)foff[p.first_seg[f]] + align_up(im.gpu_bitstream_len, 16);
+    }
+    if (used > p.arena_cap) return HIPJPEG_STATUS_HIP_ERROR;  // cannot happen: the capacity assumes every byte is stuffed
     if (!direct) {
         hipjpegStatus_t st;
-        if ((st = penc_out_.reserve(used + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
-        if (hipMemcpyAsync(penc_out_.data(), penc_dev2_.data() + q.d2.arena, used, hipMemcpyDeviceToHost, (hipStream_t)stream_) != hipSuccess ||
+        if ((st = a.out.reserve(used + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
+        if (hipMemcpyAsync(a.out.data(), a.dev2.data() + p.d2.arena, used, hipMemcpyDeviceToHost, (hipStream_t)stream_) != hipSuccess ||
             hipStreamSynchronize((hipStream_t)stream_) != hipSuccess)
             return HIPJPEG_STATUS_HIP_ERROR;
     }
-    for (size_t g = 0; g < q.idx.size(); g++) {
-        size_t flen = 0;
-        for (int k = q.first_scan[g]; k < q.first_scan[g + 1]; k++) flen += len[k];
-        images_[q.idx[g]].gpu_bitstream = penc_out_.data() + foff[q.first_scan[g]];
-        images_[q.idx[g]].gpu_bitstream_len = flen;
-    }
-    gpu_entropy_images_ += (uint64_t)q.idx.size();
+    for (size_t f = 0; f < p.idx.size(); f++) images_[p.idx[f]].gpu_bitstream = a.out.data() + foff[p.first_seg[f]];
+    gpu_entropy_images_ += (uint64_t)p.idx.size();
     return HIPJPEG_STATUS_SUCCESS;
 }
 

@@ -89,29 +89,38 @@ private:
     std::vector<char> host_coder_;
     int host_images_ = 0;
 
-    // ---- gpu_entropy_stage(): two short host round trips (after the length scan: the bit-buffer sizes; after the layout: the
-    // file sizes), everything else queued on the stream the forward kernel ran on
-    struct HencPlan;  // what the phases hand on
-    struct PencPlan;  // the same for progressive output
+    // ---- gpu_entropy_stage(): a file is a run of segments (header bytes, then entropy-coded data): a baseline file is one
+    // segment, a progressive file one per scan.  Phase 1 is the flavour's own and ends with every segment's total bits on the
+    // host; phase 2 (henc_chunks, henc_assemble, henc_collect) is shared, runs once per flavour that has images and ends with the
+    // file sizes on the host.  Everything else is queued on the stream the forward kernel ran on.
+    struct SegmentPlan;  // what phase 1 hands to phase 2
+    struct HencPlan;     // SegmentPlan and what phase 1 of baseline output hands on
+    struct PencPlan;     // the same for progressive output
+    // One flavour's memory: phase-1 and phase-2 device arenas, pinned staging, and the finished files.  The files of one flavour
+    // stay in `out` while the other flavour's images of the same batch are coded.
+    struct HencArenas {
+        explicit HencArenas(const MemoryHooks* hooks)
+            : dev(Buffer::kDevice, hooks), dev2(Buffer::kDevice, hooks), pinned(Buffer::kPinned, hooks), out(Buffer::kPinned, hooks) {}
+        Buffer dev, dev2, pinned, out;
+    };
     hipjpegStatus_t gpu_entropy_stage();
     void henc_choose(HencPlan& p, PencPlan& q);
+    // baseline output, Annex-K or optimized tables: one host round trip more when any image wants tables of its own
     void henc_describe(HencPlan& p);
     hipjpegStatus_t henc_stage_phase1(HencPlan& p);
     hipjpegStatus_t henc_histograms(HencPlan& p);
     hipjpegStatus_t henc_lengths(HencPlan& p);
-    void henc_chunks(HencPlan& p);
-    hipjpegStatus_t henc_assemble(HencPlan& p, bool* direct);
-    hipjpegStatus_t henc_collect(HencPlan& p, bool direct);
-    Buffer henc_dev_, henc_dev2_, henc_pinned_, henc_out_;
-    // progressive output (progressive_encode.h): one more host round trip than baseline -- the symbol counts of every scan, for
-    // the per-scan optimal tables -- and one segment (tables, SOS, data) per scan in the files
+    // progressive output (progressive_encode.h): always that round trip -- the symbol counts of every scan, for the per-scan
+    // optimal tables -- and a segment's header is the scan's tables and SOS
     void penc_describe(PencPlan& q);
     hipjpegStatus_t penc_statistics(PencPlan& q);
     hipjpegStatus_t penc_lengths(PencPlan& q);
-    void penc_chunks(PencPlan& q);
-    hipjpegStatus_t penc_assemble(PencPlan& q, bool* direct);
-    hipjpegStatus_t penc_collect(PencPlan& q, bool direct);
-    Buffer penc_dev_, penc_dev2_, penc_pinned_, penc_out_;
+    // phase 2; `write` queues the flavour's kernel that fills the segments' bit buffers
+    void henc_chunks(SegmentPlan& p, const HencArenas& a);
+    template <class Write>
+    hipjpegStatus_t henc_assemble(SegmentPlan& p, HencArenas& a, Write write, bool* direct);
+    hipjpegStatus_t henc_collect(SegmentPlan& p, HencArenas& a, bool direct);
+    HencArenas henc_, penc_;
     uint64_t gpu_entropy_images_ = 0;
 };
 

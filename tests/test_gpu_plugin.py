@@ -386,6 +386,14 @@ def test_encoder_with_custom_allocators_assembles_files_in_hbm(torch_mod):
         want = plain.encode([api.as_image(d) for d in dev], "jpeg", opt)
     assert all(b is not None and len(b) < len(oracle.encode(im, "420", 90)) for im, b in zip(imgs, out))
     assert out == want
+    # progressive output: the same assembly, one segment per scan
+    prog = api.EncodeParams(quality=90, chroma_subsampling=api.ChromaSubsampling.CSS_420,
+                            jpeg_encode_params=api.JpegEncodeParams(progressive=True))
+    out = enc.encode([api.as_image(d) for d in dev], "jpeg", prog)
+    with api.Encoder(max_num_cpu_threads=2) as plain:
+        want = plain.encode([api.as_image(d) for d in dev], "jpeg", prog)
+    assert all(b is not None and b"\xff\xc2" in b[:700] for b in out)
+    assert out == want
     assert calls["dev"] >= 1 and calls["pin"] >= 1
     enc.close()
     assert calls["devfree"] == calls["dev"] and calls["pinfree"] == calls["pin"]
