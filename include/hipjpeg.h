@@ -73,7 +73,8 @@ typedef enum {
                                             intervals; progressive SOF2 with up to 24 scans); the host then only finds the scans.  Other
                                             streams keep the host entropy stage.  Encoding: entropy-code on the GPU every image without a
                                             restart interval -- baseline with Annex-K or optimized tables, or progressive output -- see
-                                            hipjpegEncodeBatchEntropy. */
+                                            hipjpegEncodeBatchEntropy; images with a restart interval stay with the host coder unless
+                                            HIPJPEG_FLAG_GPU_RESTART_INTERVALS is set too. */
 #define HIPJPEG_FLAG_FAST_IDCT 4u        /* the fast integer IDCT (plugin option hipjpeg_decoder:fast_idct=1; the reference's fast_idct, which
                                             selects JDCT_IFAST): the pixels are those of libjpeg-turbo's x86-64 SIMD routine
                                             jsimd_idct_ifast_sse2, which differs from jidctfst.c only on streams whose samples leave the
@@ -247,6 +248,10 @@ typedef struct {
                                   with per-scan optimal tables, what nvimgcodecJpegImageInfo_t::encoding = PROGRESSIVE_DCT_HUFFMAN asks
                                   for (reference extensions/nvjpeg/cuda_encoder.cpp:339-346) */
 } hipjpegEncodeParams_t;
+#define HIPJPEG_FLAG_GPU_RESTART_INTERVALS 8u /* encoding, together with HIPJPEG_FLAG_GPU_HUFFMAN in hipjpegEncodeBatchEntropy and
+                                            hipjpegEncodeBatchSubmit: the GPU coder also takes baseline images (Annex-K or optimized tables)
+                                            whose restart_interval is not 0.  Progressive output with a restart interval stays with the host
+                                            coder.  No meaning alone; the decode entry points ignore it. */
 
 /* Device stage only: colour conversion + downsampling + FDCT + quantization for the whole batch (asynchronous). */
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchDevice(hipjpegHandle_t handle, const hipjpegEncodeInput_t* inputs,
@@ -259,8 +264,11 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchHost(hipjpegHandle_t handle, hipjp
  * Annex-K tables, or optimized ones (histograms on the device, jpeg_gen_optimal_table on the host, second pass on the device), and
  * progressive output (per-block summaries and the EOB-run resolution on the device, per-scan optimal tables on the host, then one
  * segment per scan; byte-identical to the host coder's SOF2 files); then lengths, prefix sums, bit packing, byte stuffing, file
- * assembly -- only finished JPEG files cross PCIe.  Restart intervals (which the reference's encode parameters do not have), and
- * everything when flags = 0, go through the host coder as in hipjpegEncodeBatchHost.  Blocking. */
+ * assembly -- only finished JPEG files cross PCIe.  Images with a restart interval (which the reference's encode parameters do not have)
+ * go through the host coder as in hipjpegEncodeBatchHost, and so does everything when flags = 0.  flags = HIPJPEG_FLAG_GPU_HUFFMAN |
+ * HIPJPEG_FLAG_GPU_RESTART_INTERVALS: the GPU coder takes baseline images with a restart interval too (predictor reset, byte alignment
+ * and RSTn markers on the device, the markers exempt from byte stuffing; byte-identical to the host coder's files); progressive output
+ * with a restart interval still goes to the host coder.  Blocking. */
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchEntropy(hipjpegHandle_t handle, unsigned flags, hipjpegStatus_t* statuses);
 /* Both of the above. */
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatch(hipjpegHandle_t handle, const hipjpegEncodeInput_t* inputs, const hipjpegEncodeParams_t* params,
@@ -282,8 +290,9 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeGetBitstream(hipjpegHandle_t handle, in
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeGetCoefficients(hipjpegHandle_t handle, int index, int component, const int16_t** coef,
                                                          int32_t grid[4] /* blocks_w, blocks_h, real_w, real_h */);
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchStats(hipjpegHandle_t handle, int32_t* num_units, uint64_t* pixel_bytes, uint64_t* coef_bytes);
-/* How many images of the handle's last entropy stage the GPU entropy coder took (no restart intervals: baseline with Annex-K or optimized
- * tables, and progressive output); the others were coded by the host coder. */
+/* How many images of the handle's last entropy stage the GPU entropy coder took (baseline with Annex-K or optimized tables, and
+ * progressive output; with a restart interval only baseline images, and only under HIPJPEG_FLAG_GPU_RESTART_INTERVALS); the others were
+ * coded by the host coder. */
 HIPJPEG_API int32_t hipjpegEncodeBatchGpuEntropyImages(hipjpegHandle_t handle);
 /* Host-only: entropy-code given coefficient grids (zigzag order, MCU-padded grids as above) into a JFIF file.
  * Returns HIPJPEG_STATUS_BUFFER_TOO_SMALL with *length = needed size if capacity is insufficient. */
@@ -296,6 +305,12 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeFromCoefficientsHost(int32_t width, int
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeFromCoefficientsGpuAlgorithmHost(int32_t width, int32_t height, const hipjpegEncodeParams_t* params,
                                                                           const int16_t* const coef[3], uint8_t* out, size_t capacity,
                                                                           size_t* length);
+/* The GPU entropy coder's baseline algorithm (csrc/huffman_encode_core.h: per-block coding, the segmented scan of the bit offsets,
+ * padding, restart-marker placement, byte stuffing that spares the markers) executed on the host with the very code the kernels run.
+ * Any restart_interval (0..65535, 0 = none), Annex-K or optimized tables.  Same signature and output as
+ * hipjpegEncodeFromCoefficientsHost; HIPJPEG_STATUS_UNSUPPORTED for progressive output. */
+HIPJPEG_API hipjpegStatus_t hipjpegEncodeBaselineGpuAlgorithmHost(int32_t width, int32_t height, const hipjpegEncodeParams_t* params,
+                                                                  const int16_t* const coef[3], uint8_t* out, size_t capacity, size_t* length);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@ STATUS_NAMES = {0: "SUCCESS", 1: "INVALID_ARGUMENT", 2: "BAD_JPEG", 3: "UNSUPPOR
 OUTPUT_RGBI, OUTPUT_BGRI, OUTPUT_RGB_PLANAR, OUTPUT_BGR_PLANAR, OUTPUT_Y, OUTPUT_YUV_PLANAR = range(6)
 FLAG_FANCY_UPSAMPLING = 1
 FLAG_GPU_HUFFMAN = 2
+FLAG_GPU_RESTART_INTERVALS = 8
 FLAG_FAST_IDCT = 4  # JDCT_IFAST as libjpeg-turbo's x86-64 SIMD routine computes it (the reference's fast_idct)
 
 
@@ -126,5 +127,6 @@ def load():
     L.hipjpegEncodeBatchGpuEntropyImages.restype = i32
     L.hipjpegEncodeFromCoefficientsHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
     L.hipjpegEncodeFromCoefficientsGpuAlgorithmHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
+    L.hipjpegEncodeBaselineGpuAlgorithmHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
     _lib = L
     return L

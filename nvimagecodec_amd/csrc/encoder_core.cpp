@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "encode_kernels.h"
+#include "huffman_encode_core.h"
 #include "jpeg_syntax.h"
 #include "progressive_encode.h"
 
@@ -264,11 +265,11 @@ hipjpegStatus_t EncodeBatch::fetch_coefficients()
 }
 
 // ---------------------------------------------------------------- entropy coding
-hipjpegStatus_t EncodeBatch::route_entropy(bool gpu_huffman)
+hipjpegStatus_t EncodeBatch::route_entropy(bool gpu_huffman, bool gpu_restart)
 {
     for (size_t i = 0; i < images_.size(); i++) host_coder_[i] = images_[i].status == HIPJPEG_STATUS_SUCCESS;
     hipjpegStatus_t st;
-    if (gpu_huffman && (st = gpu_entropy_stage()) != HIPJPEG_STATUS_SUCCESS) return st;
+    if (gpu_huffman && (st = gpu_entropy_stage(gpu_restart)) != HIPJPEG_STATUS_SUCCESS) return st;
     host_images_ = (int)std::count(host_coder_.begin(), host_coder_.end(), 1);
     // the host coder needs the coefficients on its side of PCIe
     return host_images_ ? fetch_coefficients() : HIPJPEG_STATUS_SUCCESS;
@@ -338,6 +339,7 @@ struct EncodeBatch::SegmentPlan {
 struct EncodeBatch::HencPlan : SegmentPlan {
     std::vector<HencUnit> units;  // length / write units (256 blocks each)
     std::vector<int> opt_slot;    // slot among the images with tables of their own (optimized_huffman), or -1
+    bool restart = false;         // an image has restart intervals: every launch takes the kernels' flavour that carries them
     int nopt = 0;
     size_t total_blocks = 0;  // entries of the per-block arrays
     HencLayout1 d1{};
@@ -351,20 +353,20 @@ struct EncodeBatch::PencPlan : SegmentPlan {
     PencLayout1 d1{};
 };
 
-hipjpegStatus_t EncodeBatch::gpu_entropy_stage()
+hipjpegStatus_t EncodeBatch::gpu_entropy_stage(bool gpu_restart)
 {
     gpu_entropy_images_ = 0;
     if (!launched_) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (hipSetDevice(device_id_) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
     HencPlan p;
     PencPlan q;
-    henc_choose(p, q);
+    henc_choose(p, q, gpu_restart);
     hipjpegStatus_t st;
     if (!p.idx.empty()) {
         const HencLayout1& d1 = p.d1;
         const auto write = [&](const HencImage* dsegs) {
             return launch_henc_write(dsegs, at<const HencUnit>(henc_.dev, d1.units), (int)p.units.size(), at<const StandardCodeTables>(henc_.dev, d1.tables),
-                                     at<const uint32_t>(henc_.dev, d1.off), at<const uint16_t>(henc_.dev, d1.bits), stream_);
+                                     at<const uint32_t>(henc_.dev, d1.off), at<const uint16_t>(henc_.dev, d1.bits), stream_, p.restart);
         };
         bool direct = false;
         henc_describe(p);
@@ -372,7 +374,8 @@ hipjpegStatus_t EncodeBatch::gpu_entropy_stage()
             (st = henc_lengths(p)) != HIPJPEG_STATUS_SUCCESS)
             return st;
         henc_chunks(p, henc_);
-        if ((st = henc_assemble(p, henc_, write, &direct)) != HIPJPEG_STATUS_SUCCESS || (st = henc_collect(p, henc_, direct)) != HIPJPEG_STATUS_SUCCESS) return st;
+        if ((st = henc_assemble(p, henc_, write, &direct, p.restart)) != HIPJPEG_STATUS_SUCCESS || (st = henc_collect(p, henc_, direct)) != HIPJPEG_STATUS_SUCCESS)
+            return st;
     }
     if (!q.idx.empty()) {
         const PencLayout1& d1 = q.d1;
@@ -392,14 +395,16 @@ hipjpegStatus_t EncodeBatch::gpu_entropy_stage()
     return HIPJPEG_STATUS_SUCCESS;
 }
 
-// Every image the host coder would code except those with restart markers: baseline ones into p, progressive ones into q.
-void EncodeBatch::henc_choose(HencPlan& p, PencPlan& q)
+// Every image the host coder would code and the GPU coder takes: baseline ones into p, progressive ones into q.  Restart intervals:
+// baseline images when the caller asked for them (HIPJPEG_FLAG_GPU_RESTART_INTERVALS), progressive ones never (jcphuff.c emit_restart
+// flushes the EOB run, which the run walk of progressive_encode.hip does not do).
+void EncodeBatch::henc_choose(HencPlan& p, PencPlan& q, bool gpu_restart)
 {
     for (int i = 0; i < (int)images_.size(); i++) {
         PlannedEncode& im = images_[i];
         im.gpu_bitstream = nullptr;
         im.gpu_bitstream_len = 0;
-        if (!host_coder_[i] || im.params.restart_interval != 0) continue;
+        if (!host_coder_[i] || (im.params.restart_interval != 0 && (!gpu_restart || im.params.progressive))) continue;
         host_coder_[i] = 0;
         (im.params.progressive ? q.idx : p.idx).push_back(i);
     }
@@ -431,13 +436,15 @@ void EncodeBatch::henc_describe(HencPlan& p)
         h.bpm = eg.ncomp == 3 ? (uint32_t)(eg.hs * eg.vs + 2) : 1u;
         h.total_blocks = h.mcus_x * h.mcus_y * h.bpm;
         h.first_block = (uint32_t)p.total_blocks;
-        h.nseg = 1;  // a baseline file is one segment
+        h.rst_blocks = (uint32_t)im.params.restart_interval * h.bpm;
+        if (h.rst_blocks) p.restart = true;
+        h.nseg = 1;  // a baseline file is one segment, with or without restart intervals
         h.last_seg = 1;
         p.first_seg.push_back(g);
         for (uint32_t b = 0; b < h.total_blocks; b += 256) p.units.push_back(HencUnit{(uint32_t)g, b});
         p.total_blocks += (h.total_blocks + 63) & ~(size_t)63;
         if (im.params.optimized_huffman) p.opt_slot[g] = p.nopt++;
-        write_standard_headers(eg, im.qlum, im.qchr, &p.headers[g]);
+        write_standard_headers(eg, im.qlum, im.qchr, &p.headers[g], im.params.restart_interval);
     }
     p.first_seg.push_back(ng);
 }
@@ -480,7 +487,7 @@ hipjpegStatus_t EncodeBatch::henc_histograms(HencPlan& p)
     copy_table(henc_.pinned, d1.desc, p.segs);
     if (hipMemcpyAsync(henc_.dev.data(), henc_.pinned.data(), d1.opt_tables, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemsetAsync(henc_.dev.data() + d1.hist, 0, hist_bytes, s) != hipSuccess ||
-        launch_henc_hist(at<const HencImage>(henc_.dev, d1.desc), at<const HencUnit>(henc_.dev, d1.units), (int)p.units.size(), stream_) != 0 ||
+        launch_henc_hist(at<const HencImage>(henc_.dev, d1.desc), at<const HencUnit>(henc_.dev, d1.units), (int)p.units.size(), stream_, p.restart) != 0 ||
         hipMemcpyAsync(henc_.pinned.data() + p.pin.hist, henc_.dev.data() + d1.hist, hist_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;
@@ -491,7 +498,7 @@ hipjpegStatus_t EncodeBatch::henc_histograms(HencPlan& p)
         const auto* counts = at<const uint32_t[2][256]>(henc_.pinned, p.pin.hist + kHistBytes * (size_t)k);
         const size_t tables = d1.opt_tables + sizeof(StandardCodeTables) * (size_t)k;
         p.headers[g].clear();
-        optimal_code_tables(counts, im.geom, im.qlum, im.qchr, at<StandardCodeTables>(henc_.pinned, tables), &p.headers[g]);
+        optimal_code_tables(counts, im.geom, im.qlum, im.qchr, at<StandardCodeTables>(henc_.pinned, tables), &p.headers[g], im.params.restart_interval);
         p.segs[g].hist = nullptr;
         p.segs[g].tables = at<const StandardCodeTables>(henc_.dev, tables);
     }
@@ -508,8 +515,9 @@ hipjpegStatus_t EncodeBatch::henc_lengths(HencPlan& p)
     hipStream_t s = (hipStream_t)stream_;
     if (hipMemcpyAsync(henc_.dev.data(), henc_.pinned.data(), d1.upload(), hipMemcpyHostToDevice, s) != hipSuccess ||
         launch_henc_length(dimg, at<const HencUnit>(henc_.dev, d1.units), (int)p.units.size(), at<const StandardCodeTables>(henc_.dev, d1.tables),
-                           at<uint16_t>(henc_.dev, d1.bits), stream_) != 0 ||
-        launch_henc_scan(dimg, ng, at<const uint16_t>(henc_.dev, d1.bits), at<uint32_t>(henc_.dev, d1.off), at<uint32_t>(henc_.dev, d1.totals), stream_) != 0 ||
+                           at<uint16_t>(henc_.dev, d1.bits), stream_, p.restart) != 0 ||
+        launch_henc_scan(dimg, ng, at<const uint16_t>(henc_.dev, d1.bits), at<uint32_t>(henc_.dev, d1.off), at<uint32_t>(henc_.dev, d1.totals), stream_,
+                         p.restart) != 0 ||
         hipMemcpyAsync(henc_.pinned.data() + p.pin.totals, henc_.dev.data() + d1.totals, (size_t)ng * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;
@@ -639,9 +647,11 @@ void EncodeBatch::henc_chunks(SegmentPlan& p, const HencArenas& a)
             h.num_chunks = (h.raw_bytes + kHencChunk - 1) / kHencChunk;
             for (uint32_t c = 0; c < h.num_chunks; c++) p.chunk_units.push_back(HencUnit{(uint32_t)k, c});
             h.header_bytes = (uint32_t)p.headers[k].size();
-            p.raw_off[k] = raw.take((size_t)h.raw_bytes + 16);
+            // a segment with restart intervals: the markers are part of raw_bytes (the scan counted them), and the marker bitmap lies
+            // behind the buffer -- zeroed with it, one bit per byte (huffman_encode_core.h)
+            p.raw_off[k] = raw.take(h.rst_blocks ? (size_t)henc_map_offset(h.raw_bytes) + henc_map_bytes(h.raw_bytes) : (size_t)h.raw_bytes + 16);
             p.hdr_off[k] = hdr.take(p.headers[k].size(), 16);
-            file_bytes += (size_t)h.header_bytes + 2 * (size_t)h.raw_bytes;  // every byte could be 0xFF
+            file_bytes += (size_t)h.header_bytes + 2 * (size_t)h.raw_bytes;  // every byte could be 0xFF (a marker's is, and is not stuffed)
         }
         // as henc_layout_kernel places them: a file's segments back to back, every file at a 16-byte boundary
         p.arena_cap += align_up(file_bytes, 16);
@@ -655,7 +665,7 @@ void EncodeBatch::henc_chunks(SegmentPlan& p, const HencArenas& a)
 // device's address space): the expand kernel's stores cross PCIe themselves and no copy follows.  With a caller-supplied pinned
 // allocator the mapping is unknown, so the files are assembled in HBM.
 template <class Write>
-hipjpegStatus_t EncodeBatch::henc_assemble(SegmentPlan& p, HencArenas& a, Write write, bool* direct)
+hipjpegStatus_t EncodeBatch::henc_assemble(SegmentPlan& p, HencArenas& a, Write write, bool* direct, bool restart)
 {
     const int ns = (int)p.segs.size();
     const size_t nchunks = p.chunk_units.size();
@@ -689,9 +699,9 @@ hipjpegStatus_t EncodeBatch::henc_assemble(SegmentPlan& p, HencArenas& a, Write 
     hipStream_t s = (hipStream_t)stream_;
     if (hipMemcpyAsync(a.dev2.data(), a.pinned.data() + p.pin.up2, d2.upload(), hipMemcpyHostToDevice, s) != hipSuccess ||
         launch_henc_zero(a.dev2.data() + d2.raw, p.raw_total, stream_) != 0 || write(dsegs) != 0 ||
-        launch_henc_count(dsegs, dchunks, (int)nchunks, chunk_ff, stream_) != 0 ||
+        launch_henc_count(dsegs, dchunks, (int)nchunks, chunk_ff, stream_, restart) != 0 ||
         launch_henc_layout(dsegs, ns, chunk_ff, chunk_out, len, foff, stream_) != 0 ||
-        launch_henc_expand(dsegs, dchunks, (int)nchunks, chunk_out, len, foff, *direct ? a.out.data() : a.dev2.data() + d2.arena, stream_) != 0 ||
+        launch_henc_expand(dsegs, dchunks, (int)nchunks, chunk_out, len, foff, *direct ? a.out.data() : a.dev2.data() + d2.arena, stream_, restart) != 0 ||
         hipMemcpyAsync(a.pinned.data() + p.pin.len, len, (size_t)ns * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(a.pinned.data() + p.pin.foff, foff, (size_t)ns * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)

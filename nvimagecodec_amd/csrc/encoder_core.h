@@ -48,7 +48,7 @@ public:
     // Decides who entropy-codes each planned image: with gpu_huffman the GPU coder (blocking) takes every image it can -- Annex-K
     // or optimized tables or progressive output, no restart markers -- and the rest is flagged for the host coder (every planned
     // image without gpu_huffman).  Fetches the coefficients when the host coder has anything to do.
-    hipjpegStatus_t route_entropy(bool gpu_huffman);
+    hipjpegStatus_t route_entropy(bool gpu_huffman, bool gpu_restart = false);
     // Host coder: Huffman + markers for image i when route_entropy() left it to the host; otherwise nothing.  Thread-safe for distinct i.
     void entropy_stage(int i);
     int host_images() const { return host_images_; }  // images route_entropy() left to the host coder
@@ -103,8 +103,8 @@ private:
             : dev(Buffer::kDevice, hooks), dev2(Buffer::kDevice, hooks), pinned(Buffer::kPinned, hooks), out(Buffer::kPinned, hooks) {}
         Buffer dev, dev2, pinned, out;
     };
-    hipjpegStatus_t gpu_entropy_stage();
-    void henc_choose(HencPlan& p, PencPlan& q);
+    hipjpegStatus_t gpu_entropy_stage(bool gpu_restart);
+    void henc_choose(HencPlan& p, PencPlan& q, bool gpu_restart);
     // baseline output, Annex-K or optimized tables: one host round trip more when any image wants tables of its own
     void henc_describe(HencPlan& p);
     hipjpegStatus_t henc_stage_phase1(HencPlan& p);
@@ -118,7 +118,7 @@ private:
     // phase 2; `write` queues the flavour's kernel that fills the segments' bit buffers
     void henc_chunks(SegmentPlan& p, const HencArenas& a);
     template <class Write>
-    hipjpegStatus_t henc_assemble(SegmentPlan& p, HencArenas& a, Write write, bool* direct);
+    hipjpegStatus_t henc_assemble(SegmentPlan& p, HencArenas& a, Write write, bool* direct, bool restart = false);
     hipjpegStatus_t henc_collect(SegmentPlan& p, HencArenas& a, bool direct);
     HencArenas henc_, penc_;
     uint64_t gpu_entropy_images_ = 0;

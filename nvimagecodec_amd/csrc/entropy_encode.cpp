@@ -730,14 +730,14 @@ void progressive_scan_header(const ScanSpec& sc, const uint32_t counts[256], uin
     write_sos(sc, out);
 }
 
-void write_standard_headers(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out)
+void write_standard_headers(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out, int restart_interval)
 {
     HuffTable dcl, dcc, acl, acc;
     dcl.set(kDcLumBits, kDcVals);
     dcc.set(kDcChrBits, kDcVals);
     acl.set(kAcLumBits, kAcLumVals);
     acc.set(kAcChrBits, kAcChrVals);
-    write_headers(g, qlum, qchr, dcl, acl, dcc, acc, 0, out);
+    write_headers(g, qlum, qchr, dcl, acl, dcc, acc, restart_interval, out);
 }
 
 void standard_code_tables(StandardCodeTables* t)
@@ -760,7 +760,7 @@ void standard_code_tables(StandardCodeTables* t)
 }
 
 void optimal_code_tables(const uint32_t counts[2][2][256], const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64],
-                         StandardCodeTables* t, std::vector<uint8_t>* headers)
+                         StandardCodeTables* t, std::vector<uint8_t>* headers, int restart_interval)
 {
     HuffTable dc[2], ac[2];
     dc[0].set(kDcLumBits, kDcVals);
@@ -787,7 +787,7 @@ void optimal_code_tables(const uint32_t counts[2][2][256], const EncodeGeometry&
             t->ac_size[k][i] = ac[k].size[i];
         }
     }
-    write_headers(g, qlum, qchr, dc[0], ac[0], dc[1], ac[1], 0, headers);
+    write_headers(g, qlum, qchr, dc[0], ac[0], dc[1], ac[1], restart_interval, headers);
 }
 
 void encode_jfif(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], const int16_t* const coef[3],

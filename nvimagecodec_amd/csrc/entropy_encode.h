@@ -35,7 +35,7 @@ void encode_jfif(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_
                  const EntropyEncodeOptions& opt, std::vector<uint8_t>* out);
 
 // For the GPU entropy coder (gpu_huffman_encode.hip): the Annex-K tables as (code, length) per symbol, [0] luma [1] chroma,
-// and the bytes of SOI .. SOS for those tables (no DRI).
+// and the bytes of SOI .. SOS for those tables (restart_interval != 0: with the DRI segment where jcmarker.c puts it, between DHT and SOS).
 struct StandardCodeTables {
     uint16_t dc_code[2][16];
     uint16_t ac_code[2][256];
@@ -47,8 +47,9 @@ void standard_code_tables(StandardCodeTables* t);
 // symbol] for AC table t; t = 0 luma, 1 chroma) to the (code, length) tables and the bytes of SOI .. SOS with the matching DHT segments --
 // jchuff.c jpeg_gen_optimal_table, the very routine the host coder's optimized_huffman path uses, so both paths write the same file.
 void optimal_code_tables(const uint32_t counts[2][2][256], const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64],
-                         StandardCodeTables* t, std::vector<uint8_t>* headers);
-void write_standard_headers(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out);
+                         StandardCodeTables* t, std::vector<uint8_t>* headers, int restart_interval = 0);
+void write_standard_headers(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out,
+                            int restart_interval = 0);
 
 // ---- progressive output on the GPU coder (progressive_encode.hip): the host coder's scan script, frame header and per-scan tables
 // One scan of a progressive script: components (indices), spectral band ss..se, successive approximation ah / al.

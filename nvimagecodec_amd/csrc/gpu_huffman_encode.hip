@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gpu_huffman_encode.h"
+#include "huffman_encode_core.h"
 
 namespace hipjpeg {
 
@@ -28,204 +29,53 @@ __device__ __forceinline__ void load_tables(LdsTables* dst, const StandardCodeTa
     for (int i = threadIdx.x; i < (int)(sizeof(LdsTables) / 4); i += kThreads) d[i] = s[i];
 }
 
-// Where block s of the scan (MCU order) lives, and where the previous block of the same component is.
-struct BlockRef {
-    int c;              // component
-    uint32_t bx, by;    // block coordinates in the component's grid
-    bool has_prev;
-    uint32_t pbx, pby;  // the same component's previous block in scan order (DC predictor)
-};
-
-__device__ __forceinline__ BlockRef locate(const HencImage& im, uint32_t s)
-{
-    BlockRef r;
-    const uint32_t mcu = s / im.bpm, k = s - mcu * im.bpm;
-    const uint32_t my = mcu / im.mcus_x, mx = mcu - my * im.mcus_x;
-    uint32_t mh = 1, mv = 1, j = 0;
-    r.c = 0;
-    if (im.ncomp == 3) {
-        const uint32_t nl = im.hs * im.vs;
-        if (k < nl) {
-            j = k;
-            mh = im.hs;
-            mv = im.vs;
-        } else {
-            r.c = (int)(k - nl + 1);
-        }
-    }
-    const uint32_t dy = j / mh, dx = j - dy * mh;
-    r.bx = mx * mh + dx;
-    r.by = my * mv + dy;
-    if (j > 0) {
-        const uint32_t pj = j - 1, pdy = pj / mh, pdx = pj - pdy * mh;
-        r.has_prev = true;
-        r.pbx = mx * mh + pdx;
-        r.pby = my * mv + pdy;
-    } else if (mcu > 0) {
-        const uint32_t pm = mcu - 1, pmy = pm / im.mcus_x, pmx = pm - pmy * im.mcus_x;
-        r.has_prev = true;
-        r.pbx = pmx * mh + (mh - 1);
-        r.pby = pmy * mv + (mv - 1);
-    } else {
-        r.has_prev = false;
-        r.pbx = r.pby = 0;
-    }
-    return r;
-}
-
-// DC value libjpeg gives a block: real blocks their own; dummy blocks the DC of the preceding block in MCU order
-// (entropy_encode.cpp BlockSource::dc_of).
-__device__ __forceinline__ int dc_value(const HencImage& im, int c, uint32_t bx, uint32_t by)
-{
-    const uint32_t mh = (c == 0 && im.ncomp == 3) ? im.hs : 1;
-    while (by >= im.real_h[c]) {
-        bx = (bx / mh) * mh + mh - 1;
-        by--;
-    }
-    if (bx >= im.real_w[c]) bx = im.real_w[c] - 1;
-    return im.coef[c][((size_t)by * im.blocks_w[c] + bx) * 64];
-}
-
-__device__ __forceinline__ int bit_length(unsigned v) { return v ? 32 - __builtin_clz(v) : 0; }
-
-// Bit sink of the write kernel.  The workgroup's 256 blocks cover one contiguous bit range of the image's bit buffer; that
+// Word sink of the write kernel's emitter.  The workgroup's 256 blocks cover one contiguous bit range of the image's bit buffer; that
 // range is assembled in LDS (zeroed, bits OR-ed in with ds_or -- LDS atomics are cheap) and then copied out as whole words,
 // coalesced.  Only the first and the last word of the range can be shared with a neighbouring workgroup: those two go out
 // with a global atomic OR (the bit buffer starts out zeroed).  A range that does not fit the window (very high bit rates)
 // falls back to OR-ing every word into the global buffer directly.
 constexpr int kWindowWords = 4096;  // 16 KB: 256 blocks x 64 bytes on average
 
-struct Emitter {
-    uint32_t* gwords;             // the image's bit buffer
-    HJ_LDS uint32_t* window;      // LDS window (LDS address 0 is a valid place for it: never test this pointer)
-    bool use_window;              // false: write through to gwords
-    uint32_t window_word0;        // index (in gwords) of window[0]
-    unsigned long long acc;
-    uint32_t n;        // valid bits at the low end of acc
-    uint32_t widx;     // next word (index into gwords)
-    uint32_t emitted;  // bits of this block so far
-    __device__ __forceinline__ void start(uint8_t* raw, uint32_t off, HJ_LDS uint32_t* win, bool use_win, uint32_t win_word0)
-    {
-        gwords = reinterpret_cast<uint32_t*>(raw);
-        window = win;
-        use_window = use_win;
-        window_word0 = win_word0;
-        acc = 0;
-        n = off & 31;
-        widx = off >> 5;
-        emitted = 0;
-    }
-    __device__ __forceinline__ void out(uint32_t w)  // w: bits in stream order, most significant first
+struct WindowWords {
+    uint32_t* gwords;         // the image's bit buffer
+    HJ_LDS uint32_t* window;  // LDS window (LDS address 0 is a valid place for it: never test this pointer)
+    bool use_window;          // false: write through to gwords
+    uint32_t window_word0;    // index (in gwords) of window[0]
+    __device__ __forceinline__ void or_word(uint32_t widx, uint32_t w) const  // w: bits in stream order, most significant first
     {
         if (use_window)
             __hip_atomic_fetch_or(&window[widx - window_word0], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         else
             atomicOr(&gwords[widx], __builtin_bswap32(w));
-        widx++;
     }
-    __device__ __forceinline__ void put(uint32_t bits, uint32_t size)  // size <= 16, bits already masked
+};
+using Emitter = HencEmitter<WindowWords>;
+
+struct LdsCount {
+    HJ_LDS uint32_t (*hist)[256];  // [0] DC categories, [1] AC run/size symbols
+    __device__ __forceinline__ void add(int dcac, int sym) const
     {
-        acc = (acc << size) | bits;
-        n += size;
-        emitted += size;
-        if (n >= 32) {
-            out((uint32_t)(acc >> (n - 32)));
-            n -= 32;
-        }
-    }
-    __device__ __forceinline__ void finish()
-    {
-        if (n > 0) out((uint32_t)(acc << (32 - n)));
+        __hip_atomic_fetch_add(&hist[dcac][sym], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
 };
 
-// One block.  q = its 64 coefficients in zigzag order (two per dword), ignored for dummy blocks.  Returns the bit length.
+// A block's 64 coefficients as loaded (8 x 16 bytes) -> two per dword
+#define HJ_BLOCK_WORDS(q)                                                                                                                            \
+    {q[0].x, q[0].y, q[0].z, q[0].w, q[1].x, q[1].y, q[1].z, q[1].w, q[2].x, q[2].y, q[2].z, q[2].w, q[3].x, q[3].y, q[3].z, q[3].w,                   \
+     q[4].x, q[4].y, q[4].z, q[4].w, q[5].x, q[5].y, q[5].z, q[5].w, q[6].x, q[6].y, q[6].z, q[6].w, q[7].x, q[7].y, q[7].z, q[7].w}
+
 template <bool WRITE>
 __device__ __forceinline__ uint32_t code_block(const uint4 (&q)[8], bool real, int diff, const HJ_LDS LdsTables* T, int ti, Emitter* em)
 {
-    uint32_t len;
-    {
-        const unsigned t = (unsigned)(diff < 0 ? -diff : diff);
-        const int nb = bit_length(t);
-        const uint32_t size = T->dc_size[ti][nb];
-        len = size + nb;
-        if (WRITE) {
-            em->put(T->dc_code[ti][nb], size);
-            if (nb) em->put((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << nb) - 1), nb);
-        }
-    }
-    if (!real) {  // dummy block: all AC zero -> EOB
-        const uint32_t size = T->ac_size[ti][0];
-        if (WRITE) em->put(T->ac_code[ti][0], size);
-        return len + size;
-    }
-    const uint32_t w[32] = {q[0].x, q[0].y, q[0].z, q[0].w, q[1].x, q[1].y, q[1].z, q[1].w, q[2].x, q[2].y, q[2].z, q[2].w, q[3].x, q[3].y, q[3].z, q[3].w,
-                            q[4].x, q[4].y, q[4].z, q[4].w, q[5].x, q[5].y, q[5].z, q[5].w, q[6].x, q[6].y, q[6].z, q[6].w, q[7].x, q[7].y, q[7].z, q[7].w};
-    int run = 0;
-#pragma unroll
-    for (int k = 1; k < 64; k++) {
-        const int v = (k & 1) ? ((int)w[k >> 1] >> 16) : ((int)(w[k >> 1] << 16) >> 16);
-        if (v == 0) {
-            run++;
-            continue;
-        }
-        while (run > 15) {  // ZRL
-            const uint32_t size = T->ac_size[ti][0xF0];
-            len += size;
-            if (WRITE) em->put(T->ac_code[ti][0xF0], size);
-            run -= 16;
-        }
-        const int nb = bit_length((unsigned)(v < 0 ? -v : v));
-        const int sym = (run << 4) + nb;
-        const uint32_t size = T->ac_size[ti][sym];
-        len += size + nb;
-        if (WRITE) {
-            em->put(T->ac_code[ti][sym], size);
-            em->put((uint32_t)(v < 0 ? v - 1 : v) & ((1u << nb) - 1), nb);
-        }
-        run = 0;
-    }
-    if (run > 0) {
-        const uint32_t size = T->ac_size[ti][0];
-        len += size;
-        if (WRITE) em->put(T->ac_code[ti][0], size);
-    }
-    return len;
+    const uint32_t w[32] = HJ_BLOCK_WORDS(q);
+    return henc_code_block<WRITE>(w, real, diff, T, ti, em);
 }
 
-// The symbols of one block, counted instead of coded (jchuff.c htest_one_block): hist[0][category] for the DC difference, hist[1][run/size]
-// for the coefficients, ZRL and EOB included -- the same walk as code_block.
-__device__ __forceinline__ void count_block(const uint4 (&q)[8], bool real, int diff, HJ_LDS uint32_t (*hist)[256])
-{
-    __hip_atomic_fetch_add(&hist[0][bit_length((unsigned)(diff < 0 ? -diff : diff))], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (!real) {
-        __hip_atomic_fetch_add(&hist[1][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return;
-    }
-    const uint32_t w[32] = {q[0].x, q[0].y, q[0].z, q[0].w, q[1].x, q[1].y, q[1].z, q[1].w, q[2].x, q[2].y, q[2].z, q[2].w, q[3].x, q[3].y, q[3].z, q[3].w,
-                            q[4].x, q[4].y, q[4].z, q[4].w, q[5].x, q[5].y, q[5].z, q[5].w, q[6].x, q[6].y, q[6].z, q[6].w, q[7].x, q[7].y, q[7].z, q[7].w};
-    int run = 0;
-#pragma unroll
-    for (int k = 1; k < 64; k++) {
-        const int v = (k & 1) ? ((int)w[k >> 1] >> 16) : ((int)(w[k >> 1] << 16) >> 16);
-        if (v == 0) {
-            run++;
-            continue;
-        }
-        while (run > 15) {
-            __hip_atomic_fetch_add(&hist[1][0xF0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            run -= 16;
-        }
-        __hip_atomic_fetch_add(&hist[1][(run << 4) + bit_length((unsigned)(v < 0 ? -v : v))], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        run = 0;
-    }
-    if (run > 0) __hip_atomic_fetch_add(&hist[1][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// Loads what code_block needs for block s.
+// Loads what code_block needs for block s.  RST: the launch has images with restart intervals (huffman_encode_core.h).
+template <bool RST>
 __device__ __forceinline__ void fetch_block(const HencImage& im, uint32_t s, uint4 (&q)[8], bool* real, int* diff, int* ti)
 {
-    const BlockRef r = locate(im, s);
+    const HencBlockRef r = henc_locate<RST>(im, s);
     *ti = r.c == 0 ? 0 : 1;
     *real = r.bx < im.real_w[r.c] && r.by < im.real_h[r.c];
     int dc;
@@ -237,12 +87,13 @@ __device__ __forceinline__ void fetch_block(const HencImage& im, uint32_t s, uin
     } else {
 #pragma unroll
         for (int i = 0; i < 8; i++) q[i] = make_uint4(0u, 0u, 0u, 0u);
-        dc = dc_value(im, r.c, r.bx, r.by);
+        dc = henc_dc_value(im, r.c, r.bx, r.by);
     }
-    const int pred = r.has_prev ? dc_value(im, r.c, r.pbx, r.pby) : 0;
+    const int pred = r.has_prev ? henc_dc_value(im, r.c, r.pbx, r.pby) : 0;
     *diff = dc - pred;
 }
 
+template <bool RST>
 __global__ __launch_bounds__(kThreads) void henc_hist_kernel(const HencImage* __restrict__ images, const HencUnit* __restrict__ units)
 {
     __shared__ uint32_t hist[2][2][256];
@@ -256,8 +107,9 @@ __global__ __launch_bounds__(kThreads) void henc_hist_kernel(const HencImage* __
         uint4 q[8];
         bool real;
         int diff, ti;
-        fetch_block(im, s, q, &real, &diff, &ti);
-        count_block(q, real, diff, (HJ_LDS uint32_t(*)[256])hist[ti]);
+        fetch_block<RST>(im, s, q, &real, &diff, &ti);
+        const uint32_t w[32] = HJ_BLOCK_WORDS(q);
+        henc_count_block(w, real, diff, LdsCount{(HJ_LDS uint32_t(*)[256])hist[ti]});
     }
     __syncthreads();
     for (int i = threadIdx.x; i < 1024; i += kThreads) {
@@ -266,6 +118,7 @@ __global__ __launch_bounds__(kThreads) void henc_hist_kernel(const HencImage* __
     }
 }
 
+template <bool RST>
 __global__ __launch_bounds__(kThreads) void henc_length_kernel(const HencImage* __restrict__ images, const HencUnit* __restrict__ units,
                                                                const StandardCodeTables* __restrict__ tables, uint16_t* __restrict__ block_bits)
 {
@@ -279,7 +132,7 @@ __global__ __launch_bounds__(kThreads) void henc_length_kernel(const HencImage* 
     uint4 q[8];
     bool real;
     int diff, ti;
-    fetch_block(im, s, q, &real, &diff, &ti);
+    fetch_block<RST>(im, s, q, &real, &diff, &ti);
     block_bits[im.first_block + s] = (uint16_t)code_block<false>(q, real, diff, (const HJ_LDS LdsTables*)&T, ti, nullptr);
 }
 
@@ -325,6 +178,74 @@ __global__ __launch_bounds__(kThreads) void henc_scan_kernel(const HencImage* __
     if (threadIdx.x == kThreads - 1) total_bits[blockIdx.x] = s_sum[kThreads - 1];
 }
 
+// The same for a launch with restart intervals: a segmented scan.  Behind the last block of every interval but the image's last the
+// running offset is rounded up to a byte and the marker's 16 bits are added (HencSpan, huffman_encode_core.h); a lane's range and
+// the ranges in front of it compose with henc_span_join, which is associative but not commutative: left operand first.
+__global__ __launch_bounds__(kThreads) void henc_scan_rst_kernel(const HencImage* __restrict__ images, const uint16_t* __restrict__ block_bits,
+                                                                 uint32_t* __restrict__ block_off, uint32_t* __restrict__ total_bits)
+{
+    __shared__ uint32_t s_a[kThreads], s_b[kThreads], s_cut[kThreads];
+    const HencImage& im = images[blockIdx.x];
+    const uint16_t* bits = block_bits + im.first_block;
+    uint32_t* off = block_off + im.first_block;
+    const uint32_t n = im.total_blocks;
+    const uint32_t per = (n + kThreads - 1) / kThreads;
+    const uint32_t lo = min(n, threadIdx.x * per), hi = min(n, lo + per);
+    constexpr int kBatch = 8;  // independent loads in flight per lane
+    // blocks left in the interval that block lo lies in; the image's last block ends none (henc_ends_interval)
+    const uint32_t rst = im.rst_blocks;
+    const uint32_t left0 = rst ? rst - lo % rst : 0xFFFFFFFFu;
+    HencSpan sp{0u, 0u, 0u};
+    uint32_t left = left0;
+    for (uint32_t i = lo; i < hi; i += kBatch) {
+        uint32_t d[kBatch];
+#pragma unroll
+        for (int k = 0; k < kBatch; k++) d[k] = i + k < hi ? bits[i + k] : 0u;
+#pragma unroll
+        for (int k = 0; k < kBatch; k++) {
+            if (i + k < hi) {
+                const bool ends = --left == 0 && i + k + 1 < n;
+                if (left == 0) left = rst;
+                sp = henc_span_join(sp, henc_span_block(d[k], ends));
+            }
+        }
+    }
+    s_a[threadIdx.x] = sp.a;
+    s_b[threadIdx.x] = sp.b;
+    s_cut[threadIdx.x] = sp.cut;
+    __syncthreads();
+    for (int d = 1; d < kThreads; d <<= 1) {
+        const bool has = threadIdx.x >= (unsigned)d;
+        HencSpan l{0u, 0u, 0u};
+        if (has) l = HencSpan{s_a[threadIdx.x - d], s_b[threadIdx.x - d], s_cut[threadIdx.x - d]};
+        __syncthreads();
+        if (has) {
+            const HencSpan j = henc_span_join(l, HencSpan{s_a[threadIdx.x], s_b[threadIdx.x], s_cut[threadIdx.x]});
+            s_a[threadIdx.x] = j.a;
+            s_b[threadIdx.x] = j.b;
+            s_cut[threadIdx.x] = j.cut;
+        }
+        __syncthreads();
+    }
+    uint32_t run = threadIdx.x ? henc_span_apply(0u, HencSpan{s_a[threadIdx.x - 1], s_b[threadIdx.x - 1], s_cut[threadIdx.x - 1]}) : 0;
+    left = left0;
+    for (uint32_t i = lo; i < hi; i += kBatch) {
+        uint32_t d[kBatch];
+#pragma unroll
+        for (int k = 0; k < kBatch; k++) d[k] = i + k < hi ? bits[i + k] : 0u;
+#pragma unroll
+        for (int k = 0; k < kBatch; k++) {
+            if (i + k < hi) {
+                off[i + k] = run;
+                const bool ends = --left == 0 && i + k + 1 < n;
+                if (left == 0) left = rst;
+                run = henc_span_apply(run, henc_span_block(d[k], ends));
+            }
+        }
+    }
+    if (threadIdx.x == kThreads - 1) total_bits[blockIdx.x] = henc_span_apply(0u, HencSpan{s_a[kThreads - 1], s_b[kThreads - 1], s_cut[kThreads - 1]});
+}
+
 // Zeroes the bit buffers (16 bytes per lane).
 __global__ __launch_bounds__(kThreads) void henc_zero_kernel(uint4* __restrict__ p, size_t n16)
 {
@@ -332,6 +253,7 @@ __global__ __launch_bounds__(kThreads) void henc_zero_kernel(uint4* __restrict__
     if (i < n16) p[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
+template <bool RST>
 __global__ __launch_bounds__(kThreads) void henc_write_kernel(const HencImage* __restrict__ images, const HencUnit* __restrict__ units,
                                                               const StandardCodeTables* __restrict__ tables, const uint32_t* __restrict__ block_off,
                                                               const uint16_t* __restrict__ block_bits)
@@ -350,7 +272,9 @@ __global__ __launch_bounds__(kThreads) void henc_write_kernel(const HencImage* _
         const uint32_t first_bit = block_off[im.first_block + u.first];
         // one past the range's last bit; the image's last block is followed by up to 7 padding bits.  The range must not be
         // overestimated: its last word is the one that may be shared with the next workgroup.
-        const uint32_t end_bit = block_off[im.first_block + last] + block_bits[im.first_block + last] + (last == im.total_blocks - 1 ? 7u : 0u);
+        // With restart intervals: an interval's last block is followed by its padding and the marker, exactly.
+        uint32_t end_bit = block_off[im.first_block + last] + block_bits[im.first_block + last] + (last == im.total_blocks - 1 ? 7u : 0u);
+        if (henc_ends_interval<RST>(im, last)) end_bit = henc_byte_up(end_bit) + 16u;
         const uint32_t w0 = first_bit >> 5, w1 = (end_bit - 1) >> 5;
         span[0] = w0;
         span[1] = (w1 - w0 + 1 <= (uint32_t)kWindowWords) ? w1 - w0 + 1 : 0u;
@@ -363,16 +287,15 @@ __global__ __launch_bounds__(kThreads) void henc_write_kernel(const HencImage* _
         uint4 q[8];
         bool real;
         int diff, ti;
-        fetch_block(im, s, q, &real, &diff, &ti);
+        fetch_block<RST>(im, s, q, &real, &diff, &ti);
         const uint32_t off = block_off[im.first_block + s];
         Emitter em;
-        em.start(im.raw, off, (HJ_LDS uint32_t*)window, nwin != 0, w0);
+        em.start(WindowWords{reinterpret_cast<uint32_t*>(im.raw), (HJ_LDS uint32_t*)window, nwin != 0, w0}, off);
         code_block<true>(q, real, diff, (const HJ_LDS LdsTables*)&T, ti, &em);
-        if (s == im.total_blocks - 1) {
-            // jchuff.c flush_bits: the last byte of the scan is filled up with one-bits
-            const uint32_t padn = (8 - ((off + em.emitted) & 7)) & 7;
-            if (padn) em.put((1u << padn) - 1, padn);
-        }
+        // jchuff.c flush_bits: the last byte of the scan -- and of every restart interval -- is filled up with one-bits; RSTn follows
+        // an interval and is marked in the bitmap behind the bit buffer
+        const uint32_t marker = henc_finish_block<RST>(im, s, off, &em);
+        if (RST && marker != ~0u) atomicOr(reinterpret_cast<uint32_t*>(im.raw + henc_map_offset(im.raw_bytes)) + (marker >> 5), 1u << (marker & 31));
         em.finish();
     }
     __syncthreads();
@@ -403,13 +326,23 @@ __device__ __forceinline__ uint32_t piece_len(const HencImage& im, uint32_t chun
     return off >= im.raw_bytes ? 0u : min(16u, im.raw_bytes - off);
 }
 
-__device__ __forceinline__ uint32_t count_ff(const uint4& v, uint32_t len)
+// The marker bits of this lane's 16-byte piece of chunk `chunk` (bit i: byte i is a restart marker's FF, not data)
+__device__ __forceinline__ uint32_t piece_markers(const HencImage& im, uint32_t chunk)
+{
+    if (!im.rst_blocks) return 0u;  // an image without restart intervals in a launch that has some: no bitmap behind its buffer
+    return reinterpret_cast<const uint16_t*>(im.raw + henc_map_offset(im.raw_bytes))[chunk * (kHencChunk / 16) + threadIdx.x];
+}
+
+// 0xFF bytes that need a stuffed 0x00 behind them: all but the markers' (`markers`: piece_markers, 0 without restart intervals)
+template <bool RST>
+__device__ __forceinline__ uint32_t count_ff(const uint4& v, uint32_t len, uint32_t markers)
 {
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
     uint32_t n = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         uint32_t m = ff_mask(w[i]);
+        if (RST) m &= ~henc_marker_mask((markers >> (4 * i)) & 15u);
         const int valid = (int)len - 4 * i;  // bytes of this dword that belong to the stream
         if (valid <= 0)
             m = 0;
@@ -430,6 +363,7 @@ __device__ __forceinline__ uint32_t wg_sum(uint32_t v, uint32_t* scratch /*[4]*/
     return total;
 }
 
+template <bool RST>
 __global__ __launch_bounds__(kThreads) void henc_count_kernel(const HencImage* __restrict__ images, const HencUnit* __restrict__ units,
                                                               uint32_t* __restrict__ chunk_ff)
 {
@@ -438,7 +372,7 @@ __global__ __launch_bounds__(kThreads) void henc_count_kernel(const HencImage* _
     const HencImage& im = images[u.image];
     const uint32_t len = piece_len(im, u.first);
     uint32_t n = 0;
-    if (len) n = count_ff(*reinterpret_cast<const uint4*>(im.raw + (size_t)u.first * kHencChunk + threadIdx.x * 16), len);
+    if (len) n = count_ff<RST>(*reinterpret_cast<const uint4*>(im.raw + (size_t)u.first * kHencChunk + threadIdx.x * 16), len, RST ? piece_markers(im, u.first) : 0u);
     const uint32_t total = wg_sum(n, scratch);
     if (threadIdx.x == 0) chunk_ff[im.first_chunk + u.first] = total;
 }
@@ -488,8 +422,9 @@ __global__ __launch_bounds__(kThreads) void henc_layout_kernel(const HencImage* 
     }
 }
 
-// Per chunk: bytes with a 0x00 behind every 0xFF, assembled in LDS at the destination's misalignment and copied out as
+// Per chunk: bytes with a 0x00 behind every 0xFF that is data, assembled in LDS at the destination's misalignment and copied out as
 // dwords (bytes at the ragged ends, which neighbouring chunks share).  Chunk 0 also writes the header, the last chunk EOI.
+template <bool RST>
 __global__ __launch_bounds__(kThreads) void henc_expand_kernel(const HencImage* __restrict__ images, const HencUnit* __restrict__ units,
                                                                const uint32_t* __restrict__ chunk_out, const uint32_t* __restrict__ final_len,
                                                                const unsigned long long* __restrict__ final_off, uint8_t* __restrict__ arena, int nchunks)
@@ -512,7 +447,8 @@ __global__ __launch_bounds__(kThreads) void henc_expand_kernel(const HencImage* 
     const uint32_t len = piece_len(im, u.first);
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
     if (len) v = *reinterpret_cast<const uint4*>(im.raw + (size_t)u.first * kHencChunk + t * 16);
-    const uint32_t n = len ? count_ff(v, len) : 0;
+    const uint32_t markers = RST && len ? piece_markers(im, u.first) : 0u;
+    const uint32_t n = len ? count_ff<RST>(v, len, markers) : 0;
     uint32_t incl = n;
     for (int d = 1; d < 64; d <<= 1) {
         const uint32_t x = __shfl_up(incl, d);
@@ -529,7 +465,7 @@ __global__ __launch_bounds__(kThreads) void henc_expand_kernel(const HencImage* 
         for (uint32_t i = 0; i < len; i++) {
             const uint8_t b = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
             out[o++] = b;
-            if (b == 0xFF) out[o++] = 0;
+            if (b == 0xFF && !(RST && ((markers >> i) & 1))) out[o++] = 0;
         }
     }
     __syncthreads();
@@ -558,32 +494,36 @@ __global__ __launch_bounds__(kThreads) void henc_expand_kernel(const HencImage* 
 
 constexpr int kExpandGrid = 64;  // resident workgroups of the expand kernel: enough stores in flight for PCIe (swept 32..1024 on MI355X)
 
-int launch_henc_hist(const HencImage* images, const HencUnit* units, int nunits, void* stream)
+// `restart`: the launch has images with restart intervals and takes the kernels' flavour that carries the interval arithmetic; without
+// it the kernels are the ones a batch without restart intervals has always run.
+int launch_henc_hist(const HencImage* images, const HencUnit* units, int nunits, void* stream, bool restart)
 {
     if (nunits <= 0) return 0;
-    hipLaunchKernelGGL(henc_hist_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
+    hipLaunchKernelGGL(restart ? henc_hist_kernel<true> : henc_hist_kernel<false>, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
     return (int)hipGetLastError();
 }
 
-int launch_henc_length(const HencImage* images, const HencUnit* units, int nunits, const StandardCodeTables* tables, uint16_t* block_bits, void* stream)
+int launch_henc_length(const HencImage* images, const HencUnit* units, int nunits, const StandardCodeTables* tables, uint16_t* block_bits, void* stream,
+                       bool restart)
 {
     if (nunits <= 0) return 0;
-    hipLaunchKernelGGL(henc_length_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units, tables, block_bits);
+    hipLaunchKernelGGL(restart ? henc_length_kernel<true> : henc_length_kernel<false>, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units, tables, block_bits);
     return (int)hipGetLastError();
 }
 
-int launch_henc_scan(const HencImage* images, int nimages, const uint16_t* block_bits, uint32_t* block_off, uint32_t* total_bits, void* stream)
+int launch_henc_scan(const HencImage* images, int nimages, const uint16_t* block_bits, uint32_t* block_off, uint32_t* total_bits, void* stream,
+                     bool restart)
 {
     if (nimages <= 0) return 0;
-    hipLaunchKernelGGL(henc_scan_kernel, dim3(nimages), dim3(kThreads), 0, (hipStream_t)stream, images, block_bits, block_off, total_bits);
+    hipLaunchKernelGGL(restart ? henc_scan_rst_kernel : henc_scan_kernel, dim3(nimages), dim3(kThreads), 0, (hipStream_t)stream, images, block_bits, block_off, total_bits);
     return (int)hipGetLastError();
 }
 
 int launch_henc_write(const HencImage* images, const HencUnit* units, int nunits, const StandardCodeTables* tables, const uint32_t* block_off,
-                      const uint16_t* block_bits, void* stream)
+                      const uint16_t* block_bits, void* stream, bool restart)
 {
     if (nunits <= 0) return 0;
-    hipLaunchKernelGGL(henc_write_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units, tables, block_off, block_bits);
+    hipLaunchKernelGGL(restart ? henc_write_kernel<true> : henc_write_kernel<false>, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units, tables, block_off, block_bits);
     return (int)hipGetLastError();
 }
 
@@ -595,10 +535,10 @@ int launch_henc_zero(void* p, size_t bytes, void* stream)
     return (int)hipGetLastError();
 }
 
-int launch_henc_count(const HencImage* images, const HencUnit* chunk_units, int nchunks, uint32_t* chunk_ff, void* stream)
+int launch_henc_count(const HencImage* images, const HencUnit* chunk_units, int nchunks, uint32_t* chunk_ff, void* stream, bool restart)
 {
     if (nchunks <= 0) return 0;
-    hipLaunchKernelGGL(henc_count_kernel, dim3(nchunks), dim3(kThreads), 0, (hipStream_t)stream, images, chunk_units, chunk_ff);
+    hipLaunchKernelGGL(restart ? henc_count_kernel<true> : henc_count_kernel<false>, dim3(nchunks), dim3(kThreads), 0, (hipStream_t)stream, images, chunk_units, chunk_ff);
     return (int)hipGetLastError();
 }
 
@@ -611,11 +551,11 @@ int launch_henc_layout(const HencImage* images, int nimages, const uint32_t* chu
 }
 
 int launch_henc_expand(const HencImage* images, const HencUnit* chunk_units, int nchunks, const uint32_t* chunk_out, const uint32_t* final_len,
-                       const unsigned long long* final_off, uint8_t* arena, void* stream)
+                       const unsigned long long* final_off, uint8_t* arena, void* stream, bool restart)
 {
     if (nchunks <= 0) return 0;
     const int grid = nchunks < kExpandGrid ? nchunks : kExpandGrid;
-    hipLaunchKernelGGL(henc_expand_kernel, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, images, chunk_units, chunk_out, final_len, final_off,
+    hipLaunchKernelGGL(restart ? henc_expand_kernel<true> : henc_expand_kernel<false>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, images, chunk_units, chunk_out, final_len, final_off,
                        arena, nchunks);
     return (int)hipGetLastError();
 }

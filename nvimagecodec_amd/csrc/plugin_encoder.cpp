@@ -11,6 +11,7 @@
 // on the framework's executor threads.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstring>
@@ -72,10 +73,22 @@ public:
     HipJpegEncoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgcodecExecutionParams_t* ep, const char* options)
         : fw_(fw), ep_(ep), hooks_(memory_hooks(ep)), device_(ep->device_id)
     {
-        // "hipjpeg_encoder:gpu_huffman=0" keeps the entropy coder on the executor threads (default: on the GPU)
+        // "hipjpeg_encoder:gpu_huffman=0" keeps the entropy coder on the executor threads (default: on the GPU);
+        // "hipjpeg_encoder:restart_interval=N" asks for a restart marker every N MCUs (0..65535, 0: none), "hipjpeg_encoder:restart_rows=R"
+        // for one every R MCU rows (libjpeg's restart_in_rows; it wins over restart_interval).  A value that does not parse or is out
+        // of range is logged and ignored.
         for_each_option(options, kEncoderId, [&](const std::string& key, const std::string& value) {
             std::istringstream v(value);
-            if (key == "gpu_huffman") v >> gpu_huffman_;
+            if (key == "gpu_huffman") {
+                v >> gpu_huffman_;
+            } else if (key == "restart_interval" || key == "restart_rows") {
+                long long x = -1;
+                char rest;
+                if (!(v >> x) || (v >> rest) || x < 0 || x > 65535)
+                    HJ_LOG_WARNING(fw_, kEncoderId, "option " << key << "='" << value << "' ignored (an integer 0..65535)");
+                else
+                    (key == "restart_rows" ? restart_rows_ : restart_interval_) = (int)x;
+            }
         });
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess || device_ < 0 || device_ >= count) {
@@ -127,7 +140,10 @@ private:
     MemoryHooks hooks_;
     int device_;
     bool ok_ = false;
-    bool gpu_huffman_ = true;       // entropy-code on the GPU what it can take (Annex-K or optimized tables, or progressive output; no restart markers)
+    bool gpu_huffman_ = true;       // entropy-code on the GPU what it can take (Annex-K or optimized tables, with or without restart intervals, or
+                                    // progressive output without them)
+    int restart_interval_ = 0;      // in MCUs
+    int restart_rows_ = 0;          // in MCU rows: per image min(rows x MCUs per row, 65535); 0: restart_interval_ holds
     hipStream_t stream_ = nullptr;
     hipEvent_t event_ = nullptr;
     std::unique_ptr<EncodeBatch> batch_;
@@ -308,6 +324,16 @@ nvimgcodecStatus_t HipJpegEncoder::encode(nvimgcodecImageDesc_t** images, nvimgc
         eparams[i].input_format = fmt;
         eparams[i].optimized_huffman = jp ? jp->optimized_huffman : 0;
         eparams[i].progressive = ji.encoding == NVIMGCODEC_JPEG_ENCODING_PROGRESSIVE_DCT_HUFFMAN;  // cuda_encoder.cpp:339-346
+        eparams[i].restart_interval = restart_interval_;
+        if (restart_rows_ > 0) {  // jcmaster.c: restart_in_rows x MCUs_per_row, at most 65535
+            hipjpeg::EncodeGeometry g;
+            g.width = inputs[i].width;
+            g.height = inputs[i].height;
+            if (hipjpeg::subsampling_factors(css, &g.ncomp, &g.hs, &g.vs) == HIPJPEG_STATUS_SUCCESS) {
+                hipjpeg::compute_geometry(&g);
+                eparams[i].restart_interval = (int32_t)std::min<long long>((long long)restart_rows_ * g.mcus_x, 65535);
+            }
+        }
         // our stream must see the producer's pixels (cuda_encoder.cpp:311-312)
         if (gpu_ok && (hipEventRecord(event_, (hipStream_t)info.cuda_stream) != hipSuccess || hipStreamWaitEvent(stream_, event_, 0) != hipSuccess))
             gpu_ok = false;
@@ -315,7 +341,7 @@ nvimgcodecStatus_t HipJpegEncoder::encode(nvimgcodecImageDesc_t** images, nvimgc
     std::vector<hipjpegStatus_t> statuses(n, HIPJPEG_STATUS_SUCCESS);
     if (gpu_ok) gpu_ok = batch_->device_stage(inputs.data(), eparams.data(), n, statuses.data(), stream_) == HIPJPEG_STATUS_SUCCESS;
     // blocks: the GPU coder, or the coefficients' way down for the host coder (like cudaEventSynchronize in cuda_encoder.cpp:374-375)
-    if (gpu_ok) gpu_ok = batch_->route_entropy(gpu_huffman_) == HIPJPEG_STATUS_SUCCESS;
+    if (gpu_ok) gpu_ok = batch_->route_entropy(gpu_huffman_, gpu_huffman_) == HIPJPEG_STATUS_SUCCESS;  // the GPU coder takes restart intervals too
     } catch (...) {
         gpu_ok = false;  // an exception while marshalling or in the device stage: the whole batch is reported failed below
     }

@@ -371,14 +371,27 @@ def encode_from_coefficients_gpu_algorithm_host(width, height, coefs_natural, su
                                 restart_interval, False, progressive)
 
 
-class BatchEncoder:
-    """hipjpegEncodeBatch* on one device; inputs are torch CUDA uint8 tensors ([H, W, 3] interleaved, [3, H, W] planar or [H, W] gray)."""
+def encode_from_coefficients_baseline_gpu_algorithm_host(width, height, coefs_natural, subsampling="420", quality=90, restart_interval=0,
+                                                         optimized_huffman=False, progressive=False):
+    """The GPU entropy coder's baseline algorithm run on the host with the kernels' own code (no GPU): per-block coding, the segmented
+    scan of the bit offsets, padding, restart markers and the byte stuffing that spares them.  Any restart_interval, Annex-K or
+    optimized tables: the file encode_from_coefficients_host writes for the same arguments.  Raises HipJpegError (UNSUPPORTED) for
+    progressive output."""
+    return _encode_coefficients("hipjpegEncodeBaselineGpuAlgorithmHost", width, height, coefs_natural, subsampling, quality, restart_interval,
+                                optimized_huffman, progressive)
 
-    def __init__(self, device=0, num_threads=0, gpu_huffman=False):
+
+class BatchEncoder:
+    """hipjpegEncodeBatch* on one device; inputs are torch CUDA uint8 tensors ([H, W, 3] interleaved, [3, H, W] planar or [H, W] gray).
+    gpu_huffman: the entropy stage's default route; gpu_restart: with gpu_huffman, the GPU coder also takes baseline images with a restart
+    interval (FLAG_GPU_RESTART_INTERVALS)."""
+
+    def __init__(self, device=0, num_threads=0, gpu_huffman=False, gpu_restart=False):
         import torch
         self._torch = torch
         self.device = int(device)
         self.gpu_huffman = bool(gpu_huffman)
+        self.gpu_restart = bool(gpu_restart)
         self._inflight = []
         self._h = ctypes.c_void_p()
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
@@ -402,12 +415,18 @@ class BatchEncoder:
         s = stream if stream is not None else self._torch.cuda.current_stream(self.device)
         return ctypes.c_void_p(s.cuda_stream)
 
+    def _entropy_flags(self, gpu_huffman):
+        if not gpu_huffman:
+            return 0
+        return N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0)
+
     def _marshal(self, images, subsampling, quality, input_format, restart_interval, optimized_huffman, progressive=False):
         n = len(images)
         I = (N.EncodeInput * n)()
         P = (N.EncodeParams * n)()
         subs = subsampling if isinstance(subsampling, (list, tuple)) else [subsampling] * n
         quals = quality if isinstance(quality, (list, tuple)) else [quality] * n
+        rsts = restart_interval if isinstance(restart_interval, (list, tuple)) else [restart_interval] * n
         for i, t in enumerate(images):
             fmt = input_format
             if fmt in ("rgb", "bgr"):
@@ -429,7 +448,7 @@ class BatchEncoder:
                     I[i].plane[p] = t[p].data_ptr()
                     I[i].pitch[p] = t.stride(1)
             I[i].width, I[i].height = w, h
-            P[i] = _enc_params(subs[i], quals[i], fmt, restart_interval, optimized_huffman, progressive)
+            P[i] = _enc_params(subs[i], quals[i], fmt, rsts[i], optimized_huffman, progressive)
         self._keep = (images, I, P)
         self._n = n
         return I, P
@@ -450,7 +469,7 @@ class BatchEncoder:
         if gpu_huffman is None:
             gpu_huffman = self.gpu_huffman
         I, P = self._marshal(images, subsampling, quality, input_format, restart_interval, optimized_huffman, progressive)
-        st = N.load().hipjpegEncodeBatchSubmit(self._h, I, P, self._n, N.FLAG_GPU_HUFFMAN if gpu_huffman else 0, self._stream_ptr(stream))
+        st = N.load().hipjpegEncodeBatchSubmit(self._h, I, P, self._n, self._entropy_flags(gpu_huffman), self._stream_ptr(stream))
         if st:
             raise N.HipJpegError(st, "hipjpegEncodeBatchSubmit")
         self._inflight.append((self._n, self._keep))
@@ -470,12 +489,14 @@ class BatchEncoder:
             raise N.HipJpegError(st, "hipjpegEncodeBatchRelaunch")
 
     def host_stage(self, gpu_huffman=None):
-        """Entropy stage of the prepared batch.  gpu_huffman (default: the encoder's setting): code on the GPU what it can
-        take (Annex-K tables, no restart markers); the rest, or everything when False, on the host thread pool."""
+        """Entropy stage of the prepared batch.  gpu_huffman (default: the encoder's setting): code on the GPU what it can take --
+        baseline output with Annex-K or optimized tables and progressive output, without a restart interval; with the encoder's
+        gpu_restart=True also baseline output with a restart interval -- and the rest (progressive output with a restart interval
+        always), or everything when False, on the host thread pool."""
         if gpu_huffman is None:
             gpu_huffman = self.gpu_huffman
         st_arr = (ctypes.c_int * self._n)()
-        st = N.load().hipjpegEncodeBatchEntropy(self._h, N.FLAG_GPU_HUFFMAN if gpu_huffman else 0, st_arr)
+        st = N.load().hipjpegEncodeBatchEntropy(self._h, self._entropy_flags(gpu_huffman), st_arr)
         if st:
             raise N.HipJpegError(st, "hipjpegEncodeBatchEntropy")
         return list(st_arr)

@@ -14,6 +14,7 @@ run tests/campaigns/fuzz_gpu.py 32 $((40 * S))
 run tests/campaigns/fuzz_damage.py 33 $((60 * S))
 run tests/campaigns/fuzz_progressive.py 41 $((40 * S))
 run tests/campaigns/fuzz_encode.py 34 $((60 * S))
+run tests/campaigns/fuzz_restart_encode.py 42 $((30 * S))
 run tests/campaigns/fuzz_outputs.py 35 $((20 * S))
 run tests/campaigns/fuzz_geometry.py 36 $((20 * S))
 run tests/campaigns/fuzz_plugin.py 37 $((30 * S))
