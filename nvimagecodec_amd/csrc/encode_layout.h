@@ -19,7 +19,9 @@ enum InFormat : uint32_t {
 };
 
 // Quantizer of one table, indexed by ZIGZAG position k: divisor = 8*q[k]; half = divisor/2; magic = floor(2^28/divisor)+1
-// so that  floor(n / divisor) == (n * magic) >> 28  for every n < 2^17.
+// so that  floor(n / divisor) == (n * magic) >> 28  for every n < 2^17.  On paper: with e = magic*divisor - 2^28, 0 < e <= divisor
+// <= 2040 (8-bit tables), n*magic / 2^28 = n/divisor + n*e / (divisor * 2^28); n < 2^17 makes n*e < 2^28, so the second term is
+// below 1/divisor and cannot carry n/divisor over the next integer.  The kernels' numerators are |FDCT output| + half <= 8192 + 1020.
 struct alignas(16) EncodeQuant {
     uint32_t magic[64];
     uint32_t half[64];

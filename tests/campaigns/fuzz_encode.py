@@ -1,5 +1,6 @@
 """Random encode parameters against the oracle (dev tool, GPU box): input layouts (interleaved / planar / gray, RGB / BGR, odd
-pitches), every sampling, restart intervals, qualities 1..100 -- bitstreams must equal the oracle's byte for byte; with
+pitches), every sampling, restart intervals, qualities 1..100, one picture in four from tests/helpers/extreme_images.py (saturated
+flats, checkerboards, {0,255} random, full-range noise) instead of synth_image -- bitstreams must equal the oracle's byte for byte; with
 per-image optimized Huffman tables (which the oracle does not write) the decoded pixels must equal the decode of the
 oracle's standard-table stream (same coefficients)."""
 import sys, os, random
@@ -8,6 +9,7 @@ import numpy as np, torch
 import oracle
 from nvimagecodec_amd.lowlevel import BatchEncoder
 from nvimagecodec_amd.synth import synth_image
+from tests.helpers.extreme_images import PATTERNS, extreme_image
 
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -22,6 +24,8 @@ for rnd in range(rounds):
     for _ in range(12):
         w, h = rng.choice([rng.randrange(1, 40), rng.randrange(40, 400)]), rng.choice([rng.randrange(1, 40), rng.randrange(40, 300)])
         im = synth_image(w, h, seed=rng.randrange(1 << 30))
+        if rng.randrange(4) == 0:
+            im = extreme_image(rng.choice(PATTERNS), w, h, seed=rng.randrange(1 << 30))
         sub = "gray" if fmt == "gray" else rng.choice(["420", "422", "444", "440", "411", "410"])
         imgs.append(im); subs.append(sub); quals.append(rng.randrange(1, 101))
         if fmt == "gray":
