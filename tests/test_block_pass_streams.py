@@ -8,55 +8,11 @@ import pytest
 
 import oracle
 from helpers import jpeg_from_coefficients as jc
+from helpers.steered_streams import EOB, ZRL, c, gray_file, scan_bits
 from nvimagecodec_amd import _native as N
 from nvimagecodec_amd import lowlevel
 
-# AC table: (run << 4 | size) by code length.  00 = (0,1), 01 = ZRL, 100 = EOB, 101 = (0,2), 1100 = (1,1), 1101 = (0,3), 11100 = (2,1),
-# 1110100000000000 = (0,4): a 16-bit code.
-AC_BITS = [0, 2, 2, 2, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1]
-AC_VALS = [0x01, 0xF0, 0x00, 0x02, 0x11, 0x03, 0x21, 0x04]
-AC = jc._codes(AC_BITS, AC_VALS)
-DC = jc._codes(*jc.DC_LUMA)
-EOB, ZRL = ("eob",), ("zrl",)
 TRUNCATED, CORRUPT = 4, 5  # hipjpegStatus_t
-
-
-def c(run, value):
-    return ("c", run, value)
-
-
-def scan_bits(blocks):
-    """blocks: [(dc difference, [tokens])] -> the entropy-coded bytes (stuffed, padded with ones) -- the tokens exactly as given."""
-    bw = jc._Bits()
-    for diff, tokens in blocks:
-        nb, bits = jc._magnitude(diff)
-        bw.put(*DC[nb])
-        if nb:
-            bw.put(bits, nb)
-        for tok in tokens:
-            if tok == EOB:
-                bw.put(*AC[0x00])
-            elif tok == ZRL:
-                bw.put(*AC[0xF0])
-            else:
-                nb, bits = jc._magnitude(tok[2])
-                bw.put(*AC[(tok[1] << 4) | nb])
-                bw.put(bits, nb)
-    bw.flush()
-    return bytes(bw.out)
-
-
-def gray_file(blocks, scan=None):
-    """A one-component baseline file of len(blocks) 8x8 blocks in a row, quantizers 1."""
-    n = len(blocks)
-    out = bytearray(b"\xff\xd8")
-    out += b"\xff\xdb" + (67).to_bytes(2, "big") + b"\x00" + bytes([1] * 64)
-    out += b"\xff\xc0" + (11).to_bytes(2, "big") + b"\x08" + (8).to_bytes(2, "big") + (8 * n).to_bytes(2, "big") + b"\x01\x01\x11\x00"
-    for ident, bits, vals in ((0x00, *jc.DC_LUMA), (0x10, AC_BITS, AC_VALS)):
-        out += b"\xff\xc4" + (19 + len(vals)).to_bytes(2, "big") + bytes([ident]) + bytes(bits) + bytes(vals)
-    out += b"\xff\xda" + (8).to_bytes(2, "big") + b"\x01\x01\x00\x00\x3f\x00"
-    out += scan_bits(blocks) if scan is None else scan
-    return bytes(out + b"\xff\xd9")
 
 
 def expected(blocks):
@@ -146,11 +102,14 @@ def test_last_symbols_at_the_end_of_the_stream():
     check_good([(0, [c(0, 1)] * 63)])
 
 
+TRUNCATION_BLOCKS = [(3, [c(0, 1), c(0, -1), c(0, 2), ZRL, c(0, 1), c(0, 1), EOB]), (1, [c(0, 1)] * 63), (-2, [c(0, 3), c(0, 1), EOB]),
+                     (0, [c(0, 1), c(0, 1), c(0, 1), c(0, 1), EOB])]
+
+
 def test_truncated_streams_get_the_host_verdict():
     """Cut the scan after every byte: a stream that ends inside a block, or before the last block, is TRUNCATED for the GPU
     algorithm and for the host entropy decoder; only the whole scan decodes, and to equal coefficients."""
-    blocks = [(3, [c(0, 1), c(0, -1), c(0, 2), ZRL, c(0, 1), c(0, 1), EOB]), (1, [c(0, 1)] * 63), (-2, [c(0, 3), c(0, 1), EOB]),
-              (0, [c(0, 1), c(0, 1), c(0, 1), c(0, 1), EOB])]
+    blocks = TRUNCATION_BLOCKS
     scan = scan_bits(blocks)
     rejected = 0
     for keep in range(1, len(scan) + 1):
