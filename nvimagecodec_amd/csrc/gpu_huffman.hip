@@ -18,7 +18,8 @@
 //   huff_scan_kernel   per image: exclusive scan of completed-block counts -> first block index of every subsequence
 //   huff_copy_records_kernel  where every block starts: copies the records the last synchronisation decodes took
 //   huff_pos_kernel    walks from the converged states the subsequences without a usable record
-//   huff_blocks_kernel one lane per block: decode into LDS, store whole 128-byte lines (DC differences to a compact array)
+//   huff_blocks_kernel one lane per block: decode into LDS, store whole 128-byte lines (DC differences to a compact array);
+//                      two 256-lane teams per workgroup share one copy of the tables: 16 waves per CU
 //   huff_dc_kernel     per (image, component): DC differences -> DC values, stored into the blocks
 #include <hip/hip_runtime.h>
 
@@ -199,7 +200,8 @@ __device__ __forceinline__ void stage_pool(HJ_LDS uint16_t* pool, const HuffImag
     }
 }
 
-// per-MCU-position constants and the zigzag permutation -> LDS (needs >= 80 lanes)
+// per-MCU-position constants and the zigzag permutation -> LDS (needs >= 80 lanes).  zzw (the block pass alone) takes the permutation as
+// byte offsets into a block of int16: 2 * index, still a byte each (<= 126).
 __device__ __forceinline__ void stage_constants(uint32_t* tsel, KSlot* kslot, uint32_t* zzw, const HuffImage& im, bool with_addresses)
 {
     const int t = threadIdx.x;
@@ -217,7 +219,7 @@ __device__ __forceinline__ void stage_constants(uint32_t* tsel, KSlot* kslot, ui
     if (zzw && t >= 64 && t < 80) {
         constexpr uint8_t zz[64] = HJ_ZIGZAG_DEVICE_TABLE;
         const int i = (t - 64) * 4;
-        zzw[t - 64] = (uint32_t)zz[i] | ((uint32_t)zz[i + 1] << 8) | ((uint32_t)zz[i + 2] << 16) | ((uint32_t)zz[i + 3] << 24);
+        zzw[t - 64] = ((uint32_t)zz[i] | ((uint32_t)zz[i + 1] << 8) | ((uint32_t)zz[i + 2] << 16) | ((uint32_t)zz[i + 3] << 24)) << 1;
     }
 }
 
@@ -1085,52 +1087,74 @@ __global__ __launch_bounds__(kSyncThreads) void huff_pos_kernel(HuffImage* __res
 }
 
 // ---- write pass, step 2: one lane per block -----------------------------------------------------------------------------------
-// kHuffMcusPerWg consecutive MCUs (scan order) of one image per workgroup, 256 blocks per round.  Every lane decodes
-// its block into a 128-byte LDS buffer, and the finished blocks leave as whole 128-byte lines, eight lanes per block --
+// A TEAM of 256 lanes takes one block unit: kHuffMcusPerWg consecutive MCUs (scan order) of one image, 256 blocks per round.  Every
+// lane decodes its block into a 128-byte LDS buffer, and the finished blocks leave as whole 128-byte lines, eight lanes per block --
 // each line written once, no memset, no partial-line traffic.  Lanes idle once their block is done: chroma blocks are
-// short, luma blocks long; the wave runs as long as its longest block.  Block buffers, destination slots and the flush are a wave's
-// own (lane t flushes buffers of lanes t & ~63 ...), so between the rounds a wave only has to order its own LDS traffic: the waves
-// of a workgroup do not wait for each other's longest block.
-constexpr int kBThreads = kHuffBlocksPerWg;
-// Words of the bitstream a workgroup may stage in LDS.  0 (shipped): the lanes read the stream through the vector cache instead
-// -- a workgroup's span is ~7 KB and every word is needed by one or two neighbouring lanes, the prefetch in the bit reader covers
-// the longer latency, and without the 16 KB stage three workgroups fit a CU instead of two (A/B on 256 x 1080p: 771 us against
-// 959 us with 4096 words staged, 971 us with 2048).
-#ifndef HJ_BLOCK_STREAM_WORDS
-#define HJ_BLOCK_STREAM_WORDS 0
-#endif
-constexpr int kBStreamWords = HJ_BLOCK_STREAM_WORDS;
-constexpr int kBlockBufBytes = 144;  // 128 + 16: 16-byte aligned buffers whose starts are spread over the banks
+// short, luma blocks long; the wave runs as long as its longest block.  Block buffers and the flush are a wave's own (lane t flushes
+// buffers of lanes t & ~63 ..., and fetches their destinations with a cross-lane read), so between the rounds a wave only has to order
+// its own LDS traffic: the waves of a team do not wait for each other's longest block.
+//
+// A WORKGROUP is kBTeams = 2 teams: two consecutive units of the same image, one copy of the image's lookup tables and constants.  What
+// this buys is residency: the pass waits on latency, LDS is what limits its waves, and the table copy was the part of a workgroup's LDS
+// that bought no lanes.  Per 512 lanes: 2 x 32 KB of block buffers + the tables (13,824 B for the standard ones) + 384 B of constants
+// = 79,744 B, so two workgroups fit the CU's 160 KiB -- 16 waves per CU, four per SIMD, where 256-lane workgroups with a table copy
+// each stopped at three (static_assert below).  Larger tables (up to 24 KB): one workgroup per CU, 8 waves, as two 256-lane ones had
+// before.  Measured on 256 x 1080p: 576 us against 600 (profiles/block_pass_teams/).
+//   * The units of an image are consecutive in `units`, unit j of the image covering MCUs j * kHuffMcusPerWg ...; the grid has one
+//     workgroup per unit, and the workgroup that looks at unit j works only if j is a multiple of kBTeams: it takes units j .. j +
+//     kBTeams - 1 as far as the image has them.  The others leave at once, whole workgroups, in front of every barrier (which
+//     workgroup looks at which unit: see the kernel).  A workgroup never spans two images; an image with an odd number of units
+//     ends with a workgroup whose second team has no unit.
+//   * A team without work -- no unit, or a truncated stream whose decoded blocks end in front of its unit -- has zero items: it
+//     stages its share of the tables, arrives at both workgroup barriers, and writes zero group sums for its unit if it has one.
+//     No lane returns between the two barriers.
+//   * Each unit keeps its own four group sums: the DC pass sees what it saw with one unit per workgroup.
+constexpr int kBTeamThreads = kHuffBlocksPerWg;  // lanes of a team (one block per lane per round)
+constexpr int kBTeams = 2;                       // measured: 1 team (3 workgroups per CU) 651 us, 2: 576, 4 (one 1024-lane workgroup): 634 -- DESIGN.md §3.2
+constexpr int kBThreads = kBTeams * kBTeamThreads;
+static_assert((kBTeams & (kBTeams - 1)) == 0, "unit j starts a workgroup when j % kBTeams == 0");
+// 128-byte buffers, lane L's at byte L * 128.  The starts of a wave's buffers would all fall on bank 0; instead of padding the
+// stride (144 before: 16 bytes per lane that the budget above does not have) the 16-byte chunks inside a buffer are swizzled:
+// byte x of lane L's block lives at (L * 128 | (L & 7) << 4) ^ x.  For equal x the lanes of a wave then hit eight distinct 16-byte
+// offsets of the 128 bytes the 32 banks of a 2-byte store span -- the same spread as stride 144 (L * 144 mod 128 = (L & 7) * 16) --
+// and the store's address is one XOR of a per-lane constant with the byte offset, which the zigzag table holds ready (doubled).
+constexpr int kBlockBufBytes = 128;
 
 struct BlockShared {
-    uint32_t stream[kBStreamWords > 0 ? kBStreamWords : 1];
-    __attribute__((aligned(16))) uint8_t blocks[kBThreads * kBlockBufBytes];
-    int16_t* dst[kBThreads];
+    // the constants first: their addresses stay below 64 KB, the reach of the offset field of an LDS instruction (the zigzag byte
+    // is read in every coefficient step)
     KSlot kslot[10];
     uint32_t tsel[10];
-    uint32_t zz[16];  // zigzag permutation, 4 entries per word
-    uint32_t span[2]; // first staged word, number of staged words (0: the span does not fit, read from memory)
-    int32_t dc_sum[4];  // per component: sum of the DC differences of the workgroup's blocks
-    uint32_t kcomp[10]; // component of MCU position k
+    uint32_t zz[16];  // zigzag permutation as BYTE offsets into a block (2 * index), 4 entries per word
+    int32_t dc_sum[kBTeams][4];  // per team and component: sum of the DC differences of the team's blocks
+    uint32_t kcomp[10];          // component of MCU position k
+    __attribute__((aligned(128))) uint8_t blocks[kBThreads * kBlockBufBytes];  // 128-aligned: the swizzle XORs below bit 7
 };
+// The budget.  gfx950 hands out LDS in units of 1,280 bytes (160 KiB / 128), measured on the device: 256-lane workgroups with 53,760 B
+// are resident three per CU, with 54,272 B two (units of 512 B would still allow three); 81,920 B two, 81,921 B one
+// (profiles/block_pass_teams/lds_granule.txt).  Two workgroups with the standard tables must fit a CU: the four Annex K tables are
+// 13,696 B as the stage expands them (6,144 first-level and pair entries + 11 second-level tables of 64), 13,824 B of dynamic LDS
+// as the launcher rounds it.
+constexpr unsigned kLdsBytesPerCu = 160u * 1024u, kLdsGranule = 1280u, kStandardPoolBytes = 13824u;
+constexpr unsigned lds_allocated(unsigned bytes) { return (bytes + kLdsGranule - 1) / kLdsGranule * kLdsGranule; }
+static_assert(2 * lds_allocated((unsigned)sizeof(BlockShared) + kStandardPoolBytes) <= kLdsBytesPerCu,
+              "two 512-lane workgroups of the block pass per CU (16 waves) with the standard lookup tables");
 
 struct BlockEnv {
-    uint32_t stream_base, word0, staged;  // LDS byte address of the staged words, image index of the first, how many
     const uint32_t* gstream;
     uint32_t gwords;
-    uint32_t pool, buf;
+    uint32_t pool, buf;  // LDS byte addresses: lookup tables; this lane's block buffer with its swizzle, (L * 128 | (L & 7) << 4)
     const HJ_LDS uint32_t* tsel;
     const HJ_LDS KSlot* kslot;
     const HJ_LDS uint8_t* zz;
     static constexpr uint32_t kCursorStep = 1;  // the cursor is the word index
     __device__ __forceinline__ uint32_t cursor(uint32_t i) const { return i; }
     __device__ __forceinline__ uint32_t fetch(uint32_t i) const { return word(i); }
+    // The lanes read the stream through the vector cache: a unit's span is ~7 KB and every word is needed by one or two neighbouring
+    // lanes, the prefetch in the bit reader covers the latency, and LDS is what limits the waves (staging 4096 words per 256 lanes was
+    // measured at 959 us against 771 us without, 256 x 1080p).
     __device__ __forceinline__ uint32_t word(uint32_t i) const
     {
-        if (kBStreamWords > 0) {
-            const uint32_t local = i - word0;
-            if (local < staged) return *(const HJ_LDS uint32_t*)(uintptr_t)(stream_base + (local << 2));
-        }
         // unconditional load from a clamped index, selection afterwards: the request leaves at the top of the decode step and
         // nothing waits for it before the value is consumed at the bottom
         // (byte offset in 32 bits -- a stream is far below 4 GB: SGPR base + VGPR offset addressing)
@@ -1153,81 +1177,70 @@ struct BlockEnv {
         const uint32_t sy = s->stride_y, sx = s->stride_x;
         return base + (size_t)(my * sy + mx * sx) * 64;
     }
+    // decode_block hands zigzag()'s value to put(): here it is the coefficient's byte offset in the block, not its index
     __device__ __forceinline__ int zigzag(int z) const { return zz[z]; }
-    __device__ __forceinline__ void put(int index, int value) const { *(HJ_LDS int16_t*)(uintptr_t)(buf + index * 2) = (int16_t)value; }
+    __device__ __forceinline__ void put(int byte_offset, int value) const { *(HJ_LDS int16_t*)(uintptr_t)(buf ^ (uint32_t)byte_offset) = (int16_t)value; }
 };
 
-__global__ __launch_bounds__(kBThreads) void huff_blocks_kernel(HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
-                                                                int32_t* __restrict__ group_sums)
+// (kBThreads, 4): four waves per SIMD, i.e. at most 128 VGPRs -- two workgroups of eight waves on a CU's four SIMDs
+__global__ __launch_bounds__(kBThreads, 4) void huff_blocks_kernel(HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
+                                                                   uint32_t nunits, int32_t* __restrict__ group_sums)
 {
     __shared__ BlockShared sh;
     extern __shared__ uint16_t dyn_pool[];
     HJ_LDS uint16_t* pool = (HJ_LDS uint16_t*)dyn_pool;
-    const HuffUnit u = units[blockIdx.x];  // first = first MCU of the workgroup's kHuffMcusPerWg MCUs
-    HuffImage& im = images[u.image];
+    // Workgroup w looks at unit (w % H) * kBTeams + w / H, H = gridDim.x / kBTeams: the first H workgroups at every kBTeams-th unit,
+    // which is where the workgroups with work are unless images with an odd number of units have shifted them -- the ones that
+    // leave at once come behind them and pass through the slots the last working ones free.  (Workgroups go to the chip's eight
+    // XCDs in turn: with unit w for workgroup w the working ones, every second, all landed on four of them -- twice the time.)
+    const uint32_t per_team = gridDim.x / (uint32_t)kBTeams;
+    const uint32_t unit0 = (blockIdx.x % per_team) * (uint32_t)kBTeams + blockIdx.x / per_team;
+    if (unit0 >= nunits) return;
+    const HuffUnit u0 = units[unit0];  // first = first MCU of a unit (kHuffMcusPerWg MCUs)
+    // the unit is a second team's: the workgroup of the unit in front of it takes it (uniform: the whole workgroup leaves)
+    if ((u0.first / (uint32_t)kHuffMcusPerWg) % (uint32_t)kBTeams != 0) return;
+    HuffImage& im = images[u0.image];
     const HuffGeom geom = make_geom(im);
     const uint32_t bpm = geom.blocks_per_mcu;
     const uint32_t nblocks = min(im.total_blocks, im.decoded_blocks);  // a truncated stream: the scan kernel has flagged it
-    const uint32_t b_first = u.first * bpm;
-    const int t = threadIdx.x;
-    if (b_first >= nblocks) {
-        if (t < 4) group_sums[(size_t)blockIdx.x * 4 + t] = 0;
-        return;
-    }
-    if (t < 4) sh.dc_sum[t] = 0;
-    if (t >= 32 && t < 42) sh.kcomp[t - 32] = im.k[t - 32].comp & 3;
-    const uint32_t mcus = min((uint32_t)kHuffMcusPerWg, geom.mcus_x * geom.mcus_y - u.first);
+    const uint32_t total_mcus = geom.mcus_x * geom.mcus_y;
+    const int t = threadIdx.x, team = t / kBTeamThreads, tt = t % kBTeamThreads;
+    // the team's unit is units[unit0 + team] = {u0.image, first} if the image has it
+    const uint32_t first = u0.first + (uint32_t)team * kHuffMcusPerWg;
+    const bool has_unit = first < total_mcus;
+    const uint32_t b_first = first * bpm;
+    // nothing to decode (no unit, or the decoded blocks end in front of it): no items, but every barrier below
+    const uint32_t mcus = has_unit && b_first < nblocks ? min((uint32_t)kHuffMcusPerWg, total_mcus - first) : 0u;
     const uint32_t items = mcus * bpm;
-    if (t == 0) {
-        // the span of the stream these blocks cover: from the first block's word to the start of the block behind the last
-        const uint32_t b_end = b_first + items;
-        const uint32_t end_bit = b_end < nblocks ? im.block_pos[b_end] : geom.total_bits;
-        const uint32_t w_lo = im.block_pos[b_first] >> 5, w_hi = (end_bit >> 5) + 4;
-        sh.span[0] = w_lo;
-        sh.span[1] = (kBStreamWords > 0 && w_hi - w_lo <= (uint32_t)kBStreamWords) ? w_hi - w_lo : 0u;
-    }
+    if (t < 4 * kBTeams) sh.dc_sum[t >> 2][t & 3] = 0;
+    if (t >= 32 && t < 42) sh.kcomp[t - 32] = im.k[t - 32].comp & 3;
     stage_pool<kBThreads>(pool, im);
     stage_constants(sh.tsel, sh.kslot, sh.zz, im, true);
     HJ_LDS u32x4* my_buf = (HJ_LDS u32x4*)&sh.blocks[t * kBlockBufBytes];
 #pragma unroll
     for (int i = 0; i < kBlockBufBytes / 16; i++) my_buf[i] = u32x4{0u, 0u, 0u, 0u};
-    __syncthreads();
-    const uint32_t w_lo = sh.span[0], staged = sh.span[1];
-    {
-        const HJ_GLOBAL uint32_t* g = (const HJ_GLOBAL uint32_t*)im.stream;
-        const uint32_t gwords = im.stream_words;
-        for (uint32_t i = t; i < staged; i += kBThreads) sh.stream[i] = w_lo + i < gwords ? __builtin_bswap32(g[w_lo + i]) : ~0u;
-    }
+    __syncthreads();  // barrier 1 of 2: tables, constants and zeroed sums are in place
     BlockEnv env;
-    env.stream_base = (uint32_t)(uintptr_t)(HJ_LDS uint32_t*)sh.stream;
-    env.word0 = w_lo;
-    env.staged = staged;
     env.gstream = reinterpret_cast<const uint32_t*>(im.stream);
     env.gwords = im.stream_words;
     env.pool = (uint32_t)(uintptr_t)pool;
-    env.buf = (uint32_t)(uintptr_t)(HJ_LDS uint8_t*)&sh.blocks[t * kBlockBufBytes];
+    env.buf = (uint32_t)(uintptr_t)(HJ_LDS uint8_t*)sh.blocks + (((uint32_t)t * kBlockBufBytes) | (((uint32_t)t & 7u) << 4));
     env.tsel = (const HJ_LDS uint32_t*)sh.tsel;
     env.kslot = (const HJ_LDS KSlot*)sh.kslot;
     env.zz = (const HJ_LDS uint8_t*)sh.zz;
     uint32_t err = 0;
-    // Between the steps of a round a wave waits for its own lanes only (wave_sync: LDS operations of a wave complete in order) --
-    // unless the stream is staged in LDS, which the whole workgroup fills and reads.
-    static_assert(kBThreads % 64 == 0, "whole waves: lane t flushes the buffers of lanes (t & ~63) ...");
-    auto round_sync = [] {
-        if (kBStreamWords == 0)
-            wave_sync();
-        else
-            __syncthreads();
-    };
+    // Between the steps of a round a wave waits for its own lanes only (wave_sync: LDS operations of a wave complete in order).  The
+    // trip count is a team's own; nothing in the loop waits for another wave.
+    static_assert(kBTeamThreads % 64 == 0, "whole waves: lane t flushes the buffers of lanes (t & ~63) ...");
     // Work items are ordered by MCU position first: item i is position i / mcus of MCU i % mcus, so that the 256 lanes of
     // a round hold blocks of the same component -- luma blocks run ~4x longer than chroma blocks, and a wave takes as long
     // as its longest block.
-    for (uint32_t base = 0; base < items; base += kBThreads) {
-        round_sync();  // staged stream (first round) / zeroed buffers (later rounds) are in place
-        const uint32_t item = base + t;
+    for (uint32_t base = 0; base < items; base += kBTeamThreads) {
+        wave_sync();  // zeroed buffers are in place
+        const uint32_t item = base + tt;
         int16_t* dst = nullptr;
         if (item < items) {
-            const uint32_t k = item / mcus, mcu = u.first + (item - k * mcus);
+            const uint32_t k = item / mcus, mcu = first + (item - k * mcus);
             const uint32_t b = mcu * bpm + k;
             if (b < nblocks) {
                 const uint32_t my = mcu / geom.mcus_x, mx = mcu - my * geom.mcus_x;
@@ -1240,30 +1253,41 @@ __global__ __launch_bounds__(kBThreads) void huff_blocks_kernel(HuffImage* __res
                     err = 1;
                 const int dc = decode_block(geom, env, bpos, (int)k, &err);
                 ((HJ_GLOBAL int16_t*)geom.dc_diff)[b] = (int16_t)dc;
-                atomicAdd(&sh.dc_sum[sh.kcomp[k]], (int)(int16_t)dc);
+                atomicAdd(&sh.dc_sum[team][sh.kcomp[k]], (int)(int16_t)dc);
             }
         }
-        sh.dst[t] = dst;
-        round_sync();
-        // eight lanes per block, 16 bytes each: every store instruction writes eight whole lines
+        wave_sync();
+        // eight lanes per block, 16 bytes each: every store instruction writes eight whole lines.  Lane 8 * i + j of the wave holds
+        // the destination of the block that lanes 8 * j .. 8 * j + 7 store in step i; chunk c of lane L's buffer sits at unit c ^ (L & 7).
+        const uint32_t dst_lo = (uint32_t)(uintptr_t)dst, dst_hi = (uint32_t)((uintptr_t)dst >> 32);
+        const int lane = t & 63, chunk = t & 7;
+        // (all cross-lane reads, then all buffer reads -- a wave's own buffers, readable whether or not the block exists -- then the
+        // stores: the LDS round trips overlap instead of following each other)
+        int16_t* p[8];
+        u32x4 v[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-            const int blk = (t & ~63) + 8 * i + ((t & 63) >> 3), chunk = t & 7;
-            int16_t* p = sh.dst[blk];
-            if (p) {
-                const u32x4 v = *(const HJ_LDS u32x4*)&sh.blocks[blk * kBlockBufBytes + chunk * 16];
-                __builtin_nontemporal_store(v, (HJ_GLOBAL u32x4*)p + chunk);
-            }
+            const int src = 8 * i + (lane >> 3);
+            const uint32_t lo = (uint32_t)__shfl((int)dst_lo, src, 64), hi = (uint32_t)__shfl((int)dst_hi, src, 64);
+            p[i] = (int16_t*)(((uintptr_t)hi << 32) | lo);
         }
-        if (base + kBThreads < items) {
-            round_sync();
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int blk = (t & ~63) + 8 * i + (lane >> 3);
+            v[i] = *(const HJ_LDS u32x4*)&sh.blocks[blk * kBlockBufBytes + ((chunk ^ (blk & 7)) << 4)];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+            if (p[i]) __builtin_nontemporal_store(v[i], (HJ_GLOBAL u32x4*)p[i] + chunk);
+        if (base + kBTeamThreads < items) {
+            wave_sync();
 #pragma unroll
             for (int i = 0; i < 8; i++) my_buf[i] = u32x4{0u, 0u, 0u, 0u};
         }
     }
     if (err) im.status = 1;  // benign race: every writer stores the same value
-    __syncthreads();
-    if (t < 4) group_sums[(size_t)blockIdx.x * 4 + t] = sh.dc_sum[t];
+    __syncthreads();         // barrier 2 of 2: every team arrives, with or without items
+    if (has_unit && tt < 4) group_sums[(size_t)(unit0 + team) * 4 + tt] = sh.dc_sum[team][tt];
 }
 
 // ---- fused decode (round 3): the DC differences alone ------------------------------------------------------------------------
@@ -1541,7 +1565,8 @@ int launch_huff_write(HuffImage* images, const HuffUnit* sync_units, int nsync_u
         if (dc_only)
             hipLaunchKernelGGL(huff_dcdiff_kernel, dim3(nblock_units), dim3(kThreads), 0, (hipStream_t)stream, images, block_units, group_sums);
         else
-            hipLaunchKernelGGL(huff_blocks_kernel, dim3(nblock_units), dim3(kBThreads), pool_bytes, (hipStream_t)stream, images, block_units, group_sums);
+            hipLaunchKernelGGL(huff_blocks_kernel, dim3((nblock_units + kBTeams - 1) / kBTeams * kBTeams), dim3(kBThreads), pool_bytes, (hipStream_t)stream,
+                               images, block_units, (uint32_t)nblock_units, group_sums);
     }
     return (int)hipGetLastError();
 }

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: tools/build_variant.sh <name> "<extra hipcc flags, e.g. -DHJ_BLOCK_STREAM_WORDS=0>" [file.hip ...]
+# usage: tools/build_variant.sh <name> "<extra hipcc flags, e.g. -DHJ_MCUS_PER_WG=256>" [file.hip ...]
 # Builds nvimagecodec_amd/variants/lib_<name>.so: the named .hip files (default gpu_huffman.hip) recompiled with the flags, every
 # other object taken from the shipped build.  For A/B runs on one GPU box (tools/ab_entropy.sh); variants/ is git-ignored.
 set -e
