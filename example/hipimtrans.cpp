@@ -9,7 +9,12 @@
 //   hipimtrans -i <file|dir> [-o <dir>] [-b batch] [-w warmup batches] [-r repeats] [-q quality] [-s 444|422|420|gray]
 //              [-d device] [-t cpu threads] [-p batches in flight (decode only)] [--skip_encode] [--options "<plugin options>"] [-v]
 //              [--jpeg_encoding baseline_dct|progressive_dct] [--optimized_huffman true|false]
-//              [--devices a,b,...] [--checksums file]
+//              [--devices a,b,...] [--checksums file] [--lossless]
+// --lossless: no pixels -- every batch goes through hipjpegTranscodeBatch (include/hipjpeg.h: GPU entropy decoder, coefficient relayout
+// kernel, GPU entropy coder), which keeps the coefficients and quantization tables of the sources and changes only their coding, like
+// jpegtran -optimize / -progressive; with --jpeg_encoding, --optimized_huffman, -b and one batch in flight.  -q and -s mean nothing
+// there and are refused.  Sources the call reports as unsupported (CMYK, 16-bit tables, ...) are named and skipped; the exit status
+// is non-zero only for real failures.  The plugin ABI has no transcode call, so this mode talks to the C-ABI of the extension directly.
 // --devices a,b,... (decode only): ONE process drives several devices -- a decoder instance per entry (nvimgcodecDecoderCreate with that
 // device_id: the reference keys its worker pools by device in the same way, src/default_executor.cpp:45-58), a host thread and a queue
 // per entry; the input list is partitioned over the queues by greedy longest-processing-time on (MCU-padded coefficient bytes +
@@ -19,9 +24,11 @@
 // -p N > 1 uses what the API offers for throughput: nvimgcodecDecoderDecode returns a future as soon as the batch is scheduled
 // (include/nvimgcodec_abi.h; reference nvimgcodec.h:1455-1459), so the caller submits batch n+1 before it waits for batch n.
 #include <dirent.h>
+#include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
 #include <sys/stat.h>
 #include <time.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
@@ -33,6 +40,7 @@
 #include <thread>
 #include <vector>
 
+#include "../include/hipjpeg.h"
 #include "../include/nvimgcodec_abi.h"
 
 namespace {
@@ -68,6 +76,7 @@ struct Params {
     std::string subsampling = "420";
     bool progressive = false, optimized_huffman = false;  // nvimtrans --jpeg_encoding / --optimized_huffman (command_line_params.h:195-207)
     bool skip_encode = false;
+    bool lossless = false, quality_given = false, subsampling_given = false;
 };
 
 bool is_dir(const std::string& p)
@@ -332,6 +341,152 @@ int run_multi_device(nvimgcodecInstance_t instance, const Params& p, const std::
     return failed ? EXIT_FAILURE : EXIT_SUCCESS;
 }
 
+// ---- --lossless: the extension's own C-ABI, found next to this program like the host harness finds it
+struct TranscodeApi {
+    decltype(&hipjpegCreate) create = nullptr;
+    decltype(&hipjpegDestroy) destroy = nullptr;
+    decltype(&hipjpegTranscodeBatch) transcode = nullptr;
+    decltype(&hipjpegTranscodeBatchStats) stats = nullptr;
+    decltype(&hipjpegEncodeGetBitstream) bitstream = nullptr;
+    decltype(&hipjpegStatusString) status_string = nullptr;
+    bool load()
+    {
+        std::string dir = ".";
+        char exe[4096];
+        const ssize_t len = readlink("/proc/self/exe", exe, sizeof exe - 1);
+        if (len > 0) {
+            const std::string path(exe, (size_t)len);
+            const size_t slash = path.rfind('/');
+            if (slash != std::string::npos) dir = path.substr(0, slash);
+        }
+        void* lib = dlopen((dir + "/libhipjpeg_ext.so").c_str(), RTLD_NOW | RTLD_LOCAL);
+        if (!lib) {
+            fprintf(stderr, "cannot load the extension: %s\n", dlerror());
+            return false;
+        }
+        create = (decltype(create))dlsym(lib, "hipjpegCreate");
+        destroy = (decltype(destroy))dlsym(lib, "hipjpegDestroy");
+        transcode = (decltype(transcode))dlsym(lib, "hipjpegTranscodeBatch");
+        stats = (decltype(stats))dlsym(lib, "hipjpegTranscodeBatchStats");
+        bitstream = (decltype(bitstream))dlsym(lib, "hipjpegEncodeGetBitstream");
+        status_string = (decltype(status_string))dlsym(lib, "hipjpegStatusString");
+        return create && destroy && transcode && stats && bitstream && status_string;
+    }
+};
+
+int run_lossless(const Params& p, const std::vector<std::string>& names)
+{
+    TranscodeApi api;
+    if (!api.load()) return EXIT_FAILURE;
+    hipjpegHandle_t handle = nullptr;
+    if (api.create(&handle, p.device, p.threads) != HIPJPEG_STATUS_SUCCESS) {
+        fprintf(stderr, "hipjpegCreate failed\n");
+        return EXIT_FAILURE;
+    }
+    hipStream_t stream = nullptr;
+    CHECK_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    const size_t total_images = names.size() * (size_t)p.repeats;
+    std::vector<std::vector<unsigned char>> file_data((size_t)p.batch);
+    double t_read = 0, t_code = 0, t_write = 0;
+    size_t processed = 0, failed = 0, unsupported = 0, cursor = 0;
+    long long gpu_decoded = 0, gpu_coded = 0, blocks = 0;
+    int warm = 0;
+    double t_timed_start = wtime();
+    while (processed < total_images) {
+        const int n = (int)std::min<size_t>((size_t)p.batch, total_images - processed);
+        double t0 = wtime();
+        std::vector<std::string> current((size_t)n);
+        std::vector<const uint8_t*> data((size_t)n);
+        std::vector<size_t> lengths((size_t)n);
+        for (int i = 0; i < n; i++) {
+            current[(size_t)i] = names[(cursor + (size_t)i) % names.size()];
+            if (!read_file(current[(size_t)i], &file_data[(size_t)i])) {
+                fprintf(stderr, "cannot read %s\n", current[(size_t)i].c_str());
+                return EXIT_FAILURE;
+            }
+            data[(size_t)i] = file_data[(size_t)i].data();
+            lengths[(size_t)i] = file_data[(size_t)i].size();
+        }
+        const double reading = wtime() - t0;
+        t0 = wtime();
+        const hipjpegTranscodeParams_t one{p.optimized_huffman ? 1 : 0, p.progressive ? 1 : 0, 0, 0};
+        std::vector<hipjpegTranscodeParams_t> params((size_t)n, one);
+        std::vector<hipjpegStatus_t> status((size_t)n, HIPJPEG_STATUS_SUCCESS);
+        const hipjpegStatus_t st = api.transcode(handle, data.data(), lengths.data(), n, params.data(), HIPJPEG_FLAG_GPU_HUFFMAN, status.data(), stream);
+        if (st != HIPJPEG_STATUS_SUCCESS) {
+            fprintf(stderr, "hipjpegTranscodeBatch failed: %s\n", api.status_string(st));
+            return EXIT_FAILURE;
+        }
+        const double coding = wtime() - t0;
+        const bool timed = warm >= p.warmup;
+        t0 = wtime();
+        for (int i = 0; i < n; i++) {
+            if (status[(size_t)i] == HIPJPEG_STATUS_UNSUPPORTED) {
+                if (timed) {
+                    unsupported++;
+                    fprintf(stderr, "Skipped: %s cannot be transcoded without loss (%s)\n", current[(size_t)i].c_str(), api.status_string(status[(size_t)i]));
+                }
+                continue;
+            }
+            const uint8_t* bytes = nullptr;
+            size_t length = 0;
+            if (status[(size_t)i] != HIPJPEG_STATUS_SUCCESS || api.bitstream(handle, i, &bytes, &length) != HIPJPEG_STATUS_SUCCESS) {
+                if (timed) {
+                    failed++;
+                    fprintf(stderr, "Error: something went wrong during transcoding image %s (%s), it will not be saved\n", current[(size_t)i].c_str(),
+                            api.status_string(status[(size_t)i]));
+                }
+                continue;
+            }
+            if (p.output.empty()) continue;
+            const std::string path = p.output + "/" + current[(size_t)i].substr(current[(size_t)i].find_last_of('/') + 1);
+            FILE* f = fopen(path.c_str(), "wb");
+            const bool ok = f && fwrite(bytes, 1, length, f) == length;
+            if (f) fclose(f);
+            if (!ok) {
+                fprintf(stderr, "cannot write %s\n", path.c_str());
+                return EXIT_FAILURE;
+            }
+        }
+        const double writing = wtime() - t0;
+        if (p.verbose) fprintf(stderr, "batch of %d: read %.2f ms, transcode %.2f ms, write %.2f ms\n", n, reading * 1e3, coding * 1e3, writing * 1e3);
+        if (!timed) {
+            warm++;  // the batch is processed again once the warm-up is over
+            t_timed_start = wtime();
+            continue;
+        }
+        int32_t d = 0, c = 0, b = 0;
+        (void)api.stats(handle, &d, &c, &b);
+        gpu_decoded += d;
+        gpu_coded += c;
+        blocks += b;
+        cursor += (size_t)n;
+        processed += (size_t)n;
+        t_read += reading;
+        t_code += coding;
+        t_write += writing;
+        putchar('.');
+        fflush(stdout);
+    }
+    const double total = wtime() - t_timed_start;
+    (void)hipStreamDestroy(stream);
+    api.destroy(handle);
+    const double nb = (double)((total_images + (size_t)p.batch - 1) / (size_t)p.batch);
+    auto report = [&](const char* what, double t) {
+        printf("Total %s time: %f\n", what, t);
+        printf("Avg %s time per image: %f\n", what, t / total_images);
+        printf("Avg %s speed  (in images per sec): %f\n", what, t > 0 ? total_images / t : 0.0);
+        printf("Avg %s time per batch: %f\n\n", what, t / nb);
+    };
+    printf("\nTotal images: %zu (failed: %zu, unsupported: %zu), batch size %d\n", total_images, failed, unsupported, p.batch);
+    printf("GPU entropy decoder: %lld images, GPU entropy coder: %lld images, blocks through the relayout kernel: %lld\n", gpu_decoded, gpu_coded, blocks);
+    report("transcoding", total);
+    report("reading", t_read);
+    report("lossless coding", t_code);
+    report("writing", t_write);
+    return failed ? EXIT_FAILURE : EXIT_SUCCESS;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -345,8 +500,13 @@ int main(int argc, char** argv)
         else if (a == "-b") p.batch = atoi(next());
         else if (a == "-w") p.warmup = atoi(next());
         else if (a == "-r") p.repeats = atoi(next());
-        else if (a == "-q") p.quality = atoi(next());
-        else if (a == "-s") p.subsampling = next();
+        else if (a == "-q") {
+            p.quality = atoi(next());
+            p.quality_given = true;
+        } else if (a == "-s") {
+            p.subsampling = next();
+            p.subsampling_given = true;
+        } else if (a == "--lossless") p.lossless = true;
         else if (a == "-d") p.device = atoi(next());
         else if (a == "-t") p.threads = atoi(next());
         else if (a == "-p") p.in_flight = std::max(1, std::min(6, atoi(next())));
@@ -367,12 +527,17 @@ int main(int argc, char** argv)
         else {
             fprintf(stderr, "usage: %s -i <file|dir> [-o dir] [-b batch] [-w warmup] [-r repeats] [-q quality] [-s 444|422|420|gray] [-d device] "
                             "[-t threads] [-p batches in flight] [--skip_encode] [--jpeg_encoding baseline_dct|progressive_dct] [--optimized_huffman true|false] "
-                            "[--options str] [--devices a,b,...] [--checksums file] [-v]\n", argv[0]);
+                            "[--options str] [--devices a,b,...] [--checksums file] [--lossless] [-v]\n", argv[0]);
             return EXIT_FAILURE;
         }
     }
     if (p.input.empty() || p.batch < 1) {
         fprintf(stderr, "an input (-i) and a positive batch size are needed\n");
+        return EXIT_FAILURE;
+    }
+    if (p.lossless && (p.quality_given || p.subsampling_given || p.in_flight > 1 || !p.devices.empty() || p.skip_encode)) {
+        fprintf(stderr, "--lossless keeps the coefficients and sampling of the sources: it goes with --jpeg_encoding, --optimized_huffman, -b and -p 1 only "
+                        "(not with -q, -s, -p > 1, --devices, --skip_encode)\n");
         return EXIT_FAILURE;
     }
     if (p.output.empty()) p.skip_encode = true;
@@ -382,6 +547,7 @@ int main(int argc, char** argv)
         return EXIT_FAILURE;
     }
     CHECK_HIP(hipSetDevice(p.device));
+    if (p.lossless) return run_lossless(p, names);
 
     nvimgcodecInstance_t instance = nullptr;
     nvimgcodecInstanceCreateInfo_t ci{};

@@ -312,6 +312,42 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeFromCoefficientsGpuAlgorithmHost(int32_
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBaselineGpuAlgorithmHost(int32_t width, int32_t height, const hipjpegEncodeParams_t* params,
                                                                   const int16_t* const coef[3], uint8_t* out, size_t capacity, size_t* length);
 
+/* ---- lossless transcode: entropy decode -> coefficient relayout -> entropy coder; no pixel is computed, every coefficient of the source
+ *      survives (what jpegtran -optimize / -progressive do).  The output is the JFIF file hipjpegEncodeFromCoefficientsHost writes for the
+ *      source's geometry, coefficients and quantization tables: APP0, components 1/2/3, SOF0 or SOF2, libjpeg's dummy blocks where the MCU
+ *      grid overhangs the picture.  APPn / COM segments of the source (EXIF, ICC, comments) are NOT copied: a caller who needs them keeps
+ *      them himself.  The source's own restart interval is not carried over either.
+ *      An image is transcodable when it is SOF0 / SOF1 / SOF2 with 8-bit samples; has one component, or three with colour model YCbCr (RGB
+ *      streams -- Adobe transform 0 or component ids R, G, B -- are refused: the writer would label them YCbCr); chroma sampled 1x1 and
+ *      luma 1x1, 2x1, 2x2, 1x2, 4x1 or 4x2; every quantizer entry <= 255 and Cb, Cr tables of equal contents; every DC value in
+ *      [-1024, 1023] and every AC value in [-1023, 1023] (jchuff.c's limits for 8-bit data).  Anything else is
+ *      HIPJPEG_STATUS_UNSUPPORTED; damaged sources keep the decoder's statuses (BAD_JPEG, TRUNCATED, CORRUPT). ---- */
+typedef struct {
+    int32_t optimized_huffman; /* as hipjpegEncodeParams_t */
+    int32_t progressive;       /* as hipjpegEncodeParams_t */
+    int32_t restart_interval;  /* MCUs, 0 = none (the source's own interval is not carried over) */
+    int32_t reserved;          /* 0 */
+} hipjpegTranscodeParams_t;
+
+/* Host only, usable without a GPU: host entropy decoder -> host coder.  HIPJPEG_STATUS_BUFFER_TOO_SMALL with *out_length = needed size
+ * if capacity is insufficient (as hipjpegEncodeFromCoefficientsHost). */
+HIPJPEG_API hipjpegStatus_t hipjpegTranscodeHost(const uint8_t* data, size_t length, const hipjpegTranscodeParams_t* params, uint8_t* out,
+                                                 size_t capacity, size_t* out_length);
+/* Device: entropy decode, coef_relayout_kernel (csrc/transcode_kernels.hip: decoder layout -> coder layout, with the range check) and the
+ * entropy coder in one blocking call on `stream`; the files are then read with hipjpegEncodeGetBitstream(handle, i, ...), which reports
+ * the image's status for an image without a file.  `params`: one per image.  `flags`: HIPJPEG_FLAG_GPU_HUFFMAN puts both entropy stages
+ * on the device for every image each of them takes (the decode side honours hipjpegSetHybridHuffmanThreshold; progressive output with a
+ * restart interval goes to the host coder), HIPJPEG_FLAG_GPU_RESTART_INTERVALS as in hipjpegEncodeBatchEntropy; 0 = both stages on the
+ * host pool.  The bytes do not depend on the flags.  A failing image leaves the rest of the batch alone.  The call occupies a decode page
+ * and the encode batch of the handle: it must not overlap a hipjpegDecodeBatchSubmit / hipjpegEncodeBatchSubmit still in flight on the
+ * same handle (HIPJPEG_STATUS_INVALID_ARGUMENT). */
+HIPJPEG_API hipjpegStatus_t hipjpegTranscodeBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
+                                                  const hipjpegTranscodeParams_t* params, unsigned flags, hipjpegStatus_t* statuses, void* stream);
+/* Of the handle's last transcode batch: images the GPU entropy decoder took, images the GPU entropy coder took, blocks the relayout
+ * kernel moved (the real blocks of every image that reached it). */
+HIPJPEG_API hipjpegStatus_t hipjpegTranscodeBatchStats(hipjpegHandle_t handle, int32_t* gpu_decoded_images, int32_t* gpu_coded_images,
+                                                       int32_t* relayout_blocks);
+
 #ifdef __cplusplus
 }
 #endif

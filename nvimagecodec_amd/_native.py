@@ -38,6 +38,11 @@ class EncodeParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("quality", "subsampling", "input_format", "restart_interval", "optimized_huffman", "progressive")]
 
 
+class TranscodeParams(ctypes.Structure):
+    """hipjpegTranscodeParams_t"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("optimized_huffman", "progressive", "restart_interval", "reserved")]
+
+
 CSS = {"444": 0, "422": 1, "420": 2, "440": 3, "411": 4, "410": 5, "gray": 6}
 
 
@@ -128,5 +133,8 @@ def load():
     L.hipjpegEncodeFromCoefficientsHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
     L.hipjpegEncodeFromCoefficientsGpuAlgorithmHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
     L.hipjpegEncodeBaselineGpuAlgorithmHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
+    L.hipjpegTranscodeHost.argtypes = [vp, sz, ctypes.POINTER(TranscodeParams), vp, sz, ctypes.POINTER(sz)]
+    L.hipjpegTranscodeBatch.argtypes = [vp, vp, vp, i32, vp, ctypes.c_uint, vp, vp]
+    L.hipjpegTranscodeBatchStats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     _lib = L
     return L

@@ -15,6 +15,7 @@
 #include "entropy_decode.h"
 #include "gpu_huffman_host.h"
 #include "progressive_gpu_host.h"
+#include "transcode_core.h"
 
 namespace hipjpeg {
 
@@ -222,11 +223,26 @@ hipjpegStatus_t DecodeBatch::plan(const uint8_t* const* data, const size_t* leng
                                   hipjpegOutputFormat_t format, unsigned flags, hipjpegStatus_t* statuses,
                                   const hipjpegOutputFormat_t* formats, ForkJoinPool* pool, const hipjpegTransform_t* transforms)
 {
+    pool_ = pool;
+    coef_only_ = false;
+    return plan_attempts(PlanArgs{data, lengths, outputs, format, flags, formats, transforms, nullptr}, n, statuses);
+}
+
+hipjpegStatus_t DecodeBatch::plan_coefficients(const uint8_t* const* data, const size_t* lengths, int n, unsigned flags, hipjpegStatus_t* statuses,
+                                               ForkJoinPool* pool)
+{
+    pool_ = pool;
+    coef_only_ = true;
+    return plan_attempts(PlanArgs{data, lengths, nullptr, HIPJPEG_OUTPUT_RGBI, flags & HIPJPEG_FLAG_GPU_HUFFMAN, nullptr, nullptr, nullptr}, n, statuses);
+}
+
+hipjpegStatus_t DecodeBatch::plan_attempts(const PlanArgs& a, int n, hipjpegStatus_t* statuses)
+{
     // An allocation that fails costs only the images that made the arenas grow: the biggest remaining image is given up
     // (ALLOC_FAILED) and the layout is computed again without it.
     std::vector<char> give_up((size_t)std::max(n, 0), 0);
-    pool_ = pool;
-    const PlanArgs args{data, lengths, outputs, format, flags, formats, transforms, give_up.data()};
+    PlanArgs args = a;
+    args.give_up = give_up.data();
     for (int attempt = 0;; attempt++) {
         const hipjpegStatus_t st = plan_once(args, n, statuses);
         if (st != HIPJPEG_STATUS_ALLOC_FAILED || attempt >= 16) return st;
@@ -247,7 +263,7 @@ hipjpegStatus_t DecodeBatch::plan(const uint8_t* const* data, const size_t* leng
 
 hipjpegStatus_t DecodeBatch::plan_once(const PlanArgs& a, int n, hipjpegStatus_t* statuses)
 {
-    if (n < 0 || (n > 0 && (!a.data || !a.lengths || !a.outputs))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (n < 0 || (n > 0 && (!a.data || !a.lengths || (!a.outputs && !coef_only_)))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if ((int)a.format < 0 || (int)a.format > (int)HIPJPEG_OUTPUT_YUV_PLANAR) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     ScopedRange range("hipjpeg plan (parse headers, lay out staging)");
     fault_point("plan");
@@ -305,11 +321,18 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
     im.status = a.data[i] ? status_from_parse(parse_jpeg(a.data[i], a.lengths[i], &im.frame)) : HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (im.status == HIPJPEG_STATUS_SUCCESS && ((uint64_t)f.width * (uint64_t)f.height * (uint64_t)f.ncomp >= max_image_samples() || a.give_up[i]))
         im.status = HIPJPEG_STATUS_ALLOC_FAILED;  // this image only; its neighbours decode
-    if (im.status == HIPJPEG_STATUS_SUCCESS && !choose_variant(f, fmt, fancy, &im.variant)) im.status = HIPJPEG_STATUS_UNSUPPORTED;
-    for (int p = 0; im.status == HIPJPEG_STATUS_SUCCESS && p < (fmt == kOutPlanarYUV ? f.ncomp : out_planes(fmt)); p++)
-        if (!a.outputs[i].plane[p]) im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
-    if (im.status == HIPJPEG_STATUS_SUCCESS && a.transforms) im.status = normalise_transform(im, a.transforms[i], fmt);
-    if (im.status == HIPJPEG_STATUS_SUCCESS && !pitch_ok(i, a.outputs[i], fmt)) im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (coef_only_) {
+        // coefficients only: no kernel variant (-4: no pixel work at all), no output to check; what counts is whether the coder takes it
+        TranscodePicture pic;
+        im.variant = -4;
+        if (im.status == HIPJPEG_STATUS_SUCCESS) im.status = transcode_picture(f, &pic);
+    } else {
+        if (im.status == HIPJPEG_STATUS_SUCCESS && !choose_variant(f, fmt, fancy, &im.variant)) im.status = HIPJPEG_STATUS_UNSUPPORTED;
+        for (int p = 0; im.status == HIPJPEG_STATUS_SUCCESS && p < (fmt == kOutPlanarYUV ? f.ncomp : out_planes(fmt)); p++)
+            if (!a.outputs[i].plane[p]) im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
+        if (im.status == HIPJPEG_STATUS_SUCCESS && a.transforms) im.status = normalise_transform(im, a.transforms[i], fmt);
+        if (im.status == HIPJPEG_STATUS_SUCCESS && !pitch_ok(i, a.outputs[i], fmt)) im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
+    }
     const bool want_gpu_entropy = (a.flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0;
     const bool big_enough = (uint64_t)f.width * (uint64_t)f.height > gpu_entropy_min_pixels_ || gpu_entropy_min_pixels_ == 0;
     if (im.status == HIPJPEG_STATUS_SUCCESS && want_gpu_entropy && big_enough && gpu_entropy_eligible(f)) {
@@ -344,7 +367,7 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
     d.color_model = (uint32_t)f.color;
     d.out_format = (uint32_t)fmt;
     d.flags = (fancy ? kFlagFancyUpsampling : 0) | (f.saw_adobe ? kFlagAdobeMarker : 0);
-    for (int p = 0; p < 3; p++) {
+    for (int p = 0; p < 3 && a.outputs; p++) {
         d.out[p] = static_cast<uint8_t*>(a.outputs[i].plane[p]);
         d.out_pitch[p] = a.outputs[i].pitch[p];
     }
@@ -544,7 +567,7 @@ void DecodeBatch::layout(const Sizing& s)
     L.coef = c.take(0);
     // HIPJPEG_DENSE_STAGING=1: dense int16 blocks for every host-decoded picture as in rounds 1-2 (A/B and cross-check aid)
     static const bool sparse_enabled = getenv("HIPJPEG_DENSE_STAGING") == nullptr;
-    sparse_mode_ = sparse_enabled;
+    sparse_mode_ = sparse_enabled && !coef_only_;  // (the relayout kernel reads dense blocks)
     host_coef_used_.store(0);
     for (int pass = 0; pass < 2; pass++) {  // host-decoded images first, GPU-decoded ones behind the H2D boundary
         if (pass == 1) {
@@ -766,7 +789,7 @@ void DecodeBatch::finalize(hipjpegStatus_t* statuses)
     // its TIME rises (2.72 -> 3.20 ms per 256 x 1080p): both halves are bound by instruction issue, and inside the pixel kernels only 32
     // of a wave's 64 lanes have a block to decode.  Off by default; kept as a switch and covered by the parity tests.
     static const bool fused_enabled = getenv("HIPJPEG_FUSED_DECODE") != nullptr && atoi(getenv("HIPJPEG_FUSED_DECODE")) != 0;
-    fused_ = fused_enabled && !fast_idct_;  // the FUSED builds compute ISLOW only: a fast-IDCT batch takes the plain ones
+    fused_ = fused_enabled && !fast_idct_ && !coef_only_;  // the FUSED builds compute ISLOW only: a fast-IDCT batch takes the plain ones; they write no blocks
     // all or nothing per batch: with fused_ set the block pass is not launched at all, so every GPU-decoded baseline picture must be one the
     // FUSED builds cover completely -- a region of interest launches only the tiles that touch it, the other blocks would go undecoded and
     // unchecked

@@ -90,6 +90,14 @@ public:
                          hipjpegOutputFormat_t format, unsigned flags, hipjpegStatus_t* statuses,
                          const hipjpegOutputFormat_t* formats = nullptr, ForkJoinPool* pool = nullptr,
                          const hipjpegTransform_t* transforms = nullptr);
+    // Lossless transcode (hipjpegTranscodeBatch): plans the entropy stage alone -- no outputs, no pixel kernels, no geometry; the
+    // coefficients stay in HBM in the decoder's layout, host-decoded pictures as dense blocks.  Of `flags` only
+    // HIPJPEG_FLAG_GPU_HUFFMAN counts.  Sources the coder cannot take (transcode_core.h transcode_picture) are UNSUPPORTED.
+    // Then entropy_stage() per image, finalize(), transfer() and launch(stream, 3) as for any batch.
+    hipjpegStatus_t plan_coefficients(const uint8_t* const* data, const size_t* lengths, int n, unsigned flags, hipjpegStatus_t* statuses,
+                                      ForkJoinPool* pool);
+    // The batch's DecodeImage table as the kernels see it (valid after transfer()).
+    const DecodeImage* device_descriptors() const { return at<const DecodeImage>(device_, staging_.desc); }
     // GPU entropy stage only for images of MORE than this many pixels (width x height); smaller ones keep the host Huffman decoder.
     // The reference's nvJPEG plugin has the same switch between its HYBRID and GPU_HYBRID backends (`hybrid_huffman_threshold`,
     // extensions/nvjpeg/cuda_decoder.cpp:188-209, 512-521; default 1000 x 1000 there).  Default here 0: every eligible stream goes to
@@ -144,6 +152,8 @@ private:
     // ---- plan(): per-image checks and descriptors, sizes, layout of the arenas, device pointers
     struct PlanArgs;  // plan()'s arguments as prepare() reads them
     struct Sizing;    // what the per-image sizing adds up
+    hipjpegStatus_t plan_attempts(const PlanArgs& a, int n, hipjpegStatus_t* statuses);
+    bool coef_only_ = false;  // the batch was planned by plan_coefficients()
     hipjpegStatus_t plan_once(const PlanArgs& a, int n, hipjpegStatus_t* statuses);
     void prepare(int i, const PlanArgs& a);
     bool pitch_ok(int i, const hipjpegOutput_t& out, OutFormat fmt) const;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -96,6 +97,7 @@ hipjpegStatus_t EncodeBatch::device_stage(const hipjpegEncodeInput_t* inputs, co
     desc_.assign(n, EncodeImage());
     host_coder_.assign(n, 0);
     units_.clear();
+    relayout_units_.clear();
     for (auto& v : unit_lists_) v.clear();
     coef_total_ = 0;
     pixel_bytes_ = coef_bytes_ = 0;
@@ -203,6 +205,8 @@ void EncodeBatch::layout()
     Carve c;
     staging_.desc = c.take(sizeof(EncodeImage) * desc_.size());
     staging_.units = c.take(sizeof(EncodeUnit) * units_.size());
+    staging_.relayout = c.take(sizeof(RelayoutUnit) * relayout_units_.size());
+    staging_.flags = c.take(relayout_units_.empty() ? 0 : sizeof(uint32_t) * images_.size());
     staging_.coef = c.take(coef_total_);
     staging_.total = c.end;
 }
@@ -223,6 +227,8 @@ void EncodeBatch::bind_pointers()
     }
     copy_table(pinned_desc_, staging_.desc, desc_);
     copy_table(pinned_desc_, staging_.units, units_);
+    copy_table(pinned_desc_, staging_.relayout, relayout_units_);
+    if (!relayout_units_.empty()) memset(pinned_desc_.data() + staging_.flags, 0, sizeof(uint32_t) * images_.size());
 }
 
 hipjpegStatus_t EncodeBatch::relaunch(void* stream)
@@ -247,6 +253,93 @@ hipjpegStatus_t EncodeBatch::relaunch(void* stream)
     launched_ = true;
     fetched_ = false;
     stream_ = stream;
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+// ---------------------------------------------------------------- coefficient_stage
+hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, int n, const DecodeImage* src, void* stream)
+{
+    if (n < 0 || (n > 0 && (!pics || !src))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(device_id_) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    if (launched_ && event_) (void)hipEventSynchronize((hipEvent_t)event_);  // previous use of the buffers must have drained
+    launched_ = fetched_ = false;
+    images_.assign(n, PlannedEncode());
+    desc_.assign(n, EncodeImage());
+    host_coder_.assign(n, 0);
+    units_.clear();
+    relayout_units_.clear();
+    for (auto& v : unit_lists_) v.clear();
+    coef_total_ = 0;
+    pixel_bytes_ = coef_bytes_ = 0;
+    relayout_blocks_ = 0;
+    gpu_entropy_images_ = 0;
+    for (int i = 0; i < n; i++) {
+        PlannedEncode& im = images_[i];
+        im.status = pics[i].status;
+        if (im.status != HIPJPEG_STATUS_SUCCESS) continue;
+        im.geom = pics[i].picture.geom;
+        im.params = pics[i].params;
+        memcpy(im.qlum, pics[i].picture.qlum, sizeof im.qlum);
+        memcpy(im.qchr, pics[i].picture.qchr, sizeof im.qchr);
+        const EncodeGeometry& g = im.geom;
+        EncodeImage& d = desc_[i];
+        memset(&d, 0, sizeof d);
+        d.width = (uint32_t)g.width;
+        d.height = (uint32_t)g.height;
+        d.ncomp = (uint32_t)g.ncomp;
+        d.hs = (uint32_t)g.hs;
+        d.vs = (uint32_t)g.vs;
+        for (int c = 0; c < g.ncomp; c++) {
+            d.blocks_w[c] = (uint32_t)g.blocks_w[c];
+            d.blocks_h[c] = (uint32_t)g.blocks_h[c];
+            d.real_w[c] = (uint32_t)g.real_w[c];
+            d.real_h[c] = (uint32_t)g.real_h[c];
+            im.coef_offset[c] = coef_total_;
+            coef_total_ += (size_t)g.blocks_w[c] * g.blocks_h[c] * 128;
+            const uint32_t nreal = (uint32_t)(g.real_w[c] * g.real_h[c]);
+            for (uint32_t b = 0; b < nreal; b += kRelayoutBlocksPerUnit) relayout_units_.push_back(RelayoutUnit{(uint32_t)i, (uint32_t)c, b, 0u});
+            relayout_blocks_ += nreal;
+        }
+    }
+    coef_bytes_ = relayout_blocks_ * 128;
+    layout();
+    hipjpegStatus_t st;
+    if ((st = reserve()) != HIPJPEG_STATUS_SUCCESS) return st;
+    bind_pointers();
+    stream_ = stream;
+    hipStream_t s = (hipStream_t)stream;
+    if (staging_.coef && hipMemcpyAsync(device_.data(), pinned_desc_.data(), staging_.coef, hipMemcpyHostToDevice, s) != hipSuccess)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    // HIPJPEG_DEBUG_TIMING (debug aid, as in the decode host stage): the kernel's own time on stderr (tools/prof_transcode.py reads it)
+    static const bool timing = getenv("HIPJPEG_DEBUG_TIMING") != nullptr;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (timing && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, s) != hipSuccess)) return HIPJPEG_STATUS_HIP_ERROR;
+    if (launch_coef_relayout(src, at<const EncodeImage>(device_, staging_.desc), at<const RelayoutUnit>(device_, staging_.relayout),
+                             (int)relayout_units_.size(), at<uint32_t>(device_, staging_.flags), stream) != 0)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    if (timing && hipEventRecord(t1, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+    uint32_t* flags = at<uint32_t>(pinned_desc_, staging_.flags);
+    if (!relayout_units_.empty() &&
+        hipMemcpyAsync(flags, device_.data() + staging_.flags, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    if (!event_) {
+        hipEvent_t ev;
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+        event_ = ev;
+    }
+    if (hipEventRecord((hipEvent_t)event_, s) != hipSuccess || hipEventSynchronize((hipEvent_t)event_) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+    launched_ = true;
+    if (timing) {
+        float ms = 0;
+        (void)hipEventSynchronize(t1);
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        fprintf(stderr, "[hipjpeg] coef_relayout_kernel: %zu workgroups, %llu blocks, %.4f ms\n", relayout_units_.size(), (unsigned long long)relayout_blocks_, ms);
+        (void)hipEventDestroy(t0);
+        (void)hipEventDestroy(t1);
+    }
+    // the range guard: such values are outside what the coders' tables cover, so no coder gets to see them
+    for (int i = 0; i < n && !relayout_units_.empty(); i++)
+        if (images_[i].status == HIPJPEG_STATUS_SUCCESS && flags[i] != 0) images_[i].status = HIPJPEG_STATUS_UNSUPPORTED;
     return HIPJPEG_STATUS_SUCCESS;
 }
 

@@ -10,6 +10,8 @@
 #include "entropy_encode.h"
 #include "gpu_huffman_encode.h"
 #include "staging.h"
+#include "transcode_core.h"
+#include "transcode_kernels.h"
 
 namespace hipjpeg {
 
@@ -24,6 +26,14 @@ struct PlannedEncode {
     size_t gpu_bitstream_len = 0;
     const uint8_t* file() const { return gpu_bitstream ? gpu_bitstream : bitstream.data(); }
     size_t file_size() const { return gpu_bitstream ? gpu_bitstream_len : bitstream.size(); }
+};
+
+// Lossless transcode: a picture given by its geometry, quantization tables and coding parameters instead of pixels; its coefficients
+// lie in HBM in the decoder's layout.  status != SUCCESS: the image has no source (it keeps that status and gets no file).
+struct CoefficientPicture {
+    hipjpegStatus_t status = HIPJPEG_STATUS_SUCCESS;
+    TranscodePicture picture;
+    hipjpegEncodeParams_t params{};  // restart_interval, optimized_huffman, progressive; the rest is not read
 };
 
 // Flavours of the forward kernel, in the order their unit lists lie in the units table.
@@ -43,6 +53,12 @@ public:
     hipjpegStatus_t device_stage(const hipjpegEncodeInput_t* inputs, const hipjpegEncodeParams_t* params, int n, hipjpegStatus_t* statuses,
                                  void* stream);
     hipjpegStatus_t relaunch(void* stream);
+    // Lossless transcode, in place of device_stage(): plans picture i from pics[i], reserves the coefficient area and lets
+    // coef_relayout_kernel fill it from `src` (the DecodeImage table of the batch that decoded the same pictures, same indices) on
+    // `stream`.  Blocks until the kernel's range flags are back: an image with a coefficient outside jchuff.c's limits becomes
+    // UNSUPPORTED before any coder sees it.  route_entropy() / entropy_stage() follow as after device_stage().
+    hipjpegStatus_t coefficient_stage(const CoefficientPicture* pics, int n, const DecodeImage* src, void* stream);
+    uint64_t relayout_blocks() const { return relayout_blocks_; }  // blocks the last coefficient_stage() moved
     // Coefficients D2H (on the stream used by device_stage), wait.
     hipjpegStatus_t fetch_coefficients();
     // Decides who entropy-codes each planned image: with gpu_huffman the GPU coder (blocking) takes every image it can -- Annex-K
@@ -76,9 +92,12 @@ private:
     size_t unit_first_[kNumFwdFlavours] = {};
     // Descriptor arena, pinned and mirrored on the device at the same offsets: EncodeImage[] | EncodeUnit[] (the upload, [0, coef))
     // || (device only) the coefficients, which pinned_coef_ receives at offset 0.
+    // (coefficient_stage(): relayout units and one range-flag word per image ride in the upload, the flags as zeros)
     struct EncodeStaging {
-        size_t desc, units, coef, total;
+        size_t desc, units, relayout, flags, coef, total;
     } staging_{};
+    std::vector<RelayoutUnit> relayout_units_;
+    uint64_t relayout_blocks_ = 0;
     size_t coef_total_ = 0;
     uint64_t pixel_bytes_ = 0, coef_bytes_ = 0;
     void* stream_ = nullptr;

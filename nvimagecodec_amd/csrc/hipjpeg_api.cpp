@@ -16,6 +16,7 @@
 #include "progressive_encode.h"
 #include "progressive_gpu_host.h"
 #include "thread_pool.h"
+#include "transcode_core.h"
 
 #include <chrono>
 #include <future>
@@ -79,6 +80,8 @@ struct hipjpegHandle {
     static constexpr int kEncodePages = 3;
     EncodePage encode_pages[kEncodePages];
     int encode_next = 0, encode_oldest = 0, encode_in_flight = 0;
+    // the last hipjpegTranscodeBatch: images on the GPU entropy decoder / coder, blocks through the relayout kernel
+    int32_t transcode_gpu_decoded = 0, transcode_gpu_coded = 0, transcode_blocks = 0;
 };
 
 extern "C" {
@@ -738,6 +741,69 @@ hipjpegStatus_t hipjpegEncodeBaselineGpuAlgorithmHost(int32_t width, int32_t hei
     *length = bytes.size();
     if (!out || capacity < bytes.size()) return HIPJPEG_STATUS_BUFFER_TOO_SMALL;
     memcpy(out, bytes.data(), bytes.size());
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+// ---------------------------------------------------------------- lossless transcode
+// (hipjpegTranscodeHost: transcode_core.cpp, with the rest of the host route)
+hipjpegStatus_t hipjpegTranscodeBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
+                                      const hipjpegTranscodeParams_t* params, unsigned flags, hipjpegStatus_t* statuses, void* stream)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle || batch_size < 0 || (batch_size > 0 && (!data || !lengths || !params))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    // the call takes a decode page and the encode batch for itself: nothing submitted may still be using either
+    if (handle->num_submitted != 0 || handle->encode_in_flight != 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    handle->transcode_gpu_decoded = handle->transcode_gpu_coded = handle->transcode_blocks = 0;
+    // (the call blocks and nothing is submitted: the current decode page is free, and staying on it keeps its arenas warm)
+    DecodeBatch& d = handle->cur();
+    // decode side: the entropy stage alone, verdicts settled (launch 3 = entropy kernels + resolve) before anything is coded
+    hipjpegStatus_t st = d.plan_coefficients(data, lengths, batch_size, flags, nullptr, handle->pool.get());
+    if (st != HIPJPEG_STATUS_SUCCESS) return st;
+    for (int i = 0; i < batch_size; i++)
+        if (transcode_params_ok(params[i]) != HIPJPEG_STATUS_SUCCESS) d.reject(i, HIPJPEG_STATUS_INVALID_ARGUMENT);
+    handle->pool->parallel_for(batch_size, [&](int i, int) { d.entropy_stage(i); });
+    d.finalize(nullptr);
+    if ((st = d.transfer(stream)) != HIPJPEG_STATUS_SUCCESS || (st = d.launch(stream, 3)) != HIPJPEG_STATUS_SUCCESS) {
+        (void)hipStreamSynchronize((hipStream_t)stream);  // nothing of this batch stays queued behind an error
+        return st;
+    }
+    // encode side: the pictures by geometry and the source's tables, the coefficient area filled by the relayout kernel
+    std::vector<CoefficientPicture> pics((size_t)batch_size);
+    for (int i = 0; i < batch_size; i++) {
+        CoefficientPicture& p = pics[(size_t)i];
+        p.status = d.image(i).status;
+        if (p.status == HIPJPEG_STATUS_SUCCESS) p.status = transcode_picture(d.image(i).frame, &p.picture);
+        if (p.status != HIPJPEG_STATUS_SUCCESS) continue;
+        p.params.restart_interval = params[i].restart_interval;
+        p.params.optimized_huffman = params[i].optimized_huffman;
+        p.params.progressive = params[i].progressive;
+    }
+    EncodeBatch& e = *handle->encode;
+    handle->encode_view = &e;
+    if ((st = e.coefficient_stage(pics.data(), batch_size, d.device_descriptors(), stream)) != HIPJPEG_STATUS_SUCCESS) {
+        (void)hipStreamSynchronize((hipStream_t)stream);
+        return st;
+    }
+    if ((st = e.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0, (flags & HIPJPEG_FLAG_GPU_RESTART_INTERVALS) != 0)) != HIPJPEG_STATUS_SUCCESS) return st;
+    if (e.host_images()) handle->pool->parallel_for(e.size(), [&](int i, int) { e.entropy_stage(i); });
+    if (statuses)
+        for (int i = 0; i < batch_size; i++) statuses[i] = e.image(i).status;
+    handle->transcode_gpu_decoded = d.gpu_entropy_images();
+    handle->transcode_gpu_coded = (int32_t)e.gpu_entropy_images();
+    handle->transcode_blocks = (int32_t)e.relayout_blocks();
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+hipjpegStatus_t hipjpegTranscodeBatchStats(hipjpegHandle_t handle, int32_t* gpu_decoded_images, int32_t* gpu_coded_images, int32_t* relayout_blocks)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (gpu_decoded_images) *gpu_decoded_images = handle->transcode_gpu_decoded;
+    if (gpu_coded_images) *gpu_coded_images = handle->transcode_gpu_coded;
+    if (relayout_blocks) *relayout_blocks = handle->transcode_blocks;
     return HIPJPEG_STATUS_SUCCESS;
     });
 }

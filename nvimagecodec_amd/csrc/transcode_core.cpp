@@ -1,0 +1,130 @@
+// transcode_core.cpp -- see transcode_core.h
+#include "transcode_core.h"
+
+#include <cstring>
+#include <new>
+
+#include "entropy_decode.h"
+
+namespace hipjpeg {
+
+hipjpegStatus_t transcode_picture(const FrameInfo& f, TranscodePicture* p)
+{
+    if (f.precision != 8 || (f.sof != 0xC0 && f.sof != 0xC1 && f.sof != 0xC2)) return HIPJPEG_STATUS_UNSUPPORTED;
+    if (f.width < 1 || f.height < 1 || f.width > 65535 || f.height > 65535) return HIPJPEG_STATUS_UNSUPPORTED;
+    EncodeGeometry& g = p->geom;
+    g = EncodeGeometry();
+    g.width = f.width;
+    g.height = f.height;
+    if (f.ncomp == 1) {
+        // one component: its sampling factors mean nothing (the scan is not interleaved), the writer says 1x1
+        g.ncomp = 1;
+        g.hs = g.vs = 1;
+    } else if (f.ncomp == 3 && f.color == ColorModel::YCbCr) {
+        g.ncomp = 3;
+        g.hs = f.comp[0].h;
+        g.vs = f.comp[0].v;
+        for (int c = 1; c < 3; c++)
+            if (f.comp[c].h != 1 || f.comp[c].v != 1) return HIPJPEG_STATUS_UNSUPPORTED;
+        const bool known = (g.vs == 1 && (g.hs == 1 || g.hs == 2 || g.hs == 4)) || (g.vs == 2 && (g.hs == 1 || g.hs == 2 || g.hs == 4));
+        if (!known) return HIPJPEG_STATUS_UNSUPPORTED;
+        if (memcmp(f.qtab[1], f.qtab[2], sizeof f.qtab[1]) != 0) return HIPJPEG_STATUS_UNSUPPORTED;  // the writer has one chroma table
+    } else {
+        return HIPJPEG_STATUS_UNSUPPORTED;
+    }
+    for (int c = 0; c < f.ncomp; c++)
+        for (int j = 0; j < 64; j++)
+            if (f.qtab[c][j] > 255 || f.qtab[c][j] == 0) return HIPJPEG_STATUS_UNSUPPORTED;  // the writer emits 8-bit DQTs
+    compute_geometry(&g);
+    // the decoder's grid must hold the blocks the coder reads (it always does: both pad to whole MCUs of the same frame)
+    for (int c = 0; c < g.ncomp; c++)
+        if (g.real_w[c] > f.comp[c].blocks_w || g.real_h[c] > f.comp[c].blocks_h) return HIPJPEG_STATUS_UNSUPPORTED;
+    memcpy(p->qlum, f.qtab[0], sizeof p->qlum);
+    memcpy(p->qchr, f.qtab[f.ncomp == 3 ? 1 : 0], sizeof p->qchr);
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+hipjpegStatus_t transcode_params_ok(const hipjpegTranscodeParams_t& p)
+{
+    return (p.restart_interval < 0 || p.restart_interval > 65535 || p.reserved != 0) ? HIPJPEG_STATUS_INVALID_ARGUMENT : HIPJPEG_STATUS_SUCCESS;
+}
+
+EntropyEncodeOptions transcode_options(const hipjpegTranscodeParams_t& p)
+{
+    return EntropyEncodeOptions{p.restart_interval, p.optimized_huffman != 0, p.progressive != 0};
+}
+
+hipjpegStatus_t transcode_host(const uint8_t* data, size_t size, const hipjpegTranscodeParams_t& params, std::vector<uint8_t>* out)
+{
+    hipjpegStatus_t st = transcode_params_ok(params);
+    if (st != HIPJPEG_STATUS_SUCCESS) return st;
+    FrameInfo f;
+    const ParseStatus ps = parse_jpeg(data, size, &f);
+    if (ps != kParseOk) return ps == kParseUnsupported ? HIPJPEG_STATUS_UNSUPPORTED : ps == kParseTruncated ? HIPJPEG_STATUS_TRUNCATED : HIPJPEG_STATUS_BAD_JPEG;
+    TranscodePicture pic;
+    if ((st = transcode_picture(f, &pic)) != HIPJPEG_STATUS_SUCCESS) return st;
+    // the decoder's blocks: column-major over the frame's MCU-padded grid
+    std::vector<int16_t> src(f.total_blocks() * 64, 0);
+    int16_t* sptr[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t off = 0;
+    for (int c = 0; c < f.ncomp; c++) {
+        sptr[c] = src.data() + off;
+        off += (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 64;
+    }
+    switch (decode_coefficients(data, size, f, sptr)) {
+    case kEntropyOk: break;
+    case kEntropyTruncated: return HIPJPEG_STATUS_TRUNCATED;
+    case kEntropyMissingTable: return HIPJPEG_STATUS_BAD_JPEG;
+    default: return HIPJPEG_STATUS_CORRUPT;
+    }
+    // the coder's blocks: zigzag order over its own grid; only the real area is read
+    const EncodeGeometry& g = pic.geom;
+    std::vector<int16_t> dst;
+    size_t doff[3] = {0, 0, 0}, total = 0;
+    for (int c = 0; c < g.ncomp; c++) {
+        doff[c] = total;
+        total += (size_t)g.blocks_w[c] * g.blocks_h[c] * 64;
+    }
+    dst.assign(total, 0);
+    int from[64];  // zigzag index -> position in the decoder's block (column * 8 + row)
+    for (int k = 0; k < 64; k++) from[k] = (kZigzagNatural[k] & 7) * 8 + (kZigzagNatural[k] >> 3);
+    for (int c = 0; c < g.ncomp; c++)
+        for (int by = 0; by < g.real_h[c]; by++)
+            for (int bx = 0; bx < g.real_w[c]; bx++) {
+                const int16_t* s = sptr[c] + ((size_t)by * f.comp[c].blocks_w + bx) * 64;
+                int16_t* d = dst.data() + doff[c] + ((size_t)by * g.blocks_w[c] + bx) * 64;
+                if (s[0] < kTranscodeDcMin || s[0] > kTranscodeDcMax) return HIPJPEG_STATUS_UNSUPPORTED;
+                d[0] = s[0];
+                for (int k = 1; k < 64; k++) {
+                    const int v = s[from[k]];
+                    if (v < -kTranscodeAcMax || v > kTranscodeAcMax) return HIPJPEG_STATUS_UNSUPPORTED;
+                    d[k] = (int16_t)v;
+                }
+            }
+    const int16_t* coef[3] = {nullptr, nullptr, nullptr};
+    for (int c = 0; c < g.ncomp; c++) coef[c] = dst.data() + doff[c];
+    encode_jfif(g, pic.qlum, pic.qchr, coef, transcode_options(params), out);
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+}  // namespace hipjpeg
+
+// The host route's C entry point lives here, not in hipjpeg_api.cpp, so that it links without the HIP runtime (tests/sanitizers).
+extern "C" hipjpegStatus_t hipjpegTranscodeHost(const uint8_t* data, size_t length, const hipjpegTranscodeParams_t* params, uint8_t* out,
+                                                size_t capacity, size_t* out_length)
+{
+    try {  // no C++ exception crosses the C boundary
+        if (!data || !params || !out_length) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+        std::vector<uint8_t> bytes;
+        const hipjpegStatus_t st = hipjpeg::transcode_host(data, length, *params, &bytes);
+        if (st != HIPJPEG_STATUS_SUCCESS) return st;
+        *out_length = bytes.size();
+        if (!out || capacity < bytes.size()) return HIPJPEG_STATUS_BUFFER_TOO_SMALL;
+        memcpy(out, bytes.data(), bytes.size());
+        return HIPJPEG_STATUS_SUCCESS;
+    } catch (const std::bad_alloc&) {
+        return HIPJPEG_STATUS_ALLOC_FAILED;
+    } catch (...) {
+        return HIPJPEG_STATUS_INTERNAL_ERROR;
+    }
+}

@@ -541,3 +541,86 @@ class BatchEncoder:
         pb, cb = ctypes.c_uint64(), ctypes.c_uint64()
         N.load().hipjpegEncodeBatchStats(self._h, ctypes.byref(u), ctypes.byref(pb), ctypes.byref(cb))
         return dict(units=u.value, pixel_bytes=pb.value, coef_bytes=cb.value, gpu_entropy_images=int(N.load().hipjpegEncodeBatchGpuEntropyImages(self._h)))
+
+
+def transcode_host(data, optimized_huffman=False, progressive=False, restart_interval=0):
+    """Lossless transcode on the host (no GPU): host entropy decoder -> host coder.  The file keeps every coefficient and the
+    quantization tables of the source; APPn / COM segments are not copied.  Raises HipJpegError: UNSUPPORTED for sources the coder
+    cannot take (include/hipjpeg.h lists the rules), the decoder's statuses for damaged ones."""
+    a = _as_u8(data)
+    p = N.TranscodeParams(int(bool(optimized_huffman)), int(bool(progressive)), int(restart_interval), 0)
+    n = ctypes.c_size_t()
+    cap = a.size * 2 + 65536
+    for _ in range(2):
+        out = np.empty(cap, dtype=np.uint8)
+        st = N.load().hipjpegTranscodeHost(a.ctypes.data, a.size, ctypes.byref(p), out.ctypes.data, cap, ctypes.byref(n))
+        if st != 9:  # BUFFER_TOO_SMALL: n holds the needed size
+            break
+        cap = n.value
+    if st:
+        raise N.HipJpegError(st, "hipjpegTranscodeHost")
+    return out[: n.value].tobytes()
+
+
+class BatchTranscoder:
+    """hipjpegTranscodeBatch on one device: entropy decode, coefficient relayout kernel and entropy coder in one blocking call.
+    gpu_huffman: both entropy stages on the GPU for every image each of them takes; gpu_restart: with gpu_huffman, the GPU coder also
+    takes baseline output with a restart interval (FLAG_GPU_RESTART_INTERVALS).  The bytes do not depend on either."""
+
+    def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False):
+        import torch
+        self._torch = torch
+        self.device = int(device)
+        self.gpu_huffman = bool(gpu_huffman)
+        self.gpu_restart = bool(gpu_restart)
+        self._h = ctypes.c_void_p()
+        st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
+        if st:
+            raise N.HipJpegError(st, "hipjpegCreate")
+
+    def close(self):
+        if self._h:
+            N.load().hipjpegDestroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_hybrid_huffman_threshold(self, pixels):
+        st = N.load().hipjpegSetHybridHuffmanThreshold(self._h, int(pixels))
+        if st:
+            raise N.HipJpegError(st, "hipjpegSetHybridHuffmanThreshold")
+
+    def transcode(self, jpegs, optimized_huffman=False, progressive=False, restart_interval=0, stream=None, gpu_huffman=None):
+        """Returns (statuses, files): files[i] is bytes, or None where statuses[i] != 0.  optimized_huffman / progressive /
+        restart_interval: one value for the batch or a list with one per image."""
+        n = len(jpegs)
+        if gpu_huffman is None:
+            gpu_huffman = self.gpu_huffman
+        flags = (N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0)) if gpu_huffman else 0
+        per = [v if isinstance(v, (list, tuple)) else [v] * n for v in (optimized_huffman, progressive, restart_interval)]
+        P = (N.TranscodeParams * n)()
+        for i in range(n):
+            P[i] = N.TranscodeParams(int(bool(per[0][i])), int(bool(per[1][i])), int(per[2][i]), 0)
+        arrs = [j if (hasattr(j, "data_ptr") and hasattr(j, "numel")) else _as_u8(j) for j in jpegs]
+        ptrs = (ctypes.c_void_p * n)(*[(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data) for a in arrs])
+        lens = (ctypes.c_size_t * n)(*[(a.numel() if hasattr(a, "numel") else a.size) for a in arrs])
+        statuses = (ctypes.c_int * n)()
+        s = stream if stream is not None else self._torch.cuda.current_stream(self.device)
+        st = N.load().hipjpegTranscodeBatch(self._h, ptrs, lens, n, P, flags, statuses, ctypes.c_void_p(s.cuda_stream))
+        if st:
+            raise N.HipJpegError(st, "hipjpegTranscodeBatch")
+        files = []
+        for i in range(n):
+            p, ln = ctypes.c_void_p(), ctypes.c_size_t()
+            ok = statuses[i] == 0 and N.load().hipjpegEncodeGetBitstream(self._h, i, ctypes.byref(p), ctypes.byref(ln)) == 0
+            files.append(ctypes.string_at(p, ln.value) if ok else None)
+        return list(statuses), files
+
+    def stats(self):
+        d, c, b = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        N.load().hipjpegTranscodeBatchStats(self._h, ctypes.byref(d), ctypes.byref(c), ctypes.byref(b))
+        return dict(gpu_decoded_images=d.value, gpu_coded_images=c.value, relayout_blocks=b.value)
