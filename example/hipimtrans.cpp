@@ -9,12 +9,14 @@
 //   hipimtrans -i <file|dir> [-o <dir>] [-b batch] [-w warmup batches] [-r repeats] [-q quality] [-s 444|422|420|gray]
 //              [-d device] [-t cpu threads] [-p batches in flight (decode only)] [--skip_encode] [--options "<plugin options>"] [-v]
 //              [--jpeg_encoding baseline_dct|progressive_dct] [--optimized_huffman true|false]
-//              [--devices a,b,...] [--checksums file] [--lossless]
+//              [--devices a,b,...] [--checksums file] [--lossless [--orientation 1..8|exif] [--trim]]
 // --lossless: no pixels -- every batch goes through hipjpegTranscodeBatch (include/hipjpeg.h: GPU entropy decoder, coefficient relayout
 // kernel, GPU entropy coder), which keeps the coefficients and quantization tables of the sources and changes only their coding, like
 // jpegtran -optimize / -progressive; with --jpeg_encoding, --optimized_huffman, -b and one batch in flight.  -q and -s mean nothing
 // there and are refused.  Sources the call reports as unsupported (CMYK, 16-bit tables, ...) are named and skipped; the exit status
-// is non-zero only for real failures.  The plugin ABI has no transcode call, so this mode talks to the C-ABI of the extension directly.
+// is non-zero only for real failures.  --orientation k (1..8, or "exif" for each source's own tag) also brings the pictures upright for
+// that EXIF orientation, still on the coefficients (jpegtran -flip / -transpose / -transverse / -rotate); a mirror moves whole iMCUs, so
+// sources with a partial iMCU along a mirrored axis are skipped as unsupported unless --trim cuts it off.  The plugin ABI has no transcode call, so this mode talks to the C-ABI of the extension directly.
 // --devices a,b,... (decode only): ONE process drives several devices -- a decoder instance per entry (nvimgcodecDecoderCreate with that
 // device_id: the reference keys its worker pools by device in the same way, src/default_executor.cpp:45-58), a host thread and a queue
 // per entry; the input list is partitioned over the queues by greedy longest-processing-time on (MCU-padded coefficient bytes +
@@ -77,6 +79,10 @@ struct Params {
     bool progressive = false, optimized_huffman = false;  // nvimtrans --jpeg_encoding / --optimized_huffman (command_line_params.h:195-207)
     bool skip_encode = false;
     bool lossless = false, quality_given = false, subsampling_given = false;
+    // --lossless only: the files come out brought upright for this EXIF orientation (jpegtran -flip / -transpose / -rotate), "exif" =
+    // for each source's own tag; --trim cuts partial iMCUs off the mirrored axes instead of refusing the image (jpegtran -trim)
+    int orientation_field = 0;
+    bool orientation_given = false, orientation_bad = false, trim = false;
 };
 
 bool is_dir(const std::string& p)
@@ -409,7 +415,7 @@ int run_lossless(const Params& p, const std::vector<std::string>& names)
         }
         const double reading = wtime() - t0;
         t0 = wtime();
-        const hipjpegTranscodeParams_t one{p.optimized_huffman ? 1 : 0, p.progressive ? 1 : 0, 0, 0};
+        const hipjpegTranscodeParams_t one{p.optimized_huffman ? 1 : 0, p.progressive ? 1 : 0, 0, p.orientation_field | (p.trim ? HIPJPEG_TRANSCODE_TRIM : 0)};
         std::vector<hipjpegTranscodeParams_t> params((size_t)n, one);
         std::vector<hipjpegStatus_t> status((size_t)n, HIPJPEG_STATUS_SUCCESS);
         const hipjpegStatus_t st = api.transcode(handle, data.data(), lengths.data(), n, params.data(), HIPJPEG_FLAG_GPU_HUFFMAN, status.data(), stream);
@@ -507,6 +513,13 @@ int main(int argc, char** argv)
             p.subsampling = next();
             p.subsampling_given = true;
         } else if (a == "--lossless") p.lossless = true;
+        else if (a == "--orientation") {
+            const std::string v = next();
+            p.orientation_given = true;
+            if (v == "exif") p.orientation_field = HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF;
+            else if (v.size() == 1 && v[0] >= '1' && v[0] <= '8') p.orientation_field = v[0] == '1' ? 0 : v[0] - '0';  // the field spells the identity 0
+            else p.orientation_bad = true;
+        } else if (a == "--trim") p.trim = true;
         else if (a == "-d") p.device = atoi(next());
         else if (a == "-t") p.threads = atoi(next());
         else if (a == "-p") p.in_flight = std::max(1, std::min(6, atoi(next())));
@@ -527,7 +540,7 @@ int main(int argc, char** argv)
         else {
             fprintf(stderr, "usage: %s -i <file|dir> [-o dir] [-b batch] [-w warmup] [-r repeats] [-q quality] [-s 444|422|420|gray] [-d device] "
                             "[-t threads] [-p batches in flight] [--skip_encode] [--jpeg_encoding baseline_dct|progressive_dct] [--optimized_huffman true|false] "
-                            "[--options str] [--devices a,b,...] [--checksums file] [--lossless] [-v]\n", argv[0]);
+                            "[--options str] [--devices a,b,...] [--checksums file] [--lossless [--orientation 1..8|exif] [--trim]] [-v]\n", argv[0]);
             return EXIT_FAILURE;
         }
     }
@@ -538,6 +551,14 @@ int main(int argc, char** argv)
     if (p.lossless && (p.quality_given || p.subsampling_given || p.in_flight > 1 || !p.devices.empty() || p.skip_encode)) {
         fprintf(stderr, "--lossless keeps the coefficients and sampling of the sources: it goes with --jpeg_encoding, --optimized_huffman, -b and -p 1 only "
                         "(not with -q, -s, -p > 1, --devices, --skip_encode)\n");
+        return EXIT_FAILURE;
+    }
+    if ((p.orientation_given || p.trim) && !p.lossless) {
+        fprintf(stderr, "--orientation and --trim turn the coefficients themselves: they go with --lossless only\n");
+        return EXIT_FAILURE;
+    }
+    if (p.orientation_bad) {
+        fprintf(stderr, "--orientation takes 1..8 or exif\n");
         return EXIT_FAILURE;
     }
     if (p.output.empty()) p.skip_encode = true;

@@ -321,21 +321,44 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeBaselineGpuAlgorithmHost(int32_t width,
  *      streams -- Adobe transform 0 or component ids R, G, B -- are refused: the writer would label them YCbCr); chroma sampled 1x1 and
  *      luma 1x1, 2x1, 2x2, 1x2, 4x1 or 4x2; every quantizer entry <= 255 and Cb, Cr tables of equal contents; every DC value in
  *      [-1024, 1023] and every AC value in [-1023, 1023] (jchuff.c's limits for 8-bit data).  Anything else is
- *      HIPJPEG_STATUS_UNSUPPORTED; damaged sources keep the decoder's statuses (BAD_JPEG, TRUNCATED, CORRUPT). ---- */
+ *      HIPJPEG_STATUS_UNSUPPORTED; damaged sources keep the decoder's statuses (BAD_JPEG, TRUNCATED, CORRUPT).
+ *
+ *      Lossless turns (jpegtran -flip / -transpose / -transverse / -rotate): `orientation` 1..8 has the meaning it has in
+ *      hipjpegTransform_t -- the output is the source brought upright for that EXIF value (2 horizontal mirror, 3 rotate 180, 4 vertical
+ *      mirror, 5 transpose, 6 rotate 90 clockwise, 7 transverse, 8 rotate 270 clockwise).  Orientation 1, the picture as it is, is
+ *      written 0 in the field: a 1 there stays HIPJPEG_STATUS_INVALID_ARGUMENT, as it was while the field was reserved.  Blocks change
+ *      places, a transposing turn transposes every block, swaps width and height and the luma factors (2x1 <-> 1x2) and transposes the
+ *      quantization tables; a mirror negates the coefficients of odd horizontal (vertical) frequency.  No coefficient is requantized.
+ *      A mirror moves whole iMCUs only.  In source terms orientations 2, 3, 7, 8 mirror the x axis and 3, 4, 6, 7 the y axis; 5 mirrors
+ *      neither.  By default the source's size along every mirrored axis must be a multiple of its iMCU size there (8 * luma factor; 8 for
+ *      one component), otherwise the image is HIPJPEG_STATUS_UNSUPPORTED (jpegtran -perfect).  With HIPJPEG_TRANSCODE_TRIM the source is
+ *      first cut to whole iMCUs along the mirrored axes, keeping its left / top part, and the output has the cut picture's size (jpegtran
+ *      -trim); a mirrored axis shorter than one iMCU is UNSUPPORTED (jpegtran would leave that strip where it is, unmirrored: a file
+ *      that is not the turned picture).  Along an axis that is not mirrored ragged edge blocks travel as they are.  Transposing turns of
+ *      4x1 or 4x2 luma are UNSUPPORTED (the writer has no 1x4 / 2x4).  The range rule is checked on the blocks that are carried over.
+ *      HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF takes the orientation from the source's own EXIF tag (hipjpegGetExifOrientation) instead
+ *      of the low bits, which must then be 0; the output carries no EXIF, so it is upright and says nothing to the contrary. ---- */
+#define HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF 0x10000 /* or-ed into hipjpegTranscodeParams_t::orientation */
+#define HIPJPEG_TRANSCODE_TRIM 0x20000                  /* or-ed into hipjpegTranscodeParams_t::orientation */
 typedef struct {
     int32_t optimized_huffman; /* as hipjpegEncodeParams_t */
     int32_t progressive;       /* as hipjpegEncodeParams_t */
     int32_t restart_interval;  /* MCUs, 0 = none (the source's own interval is not carried over) */
-    int32_t reserved;          /* 0 */
+    int32_t orientation;       /* 0 (none) or 2..8, optionally | HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF | HIPJPEG_TRANSCODE_TRIM; any other bit is
+                                  HIPJPEG_STATUS_INVALID_ARGUMENT */
 } hipjpegTranscodeParams_t;
 
+/* Host only: the EXIF orientation (tag 0x0112 of IFD0 in the first APP1/Exif segment before the first scan) of a JPEG file, 1..8;
+ * 1 when there is no such tag or its value is outside 1..8. */
+HIPJPEG_API hipjpegStatus_t hipjpegGetExifOrientation(const uint8_t* data, size_t length, int32_t* orientation);
 /* Host only, usable without a GPU: host entropy decoder -> host coder.  HIPJPEG_STATUS_BUFFER_TOO_SMALL with *out_length = needed size
  * if capacity is insufficient (as hipjpegEncodeFromCoefficientsHost). */
 HIPJPEG_API hipjpegStatus_t hipjpegTranscodeHost(const uint8_t* data, size_t length, const hipjpegTranscodeParams_t* params, uint8_t* out,
                                                  size_t capacity, size_t* out_length);
 /* Device: entropy decode, coef_relayout_kernel (csrc/transcode_kernels.hip: decoder layout -> coder layout, with the range check) and the
  * entropy coder in one blocking call on `stream`; the files are then read with hipjpegEncodeGetBitstream(handle, i, ...), which reports
- * the image's status for an image without a file.  `params`: one per image.  `flags`: HIPJPEG_FLAG_GPU_HUFFMAN puts both entropy stages
+ * the image's status for an image without a file.  `params`: one per image (turned images go through coef_transform_kernel of the same
+ * file, the others through coef_relayout_kernel: one launch each).  `flags`: HIPJPEG_FLAG_GPU_HUFFMAN puts both entropy stages
  * on the device for every image each of them takes (the decode side honours hipjpegSetHybridHuffmanThreshold; progressive output with a
  * restart interval goes to the host coder), HIPJPEG_FLAG_GPU_RESTART_INTERVALS as in hipjpegEncodeBatchEntropy; 0 = both stages on the
  * host pool.  The bytes do not depend on the flags.  A failing image leaves the rest of the batch alone.  The call occupies a decode page
@@ -344,7 +367,7 @@ HIPJPEG_API hipjpegStatus_t hipjpegTranscodeHost(const uint8_t* data, size_t len
 HIPJPEG_API hipjpegStatus_t hipjpegTranscodeBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
                                                   const hipjpegTranscodeParams_t* params, unsigned flags, hipjpegStatus_t* statuses, void* stream);
 /* Of the handle's last transcode batch: images the GPU entropy decoder took, images the GPU entropy coder took, blocks the relayout
- * kernel moved (the real blocks of every image that reached it). */
+ * kernels moved (the real blocks of every image that reached them: of a turned image, those of the trimmed, turned picture). */
 HIPJPEG_API hipjpegStatus_t hipjpegTranscodeBatchStats(hipjpegHandle_t handle, int32_t* gpu_decoded_images, int32_t* gpu_coded_images,
                                                        int32_t* relayout_blocks);
 

@@ -14,6 +14,8 @@ OUTPUT_RGBI, OUTPUT_BGRI, OUTPUT_RGB_PLANAR, OUTPUT_BGR_PLANAR, OUTPUT_Y, OUTPUT
 FLAG_FANCY_UPSAMPLING = 1
 FLAG_GPU_HUFFMAN = 2
 FLAG_GPU_RESTART_INTERVALS = 8
+TRANSCODE_ORIENTATION_FROM_EXIF = 0x10000  # or-ed into TranscodeParams.orientation
+TRANSCODE_TRIM = 0x20000
 FLAG_FAST_IDCT = 4  # JDCT_IFAST as libjpeg-turbo's x86-64 SIMD routine computes it (the reference's fast_idct)
 
 
@@ -40,7 +42,7 @@ class EncodeParams(ctypes.Structure):
 
 class TranscodeParams(ctypes.Structure):
     """hipjpegTranscodeParams_t"""
-    _fields_ = [(n, ctypes.c_int32) for n in ("optimized_huffman", "progressive", "restart_interval", "reserved")]
+    _fields_ = [(n, ctypes.c_int32) for n in ("optimized_huffman", "progressive", "restart_interval", "orientation")]
 
 
 CSS = {"444": 0, "422": 1, "420": 2, "440": 3, "411": 4, "410": 5, "gray": 6}
@@ -135,6 +137,7 @@ def load():
     L.hipjpegEncodeBaselineGpuAlgorithmHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
     L.hipjpegTranscodeHost.argtypes = [vp, sz, ctypes.POINTER(TranscodeParams), vp, sz, ctypes.POINTER(sz)]
     L.hipjpegTranscodeBatch.argtypes = [vp, vp, vp, i32, vp, ctypes.c_uint, vp, vp]
+    L.hipjpegGetExifOrientation.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_int32)]
     L.hipjpegTranscodeBatchStats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     _lib = L
     return L

@@ -273,6 +273,8 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
     pixel_bytes_ = coef_bytes_ = 0;
     relayout_blocks_ = 0;
     gpu_entropy_images_ = 0;
+    std::vector<RelayoutUnit> turned;
+    uint64_t turned_blocks = 0;
     for (int i = 0; i < n; i++) {
         PlannedEncode& im = images_[i];
         im.status = pics[i].status;
@@ -297,10 +299,14 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
             im.coef_offset[c] = coef_total_;
             coef_total_ += (size_t)g.blocks_w[c] * g.blocks_h[c] * 128;
             const uint32_t nreal = (uint32_t)(g.real_w[c] * g.real_h[c]);
-            for (uint32_t b = 0; b < nreal; b += kRelayoutBlocksPerUnit) relayout_units_.push_back(RelayoutUnit{(uint32_t)i, (uint32_t)c, b, 0u});
+            std::vector<RelayoutUnit>& list = pics[i].turn ? turned : relayout_units_;
+            for (uint32_t b = 0; b < nreal; b += kRelayoutBlocksPerUnit) list.push_back(RelayoutUnit{(uint32_t)i, (uint32_t)c, b, pics[i].turn});
             relayout_blocks_ += nreal;
+            if (pics[i].turn) turned_blocks += nreal;
         }
     }
+    identity_units_ = relayout_units_.size();
+    relayout_units_.insert(relayout_units_.end(), turned.begin(), turned.end());
     coef_bytes_ = relayout_blocks_ * 128;
     layout();
     hipjpegStatus_t st;
@@ -312,12 +318,16 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
         return HIPJPEG_STATUS_HIP_ERROR;
     // HIPJPEG_DEBUG_TIMING (debug aid, as in the decode host stage): the kernel's own time on stderr (tools/prof_transcode.py reads it)
     static const bool timing = getenv("HIPJPEG_DEBUG_TIMING") != nullptr;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (timing && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, s) != hipSuccess)) return HIPJPEG_STATUS_HIP_ERROR;
-    if (launch_coef_relayout(src, at<const EncodeImage>(device_, staging_.desc), at<const RelayoutUnit>(device_, staging_.relayout),
-                             (int)relayout_units_.size(), at<uint32_t>(device_, staging_.flags), stream) != 0)
+    hipEvent_t t0 = nullptr, t1 = nullptr, t2 = nullptr;
+    if (timing && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess || hipEventCreate(&t2) != hipSuccess || hipEventRecord(t0, s) != hipSuccess))
         return HIPJPEG_STATUS_HIP_ERROR;
+    const EncodeImage* dimg = at<const EncodeImage>(device_, staging_.desc);
+    const RelayoutUnit* dunits = at<const RelayoutUnit>(device_, staging_.relayout);
+    const int nturned = (int)(relayout_units_.size() - identity_units_);
+    if (launch_coef_relayout(src, dimg, dunits, (int)identity_units_, at<uint32_t>(device_, staging_.flags), stream) != 0) return HIPJPEG_STATUS_HIP_ERROR;
     if (timing && hipEventRecord(t1, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+    if (launch_coef_transform(src, dimg, dunits + identity_units_, nturned, at<uint32_t>(device_, staging_.flags), stream) != 0) return HIPJPEG_STATUS_HIP_ERROR;
+    if (timing && hipEventRecord(t2, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
     uint32_t* flags = at<uint32_t>(pinned_desc_, staging_.flags);
     if (!relayout_units_.empty() &&
         hipMemcpyAsync(flags, device_.data() + staging_.flags, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess)
@@ -330,12 +340,17 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
     if (hipEventRecord((hipEvent_t)event_, s) != hipSuccess || hipEventSynchronize((hipEvent_t)event_) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
     launched_ = true;
     if (timing) {
-        float ms = 0;
-        (void)hipEventSynchronize(t1);
+        float ms = 0, ms_turned = 0;
+        (void)hipEventSynchronize(t2);
         (void)hipEventElapsedTime(&ms, t0, t1);
-        fprintf(stderr, "[hipjpeg] coef_relayout_kernel: %zu workgroups, %llu blocks, %.4f ms\n", relayout_units_.size(), (unsigned long long)relayout_blocks_, ms);
+        (void)hipEventElapsedTime(&ms_turned, t1, t2);
+        if (identity_units_ || !nturned)
+            fprintf(stderr, "[hipjpeg] coef_relayout_kernel: %zu workgroups, %llu blocks, %.4f ms\n", identity_units_, (unsigned long long)(relayout_blocks_ - turned_blocks), ms);
+        if (nturned)
+            fprintf(stderr, "[hipjpeg] coef_transform_kernel: %d workgroups, %llu blocks, %.4f ms\n", nturned, (unsigned long long)turned_blocks, ms_turned);
         (void)hipEventDestroy(t0);
         (void)hipEventDestroy(t1);
+        (void)hipEventDestroy(t2);
     }
     // the range guard: such values are outside what the coders' tables cover, so no coder gets to see them
     for (int i = 0; i < n && !relayout_units_.empty(); i++)

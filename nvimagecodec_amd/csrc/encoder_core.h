@@ -32,7 +32,8 @@ struct PlannedEncode {
 // lie in HBM in the decoder's layout.  status != SUCCESS: the image has no source (it keeps that status and gets no file).
 struct CoefficientPicture {
     hipjpegStatus_t status = HIPJPEG_STATUS_SUCCESS;
-    TranscodePicture picture;
+    TranscodePicture picture;        // the OUTPUT picture (transcode_turn)
+    unsigned turn = 0;               // kTurn* bits: where its blocks come from; 0 = the source's own places
     hipjpegEncodeParams_t params{};  // restart_interval, optimized_huffman, progressive; the rest is not read
 };
 
@@ -54,8 +55,8 @@ public:
                                  void* stream);
     hipjpegStatus_t relaunch(void* stream);
     // Lossless transcode, in place of device_stage(): plans picture i from pics[i], reserves the coefficient area and lets
-    // coef_relayout_kernel fill it from `src` (the DecodeImage table of the batch that decoded the same pictures, same indices) on
-    // `stream`.  Blocks until the kernel's range flags are back: an image with a coefficient outside jchuff.c's limits becomes
+    // coef_relayout_kernel (pictures with turn == 0) and coef_transform_kernel (the turned ones), one launch each, fill it from `src`
+    // (the DecodeImage table of the batch that decoded the same pictures, same indices) on `stream`.  Blocks until the kernel's range flags are back: an image with a coefficient outside jchuff.c's limits becomes
     // UNSUPPORTED before any coder sees it.  route_entropy() / entropy_stage() follow as after device_stage().
     hipjpegStatus_t coefficient_stage(const CoefficientPicture* pics, int n, const DecodeImage* src, void* stream);
     uint64_t relayout_blocks() const { return relayout_blocks_; }  // blocks the last coefficient_stage() moved
@@ -96,7 +97,8 @@ private:
     struct EncodeStaging {
         size_t desc, units, relayout, flags, coef, total;
     } staging_{};
-    std::vector<RelayoutUnit> relayout_units_;
+    std::vector<RelayoutUnit> relayout_units_;  // the units of the pictures that stay as they are, then those of the turned ones
+    size_t identity_units_ = 0;
     uint64_t relayout_blocks_ = 0;
     size_t coef_total_ = 0;
     uint64_t pixel_bytes_ = 0, coef_bytes_ = 0;

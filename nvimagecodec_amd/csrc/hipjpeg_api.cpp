@@ -774,7 +774,11 @@ hipjpegStatus_t hipjpegTranscodeBatch(hipjpegHandle_t handle, const uint8_t* con
     for (int i = 0; i < batch_size; i++) {
         CoefficientPicture& p = pics[(size_t)i];
         p.status = d.image(i).status;
-        if (p.status == HIPJPEG_STATUS_SUCCESS) p.status = transcode_picture(d.image(i).frame, &p.picture);
+        TranscodePicture source;
+        if (p.status == HIPJPEG_STATUS_SUCCESS) p.status = transcode_picture(d.image(i).frame, &source);
+        if (p.status == HIPJPEG_STATUS_SUCCESS)
+            p.status = transcode_turn(source, transcode_orientation(params[i], data[i], lengths[i]), (params[i].orientation & HIPJPEG_TRANSCODE_TRIM) != 0,
+                                      &p.picture, &p.turn);
         if (p.status != HIPJPEG_STATUS_SUCCESS) continue;
         p.params.restart_interval = params[i].restart_interval;
         p.params.optimized_huffman = params[i].optimized_huffman;

@@ -296,31 +296,7 @@ nvimgcodecIoStreamDesc_t make_io_desc(IoStream* s)
 }
 
 // ---------------------------------------------------------------------------------------------- EXIF orientation (APP1)
-// Only the orientation tag (0x0112) of IFD0 is read; mapping = reference src/parsers/exif_orientation.h:36-57.
-int exif_orientation_tag(const uint8_t* p, size_t n)
-{
-    if (n < 14 || memcmp(p, "Exif\0\0", 6) != 0) return 0;
-    const uint8_t* t = p + 6;
-    size_t tn = n - 6;
-    bool le = t[0] == 'I' && t[1] == 'I';
-    if (!le && !(t[0] == 'M' && t[1] == 'M')) return 0;
-    auto u16 = [&](size_t o) -> unsigned { return o + 2 <= tn ? (le ? t[o] | (t[o + 1] << 8) : (t[o] << 8) | t[o + 1]) : 0; };
-    auto u32 = [&](size_t o) -> unsigned {
-        if (o + 4 > tn) return 0;
-        return le ? (t[o] | (t[o + 1] << 8) | (t[o + 2] << 16) | ((unsigned)t[o + 3] << 24))
-                  : (((unsigned)t[o] << 24) | (t[o + 1] << 16) | (t[o + 2] << 8) | t[o + 3]);
-    };
-    if (u16(2) != 42) return 0;
-    size_t ifd = u32(4);
-    unsigned cnt = u16(ifd);
-    for (unsigned i = 0; i < cnt; i++) {
-        size_t e = ifd + 2 + 12 * (size_t)i;
-        if (e + 12 > tn) break;
-        if (u16(e) == 0x0112) return (int)u16(e + 8);
-    }
-    return 0;
-}
-
+// The orientation tag (0x0112) of IFD0: jpeg_syntax.h exif_orientation_tag; mapping = reference src/parsers/exif_orientation.h:36-57.
 void set_orientation(nvimgcodecOrientation_t* o, int exif)
 {
     int rot = 0, fx = 0, fy = 0;

@@ -358,6 +358,48 @@ ParseStatus parse_jpeg(const uint8_t* data, size_t size, FrameInfo* f, bool head
 }
 
 // The sampling layout as the API names it (the reference's parser does the same from the SOF factors, src/parsers/jpeg.cpp:262-330).
+// ---------------------------------------------------------------------------------------------- EXIF orientation (APP1)
+int exif_orientation_tag(const uint8_t* p, size_t n)
+{
+    if (n < 14 || memcmp(p, "Exif\0\0", 6) != 0) return 0;
+    const uint8_t* t = p + 6;
+    size_t tn = n - 6;
+    bool le = t[0] == 'I' && t[1] == 'I';
+    if (!le && !(t[0] == 'M' && t[1] == 'M')) return 0;
+    auto u16 = [&](size_t o) -> unsigned { return o + 2 <= tn ? (le ? t[o] | (t[o + 1] << 8) : (t[o] << 8) | t[o + 1]) : 0; };
+    auto u32 = [&](size_t o) -> unsigned {
+        if (o + 4 > tn) return 0;
+        return le ? (t[o] | (t[o + 1] << 8) | (t[o + 2] << 16) | ((unsigned)t[o + 3] << 24))
+                  : (((unsigned)t[o] << 24) | (t[o + 1] << 16) | (t[o + 2] << 8) | t[o + 3]);
+    };
+    if (u16(2) != 42) return 0;
+    size_t ifd = u32(4);
+    unsigned cnt = u16(ifd);
+    for (unsigned i = 0; i < cnt; i++) {
+        size_t e = ifd + 2 + 12 * (size_t)i;
+        if (e + 12 > tn) break;
+        if (u16(e) == 0x0112) return (int)u16(e + 8);
+    }
+    return 0;
+}
+
+int exif_orientation(const uint8_t* p, size_t n)
+{
+    if (!p || n < 4 || p[0] != 0xFF || p[1] != 0xD8) return 1;
+    for (size_t pos = 2; pos + 4 <= n && p[pos] == 0xFF;) {
+        const int m = p[pos + 1];
+        if (m == 0xDA || m == 0xD9) break;
+        const size_t L = ((size_t)p[pos + 2] << 8) | p[pos + 3];
+        if (L < 2 || pos + 2 + L > n) break;
+        if (m == 0xE1 && L >= 8 && memcmp(p + pos + 4, "Exif\0\0", 6) == 0) {
+            const int o = exif_orientation_tag(p + pos + 4, L - 2);
+            return o >= 1 && o <= 8 ? o : 1;
+        }
+        pos += 2 + L;
+    }
+    return 1;
+}
+
 hipjpegChromaSubsampling_t classify_subsampling(const FrameInfo& f)
 {
     if (f.ncomp == 1) return HIPJPEG_CSS_GRAY;

@@ -80,4 +80,10 @@ extern const uint8_t kZigzagNatural[64];  // zigzag index -> natural (row-major)
 
 hipjpegChromaSubsampling_t classify_subsampling(const FrameInfo& f);
 
+// EXIF: the orientation tag (0x0112) of IFD0 in the payload of an APP1 segment ("Exif\0\0" + TIFF, either byte order); 0 when the
+// payload is not EXIF or has no such tag.
+int exif_orientation_tag(const uint8_t* payload, size_t n);
+// Of a whole file: the tag of the first APP1/Exif segment before the first scan, 1..8; 1 when it is missing or outside 1..8.
+int exif_orientation(const uint8_t* data, size_t size);
+
 }  // namespace hipjpeg

@@ -46,7 +46,58 @@ hipjpegStatus_t transcode_picture(const FrameInfo& f, TranscodePicture* p)
 
 hipjpegStatus_t transcode_params_ok(const hipjpegTranscodeParams_t& p)
 {
-    return (p.restart_interval < 0 || p.restart_interval > 65535 || p.reserved != 0) ? HIPJPEG_STATUS_INVALID_ARGUMENT : HIPJPEG_STATUS_SUCCESS;
+    if (p.restart_interval < 0 || p.restart_interval > 65535) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    const uint32_t o = (uint32_t)p.orientation, value = o & ~(uint32_t)(HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF | HIPJPEG_TRANSCODE_TRIM);
+    // (the identity is written 0: a 1 in this field was INVALID_ARGUMENT while the field was reserved, and callers rely on that)
+    if (value == 1 || value > 8 || (value != 0 && (o & HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+int transcode_orientation(const hipjpegTranscodeParams_t& p, const uint8_t* data, size_t size)
+{
+    if (p.orientation & HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF) return exif_orientation(data, size);
+    const int value = p.orientation & 15;
+    return value == 0 ? 1 : value;
+}
+
+hipjpegStatus_t transcode_turn(const TranscodePicture& src, int orientation, bool trim, TranscodePicture* dst, unsigned* turn)
+{
+    static const unsigned kTurns[9] = {0, 0, kTurnMirrorX, kTurnMirrorX | kTurnMirrorY, kTurnMirrorY, kTurnTranspose, kTurnTranspose | kTurnMirrorX,
+                                       kTurnTranspose | kTurnMirrorX | kTurnMirrorY, kTurnTranspose | kTurnMirrorY};
+    const unsigned t = kTurns[orientation];
+    *turn = t;
+    *dst = src;
+    if (t == 0) return HIPJPEG_STATUS_SUCCESS;
+    const EncodeGeometry& s = src.geom;
+    const bool transpose = (t & kTurnTranspose) != 0;
+    if (transpose && s.hs == 4) return HIPJPEG_STATUS_UNSUPPORTED;  // the writer has no 1x4 / 2x4
+    // the output's mirrors in source terms: after a transpose the output's x axis is the source's y axis
+    const bool mirror_sx = (t & (transpose ? kTurnMirrorY : kTurnMirrorX)) != 0, mirror_sy = (t & (transpose ? kTurnMirrorX : kTurnMirrorY)) != 0;
+    int w = s.width, h = s.height;
+    const int mcu_w = 8 * s.hs, mcu_h = 8 * s.vs;
+    if (mirror_sx && w % mcu_w != 0) {
+        if (!trim || w < mcu_w) return HIPJPEG_STATUS_UNSUPPORTED;
+        w -= w % mcu_w;
+    }
+    if (mirror_sy && h % mcu_h != 0) {
+        if (!trim || h < mcu_h) return HIPJPEG_STATUS_UNSUPPORTED;
+        h -= h % mcu_h;
+    }
+    EncodeGeometry& g = dst->geom;
+    g = EncodeGeometry();
+    g.ncomp = s.ncomp;
+    g.width = transpose ? h : w;
+    g.height = transpose ? w : h;
+    g.hs = transpose ? s.vs : s.hs;
+    g.vs = transpose ? s.hs : s.vs;
+    compute_geometry(&g);
+    if (transpose)
+        for (int j = 0; j < 64; j++) {
+            const int tr = (j & 7) * 8 + (j >> 3);
+            dst->qlum[j] = src.qlum[tr];
+            dst->qchr[j] = src.qchr[tr];
+        }
+    return HIPJPEG_STATUS_SUCCESS;
 }
 
 EntropyEncodeOptions transcode_options(const hipjpegTranscodeParams_t& p)
@@ -61,8 +112,12 @@ hipjpegStatus_t transcode_host(const uint8_t* data, size_t size, const hipjpegTr
     FrameInfo f;
     const ParseStatus ps = parse_jpeg(data, size, &f);
     if (ps != kParseOk) return ps == kParseUnsupported ? HIPJPEG_STATUS_UNSUPPORTED : ps == kParseTruncated ? HIPJPEG_STATUS_TRUNCATED : HIPJPEG_STATUS_BAD_JPEG;
-    TranscodePicture pic;
-    if ((st = transcode_picture(f, &pic)) != HIPJPEG_STATUS_SUCCESS) return st;
+    TranscodePicture source, pic;
+    unsigned turn = 0;
+    if ((st = transcode_picture(f, &source)) != HIPJPEG_STATUS_SUCCESS) return st;
+    if ((st = transcode_turn(source, transcode_orientation(params, data, size), (params.orientation & HIPJPEG_TRANSCODE_TRIM) != 0, &pic, &turn)) !=
+        HIPJPEG_STATUS_SUCCESS)
+        return st;
     // the decoder's blocks: column-major over the frame's MCU-padded grid
     std::vector<int16_t> src(f.total_blocks() * 64, 0);
     int16_t* sptr[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -86,19 +141,30 @@ hipjpegStatus_t transcode_host(const uint8_t* data, size_t size, const hipjpegTr
         total += (size_t)g.blocks_w[c] * g.blocks_h[c] * 64;
     }
     dst.assign(total, 0);
-    int from[64];  // zigzag index -> position in the decoder's block (column * 8 + row)
-    for (int k = 0; k < 64; k++) from[k] = (kZigzagNatural[k] & 7) * 8 + (kZigzagNatural[k] >> 3);
+    // zigzag index -> position in the decoder's block (column * 8 + row) -- read the other way round, the block comes out transposed --
+    // and whether a mirror of the output negates it (odd u: mirror x, odd v: mirror y; both: twice)
+    const bool transpose = (turn & kTurnTranspose) != 0;
+    int from[64];
+    bool negate[64];
+    for (int k = 0; k < 64; k++) {
+        const int u = kZigzagNatural[k] & 7, v = kZigzagNatural[k] >> 3;
+        from[k] = transpose ? v * 8 + u : u * 8 + v;
+        negate[k] = (((turn & kTurnMirrorX) != 0) & (u & 1)) ^ (((turn & kTurnMirrorY) != 0) & (v & 1));
+    }
     for (int c = 0; c < g.ncomp; c++)
         for (int by = 0; by < g.real_h[c]; by++)
             for (int bx = 0; bx < g.real_w[c]; bx++) {
-                const int16_t* s = sptr[c] + ((size_t)by * f.comp[c].blocks_w + bx) * 64;
+                // the source block: undo the output's mirrors over its real area, then the transpose
+                const int ty = (turn & kTurnMirrorY) ? g.real_h[c] - 1 - by : by, tx = (turn & kTurnMirrorX) ? g.real_w[c] - 1 - bx : bx;
+                const int sy = transpose ? tx : ty, sx = transpose ? ty : tx;
+                const int16_t* s = sptr[c] + ((size_t)sy * f.comp[c].blocks_w + sx) * 64;
                 int16_t* d = dst.data() + doff[c] + ((size_t)by * g.blocks_w[c] + bx) * 64;
                 if (s[0] < kTranscodeDcMin || s[0] > kTranscodeDcMax) return HIPJPEG_STATUS_UNSUPPORTED;
                 d[0] = s[0];
                 for (int k = 1; k < 64; k++) {
                     const int v = s[from[k]];
                     if (v < -kTranscodeAcMax || v > kTranscodeAcMax) return HIPJPEG_STATUS_UNSUPPORTED;
-                    d[k] = (int16_t)v;
+                    d[k] = (int16_t)(negate[k] ? -v : v);
                 }
             }
     const int16_t* coef[3] = {nullptr, nullptr, nullptr};
@@ -127,4 +193,11 @@ extern "C" hipjpegStatus_t hipjpegTranscodeHost(const uint8_t* data, size_t leng
     } catch (...) {
         return HIPJPEG_STATUS_INTERNAL_ERROR;
     }
+}
+
+extern "C" hipjpegStatus_t hipjpegGetExifOrientation(const uint8_t* data, size_t length, int32_t* orientation)
+{
+    if (!data || !orientation) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    *orientation = hipjpeg::exif_orientation(data, length);
+    return HIPJPEG_STATUS_SUCCESS;
 }

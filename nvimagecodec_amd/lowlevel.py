@@ -543,12 +543,34 @@ class BatchEncoder:
         return dict(units=u.value, pixel_bytes=pb.value, coef_bytes=cb.value, gpu_entropy_images=int(N.load().hipjpegEncodeBatchGpuEntropyImages(self._h)))
 
 
-def transcode_host(data, optimized_huffman=False, progressive=False, restart_interval=0):
-    """Lossless transcode on the host (no GPU): host entropy decoder -> host coder.  The file keeps every coefficient and the
-    quantization tables of the source; APPn / COM segments are not copied.  Raises HipJpegError: UNSUPPORTED for sources the coder
-    cannot take (include/hipjpeg.h lists the rules), the decoder's statuses for damaged ones."""
+def _orientation_field(orientation, trim, from_exif):
+    """hipjpegTranscodeParams_t::orientation"""
+    if from_exif:
+        return N.TRANSCODE_ORIENTATION_FROM_EXIF | (N.TRANSCODE_TRIM if trim else 0)
+    o = int(orientation)
+    if not 0 <= o <= 8:
+        raise ValueError("orientation must be 1..8")
+    return (0 if o == 1 else o) | (N.TRANSCODE_TRIM if trim else 0)  # the field spells the identity 0
+
+
+def exif_orientation(data):
+    """The EXIF orientation (1..8) of a JPEG file: tag 0x0112 of IFD0 in its first APP1/Exif segment; 1 when it is missing or out of range."""
     a = _as_u8(data)
-    p = N.TranscodeParams(int(bool(optimized_huffman)), int(bool(progressive)), int(restart_interval), 0)
+    o = ctypes.c_int32()
+    st = N.load().hipjpegGetExifOrientation(a.ctypes.data, a.size, ctypes.byref(o))
+    if st:
+        raise N.HipJpegError(st, "hipjpegGetExifOrientation")
+    return o.value
+
+
+def transcode_host(data, optimized_huffman=False, progressive=False, restart_interval=0, orientation=1, trim=False, from_exif=False):
+    """Lossless transcode on the host (no GPU): host entropy decoder -> host coder.  The file keeps every coefficient and the
+    quantization tables of the source; APPn / COM segments are not copied.  orientation 1..8: the file holds the picture brought
+    upright for that EXIF value (from_exif: for the source's own tag), still without requantizing; a mirror moves whole iMCUs, so the
+    mirrored axes must be multiples of the iMCU size unless trim cuts them (include/hipjpeg.h).  Raises HipJpegError: UNSUPPORTED for
+    sources the coder cannot take (include/hipjpeg.h lists the rules), the decoder's statuses for damaged ones."""
+    a = _as_u8(data)
+    p = N.TranscodeParams(int(bool(optimized_huffman)), int(bool(progressive)), int(restart_interval), _orientation_field(orientation, trim, from_exif))
     n = ctypes.c_size_t()
     cap = a.size * 2 + 65536
     for _ in range(2):
@@ -594,17 +616,19 @@ class BatchTranscoder:
         if st:
             raise N.HipJpegError(st, "hipjpegSetHybridHuffmanThreshold")
 
-    def transcode(self, jpegs, optimized_huffman=False, progressive=False, restart_interval=0, stream=None, gpu_huffman=None):
+    def transcode(self, jpegs, optimized_huffman=False, progressive=False, restart_interval=0, stream=None, gpu_huffman=None, orientation=1,
+                  trim=False, from_exif=False):
         """Returns (statuses, files): files[i] is bytes, or None where statuses[i] != 0.  optimized_huffman / progressive /
-        restart_interval: one value for the batch or a list with one per image."""
+        restart_interval / orientation: one value for the batch or a list with one per image.  orientation, trim, from_exif: as
+        transcode_host."""
         n = len(jpegs)
         if gpu_huffman is None:
             gpu_huffman = self.gpu_huffman
         flags = (N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0)) if gpu_huffman else 0
-        per = [v if isinstance(v, (list, tuple)) else [v] * n for v in (optimized_huffman, progressive, restart_interval)]
+        per = [v if isinstance(v, (list, tuple)) else [v] * n for v in (optimized_huffman, progressive, restart_interval, orientation)]
         P = (N.TranscodeParams * n)()
         for i in range(n):
-            P[i] = N.TranscodeParams(int(bool(per[0][i])), int(bool(per[1][i])), int(per[2][i]), 0)
+            P[i] = N.TranscodeParams(int(bool(per[0][i])), int(bool(per[1][i])), int(per[2][i]), _orientation_field(per[3][i], trim, from_exif))
         arrs = [j if (hasattr(j, "data_ptr") and hasattr(j, "numel")) else _as_u8(j) for j in jpegs]
         ptrs = (ctypes.c_void_p * n)(*[(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data) for a in arrs])
         lens = (ctypes.c_size_t * n)(*[(a.numel() if hasattr(a, "numel") else a.size) for a in arrs])

@@ -2,8 +2,10 @@
  (a) coef_relayout_kernel: time per batch (the library's own event bracket, HIPJPEG_DEBUG_TIMING) and its bytes/time against a
      device-to-device copy of the same byte count in the same run;
  (b) images/s of hipjpegTranscodeBatch to optimized baseline and to progressive files, next to hipimtrans' decode -> encode route with
-     the same output settings, one call outstanding (its decoding + encoding stage times, file reading and parsing left out).
-usage: python tools/prof_transcode.py [--batch 256] [--steps 5] [--skip-pixel-route]"""
+     the same output settings, one call outstanding (its decoding + encoding stage times, file reading and parsing left out);
+ (c) with --orientation: coef_transform_kernel on the same batch turned for each of the given EXIF orientations (with trim: 1080 is no
+     multiple of the 16-row iMCU), its time next to coef_relayout_kernel's of (a), per batch and per block moved.
+usage: python tools/prof_transcode.py [--batch 256] [--steps 5] [--orientation 2,5,6] [--skip-pixel-route]"""
 import argparse
 import os
 import re
@@ -22,7 +24,8 @@ from nvimagecodec_amd import lowlevel  # noqa: E402
 
 
 def kernel_times(fn):
-    """runs fn() with stderr captured at the file-descriptor level; -> (result, [ms of every coef_relayout_kernel line])"""
+    """runs fn() with stderr captured at the file-descriptor level; -> (result, [ms of every coef_relayout_kernel line],
+    [ms of every coef_transform_kernel line])"""
     sys.stderr.flush()
     saved = os.dup(2)
     with tempfile.TemporaryFile(mode="w+b") as tmp:
@@ -34,13 +37,14 @@ def kernel_times(fn):
             os.close(saved)
         tmp.seek(0)
         text = tmp.read().decode(errors="replace")
-    return res, [float(m) for m in re.findall(r"coef_relayout_kernel: .* ([0-9.]+) ms", text)]
+    return res, *([float(m) for m in re.findall(kernel + r": .* ([0-9.]+) ms", text)] for kernel in ("coef_relayout_kernel", "coef_transform_kernel"))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--orientation", default="", help="comma-separated EXIF orientations 2..8 to time coef_transform_kernel on")
     ap.add_argument("--skip-pixel-route", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
@@ -63,7 +67,7 @@ def main():
             torch.cuda.synchronize()
             return time.perf_counter() - t0
 
-        seconds, ms = kernel_times(timed)
+        seconds, ms, _ = kernel_times(timed)
         st = t.stats()
         nbytes = st["relayout_blocks"] * 128
         print(f"[{name}] hipjpegTranscodeBatch: {a.batch * a.steps / seconds:.0f} images/s ({seconds / a.steps * 1e3:.2f} ms per batch; "
@@ -71,6 +75,25 @@ def main():
         k = sorted(ms)[len(ms) // 2]
         print(f"[{name}] coef_relayout_kernel: median {k:.4f} ms per batch (min {min(ms):.4f}, max {max(ms):.4f}, {len(ms)} launches), {nbytes / 1e6:.1f} MB read + "
               f"as many written: {2 * nbytes / k / 1e6:.0f} GB/s of traffic")
+    identity_ms, identity_blocks = k, st["relayout_blocks"]
+    for orientation in [int(v) for v in a.orientation.split(",") if v]:
+        kw = dict(optimized_huffman=True, orientation=orientation, trim=True)
+        for _ in range(2):
+            statuses, files = t.transcode(jpegs, **kw)
+        assert statuses == [0] * a.batch
+        assert files[0] == lowlevel.transcode_host(jpegs[0], **kw), "the device route must write the host route's file"
+
+        def turned():
+            for _ in range(a.steps):
+                t.transcode(jpegs, **kw)
+
+        _, ms_identity, ms = kernel_times(turned)
+        assert not ms_identity and len(ms) == a.steps
+        blocks = t.stats()["relayout_blocks"]
+        m = sorted(ms)[len(ms) // 2]
+        print(f"[orientation {orientation}] coef_transform_kernel: median {m:.4f} ms per batch (min {min(ms):.4f}, max {max(ms):.4f}, {len(ms)} launches), "
+              f"{blocks} blocks ({blocks / identity_blocks:.4f} of the untrimmed batch): {2 * blocks * 128 / m / 1e6:.0f} GB/s of traffic; "
+              f"/ coef_relayout_kernel = {m / identity_ms:.3f} per batch, {m / blocks / (identity_ms / identity_blocks):.3f} per block")
     # the same byte count through the copy engine's kernel path, same run
     a_dev = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     b_dev = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
