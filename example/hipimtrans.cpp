@@ -9,14 +9,18 @@
 //   hipimtrans -i <file|dir> [-o <dir>] [-b batch] [-w warmup batches] [-r repeats] [-q quality] [-s 444|422|420|gray]
 //              [-d device] [-t cpu threads] [-p batches in flight (decode only)] [--skip_encode] [--options "<plugin options>"] [-v]
 //              [--jpeg_encoding baseline_dct|progressive_dct] [--optimized_huffman true|false]
-//              [--devices a,b,...] [--checksums file] [--lossless [--orientation 1..8|exif] [--trim]]
+//              [--devices a,b,...] [--checksums file] [--lossless [--orientation 1..8|exif] [--trim] [--crop WxH+X+Y] [--expand]
+//              [--grayscale] [--copy-markers]]
 // --lossless: no pixels -- every batch goes through hipjpegTranscodeBatch (include/hipjpeg.h: GPU entropy decoder, coefficient relayout
 // kernel, GPU entropy coder), which keeps the coefficients and quantization tables of the sources and changes only their coding, like
 // jpegtran -optimize / -progressive; with --jpeg_encoding, --optimized_huffman, -b and one batch in flight.  -q and -s mean nothing
 // there and are refused.  Sources the call reports as unsupported (CMYK, 16-bit tables, ...) are named and skipped; the exit status
 // is non-zero only for real failures.  --orientation k (1..8, or "exif" for each source's own tag) also brings the pictures upright for
 // that EXIF orientation, still on the coefficients (jpegtran -flip / -transpose / -transverse / -rotate); a mirror moves whole iMCUs, so
-// sources with a partial iMCU along a mirrored axis are skipped as unsupported unless --trim cuts it off.  The plugin ABI has no transcode call, so this mode talks to the C-ABI of the extension directly.
+// sources with a partial iMCU along a mirrored axis are skipped as unsupported unless --trim cuts it off.  --grayscale drops the chroma components, --crop WxH+X+Y (jpegtran's spelling) then cuts that region out of every picture -- its origin must lie
+// on the iMCU grid unless --expand moves it left / up onto it, as jpegtran does -- and the turn applies to what is left; --copy-markers
+// carries the sources' APPn / COM segments (EXIF, ICC, comments) over, with the EXIF orientation reset when the picture is turned.
+// The plugin ABI has no transcode call, so this mode talks to the C-ABI of the extension directly.
 // --devices a,b,... (decode only): ONE process drives several devices -- a decoder instance per entry (nvimgcodecDecoderCreate with that
 // device_id: the reference keys its worker pools by device in the same way, src/default_executor.cpp:45-58), a host thread and a queue
 // per entry; the input list is partitioned over the queues by greedy longest-processing-time on (MCU-padded coefficient bytes +
@@ -83,6 +87,9 @@ struct Params {
     // for each source's own tag; --trim cuts partial iMCUs off the mirrored axes instead of refusing the image (jpegtran -trim)
     int orientation_field = 0;
     bool orientation_given = false, orientation_bad = false, trim = false;
+    // --lossless only: --crop WxH+X+Y as x0..y1, --expand, --grayscale, --copy-markers (hipjpegTranscodeRegion_t and the HIPJPEG_TRANSCODE_* flags)
+    hipjpegTranscodeRegion_t crop{0, 0, 0, 0};
+    bool crop_given = false, crop_bad = false, expand = false, grayscale = false, copy_markers = false;
 };
 
 bool is_dir(const std::string& p)
@@ -353,6 +360,7 @@ struct TranscodeApi {
     decltype(&hipjpegDestroy) destroy = nullptr;
     decltype(&hipjpegTranscodeBatch) transcode = nullptr;
     decltype(&hipjpegTranscodeBatchStats) stats = nullptr;
+    decltype(&hipjpegTranscodeBatchSetRegions) set_regions = nullptr;
     decltype(&hipjpegEncodeGetBitstream) bitstream = nullptr;
     decltype(&hipjpegStatusString) status_string = nullptr;
     bool load()
@@ -374,9 +382,10 @@ struct TranscodeApi {
         destroy = (decltype(destroy))dlsym(lib, "hipjpegDestroy");
         transcode = (decltype(transcode))dlsym(lib, "hipjpegTranscodeBatch");
         stats = (decltype(stats))dlsym(lib, "hipjpegTranscodeBatchStats");
+        set_regions = (decltype(set_regions))dlsym(lib, "hipjpegTranscodeBatchSetRegions");
         bitstream = (decltype(bitstream))dlsym(lib, "hipjpegEncodeGetBitstream");
         status_string = (decltype(status_string))dlsym(lib, "hipjpegStatusString");
-        return create && destroy && transcode && stats && bitstream && status_string;
+        return create && destroy && transcode && stats && set_regions && bitstream && status_string;
     }
 };
 
@@ -415,8 +424,17 @@ int run_lossless(const Params& p, const std::vector<std::string>& names)
         }
         const double reading = wtime() - t0;
         t0 = wtime();
-        const hipjpegTranscodeParams_t one{p.optimized_huffman ? 1 : 0, p.progressive ? 1 : 0, 0, p.orientation_field | (p.trim ? HIPJPEG_TRANSCODE_TRIM : 0)};
+        const int32_t field = p.orientation_field | (p.trim ? HIPJPEG_TRANSCODE_TRIM : 0) | (p.grayscale ? HIPJPEG_TRANSCODE_GRAYSCALE : 0) |
+                              (p.expand ? HIPJPEG_TRANSCODE_CROP_EXPAND : 0) | (p.copy_markers ? HIPJPEG_TRANSCODE_COPY_MARKERS : 0);
+        const hipjpegTranscodeParams_t one{p.optimized_huffman ? 1 : 0, p.progressive ? 1 : 0, 0, field};
         std::vector<hipjpegTranscodeParams_t> params((size_t)n, one);
+        if (p.crop_given) {
+            const std::vector<hipjpegTranscodeRegion_t> regions((size_t)n, p.crop);
+            if (api.set_regions(handle, regions.data(), n) != HIPJPEG_STATUS_SUCCESS) {
+                fprintf(stderr, "hipjpegTranscodeBatchSetRegions failed\n");
+                return EXIT_FAILURE;
+            }
+        }
         std::vector<hipjpegStatus_t> status((size_t)n, HIPJPEG_STATUS_SUCCESS);
         const hipjpegStatus_t st = api.transcode(handle, data.data(), lengths.data(), n, params.data(), HIPJPEG_FLAG_GPU_HUFFMAN, status.data(), stream);
         if (st != HIPJPEG_STATUS_SUCCESS) {
@@ -520,6 +538,19 @@ int main(int argc, char** argv)
             else if (v.size() == 1 && v[0] >= '1' && v[0] <= '8') p.orientation_field = v[0] == '1' ? 0 : v[0] - '0';  // the field spells the identity 0
             else p.orientation_bad = true;
         } else if (a == "--trim") p.trim = true;
+        else if (a == "--crop") {
+            // jpegtran's WxH+X+Y; the library takes x0, y0, x1, y1
+            const char* v = next();
+            int w = 0, h = 0, x = 0, y = 0, used = 0;
+            p.crop_given = true;
+            if (sscanf(v, "%dx%d+%d+%d%n", &w, &h, &x, &y, &used) == 4 && v[used] == 0 && w > 0 && h > 0 && x >= 0 && y >= 0 && w <= 65535 && h <= 65535 &&
+                x <= 65535 && y <= 65535)
+                p.crop = hipjpegTranscodeRegion_t{x, y, x + w, y + h};
+            else
+                p.crop_bad = true;
+        } else if (a == "--expand") p.expand = true;
+        else if (a == "--grayscale") p.grayscale = true;
+        else if (a == "--copy-markers") p.copy_markers = true;
         else if (a == "-d") p.device = atoi(next());
         else if (a == "-t") p.threads = atoi(next());
         else if (a == "-p") p.in_flight = std::max(1, std::min(6, atoi(next())));
@@ -540,7 +571,8 @@ int main(int argc, char** argv)
         else {
             fprintf(stderr, "usage: %s -i <file|dir> [-o dir] [-b batch] [-w warmup] [-r repeats] [-q quality] [-s 444|422|420|gray] [-d device] "
                             "[-t threads] [-p batches in flight] [--skip_encode] [--jpeg_encoding baseline_dct|progressive_dct] [--optimized_huffman true|false] "
-                            "[--options str] [--devices a,b,...] [--checksums file] [--lossless [--orientation 1..8|exif] [--trim]] [-v]\n", argv[0]);
+                            "[--options str] [--devices a,b,...] [--checksums file] [--lossless [--orientation 1..8|exif] [--trim] [--crop WxH+X+Y] [--expand] "
+                            "[--grayscale] [--copy-markers]] [-v]\n", argv[0]);
             return EXIT_FAILURE;
         }
     }
@@ -555,6 +587,14 @@ int main(int argc, char** argv)
     }
     if ((p.orientation_given || p.trim) && !p.lossless) {
         fprintf(stderr, "--orientation and --trim turn the coefficients themselves: they go with --lossless only\n");
+        return EXIT_FAILURE;
+    }
+    if ((p.crop_given || p.expand || p.grayscale || p.copy_markers) && !p.lossless) {
+        fprintf(stderr, "--crop, --expand, --grayscale and --copy-markers work on the coefficients and segments of the sources: they go with --lossless only\n");
+        return EXIT_FAILURE;
+    }
+    if (p.crop_bad) {
+        fprintf(stderr, "--crop takes WxH+X+Y\n");
         return EXIT_FAILURE;
     }
     if (p.orientation_bad) {

@@ -315,8 +315,8 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeBaselineGpuAlgorithmHost(int32_t width,
 /* ---- lossless transcode: entropy decode -> coefficient relayout -> entropy coder; no pixel is computed, every coefficient of the source
  *      survives (what jpegtran -optimize / -progressive do).  The output is the JFIF file hipjpegEncodeFromCoefficientsHost writes for the
  *      source's geometry, coefficients and quantization tables: APP0, components 1/2/3, SOF0 or SOF2, libjpeg's dummy blocks where the MCU
- *      grid overhangs the picture.  APPn / COM segments of the source (EXIF, ICC, comments) are NOT copied: a caller who needs them keeps
- *      them himself.  The source's own restart interval is not carried over either.
+ *      grid overhangs the picture.  APPn / COM segments of the source (EXIF, ICC, comments) are copied only with
+ *      HIPJPEG_TRANSCODE_COPY_MARKERS (below).  The source's own restart interval is not carried over.
  *      An image is transcodable when it is SOF0 / SOF1 / SOF2 with 8-bit samples; has one component, or three with colour model YCbCr (RGB
  *      streams -- Adobe transform 0 or component ids R, G, B -- are refused: the writer would label them YCbCr); chroma sampled 1x1 and
  *      luma 1x1, 2x1, 2x2, 1x2, 4x1 or 4x2; every quantizer entry <= 255 and Cb, Cr tables of equal contents; every DC value in
@@ -337,16 +337,49 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeBaselineGpuAlgorithmHost(int32_t width,
  *      that is not the turned picture).  Along an axis that is not mirrored ragged edge blocks travel as they are.  Transposing turns of
  *      4x1 or 4x2 luma are UNSUPPORTED (the writer has no 1x4 / 2x4).  The range rule is checked on the blocks that are carried over.
  *      HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF takes the orientation from the source's own EXIF tag (hipjpegGetExifOrientation) instead
- *      of the low bits, which must then be 0; the output carries no EXIF, so it is upright and says nothing to the contrary. ---- */
+ *      of the low bits, which must then be 0; without HIPJPEG_TRANSCODE_COPY_MARKERS the output carries no EXIF, so it is upright and says
+ *      nothing to the contrary.
+ *
+ *      Three more operations, applied in this order BEFORE the turn: drop chroma -> crop -> turn.  Each rule speaks of the picture being
+ *      written at that step.
+ *      HIPJPEG_TRANSCODE_GRAYSCALE (jpegtran -grayscale): a three-component YCbCr source becomes a one-component picture: the luma
+ *      component's blocks over ceil(w/8) x ceil(h/8) and the luma table, written 1x1.  The rules that concern chroma only are waived (equal
+ *      Cb/Cr tables, chroma quantizers <= 255, chroma sampled 1x1, the list of luma factors, the range rule on chroma blocks); what remains:
+ *      SOF0/1/2 with 8-bit samples, one component or three with colour model YCbCr, luma quantizers in 1..255, the range rule on the luma
+ *      blocks carried over, and the luma component sampled at the frame's full resolution (its factors are the frame's largest).  On a
+ *      one-component source the flag does nothing.  From here on the iMCU is 8x8 (transupp.c: the iMCU of the output's component count).
+ *      Crop (jpegtran -crop): a region per image (hipjpegTranscodeRegion_t: stored-image coordinates, end exclusive, all zeros = the whole
+ *      picture, as in hipjpegTransform_t).  A region that is not all zeros must satisfy 0 <= x0 < x1 <= width and 0 <= y0 < y1 <= height of
+ *      a source that is transcodable at all, else that image is HIPJPEG_STATUS_INVALID_ARGUMENT.  x0 and y0 must be multiples of the iMCU
+ *      (8 * luma factors; 8x8 for one component, so also after GRAYSCALE), else HIPJPEG_STATUS_UNSUPPORTED -- unless
+ *      HIPJPEG_TRANSCODE_CROP_EXPAND moves the origin left / up to the iMCU boundary; x1 and y1 stay, so the region grows (what jpegtran
+ *      -crop does).  The output is (x1 - x0') x (y1 - y0'); every component carries the blocks of its real area for that size, read from
+ *      block origin (x0'/8 * h_c/hs, y0'/8 * v_c/vs) of the source's grid.  x1 and y1 need no alignment: a partial edge block travels whole,
+ *      and beyond the real area the writer makes libjpeg's dummy blocks.  The range rule is checked on the blocks carried over.  A region
+ *      that covers the whole picture writes the file that no region writes.  The turn then applies to the cropped picture: the perfect /
+ *      TRIM rule is judged on the cropped size, and trim keeps the cropped picture's left / top part.
+ *      HIPJPEG_TRANSCODE_COPY_MARKERS (jpegtran -copy all): every APP0..APP15 and COM segment of the source between SOI and the first SOS
+ *      is copied verbatim, in source order, right behind the writer's own JFIF APP0 and before the first DQT.  An APP0 whose payload begins
+ *      "JFIF\0" is not copied (the writer has written its own; a JFXX APP0 is); fill bytes in front of markers are not copied; there is no
+ *      cap on the total.  When the effective turn is not the identity and the first APP1/Exif segment (the one hipjpegGetExifOrientation
+ *      reads) is among the copies, the two value bytes of its orientation tag are overwritten with 1 in the segment's byte order, so the
+ *      turned file does not go on asking to be turned.  Nothing else in that segment changes: pixel-dimension tags (PixelXDimension,
+ *      ImageWidth, ...) and embedded thumbnails stay as they are, also after a crop. ---- */
 #define HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF 0x10000 /* or-ed into hipjpegTranscodeParams_t::orientation */
 #define HIPJPEG_TRANSCODE_TRIM 0x20000                  /* or-ed into hipjpegTranscodeParams_t::orientation */
+#define HIPJPEG_TRANSCODE_GRAYSCALE 0x80000             /* or-ed into hipjpegTranscodeParams_t::orientation */
+#define HIPJPEG_TRANSCODE_CROP_EXPAND 0x100000          /* or-ed into hipjpegTranscodeParams_t::orientation */
+#define HIPJPEG_TRANSCODE_COPY_MARKERS 0x200000         /* or-ed into hipjpegTranscodeParams_t::orientation */
 typedef struct {
     int32_t optimized_huffman; /* as hipjpegEncodeParams_t */
     int32_t progressive;       /* as hipjpegEncodeParams_t */
     int32_t restart_interval;  /* MCUs, 0 = none (the source's own interval is not carried over) */
-    int32_t orientation;       /* 0 (none) or 2..8, optionally | HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF | HIPJPEG_TRANSCODE_TRIM; any other bit is
+    int32_t orientation;       /* 0 (none) or 2..8, optionally or-ed with the HIPJPEG_TRANSCODE_* flags above; any other bit is
                                   HIPJPEG_STATUS_INVALID_ARGUMENT */
 } hipjpegTranscodeParams_t;
+typedef struct {
+    int32_t x0, y0, x1, y1; /* stored-image coordinates, end exclusive; all zeros = the whole picture */
+} hipjpegTranscodeRegion_t;
 
 /* Host only: the EXIF orientation (tag 0x0112 of IFD0 in the first APP1/Exif segment before the first scan) of a JPEG file, 1..8;
  * 1 when there is no such tag or its value is outside 1..8. */
@@ -355,10 +388,16 @@ HIPJPEG_API hipjpegStatus_t hipjpegGetExifOrientation(const uint8_t* data, size_
  * if capacity is insufficient (as hipjpegEncodeFromCoefficientsHost). */
 HIPJPEG_API hipjpegStatus_t hipjpegTranscodeHost(const uint8_t* data, size_t length, const hipjpegTranscodeParams_t* params, uint8_t* out,
                                                  size_t capacity, size_t* out_length);
+/* hipjpegTranscodeHost with a region (NULL = the whole picture); links without the HIP runtime, like hipjpegTranscodeHost. */
+HIPJPEG_API hipjpegStatus_t hipjpegTranscodeHostRegion(const uint8_t* data, size_t length, const hipjpegTranscodeParams_t* params,
+                                                       const hipjpegTranscodeRegion_t* region, uint8_t* out, size_t capacity, size_t* out_length);
+/* Regions for the NEXT hipjpegTranscodeBatch on this handle: batch_size entries (copied), NULL = none; consumed by that one batch; a count
+ * that differs from that batch's size makes it return HIPJPEG_STATUS_INVALID_ARGUMENT. */
+HIPJPEG_API hipjpegStatus_t hipjpegTranscodeBatchSetRegions(hipjpegHandle_t handle, const hipjpegTranscodeRegion_t* regions, int batch_size);
 /* Device: entropy decode, coef_relayout_kernel (csrc/transcode_kernels.hip: decoder layout -> coder layout, with the range check) and the
  * entropy coder in one blocking call on `stream`; the files are then read with hipjpegEncodeGetBitstream(handle, i, ...), which reports
- * the image's status for an image without a file.  `params`: one per image (turned images go through coef_transform_kernel of the same
- * file, the others through coef_relayout_kernel: one launch each).  `flags`: HIPJPEG_FLAG_GPU_HUFFMAN puts both entropy stages
+ * the image's status for an image without a file.  `params`: one per image (turned images, and images cropped at an origin other than (0, 0), go
+ * through coef_transform_kernel of the same file, the others through coef_relayout_kernel: one launch each).  `flags`: HIPJPEG_FLAG_GPU_HUFFMAN puts both entropy stages
  * on the device for every image each of them takes (the decode side honours hipjpegSetHybridHuffmanThreshold; progressive output with a
  * restart interval goes to the host coder), HIPJPEG_FLAG_GPU_RESTART_INTERVALS as in hipjpegEncodeBatchEntropy; 0 = both stages on the
  * host pool.  The bytes do not depend on the flags.  A failing image leaves the rest of the batch alone.  The call occupies a decode page
@@ -367,7 +406,7 @@ HIPJPEG_API hipjpegStatus_t hipjpegTranscodeHost(const uint8_t* data, size_t len
 HIPJPEG_API hipjpegStatus_t hipjpegTranscodeBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
                                                   const hipjpegTranscodeParams_t* params, unsigned flags, hipjpegStatus_t* statuses, void* stream);
 /* Of the handle's last transcode batch: images the GPU entropy decoder took, images the GPU entropy coder took, blocks the relayout
- * kernels moved (the real blocks of every image that reached them: of a turned image, those of the trimmed, turned picture). */
+ * kernels moved (the real blocks of every image that reached them: those of the picture written -- gray, cropped, trimmed, turned). */
 HIPJPEG_API hipjpegStatus_t hipjpegTranscodeBatchStats(hipjpegHandle_t handle, int32_t* gpu_decoded_images, int32_t* gpu_coded_images,
                                                        int32_t* relayout_blocks);
 

@@ -16,6 +16,9 @@ FLAG_GPU_HUFFMAN = 2
 FLAG_GPU_RESTART_INTERVALS = 8
 TRANSCODE_ORIENTATION_FROM_EXIF = 0x10000  # or-ed into TranscodeParams.orientation
 TRANSCODE_TRIM = 0x20000
+TRANSCODE_GRAYSCALE = 0x80000
+TRANSCODE_CROP_EXPAND = 0x100000
+TRANSCODE_COPY_MARKERS = 0x200000
 FLAG_FAST_IDCT = 4  # JDCT_IFAST as libjpeg-turbo's x86-64 SIMD routine computes it (the reference's fast_idct)
 
 
@@ -43,6 +46,11 @@ class EncodeParams(ctypes.Structure):
 class TranscodeParams(ctypes.Structure):
     """hipjpegTranscodeParams_t"""
     _fields_ = [(n, ctypes.c_int32) for n in ("optimized_huffman", "progressive", "restart_interval", "orientation")]
+
+
+class TranscodeRegion(ctypes.Structure):
+    """hipjpegTranscodeRegion_t: stored-image coordinates, end exclusive; all zero = the whole picture"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("x0", "y0", "x1", "y1")]
 
 
 CSS = {"444": 0, "422": 1, "420": 2, "440": 3, "411": 4, "410": 5, "gray": 6}
@@ -136,6 +144,8 @@ def load():
     L.hipjpegEncodeFromCoefficientsGpuAlgorithmHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
     L.hipjpegEncodeBaselineGpuAlgorithmHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
     L.hipjpegTranscodeHost.argtypes = [vp, sz, ctypes.POINTER(TranscodeParams), vp, sz, ctypes.POINTER(sz)]
+    L.hipjpegTranscodeHostRegion.argtypes = [vp, sz, ctypes.POINTER(TranscodeParams), ctypes.POINTER(TranscodeRegion), vp, sz, ctypes.POINTER(sz)]
+    L.hipjpegTranscodeBatchSetRegions.argtypes = [vp, vp, i32]
     L.hipjpegTranscodeBatch.argtypes = [vp, vp, vp, i32, vp, ctypes.c_uint, vp, vp]
     L.hipjpegGetExifOrientation.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_int32)]
     L.hipjpegTranscodeBatchStats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]

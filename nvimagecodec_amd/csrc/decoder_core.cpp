@@ -196,6 +196,7 @@ static hipjpegStatus_t normalise_transform(PlannedImage& im, const hipjpegTransf
 struct DecodeBatch::PlanArgs {  // plan()'s arguments; give_up: per image, given up after a failed allocation
     const uint8_t* const* data; const size_t* lengths; const hipjpegOutput_t* outputs; hipjpegOutputFormat_t format; unsigned flags;
     const hipjpegOutputFormat_t* formats; const hipjpegTransform_t* transforms; const char* give_up;
+    const hipjpegTranscodeParams_t* transcode = nullptr;  // plan_coefficients(): per image, or nullptr
 };
 
 // What the per-image sizing adds up, in bytes unless noted; every region is carved in image order.
@@ -229,11 +230,11 @@ hipjpegStatus_t DecodeBatch::plan(const uint8_t* const* data, const size_t* leng
 }
 
 hipjpegStatus_t DecodeBatch::plan_coefficients(const uint8_t* const* data, const size_t* lengths, int n, unsigned flags, hipjpegStatus_t* statuses,
-                                               ForkJoinPool* pool)
+                                               ForkJoinPool* pool, const hipjpegTranscodeParams_t* params)
 {
     pool_ = pool;
     coef_only_ = true;
-    return plan_attempts(PlanArgs{data, lengths, nullptr, HIPJPEG_OUTPUT_RGBI, flags & HIPJPEG_FLAG_GPU_HUFFMAN, nullptr, nullptr, nullptr}, n, statuses);
+    return plan_attempts(PlanArgs{data, lengths, nullptr, HIPJPEG_OUTPUT_RGBI, flags & HIPJPEG_FLAG_GPU_HUFFMAN, nullptr, nullptr, nullptr, params}, n, statuses);
 }
 
 hipjpegStatus_t DecodeBatch::plan_attempts(const PlanArgs& a, int n, hipjpegStatus_t* statuses)
@@ -325,7 +326,8 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
         // coefficients only: no kernel variant (-4: no pixel work at all), no output to check; what counts is whether the coder takes it
         TranscodePicture pic;
         im.variant = -4;
-        if (im.status == HIPJPEG_STATUS_SUCCESS) im.status = transcode_picture(f, &pic);
+        const bool grayscale = a.transcode && (a.transcode[i].orientation & HIPJPEG_TRANSCODE_GRAYSCALE) != 0;
+        if (im.status == HIPJPEG_STATUS_SUCCESS) im.status = transcode_picture(f, grayscale, &pic);
     } else {
         if (im.status == HIPJPEG_STATUS_SUCCESS && !choose_variant(f, fmt, fancy, &im.variant)) im.status = HIPJPEG_STATUS_UNSUPPORTED;
         for (int p = 0; im.status == HIPJPEG_STATUS_SUCCESS && p < (fmt == kOutPlanarYUV ? f.ncomp : out_planes(fmt)); p++)

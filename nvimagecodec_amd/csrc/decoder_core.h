@@ -94,8 +94,9 @@ public:
     // coefficients stay in HBM in the decoder's layout, host-decoded pictures as dense blocks.  Of `flags` only
     // HIPJPEG_FLAG_GPU_HUFFMAN counts.  Sources the coder cannot take (transcode_core.h transcode_picture) are UNSUPPORTED.
     // Then entropy_stage() per image, finalize(), transfer() and launch(stream, 3) as for any batch.
+    // `params` (per image, or nullptr): HIPJPEG_TRANSCODE_GRAYSCALE waives the chroma rules for that image.
     hipjpegStatus_t plan_coefficients(const uint8_t* const* data, const size_t* lengths, int n, unsigned flags, hipjpegStatus_t* statuses,
-                                      ForkJoinPool* pool);
+                                      ForkJoinPool* pool, const hipjpegTranscodeParams_t* params = nullptr);
     // The batch's DecodeImage table as the kernels see it (valid after transfer()).
     const DecodeImage* device_descriptors() const { return at<const DecodeImage>(device_, staging_.desc); }
     // GPU entropy stage only for images of MORE than this many pixels (width x height); smaller ones keep the host Huffman decoder.

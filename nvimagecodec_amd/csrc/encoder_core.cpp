@@ -96,6 +96,7 @@ hipjpegStatus_t EncodeBatch::device_stage(const hipjpegEncodeInput_t* inputs, co
     images_.assign(n, PlannedEncode());
     desc_.assign(n, EncodeImage());
     host_coder_.assign(n, 0);
+    markers_.assign((size_t)n, std::vector<uint8_t>());
     units_.clear();
     relayout_units_.clear();
     for (auto& v : unit_lists_) v.clear();
@@ -266,6 +267,7 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
     images_.assign(n, PlannedEncode());
     desc_.assign(n, EncodeImage());
     host_coder_.assign(n, 0);
+    markers_.assign((size_t)n, std::vector<uint8_t>());
     units_.clear();
     relayout_units_.clear();
     for (auto& v : unit_lists_) v.clear();
@@ -283,7 +285,10 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
         im.params = pics[i].params;
         memcpy(im.qlum, pics[i].picture.qlum, sizeof im.qlum);
         memcpy(im.qchr, pics[i].picture.qchr, sizeof im.qchr);
+        markers_[(size_t)i] = pics[i].markers;
         const EncodeGeometry& g = im.geom;
+        // cropped at an origin: the turned kernel, with turn 0 if need be (the origin of the unit's component rides behind the turn)
+        const bool moved = pics[i].turn != 0 || pics[i].origin.any();
         EncodeImage& d = desc_[i];
         memset(&d, 0, sizeof d);
         d.width = (uint32_t)g.width;
@@ -299,10 +304,11 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
             im.coef_offset[c] = coef_total_;
             coef_total_ += (size_t)g.blocks_w[c] * g.blocks_h[c] * 128;
             const uint32_t nreal = (uint32_t)(g.real_w[c] * g.real_h[c]);
-            std::vector<RelayoutUnit>& list = pics[i].turn ? turned : relayout_units_;
-            for (uint32_t b = 0; b < nreal; b += kRelayoutBlocksPerUnit) list.push_back(RelayoutUnit{(uint32_t)i, (uint32_t)c, b, pics[i].turn});
+            std::vector<RelayoutUnit>& list = moved ? turned : relayout_units_;
+            const uint32_t pad = pics[i].turn | ((uint32_t)pics[i].origin.ox[c] << kOriginShiftX) | ((uint32_t)pics[i].origin.oy[c] << kOriginShiftY);
+            for (uint32_t b = 0; b < nreal; b += kRelayoutBlocksPerUnit) list.push_back(RelayoutUnit{(uint32_t)i, (uint32_t)c, b, pad});
             relayout_blocks_ += nreal;
-            if (pics[i].turn) turned_blocks += nreal;
+            if (moved) turned_blocks += nreal;
         }
     }
     identity_units_ = relayout_units_.size();
@@ -392,7 +398,9 @@ void EncodeBatch::entropy_stage(int i)
     im.bitstream.clear();
     im.gpu_bitstream = nullptr;
     im.gpu_bitstream_len = 0;
-    encode_jfif(im.geom, im.qlum, im.qchr, coef, entropy_options(im.params), &im.bitstream);
+    EntropyEncodeOptions opt = entropy_options(im.params);
+    opt.markers = markers_of(i);
+    encode_jfif(im.geom, im.qlum, im.qchr, coef, opt, &im.bitstream);
 }
 
 // ---------------------------------------------------------------- GPU entropy coder
@@ -552,7 +560,7 @@ void EncodeBatch::henc_describe(HencPlan& p)
         for (uint32_t b = 0; b < h.total_blocks; b += 256) p.units.push_back(HencUnit{(uint32_t)g, b});
         p.total_blocks += (h.total_blocks + 63) & ~(size_t)63;
         if (im.params.optimized_huffman) p.opt_slot[g] = p.nopt++;
-        write_standard_headers(eg, im.qlum, im.qchr, &p.headers[g], im.params.restart_interval);
+        write_standard_headers(eg, im.qlum, im.qchr, &p.headers[g], im.params.restart_interval, markers_of(p.idx[g]));
     }
     p.first_seg.push_back(ng);
 }
@@ -606,7 +614,8 @@ hipjpegStatus_t EncodeBatch::henc_histograms(HencPlan& p)
         const auto* counts = at<const uint32_t[2][256]>(henc_.pinned, p.pin.hist + kHistBytes * (size_t)k);
         const size_t tables = d1.opt_tables + sizeof(StandardCodeTables) * (size_t)k;
         p.headers[g].clear();
-        optimal_code_tables(counts, im.geom, im.qlum, im.qchr, at<StandardCodeTables>(henc_.pinned, tables), &p.headers[g], im.params.restart_interval);
+        optimal_code_tables(counts, im.geom, im.qlum, im.qchr, at<StandardCodeTables>(henc_.pinned, tables), &p.headers[g], im.params.restart_interval,
+                            markers_of(p.idx[(size_t)g]));
         p.segs[g].hist = nullptr;
         p.segs[g].tables = at<const StandardCodeTables>(henc_.dev, tables);
     }
@@ -656,7 +665,7 @@ void EncodeBatch::penc_describe(PencPlan& q)
             q.segs.push_back(h);
             q.headers.emplace_back();
         }
-        write_progressive_frame_header(im.geom, im.qlum, im.qchr, &q.headers[s0]);
+        write_progressive_frame_header(im.geom, im.qlum, im.qchr, &q.headers[s0], markers_of(q.idx[g]));
     }
     q.first_seg.push_back((int)q.scans.size());
 }

@@ -34,6 +34,8 @@ struct CoefficientPicture {
     hipjpegStatus_t status = HIPJPEG_STATUS_SUCCESS;
     TranscodePicture picture;        // the OUTPUT picture (transcode_turn)
     unsigned turn = 0;               // kTurn* bits: where its blocks come from; 0 = the source's own places
+    TranscodeOrigin origin;          // block origin per component in the source's grid (transcode_crop)
+    std::vector<uint8_t> markers;    // marker segments to go behind APP0 (transcode_markers), usually none
     hipjpegEncodeParams_t params{};  // restart_interval, optimized_huffman, progressive; the rest is not read
 };
 
@@ -55,7 +57,7 @@ public:
                                  void* stream);
     hipjpegStatus_t relaunch(void* stream);
     // Lossless transcode, in place of device_stage(): plans picture i from pics[i], reserves the coefficient area and lets
-    // coef_relayout_kernel (pictures with turn == 0) and coef_transform_kernel (the turned ones), one launch each, fill it from `src`
+    // coef_relayout_kernel (pictures with neither turn nor origin) and coef_transform_kernel (the turned ones and those cropped at an origin), one launch each, fill it from `src`
     // (the DecodeImage table of the batch that decoded the same pictures, same indices) on `stream`.  Blocks until the kernel's range flags are back: an image with a coefficient outside jchuff.c's limits becomes
     // UNSUPPORTED before any coder sees it.  route_entropy() / entropy_stage() follow as after device_stage().
     hipjpegStatus_t coefficient_stage(const CoefficientPicture* pics, int n, const DecodeImage* src, void* stream);
@@ -97,7 +99,11 @@ private:
     struct EncodeStaging {
         size_t desc, units, relayout, flags, coef, total;
     } staging_{};
-    std::vector<RelayoutUnit> relayout_units_;  // the units of the pictures that stay as they are, then those of the turned ones
+    std::vector<RelayoutUnit> relayout_units_;  // the units of the pictures that stay as they are, then those of the turned / cropped ones
+    // per image: marker segments for the header writers of every coding route (coefficient_stage(); empty otherwise).  Not a PlannedEncode
+    // field, for the reason given at host_coder_.
+    std::vector<std::vector<uint8_t>> markers_;
+    const std::vector<uint8_t>* markers_of(int i) const { return markers_[(size_t)i].empty() ? nullptr : &markers_[(size_t)i]; }
     size_t identity_units_ = 0;
     uint64_t relayout_blocks_ = 0;
     size_t coef_total_ = 0;

@@ -333,14 +333,16 @@ void compute_geometry(EncodeGeometry* g)
     }
 }
 
-// SOI, APP0, DQT.., SOFn (jcmarker.c write_file_header + write_frame_header)
-static void write_frame_header(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], int sof_marker, std::vector<uint8_t>* o)
+// SOI, APP0, [copied APPn / COM segments], DQT.., SOFn (jcmarker.c write_file_header + write_frame_header; jpegtran's place for the copies)
+static void write_frame_header(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], int sof_marker, std::vector<uint8_t>* o,
+                               const std::vector<uint8_t>* markers)
 {
     put16(o, 0xFFD8);
     put16(o, 0xFFE0);
     put16(o, 16);
     const uint8_t jfif[14] = {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
     o->insert(o->end(), jfif, jfif + 14);
+    if (markers) o->insert(o->end(), markers->begin(), markers->end());
     for (int t = 0; t < (g.ncomp == 3 ? 2 : 1); t++) {
         put16(o, 0xFFDB);
         put16(o, 67);
@@ -362,10 +364,11 @@ static void write_frame_header(const EncodeGeometry& g, const uint16_t qlum[64],
 
 // Everything in front of the entropy-coded data: SOI .. SOS, in jcmarker.c's order.
 static void write_headers(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], const HuffTable& dcl, const HuffTable& acl,
-                          const HuffTable& dcc, const HuffTable& acc, int restart_interval, std::vector<uint8_t>* o)
+                          const HuffTable& dcc, const HuffTable& acc, int restart_interval, std::vector<uint8_t>* o,
+                          const std::vector<uint8_t>* markers)
 {
     // marker order of jcmarker.c: SOI, APP0, DQT.., SOF0, DHT.., [DRI], SOS
-    write_frame_header(g, qlum, qchr, 0xFFC0, o);
+    write_frame_header(g, qlum, qchr, 0xFFC0, o, markers);
     write_dht(o, 0x00, dcl);
     write_dht(o, 0x10, acl);
     if (g.ncomp == 3) {
@@ -675,11 +678,11 @@ void write_sos(const ScanSpec& sc, std::vector<uint8_t>* o)
 }
 
 void encode_progressive(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], const int16_t* const coef[3],
-                        int restart_interval, std::vector<uint8_t>* o)
+                        int restart_interval, std::vector<uint8_t>* o, const std::vector<uint8_t>* markers)
 {
     bool dri_sent = false;
     BlockSource src{g, coef};
-    write_frame_header(g, qlum, qchr, 0xFFC2, o);
+    write_frame_header(g, qlum, qchr, 0xFFC2, o, markers);
     for (const ScanSpec& sc : simple_progression(g.ncomp)) {
         const bool needs_table = !(sc.ss == 0 && sc.ah != 0);
         HuffTable tables[2];
@@ -704,9 +707,10 @@ void encode_progressive(const EncodeGeometry& g, const uint16_t qlum[64], const 
 
 }  // namespace
 
-void write_progressive_frame_header(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out)
+void write_progressive_frame_header(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out,
+                                    const std::vector<uint8_t>* markers)
 {
-    write_frame_header(g, qlum, qchr, 0xFFC2, out);
+    write_frame_header(g, qlum, qchr, 0xFFC2, out, markers);
 }
 
 void progressive_scan_header(const ScanSpec& sc, const uint32_t counts[256], uint32_t codes[256], std::vector<uint8_t>* out)
@@ -730,14 +734,15 @@ void progressive_scan_header(const ScanSpec& sc, const uint32_t counts[256], uin
     write_sos(sc, out);
 }
 
-void write_standard_headers(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out, int restart_interval)
+void write_standard_headers(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out, int restart_interval,
+                            const std::vector<uint8_t>* markers)
 {
     HuffTable dcl, dcc, acl, acc;
     dcl.set(kDcLumBits, kDcVals);
     dcc.set(kDcChrBits, kDcVals);
     acl.set(kAcLumBits, kAcLumVals);
     acc.set(kAcChrBits, kAcChrVals);
-    write_headers(g, qlum, qchr, dcl, acl, dcc, acc, restart_interval, out);
+    write_headers(g, qlum, qchr, dcl, acl, dcc, acc, restart_interval, out, markers);
 }
 
 void standard_code_tables(StandardCodeTables* t)
@@ -760,7 +765,7 @@ void standard_code_tables(StandardCodeTables* t)
 }
 
 void optimal_code_tables(const uint32_t counts[2][2][256], const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64],
-                         StandardCodeTables* t, std::vector<uint8_t>* headers, int restart_interval)
+                         StandardCodeTables* t, std::vector<uint8_t>* headers, int restart_interval, const std::vector<uint8_t>* markers)
 {
     HuffTable dc[2], ac[2];
     dc[0].set(kDcLumBits, kDcVals);
@@ -787,7 +792,7 @@ void optimal_code_tables(const uint32_t counts[2][2][256], const EncodeGeometry&
             t->ac_size[k][i] = ac[k].size[i];
         }
     }
-    write_headers(g, qlum, qchr, dc[0], ac[0], dc[1], ac[1], restart_interval, headers);
+    write_headers(g, qlum, qchr, dc[0], ac[0], dc[1], ac[1], restart_interval, headers, markers);
 }
 
 void encode_jfif(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], const int16_t* const coef[3],
@@ -795,7 +800,7 @@ void encode_jfif(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_
 {
     if (opt.progressive) {
         o->reserve(o->size() + (size_t)g.width * g.height / 2 + 1024);
-        encode_progressive(g, qlum, qchr, coef, opt.restart_interval, o);
+        encode_progressive(g, qlum, qchr, coef, opt.restart_interval, o, opt.markers);
         return;
     }
     HuffTable dcl, dcc, acl, acc;
@@ -819,7 +824,7 @@ void encode_jfif(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_
         }
     }
     o->reserve(o->size() + (size_t)g.width * g.height / 2 + 1024);
-    write_headers(g, qlum, qchr, dcl, acl, dcc, acc, opt.restart_interval, o);
+    write_headers(g, qlum, qchr, dcl, acl, dcc, acc, opt.restart_interval, o, opt.markers);
     BitWriter bw(o);
     walk_scan(g, src, opt.restart_interval, dct, act, &bw, nullptr, nullptr);
     bw.align();

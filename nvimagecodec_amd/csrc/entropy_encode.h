@@ -27,6 +27,9 @@ struct EntropyEncodeOptions {
     bool optimized_huffman = false;  // two-pass optimal tables (jchuff.c jpeg_gen_optimal_table); default = Annex-K tables
     bool progressive = false;        // SOF2: jcparam.c jpeg_simple_progression's scan script coded as jcphuff.c does, per-scan optimal
                                      // tables (libjpeg forces them in progressive mode)
+    // marker segments (whole: marker, length, payload) to go right behind the writer's APP0 and before the first DQT, where jpegtran puts
+    // the source's APPn / COM segments; nullptr = none.  Every header writer below takes the same bytes, so all routes place them alike.
+    const std::vector<uint8_t>* markers = nullptr;
 };
 
 // coef[c]: zigzag-ordered int16[64] blocks over the MCU-padded grid; only the real_w x real_h area is read.
@@ -47,9 +50,10 @@ void standard_code_tables(StandardCodeTables* t);
 // symbol] for AC table t; t = 0 luma, 1 chroma) to the (code, length) tables and the bytes of SOI .. SOS with the matching DHT segments --
 // jchuff.c jpeg_gen_optimal_table, the very routine the host coder's optimized_huffman path uses, so both paths write the same file.
 void optimal_code_tables(const uint32_t counts[2][2][256], const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64],
-                         StandardCodeTables* t, std::vector<uint8_t>* headers, int restart_interval = 0);
+                         StandardCodeTables* t, std::vector<uint8_t>* headers, int restart_interval = 0,
+                         const std::vector<uint8_t>* markers = nullptr);
 void write_standard_headers(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out,
-                            int restart_interval = 0);
+                            int restart_interval = 0, const std::vector<uint8_t>* markers = nullptr);
 
 // ---- progressive output on the GPU coder (progressive_encode.hip): the host coder's scan script, frame header and per-scan tables
 // One scan of a progressive script: components (indices), spectral band ss..se, successive approximation ah / al.
@@ -60,7 +64,8 @@ struct ScanSpec {
 // jcparam.c jpeg_simple_progression: the 10-scan script for YCbCr, the all-purpose 6-scan script for one component.
 std::vector<ScanSpec> simple_progression(int ncomp);
 // SOI, APP0, DQT.., SOF2 -- what precedes the first scan's tables.
-void write_progressive_frame_header(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out);
+void write_progressive_frame_header(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out,
+                                    const std::vector<uint8_t>* markers = nullptr);
 // One scan's optimal table(s) from its symbol counts, and its DHT segments and SOS as the host coder writes them (no DRI).  Layout of
 // `counts` and `codes` (code | length << 16): DC first scans [t * 16 + category] (t = 0 luma, 1 chroma); AC scans [run/size symbol].
 // DC refinement scans use no table: counts are ignored and `codes` is left alone.

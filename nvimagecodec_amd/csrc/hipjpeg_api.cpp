@@ -82,6 +82,9 @@ struct hipjpegHandle {
     int encode_next = 0, encode_oldest = 0, encode_in_flight = 0;
     // the last hipjpegTranscodeBatch: images on the GPU entropy decoder / coder, blocks through the relayout kernel
     int32_t transcode_gpu_decoded = 0, transcode_gpu_coded = 0, transcode_blocks = 0;
+    // hipjpegTranscodeBatchSetRegions: for the next hipjpegTranscodeBatch only
+    std::vector<hipjpegTranscodeRegion_t> transcode_regions;
+    bool transcode_regions_set = false;
 };
 
 extern "C" {
@@ -746,7 +749,20 @@ hipjpegStatus_t hipjpegEncodeBaselineGpuAlgorithmHost(int32_t width, int32_t hei
 }
 
 // ---------------------------------------------------------------- lossless transcode
-// (hipjpegTranscodeHost: transcode_core.cpp, with the rest of the host route)
+// (hipjpegTranscodeHost / hipjpegTranscodeHostRegion: transcode_core.cpp, with the rest of the host route)
+hipjpegStatus_t hipjpegTranscodeBatchSetRegions(hipjpegHandle_t handle, const hipjpegTranscodeRegion_t* regions, int batch_size)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle || batch_size < 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    handle->transcode_regions_set = regions != nullptr;
+    if (regions)
+        handle->transcode_regions.assign(regions, regions + batch_size);
+    else
+        handle->transcode_regions.clear();
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
 hipjpegStatus_t hipjpegTranscodeBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
                                       const hipjpegTranscodeParams_t* params, unsigned flags, hipjpegStatus_t* statuses, void* stream)
 {
@@ -756,34 +772,50 @@ hipjpegStatus_t hipjpegTranscodeBatch(hipjpegHandle_t handle, const uint8_t* con
     if (handle->num_submitted != 0 || handle->encode_in_flight != 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
     handle->transcode_gpu_decoded = handle->transcode_gpu_coded = handle->transcode_blocks = 0;
+    // the regions belong to this batch alone, whatever becomes of it
+    std::vector<hipjpegTranscodeRegion_t> regions;
+    regions.swap(handle->transcode_regions);
+    const bool have_regions = handle->transcode_regions_set;
+    handle->transcode_regions_set = false;
+    if (have_regions && (int)regions.size() != batch_size) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     // (the call blocks and nothing is submitted: the current decode page is free, and staying on it keeps its arenas warm)
     DecodeBatch& d = handle->cur();
-    // decode side: the entropy stage alone, verdicts settled (launch 3 = entropy kernels + resolve) before anything is coded
-    hipjpegStatus_t st = d.plan_coefficients(data, lengths, batch_size, flags, nullptr, handle->pool.get());
+    // decode side: the headers first
+    hipjpegStatus_t st = d.plan_coefficients(data, lengths, batch_size, flags, nullptr, handle->pool.get(), params);
     if (st != HIPJPEG_STATUS_SUCCESS) return st;
-    for (int i = 0; i < batch_size; i++)
+    // the pictures by geometry and the source's tables, as transcode_host derives them: drop chroma -> crop -> turn.  What the header
+    // settles is settled before anything is decoded: a refused request costs no entropy decoding and reports what the host route reports.
+    std::vector<CoefficientPicture> pics((size_t)batch_size);
+    for (int i = 0; i < batch_size; i++) {
+        CoefficientPicture& p = pics[(size_t)i];
         if (transcode_params_ok(params[i]) != HIPJPEG_STATUS_SUCCESS) d.reject(i, HIPJPEG_STATUS_INVALID_ARGUMENT);
+        if ((p.status = d.image(i).status) != HIPJPEG_STATUS_SUCCESS) continue;
+        TranscodePicture source, cropped;
+        const int32_t field = params[i].orientation;
+        const int orientation = transcode_orientation(params[i], data[i], lengths[i]);
+        p.status = transcode_picture(d.image(i).frame, (field & HIPJPEG_TRANSCODE_GRAYSCALE) != 0, &source);
+        if (p.status == HIPJPEG_STATUS_SUCCESS)
+            p.status = transcode_crop(source, have_regions ? &regions[(size_t)i] : nullptr, (field & HIPJPEG_TRANSCODE_CROP_EXPAND) != 0, &cropped, &p.origin);
+        if (p.status == HIPJPEG_STATUS_SUCCESS) p.status = transcode_turn(cropped, orientation, (field & HIPJPEG_TRANSCODE_TRIM) != 0, &p.picture, &p.turn);
+        if (p.status != HIPJPEG_STATUS_SUCCESS) {
+            d.reject(i, p.status);
+            continue;
+        }
+        transcode_markers(params[i], orientation, data[i], lengths[i], &p.markers);
+        p.params.restart_interval = params[i].restart_interval;
+        p.params.optimized_huffman = params[i].optimized_huffman;
+        p.params.progressive = params[i].progressive;
+    }
+    // decode side: the entropy stage alone, verdicts settled (launch 3 = entropy kernels + resolve) before anything is coded
     handle->pool->parallel_for(batch_size, [&](int i, int) { d.entropy_stage(i); });
     d.finalize(nullptr);
     if ((st = d.transfer(stream)) != HIPJPEG_STATUS_SUCCESS || (st = d.launch(stream, 3)) != HIPJPEG_STATUS_SUCCESS) {
         (void)hipStreamSynchronize((hipStream_t)stream);  // nothing of this batch stays queued behind an error
         return st;
     }
-    // encode side: the pictures by geometry and the source's tables, the coefficient area filled by the relayout kernel
-    std::vector<CoefficientPicture> pics((size_t)batch_size);
-    for (int i = 0; i < batch_size; i++) {
-        CoefficientPicture& p = pics[(size_t)i];
-        p.status = d.image(i).status;
-        TranscodePicture source;
-        if (p.status == HIPJPEG_STATUS_SUCCESS) p.status = transcode_picture(d.image(i).frame, &source);
-        if (p.status == HIPJPEG_STATUS_SUCCESS)
-            p.status = transcode_turn(source, transcode_orientation(params[i], data[i], lengths[i]), (params[i].orientation & HIPJPEG_TRANSCODE_TRIM) != 0,
-                                      &p.picture, &p.turn);
-        if (p.status != HIPJPEG_STATUS_SUCCESS) continue;
-        p.params.restart_interval = params[i].restart_interval;
-        p.params.optimized_huffman = params[i].optimized_huffman;
-        p.params.progressive = params[i].progressive;
-    }
+    // encode side: the coefficient area filled by the relayout kernels; what the decoder found wrong with an image stands
+    for (int i = 0; i < batch_size; i++)
+        if (pics[(size_t)i].status == HIPJPEG_STATUS_SUCCESS) pics[(size_t)i].status = d.image(i).status;
     EncodeBatch& e = *handle->encode;
     handle->encode_view = &e;
     if ((st = e.coefficient_stage(pics.data(), batch_size, d.device_descriptors(), stream)) != HIPJPEG_STATUS_SUCCESS) {

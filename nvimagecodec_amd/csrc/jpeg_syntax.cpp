@@ -359,7 +359,9 @@ ParseStatus parse_jpeg(const uint8_t* data, size_t size, FrameInfo* f, bool head
 
 // The sampling layout as the API names it (the reference's parser does the same from the SOF factors, src/parsers/jpeg.cpp:262-330).
 // ---------------------------------------------------------------------------------------------- EXIF orientation (APP1)
-int exif_orientation_tag(const uint8_t* p, size_t n)
+// Offset, inside an APP1 payload, of the two value bytes of IFD0's orientation entry, and the payload's byte order; 0 when the payload
+// is not EXIF or has no such entry (the offset of a real entry is at least 24).
+static size_t exif_orientation_value(const uint8_t* p, size_t n, bool* little_endian)
 {
     if (n < 14 || memcmp(p, "Exif\0\0", 6) != 0) return 0;
     const uint8_t* t = p + 6;
@@ -378,9 +380,20 @@ int exif_orientation_tag(const uint8_t* p, size_t n)
     for (unsigned i = 0; i < cnt; i++) {
         size_t e = ifd + 2 + 12 * (size_t)i;
         if (e + 12 > tn) break;
-        if (u16(e) == 0x0112) return (int)u16(e + 8);
+        if (u16(e) == 0x0112) {
+            *little_endian = le;
+            return 6 + e + 8;
+        }
     }
     return 0;
+}
+
+int exif_orientation_tag(const uint8_t* p, size_t n)
+{
+    bool le = false;
+    const size_t at = exif_orientation_value(p, n, &le);
+    if (at == 0) return 0;
+    return le ? p[at] | (p[at + 1] << 8) : (p[at] << 8) | p[at + 1];
 }
 
 int exif_orientation(const uint8_t* p, size_t n)
@@ -398,6 +411,48 @@ int exif_orientation(const uint8_t* p, size_t n)
         pos += 2 + L;
     }
     return 1;
+}
+
+// ---------------------------------------------------------------------------------------------- APPn / COM segments (-copy all)
+void collect_marker_segments(const uint8_t* p, size_t n, std::vector<uint8_t>* out, size_t* exif_value, bool* exif_little_endian)
+{
+    *exif_value = 0;
+    if (!p || n < 4 || p[0] != 0xFF || p[1] != 0xD8) return;
+    bool seen_exif = false;
+    // parse_jpeg's walk: fill bytes (further 0xFF in front of a marker) are passed over and not copied
+    for (size_t pos = 2;;) {
+        while (pos < n && p[pos] != 0xFF) pos++;
+        while (pos < n && p[pos] == 0xFF) pos++;
+        if (pos >= n) return;
+        const int m = p[pos++];
+        if (m == 0xDA || m == 0xD9) return;
+        if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
+        if (pos + 2 > n) return;
+        const size_t L = ((size_t)p[pos] << 8) | p[pos + 1];
+        if (L < 2 || pos + L > n) return;
+        const uint8_t* payload = p + pos + 2;
+        const bool wanted = ((m >= 0xE0 && m <= 0xEF) || m == 0xFE) && !(m == 0xE0 && L >= 7 && memcmp(payload, "JFIF", 5) == 0);
+        if (wanted) {
+            const size_t at = out->size();
+            out->push_back(0xFF);
+            out->push_back((uint8_t)m);
+            out->insert(out->end(), p + pos, p + pos + L);
+            // the first APP1/Exif segment is the one exif_orientation() reads: where its orientation value lies in the copy
+            if (m == 0xE1 && L >= 8 && !seen_exif && memcmp(payload, "Exif\0\0", 6) == 0) {
+                seen_exif = true;
+                const size_t v = exif_orientation_value(payload, L - 2, exif_little_endian);
+                if (v) *exif_value = at + 4 + v;
+            }
+        }
+        pos += L;
+    }
+}
+
+void reset_exif_orientation(std::vector<uint8_t>* segments, size_t exif_value, bool little_endian)
+{
+    if (exif_value == 0 || exif_value + 2 > segments->size()) return;
+    (*segments)[exif_value] = little_endian ? 1 : 0;
+    (*segments)[exif_value + 1] = little_endian ? 0 : 1;
 }
 
 hipjpegChromaSubsampling_t classify_subsampling(const FrameInfo& f)

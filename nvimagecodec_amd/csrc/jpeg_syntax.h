@@ -86,4 +86,12 @@ int exif_orientation_tag(const uint8_t* payload, size_t n);
 // Of a whole file: the tag of the first APP1/Exif segment before the first scan, 1..8; 1 when it is missing or outside 1..8.
 int exif_orientation(const uint8_t* data, size_t size);
 
+// Appends to `out`, verbatim (marker, length, payload) and in file order, every APP0..APP15 and COM segment between SOI and the first SOS,
+// except an APP0 whose payload begins "JFIF\0" (the writer has its own); fill bytes in front of markers are not copied.  *exif_value:
+// offset in `out` of the two value bytes of the orientation tag in the first APP1/Exif segment copied (the segment exif_orientation()
+// reads), 0 when there is none; *exif_little_endian: that segment's byte order.  Stops quietly at the first thing it cannot walk.
+void collect_marker_segments(const uint8_t* data, size_t size, std::vector<uint8_t>* out, size_t* exif_value, bool* exif_little_endian);
+// Overwrites that value with 1 (exif_value == 0: nothing happens); no other byte of the segment changes.
+void reset_exif_orientation(std::vector<uint8_t>* segments, size_t exif_value, bool little_endian);
+
 }  // namespace hipjpeg

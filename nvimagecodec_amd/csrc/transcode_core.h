@@ -8,6 +8,9 @@
 // rows and negates odd v, a transpose sends block (by, bx) to (bx, by) and coefficient (u, v) to (v, u).  Every orientation is "transpose
 // or not", then "mirror x or not" and "mirror y or not" in the OUTPUT's frame (kTurn* bits): 6 = transpose | mirror x, 8 = transpose |
 // mirror y, 7 = all three.  The host route below applies them in plain C++ and is the definition coef_transform_kernel reproduces.
+//
+// Before the turn come, in this order, the drop of the chroma components (transcode_picture's grayscale mode) and the crop
+// (transcode_crop: a block origin per component, added to the source block's coordinates after the mirrors and the transpose are undone).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -30,12 +33,29 @@ struct TranscodePicture {
 
 // How the output's blocks come from the source's (uniform per image; RelayoutUnit::pad carries it to the kernel)
 constexpr unsigned kTurnTranspose = 1u, kTurnMirrorX = 2u, kTurnMirrorY = 4u;
+// ... and where in the source's grid they start: per component the block origin of a cropped picture (behind the turn in `pad`:
+// transcode_kernels.h kOrigin*)
+struct TranscodeOrigin {
+    int ox[3] = {0, 0, 0}, oy[3] = {0, 0, 0};
+    bool any() const { return (ox[0] | oy[0] | ox[1] | oy[1] | ox[2] | oy[2]) != 0; }
+};
+constexpr uint32_t kTranscodeFlags = HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF | HIPJPEG_TRANSCODE_TRIM | HIPJPEG_TRANSCODE_GRAYSCALE |
+                                     HIPJPEG_TRANSCODE_CROP_EXPAND | HIPJPEG_TRANSCODE_COPY_MARKERS;
 
 // The header rules of include/hipjpeg.h (frame type, components, colour model, sampling, tables): SUCCESS and *p, or UNSUPPORTED.
-hipjpegStatus_t transcode_picture(const FrameInfo& f, TranscodePicture* p);
+// `grayscale` (HIPJPEG_TRANSCODE_GRAYSCALE): the one-component picture of a YCbCr source's luma; the chroma-only rules are waived.
+hipjpegStatus_t transcode_picture(const FrameInfo& f, bool grayscale, TranscodePicture* p);
 // INVALID_ARGUMENT for a restart interval outside 0..65535 or an orientation field with an orientation of 1 or above 8, an orientation next
-// to HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF, or a bit that is neither flag.
+// to HIPJPEG_TRANSCODE_ORIENTATION_FROM_EXIF, or a bit that is none of the flags.
 hipjpegStatus_t transcode_params_ok(const hipjpegTranscodeParams_t& p);
+// The picture `src` (of transcode_picture) cut to `region` (nullptr or all zeros: the whole picture, `src` itself) and the block origins
+// its components are read from.  INVALID_ARGUMENT for a region outside the picture or empty, UNSUPPORTED for an origin off the iMCU grid
+// unless `expand` moves it left / up onto it.
+hipjpegStatus_t transcode_crop(const TranscodePicture& src, const hipjpegTranscodeRegion_t* region, bool expand, TranscodePicture* dst,
+                               TranscodeOrigin* origin);
+// The source's APPn / COM segments as the output carries them (empty without HIPJPEG_TRANSCODE_COPY_MARKERS), the EXIF orientation reset
+// when `orientation` (of transcode_orientation) is a turn.
+void transcode_markers(const hipjpegTranscodeParams_t& p, int orientation, const uint8_t* data, size_t size, std::vector<uint8_t>* markers);
 // The orientation 1..8 the (valid) parameters ask for, the source's own EXIF tag where they say so.
 int transcode_orientation(const hipjpegTranscodeParams_t& p, const uint8_t* data, size_t size);
 // The picture `src` (of transcode_picture) brought upright for `orientation`, and the kTurn* bits that say where its blocks come from.
@@ -44,6 +64,7 @@ int transcode_orientation(const hipjpegTranscodeParams_t& p, const uint8_t* data
 hipjpegStatus_t transcode_turn(const TranscodePicture& src, int orientation, bool trim, TranscodePicture* dst, unsigned* turn);
 EntropyEncodeOptions transcode_options(const hipjpegTranscodeParams_t& p);
 // Host route.  Appends the file to `out`; nothing is appended unless the status is SUCCESS.
-hipjpegStatus_t transcode_host(const uint8_t* data, size_t size, const hipjpegTranscodeParams_t& params, std::vector<uint8_t>* out);
+hipjpegStatus_t transcode_host(const uint8_t* data, size_t size, const hipjpegTranscodeParams_t& params, const hipjpegTranscodeRegion_t* region,
+                               std::vector<uint8_t>* out);
 
 }  // namespace hipjpeg

@@ -21,6 +21,8 @@
 // before, and computes the source block of each; every source block is still one aligned 128-byte read.  The block's own transpose costs
 // nothing: the decoder's block is column-major, so gathering with row-major offsets (a second offsets table) IS the transpose.  A mirror
 // negates the coefficients of odd horizontal / vertical frequency: per piece an 8-bit mask, applied while the halves are packed.
+// A picture cropped at an origin other than (0, 0) takes this kernel too, turned or not (turn 0 is the plain copy): the origin of the
+// unit's component rides behind the turn in RelayoutUnit::pad.
 #include <hip/hip_runtime.h>
 
 #include "transcode_kernels.h"
@@ -206,11 +208,16 @@ __global__ __launch_bounds__(kThreads) void coef_transform_kernel(const DecodeIm
     const unsigned dst_w = c == 0 ? im.blocks_w[0] : c == 1 ? im.blocks_w[1] : im.blocks_w[2];
     gbl_i16* out = (gbl_i16*)(c == 0 ? im.coef[0] : c == 1 ? im.coef[1] : im.coef[2]);
     const unsigned src_w = sc.blocks_w, nreal = real_w * real_h;
-    const gbl_i16* in = (const gbl_i16*)sc.coef;
-    const gbl_i16* dcs = (const gbl_i16*)sc.dc;
     const unsigned dc_stride = sc.dc_stride;
     // the turn (uniform): bit 0 transpose, bit 1 mirror x, bit 2 mirror y of the output
     const bool transpose = (u.pad & 1u) != 0u, mirror_x = (u.pad & 2u) != 0u, mirror_y = (u.pad & 4u) != 0u;
+    // the crop (uniform): block (oy, ox) of the decoder's grid is where this component of the picture begins.  The origin is added after
+    // the mirrors and the transpose are undone, i.e. to every source block alike: it moves the two base pointers, once per workgroup on
+    // the scalar unit, and the per-block address arithmetic stays what it is for an uncropped picture.
+    const unsigned ox = (u.pad >> kOriginShiftX) & kOriginMask, oy = (u.pad >> kOriginShiftY) & kOriginMask;
+    const size_t first = (size_t)oy * src_w + ox;
+    const gbl_i16* in = (const gbl_i16*)sc.coef + first * 64;
+    const gbl_i16* dcs = (const gbl_i16*)sc.dc + first * dc_stride;
 
     const unsigned piece = threadIdx.x & 7u, slot_index = threadIdx.x >> 3;
     lds_char* slot = (lds_char*)slots + slot_index * kSlotStride;
@@ -227,7 +234,8 @@ __global__ __launch_bounds__(kThreads) void coef_transform_kernel(const DecodeIm
     };
     // As in coef_relayout_kernel no branch surrounds the loads; lanes past the unit's last block read the source of the component's
     // last output block again.  The source block: undo the output's mirrors over its real area, then the transpose -- the real area
-    // of the (trimmed) source is the output's with the axes swapped, so every index stays inside the decoder's grid.
+    // of the (cropped, trimmed) source is the output's with the axes swapped, and transcode_crop keeps origin + real area inside the
+    // source's own real area, so every index stays inside the decoder's grid.
     auto fetch = [&](int pass) {
         Fetched f;
         const unsigned r = u.first_block + (unsigned)pass * kBlocksPerPass + slot_index;

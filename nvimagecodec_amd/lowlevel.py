@@ -543,14 +543,21 @@ class BatchEncoder:
         return dict(units=u.value, pixel_bytes=pb.value, coef_bytes=cb.value, gpu_entropy_images=int(N.load().hipjpegEncodeBatchGpuEntropyImages(self._h)))
 
 
-def _orientation_field(orientation, trim, from_exif):
+def _orientation_field(orientation, trim, from_exif, grayscale=False, expand=False, copy_markers=False):
     """hipjpegTranscodeParams_t::orientation"""
+    flags = (N.TRANSCODE_TRIM if trim else 0) | (N.TRANSCODE_GRAYSCALE if grayscale else 0) | (N.TRANSCODE_CROP_EXPAND if expand else 0) | \
+        (N.TRANSCODE_COPY_MARKERS if copy_markers else 0)
     if from_exif:
-        return N.TRANSCODE_ORIENTATION_FROM_EXIF | (N.TRANSCODE_TRIM if trim else 0)
+        return N.TRANSCODE_ORIENTATION_FROM_EXIF | flags
     o = int(orientation)
     if not 0 <= o <= 8:
         raise ValueError("orientation must be 1..8")
-    return (0 if o == 1 else o) | (N.TRANSCODE_TRIM if trim else 0)  # the field spells the identity 0
+    return (0 if o == 1 else o) | flags  # the field spells the identity 0
+
+
+def _region(region):
+    """hipjpegTranscodeRegion_t of (x0, y0, x1, y1); None = the whole picture (all zeros)"""
+    return N.TranscodeRegion(*(int(v) for v in region)) if region is not None else N.TranscodeRegion(0, 0, 0, 0)
 
 
 def exif_orientation(data):
@@ -563,24 +570,30 @@ def exif_orientation(data):
     return o.value
 
 
-def transcode_host(data, optimized_huffman=False, progressive=False, restart_interval=0, orientation=1, trim=False, from_exif=False):
+def transcode_host(data, optimized_huffman=False, progressive=False, restart_interval=0, orientation=1, trim=False, from_exif=False, region=None,
+                   grayscale=False, expand=False, copy_markers=False):
     """Lossless transcode on the host (no GPU): host entropy decoder -> host coder.  The file keeps every coefficient and the
-    quantization tables of the source; APPn / COM segments are not copied.  orientation 1..8: the file holds the picture brought
+    quantization tables of the source; APPn / COM segments are copied only with copy_markers (the EXIF orientation is reset to 1 when
+    the picture is turned).  Before the turn: grayscale drops the chroma components, then region=(x0, y0, x1, y1) (stored-image
+    coordinates, end exclusive) cuts the picture; its origin must lie on the iMCU grid unless expand moves it left / up onto it.  orientation 1..8: the file holds the picture brought
     upright for that EXIF value (from_exif: for the source's own tag), still without requantizing; a mirror moves whole iMCUs, so the
     mirrored axes must be multiples of the iMCU size unless trim cuts them (include/hipjpeg.h).  Raises HipJpegError: UNSUPPORTED for
     sources the coder cannot take (include/hipjpeg.h lists the rules), the decoder's statuses for damaged ones."""
     a = _as_u8(data)
-    p = N.TranscodeParams(int(bool(optimized_huffman)), int(bool(progressive)), int(restart_interval), _orientation_field(orientation, trim, from_exif))
+    p = N.TranscodeParams(int(bool(optimized_huffman)), int(bool(progressive)), int(restart_interval),
+                          _orientation_field(orientation, trim, from_exif, grayscale, expand, copy_markers))
+    r = _region(region)
     n = ctypes.c_size_t()
     cap = a.size * 2 + 65536
     for _ in range(2):
         out = np.empty(cap, dtype=np.uint8)
-        st = N.load().hipjpegTranscodeHost(a.ctypes.data, a.size, ctypes.byref(p), out.ctypes.data, cap, ctypes.byref(n))
+        st = N.load().hipjpegTranscodeHostRegion(a.ctypes.data, a.size, ctypes.byref(p), ctypes.byref(r) if region is not None else None,
+                                                 out.ctypes.data, cap, ctypes.byref(n))
         if st != 9:  # BUFFER_TOO_SMALL: n holds the needed size
             break
         cap = n.value
     if st:
-        raise N.HipJpegError(st, "hipjpegTranscodeHost")
+        raise N.HipJpegError(st, "hipjpegTranscodeHostRegion")
     return out[: n.value].tobytes()
 
 
@@ -617,18 +630,27 @@ class BatchTranscoder:
             raise N.HipJpegError(st, "hipjpegSetHybridHuffmanThreshold")
 
     def transcode(self, jpegs, optimized_huffman=False, progressive=False, restart_interval=0, stream=None, gpu_huffman=None, orientation=1,
-                  trim=False, from_exif=False):
+                  trim=False, from_exif=False, region=None, grayscale=False, expand=False, copy_markers=False):
         """Returns (statuses, files): files[i] is bytes, or None where statuses[i] != 0.  optimized_huffman / progressive /
-        restart_interval / orientation: one value for the batch or a list with one per image.  orientation, trim, from_exif: as
-        transcode_host."""
+        restart_interval / orientation / grayscale / copy_markers: one value for the batch or a list with one per image.  region: None,
+        one (x0, y0, x1, y1) for every image, or a list with a tuple or None per image.  orientation, trim, from_exif, region, grayscale,
+        expand, copy_markers: as transcode_host."""
         n = len(jpegs)
         if gpu_huffman is None:
             gpu_huffman = self.gpu_huffman
         flags = (N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0)) if gpu_huffman else 0
-        per = [v if isinstance(v, (list, tuple)) else [v] * n for v in (optimized_huffman, progressive, restart_interval, orientation)]
+        per = [v if isinstance(v, (list, tuple)) else [v] * n for v in (optimized_huffman, progressive, restart_interval, orientation, grayscale,
+                                                                         copy_markers)]
         P = (N.TranscodeParams * n)()
         for i in range(n):
-            P[i] = N.TranscodeParams(int(bool(per[0][i])), int(bool(per[1][i])), int(per[2][i]), _orientation_field(per[3][i], trim, from_exif))
+            P[i] = N.TranscodeParams(int(bool(per[0][i])), int(bool(per[1][i])), int(per[2][i]),
+                                     _orientation_field(per[3][i], trim, from_exif, per[4][i], expand, per[5][i]))
+        if region is not None:
+            regions = region if isinstance(region, list) else [region] * n
+            R = (N.TranscodeRegion * max(n, 1))(*[_region(r) for r in regions])
+            st = N.load().hipjpegTranscodeBatchSetRegions(self._h, R, len(regions))
+            if st:
+                raise N.HipJpegError(st, "hipjpegTranscodeBatchSetRegions")
         arrs = [j if (hasattr(j, "data_ptr") and hasattr(j, "numel")) else _as_u8(j) for j in jpegs]
         ptrs = (ctypes.c_void_p * n)(*[(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data) for a in arrs])
         lens = (ctypes.c_size_t * n)(*[(a.numel() if hasattr(a, "numel") else a.size) for a in arrs])

@@ -5,7 +5,11 @@
      the same output settings, one call outstanding (its decoding + encoding stage times, file reading and parsing left out);
  (c) with --orientation: coef_transform_kernel on the same batch turned for each of the given EXIF orientations (with trim: 1080 is no
      multiple of the 16-row iMCU), its time next to coef_relayout_kernel's of (a), per batch and per block moved.
-usage: python tools/prof_transcode.py [--batch 256] [--steps 5] [--orientation 2,5,6] [--skip-pixel-route]"""
+ (d) with --crop WxH+X+Y (jpegtran's spelling; the origin on the 16x16 iMCU grid): coef_transform_kernel on the same batch cut to that
+     region, as it is and brought upright for orientation 6, its time per carried block next to coef_relayout_kernel's of (a); and images/s
+     of hipjpegTranscodeBatch for that crop next to the pixel route decode (the region through hipjpegDecodeBatchSetTransforms) -> encode
+     of this library, optimized tables both ways.
+usage: python tools/prof_transcode.py [--batch 256] [--steps 5] [--orientation 2,5,6] [--crop 1280x720+320+176] [--skip-pixel-route]"""
 import argparse
 import os
 import re
@@ -45,6 +49,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--orientation", default="", help="comma-separated EXIF orientations 2..8 to time coef_transform_kernel on")
+    ap.add_argument("--crop", default="", help="WxH+X+Y: also time the batch cut to this region, orientation 1 and 6")
     ap.add_argument("--skip-pixel-route", action="store_true")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
@@ -76,6 +81,7 @@ def main():
         print(f"[{name}] coef_relayout_kernel: median {k:.4f} ms per batch (min {min(ms):.4f}, max {max(ms):.4f}, {len(ms)} launches), {nbytes / 1e6:.1f} MB read + "
               f"as many written: {2 * nbytes / k / 1e6:.0f} GB/s of traffic")
     identity_ms, identity_blocks = k, st["relayout_blocks"]
+    nbytes = identity_blocks * 128
     for orientation in [int(v) for v in a.orientation.split(",") if v]:
         kw = dict(optimized_huffman=True, orientation=orientation, trim=True)
         for _ in range(2):
@@ -94,6 +100,53 @@ def main():
         print(f"[orientation {orientation}] coef_transform_kernel: median {m:.4f} ms per batch (min {min(ms):.4f}, max {max(ms):.4f}, {len(ms)} launches), "
               f"{blocks} blocks ({blocks / identity_blocks:.4f} of the untrimmed batch): {2 * blocks * 128 / m / 1e6:.0f} GB/s of traffic; "
               f"/ coef_relayout_kernel = {m / identity_ms:.3f} per batch, {m / blocks / (identity_ms / identity_blocks):.3f} per block")
+    if a.crop:
+        w, h, x, y = (int(v) for v in re.fullmatch(r"(\d+)x(\d+)\+(\d+)\+(\d+)", a.crop).groups())
+        region = (x, y, x + w, y + h)
+        for orientation in (1, 6):
+            kw = dict(optimized_huffman=True, orientation=orientation, trim=True, region=region)
+            for _ in range(2):
+                statuses, files = t.transcode(jpegs, **kw)
+            assert statuses == [0] * a.batch
+            assert files[0] == lowlevel.transcode_host(jpegs[0], **kw), "the device route must write the host route's file"
+
+            def cropped():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    t.transcode(jpegs, **kw)
+                torch.cuda.synchronize()
+                return time.perf_counter() - t0
+
+            seconds, ms_identity, ms = kernel_times(cropped)
+            assert not ms_identity and len(ms) == a.steps
+            blocks = t.stats()["relayout_blocks"]
+            m = sorted(ms)[len(ms) // 2]
+            print(f"[crop {a.crop}, orientation {orientation}] coef_transform_kernel: median {m:.4f} ms per batch (min {min(ms):.4f}, max {max(ms):.4f}, "
+                  f"{len(ms)} launches), {blocks} blocks carried: {2 * blocks * 128 / m / 1e6:.0f} GB/s of traffic; per block / coef_relayout_kernel per block = "
+                  f"{m / blocks / (identity_ms / identity_blocks):.3f}; hipjpegTranscodeBatch {a.batch * a.steps / seconds:.0f} images/s")
+        if not a.skip_pixel_route:
+            dec = lowlevel.BatchDecoder(device=0, num_threads=bench.usable_cpus())
+            enc = lowlevel.BatchEncoder(device=0, num_threads=bench.usable_cpus(), gpu_huffman=True)
+            transforms = [(region, 1)] * a.batch
+            outs = dec.allocate_outputs(jpegs, "rgb", transforms)
+
+            def pixel_route():
+                dec.decode(jpegs, fmt="rgb", outs=outs, gpu_huffman=True, transforms=transforms)
+                return enc.encode(outs, "420", 90, optimized_huffman=True)
+
+            for _ in range(2):
+                pixel_route()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                pixel_route()
+            torch.cuda.synchronize()
+            seconds = time.perf_counter() - t0
+            print(f"[crop {a.crop}] decode with the region -> encode (4:2:0 q90, optimized tables, both entropy stages on the GPU): "
+                  f"{a.batch * a.steps / seconds:.0f} images/s")
+            dec.close()
+            enc.close()
     # the same byte count through the copy engine's kernel path, same run
     a_dev = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     b_dev = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
