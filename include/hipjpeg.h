@@ -410,6 +410,71 @@ HIPJPEG_API hipjpegStatus_t hipjpegTranscodeBatch(hipjpegHandle_t handle, const 
 HIPJPEG_API hipjpegStatus_t hipjpegTranscodeBatchStats(hipjpegHandle_t handle, int32_t* gpu_decoded_images, int32_t* gpu_coded_images,
                                                        int32_t* relayout_blocks);
 
+/* ---- coefficient tensors: the quantized DCT coefficients between the two entropy stages, read from a JPEG file and written to one
+ *      (libjpeg's jpeg_read_coefficients / jpeg_write_coefficients), on the host or as device memory that never leaves HBM.
+ *      Layout (one definition for every call below): a component's coefficients are int16 blocks of 64 values in NATURAL order
+ *      (row * 8 + column, libjpeg's JBLOCK), the blocks in raster order over the component's REAL block area: blocks_w[c] =
+ *      ceil(samp_w[c] / 8) by blocks_h[c] = ceil(samp_h[c] / 8) -- libjpeg's width_in_blocks / height_in_blocks, not the MCU-padded grid.
+ *      Block (by, bx) lies at coef[c] + (by * pitch_blocks[c] + bx) * 64 with pitch_blocks[c] >= blocks_w[c]; what lies between blocks_w
+ *      and the pitch is neither read nor written.  The values are the quantized ones as the stream codes them; nothing is dequantized.
+ *      Quantization tables are uint16[64] in natural order, one per component.
+ *
+ *      Reading takes every frame the decoder decodes: SOF0 / SOF1 / SOF2 with 8-bit samples, 1..4 components (CMYK / YCCK included), every
+ *      sampling layout, multi-scan sequential streams, restart intervals.  Everything else keeps the status decoding gives it
+ *      (UNSUPPORTED, BAD_JPEG, TRUNCATED, CORRUPT).  An image that fails writes nothing into its planes.
+ *
+ *      Writing takes what the writer writes -- the header rules of the lossless transcode above, judged on the `info`: one component, or
+ *      three with colour model YCbCr; chroma 1x1 and luma 1x1, 2x1, 2x2, 1x2, 4x1 or 4x2; every quantizer in 1..255 and equal Cb / Cr
+ *      tables; every DC value in [-1024, 1023] and every AC value in [-1023, 1023] over the real area.  Otherwise the image is
+ *      HIPJPEG_STATUS_UNSUPPORTED.  HIPJPEG_STATUS_INVALID_ARGUMENT for that image: a size outside 1..65535, blocks_w / blocks_h that
+ *      are not what the geometry gives, a pitch below blocks_w, a null pointer, a pointer that is not 16-byte aligned, a restart
+ *      interval outside 0..65535, a `params.orientation` other than 0.  The file is the one hipjpegEncodeFromCoefficientsHost writes for
+ *      that geometry, those coefficients and those tables: APP0, components 1/2/3, SOF0 or SOF2, libjpeg's dummy blocks beyond the real
+ *      area; no APPn / COM is carried.  Writing what was read from a transcodable source gives, byte for byte, the file
+ *      hipjpegTranscodeHost writes for the same coding parameters. ---- */
+typedef struct {
+    int32_t width, height, num_components; /* 1..4 when read; 1 or 3 when written */
+    int32_t color_model;                   /* as hipjpegImageInfo_t */
+    int32_t h[4], v[4];
+    int32_t blocks_w[4], blocks_h[4];      /* real block area per component */
+    uint16_t qtable[4][64];                /* natural order */
+} hipjpegCoefficientInfo_t;
+
+typedef struct {
+    void* coef[4]; /* device (or host, for the *Host calls) int16, 16-byte aligned */
+    uint32_t pitch_blocks[4];
+} hipjpegCoefficientPlanes_t;
+
+/* Host only: geometry and tables from the header, so that a caller can allocate before decoding. */
+HIPJPEG_API hipjpegStatus_t hipjpegGetCoefficientInfo(const uint8_t* data, size_t length, hipjpegCoefficientInfo_t* info);
+/* Host only, usable without a GPU (links without the HIP runtime, like hipjpegTranscodeHost): host entropy decoder -> planes. */
+HIPJPEG_API hipjpegStatus_t hipjpegDecodeCoefficientsHost(const uint8_t* data, size_t length, const hipjpegCoefficientPlanes_t* planes);
+/* Host only: planes -> host coder.  `params`: optimized_huffman, progressive, restart_interval; orientation must be 0.
+ * HIPJPEG_STATUS_BUFFER_TOO_SMALL with *out_length = needed size if capacity is insufficient (as hipjpegEncodeFromCoefficientsHost). */
+HIPJPEG_API hipjpegStatus_t hipjpegEncodeCoefficientsHost(const hipjpegCoefficientInfo_t* info, const hipjpegCoefficientPlanes_t* planes,
+                                                          const hipjpegTranscodeParams_t* params, uint8_t* out, size_t capacity,
+                                                          size_t* out_length);
+/* Device: entropy decode (`flags` as in hipjpegTranscodeBatch: HIPJPEG_FLAG_GPU_HUFFMAN = on the device for every image it takes,
+ * honouring hipjpegSetHybridHuffmanThreshold; 0 = host pool), then coef_export_kernel (csrc/coefficient_kernels.hip: decoder layout ->
+ * planes[i]) queued on `stream`.  The call returns with final statuses -- the entropy verdicts are settled -- and the caller orders on
+ * `stream` before reading the planes.  The tensors do not depend on the flags.  A failing image leaves its planes and the rest of the
+ * batch alone.  The call takes the handle's current decode page: it must not overlap a hipjpegDecodeBatchSubmit /
+ * hipjpegEncodeBatchSubmit still in flight on the same handle (HIPJPEG_STATUS_INVALID_ARGUMENT). */
+HIPJPEG_API hipjpegStatus_t hipjpegDecodeCoefficientsBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
+                                                           const hipjpegCoefficientPlanes_t* planes, unsigned flags, hipjpegStatus_t* statuses,
+                                                           void* stream);
+/* Device: coef_import_kernel (planes[i] -> the coder's layout, with the range check) queued on `stream` -- planes produced on that
+ * stream need no extra synchronisation -- then the entropy coder (`flags` as in hipjpegTranscodeBatch); blocks until the files exist.
+ * They are then read with hipjpegEncodeGetBitstream(handle, i, ...), which reports the image's status for an image without a file.  The
+ * bytes do not depend on the flags.  The call takes the handle's encode batch: the same rule about Submits in flight. */
+HIPJPEG_API hipjpegStatus_t hipjpegEncodeCoefficientsBatch(hipjpegHandle_t handle, const hipjpegCoefficientInfo_t* infos,
+                                                           const hipjpegCoefficientPlanes_t* planes, const hipjpegTranscodeParams_t* params,
+                                                           int batch_size, unsigned flags, hipjpegStatus_t* statuses, void* stream);
+/* Of the handle's last hipjpegDecodeCoefficientsBatch: images the GPU entropy decoder took; of its last hipjpegEncodeCoefficientsBatch:
+ * images the GPU entropy coder took; and the blocks the last of the two calls moved (the real blocks of every image that reached its kernel). */
+HIPJPEG_API hipjpegStatus_t hipjpegCoefficientsBatchStats(hipjpegHandle_t handle, int32_t* gpu_decoded_images, int32_t* gpu_coded_images,
+                                                          int64_t* moved_blocks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,18 @@ class TranscodeRegion(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("x0", "y0", "x1", "y1")]
 
 
+class CoefficientInfo(ctypes.Structure):
+    """hipjpegCoefficientInfo_t: geometry, real block areas and quantization tables (natural order) of a picture given by its coefficients"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "num_components", "color_model")] + [
+        ("h", ctypes.c_int32 * 4), ("v", ctypes.c_int32 * 4), ("blocks_w", ctypes.c_int32 * 4), ("blocks_h", ctypes.c_int32 * 4),
+        ("qtable", (ctypes.c_uint16 * 64) * 4)]
+
+
+class CoefficientPlanes(ctypes.Structure):
+    """hipjpegCoefficientPlanes_t: per component int16 blocks in natural order, block (by, bx) at coef + (by * pitch_blocks + bx) * 64"""
+    _fields_ = [("coef", ctypes.c_void_p * 4), ("pitch_blocks", ctypes.c_uint32 * 4)]
+
+
 CSS = {"444": 0, "422": 1, "420": 2, "440": 3, "411": 4, "410": 5, "gray": 6}
 
 
@@ -149,5 +161,12 @@ def load():
     L.hipjpegTranscodeBatch.argtypes = [vp, vp, vp, i32, vp, ctypes.c_uint, vp, vp]
     L.hipjpegGetExifOrientation.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_int32)]
     L.hipjpegTranscodeBatchStats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+    L.hipjpegGetCoefficientInfo.argtypes = [vp, sz, ctypes.POINTER(CoefficientInfo)]
+    L.hipjpegDecodeCoefficientsHost.argtypes = [vp, sz, ctypes.POINTER(CoefficientPlanes)]
+    L.hipjpegEncodeCoefficientsHost.argtypes = [ctypes.POINTER(CoefficientInfo), ctypes.POINTER(CoefficientPlanes), ctypes.POINTER(TranscodeParams), vp, sz,
+                                                ctypes.POINTER(sz)]
+    L.hipjpegDecodeCoefficientsBatch.argtypes = [vp, vp, vp, i32, vp, ctypes.c_uint, vp, vp]
+    L.hipjpegEncodeCoefficientsBatch.argtypes = [vp, vp, vp, vp, i32, ctypes.c_uint, vp, vp]
+    L.hipjpegCoefficientsBatchStats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)]
     _lib = L
     return L

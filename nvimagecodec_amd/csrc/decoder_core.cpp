@@ -68,7 +68,7 @@ hipjpegStatus_t status_from_parse(ParseStatus s)
 // ---------------------------------------------------------------- DecodeBatch
 DecodeBatch::DecodeBatch(int device_id, const MemoryHooks* hooks)
     : device_id_(device_id), pinned_(Buffer::kPinned, hooks), device_(Buffer::kDevice, hooks), planes_(Buffer::kDevice, hooks),
-      work_(Buffer::kDevice, hooks)
+      export_pinned_(Buffer::kPinned, hooks), export_device_(Buffer::kDevice, hooks), work_(Buffer::kDevice, hooks)
 {
 }
 
@@ -197,6 +197,7 @@ struct DecodeBatch::PlanArgs {  // plan()'s arguments; give_up: per image, given
     const uint8_t* const* data; const size_t* lengths; const hipjpegOutput_t* outputs; hipjpegOutputFormat_t format; unsigned flags;
     const hipjpegOutputFormat_t* formats; const hipjpegTransform_t* transforms; const char* give_up;
     const hipjpegTranscodeParams_t* transcode = nullptr;  // plan_coefficients(): per image, or nullptr
+    bool any_frame = false;                               // plan_coefficients(): the coder's rules are not asked
 };
 
 // What the per-image sizing adds up, in bytes unless noted; every region is carved in image order.
@@ -230,11 +231,12 @@ hipjpegStatus_t DecodeBatch::plan(const uint8_t* const* data, const size_t* leng
 }
 
 hipjpegStatus_t DecodeBatch::plan_coefficients(const uint8_t* const* data, const size_t* lengths, int n, unsigned flags, hipjpegStatus_t* statuses,
-                                               ForkJoinPool* pool, const hipjpegTranscodeParams_t* params)
+                                               ForkJoinPool* pool, const hipjpegTranscodeParams_t* params, bool any_frame)
 {
     pool_ = pool;
     coef_only_ = true;
-    return plan_attempts(PlanArgs{data, lengths, nullptr, HIPJPEG_OUTPUT_RGBI, flags & HIPJPEG_FLAG_GPU_HUFFMAN, nullptr, nullptr, nullptr, params}, n, statuses);
+    return plan_attempts(PlanArgs{data, lengths, nullptr, HIPJPEG_OUTPUT_RGBI, flags & HIPJPEG_FLAG_GPU_HUFFMAN, nullptr, nullptr, nullptr, params, any_frame}, n,
+                         statuses);
 }
 
 hipjpegStatus_t DecodeBatch::plan_attempts(const PlanArgs& a, int n, hipjpegStatus_t* statuses)
@@ -327,7 +329,7 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
         TranscodePicture pic;
         im.variant = -4;
         const bool grayscale = a.transcode && (a.transcode[i].orientation & HIPJPEG_TRANSCODE_GRAYSCALE) != 0;
-        if (im.status == HIPJPEG_STATUS_SUCCESS) im.status = transcode_picture(f, grayscale, &pic);
+        if (im.status == HIPJPEG_STATUS_SUCCESS && !a.any_frame) im.status = transcode_picture(f, grayscale, &pic);
     } else {
         if (im.status == HIPJPEG_STATUS_SUCCESS && !choose_variant(f, fmt, fancy, &im.variant)) im.status = HIPJPEG_STATUS_UNSUPPORTED;
         for (int p = 0; im.status == HIPJPEG_STATUS_SUCCESS && p < (fmt == kOutPlanarYUV ? f.ncomp : out_planes(fmt)); p++)
@@ -1534,6 +1536,58 @@ hipjpegStatus_t DecodeBatch::launch(void* stream, int which, void* entropy_strea
     }
     if (!ensure_event(&done_event_) || hipEventRecord((hipEvent_t)done_event_, (hipStream_t)stream) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
     in_flight_ = true;
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+// ---------------------------------------------------------------- coefficient tensors
+hipjpegStatus_t DecodeBatch::export_coefficients(const hipjpegCoefficientPlanes_t* planes, void* stream)
+{
+    exported_blocks_ = 0;
+    if (!coef_only_ || !finalized_ || (!planes && !images_.empty())) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(device_id_) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    std::vector<CoefPlane> table(images_.size() * 4, CoefPlane{nullptr, 0, 0, 0, 0});
+    std::vector<RelayoutUnit> units;
+    for (size_t i = 0; i < images_.size(); i++) {
+        const PlannedImage& im = images_[i];
+        if (im.status != HIPJPEG_STATUS_SUCCESS) continue;
+        for (int c = 0; c < im.frame.ncomp; c++) {
+            const uint32_t real_w = (uint32_t)(im.frame.comp[c].samp_w + 7) / 8, real_h = (uint32_t)(im.frame.comp[c].samp_h + 7) / 8;
+            table[i * 4 + c] = CoefPlane{static_cast<int16_t*>(planes[i].coef[c]), planes[i].pitch_blocks[c], real_w, real_h, 0};
+            for (uint32_t b = 0; b < real_w * real_h; b += kRelayoutBlocksPerUnit) units.push_back(RelayoutUnit{(uint32_t)i, (uint32_t)c, b, 0});
+            exported_blocks_ += (uint64_t)real_w * real_h;
+        }
+    }
+    if (units.empty()) return HIPJPEG_STATUS_SUCCESS;
+    // (the previous export of this page has drained: plan_coefficients() waited for the event recorded below)
+    Carve carve;
+    const size_t table_at = carve.take(sizeof(CoefPlane) * table.size()), units_at = carve.take(sizeof(RelayoutUnit) * units.size());
+    hipjpegStatus_t st;
+    if ((st = export_pinned_.reserve(carve.end + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
+    if ((st = export_device_.reserve(carve.end + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
+    copy_table(export_pinned_, table_at, table);
+    copy_table(export_pinned_, units_at, units);
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(export_device_.data(), export_pinned_.data(), carve.end, hipMemcpyHostToDevice, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+    // HIPJPEG_DEBUG_TIMING (debug aid): the kernel's own time on stderr (tools/prof_coefficients.py reads it); the aid waits for the kernel
+    static const bool timing = getenv("HIPJPEG_DEBUG_TIMING") != nullptr;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (timing && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, s) != hipSuccess)) return HIPJPEG_STATUS_HIP_ERROR;
+    if (launch_coef_export(device_descriptors(), at<const CoefPlane>(export_device_, table_at), at<const RelayoutUnit>(export_device_, units_at),
+                           (int)units.size(), stream) != 0)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    debug_check(stream, "coef_export", (int)units.size());
+    if (timing) {
+        float ms = 0;
+        if (hipEventRecord(t1, s) != hipSuccess || hipEventSynchronize(t1) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        fprintf(stderr, "[hipjpeg] coef_export_kernel: %zu workgroups, %llu blocks, %.4f ms\n", units.size(), (unsigned long long)exported_blocks_, ms);
+        (void)hipEventDestroy(t0);
+        (void)hipEventDestroy(t1);
+    }
+    // the kernel reads this page's coefficient arena and the tables above: nothing rewrites them before it has run
+    if (!ensure_event(&done_event_) || hipEventRecord((hipEvent_t)done_event_, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+    in_flight_ = true;
+    last_stream_ = stream;
     return HIPJPEG_STATUS_SUCCESS;
 }
 

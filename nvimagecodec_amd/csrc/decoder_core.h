@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/hipjpeg.h"
+#include "coefficient_kernels.h"
 #include "device_layout.h"
 #include "decode_kernels.h"
 #include "gpu_huffman.h"
@@ -95,8 +96,14 @@ public:
     // HIPJPEG_FLAG_GPU_HUFFMAN counts.  Sources the coder cannot take (transcode_core.h transcode_picture) are UNSUPPORTED.
     // Then entropy_stage() per image, finalize(), transfer() and launch(stream, 3) as for any batch.
     // `params` (per image, or nullptr): HIPJPEG_TRANSCODE_GRAYSCALE waives the chroma rules for that image.
+    // `any_frame` (hipjpegDecodeCoefficientsBatch): every frame the entropy stage decodes is taken, whatever the coder thinks of it.
     hipjpegStatus_t plan_coefficients(const uint8_t* const* data, const size_t* lengths, int n, unsigned flags, hipjpegStatus_t* statuses,
-                                      ForkJoinPool* pool, const hipjpegTranscodeParams_t* params = nullptr);
+                                      ForkJoinPool* pool, const hipjpegTranscodeParams_t* params = nullptr, bool any_frame = false);
+    // Coefficient tensors (hipjpegDecodeCoefficientsBatch), behind plan_coefficients() ... launch(stream, 3): coef_export_kernel
+    // (coefficient_kernels.hip) copies the real blocks of every image that decoded into planes[i] (checked by the caller: pointers,
+    // alignment, pitch), natural order, queued on `stream`.  Images with a status other than SUCCESS are left out.
+    hipjpegStatus_t export_coefficients(const hipjpegCoefficientPlanes_t* planes, void* stream);
+    uint64_t exported_blocks() const { return exported_blocks_; }  // blocks the last export_coefficients() moved
     // The batch's DecodeImage table as the kernels see it (valid after transfer()).
     const DecodeImage* device_descriptors() const { return at<const DecodeImage>(device_, staging_.desc); }
     // GPU entropy stage only for images of MORE than this many pixels (width x height); smaller ones keep the host Huffman decoder.
@@ -164,6 +171,8 @@ private:
     hipjpegStatus_t reserve(const Sizing& s);
     void bind_pointers(const Sizing& s);
     Buffer pinned_, device_, planes_;
+    Buffer export_pinned_, export_device_;  // export_coefficients(): CoefPlane[4 n] | RelayoutUnit[]
+    uint64_t exported_blocks_ = 0;
     // Staging area, pinned and mirrored on the device at the same offsets:  descriptors | work units | entropy descriptors, units,
     // tables | staged bitstreams [streams, coef) | coefficients of host-decoded images  ||  (device only from h2d_bytes) coefficients of
     // GPU-decoded images.  The pinned side keeps 256 spare bytes behind h2d_bytes (entropy_launch_args).

@@ -99,6 +99,7 @@ hipjpegStatus_t EncodeBatch::device_stage(const hipjpegEncodeInput_t* inputs, co
     markers_.assign((size_t)n, std::vector<uint8_t>());
     units_.clear();
     relayout_units_.clear();
+    coef_planes_.clear();
     for (auto& v : unit_lists_) v.clear();
     coef_total_ = 0;
     pixel_bytes_ = coef_bytes_ = 0;
@@ -208,6 +209,7 @@ void EncodeBatch::layout()
     staging_.units = c.take(sizeof(EncodeUnit) * units_.size());
     staging_.relayout = c.take(sizeof(RelayoutUnit) * relayout_units_.size());
     staging_.flags = c.take(relayout_units_.empty() ? 0 : sizeof(uint32_t) * images_.size());
+    staging_.planes = c.take(sizeof(CoefPlane) * coef_planes_.size());
     staging_.coef = c.take(coef_total_);
     staging_.total = c.end;
 }
@@ -229,6 +231,7 @@ void EncodeBatch::bind_pointers()
     copy_table(pinned_desc_, staging_.desc, desc_);
     copy_table(pinned_desc_, staging_.units, units_);
     copy_table(pinned_desc_, staging_.relayout, relayout_units_);
+    copy_table(pinned_desc_, staging_.planes, coef_planes_);
     if (!relayout_units_.empty()) memset(pinned_desc_.data() + staging_.flags, 0, sizeof(uint32_t) * images_.size());
 }
 
@@ -260,7 +263,20 @@ hipjpegStatus_t EncodeBatch::relaunch(void* stream)
 // ---------------------------------------------------------------- coefficient_stage
 hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, int n, const DecodeImage* src, void* stream)
 {
-    if (n < 0 || (n > 0 && (!pics || !src))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (n > 0 && !src) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    return coefficient_fill(pics, n, src, nullptr, stream);
+}
+
+hipjpegStatus_t EncodeBatch::import_stage(const CoefficientPicture* pics, const hipjpegCoefficientPlanes_t* planes, int n, void* stream)
+{
+    if (n > 0 && !planes) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    return coefficient_fill(pics, n, nullptr, planes, stream);
+}
+
+hipjpegStatus_t EncodeBatch::coefficient_fill(const CoefficientPicture* pics, int n, const DecodeImage* src, const hipjpegCoefficientPlanes_t* planes,
+                                              void* stream)
+{
+    if (n < 0 || (n > 0 && !pics)) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (hipSetDevice(device_id_) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
     if (launched_ && event_) (void)hipEventSynchronize((hipEvent_t)event_);  // previous use of the buffers must have drained
     launched_ = fetched_ = false;
@@ -270,6 +286,7 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
     markers_.assign((size_t)n, std::vector<uint8_t>());
     units_.clear();
     relayout_units_.clear();
+    coef_planes_.assign(planes ? (size_t)n * 4 : 0, CoefPlane{nullptr, 0, 0, 0, 0});
     for (auto& v : unit_lists_) v.clear();
     coef_total_ = 0;
     pixel_bytes_ = coef_bytes_ = 0;
@@ -288,7 +305,8 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
         markers_[(size_t)i] = pics[i].markers;
         const EncodeGeometry& g = im.geom;
         // cropped at an origin: the turned kernel, with turn 0 if need be (the origin of the unit's component rides behind the turn)
-        const bool moved = pics[i].turn != 0 || pics[i].origin.any();
+        // (caller memory holds the picture itself: neither turn nor origin)
+        const bool moved = !planes && (pics[i].turn != 0 || pics[i].origin.any());
         EncodeImage& d = desc_[i];
         memset(&d, 0, sizeof d);
         d.width = (uint32_t)g.width;
@@ -305,7 +323,9 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
             coef_total_ += (size_t)g.blocks_w[c] * g.blocks_h[c] * 128;
             const uint32_t nreal = (uint32_t)(g.real_w[c] * g.real_h[c]);
             std::vector<RelayoutUnit>& list = moved ? turned : relayout_units_;
-            const uint32_t pad = pics[i].turn | ((uint32_t)pics[i].origin.ox[c] << kOriginShiftX) | ((uint32_t)pics[i].origin.oy[c] << kOriginShiftY);
+            const uint32_t pad = planes ? 0u : pics[i].turn | ((uint32_t)pics[i].origin.ox[c] << kOriginShiftX) | ((uint32_t)pics[i].origin.oy[c] << kOriginShiftY);
+            if (planes)
+                coef_planes_[(size_t)i * 4 + c] = CoefPlane{static_cast<int16_t*>(planes[i].coef[c]), planes[i].pitch_blocks[c], (uint32_t)g.real_w[c], (uint32_t)g.real_h[c], 0};
             for (uint32_t b = 0; b < nreal; b += kRelayoutBlocksPerUnit) list.push_back(RelayoutUnit{(uint32_t)i, (uint32_t)c, b, pad});
             relayout_blocks_ += nreal;
             if (moved) turned_blocks += nreal;
@@ -330,7 +350,9 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
     const EncodeImage* dimg = at<const EncodeImage>(device_, staging_.desc);
     const RelayoutUnit* dunits = at<const RelayoutUnit>(device_, staging_.relayout);
     const int nturned = (int)(relayout_units_.size() - identity_units_);
-    if (launch_coef_relayout(src, dimg, dunits, (int)identity_units_, at<uint32_t>(device_, staging_.flags), stream) != 0) return HIPJPEG_STATUS_HIP_ERROR;
+    const int rc = planes ? launch_coef_import(at<const CoefPlane>(device_, staging_.planes), dimg, dunits, (int)identity_units_, at<uint32_t>(device_, staging_.flags), stream)
+                          : launch_coef_relayout(src, dimg, dunits, (int)identity_units_, at<uint32_t>(device_, staging_.flags), stream);
+    if (rc != 0) return HIPJPEG_STATUS_HIP_ERROR;
     if (timing && hipEventRecord(t1, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
     if (launch_coef_transform(src, dimg, dunits + identity_units_, nturned, at<uint32_t>(device_, staging_.flags), stream) != 0) return HIPJPEG_STATUS_HIP_ERROR;
     if (timing && hipEventRecord(t2, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
@@ -351,7 +373,8 @@ hipjpegStatus_t EncodeBatch::coefficient_stage(const CoefficientPicture* pics, i
         (void)hipEventElapsedTime(&ms, t0, t1);
         (void)hipEventElapsedTime(&ms_turned, t1, t2);
         if (identity_units_ || !nturned)
-            fprintf(stderr, "[hipjpeg] coef_relayout_kernel: %zu workgroups, %llu blocks, %.4f ms\n", identity_units_, (unsigned long long)(relayout_blocks_ - turned_blocks), ms);
+            fprintf(stderr, "[hipjpeg] %s: %zu workgroups, %llu blocks, %.4f ms\n", planes ? "coef_import_kernel" : "coef_relayout_kernel", identity_units_,
+                    (unsigned long long)(relayout_blocks_ - turned_blocks), ms);
         if (nturned)
             fprintf(stderr, "[hipjpeg] coef_transform_kernel: %d workgroups, %llu blocks, %.4f ms\n", nturned, (unsigned long long)turned_blocks, ms_turned);
         (void)hipEventDestroy(t0);

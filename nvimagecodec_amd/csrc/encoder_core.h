@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/hipjpeg.h"
+#include "coefficient_kernels.h"
 #include "encode_layout.h"
 #include "entropy_encode.h"
 #include "gpu_huffman_encode.h"
@@ -61,6 +62,11 @@ public:
     // (the DecodeImage table of the batch that decoded the same pictures, same indices) on `stream`.  Blocks until the kernel's range flags are back: an image with a coefficient outside jchuff.c's limits becomes
     // UNSUPPORTED before any coder sees it.  route_entropy() / entropy_stage() follow as after device_stage().
     hipjpegStatus_t coefficient_stage(const CoefficientPicture* pics, int n, const DecodeImage* src, void* stream);
+    // Coefficient tensors (hipjpegEncodeCoefficientsBatch), the sibling of coefficient_stage() whose source is the caller's memory:
+    // planes[i] (checked by the caller: pointers, alignment, pitch against pics[i]'s real area; turn and origin of pics[i] are not read)
+    // in the public layout of include/hipjpeg.h; coef_import_kernel (coefficient_kernels.hip) fills the coefficient area, queued on
+    // `stream` behind whatever produced the planes there.  Blocks for the range flags as coefficient_stage() does.
+    hipjpegStatus_t import_stage(const CoefficientPicture* pics, const hipjpegCoefficientPlanes_t* planes, int n, void* stream);
     uint64_t relayout_blocks() const { return relayout_blocks_; }  // blocks the last coefficient_stage() moved
     // Coefficients D2H (on the stream used by device_stage), wait.
     hipjpegStatus_t fetch_coefficients();
@@ -97,8 +103,11 @@ private:
     // || (device only) the coefficients, which pinned_coef_ receives at offset 0.
     // (coefficient_stage(): relayout units and one range-flag word per image ride in the upload, the flags as zeros)
     struct EncodeStaging {
-        size_t desc, units, relayout, flags, coef, total;
+        size_t desc, units, relayout, flags, planes, coef, total;
     } staging_{};
+    // coefficient_stage() and import_stage() are one plan: `planes` says where the blocks come from
+    hipjpegStatus_t coefficient_fill(const CoefficientPicture* pics, int n, const DecodeImage* src, const hipjpegCoefficientPlanes_t* planes, void* stream);
+    std::vector<CoefPlane> coef_planes_;  // import_stage(): four records per image (rides in the upload); empty otherwise
     std::vector<RelayoutUnit> relayout_units_;  // the units of the pictures that stay as they are, then those of the turned / cropped ones
     // per image: marker segments for the header writers of every coding route (coefficient_stage(); empty otherwise).  Not a PlannedEncode
     // field, for the reason given at host_coder_.

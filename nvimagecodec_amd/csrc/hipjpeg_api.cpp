@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/hipjpeg.h"
+#include "coefficients_core.h"
 #include "decoder_core.h"
 #include "diagnostics.h"
 #include "encoder_core.h"
@@ -85,6 +86,10 @@ struct hipjpegHandle {
     // hipjpegTranscodeBatchSetRegions: for the next hipjpegTranscodeBatch only
     std::vector<hipjpegTranscodeRegion_t> transcode_regions;
     bool transcode_regions_set = false;
+    // the last hipjpegDecodeCoefficientsBatch / hipjpegEncodeCoefficientsBatch: images on the GPU entropy decoder / coder, blocks the
+    // later of the two calls moved
+    int32_t coefficients_gpu_decoded = 0, coefficients_gpu_coded = 0;
+    int64_t coefficients_blocks = 0;
 };
 
 extern "C" {
@@ -840,6 +845,91 @@ hipjpegStatus_t hipjpegTranscodeBatchStats(hipjpegHandle_t handle, int32_t* gpu_
     if (gpu_decoded_images) *gpu_decoded_images = handle->transcode_gpu_decoded;
     if (gpu_coded_images) *gpu_coded_images = handle->transcode_gpu_coded;
     if (relayout_blocks) *relayout_blocks = handle->transcode_blocks;
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+// ---------------------------------------------------------------- coefficient tensors
+// (hipjpegGetCoefficientInfo / hipjpegDecodeCoefficientsHost / hipjpegEncodeCoefficientsHost: coefficients_core.cpp, with the rules)
+hipjpegStatus_t hipjpegDecodeCoefficientsBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
+                                               const hipjpegCoefficientPlanes_t* planes, unsigned flags, hipjpegStatus_t* statuses, void* stream)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle || batch_size < 0 || (batch_size > 0 && (!data || !lengths || !planes))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    // the call takes the current decode page for itself: nothing submitted may still be using it
+    if (handle->num_submitted != 0 || handle->encode_in_flight != 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    handle->coefficients_gpu_decoded = 0;
+    handle->coefficients_blocks = 0;
+    DecodeBatch& d = handle->cur();
+    hipjpegStatus_t st = d.plan_coefficients(data, lengths, batch_size, flags, nullptr, handle->pool.get(), nullptr, /*any_frame=*/true);
+    if (st != HIPJPEG_STATUS_SUCCESS) return st;
+    // what the header settles about the caller's planes is settled before anything is decoded
+    for (int i = 0; i < batch_size; i++) {
+        if (d.image(i).status != HIPJPEG_STATUS_SUCCESS) continue;
+        hipjpegCoefficientInfo_t info;
+        coefficient_info(d.image(i).frame, &info);
+        d.reject(i, coefficient_planes_ok(info.num_components, info.blocks_w, planes[i]));
+    }
+    // the entropy stage alone, verdicts settled (launch 3 = entropy kernels + resolve): a failing image writes nothing into its planes
+    handle->pool->parallel_for(batch_size, [&](int i, int) { d.entropy_stage(i); });
+    d.finalize(nullptr);
+    if ((st = d.transfer(stream)) != HIPJPEG_STATUS_SUCCESS || (st = d.launch(stream, 3)) != HIPJPEG_STATUS_SUCCESS ||
+        (st = d.export_coefficients(planes, stream)) != HIPJPEG_STATUS_SUCCESS) {
+        (void)hipStreamSynchronize((hipStream_t)stream);  // nothing of this batch stays queued behind an error
+        return st;
+    }
+    if (statuses)
+        for (int i = 0; i < batch_size; i++) statuses[i] = d.image(i).status;
+    handle->coefficients_gpu_decoded = d.gpu_entropy_images();
+    handle->coefficients_blocks = (int64_t)d.exported_blocks();
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+hipjpegStatus_t hipjpegEncodeCoefficientsBatch(hipjpegHandle_t handle, const hipjpegCoefficientInfo_t* infos, const hipjpegCoefficientPlanes_t* planes,
+                                               const hipjpegTranscodeParams_t* params, int batch_size, unsigned flags, hipjpegStatus_t* statuses,
+                                               void* stream)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle || batch_size < 0 || (batch_size > 0 && (!infos || !planes || !params))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    // the call takes the encode batch for itself
+    if (handle->num_submitted != 0 || handle->encode_in_flight != 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    handle->coefficients_gpu_coded = 0;
+    handle->coefficients_blocks = 0;
+    std::vector<CoefficientPicture> pics((size_t)batch_size);
+    for (int i = 0; i < batch_size; i++) {
+        CoefficientPicture& p = pics[(size_t)i];
+        p.status = coefficient_picture(infos[i], planes[i], params[i], &p.picture);
+        p.params.restart_interval = params[i].restart_interval;
+        p.params.optimized_huffman = params[i].optimized_huffman;
+        p.params.progressive = params[i].progressive;
+    }
+    EncodeBatch& e = *handle->encode;
+    handle->encode_view = &e;
+    hipjpegStatus_t st = e.import_stage(pics.data(), planes, batch_size, stream);
+    if (st != HIPJPEG_STATUS_SUCCESS) {
+        (void)hipStreamSynchronize((hipStream_t)stream);
+        return st;
+    }
+    if ((st = e.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0, (flags & HIPJPEG_FLAG_GPU_RESTART_INTERVALS) != 0)) != HIPJPEG_STATUS_SUCCESS) return st;
+    if (e.host_images()) handle->pool->parallel_for(e.size(), [&](int i, int) { e.entropy_stage(i); });
+    if (statuses)
+        for (int i = 0; i < batch_size; i++) statuses[i] = e.image(i).status;
+    handle->coefficients_gpu_coded = (int32_t)e.gpu_entropy_images();
+    handle->coefficients_blocks = (int64_t)e.relayout_blocks();
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+hipjpegStatus_t hipjpegCoefficientsBatchStats(hipjpegHandle_t handle, int32_t* gpu_decoded_images, int32_t* gpu_coded_images, int64_t* moved_blocks)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (gpu_decoded_images) *gpu_decoded_images = handle->coefficients_gpu_decoded;
+    if (gpu_coded_images) *gpu_coded_images = handle->coefficients_gpu_coded;
+    if (moved_blocks) *moved_blocks = handle->coefficients_blocks;
     return HIPJPEG_STATUS_SUCCESS;
     });
 }

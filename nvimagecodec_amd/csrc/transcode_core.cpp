@@ -152,6 +152,87 @@ EntropyEncodeOptions transcode_options(const hipjpegTranscodeParams_t& p)
     return EntropyEncodeOptions{p.restart_interval, p.optimized_huffman != 0, p.progressive != 0};
 }
 
+void natural_area(const FrameInfo& f, NaturalPlanes* p)
+{
+    *p = NaturalPlanes();
+    for (int c = 0; c < f.ncomp; c++) {
+        p->blocks_w[c] = (f.comp[c].samp_w + 7) / 8;
+        p->blocks_h[c] = (f.comp[c].samp_h + 7) / 8;
+    }
+}
+
+hipjpegStatus_t decode_natural(const uint8_t* data, size_t size, const FrameInfo& f, const NaturalPlanes& dst)
+{
+    // the decoder's blocks: column-major over the frame's MCU-padded grid
+    std::vector<int16_t> src(f.total_blocks() * 64, 0);
+    int16_t* sptr[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t off = 0;
+    for (int c = 0; c < f.ncomp; c++) {
+        sptr[c] = src.data() + off;
+        off += (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 64;
+    }
+    switch (decode_coefficients(data, size, f, sptr)) {
+    case kEntropyOk: break;
+    case kEntropyTruncated: return HIPJPEG_STATUS_TRUNCATED;
+    case kEntropyMissingTable: return HIPJPEG_STATUS_BAD_JPEG;
+    default: return HIPJPEG_STATUS_CORRUPT;
+    }
+    // nothing is written before the picture is known to be whole
+    for (int c = 0; c < f.ncomp; c++)
+        for (int by = 0; by < dst.blocks_h[c]; by++)
+            for (int bx = 0; bx < dst.blocks_w[c]; bx++) {
+                const int16_t* s = sptr[c] + ((size_t)by * f.comp[c].blocks_w + bx) * 64;
+                int16_t* d = dst.coef[c] + ((size_t)by * dst.pitch[c] + bx) * 64;
+                for (int j = 0; j < 64; j++) d[j] = s[(j & 7) * 8 + (j >> 3)];
+            }
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+hipjpegStatus_t encode_natural(const TranscodePicture& pic, const NaturalPlanes& src, const TranscodeOrigin& origin, unsigned turn,
+                               const EntropyEncodeOptions& opt, std::vector<uint8_t>* out)
+{
+    // the coder's blocks: zigzag order over its own grid; only the real area is read
+    const EncodeGeometry& g = pic.geom;
+    std::vector<int16_t> dst;
+    size_t doff[3] = {0, 0, 0}, total = 0;
+    for (int c = 0; c < g.ncomp; c++) {
+        doff[c] = total;
+        total += (size_t)g.blocks_w[c] * g.blocks_h[c] * 64;
+    }
+    dst.assign(total, 0);
+    // zigzag index -> position in the source's block (row * 8 + column) -- read the other way round, the block comes out transposed --
+    // and whether a mirror of the output negates it (odd u: mirror x, odd v: mirror y; both: twice)
+    const bool transpose = (turn & kTurnTranspose) != 0;
+    int from[64];
+    bool negate[64];
+    for (int k = 0; k < 64; k++) {
+        const int u = kZigzagNatural[k] & 7, v = kZigzagNatural[k] >> 3;
+        from[k] = transpose ? u * 8 + v : v * 8 + u;
+        negate[k] = (((turn & kTurnMirrorX) != 0) & (u & 1)) ^ (((turn & kTurnMirrorY) != 0) & (v & 1));
+    }
+    for (int c = 0; c < g.ncomp; c++)
+        for (int by = 0; by < g.real_h[c]; by++)
+            for (int bx = 0; bx < g.real_w[c]; bx++) {
+                // the source block: undo the output's mirrors over its real area, then the transpose, then the crop
+                const int ty = (turn & kTurnMirrorY) ? g.real_h[c] - 1 - by : by, tx = (turn & kTurnMirrorX) ? g.real_w[c] - 1 - bx : bx;
+                const int sy = origin.oy[c] + (transpose ? tx : ty), sx = origin.ox[c] + (transpose ? ty : tx);
+                if (sy >= src.blocks_h[c] || sx >= src.blocks_w[c]) return HIPJPEG_STATUS_INTERNAL_ERROR;  // (the planning keeps every block inside)
+                const int16_t* s = src.coef[c] + ((size_t)sy * src.pitch[c] + sx) * 64;
+                int16_t* d = dst.data() + doff[c] + ((size_t)by * g.blocks_w[c] + bx) * 64;
+                if (s[0] < kTranscodeDcMin || s[0] > kTranscodeDcMax) return HIPJPEG_STATUS_UNSUPPORTED;
+                d[0] = s[0];
+                for (int k = 1; k < 64; k++) {
+                    const int v = s[from[k]];
+                    if (v < -kTranscodeAcMax || v > kTranscodeAcMax) return HIPJPEG_STATUS_UNSUPPORTED;
+                    d[k] = (int16_t)(negate[k] ? -v : v);
+                }
+            }
+    const int16_t* coef[3] = {nullptr, nullptr, nullptr};
+    for (int c = 0; c < g.ncomp; c++) coef[c] = dst.data() + doff[c];
+    encode_jfif(g, pic.qlum, pic.qchr, coef, opt, out);
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
 hipjpegStatus_t transcode_host(const uint8_t* data, size_t size, const hipjpegTranscodeParams_t& params, const hipjpegTranscodeRegion_t* region,
                                std::vector<uint8_t>* out)
 {
@@ -169,63 +250,26 @@ hipjpegStatus_t transcode_host(const uint8_t* data, size_t size, const hipjpegTr
     if ((st = transcode_crop(source, region, (params.orientation & HIPJPEG_TRANSCODE_CROP_EXPAND) != 0, &cropped, &origin)) != HIPJPEG_STATUS_SUCCESS)
         return st;
     if ((st = transcode_turn(cropped, orientation, (params.orientation & HIPJPEG_TRANSCODE_TRIM) != 0, &pic, &turn)) != HIPJPEG_STATUS_SUCCESS) return st;
-    // the decoder's blocks: column-major over the frame's MCU-padded grid
-    std::vector<int16_t> src(f.total_blocks() * 64, 0);
-    int16_t* sptr[4] = {nullptr, nullptr, nullptr, nullptr};
+    // the source's blocks in the public layout (natural order over the real area), then from there into the coder's: the two halves
+    // hipjpegDecodeCoefficientsHost and hipjpegEncodeCoefficientsHost are made of
+    NaturalPlanes planes;
+    std::vector<int16_t> store;
+    natural_area(f, &planes);
     size_t off = 0;
+    for (int c = 0; c < f.ncomp; c++) off += (size_t)planes.blocks_w[c] * planes.blocks_h[c] * 64;
+    store.assign(off, 0);
+    off = 0;
     for (int c = 0; c < f.ncomp; c++) {
-        sptr[c] = src.data() + off;
-        off += (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 64;
+        planes.coef[c] = store.data() + off;
+        planes.pitch[c] = (uint32_t)planes.blocks_w[c];
+        off += (size_t)planes.blocks_w[c] * planes.blocks_h[c] * 64;
     }
-    switch (decode_coefficients(data, size, f, sptr)) {
-    case kEntropyOk: break;
-    case kEntropyTruncated: return HIPJPEG_STATUS_TRUNCATED;
-    case kEntropyMissingTable: return HIPJPEG_STATUS_BAD_JPEG;
-    default: return HIPJPEG_STATUS_CORRUPT;
-    }
-    // the coder's blocks: zigzag order over its own grid; only the real area is read
-    const EncodeGeometry& g = pic.geom;
-    std::vector<int16_t> dst;
-    size_t doff[3] = {0, 0, 0}, total = 0;
-    for (int c = 0; c < g.ncomp; c++) {
-        doff[c] = total;
-        total += (size_t)g.blocks_w[c] * g.blocks_h[c] * 64;
-    }
-    dst.assign(total, 0);
-    // zigzag index -> position in the decoder's block (column * 8 + row) -- read the other way round, the block comes out transposed --
-    // and whether a mirror of the output negates it (odd u: mirror x, odd v: mirror y; both: twice)
-    const bool transpose = (turn & kTurnTranspose) != 0;
-    int from[64];
-    bool negate[64];
-    for (int k = 0; k < 64; k++) {
-        const int u = kZigzagNatural[k] & 7, v = kZigzagNatural[k] >> 3;
-        from[k] = transpose ? v * 8 + u : u * 8 + v;
-        negate[k] = (((turn & kTurnMirrorX) != 0) & (u & 1)) ^ (((turn & kTurnMirrorY) != 0) & (v & 1));
-    }
-    for (int c = 0; c < g.ncomp; c++)
-        for (int by = 0; by < g.real_h[c]; by++)
-            for (int bx = 0; bx < g.real_w[c]; bx++) {
-                // the source block: undo the output's mirrors over its real area, then the transpose, then the crop
-                const int ty = (turn & kTurnMirrorY) ? g.real_h[c] - 1 - by : by, tx = (turn & kTurnMirrorX) ? g.real_w[c] - 1 - bx : bx;
-                const int sy = origin.oy[c] + (transpose ? tx : ty), sx = origin.ox[c] + (transpose ? ty : tx);
-                const int16_t* s = sptr[c] + ((size_t)sy * f.comp[c].blocks_w + sx) * 64;
-                int16_t* d = dst.data() + doff[c] + ((size_t)by * g.blocks_w[c] + bx) * 64;
-                if (s[0] < kTranscodeDcMin || s[0] > kTranscodeDcMax) return HIPJPEG_STATUS_UNSUPPORTED;
-                d[0] = s[0];
-                for (int k = 1; k < 64; k++) {
-                    const int v = s[from[k]];
-                    if (v < -kTranscodeAcMax || v > kTranscodeAcMax) return HIPJPEG_STATUS_UNSUPPORTED;
-                    d[k] = (int16_t)(negate[k] ? -v : v);
-                }
-            }
-    const int16_t* coef[3] = {nullptr, nullptr, nullptr};
-    for (int c = 0; c < g.ncomp; c++) coef[c] = dst.data() + doff[c];
+    if ((st = decode_natural(data, size, f, planes)) != HIPJPEG_STATUS_SUCCESS) return st;
     std::vector<uint8_t> markers;
     transcode_markers(params, orientation, data, size, &markers);
     EntropyEncodeOptions opt = transcode_options(params);
     if (!markers.empty()) opt.markers = &markers;
-    encode_jfif(g, pic.qlum, pic.qchr, coef, opt, out);
-    return HIPJPEG_STATUS_SUCCESS;
+    return encode_natural(pic, planes, origin, turn, opt, out);
 }
 
 }  // namespace hipjpeg

@@ -63,6 +63,24 @@ int transcode_orientation(const hipjpegTranscodeParams_t& p, const uint8_t* data
 // UNSUPPORTED.  Orientation 1 returns `src` and 0.
 hipjpegStatus_t transcode_turn(const TranscodePicture& src, int orientation, bool trim, TranscodePicture* dst, unsigned* turn);
 EntropyEncodeOptions transcode_options(const hipjpegTranscodeParams_t& p);
+
+// Coefficients in the public layout of include/hipjpeg.h (hipjpegCoefficientPlanes_t): int16[64] blocks in natural order (row * 8 +
+// column), raster order over the component's real block area blocks_w x blocks_h = ceil(samp / 8), block (by, bx) at
+// coef + (by * pitch + bx) * 64.  The host route below goes through it, so that a transcode IS a read followed by a write.
+struct NaturalPlanes {
+    int16_t* coef[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t pitch[4] = {0, 0, 0, 0};
+    int blocks_w[4] = {0, 0, 0, 0}, blocks_h[4] = {0, 0, 0, 0};
+};
+// The real block area of every component of `f` (pointers and pitches are left for the caller).
+void natural_area(const FrameInfo& f, NaturalPlanes* p);
+// Read: the host entropy decoder's output (column-major blocks over the MCU-padded grid) re-laid into `dst`.  The decoder's status for a
+// damaged stream, and then nothing is written.
+hipjpegStatus_t decode_natural(const uint8_t* data, size_t size, const FrameInfo& f, const NaturalPlanes& dst);
+// Write: the picture `pic` whose blocks come from `src` by `origin` and `turn` (all zero: its own places), natural order to zigzag over the
+// coder's grid with the range check (UNSUPPORTED), then the unchanged host coder.  Appends the file to `out`.
+hipjpegStatus_t encode_natural(const TranscodePicture& pic, const NaturalPlanes& src, const TranscodeOrigin& origin, unsigned turn,
+                               const EntropyEncodeOptions& opt, std::vector<uint8_t>* out);
 // Host route.  Appends the file to `out`; nothing is appended unless the status is SUCCESS.
 hipjpegStatus_t transcode_host(const uint8_t* data, size_t size, const hipjpegTranscodeParams_t& params, const hipjpegTranscodeRegion_t* region,
                                std::vector<uint8_t>* out);

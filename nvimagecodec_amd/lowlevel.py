@@ -670,3 +670,230 @@ class BatchTranscoder:
         d, c, b = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         N.load().hipjpegTranscodeBatchStats(self._h, ctypes.byref(d), ctypes.byref(c), ctypes.byref(b))
         return dict(gpu_decoded_images=d.value, gpu_coded_images=c.value, relayout_blocks=b.value)
+
+
+# ---------------------------------------------------------------- coefficient tensors
+def _info_dict(ci):
+    nc = ci.num_components
+    d = dict(width=ci.width, height=ci.height, num_components=nc, color_model=ci.color_model)
+    for k in ("h", "v", "blocks_w", "blocks_h"):
+        d[k] = list(getattr(ci, k))[:nc]
+    d["qtables"] = [np.array(ci.qtable[c], dtype=np.uint16) for c in range(nc)]
+    return d
+
+
+def _info_struct(info):
+    """hipjpegCoefficientInfo_t of an info dict (coefficient_info's); h / v default to 1, the colour model to gray / YCbCr"""
+    ci = N.CoefficientInfo()
+    nc = int(info["num_components"])
+    if not 0 <= nc <= 4:
+        raise ValueError("num_components must be 1..4")
+    ci.width, ci.height, ci.num_components = int(info["width"]), int(info["height"]), nc
+    ci.color_model = int(info.get("color_model", 0 if nc == 1 else 1))
+    for c in range(nc):
+        ci.h[c] = int(info["h"][c]) if "h" in info else 1
+        ci.v[c] = int(info["v"][c]) if "v" in info else 1
+        ci.blocks_w[c], ci.blocks_h[c] = int(info["blocks_w"][c]), int(info["blocks_h"][c])
+        q = np.asarray(info["qtables"][c]).reshape(64)
+        if q.min() < 0 or q.max() > 65535:
+            raise ValueError("quantizers must fit uint16")
+        q = np.ascontiguousarray(q, dtype=np.uint16)
+        ctypes.memmove(ci.qtable[c], q.ctypes.data, 128)
+    return ci
+
+
+def _coding_params(optimized_huffman, progressive, restart_interval):
+    return N.TranscodeParams(int(bool(optimized_huffman)), int(bool(progressive)), int(restart_interval), 0)
+
+
+def coefficient_info(data):
+    """Geometry and quantization tables of a JPEG file, from its header: dict(width, height, num_components, color_model, h, v,
+    blocks_w, blocks_h -- the REAL block area ceil(samp / 8) per component --, qtables: uint16[64] per component, natural order)."""
+    a = _as_u8(data)
+    ci = N.CoefficientInfo()
+    st = N.load().hipjpegGetCoefficientInfo(a.ctypes.data, a.size, ctypes.byref(ci))
+    if st:
+        raise N.HipJpegError(st, "hipjpegGetCoefficientInfo")
+    return _info_dict(ci)
+
+
+def _host_planes(coefs, what):
+    """hipjpegCoefficientPlanes_t over numpy arrays [blocks_h, pitch >= blocks_w, 8, 8] (or [.., 64]) int16, C-contiguous"""
+    P = N.CoefficientPlanes()
+    for c, a in enumerate(coefs):
+        if not isinstance(a, np.ndarray) or a.dtype != np.int16 or not a.flags["C_CONTIGUOUS"] or a.ndim not in (3, 4) or a[0, 0].size != 64:
+            raise TypeError(f"{what}: component {c} must be a C-contiguous int16 array [blocks_h, pitch, 8, 8]")
+        P.coef[c] = a.ctypes.data
+        P.pitch_blocks[c] = a.shape[1]
+    return P
+
+
+def decode_coefficients_host(data, out=None):
+    """Host only (no GPU): (info, coefs) with coefs[c] an int16 array [blocks_h, blocks_w, 8, 8], natural order, the quantized values as
+    the stream codes them.  out: arrays to fill instead (a larger second dimension is the pitch; the padding is not written)."""
+    a = _as_u8(data)
+    info = coefficient_info(a)
+    if out is None:
+        # (numpy's allocations are 16-byte aligned for anything but tiny arrays; one block is 128 bytes)
+        out = [np.zeros((bh, bw, 8, 8), dtype=np.int16) for bh, bw in zip(info["blocks_h"], info["blocks_w"])]
+    if len(out) != info["num_components"] or any(o.shape[0] < bh for o, bh in zip(out, info["blocks_h"])):
+        raise TypeError("decode_coefficients_host: one array of at least blocks_h rows per component")
+    P = _host_planes(out, "decode_coefficients_host")
+    st = N.load().hipjpegDecodeCoefficientsHost(a.ctypes.data, a.size, ctypes.byref(P))
+    if st:
+        raise N.HipJpegError(st, "hipjpegDecodeCoefficientsHost")
+    return info, out
+
+
+def encode_coefficients_host(info, coefs, optimized_huffman=False, progressive=False, restart_interval=0):
+    """Host only (no GPU): the JFIF file of a picture given by `info` (coefficient_info's dict; its tables may be replaced) and its
+    coefficients (as decode_coefficients_host returns them; a larger second dimension is the pitch).  Raises HipJpegError: UNSUPPORTED
+    for what the writer does not write (include/hipjpeg.h lists the rules), INVALID_ARGUMENT for a description that contradicts itself."""
+    ci = _info_struct(info)
+    if len(coefs) < ci.num_components:
+        raise TypeError("encode_coefficients_host: one array per component")
+    P = _host_planes(coefs[: ci.num_components], "encode_coefficients_host")
+    p = _coding_params(optimized_huffman, progressive, restart_interval)
+    n = ctypes.c_size_t()
+    cap = sum(int(a.nbytes) for a in coefs) * 2 + 65536
+    for _ in range(2):
+        out = np.empty(cap, dtype=np.uint8)
+        st = N.load().hipjpegEncodeCoefficientsHost(ctypes.byref(ci), ctypes.byref(P), ctypes.byref(p), out.ctypes.data, cap, ctypes.byref(n))
+        if st != 9:  # BUFFER_TOO_SMALL: n holds the needed size
+            break
+        cap = n.value
+    if st:
+        raise N.HipJpegError(st, "hipjpegEncodeCoefficientsHost")
+    return out[: n.value].tobytes()
+
+
+class CoefficientImage:
+    """A picture as its quantized DCT coefficients on the device: info (coefficient_info's dict) and coefs, one torch CUDA int16 tensor
+    [blocks_h, blocks_w, 8, 8] per component (natural order inside a block)."""
+
+    def __init__(self, info, coefs):
+        self.info = info
+        self.coefs = coefs
+
+
+class BatchCoefficients:
+    """hipjpegDecodeCoefficientsBatch / hipjpegEncodeCoefficientsBatch on one device: JPEG files to coefficient tensors and back, the
+    tensors never leaving the device.  gpu_huffman: the entropy stage on the GPU for every image it takes; gpu_restart: with gpu_huffman,
+    the GPU coder also takes baseline output with a restart interval.  Neither the tensors nor the bytes depend on either."""
+
+    def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False):
+        import torch
+        self._torch = torch
+        self.device = int(device)
+        self.gpu_huffman = bool(gpu_huffman)
+        self.gpu_restart = bool(gpu_restart)
+        self._h = ctypes.c_void_p()
+        st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
+        if st:
+            raise N.HipJpegError(st, "hipjpegCreate")
+
+    def close(self):
+        if self._h:
+            N.load().hipjpegDestroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_hybrid_huffman_threshold(self, pixels):
+        st = N.load().hipjpegSetHybridHuffmanThreshold(self._h, int(pixels))
+        if st:
+            raise N.HipJpegError(st, "hipjpegSetHybridHuffmanThreshold")
+
+    def _flags(self):
+        return (N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0)) if self.gpu_huffman else 0
+
+    def _stream_ptr(self, stream):
+        s = stream if stream is not None else self._torch.cuda.current_stream(self.device)
+        return ctypes.c_void_p(s.cuda_stream)
+
+    def _planes(self, coefs, blocks_h, blocks_w, what):
+        """hipjpegCoefficientPlanes_t over torch tensors [>= blocks_h, pitch >= blocks_w, 8, 8]: on this device, int16, the last three
+        dimensions contiguous (the first may have any stride that is a whole number of rows)"""
+        torch = self._torch
+        P = N.CoefficientPlanes()
+        if len(coefs) != len(blocks_h):
+            raise TypeError(f"{what}: one tensor per component")
+        for c, t in enumerate(coefs):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.device.index != self.device:
+                raise TypeError(f"{what}: component {c} must be a tensor on cuda:{self.device}")
+            if t.dtype != torch.int16 or t.dim() != 4 or tuple(t.shape[2:]) != (8, 8):
+                raise TypeError(f"{what}: component {c} must be int16 [blocks_h, blocks_w, 8, 8]")
+            if t.stride(3) != 1 or t.stride(2) != 8 or t.stride(1) != 64 or t.stride(0) % 64 != 0 or t.stride(0) < 64 * blocks_w[c]:
+                raise TypeError(f"{what}: component {c}: the last three dimensions must be contiguous and a row must hold blocks_w blocks")
+            if t.shape[0] < blocks_h[c] or t.shape[1] < blocks_w[c]:
+                raise TypeError(f"{what}: component {c} is smaller than the picture's {blocks_h[c]} x {blocks_w[c]} blocks")
+            P.coef[c] = t.data_ptr()
+            P.pitch_blocks[c] = t.stride(0) // 64
+        return P
+
+    def allocate(self, info):
+        dev = self._torch.device("cuda", self.device)
+        return [self._torch.empty((bh, bw, 8, 8), dtype=self._torch.int16, device=dev) for bh, bw in zip(info["blocks_h"], info["blocks_w"])]
+
+    def decode(self, jpegs, stream=None, outs=None):
+        """Returns (statuses, images): images[i] is a CoefficientImage, or None where statuses[i] != 0.  The export kernel is queued on
+        `stream` (default: the current one); work queued on that stream afterwards sees the tensors.  outs: per image None or a list of
+        caller tensors to fill (a larger second dimension, or a larger row stride, is the pitch; the padding is not written)."""
+        n = len(jpegs)
+        arrs = [j if (hasattr(j, "data_ptr") and hasattr(j, "numel")) else _as_u8(j) for j in jpegs]
+        ptrs = (ctypes.c_void_p * n)(*[(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data) for a in arrs])
+        lens = (ctypes.c_size_t * n)(*[(a.numel() if hasattr(a, "numel") else a.size) for a in arrs])
+        P = (N.CoefficientPlanes * max(n, 1))()
+        infos, tensors = [], []
+        for i, a in enumerate(arrs):
+            try:
+                info = coefficient_info(a)
+            except N.HipJpegError:
+                infos.append(None)  # the batch call reports why; its planes stay null and are never looked at
+                tensors.append(None)
+                continue
+            t = outs[i] if outs is not None and outs[i] is not None else self.allocate(info)
+            P[i] = self._planes(t, info["blocks_h"], info["blocks_w"], f"decode: image {i}")
+            infos.append(info)
+            tensors.append(t)
+        statuses = (ctypes.c_int * n)()
+        st = N.load().hipjpegDecodeCoefficientsBatch(self._h, ptrs, lens, n, P, self._flags(), statuses, self._stream_ptr(stream))
+        if st:
+            raise N.HipJpegError(st, "hipjpegDecodeCoefficientsBatch")
+        images = [CoefficientImage(infos[i], tensors[i]) if statuses[i] == 0 else None for i in range(n)]
+        return list(statuses), images
+
+    def encode(self, images, optimized_huffman=False, progressive=False, restart_interval=0, stream=None):
+        """images: CoefficientImage (or (info, coefs)) per picture.  Returns (statuses, files): files[i] is bytes, or None where
+        statuses[i] != 0.  optimized_huffman / progressive / restart_interval: one value for the batch or a list with one per image.  The
+        import kernel is queued on `stream` (default: the current one), behind whatever produced the tensors there."""
+        n = len(images)
+        per = [v if isinstance(v, (list, tuple)) else [v] * n for v in (optimized_huffman, progressive, restart_interval)]
+        I = (N.CoefficientInfo * max(n, 1))()
+        P = (N.CoefficientPlanes * max(n, 1))()
+        T = (N.TranscodeParams * max(n, 1))()
+        for i, im in enumerate(images):
+            info, coefs = (im.info, im.coefs) if isinstance(im, CoefficientImage) else im
+            I[i] = _info_struct(info)
+            nc = I[i].num_components
+            P[i] = self._planes(list(coefs)[:nc], list(I[i].blocks_h)[:nc], list(I[i].blocks_w)[:nc], f"encode: image {i}")
+            T[i] = _coding_params(per[0][i], per[1][i], per[2][i])
+        statuses = (ctypes.c_int * n)()
+        st = N.load().hipjpegEncodeCoefficientsBatch(self._h, I, P, T, n, self._flags(), statuses, self._stream_ptr(stream))
+        if st:
+            raise N.HipJpegError(st, "hipjpegEncodeCoefficientsBatch")
+        files = []
+        for i in range(n):
+            p, ln = ctypes.c_void_p(), ctypes.c_size_t()
+            ok = statuses[i] == 0 and N.load().hipjpegEncodeGetBitstream(self._h, i, ctypes.byref(p), ctypes.byref(ln)) == 0
+            files.append(ctypes.string_at(p, ln.value) if ok else None)
+        return list(statuses), files
+
+    def stats(self):
+        d, c, b = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        N.load().hipjpegCoefficientsBatchStats(self._h, ctypes.byref(d), ctypes.byref(c), ctypes.byref(b))
+        return dict(gpu_decoded_images=d.value, gpu_coded_images=c.value, moved_blocks=b.value)
