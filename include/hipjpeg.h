@@ -176,8 +176,8 @@ HIPJPEG_API hipjpegStatus_t hipjpegDecodeBatch(hipjpegHandle_t handle, const uin
                                                const hipjpegOutput_t* outputs, hipjpegOutputFormat_t format, unsigned flags,
                                                hipjpegStatus_t* statuses, void* stream);
 
-/* Geometry for the NEXT batch handed to hipjpegDecodeBatch / Host / Submit: `transforms` = batch_size entries (copied), or
- * NULL to go back to plain decoding.  Consumed by that one batch. */
+/* Geometry for the NEXT batch handed to hipjpegDecodeBatch / Host / Submit or to hipjpegCoefficientsToPixelsBatch: `transforms` =
+ * batch_size entries (copied), or NULL to go back to plain decoding.  Consumed by that one batch. */
 HIPJPEG_API hipjpegStatus_t hipjpegDecodeBatchSetTransforms(hipjpegHandle_t handle, const hipjpegTransform_t* transforms, int batch_size);
 
 /* The three phases separately (what hipjpegDecodeBatch does internally); used by bench.py to time the device
@@ -470,8 +470,48 @@ HIPJPEG_API hipjpegStatus_t hipjpegDecodeCoefficientsBatch(hipjpegHandle_t handl
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeCoefficientsBatch(hipjpegHandle_t handle, const hipjpegCoefficientInfo_t* infos,
                                                            const hipjpegCoefficientPlanes_t* planes, const hipjpegTranscodeParams_t* params,
                                                            int batch_size, unsigned flags, hipjpegStatus_t* statuses, void* stream);
+/* Coefficient tensors to pixels: coef_to_decoder_kernel (csrc/coefficient_kernels.hip: planes[i] -> the decoder's layout) and then the
+ * pixel kernels of hipjpegDecodeBatch (dequantize, IDCT, upsampling, colour, geometry), all queued on `stream` -- planes produced on that
+ * stream need no extra synchronisation, no coefficient crosses PCIe, there is no entropy stage.  `infos` / `planes` as in
+ * hipjpegEncodeCoefficientsBatch, `outputs` / `format` as in hipjpegDecodeBatch; of `flags`, HIPJPEG_FLAG_FANCY_UPSAMPLING and
+ * HIPJPEG_FLAG_FAST_IDCT mean what they mean there and HIPJPEG_FLAG_GPU_HUFFMAN is ignored.  Transforms set with
+ * hipjpegDecodeBatchSetTransforms apply to this batch and are consumed by it.
+ * For an image whose planes and tables are what hipjpegDecodeCoefficientsHost / hipjpegGetCoefficientInfo give for a file, the output is
+ * bit for bit what hipjpegDecodeBatch writes for that file with the same format and flags.  No range rule applies: any int16 is a
+ * coefficient and gets the decoder's arithmetic (the SIMD routines' 16-bit wrapping); the quantizers are taken as given, as the parser
+ * takes them from a DQT.  Taken: one component, or three with color_model 0 / 1 / 2 as the decoder treats a file of that colour model;
+ * every sampling layout and every output format the decoder takes for such a file (HIPJPEG_OUTPUT_YUV_PLANAR under its own rules).
+ * HIPJPEG_STATUS_UNSUPPORTED for FOUR components: the CMYK -> RGB formula turns on whether the file carried an Adobe APP14 segment, and
+ * hipjpegCoefficientInfo_t does not say.  HIPJPEG_STATUS_INVALID_ARGUMENT for that image: a size outside 1..65535, sampling factors
+ * outside 1..4, blocks_w / blocks_h that are not what the geometry gives, a pitch below blocks_w, a null pointer, a pointer that is not
+ * 16-byte aligned, an output the pitch and pointer rules of hipjpegDecodeBatch refuse.  A failing image writes nothing to its output and
+ * leaves the rest of the batch alone.
+ * The call returns when the last kernel is queued; `statuses` are final at return (only argument and header rules can fail).  It takes
+ * the handle's current decode page: the rule about Submits in flight of hipjpegDecodeCoefficientsBatch. */
+HIPJPEG_API hipjpegStatus_t hipjpegCoefficientsToPixelsBatch(hipjpegHandle_t handle, const hipjpegCoefficientInfo_t* infos,
+                                                             const hipjpegCoefficientPlanes_t* planes, int batch_size, const hipjpegOutput_t* outputs,
+                                                             hipjpegOutputFormat_t format, unsigned flags, hipjpegStatus_t* statuses, void* stream);
+/* Host only, usable without a GPU: the `info` of the file hipjpegEncodeBatch writes for a width x height picture and `params` --
+ * components and sampling factors of params->subsampling, colour model gray or YCbCr, real block areas, the quality-scaled Annex-K
+ * tables in natural order -- so that a caller can allocate for hipjpegPixelsToCoefficientsBatch.  Only `quality` and `subsampling` are
+ * read.  HIPJPEG_STATUS_UNSUPPORTED for an unknown subsampling, HIPJPEG_STATUS_INVALID_ARGUMENT for a size outside 1..65535. */
+HIPJPEG_API hipjpegStatus_t hipjpegGetEncodeCoefficientInfo(int32_t width, int32_t height, const hipjpegEncodeParams_t* params,
+                                                            hipjpegCoefficientInfo_t* info);
+/* Pixels to coefficient tensors: the forward kernels of hipjpegEncodeBatchDevice (colour conversion, downsampling, FDCT, quantization) and
+ * then coef_from_coder_kernel (csrc/coefficient_kernels.hip: the coder's layout -> planes[i]), all queued on `stream`; nothing is entropy
+ * coded and nothing blocks.  `inputs` / `params` as in hipjpegEncodeBatchDevice (every input format, every subsampling), `planes` as in
+ * hipjpegDecodeCoefficientsBatch.  For every image the planes get what hipjpegDecodeCoefficientsHost reads from the file hipjpegEncodeBatch
+ * writes for the same pixels and parameters, over the real block area of hipjpegGetEncodeCoefficientInfo; nothing between blocks_w and
+ * the pitch is written.  restart_interval, optimized_huffman and progressive do not change coefficients and are ignored beyond the
+ * argument rules.  Statuses: those of hipjpegEncodeBatchDevice, then the rules for planes (a pitch below blocks_w, a null pointer, a
+ * pointer that is not 16-byte aligned: HIPJPEG_STATUS_INVALID_ARGUMENT); final at return.  A failing image writes nothing into its
+ * planes.  The call takes the handle's encode batch: the same rule about Submits in flight. */
+HIPJPEG_API hipjpegStatus_t hipjpegPixelsToCoefficientsBatch(hipjpegHandle_t handle, const hipjpegEncodeInput_t* inputs,
+                                                             const hipjpegEncodeParams_t* params, int batch_size,
+                                                             const hipjpegCoefficientPlanes_t* planes, hipjpegStatus_t* statuses, void* stream);
 /* Of the handle's last hipjpegDecodeCoefficientsBatch: images the GPU entropy decoder took; of its last hipjpegEncodeCoefficientsBatch:
- * images the GPU entropy coder took; and the blocks the last of the two calls moved (the real blocks of every image that reached its kernel). */
+ * images the GPU entropy coder took; and the blocks the last of the four calls (those two, hipjpegCoefficientsToPixelsBatch,
+ * hipjpegPixelsToCoefficientsBatch) moved (the real blocks of every image that reached its kernel). */
 HIPJPEG_API hipjpegStatus_t hipjpegCoefficientsBatchStats(hipjpegHandle_t handle, int32_t* gpu_decoded_images, int32_t* gpu_coded_images,
                                                           int64_t* moved_blocks);
 

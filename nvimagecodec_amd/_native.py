@@ -167,6 +167,9 @@ def load():
                                                 ctypes.POINTER(sz)]
     L.hipjpegDecodeCoefficientsBatch.argtypes = [vp, vp, vp, i32, vp, ctypes.c_uint, vp, vp]
     L.hipjpegEncodeCoefficientsBatch.argtypes = [vp, vp, vp, vp, i32, ctypes.c_uint, vp, vp]
+    L.hipjpegCoefficientsToPixelsBatch.argtypes = [vp, vp, vp, i32, vp, i32, ctypes.c_uint, vp, vp]
+    L.hipjpegGetEncodeCoefficientInfo.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), ctypes.POINTER(CoefficientInfo)]
+    L.hipjpegPixelsToCoefficientsBatch.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.hipjpegCoefficientsBatchStats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)]
     _lib = L
     return L

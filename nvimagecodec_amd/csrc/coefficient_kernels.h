@@ -27,5 +27,14 @@ int launch_coef_export(const DecodeImage* src, const CoefPlane* planes, const Re
 // Components 0..2.  out_of_range[image] gets bit 0 set when a DC value leaves [-1024, 1023] or an AC value [-1023, 1023]; the caller
 // clears the words first.
 int launch_coef_import(const CoefPlane* planes, const EncodeImage* dst, const RelayoutUnit* units, int nunits, uint32_t* out_of_range, void* stream);
+// To the decoder (hipjpegCoefficientsToPixelsBatch): the caller's planes to the decoder's layout with the DC value inside the block
+// (DecodeComponent::coef, dc == coef, dc_stride == 64, as for host-decoded pictures).  Components 0..3.  Here -- and only here -- a unit's
+// first_block counts over the component's MCU-PADDED grid (DecodeComponent::blocks_w x blocks_h): the kernel writes every block of the
+// grid, zeros outside the real area, because K1 reads the whole grid and the arena holds what an earlier batch left there.  No range
+// guard: any int16 is a coefficient the decoder has arithmetic for.
+int launch_coef_to_decoder(const CoefPlane* planes, const DecodeImage* dst, const RelayoutUnit* units, int nunits, void* stream);
+// From the coder (hipjpegPixelsToCoefficientsBatch): the coder's layout (EncodeImage::coef, as the forward kernels leave it) to the
+// caller's planes, real blocks only.  Components 0..2.
+int launch_coef_from_coder(const EncodeImage* src, const CoefPlane* planes, const RelayoutUnit* units, int nunits, void* stream);
 
 }  // namespace hipjpeg

@@ -1,5 +1,6 @@
-// coefficient_kernels.hip -- coef_export_kernel and coef_import_kernel: quantized coefficient blocks between the library's two private
-// HBM layouts and the public one of include/hipjpeg.h (hipjpegDecodeCoefficientsBatch / hipjpegEncodeCoefficientsBatch).
+// coefficient_kernels.hip -- coef_export_kernel, coef_import_kernel, coef_to_decoder_kernel and coef_from_coder_kernel: quantized
+// coefficient blocks between the library's two private HBM layouts and the public one of include/hipjpeg.h
+// (hipjpegDecodeCoefficientsBatch / hipjpegEncodeCoefficientsBatch; hipjpegCoefficientsToPixelsBatch / hipjpegPixelsToCoefficientsBatch).
 //
 //   decoder side (device_layout.h)  int16[64] per block, position col * 8 + row, blocks in raster order over the frame's MCU-padded
 //                                   grid; the DC value at dc[b * dc_stride] -- a compact plane for GPU-decoded pictures (position 0
@@ -19,6 +20,10 @@
 // Import: lane j loads natural row j and stores 16-byte piece j of the zigzag-ordered block.  A natural row-major block is the decoder's
 // block transposed, so the gather offsets are those coef_transform_kernel uses for a transposing turn: zigzag[k] * 2.  The range guard of
 // the transcode kernels runs in the same pass: the DC value is the low half of the first dword of row 0 here as it is of column 0 there.
+// To the decoder: export's transpose in the other direction (a transpose is its own inverse: the same gather), over the MCU-padded grid
+// of the destination, whose blocks then lie back to back; blocks outside the real area are stored as zeros (their lanes load the nearest
+// real block, no branch, and drop it).  From the coder: lane j loads piece j of the zigzag-ordered block and stores natural row j, the
+// gather offsets being the inverse of import's: position-in-zigzag[natural index] * 2.
 #include <hip/hip_runtime.h>
 
 #include "coefficient_kernels.h"
@@ -54,6 +59,20 @@ constexpr PieceOffsets make_piece_offsets_natural()
     return t;
 }
 __device__ const PieceOffsets kPieceOffsetsNatural = make_piece_offsets_natural();
+// the inverse: byte offsets (inside a zigzag-ordered int16 block) of the eight coefficients of natural row `piece`
+constexpr PieceOffsets make_row_offsets_zigzag()
+{
+    PieceOffsets t{};
+    int where[64] = {};
+    for (int k = 0; k < 64; k++) where[kZigzag[k]] = k;
+    for (int row = 0; row < 8; row++)
+        for (int i = 0; i < 8; i++) {
+            const unsigned off = (unsigned)(where[row * 8 + i] * 2);
+            t.w[row][i >> 1] |= (i & 1) ? off << 16 : off;
+        }
+    return t;
+}
+__device__ const PieceOffsets kRowOffsetsZigzag = make_row_offsets_zigzag();
 
 using lds_char = __attribute__((address_space(3))) char;
 using lds_u16 = __attribute__((address_space(3))) unsigned short;
@@ -204,6 +223,106 @@ __global__ __launch_bounds__(kThreads) void coef_import_kernel(const CoefPlane* 
     if (__ballot(bad != 0u) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(&out_of_range[u.image], 1u);
 }
 
+__global__ __launch_bounds__(kThreads) void coef_to_decoder_kernel(const CoefPlane* __restrict__ planes, const DecodeImage* __restrict__ dst,
+                                                                  const RelayoutUnit* __restrict__ units)
+{
+    __shared__ __attribute__((aligned(16))) char slots[kDepth * kBlocksPerPass * kSlotStride];
+    const RelayoutUnit u = units[blockIdx.x];
+    const CoefPlane& sp = planes[u.image * 4u + u.comp];     // comp 0..3 (uniform): one aligned record, members at constant offsets
+    const DecodeComponent& dc = dst[u.image].comp[u.comp];  // the same
+    const unsigned real_w = sp.real_w, real_h = sp.real_h, src_w = sp.pitch;
+    const unsigned grid_w = dc.blocks_w, ngrid = (unsigned)dc.blocks_w * dc.blocks_h;
+    const gbl_i16* in = (const gbl_i16*)sp.coef;
+    gbl_i16* out = (gbl_i16*)dc.coef;
+
+    const unsigned piece = threadIdx.x & 7u, slot_index = threadIdx.x >> 3;
+    lds_char* slot = (lds_char*)slots + slot_index * kSlotStride;
+    // f.by, f.bx: the block's place in the padded grid; f.dc: 1 = it carries samples (the same for the eight lanes of a block)
+    auto fetch = [&](int pass) {
+        Fetched f;
+        const unsigned r = u.first_block + (unsigned)pass * kBlocksPerPass + slot_index;
+        f.live = r < ngrid;
+        const unsigned rr = f.live ? r : ngrid - 1u;
+        f.by = rr / grid_w;
+        f.bx = rr - f.by * grid_w;
+        f.dc = (int)((f.by < real_h) & (f.bx < real_w));
+        // (padding reads the nearest real block: an address that is always the component's own)
+        const unsigned sy = f.by < real_h ? f.by : real_h - 1u, sx = f.bx < real_w ? f.bx : real_w - 1u;
+        f.v = *reinterpret_cast<const gbl_u32x4*>(in + ((size_t)sy * src_w + sx) * 64 + piece * 8);
+        return f;
+    };
+    for (int round = 0; round < kRounds; round++) {
+        Fetched f[kDepth];
+#pragma unroll
+        for (int j = 0; j < kDepth; j++) f[j] = fetch(round * kDepth + j);
+#pragma unroll
+        for (int j = 0; j < kDepth; j++) *reinterpret_cast<lds_u32x4*>(slot + j * (kBlocksPerPass * kSlotStride) + piece * 16) = f[j].v;
+        wave_lds_fence();
+#pragma unroll
+        for (int j = 0; j < kDepth; j++) {
+            if (!f[j].live) continue;
+            // the decoder's column `piece`: element t is column `piece` of natural row t
+            const lds_char* mine = slot + j * (kBlocksPerPass * kSlotStride) + piece * 2;
+            unsigned h[8];
+#pragma unroll
+            for (int t = 0; t < 8; t++) h[t] = *reinterpret_cast<const lds_u16*>(mine + t * 16);
+            const unsigned keep = f[j].dc ? 0xFFFFFFFFu : 0u;  // padding of the grid: zeros
+            const u32x4 z = {(h[0] | (h[1] << 16)) & keep, (h[2] | (h[3] << 16)) & keep, (h[4] | (h[5] << 16)) & keep, (h[6] | (h[7] << 16)) & keep};
+            *reinterpret_cast<gbl_u32x4*>(out + ((size_t)f[j].by * grid_w + f[j].bx) * 64 + piece * 8) = z;
+        }
+        wave_lds_fence();  // the next round rewrites the slots
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void coef_from_coder_kernel(const EncodeImage* __restrict__ src, const CoefPlane* __restrict__ planes,
+                                                                  const RelayoutUnit* __restrict__ units)
+{
+    __shared__ __attribute__((aligned(16))) char slots[kDepth * kBlocksPerPass * kSlotStride];
+    const RelayoutUnit u = units[blockIdx.x];
+    const int c = (int)u.comp;  // 0, 1, 2 (uniform)
+    const CoefPlane& dp = planes[u.image * 4u + u.comp];
+    const EncodeImage& im = src[u.image];
+    const unsigned real_w = dp.real_w, nreal = dp.real_w * dp.real_h, dst_w = dp.pitch;
+    const unsigned src_w = c == 0 ? im.blocks_w[0] : c == 1 ? im.blocks_w[1] : im.blocks_w[2];
+    const gbl_i16* in = (const gbl_i16*)(c == 0 ? im.coef[0] : c == 1 ? im.coef[1] : im.coef[2]);
+    gbl_i16* out = (gbl_i16*)dp.coef;
+
+    const unsigned piece = threadIdx.x & 7u, slot_index = threadIdx.x >> 3;
+    lds_char* slot = (lds_char*)slots + slot_index * kSlotStride;
+    const uint4 zoff = *reinterpret_cast<const uint4*>(&kRowOffsetsZigzag.w[piece][0]);
+    const unsigned o[4] = {zoff.x, zoff.y, zoff.z, zoff.w};
+    auto fetch = [&](int pass) {
+        Fetched f;
+        const unsigned r = u.first_block + (unsigned)pass * kBlocksPerPass + slot_index;
+        f.live = r < nreal;
+        const unsigned rr = f.live ? r : nreal - 1u;
+        f.by = rr / real_w;
+        f.bx = rr - f.by * real_w;
+        f.v = *reinterpret_cast<const gbl_u32x4*>(in + ((size_t)f.by * src_w + f.bx) * 64 + piece * 8);
+        f.dc = 0;
+        return f;
+    };
+    for (int round = 0; round < kRounds; round++) {
+        Fetched f[kDepth];
+#pragma unroll
+        for (int j = 0; j < kDepth; j++) f[j] = fetch(round * kDepth + j);
+#pragma unroll
+        for (int j = 0; j < kDepth; j++) *reinterpret_cast<lds_u32x4*>(slot + j * (kBlocksPerPass * kSlotStride) + piece * 16) = f[j].v;
+        wave_lds_fence();
+#pragma unroll
+        for (int j = 0; j < kDepth; j++) {
+            if (!f[j].live) continue;
+            const lds_char* mine = slot + j * (kBlocksPerPass * kSlotStride);
+            unsigned h[8];
+#pragma unroll
+            for (int t = 0; t < 8; t++) h[t] = *reinterpret_cast<const lds_u16*>(mine + ((t & 1) ? (o[t >> 1] >> 16) : (o[t >> 1] & 0xFFFFu)));
+            const u32x4 z = {h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
+            *reinterpret_cast<gbl_u32x4*>(out + ((size_t)f[j].by * dst_w + f[j].bx) * 64 + piece * 8) = z;
+        }
+        wave_lds_fence();  // the next round rewrites the slots
+    }
+}
+
 int launch_coef_export(const DecodeImage* src, const CoefPlane* planes, const RelayoutUnit* units, int nunits, void* stream)
 {
     if (nunits <= 0) return 0;
@@ -215,6 +334,20 @@ int launch_coef_import(const CoefPlane* planes, const EncodeImage* dst, const Re
 {
     if (nunits <= 0) return 0;
     hipLaunchKernelGGL(coef_import_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, planes, dst, units, out_of_range);
+    return (int)hipGetLastError();
+}
+
+int launch_coef_to_decoder(const CoefPlane* planes, const DecodeImage* dst, const RelayoutUnit* units, int nunits, void* stream)
+{
+    if (nunits <= 0) return 0;
+    hipLaunchKernelGGL(coef_to_decoder_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, planes, dst, units);
+    return (int)hipGetLastError();
+}
+
+int launch_coef_from_coder(const EncodeImage* src, const CoefPlane* planes, const RelayoutUnit* units, int nunits, void* stream)
+{
+    if (nunits <= 0) return 0;
+    hipLaunchKernelGGL(coef_from_coder_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, src, planes, units);
     return (int)hipGetLastError();
 }
 

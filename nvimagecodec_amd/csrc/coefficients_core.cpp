@@ -76,6 +76,65 @@ hipjpegStatus_t coefficient_picture(const hipjpegCoefficientInfo_t& info, const 
     return transcode_picture(f, /*grayscale=*/false, pic);
 }
 
+hipjpegStatus_t coefficient_frame(const hipjpegCoefficientInfo_t& info, const hipjpegCoefficientPlanes_t& planes, FrameInfo* out)
+{
+    if (info.width < 1 || info.height < 1 || info.width > 65535 || info.height > 65535) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (info.num_components < 1 || info.num_components > 4) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    FrameInfo f;
+    f.width = info.width;
+    f.height = info.height;
+    f.precision = 8;
+    f.ncomp = info.num_components;
+    f.sof = 0xC0;
+    for (int c = 0; c < f.ncomp; c++) {
+        if (info.h[c] < 1 || info.h[c] > 4 || info.v[c] < 1 || info.v[c] > 4) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+        f.hmax = std::max(f.hmax, info.h[c]);
+        f.vmax = std::max(f.vmax, info.v[c]);
+    }
+    // (jpeg_syntax.cpp finish_frame)
+    f.mcus_x = (f.width + 8 * f.hmax - 1) / (8 * f.hmax);
+    f.mcus_y = (f.height + 8 * f.vmax - 1) / (8 * f.vmax);
+    for (int c = 0; c < f.ncomp; c++) {
+        Component& k = f.comp[c];
+        k.id = c + 1;
+        k.h = info.h[c];
+        k.v = info.v[c];
+        k.blocks_w = f.mcus_x * k.h;
+        k.blocks_h = f.mcus_y * k.v;
+        k.samp_w = (f.width * k.h + f.hmax - 1) / f.hmax;
+        k.samp_h = (f.height * k.v + f.vmax - 1) / f.vmax;
+        if (info.blocks_w[c] != (k.samp_w + 7) / 8 || info.blocks_h[c] != (k.samp_h + 7) / 8) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+        memcpy(f.qtab[c], info.qtable[c], sizeof f.qtab[c]);
+    }
+    const hipjpegStatus_t st = coefficient_planes_ok(f.ncomp, info.blocks_w, planes);
+    if (st != HIPJPEG_STATUS_SUCCESS) return st;
+    if (f.ncomp == 4 || f.ncomp == 2) return HIPJPEG_STATUS_UNSUPPORTED;
+    if (f.ncomp == 1)
+        f.color = ColorModel::Gray;
+    else if (info.color_model < (int32_t)ColorModel::Gray || info.color_model > (int32_t)ColorModel::RGB)
+        return HIPJPEG_STATUS_UNSUPPORTED;
+    else
+        f.color = (ColorModel)info.color_model;
+    *out = f;
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+void encode_coefficient_info(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], hipjpegCoefficientInfo_t* info)
+{
+    memset(info, 0, sizeof *info);
+    info->width = g.width;
+    info->height = g.height;
+    info->num_components = g.ncomp;
+    info->color_model = (int32_t)(g.ncomp == 1 ? ColorModel::Gray : ColorModel::YCbCr);
+    for (int c = 0; c < g.ncomp; c++) {
+        info->h[c] = c == 0 ? g.hs : 1;
+        info->v[c] = c == 0 ? g.vs : 1;
+        info->blocks_w[c] = g.real_w[c];
+        info->blocks_h[c] = g.real_h[c];
+        memcpy(info->qtable[c], c == 0 ? qlum : qchr, sizeof info->qtable[c]);
+    }
+}
+
 }  // namespace hipjpeg
 
 using namespace hipjpeg;
@@ -116,6 +175,20 @@ extern "C" hipjpegStatus_t hipjpegGetCoefficientInfo(const uint8_t* data, size_t
         const hipjpegStatus_t st = coefficient_parse_status(parse_jpeg(data, length, &f));
         if (st != HIPJPEG_STATUS_SUCCESS) return st;
         coefficient_info(f, info);
+        return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+extern "C" hipjpegStatus_t hipjpegGetEncodeCoefficientInfo(int32_t width, int32_t height, const hipjpegEncodeParams_t* params, hipjpegCoefficientInfo_t* info)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+        if (!params || !info) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+        memset(info, 0, sizeof *info);
+        EncodeGeometry g;
+        uint16_t ql[64], qc[64];
+        const hipjpegStatus_t st = picture_setup(*params, width, height, &g, ql, qc);
+        if (st != HIPJPEG_STATUS_SUCCESS) return st;
+        encode_coefficient_info(g, ql, qc, info);
         return HIPJPEG_STATUS_SUCCESS;
     });
 }

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <numeric>
 
+#include "coefficients_core.h"
 #include "decode_kernels.h"
 #include "diagnostics.h"
 #include "entropy_decode.h"
@@ -198,6 +199,8 @@ struct DecodeBatch::PlanArgs {  // plan()'s arguments; give_up: per image, given
     const hipjpegOutputFormat_t* formats; const hipjpegTransform_t* transforms; const char* give_up;
     const hipjpegTranscodeParams_t* transcode = nullptr;  // plan_coefficients(): per image, or nullptr
     bool any_frame = false;                               // plan_coefficients(): the coder's rules are not asked
+    const hipjpegCoefficientInfo_t* infos = nullptr;      // plan_tensors(): the pictures, in place of data / lengths
+    const hipjpegCoefficientPlanes_t* tensors = nullptr;
 };
 
 // What the per-image sizing adds up, in bytes unless noted; every region is carved in image order.
@@ -209,6 +212,7 @@ struct DecodeBatch::Sizing {
     // GPU entropy stage: staging area (scans, tables, boundaries), device-only scratch (streams, DC values, positions), chunks (a count)
     Carve raw, pools, boundaries, streams, blocks, block_pos, prog_pos, chunks;
     size_t subseq = 0, huff_wunits = 0, prog_units = 0, prog_scans = 0;
+    size_t tensor_units = 0;  // plan_tensors(): RelayoutUnit slots of coef_to_decoder_kernel
 
     // One scan: its staged bytes (padded, see entropy_stage), its destuffed stream, its destuff chunks.  Returns the stream's capacity.
     size_t scan(const ScanHeader& sc, size_t* raw_offset, size_t* stream_offset, uint32_t* first_chunk)
@@ -227,7 +231,23 @@ hipjpegStatus_t DecodeBatch::plan(const uint8_t* const* data, const size_t* leng
 {
     pool_ = pool;
     coef_only_ = false;
+    tensor_source_ = false;
     return plan_attempts(PlanArgs{data, lengths, outputs, format, flags, formats, transforms, nullptr}, n, statuses);
+}
+
+hipjpegStatus_t DecodeBatch::plan_tensors(const hipjpegCoefficientInfo_t* infos, const hipjpegCoefficientPlanes_t* planes, int n,
+                                          const hipjpegOutput_t* outputs, hipjpegOutputFormat_t format, unsigned flags, hipjpegStatus_t* statuses,
+                                          ForkJoinPool* pool, const hipjpegTransform_t* transforms)
+{
+    if (n > 0 && (!infos || !planes)) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    pool_ = pool;
+    coef_only_ = false;
+    tensor_source_ = true;
+    tensor_planes_ = planes;
+    PlanArgs a{nullptr, nullptr, outputs, format, flags & ~HIPJPEG_FLAG_GPU_HUFFMAN, nullptr, transforms, nullptr};
+    a.infos = infos;
+    a.tensors = planes;
+    return plan_attempts(a, n, statuses);
 }
 
 hipjpegStatus_t DecodeBatch::plan_coefficients(const uint8_t* const* data, const size_t* lengths, int n, unsigned flags, hipjpegStatus_t* statuses,
@@ -235,6 +255,7 @@ hipjpegStatus_t DecodeBatch::plan_coefficients(const uint8_t* const* data, const
 {
     pool_ = pool;
     coef_only_ = true;
+    tensor_source_ = false;
     return plan_attempts(PlanArgs{data, lengths, nullptr, HIPJPEG_OUTPUT_RGBI, flags & HIPJPEG_FLAG_GPU_HUFFMAN, nullptr, nullptr, nullptr, params, any_frame}, n,
                          statuses);
 }
@@ -266,7 +287,7 @@ hipjpegStatus_t DecodeBatch::plan_attempts(const PlanArgs& a, int n, hipjpegStat
 
 hipjpegStatus_t DecodeBatch::plan_once(const PlanArgs& a, int n, hipjpegStatus_t* statuses)
 {
-    if (n < 0 || (n > 0 && (!a.data || !a.lengths || (!a.outputs && !coef_only_)))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (n < 0 || (n > 0 && (((!a.data || !a.lengths) && !a.infos) || (!a.outputs && !coef_only_)))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if ((int)a.format < 0 || (int)a.format > (int)HIPJPEG_OUTPUT_YUV_PLANAR) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     ScopedRange range("hipjpeg plan (parse headers, lay out staging)");
     fault_point("plan");
@@ -312,8 +333,8 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
     PlannedImage& im = images_[i];
     im = PlannedImage();
     desc_[i] = DecodeImage();
-    im.data = a.data[i];
-    im.size = a.lengths[i];
+    im.data = a.infos ? nullptr : a.data[i];
+    im.size = a.infos ? 0 : a.lengths[i];
     if (a.formats && ((int)a.formats[i] < 0 || (int)a.formats[i] > (int)HIPJPEG_OUTPUT_YUV_PLANAR)) {
         im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
         return;
@@ -321,7 +342,10 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
     const OutFormat fmt = (OutFormat)(a.formats ? a.formats[i] : a.format);
     const bool fancy = (a.flags & HIPJPEG_FLAG_FANCY_UPSAMPLING) != 0;
     const FrameInfo& f = im.frame;
-    im.status = a.data[i] ? status_from_parse(parse_jpeg(a.data[i], a.lengths[i], &im.frame)) : HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (a.infos)  // the picture is described, not parsed
+        im.status = coefficient_frame(a.infos[i], a.tensors[i], &im.frame);
+    else
+        im.status = a.data[i] ? status_from_parse(parse_jpeg(a.data[i], a.lengths[i], &im.frame)) : HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (im.status == HIPJPEG_STATUS_SUCCESS && ((uint64_t)f.width * (uint64_t)f.height * (uint64_t)f.ncomp >= max_image_samples() || a.give_up[i]))
         im.status = HIPJPEG_STATUS_ALLOC_FAILED;  // this image only; its neighbours decode
     if (coef_only_) {
@@ -484,6 +508,8 @@ void DecodeBatch::size_image(int i, Sizing& s)
     }
     if (im.variant == -1 || im.variant == -3) s.units += (size_t)f.height;
     coef_bytes_ += f.total_blocks() * 128;
+    if (tensor_source_)
+        for (int c = 0; c < f.ncomp; c++) s.tensor_units += ((size_t)f.comp[c].blocks_w * f.comp[c].blocks_h + kRelayoutBlocksPerUnit - 1) / kRelayoutBlocksPerUnit;
     if (fmt == kOutPlanarYUV)
         for (int c = 0; c < f.ncomp; c++) output_bytes_ += (uint64_t)f.comp[c].samp_w * f.comp[c].samp_h;
     else
@@ -565,21 +591,23 @@ void DecodeBatch::layout(const Sizing& s)
     L.xform_units = c.take(sizeof(WorkUnit) * s.xform_units);
     L.prog_desc = c.take(sizeof(ProgImage) * prog_to_image_.size());
     L.prog_units = c.take(sizeof(HuffUnit) * s.prog_units);
+    L.tensor_planes = c.take(tensor_source_ ? sizeof(CoefPlane) * 4 * images_.size() : 0);
+    L.tensor_units = c.take(sizeof(RelayoutUnit) * s.tensor_units);
     L.tables = c.take(s.pools.end);
     L.boundaries = c.take(s.boundaries.end);
     L.streams = c.take(s.raw.end);
     L.coef = c.take(0);
     // HIPJPEG_DENSE_STAGING=1: dense int16 blocks for every host-decoded picture as in rounds 1-2 (A/B and cross-check aid)
     static const bool sparse_enabled = getenv("HIPJPEG_DENSE_STAGING") == nullptr;
-    sparse_mode_ = sparse_enabled && !coef_only_;  // (the relayout kernel reads dense blocks)
+    sparse_mode_ = sparse_enabled && !coef_only_ && !tensor_source_;  // (the relayout kernels read and write dense blocks)
     host_coef_used_.store(0);
-    for (int pass = 0; pass < 2; pass++) {  // host-decoded images first, GPU-decoded ones behind the H2D boundary
+    for (int pass = 0; pass < 2; pass++) {  // host-decoded images first, GPU-decoded ones (and tensors: import_tensors()) behind the H2D boundary
         if (pass == 1) {
             L.h2d_bytes = c.end;
             L.gpu_coef_begin = c.take(0);
         }
         for (PlannedImage& im : images_) {
-            if (im.status != HIPJPEG_STATUS_SUCCESS || (int)im.gpu_entropy != pass) continue;
+            if (im.status != HIPJPEG_STATUS_SUCCESS || (int)(im.gpu_entropy || tensor_source_) != pass) continue;
             if (pass == 0 && sparse_mode_) c.end += 256;  // (host-decoded pictures are placed while they are decoded: room for alignment)
             for (int k = 0; k < im.frame.ncomp; k++) im.coef_offset[k] = c.take((size_t)im.frame.comp[k].blocks_w * im.frame.comp[k].blocks_h * 128, 1);
             if (!im.gpu_entropy) continue;
@@ -671,7 +699,7 @@ void DecodeBatch::stage_chunk_drops(const ScanHeader& sc, uint32_t first_chunk)
 void DecodeBatch::entropy_stage(int i)
 {
     PlannedImage& im = images_[i];
-    if (im.status != HIPJPEG_STATUS_SUCCESS) return;
+    if (im.status != HIPJPEG_STATUS_SUCCESS || tensor_source_) return;  // (tensors: nothing to decode)
     ScopedRange range(im.gpu_entropy ? "hipjpeg host stage (stage bitstream, is_gpu_huffman=1)" : "hipjpeg host stage (Huffman decode, is_gpu_huffman=0)");
     fault_point("entropy_stage");
     if (im.gpu_prog) {
@@ -807,6 +835,7 @@ void DecodeBatch::finalize(hipjpegStatus_t* statuses)
     host_taken_.clear();
     build_pixel_units();
     build_entropy_units();
+    build_tensor_units();
     // what transfer() has to copy: in sparse mode the host-decoded region ends where the last picture was placed
     h2d_used_ = sparse_mode_ ? std::min(staging_.h2d_bytes, align_up(staging_.coef + host_coef_used_.load(), 256)) : staging_.h2d_bytes;
     stage_tables();
@@ -1067,6 +1096,8 @@ void DecodeBatch::stage_tables()
     Carve xform{staging_.xform_units};
     stage(xform_units_, xform);
     copy_table(pinned_, staging_.xform_desc, xform_desc_);
+    copy_table(pinned_, staging_.tensor_planes, tensor_table_);
+    copy_table(pinned_, staging_.tensor_units, tensor_units_);
     copy_table(pinned_, staging_.prog_desc, prog_images_);
     copy_table(pinned_, staging_.prog_units, prog_units_);
     copy_table(pinned_, staging_.huff_desc, huff_images_);
@@ -1540,6 +1571,61 @@ hipjpegStatus_t DecodeBatch::launch(void* stream, int which, void* entropy_strea
 }
 
 // ---------------------------------------------------------------- coefficient tensors
+// plan_tensors(): the caller's planes as the kernel reads them and the units of coef_to_decoder_kernel, image by image (sized by
+// size_image()); images that failed get neither.
+void DecodeBatch::build_tensor_units()
+{
+    tensor_table_.clear();
+    tensor_units_.clear();
+    imported_blocks_ = 0;
+    if (!tensor_source_) return;
+    tensor_table_.assign(images_.size() * 4, CoefPlane{nullptr, 0, 0, 0, 0});
+    for (size_t i = 0; i < images_.size() && tensor_planes_; i++) {
+        const PlannedImage& im = images_[i];
+        if (im.status != HIPJPEG_STATUS_SUCCESS) continue;
+        const hipjpegCoefficientPlanes_t& p = tensor_planes_[i];
+        for (int c = 0; c < im.frame.ncomp; c++) {
+            const Component& k = im.frame.comp[c];
+            const uint32_t real_w = (uint32_t)(k.samp_w + 7) / 8, real_h = (uint32_t)(k.samp_h + 7) / 8;
+            tensor_table_[i * 4 + (size_t)c] = CoefPlane{static_cast<int16_t*>(p.coef[c]), p.pitch_blocks[c], real_w, real_h, 0};
+            // (over the MCU-padded grid: the kernel writes the padding too, as zeros)
+            for (uint32_t b = 0; b < (uint32_t)k.blocks_w * (uint32_t)k.blocks_h; b += kRelayoutBlocksPerUnit)
+                tensor_units_.push_back(RelayoutUnit{(uint32_t)i, (uint32_t)c, b, 0});
+            imported_blocks_ += (uint64_t)real_w * real_h;
+        }
+    }
+    tensor_planes_ = nullptr;
+}
+
+hipjpegStatus_t DecodeBatch::import_tensors(void* stream)
+{
+    if (!tensor_source_ || !finalized_) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (tensor_units_.empty()) return HIPJPEG_STATUS_SUCCESS;
+    if (hipSetDevice(device_id_) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    // HIPJPEG_DEBUG_TIMING (debug aid): the kernel's own time on stderr (tools/prof_coefficient_pixels.py reads it); the aid waits for the kernel
+    static const bool timing = getenv("HIPJPEG_DEBUG_TIMING") != nullptr;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (timing && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, s) != hipSuccess)) return HIPJPEG_STATUS_HIP_ERROR;
+    if (launch_coef_to_decoder(at<const CoefPlane>(device_, staging_.tensor_planes), device_descriptors(), at<const RelayoutUnit>(device_, staging_.tensor_units),
+                               (int)tensor_units_.size(), stream) != 0)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    debug_check(stream, "coef_to_decoder", (int)tensor_units_.size());
+    if (timing) {
+        float ms = 0;
+        if (hipEventRecord(t1, s) != hipSuccess || hipEventSynchronize(t1) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        fprintf(stderr, "[hipjpeg] coef_to_decoder_kernel: %zu workgroups, %llu blocks, %.4f ms\n", tensor_units_.size(), (unsigned long long)imported_blocks_, ms);
+        (void)hipEventDestroy(t0);
+        (void)hipEventDestroy(t1);
+    }
+    // the kernel writes this page's coefficient arena and reads the staged tables: nothing rewrites them before it has run
+    if (!ensure_event(&done_event_) || hipEventRecord((hipEvent_t)done_event_, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+    in_flight_ = true;
+    last_stream_ = stream;
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
 hipjpegStatus_t DecodeBatch::export_coefficients(const hipjpegCoefficientPlanes_t* planes, void* stream)
 {
     exported_blocks_ = 0;

@@ -99,6 +99,19 @@ public:
     // `any_frame` (hipjpegDecodeCoefficientsBatch): every frame the entropy stage decodes is taken, whatever the coder thinks of it.
     hipjpegStatus_t plan_coefficients(const uint8_t* const* data, const size_t* lengths, int n, unsigned flags, hipjpegStatus_t* statuses,
                                       ForkJoinPool* pool, const hipjpegTranscodeParams_t* params = nullptr, bool any_frame = false);
+    // Coefficient tensors to pixels (hipjpegCoefficientsToPixelsBatch): plan() for pictures given by infos[i] + planes[i] instead of files.
+    // The frame is coefficients_core.h's coefficient_frame(); kernel variants, quantizers, outputs, transforms and unit tables are
+    // plan()'s own.  There is no entropy stage: every image's coefficients live in the device-only part of the arena, where
+    // import_tensors() puts them.  Of `flags` HIPJPEG_FLAG_GPU_HUFFMAN is ignored.  Then finalize(), transfer(), import_tensors(),
+    // launch(); entropy_stage() does nothing for such a batch.
+    hipjpegStatus_t plan_tensors(const hipjpegCoefficientInfo_t* infos, const hipjpegCoefficientPlanes_t* planes, int n, const hipjpegOutput_t* outputs,
+                                 hipjpegOutputFormat_t format, unsigned flags, hipjpegStatus_t* statuses, ForkJoinPool* pool,
+                                 const hipjpegTransform_t* transforms = nullptr);
+    // Behind plan_tensors() ... transfer(), which took the CoefPlane table and the relayout units up with the descriptors: queues
+    // coef_to_decoder_kernel (coefficient_kernels.hip) on `stream`: the caller's planes into the arena in the decoder's layout, zeros in
+    // the blocks of the MCU-padded grid outside the real area.  Images with a status other than SUCCESS are left out.  Nothing blocks.
+    hipjpegStatus_t import_tensors(void* stream);
+    uint64_t imported_blocks() const { return imported_blocks_; }  // real blocks the last import_tensors() moved
     // Coefficient tensors (hipjpegDecodeCoefficientsBatch), behind plan_coefficients() ... launch(stream, 3): coef_export_kernel
     // (coefficient_kernels.hip) copies the real blocks of every image that decoded into planes[i] (checked by the caller: pointers,
     // alignment, pitch), natural order, queued on `stream`.  Images with a status other than SUCCESS are left out.
@@ -162,6 +175,12 @@ private:
     struct Sizing;    // what the per-image sizing adds up
     hipjpegStatus_t plan_attempts(const PlanArgs& a, int n, hipjpegStatus_t* statuses);
     bool coef_only_ = false;  // the batch was planned by plan_coefficients()
+    bool tensor_source_ = false;  // the batch was planned by plan_tensors()
+    const hipjpegCoefficientPlanes_t* tensor_planes_ = nullptr;  // plan_tensors(): the caller's planes, read until finalize() returns
+    std::vector<CoefPlane> tensor_table_;      // plan_tensors(): four records per image and the units of coef_to_decoder_kernel,
+    std::vector<RelayoutUnit> tensor_units_;   // built by finalize(), staged with the other tables
+    void build_tensor_units();
+    uint64_t imported_blocks_ = 0;
     hipjpegStatus_t plan_once(const PlanArgs& a, int n, hipjpegStatus_t* statuses);
     void prepare(int i, const PlanArgs& a);
     bool pitch_ok(int i, const hipjpegOutput_t& out, OutFormat fmt) const;
@@ -178,7 +197,7 @@ private:
     // GPU-decoded images.  The pinned side keeps 256 spare bytes behind h2d_bytes (entropy_launch_args).
     struct StagingLayout {
         size_t desc, units, huff_desc, huff_units, huff_wunits, huff_dc_units, huff_list, huff_chunk_units, huff_drops, xform_desc, xform_units,
-            prog_desc, prog_units, tables, boundaries, streams, coef, h2d_bytes, gpu_coef_begin, total;
+            prog_desc, prog_units, tensor_planes, tensor_units, tables, boundaries, streams, coef, h2d_bytes, gpu_coef_begin, total;
     } staging_{};
     // Device-only scratch of the entropy kernels (work_): subsequence states (at 0) | first block indices | change counters | ...
     struct WorkLayout {

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "coefficients_core.h"
 #include "encode_kernels.h"
 #include "huffman_encode_core.h"
 #include "jpeg_syntax.h"
@@ -36,34 +37,6 @@ EncodeFlavour pair_flavour(int hs, int vs, bool planar)
 }
 }  // namespace
 
-hipjpegStatus_t subsampling_factors(int subsampling, int* ncomp, int* hs, int* vs)
-{
-    *ncomp = 3;
-    switch (subsampling) {
-    case HIPJPEG_CSS_444: *hs = 1; *vs = 1; break;
-    case HIPJPEG_CSS_422: *hs = 2; *vs = 1; break;
-    case HIPJPEG_CSS_420: *hs = 2; *vs = 2; break;
-    case HIPJPEG_CSS_440: *hs = 1; *vs = 2; break;
-    case HIPJPEG_CSS_411: *hs = 4; *vs = 1; break;
-    case HIPJPEG_CSS_410: *hs = 4; *vs = 2; break;
-    case HIPJPEG_CSS_GRAY: *ncomp = 1; *hs = 1; *vs = 1; break;
-    default: return HIPJPEG_STATUS_UNSUPPORTED;
-    }
-    return HIPJPEG_STATUS_SUCCESS;
-}
-
-hipjpegStatus_t picture_setup(const hipjpegEncodeParams_t& p, int width, int height, EncodeGeometry* g, uint16_t qlum[64], uint16_t qchr[64])
-{
-    g->width = width;
-    g->height = height;
-    const hipjpegStatus_t st = subsampling_factors(p.subsampling, &g->ncomp, &g->hs, &g->vs);
-    if (st != HIPJPEG_STATUS_SUCCESS) return st;
-    if (width < 1 || height < 1 || width > 65535 || height > 65535) return HIPJPEG_STATUS_INVALID_ARGUMENT;
-    compute_geometry(g);
-    quality_tables(p.quality, qlum, qchr);
-    return HIPJPEG_STATUS_SUCCESS;
-}
-
 EntropyEncodeOptions entropy_options(const hipjpegEncodeParams_t& p)
 {
     return EntropyEncodeOptions{p.restart_interval, p.optimized_huffman != 0, p.progressive != 0};
@@ -71,6 +44,7 @@ EntropyEncodeOptions entropy_options(const hipjpegEncodeParams_t& p)
 
 EncodeBatch::EncodeBatch(int device_id, const MemoryHooks* hooks)
     : device_id_(device_id), pinned_desc_(Buffer::kPinned, hooks), device_(Buffer::kDevice, hooks), pinned_coef_(Buffer::kPinned, hooks),
+      planes_pinned_(Buffer::kPinned, hooks), planes_device_(Buffer::kDevice, hooks),
       henc_(hooks), penc_(hooks)
 {
 }
@@ -384,6 +358,61 @@ hipjpegStatus_t EncodeBatch::coefficient_fill(const CoefficientPicture* pics, in
     // the range guard: such values are outside what the coders' tables cover, so no coder gets to see them
     for (int i = 0; i < n && !relayout_units_.empty(); i++)
         if (images_[i].status == HIPJPEG_STATUS_SUCCESS && flags[i] != 0) images_[i].status = HIPJPEG_STATUS_UNSUPPORTED;
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+// ---------------------------------------------------------------- planes_stage
+hipjpegStatus_t EncodeBatch::planes_stage(const hipjpegCoefficientPlanes_t* planes, hipjpegStatus_t* statuses, void* stream)
+{
+    planes_blocks_ = 0;
+    const size_t n = images_.size();
+    if (!launched_ || stream != stream_ || (n > 0 && !planes)) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(device_id_) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    std::vector<CoefPlane> table(n * 4, CoefPlane{nullptr, 0, 0, 0, 0});
+    std::vector<RelayoutUnit> units;
+    for (size_t i = 0; i < n; i++) {
+        PlannedEncode& im = images_[i];
+        if (im.status != HIPJPEG_STATUS_SUCCESS) continue;
+        const EncodeGeometry& g = im.geom;
+        const int32_t real_w[4] = {g.real_w[0], g.real_w[1], g.real_w[2], 0};
+        im.status = coefficient_planes_ok(g.ncomp, real_w, planes[i]);
+        if (statuses) statuses[i] = im.status;
+        if (im.status != HIPJPEG_STATUS_SUCCESS) continue;
+        for (int c = 0; c < g.ncomp; c++) {
+            const uint32_t nreal = (uint32_t)(g.real_w[c] * g.real_h[c]);
+            table[i * 4 + (size_t)c] = CoefPlane{static_cast<int16_t*>(planes[i].coef[c]), planes[i].pitch_blocks[c], (uint32_t)g.real_w[c], (uint32_t)g.real_h[c], 0};
+            for (uint32_t b = 0; b < nreal; b += kRelayoutBlocksPerUnit) units.push_back(RelayoutUnit{(uint32_t)i, (uint32_t)c, b, 0});
+            planes_blocks_ += nreal;
+        }
+    }
+    if (units.empty()) return HIPJPEG_STATUS_SUCCESS;
+    // (the previous use of these two buffers has drained: device_stage() waited for the event recorded below)
+    Carve carve;
+    const size_t table_at = carve.take(sizeof(CoefPlane) * table.size()), units_at = carve.take(sizeof(RelayoutUnit) * units.size());
+    hipjpegStatus_t st;
+    if ((st = planes_pinned_.reserve(carve.end + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
+    if ((st = planes_device_.reserve(carve.end + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
+    copy_table(planes_pinned_, table_at, table);
+    copy_table(planes_pinned_, units_at, units);
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(planes_device_.data(), planes_pinned_.data(), carve.end, hipMemcpyHostToDevice, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+    // HIPJPEG_DEBUG_TIMING (debug aid): the kernel's own time on stderr (tools/prof_coefficient_pixels.py reads it); the aid waits for the kernel
+    static const bool timing = getenv("HIPJPEG_DEBUG_TIMING") != nullptr;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    if (timing && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, s) != hipSuccess)) return HIPJPEG_STATUS_HIP_ERROR;
+    if (launch_coef_from_coder(at<const EncodeImage>(device_, staging_.desc), at<const CoefPlane>(planes_device_, table_at),
+                               at<const RelayoutUnit>(planes_device_, units_at), (int)units.size(), stream) != 0)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    if (timing) {
+        float ms = 0;
+        if (hipEventRecord(t1, s) != hipSuccess || hipEventSynchronize(t1) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+        (void)hipEventElapsedTime(&ms, t0, t1);
+        fprintf(stderr, "[hipjpeg] coef_from_coder_kernel: %zu workgroups, %llu blocks, %.4f ms\n", units.size(), (unsigned long long)planes_blocks_, ms);
+        (void)hipEventDestroy(t0);
+        (void)hipEventDestroy(t1);
+    }
+    // the kernel reads the coefficient area and the tables above: nothing rewrites them before it has run
+    if (hipEventRecord((hipEvent_t)event_, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
     return HIPJPEG_STATUS_SUCCESS;
 }
 

@@ -68,6 +68,12 @@ public:
     // `stream` behind whatever produced the planes there.  Blocks for the range flags as coefficient_stage() does.
     hipjpegStatus_t import_stage(const CoefficientPicture* pics, const hipjpegCoefficientPlanes_t* planes, int n, void* stream);
     uint64_t relayout_blocks() const { return relayout_blocks_; }  // blocks the last coefficient_stage() moved
+    // Pixels to coefficient tensors (hipjpegPixelsToCoefficientsBatch), behind device_stage() on the same stream: checks planes[i] against
+    // image i's real block area (coefficients_core.h coefficient_planes_ok; a failing image gets that status and is left out), uploads
+    // the CoefPlane table and the relayout units and queues coef_from_coder_kernel (coefficient_kernels.hip): the coder's layout to the
+    // caller's planes, real blocks only, for every image whose status is SUCCESS.  Nothing blocks.
+    hipjpegStatus_t planes_stage(const hipjpegCoefficientPlanes_t* planes, hipjpegStatus_t* statuses, void* stream);
+    uint64_t planes_blocks() const { return planes_blocks_; }  // blocks the last planes_stage() moved
     // Coefficients D2H (on the stream used by device_stage), wait.
     hipjpegStatus_t fetch_coefficients();
     // Decides who entropy-codes each planned image: with gpu_huffman the GPU coder (blocking) takes every image it can -- Annex-K
@@ -94,6 +100,8 @@ private:
     hipjpegStatus_t reserve();
     void bind_pointers();
     Buffer pinned_desc_, device_, pinned_coef_;
+    Buffer planes_pinned_, planes_device_;  // planes_stage(): CoefPlane[4 n] | RelayoutUnit[]
+    uint64_t planes_blocks_ = 0;
     std::vector<PlannedEncode> images_;
     std::vector<EncodeImage> desc_;
     std::vector<EncodeUnit> units_;  // every tile of the batch, grouped by flavour
@@ -160,10 +168,7 @@ private:
     uint64_t gpu_entropy_images_ = 0;
 };
 
-hipjpegStatus_t subsampling_factors(int subsampling, int* ncomp, int* hs, int* vs);
-// Geometry (subsampling factors, block grid) and quantiser tables of a width x height picture coded with `p`: UNSUPPORTED for an
-// unknown subsampling, INVALID_ARGUMENT for a size outside 1..65535 (then neither grid nor tables are filled).
-hipjpegStatus_t picture_setup(const hipjpegEncodeParams_t& p, int width, int height, EncodeGeometry* g, uint16_t qlum[64], uint16_t qchr[64]);
+// (subsampling_factors() and picture_setup(): entropy_encode.h, with the geometry and the tables they fill)
 EntropyEncodeOptions entropy_options(const hipjpegEncodeParams_t& p);
 
 }  // namespace hipjpeg

@@ -333,6 +333,34 @@ void compute_geometry(EncodeGeometry* g)
     }
 }
 
+hipjpegStatus_t subsampling_factors(int subsampling, int* ncomp, int* hs, int* vs)
+{
+    *ncomp = 3;
+    switch (subsampling) {
+    case HIPJPEG_CSS_444: *hs = 1; *vs = 1; break;
+    case HIPJPEG_CSS_422: *hs = 2; *vs = 1; break;
+    case HIPJPEG_CSS_420: *hs = 2; *vs = 2; break;
+    case HIPJPEG_CSS_440: *hs = 1; *vs = 2; break;
+    case HIPJPEG_CSS_411: *hs = 4; *vs = 1; break;
+    case HIPJPEG_CSS_410: *hs = 4; *vs = 2; break;
+    case HIPJPEG_CSS_GRAY: *ncomp = 1; *hs = 1; *vs = 1; break;
+    default: return HIPJPEG_STATUS_UNSUPPORTED;
+    }
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
+hipjpegStatus_t picture_setup(const hipjpegEncodeParams_t& p, int width, int height, EncodeGeometry* g, uint16_t qlum[64], uint16_t qchr[64])
+{
+    g->width = width;
+    g->height = height;
+    const hipjpegStatus_t st = subsampling_factors(p.subsampling, &g->ncomp, &g->hs, &g->vs);
+    if (st != HIPJPEG_STATUS_SUCCESS) return st;
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    compute_geometry(g);
+    quality_tables(p.quality, qlum, qchr);
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
 // SOI, APP0, [copied APPn / COM segments], DQT.., SOFn (jcmarker.c write_file_header + write_frame_header; jpegtran's place for the copies)
 static void write_frame_header(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], int sof_marker, std::vector<uint8_t>* o,
                                const std::vector<uint8_t>* markers)

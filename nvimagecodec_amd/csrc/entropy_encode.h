@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "../../include/hipjpeg.h"
+
 namespace hipjpeg {
 
 struct EncodeGeometry {
@@ -21,6 +23,10 @@ struct EncodeGeometry {
 void quality_tables(int quality, uint16_t lum[64], uint16_t chr[64]);
 // Fills the grid fields from width/height/ncomp/hs/vs.
 void compute_geometry(EncodeGeometry* g);
+hipjpegStatus_t subsampling_factors(int subsampling, int* ncomp, int* hs, int* vs);
+// Geometry (subsampling factors, block grid) and quantiser tables of a width x height picture coded with `p`: UNSUPPORTED for an
+// unknown subsampling, INVALID_ARGUMENT for a size outside 1..65535 (then neither grid nor tables are filled).
+hipjpegStatus_t picture_setup(const hipjpegEncodeParams_t& p, int width, int height, EncodeGeometry* g, uint16_t qlum[64], uint16_t qchr[64]);
 
 struct EntropyEncodeOptions {
     int restart_interval = 0;     // in MCUs, 0 = none

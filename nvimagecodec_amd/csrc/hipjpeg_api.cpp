@@ -86,8 +86,8 @@ struct hipjpegHandle {
     // hipjpegTranscodeBatchSetRegions: for the next hipjpegTranscodeBatch only
     std::vector<hipjpegTranscodeRegion_t> transcode_regions;
     bool transcode_regions_set = false;
-    // the last hipjpegDecodeCoefficientsBatch / hipjpegEncodeCoefficientsBatch: images on the GPU entropy decoder / coder, blocks the
-    // later of the two calls moved
+    // the last hipjpegDecodeCoefficientsBatch / hipjpegEncodeCoefficientsBatch: images on the GPU entropy decoder / coder; blocks the
+    // last of the four coefficient-tensor calls moved
     int32_t coefficients_gpu_decoded = 0, coefficients_gpu_coded = 0;
     int64_t coefficients_blocks = 0;
 };
@@ -919,6 +919,58 @@ hipjpegStatus_t hipjpegEncodeCoefficientsBatch(hipjpegHandle_t handle, const hip
         for (int i = 0; i < batch_size; i++) statuses[i] = e.image(i).status;
     handle->coefficients_gpu_coded = (int32_t)e.gpu_entropy_images();
     handle->coefficients_blocks = (int64_t)e.relayout_blocks();
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+hipjpegStatus_t hipjpegCoefficientsToPixelsBatch(hipjpegHandle_t handle, const hipjpegCoefficientInfo_t* infos, const hipjpegCoefficientPlanes_t* planes,
+                                                 int batch_size, const hipjpegOutput_t* outputs, hipjpegOutputFormat_t format, unsigned flags,
+                                                 hipjpegStatus_t* statuses, void* stream)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    // the transforms belong to this batch alone, whatever becomes of it
+    std::vector<hipjpegTransform_t> transforms;
+    transforms.swap(handle->transforms);
+    if (batch_size < 0 || (batch_size > 0 && (!infos || !planes || !outputs))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    // the call takes the current decode page for itself: nothing submitted may still be using it
+    if (handle->num_submitted != 0 || handle->encode_in_flight != 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (!transforms.empty() && (int)transforms.size() != batch_size) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    handle->coefficients_blocks = 0;
+    DecodeBatch& d = handle->cur();
+    hipjpegStatus_t st = d.plan_tensors(infos, planes, batch_size, outputs, format, flags, nullptr, handle->pool.get(),
+                                        transforms.empty() ? nullptr : transforms.data());
+    if (st != HIPJPEG_STATUS_SUCCESS) return st;
+    // no entropy stage: the statuses are final here; then descriptors and units, the relayout kernel, the pixel kernels
+    d.finalize(statuses);
+    if ((st = d.transfer(stream)) != HIPJPEG_STATUS_SUCCESS || (st = d.import_tensors(stream)) != HIPJPEG_STATUS_SUCCESS ||
+        (st = d.launch(stream)) != HIPJPEG_STATUS_SUCCESS) {
+        (void)hipStreamSynchronize((hipStream_t)stream);  // nothing of this batch stays queued behind an error
+        return st;
+    }
+    handle->coefficients_blocks = (int64_t)d.imported_blocks();
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+hipjpegStatus_t hipjpegPixelsToCoefficientsBatch(hipjpegHandle_t handle, const hipjpegEncodeInput_t* inputs, const hipjpegEncodeParams_t* params,
+                                                 int batch_size, const hipjpegCoefficientPlanes_t* planes, hipjpegStatus_t* statuses, void* stream)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle || batch_size < 0 || (batch_size > 0 && (!inputs || !params || !planes))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    // the call takes the encode batch for itself
+    if (handle->num_submitted != 0 || handle->encode_in_flight != 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    handle->coefficients_blocks = 0;
+    EncodeBatch& e = *handle->encode;
+    handle->encode_view = &e;
+    hipjpegStatus_t st = e.device_stage(inputs, params, batch_size, statuses, stream);
+    if (st == HIPJPEG_STATUS_SUCCESS) st = e.planes_stage(planes, statuses, stream);
+    if (st != HIPJPEG_STATUS_SUCCESS) {
+        (void)hipStreamSynchronize((hipStream_t)stream);  // nothing of this batch stays queued behind an error
+        return st;
+    }
+    handle->coefficients_blocks = (int64_t)e.planes_blocks();
     return HIPJPEG_STATUS_SUCCESS;
     });
 }

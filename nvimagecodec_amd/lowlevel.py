@@ -717,6 +717,25 @@ def coefficient_info(data):
     return _info_dict(ci)
 
 
+def _css(subsampling):
+    """hipjpegChromaSubsampling_t of a name or a value; a name the library does not know is HIPJPEG_CSS_UNKNOWN, which it refuses"""
+    if isinstance(subsampling, str):
+        return N.CSS.get(subsampling, -1)
+    return int(subsampling)
+
+
+def encode_coefficient_info(width, height, subsampling="420", quality=90):
+    """Host only (no GPU): the dict coefficient_info returns for the file BatchEncoder writes for a width x height picture with this
+    subsampling and quality -- what BatchCoefficients.from_pixels fills.  Raises HipJpegError: UNSUPPORTED for an unknown subsampling
+    (a name or a hipjpegChromaSubsampling_t value), INVALID_ARGUMENT for a size outside 1..65535."""
+    p = N.EncodeParams(int(quality), _css(subsampling), N.OUTPUT_RGBI, 0, 0, 0)
+    ci = N.CoefficientInfo()
+    st = N.load().hipjpegGetEncodeCoefficientInfo(int(width), int(height), ctypes.byref(p), ctypes.byref(ci))
+    if st:
+        raise N.HipJpegError(st, "hipjpegGetEncodeCoefficientInfo")
+    return _info_dict(ci)
+
+
 def _host_planes(coefs, what):
     """hipjpegCoefficientPlanes_t over numpy arrays [blocks_h, pitch >= blocks_w, 8, 8] (or [.., 64]) int16, C-contiguous"""
     P = N.CoefficientPlanes()
@@ -892,6 +911,129 @@ class BatchCoefficients:
             ok = statuses[i] == 0 and N.load().hipjpegEncodeGetBitstream(self._h, i, ctypes.byref(p), ctypes.byref(ln)) == 0
             files.append(ctypes.string_at(p, ln.value) if ok else None)
         return list(statuses), files
+
+    def _pixel_outputs(self, info, fmt, transform):
+        """what BatchDecoder.allocate_outputs allocates for a file of this geometry"""
+        torch = self._torch
+        dev = torch.device("cuda", self.device)
+        h, w = info["height"], info["width"]
+        if transform is not None:
+            roi, orientation = transform
+            if roi is not None:
+                w, h = roi[2] - roi[0], roi[3] - roi[1]
+            if orientation >= 5:
+                w, h = h, w
+        if fmt in ("rgb", "bgr"):
+            return torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+        if fmt in ("rgb_planar", "bgr_planar"):
+            return torch.empty((3, h, w), dtype=torch.uint8, device=dev)
+        if fmt == "y":
+            return torch.empty((h, w), dtype=torch.uint8, device=dev)
+        nc = min(info["num_components"], 3)
+        hs, vs = info.get("h", [1] * nc), info.get("v", [1] * nc)
+        hmax, vmax = max(hs[:nc]), max(vs[:nc])
+        return [torch.empty(((info["height"] * vs[c] + vmax - 1) // vmax, (info["width"] * hs[c] + hmax - 1) // hmax), dtype=torch.uint8, device=dev)
+                for c in range(nc)]
+
+    def to_pixels(self, images, fmt="rgb", fancy=True, fast_idct=False, outs=None, transforms=None, stream=None):
+        """images: CoefficientImage (or (info, coefs)) per picture.  Returns (statuses, outs): the pixels BatchDecoder.decode gives for
+        a file with these coefficients and tables, with no entropy stage and no file in between.  outs: the caller's outputs, or None to
+        have them allocated as BatchDecoder.allocate_outputs does for such a file (format, transforms).  transforms: per image None or
+        (roi, orientation).  Everything is queued on `stream` (default: the current one), behind whatever produced the tensors there;
+        nothing blocks, and the statuses are final."""
+        n = len(images)
+        I = (N.CoefficientInfo * max(n, 1))()
+        P = (N.CoefficientPlanes * max(n, 1))()
+        O = (N.Output * max(n, 1))()
+        infos = []
+        for i, im in enumerate(images):
+            info, coefs = (im.info, im.coefs) if isinstance(im, CoefficientImage) else im
+            I[i] = _info_struct(info)
+            nc = I[i].num_components
+            P[i] = self._planes(list(coefs)[:nc], list(I[i].blocks_h)[:nc], list(I[i].blocks_w)[:nc], f"to_pixels: image {i}")
+            infos.append(info)
+        if outs is None:
+            outs = [self._pixel_outputs(info, fmt, transforms[i] if transforms is not None else None) for i, info in enumerate(infos)]
+        for i, o in enumerate(outs):
+            if o is None:
+                continue
+            if fmt in ("rgb", "bgr", "y"):
+                O[i].plane[0], O[i].pitch[0] = o.data_ptr(), o.stride(0)
+            elif fmt in ("rgb_planar", "bgr_planar"):
+                for p in range(3):
+                    O[i].plane[p], O[i].pitch[p] = o[p].data_ptr(), o.stride(1)
+            else:
+                for p, t in enumerate(o):
+                    O[i].plane[p], O[i].pitch[p] = t.data_ptr(), t.stride(0)
+        if transforms is not None:
+            T = (N.Transform * max(n, 1))()
+            for i, t in enumerate(transforms):
+                T[i].orientation = 1
+                if t is not None:
+                    roi, orientation = t
+                    if roi is not None:
+                        T[i].x0, T[i].y0, T[i].x1, T[i].y1 = [int(v) for v in roi]
+                    T[i].orientation = int(orientation)
+            st = N.load().hipjpegDecodeBatchSetTransforms(self._h, T, n)
+            if st:
+                raise N.HipJpegError(st, "hipjpegDecodeBatchSetTransforms")
+        statuses = (ctypes.c_int * n)()
+        st = N.load().hipjpegCoefficientsToPixelsBatch(self._h, I, P, n, O, _FORMATS[fmt], _decode_flags(fancy, False, fast_idct), statuses,
+                                                       self._stream_ptr(stream))
+        if st:
+            raise N.HipJpegError(st, "hipjpegCoefficientsToPixelsBatch")
+        return list(statuses), outs
+
+    def from_pixels(self, images, subsampling="420", quality=90, input_format="rgb", outs=None, stream=None):
+        """images: torch CUDA uint8 tensors as BatchEncoder takes them ([H, W, 3] interleaved, [3, H, W] planar, [H, W] gray, or
+        [Y, Cb, Cr] for "yuv_planar").  subsampling / quality: one value for the batch or a list with one per image.  Returns (statuses,
+        images): images[i] is a CoefficientImage holding what BatchCoefficients.decode reads from the file BatchEncoder writes for the
+        same pixels and parameters, or None where statuses[i] != 0.  outs: per image None or a list of caller tensors to fill (as in
+        decode).  Everything is queued on `stream` (default: the current one); nothing blocks."""
+        n = len(images)
+        subs = subsampling if isinstance(subsampling, (list, tuple)) else [subsampling] * n
+        quals = quality if isinstance(quality, (list, tuple)) else [quality] * n
+        I = (N.EncodeInput * max(n, 1))()
+        E = (N.EncodeParams * max(n, 1))()
+        P = (N.CoefficientPlanes * max(n, 1))()
+        infos, tensors = [], []
+        for i, t in enumerate(images):
+            if input_format in ("rgb", "bgr"):
+                h, w = t.shape[0], t.shape[1]
+                I[i].plane[0], I[i].pitch[0] = t.data_ptr(), t.stride(0)
+            elif input_format == "gray":
+                h, w = t.shape
+                I[i].plane[0], I[i].pitch[0] = t.data_ptr(), t.stride(0)
+            elif input_format == "yuv_planar":
+                h, w = t[0].shape
+                for p in range(3):
+                    I[i].plane[p], I[i].pitch[p] = t[p].data_ptr(), t[p].stride(0)
+            else:
+                h, w = t.shape[1], t.shape[2]
+                for p in range(3):
+                    I[i].plane[p], I[i].pitch[p] = t[p].data_ptr(), t.stride(1)
+            I[i].width, I[i].height = w, h
+            E[i] = N.EncodeParams(int(quals[i]), _css(subs[i]), _IN_FORMATS[input_format], 0, 0, 0)
+            try:
+                info = encode_coefficient_info(w, h, subs[i], quals[i])
+            except N.HipJpegError:
+                infos.append(None)  # the batch call reports why; its planes stay null and are never looked at
+                tensors.append(None)
+                continue
+            o = outs[i] if outs is not None and outs[i] is not None else self.allocate(info)
+            if any(x is None for x in o):  # (a caller's list with a hole: the library refuses the image)
+                for c, x in enumerate(o):
+                    if x is not None:
+                        P[i].coef[c], P[i].pitch_blocks[c] = x.data_ptr(), x.stride(0) // 64
+            else:
+                P[i] = self._planes(o, info["blocks_h"], info["blocks_w"], f"from_pixels: image {i}")
+            infos.append(info)
+            tensors.append(o)
+        statuses = (ctypes.c_int * n)()
+        st = N.load().hipjpegPixelsToCoefficientsBatch(self._h, I, E, n, P, statuses, self._stream_ptr(stream))
+        if st:
+            raise N.HipJpegError(st, "hipjpegPixelsToCoefficientsBatch")
+        return list(statuses), [CoefficientImage(infos[i], tensors[i]) if statuses[i] == 0 else None for i in range(n)]
 
     def stats(self):
         d, c, b = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
