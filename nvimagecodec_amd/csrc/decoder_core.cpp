@@ -561,7 +561,7 @@ void DecodeBatch::size_image(int i, Sizing& s)
         const size_t nsub = (s.scan(sc, &q.raw_offset, &q.stream_offset, &q.first_chunk) * 8 + kSubseqBits - 1) / kSubseqBits;
         const size_t mcus = (size_t)scan_mcus_x(f, sc) * scan_mcus_y(f, sc);
         s.subseq += nsub;
-        max_huff_units_ += (nsub + kHuffOwn - 1) / kHuffOwn;
+        max_huff_units_ += std::max<size_t>((nsub + kHuffOwn - 1) / kHuffOwn, 1);  // (an empty stream keeps the unit at 0: it reports the image)
         q.pool_words = gpu_pool_words(sc);
         q.tables_offset = s.pools.take(align_up(q.pool_words * 2, 64), 1);
         max_pool_words_ = std::max(max_pool_words_, q.pool_words);
@@ -584,7 +584,6 @@ void DecodeBatch::layout(const Sizing& s)
     L.huff_units = c.take(sizeof(HuffUnit) * max_huff_units_);
     L.huff_wunits = c.take(sizeof(HuffUnit) * s.huff_wunits);
     L.huff_dc_units = c.take(sizeof(HuffUnit) * ng * 4);
-    L.huff_list = c.take(sizeof(uint32_t) * ng);
     L.huff_chunk_units = c.take(sizeof(HuffUnit) * chunks);
     L.huff_drops = c.take(sizeof(uint32_t) * chunks);
     L.xform_desc = c.take(sizeof(TransformImage) * xform_desc_.size());
@@ -636,6 +635,7 @@ void DecodeBatch::layout(const Sizing& s)
     scratch_.block_pos = w.take(s.block_pos.end);
     scratch_.records = w.take(total_subseq_ * kRecShorts * 2);  // block-start records: 64 bytes per subsequence
     scratch_.walkers = w.take(max_huff_units_ * 4);            // per sync unit: walks left to the position pass
+    scratch_.verdicts = w.take(verdict_bytes());               // what resolve() reads, where the kernels cannot store to the pinned side
     scratch_.drops = w.take(chunks * 4);
     scratch_.prog_pos = w.take(s.prog_pos.end);
     scratch_.group_sums = w.take(s.huff_wunits * 16);  // per block-pass workgroup: DC difference sums of its MCUs
@@ -652,7 +652,7 @@ hipjpegStatus_t DecodeBatch::reserve(const Sizing& s)
         in_flight_ = false;
     }
     hipjpegStatus_t st;
-    if ((st = pinned_.reserve(staging_.h2d_bytes + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
+    if ((st = pinned_.reserve(staging_.h2d_bytes + 256 + verdict_bytes())) != HIPJPEG_STATUS_SUCCESS) return st;
     if ((st = device_.reserve(staging_.total + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
     if ((st = planes_.reserve(s.planes.end + 256)) != HIPJPEG_STATUS_SUCCESS) return st;
     if (!huff_to_image_.empty() || s.prog_scans) return work_.reserve(scratch_.total + 256);
@@ -920,7 +920,6 @@ void DecodeBatch::build_pixel_units()
 void DecodeBatch::build_entropy_units()
 {
     for (std::vector<HuffUnit>* v : {&huff_units_, &huff_wunits_, &huff_chunk_units_, &huff_dc_units_, &prog_units_}) v->clear();
-    huff_list_.clear();
     uint32_t first_subseq = 0;
     stream_bytes_total_ = 0;
     huff_zero_.clear();
@@ -964,10 +963,10 @@ void DecodeBatch::build_entropy_units()
         }
         h.first_subseq = first_subseq;
         first_subseq += h.num_subseq;
-        for (uint32_t j = 0; j < h.num_subseq; j += kHuffOwn) huff_units_.push_back(HuffUnit{(uint32_t)g, j});
+        // (the unit at 0 also for an empty stream: its workgroup of the position kernel flags the image)
+        for (uint32_t j = 0; j == 0 || j < h.num_subseq; j += kHuffOwn) huff_units_.push_back(HuffUnit{(uint32_t)g, j});
         if (h.restart_interval)  // the predictor starts over inside the scan: the per-component scan (everything else: per MCU group)
             for (uint32_t i = 0; i < h.ncomp; i++) huff_dc_units_.push_back(HuffUnit{(uint32_t)g, i});
-        huff_list_.push_back((uint32_t)g);
         stream_bytes_total_ += q.stream_bytes;
     }
     merge_zero_fills();
@@ -1104,7 +1103,6 @@ void DecodeBatch::stage_tables()
     copy_table(pinned_, staging_.huff_units, huff_units_);
     copy_table(pinned_, staging_.huff_wunits, huff_wunits_);
     copy_table(pinned_, staging_.huff_dc_units, huff_dc_units_);
-    copy_table(pinned_, staging_.huff_list, huff_list_);
     copy_table(pinned_, staging_.huff_chunk_units, huff_chunk_units_);
 }
 
@@ -1200,9 +1198,14 @@ hipjpegStatus_t DecodeBatch::enqueue_gpu_entropy(void* stream)
         return HIPJPEG_STATUS_HIP_ERROR;
     if (launch_huff_sync(L.dimg, L.dunits, L.nunits, L.states, L.incoming, L.changed, 0, 1 << 20, nullptr, nullptr, L.records, L.pool_bytes, stream, 1) != 0)
         return HIPJPEG_STATUS_HIP_ERROR;
+    // The verdicts resolve() reads are stored by the stage's last kernel, into the pinned side itself: no copy command between the
+    // entropy kernels and the pixel kernels.  Pinned memory from a caller's allocator may not be mapped into the device's address
+    // space: the kernel stores to the scratch then and one copy follows.  (FUSED builds: the descriptors come back behind the pixel
+    // kernels, see launch().)
     if (!entropy_write_passes(L, stream)) return HIPJPEG_STATUS_HIP_ERROR;
-    if (hipMemcpyAsync(L.host_changed, L.changed, 8 * sizeof(unsigned int), hipMemcpyDeviceToHost, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-    if (hipMemcpyAsync(L.himg, L.dimg, sizeof(HuffImage) * huff_images_.size(), hipMemcpyDeviceToHost, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
+    if (L.verdicts_out != L.host_changed && hipMemcpyAsync(L.host_changed, L.verdicts_out, verdict_bytes(), hipMemcpyDeviceToHost, s) != hipSuccess)
+        return HIPJPEG_STATUS_HIP_ERROR;
+    if (fused_ && hipMemcpyAsync(L.himg, L.dimg, sizeof(HuffImage) * huff_images_.size(), hipMemcpyDeviceToHost, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
     entropy_pending_ = true;
     return HIPJPEG_STATUS_SUCCESS;
 }
@@ -1245,7 +1248,6 @@ DecodeBatch::EntropyLaunch DecodeBatch::entropy_launch_args()
     L.dunits = at<const HuffUnit>(device_, staging_.huff_units);
     L.dwunits = at<const HuffUnit>(device_, staging_.huff_wunits);
     L.ddc = at<const HuffUnit>(device_, staging_.huff_dc_units);
-    L.dlist = at<const uint32_t>(device_, staging_.huff_list);
     L.states = at<unsigned long long>(work_, 0);
     L.first_block = at<uint32_t>(work_, scratch_.first_block);
     // HIPJPEG_POSITION_PASS=1: the position pass walks every subsequence, as before the records (A/B aid).  So it does for a batch
@@ -1259,17 +1261,19 @@ DecodeBatch::EntropyLaunch DecodeBatch::entropy_launch_args()
     L.incoming = at<unsigned long long>(work_, scratch_.incoming);
     L.pool_bytes = (unsigned)align_up(max_pool_words_ * 2, 256);
     L.nunits = (int)huff_units_.size();
-    L.host_changed = at<unsigned int>(pinned_, staging_.h2d_bytes);  // 256 spare bytes behind the staged data
+    // behind the staged data, on the pinned side: the convergence counters, then a verdict word per HuffImage (huff_verdict())
+    L.host_changed = at<unsigned int>(pinned_, staging_.h2d_bytes);
+    L.verdicts = L.host_changed + kHuffVerdictCounters;
+    L.verdicts_out = pinned_.custom() ? at<unsigned int>(work_, scratch_.verdicts) : L.host_changed;
     L.himg = at<HuffImage>(pinned_, staging_.huff_desc);
     return L;
 }
 
 bool DecodeBatch::entropy_write_passes(const EntropyLaunch& L, void* stream)
 {
-    return launch_huff_scan(L.dimg, L.dlist, (int)huff_list_.size(), L.states, L.first_block, stream) == 0 &&
-           launch_huff_write(L.dimg, L.dunits, L.nunits, L.dwunits, (int)huff_wunits_.size(), L.states, L.first_block, L.use_records, L.walkers, L.group_sums, L.pool_bytes,
+    return launch_huff_write(L.dimg, L.dunits, L.nunits, L.dwunits, (int)huff_wunits_.size(), L.states, L.first_block, L.use_records, L.walkers, L.group_sums, L.pool_bytes,
                              stream, fused_) == 0 &&
-           launch_huff_dc(L.dimg, L.ddc, (int)huff_dc_units_.size(), L.dwunits, (int)huff_wunits_.size(), L.group_sums, stream) == 0;
+           launch_huff_dc(L.dimg, L.ddc, (int)huff_dc_units_.size(), L.dwunits, (int)huff_wunits_.size(), L.group_sums, L.changed, L.verdicts_out, stream) == 0;
 }
 
 hipjpegStatus_t DecodeBatch::wait_done()
@@ -1307,7 +1311,11 @@ hipjpegStatus_t DecodeBatch::resolve(void* stream)
     constexpr int kExtraRippleLaunches = 4;
     uint32_t last_pass = 1;
     std::vector<char> unsettled(huff_images_.size(), 0);
+    // the common case reads the verdict words the stage's last kernel left; the descriptors themselves are fetched where the write
+    // passes are repeated below (and by the FUSED builds, whose pixel kernels flag images too)
+    bool from_desc = fused_;
     if (!converged) {
+        from_desc = true;
         for (int pass = 0; pass < kExtraRippleLaunches && !converged; pass++) {
             if (hipMemsetAsync(L.changed, 0, sizeof(unsigned int), s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
             if (launch_huff_sync(L.dimg, L.dunits, L.nunits, L.states, L.incoming, L.changed, 0, 1 << 20, nullptr, nullptr, L.records, L.pool_bytes, stream, ++last_pass) != 0)
@@ -1332,7 +1340,8 @@ hipjpegStatus_t DecodeBatch::resolve(void* stream)
         if (hipStreamSynchronize(s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
         redo_pixels = true;
     } else {
-        for (size_t g = 0; g < huff_to_image_.size(); g++) unsettled[g] = L.himg[g].gave_up != 0;  // a group ran out of rounds in the tail kernel
+        // a group ran out of rounds in the tail kernel
+        for (size_t g = 0; g < huff_to_image_.size(); g++) unsettled[g] = from_desc ? L.himg[g].gave_up != 0 : huff_verdict_gave_up(L.verdicts[g]);
     }
     // The kernels could not vouch for a stream (corrupt / truncated data, a periodic stream): the host entropy decoder produces
     // either the coefficients or the precise error.
@@ -1340,7 +1349,8 @@ hipjpegStatus_t DecodeBatch::resolve(void* stream)
     std::vector<int> takeover;
     for (size_t g = 0; g < huff_to_image_.size(); g++) {
         const int i = huff_to_image_[g];
-        if (images_[i].status == HIPJPEG_STATUS_SUCCESS && (L.himg[g].status != 0 || unsettled[g]) && (takeover.empty() || takeover.back() != i))
+        const bool flagged = from_desc ? L.himg[g].status != 0 : huff_verdict_status(L.verdicts[g]) != 0;
+        if (images_[i].status == HIPJPEG_STATUS_SUCCESS && (flagged || unsettled[g]) && (takeover.empty() || takeover.back() != i))
             takeover.push_back(i);
     }
     host_fallback_images_ = (int)takeover.size();

@@ -194,15 +194,17 @@ private:
     uint64_t exported_blocks_ = 0;
     // Staging area, pinned and mirrored on the device at the same offsets:  descriptors | work units | entropy descriptors, units,
     // tables | staged bitstreams [streams, coef) | coefficients of host-decoded images  ||  (device only from h2d_bytes) coefficients of
-    // GPU-decoded images.  The pinned side keeps 256 spare bytes behind h2d_bytes (entropy_launch_args).
+    // GPU-decoded images.  The pinned side keeps 256 spare bytes and verdict_bytes() behind h2d_bytes (entropy_launch_args).
     struct StagingLayout {
-        size_t desc, units, huff_desc, huff_units, huff_wunits, huff_dc_units, huff_list, huff_chunk_units, huff_drops, xform_desc, xform_units,
+        size_t desc, units, huff_desc, huff_units, huff_wunits, huff_dc_units, huff_chunk_units, huff_drops, xform_desc, xform_units,
             prog_desc, prog_units, tensor_planes, tensor_units, tables, boundaries, streams, coef, h2d_bytes, gpu_coef_begin, total;
     } staging_{};
     // Device-only scratch of the entropy kernels (work_): subsequence states (at 0) | first block indices | change counters | ...
     struct WorkLayout {
-        size_t first_block, changed, incoming, tail, dc_diff, block_pos, records, walkers, drops, prog_pos, group_sums, streams, total;
+        size_t first_block, changed, incoming, tail, dc_diff, block_pos, records, walkers, verdicts, drops, prog_pos, group_sums, streams, total;
     } scratch_{};
+    // what resolve() reads of the GPU entropy stage: the convergence counters and one verdict word per sequential HuffImage
+    size_t verdict_bytes() const { return (kHuffVerdictCounters + huff_to_image_.size()) * sizeof(unsigned int); }
     Buffer work_;
     std::vector<PlannedImage> images_;
     std::vector<DecodeImage> desc_;  // host copy (device pointers inside)
@@ -233,7 +235,6 @@ private:
     // GPU entropy stage: one HuffImage per scan of the sequential images first, then one per scan of the progressive images
     std::vector<HuffImage> huff_images_;
     std::vector<HuffUnit> huff_units_, huff_dc_units_;
-    std::vector<uint32_t> huff_list_;
     std::vector<int> huff_to_image_;  // sequential HuffImage -> image
     int seq_gpu_images_ = 0;          // sequential images among them
     // blocks of GPU-decoded sequential pictures that no scan codes (padding of a one-component scan's grid): zeroed before the
@@ -257,7 +258,6 @@ private:
     struct EntropyLaunch {
         HuffImage* dimg;
         const HuffUnit *dunits, *dwunits, *ddc;
-        const uint32_t* dlist;
         unsigned long long *states, *incoming;
         uint32_t* first_block;
         uint16_t* records;       // block-start records of the synchronisation decodes
@@ -265,6 +265,8 @@ private:
         uint32_t* walkers;            // per sync unit: subsequences the position pass walks
         int32_t* group_sums;
         unsigned int *changed, *host_changed;
+        unsigned int* verdicts;      // pinned, behind host_changed's counters: huff_verdict() per HuffImage
+        unsigned int* verdicts_out;  // where the stage's last kernel stores counters and verdicts: host_changed itself, or the scratch
         HuffImage* himg;
         unsigned pool_bytes;
         int nunits;

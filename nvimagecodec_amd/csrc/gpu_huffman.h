@@ -37,20 +37,30 @@ int launch_destuff(HuffImage* images, const HuffUnit* chunk_units, int nchunks, 
 int launch_huff_sync(HuffImage* images, const HuffUnit* units, int nunits, unsigned long long* states, unsigned long long* incoming,
                      unsigned int* changed, int first_pass, int max_rounds, uint16_t* tail_tasks, uint32_t* tail_count, uint16_t* records,
                      unsigned pool_bytes, void* stream, unsigned pass_id = 0);
-int launch_huff_scan(HuffImage* images, const uint32_t* image_list, int nimages, const unsigned long long* states, uint32_t* first_block, void* stream);
-// Write pass: position kernel over the sync units, then the block kernel over block_units ({image, first MCU}, kHuffMcusPerWg
-// MCUs each).  A copy kernel puts every usable record into HuffImage::block_pos, and the position kernel walks only the other
-// subsequences: overflowed records, images with restart intervals; every subsequence when records == nullptr
-// (HIPJPEG_POSITION_PASS=1).  walkers: one uint32 per sync unit, between the two.
+// Write pass: the block positions over the sync units, then the block kernel over block_units ({image, first MCU}, kHuffMcusPerWg
+// MCUs each).  One kernel numbers the blocks (the block in progress where every subsequence begins: first_block, written for the
+// subsequences that are walked; HuffImage::decoded_blocks and the "stream ends before the last block" status) and puts every usable
+// record into HuffImage::block_pos; the position kernel behind it walks only the other subsequences: overflowed records, images with
+// restart intervals; every subsequence when records == nullptr (HIPJPEG_POSITION_PASS=1).  walkers: one uint32 per sync unit,
+// between the two.  Every image with a scan to decode needs a sync unit at subsequence 0, also when its stream is empty.
 // group_sums: four int32 per block unit -- the sums of the DC differences of its MCUs, per component (what the DC pass needs
 // from the groups in front of a group).
 // dc_only: the pixel kernels decode the blocks themselves (decode_kernels.hip FUSED builds); only the DC differences are read here.
 int launch_huff_write(HuffImage* images, const HuffUnit* sync_units, int nsync_units, const HuffUnit* block_units, int nblock_units,
-                      const unsigned long long* states, const uint32_t* first_block, const uint16_t* records, uint32_t* walkers,
+                      const unsigned long long* states, uint32_t* first_block, const uint16_t* records, uint32_t* walkers,
                       int32_t* group_sums, unsigned pool_bytes, void* stream, bool dc_only = false);
 // DC differences -> DC planes.  Images without restart intervals: one workgroup per block unit (its base = the sums of the
 // units in front of it); images with restart intervals: one workgroup per (image, component) in rst_units.
+// verdicts (nullptr: none): what the host reads of the stage, written by the first of these kernels -- kHuffVerdictCounters words of
+// `counters` (the sync launches' convergence counters), then huff_verdict() of every image that has a block unit: what the converged
+// path of resolve() needs, the status and gave_up (moved_pass matters only where the launches did not converge, and there the host
+// fetches the descriptors).  Memory the device
+// can store to: the host's pinned memory where it is mapped.
+constexpr int kHuffVerdictCounters = 8;
+constexpr uint32_t huff_verdict(uint32_t status, uint32_t gave_up) { return (status & 0xFFu) | (gave_up ? 0x100u : 0u); }
+constexpr uint32_t huff_verdict_status(uint32_t v) { return v & 0xFFu; }
+constexpr bool huff_verdict_gave_up(uint32_t v) { return (v & 0x100u) != 0; }
 int launch_huff_dc(const HuffImage* images, const HuffUnit* rst_units, int nrst_units, const HuffUnit* block_units, int nblock_units,
-                   const int32_t* group_sums, void* stream);
+                   const int32_t* group_sums, const unsigned int* counters, unsigned int* verdicts, void* stream);
 
 }  // namespace hipjpeg

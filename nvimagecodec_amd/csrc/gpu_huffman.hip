@@ -15,8 +15,8 @@
 // Kernels:
 //   huff_sync_kernel   pass 0 + workgroup-local synchronisation loop in LDS; publishes end states; counts the workgroups
 //                      whose LAST end state moved (the only state another workgroup consumes)
-//   huff_scan_kernel   per image: exclusive scan of completed-block counts -> first block index of every subsequence
-//   huff_copy_records_kernel  where every block starts: copies the records the last synchronisation decodes took
+//   huff_copy_records_kernel  where every block starts: first block index of every subsequence (sums and scans the completed-block
+//                      counts), then copies the records the last synchronisation decodes took
 //   huff_pos_kernel    walks from the converged states the subsequences without a usable record
 //   huff_blocks_kernel one lane per block: decode into LDS, store whole 128-byte lines (DC differences to a compact array);
 //                      two 256-lane teams per workgroup share one copy of the tables: 16 waves per CU
@@ -367,7 +367,8 @@ __global__ __launch_bounds__(kThreads) void destuff_count_kernel(const HuffImage
 }
 
 // (256 x 1080p: 94 us for 2,048 chunks, eight resident per CU.  The time is the chunks' work, not their number: two chunks per workgroup 147 us,
-// four 149.  Per CU and launch the LDS pipeline is busy 33 us -- 64 single-byte stores per lane -- and the vector ALUs 20.)
+// four 149.  Per CU and launch the LDS pipeline was busy 33 us -- 64 single-byte stores per lane then -- and the vector ALUs 20.  With the
+// loads in flight together 70 us; with the compaction in dwords 68, six resident per CU: profiles/entropy_residue/.)
 __global__ __launch_bounds__(kThreads) void destuff_compact_kernel(HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
                                                                    const uint32_t* __restrict__ drops, unsigned int* __restrict__ counters)
 {
@@ -420,18 +421,35 @@ __global__ __launch_bounds__(kThreads) void destuff_compact_kernel(HuffImage* __
     __syncthreads();
 
     const uint32_t off = chunk_begin + t * 64;
-    uint32_t m[16], x[16];
+    // The lane's 64 bytes, word by word: the mask of the bytes to drop, their count, and the word SQUEEZED -- its dropped bytes taken
+    // out, the kept ones packed to the bottom, zeros above them -- with the number of kept bytes in three bits of `kept`.  One code
+    // path for words with and without drops.  (The bytes behind the stream's end count as dropped in the squeeze, not in n.)
+    uint32_t x[16];
+    unsigned long long kept = 0;
     uint32_t n = 0, len = 0;
     if (off < raw_bytes) {
         len = min(64u, raw_bytes - off);
         const uint32_t pieces = (len + 15) / 16;
         uint32_t prev = t > 0 ? buf[(t - 1) * 17 + 15] >> 24 : before_chunk;
+#pragma unroll
         for (uint32_t i = 0; i < 16; i++) x[i] = i < pieces * 4 ? buf[t * 17 + i] : 0x01010101u;
         const uint32_t behind = pieces == 4 ? (t < kThreads - 1 ? buf[(t + 1) * 17] & 0xFFu : behind_chunk) : 0x01u;
+#pragma unroll
         for (uint32_t i = 0; i < 16; i++) {
-            m[i] = stuffed_mask(x[i], prev, i < 15 ? (x[i < 15 ? i + 1 : 15] & 0xFFu) : behind);
-            prev = x[i] >> 24;
-            n += __popc(m[i]);
+            uint32_t w = x[i];
+            uint32_t d = stuffed_mask(w, prev, i < 15 ? (x[i < 15 ? i + 1 : 15] & 0xFFu) : behind);
+            prev = w >> 24;
+            n += __popc(d);
+            if (len < 64) {  // the stream's last lane
+                const uint32_t in = len > i * 4 ? min(len - i * 4, 4u) : 0u;
+                if (in < 4) d |= 0x80808080u << (8 * in);
+            }
+            w = (d & 0x80000000u) ? (w & 0x00FFFFFFu) : w;
+            w = (d & 0x00800000u) ? ((w & 0xFFFFu) | ((w >> 8) & 0xFF0000u)) : w;
+            w = (d & 0x00008000u) ? ((w & 0xFFu) | ((w >> 8) & 0xFFFF00u)) : w;
+            w = (d & 0x00000080u) ? (w >> 8) : w;
+            x[i] = w;
+            kept |= (unsigned long long)(4 - __popc(d)) << (3 * i);
         }
     }
     // exclusive scan of the per-lane counts: inside the wave by shuffles, across the four waves through LDS
@@ -445,23 +463,34 @@ __global__ __launch_bounds__(kThreads) void destuff_compact_kernel(HuffImage* __
     uint32_t excl = incl - n;
     for (int w = 0; w < (t >> 6); w++) excl += wave_base[w];
     const uint32_t chunk_drops = wave_base[0] + wave_base[1] + wave_base[2] + wave_base[3];
-    // kept bytes of this lane -> LDS
+    // Kept bytes of this lane -> LDS, as aligned dwords: the squeezed words are appended to a register accumulator, which gives off a
+    // dword whenever it holds four bytes.  A lane's first dword can begin with the last bytes of the lanes in front: it goes out with
+    // zeros there.  What the accumulator holds at the end, fewer than four bytes, is stored byte by byte behind a barrier, into the dword
+    // that the next lane to fill one has written by then.  No two lanes store the same dword: a lane gives off a dword only once it is
+    // full, and the lanes in front of it have left that one to their byte stores.
     auto padded = [](uint32_t k) { return k + ((k >> 6) << 2); };
+    const uint32_t o0 = a + t * 64 - excl, cnt0 = o0 & 3;
+    uint32_t o = o0 & ~3u, cnt = cnt0;
+    unsigned long long acc = 0;
     if (len) {
-        uint32_t o = a + t * 64 - excl;
+#pragma unroll
         for (uint32_t i = 0; i < 16; i++) {
-            const uint32_t w = x[i], mask = m[i];
-            if (i * 4 + 4 <= len && mask == 0) {
-                bytes[padded(o)] = (uint8_t)w;
-                bytes[padded(o + 1)] = (uint8_t)(w >> 8);
-                bytes[padded(o + 2)] = (uint8_t)(w >> 16);
-                bytes[padded(o + 3)] = (uint8_t)(w >> 24);
+            acc |= (unsigned long long)x[i] << (8 * cnt);
+            cnt += (uint32_t)(kept >> (3 * i)) & 7u;
+            if (cnt >= 4) {
+                buf[(o >> 2) + (o >> 6)] = (uint32_t)acc;
+                acc >>= 32;
+                cnt -= 4;
                 o += 4;
-            } else {
-                for (uint32_t b = 0; b < 4; b++)
-                    if (i * 4 + b < len && !((mask >> (8 * b + 7)) & 1)) bytes[padded(o++)] = (uint8_t)(w >> (8 * b));
             }
         }
+    }
+    __syncthreads();
+    {  // what the accumulator still holds (in front of it the neighbours' bytes, if the lane never filled a dword)
+        const uint32_t from = o == (o0 & ~3u) ? cnt0 : 0u;
+#pragma unroll
+        for (uint32_t b = 0; b < 3; b++)
+            if (b >= from && b < cnt) bytes[padded(o + b)] = (uint8_t)((uint32_t)acc >> (8 * b));
     }
     __syncthreads();
     // LDS -> destination: whole dwords in the middle, single bytes at the ragged ends (neighbouring chunks share those dwords)
@@ -930,87 +959,98 @@ __global__ __launch_bounds__(kTailThreads, 5) void huff_tail_kernel(HuffImage* _
     }
 }
 
-// One workgroup per image: first_block[j] = sum of nblocks of subsequences before j.
-__global__ __launch_bounds__(kThreads) void huff_scan_kernel(HuffImage* __restrict__ images, const uint32_t* __restrict__ image_list,
-                                                             const unsigned long long* __restrict__ states, uint32_t* __restrict__ first_block)
-{
-    __shared__ uint32_t s_sum[kThreads];
-    HuffImage& im = images[image_list[blockIdx.x]];
-    const unsigned long long* st = states + im.first_subseq;
-    uint32_t* fb = first_block + im.first_subseq;
-    const uint32_t n = (im.total_bits + kSubseqBits - 1) / kSubseqBits;
-    const uint32_t per = (n + kThreads - 1) / kThreads;
-    const uint32_t lo = min(n, threadIdx.x * per), hi = min(n, lo + per);
-    constexpr int kBatch = 8;  // independent loads in flight per lane
-    uint32_t sum = 0;
-    for (uint32_t i = lo; i < hi; i += kBatch) {
-        uint32_t d[kBatch];
-#pragma unroll
-        for (int k = 0; k < kBatch; k++) d[k] = i + k < hi ? (uint32_t)(st[i + k] >> 48) : 0u;
-#pragma unroll
-        for (int k = 0; k < kBatch; k++) sum += d[k];
-    }
-    s_sum[threadIdx.x] = sum;
-    __syncthreads();
-    // Hillis-Steele inclusive scan over 256 partial sums
-    for (int off = 1; off < kThreads; off <<= 1) {
-        uint32_t v = threadIdx.x >= (unsigned)off ? s_sum[threadIdx.x - off] : 0;
-        __syncthreads();
-        s_sum[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = threadIdx.x ? s_sum[threadIdx.x - 1] : 0;
-    for (uint32_t i = lo; i < hi; i++) {
-        fb[i] = run;
-        run += (uint32_t)(st[i] >> 48);
-    }
-    if (threadIdx.x == kThreads - 1) {
-        im.decoded_blocks = s_sum[kThreads - 1];
-        if (s_sum[kThreads - 1] < im.total_blocks) im.status = 2;  // the stream ends before the last block
-    }
-}
-
 // ---- write pass, step 1: where the blocks start -----------------------------------------------------------------------------
-// Records first: one lane per subsequence (the sync units, lane 0 idles) takes its usable record -- the last synchronisation
-// decode took it, from the converged start state; walkers[unit] = how many lanes of the unit have none (overflow, or an image
-// with restart intervals: their damage check is in the walk).  When every lane has one, the records of the unit name one
-// contiguous run of blocks: they are gathered in LDS and leave as consecutive dwords (stored straight from the lanes, a wave's
-// stores would touch a cache line per lane).
+// One lane per subsequence (the sync units, lane 0 idles).  First the number of the block in progress where the lane's subsequence
+// begins: the completed-block counts (SubseqState::nblocks, the top 16 bits of a state) of the image's subsequences in front of the
+// unit, which every workgroup sums for itself -- at most one image's states, all of a lane's loads in flight together -- plus a scan
+// of the unit's own counts.  No workgroup waits for another.  (The sums in front cost an image of n subsequences n * n / 510 two-byte
+// loads in all: 33 k for a 1080p photograph's 4,096, cached; a single scan of 100 MB, 800 k subsequences, would pay a billion --
+// from some tens of thousands of subsequences on, the sums belong in a pass of their own again.)  The workgroup that holds the image's last subsequence knows how many
+// blocks the stream completes: it writes decoded_blocks and flags a stream that ends before the last block.
+// Then the records: a lane takes its usable record -- the last synchronisation decode took it, from the converged start state;
+// walkers[unit] = how many lanes of the unit have none (overflow, an image with restart intervals: their damage check is in the
+// walk, or records == nullptr: HIPJPEG_POSITION_PASS=1); those get first_block[] for huff_pos_kernel.  When every lane has one, the
+// records of the unit name one contiguous run of blocks: they are gathered in LDS and leave as consecutive dwords (stored straight
+// from the lanes, a wave's stores would touch a cache line per lane).
 constexpr int kCopyCapacity = kHuffOwn * kRecSlots;  // blocks the records of a unit can name
+constexpr int kSyncWaves = kSyncThreads / 64;
 __global__ __launch_bounds__(kSyncThreads) void huff_copy_records_kernel(HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
-                                                                     const uint32_t* __restrict__ first_block, const uint16_t* __restrict__ records,
-                                                                     uint32_t* __restrict__ walkers)
+                                                                     const unsigned long long* __restrict__ states, uint32_t* __restrict__ first_block,
+                                                                     const uint16_t* __restrict__ records, uint32_t* __restrict__ walkers)
 {
     __shared__ uint32_t s_pos[kCopyCapacity];
     __shared__ uint32_t s_range[2];  // first block of the run, block behind it
+    __shared__ uint32_t s_front[kSyncWaves], s_own[kSyncWaves];
     const HuffUnit u = units[blockIdx.x];
     HuffImage& im = images[u.image];
     const uint32_t nsub = (im.total_bits + kSubseqBits - 1) / kSubseqBits;
     const int t = threadIdx.x;
     const uint32_t j = u.first - 1 + t;
     const bool owner = t != 0 && j < nsub;
+    const uint32_t g = im.first_subseq + j;
+    // the counts: little-endian states, nblocks in bits 48..63 = the fourth uint16
+    const HJ_GLOBAL uint16_t* counts = (const HJ_GLOBAL uint16_t*)(states + im.first_subseq) + 3;
+    const uint32_t nfront = min(u.first, nsub);
+    uint32_t front = 0;
+    constexpr int kBatch = 8;  // independent loads in flight per lane
+    for (uint32_t i0 = t; i0 < nfront; i0 += kBatch * kSyncThreads) {
+        uint32_t d[kBatch];
+#pragma unroll
+        for (int k = 0; k < kBatch; k++) {
+            const uint32_t i = i0 + k * kSyncThreads;
+            d[k] = i < nfront ? counts[(size_t)i * 4] : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < kBatch; k++) front += d[k];
+    }
+    const uint32_t own = owner ? counts[(size_t)j * 4] : 0u;
     bool walk = owner;
-    uint32_t n = 0, b0 = 0;
+    uint32_t n = 0, fresh = 0;
     u32x4 v[kRecShorts / 8];
-    if (owner && im.restart_interval == 0) {
+    if (owner && records && im.restart_interval == 0) {
         // the whole record in one go (64 bytes: four 16-byte loads in flight together), the mark last
-        const uint32_t g = im.first_subseq + j;
         const HJ_GLOBAL u32x4* src = (const HJ_GLOBAL u32x4*)records + (size_t)g * (kRecShorts / 8);
 #pragma unroll
         for (int q = 0; q < kRecShorts / 8; q++) v[q] = src[q];
         const uint32_t mark = v[kRecShorts / 8 - 1].w >> 16;
         if (mark_valid(mark)) {
-            // the record's blocks are consecutive: the one in progress at the start (first_block) if fresh, else the next one
             walk = false;
             n = mark & (kRecFresh - 1u);
-            b0 = first_block[g] + ((mark & kRecFresh) ? 0u : 1u);
+            fresh = mark & kRecFresh;
         }
     }
+    // wave sums of the counts in front, inclusive wave scans of the own counts; the rest through LDS
+    for (int off = 32; off > 0; off >>= 1) front += __shfl_xor(front, off);
+    uint32_t incl = own;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t x = __shfl_up(incl, d);
+        if ((t & 63) >= d) incl += x;
+    }
+    if ((t & 63) == 63) {
+        s_front[t >> 6] = front;
+        s_own[t >> 6] = incl;
+    }
     const int n_walk = __syncthreads_count(walk);
+    uint32_t fb = incl - own;  // the block in progress where subsequence j begins
+#pragma unroll
+    for (int w = 0; w < kSyncWaves; w++) fb += s_front[w] + (w < (t >> 6) ? s_own[w] : 0u);
     if (t == 0) walkers[blockIdx.x] = (uint32_t)n_walk;
+    const uint32_t total_blocks = im.total_blocks;
+    {
+        // the image's last subsequence (a stream without a bit: the unit at 0, its lane 0)
+        const uint32_t last_sub = nsub ? nsub - 1 : 0u;
+        if (nsub ? j == last_sub && t != 0 : u.first == 0 && t == 0) {
+            const uint32_t decoded = fb + own;
+            im.decoded_blocks = decoded;
+            if (decoded < total_blocks) im.status = 2;  // the stream ends before the last block
+        }
+    }
     if (u.first >= nsub) return;  // uniform: no subsequence here
+    if (walk) first_block[g] = fb;
+    // the record's blocks are consecutive: the one in progress at the start if fresh, else the next one
+    const uint32_t b0 = fb + (fresh ? 0u : 1u);
     HJ_GLOBAL uint32_t* out = (HJ_GLOBAL uint32_t*)im.block_pos;
-    const uint32_t total_blocks = im.total_blocks, bit0 = j * kSubseqBits;
+    const uint32_t bit0 = j * kSubseqBits;
     auto slot = [&](int i) { return bit0 + ((v[i >> 3][(i >> 1) & 3] >> (16 * (i & 1))) & 0xFFFFu); };
     if (n_walk == 0) {
         // uniform: lane 1 holds the first block of the run, the last owner the block behind it (unsettled streams -- the host
@@ -1039,6 +1079,9 @@ __global__ __launch_bounds__(kSyncThreads) void huff_copy_records_kernel(HuffIma
 // Then the walks, same workgroup shape: every lane whose subsequence has no usable record walks it from the converged start state
 // and records the bit position of each block that starts inside it.  A workgroup without such lanes leaves at once.
 // records == nullptr: every subsequence is walked (HIPJPEG_POSITION_PASS=1).
+// A launch of its own, behind every batch (which records overflowed only the device knows): the walk's registers (97, four waves per
+// SIMD) and its LDS (the staged rows and tables, 50 KB) inside huff_copy_records_kernel would take that kernel from five resident
+// workgroups per CU to three.
 __global__ __launch_bounds__(kSyncThreads) void huff_pos_kernel(HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
                                                             const unsigned long long* __restrict__ states, const uint32_t* __restrict__ first_block,
                                                             const uint16_t* __restrict__ records, const uint32_t* __restrict__ walkers)
@@ -1355,13 +1398,23 @@ __global__ __launch_bounds__(kThreads) void huff_dcdiff_kernel(HuffImage* __rest
 // Images without restart intervals: one workgroup per block-pass unit (kHuffMcusPerWg MCUs).  The predictor value a group
 // starts from is the sum of the group sums in front of it (the block pass left them: a few dozen numbers), so every group
 // integrates its own MCUs without waiting for anybody; wave c takes component c and scans its entries 64 at a time.
+//
+// This is the last kernel of the stage that every image passes, and nothing behind it changes a verdict: the group at an image's MCU 0
+// reports the image (huff_verdict(): status, gave_up), the first workgroup the stage's convergence counters, into
+// `verdicts` -- the host's pinned memory where that is mapped (kHuffVerdictCounters words of counters, then a word per image), so that
+// no copy command has to follow the stage.
 __global__ __launch_bounds__(kThreads) void huff_dc_group_kernel(const HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
-                                                                 const int32_t* __restrict__ group_sums)
+                                                                 const int32_t* __restrict__ group_sums, const unsigned int* __restrict__ counters,
+                                                                 unsigned int* __restrict__ verdicts)
 {
     __shared__ int16_t s_diff[kHuffMcusPerWg * 10];
     __shared__ int s_base[4];
     const HuffUnit u = units[blockIdx.x];  // first = first MCU of the group
     const HuffImage& im = images[u.image];
+    if (verdicts) {
+        if (blockIdx.x == 0 && threadIdx.x < kHuffVerdictCounters) verdicts[threadIdx.x] = counters[threadIdx.x];
+        if (u.first == 0 && threadIdx.x == 64) verdicts[kHuffVerdictCounters + u.image] = huff_verdict(im.status, im.gave_up);
+    }
     if (im.restart_interval != 0) return;  // uniform: huff_dc_kernel takes those
     const int t = threadIdx.x;
     const uint32_t bpm = im.blocks_per_mcu;
@@ -1544,21 +1597,13 @@ int launch_huff_sync(HuffImage* images, const HuffUnit* units, int nunits, unsig
     return (int)hipGetLastError();
 }
 
-int launch_huff_scan(HuffImage* images, const uint32_t* image_list, int nimages, const unsigned long long* states, uint32_t* first_block, void* stream)
-{
-    if (nimages <= 0) return 0;
-    hipLaunchKernelGGL(huff_scan_kernel, dim3(nimages), dim3(kThreads), 0, (hipStream_t)stream, images, image_list, states, first_block);
-    return (int)hipGetLastError();
-}
-
 int launch_huff_write(HuffImage* images, const HuffUnit* sync_units, int nsync_units, const HuffUnit* block_units, int nblock_units,
-                      const unsigned long long* states, const uint32_t* first_block, const uint16_t* records, uint32_t* walkers, int32_t* group_sums,
+                      const unsigned long long* states, uint32_t* first_block, const uint16_t* records, uint32_t* walkers, int32_t* group_sums,
                       unsigned pool_bytes, void* stream, bool dc_only)
 {
     if (nsync_units <= 0) return 0;
-    if (records)
-        hipLaunchKernelGGL(huff_copy_records_kernel, dim3(nsync_units), dim3(kSyncThreads), 0, (hipStream_t)stream, images, sync_units, first_block, records,
-                           walkers);
+    hipLaunchKernelGGL(huff_copy_records_kernel, dim3(nsync_units), dim3(kSyncThreads), 0, (hipStream_t)stream, images, sync_units, states, first_block,
+                       records, walkers);
     hipLaunchKernelGGL(huff_pos_kernel, dim3(nsync_units), dim3(kSyncThreads), pool_bytes, (hipStream_t)stream, images, sync_units, states, first_block,
                        records, walkers);
     if (nblock_units > 0) {
@@ -1572,10 +1617,11 @@ int launch_huff_write(HuffImage* images, const HuffUnit* sync_units, int nsync_u
 }
 
 int launch_huff_dc(const HuffImage* images, const HuffUnit* rst_units, int nrst_units, const HuffUnit* block_units, int nblock_units,
-                   const int32_t* group_sums, void* stream)
+                   const int32_t* group_sums, const unsigned int* counters, unsigned int* verdicts, void* stream)
 {
     if (nblock_units > 0)
-        hipLaunchKernelGGL(huff_dc_group_kernel, dim3(nblock_units), dim3(kThreads), 0, (hipStream_t)stream, images, block_units, group_sums);
+        hipLaunchKernelGGL(huff_dc_group_kernel, dim3(nblock_units), dim3(kThreads), 0, (hipStream_t)stream, images, block_units, group_sums, counters,
+                           verdicts);
     if (nrst_units > 0) hipLaunchKernelGGL(huff_dc_kernel, dim3(nrst_units), dim3(kThreads), 0, (hipStream_t)stream, images, rst_units);
     return (int)hipGetLastError();
 }

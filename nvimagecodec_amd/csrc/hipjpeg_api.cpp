@@ -54,6 +54,7 @@ struct hipjpegHandle {
     int pages = 3;
     std::unique_ptr<DecodeBatch> batches[kMaxPages];
     int current = 0;
+    int settled = -1;  // page whose batch the last Wait settled, until the next batch is planned (hipjpegTestHostFallbacks)
     DecodeBatch& cur() { return *batches[current]; }
     // pipelined submission (hipjpegDecodeBatchSubmit / Wait): pages in flight, oldest first, with the stream each runs on
     std::vector<hipjpegTransform_t> transforms;  // geometry for the next batch (hipjpegDecodeBatchSetTransforms)
@@ -303,6 +304,7 @@ hipjpegStatus_t hipjpegDecodeBatchHost(hipjpegHandle_t handle, const uint8_t* co
     return guarded([&]() -> hipjpegStatus_t {
     if (!handle) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     handle->current = (handle->current + 1) % handle->pages;
+    handle->settled = -1;
     DecodeBatch& b = handle->cur();
     static const bool timing = getenv("HIPJPEG_DEBUG_TIMING") != nullptr;  // debug aid: host-stage phase times on stderr
     const auto t0 = std::chrono::steady_clock::now();
@@ -456,6 +458,7 @@ hipjpegStatus_t hipjpegSetPipelineDepth(hipjpegHandle_t handle, int depth)
     if (!handle || depth < 1 || depth > hipjpegHandle::kMaxPages || handle->num_submitted != 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     handle->pages = depth;
     handle->current = 0;
+    handle->settled = -1;
     return HIPJPEG_STATUS_SUCCESS;
     });
 }
@@ -465,6 +468,7 @@ hipjpegStatus_t hipjpegDecodeBatchWait(hipjpegHandle_t handle, hipjpegStatus_t* 
     return guarded([&]() -> hipjpegStatus_t {
     if (!handle || handle->num_submitted == 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     DecodeBatch& b = *handle->batches[handle->submitted[0]];
+    handle->settled = handle->submitted[0];
     void* stream = handle->submitted_stream[0];
     if (statuses && batch_size != b.size()) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     for (int k = 1; k < handle->num_submitted; k++) {
@@ -532,7 +536,9 @@ int32_t hipjpegTestScanChunkDrops(const uint8_t* data, size_t length, int scan_i
 
 int32_t hipjpegTestHostFallbacks(hipjpegHandle_t handle)
 {
-    return handle && test_hooks_enabled() ? handle->cur().host_fallback_images() : -1;
+    // the batch the last Wait settled, if no batch has been planned since; else the current page's
+    if (!handle || !test_hooks_enabled()) return -1;
+    return handle->batches[handle->settled >= 0 ? handle->settled : handle->current]->host_fallback_images();
 }
 
 hipjpegStatus_t hipjpegTestKernelFlavours(hipjpegHandle_t handle, int32_t plane_units[1], int32_t luma_units[3])

@@ -1,4 +1,6 @@
-"""Profiling driver (dev tool): one 256x1080p batch, GPU entropy stage run N times.  Run under rocprofv3."""
+"""Profiling driver (dev tool): one 256x1080p batch, GPU entropy stage run N times.  Run under rocprofv3.
+usage: prof_gh.py [N [batch [steps]]] -- with `steps` every repetition is the bench's step (entropy stage enqueued, K1, K2) instead of
+the entropy stage with its verdicts read back: the timeline between the stage's last kernel and the first pixel kernel."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -13,7 +15,12 @@ outs = dec.allocate_outputs(jpegs)
 dec.host_stage(jpegs, outs, gpu_huffman=True)
 dec.transfer()
 torch.cuda.synchronize()
+steps = len(sys.argv) > 3 and sys.argv[3] == "steps"
 for _ in range(n):
-    dec.device_stage(which=3)
+    if steps:
+        for which in (6, 0, 1):
+            dec.device_stage(which=which)
+    else:
+        dec.device_stage(which=3)
 torch.cuda.synchronize()
 print("done", dec.stats())
