@@ -286,26 +286,38 @@ __global__ __launch_bounds__(kThreads) void gather_raw_kernel(const HuffImage* _
 // ---- byte-stuffing removal ------------------------------------------------------------------------------------------
 // The file's entropy-coded segment escapes every 0xFF data byte as FF 00.  Two kernels turn it into the plain bitstream the
 // decoders read: the first counts the stuffed bytes of every 16 KB chunk, the second compacts each chunk to its final
-// position (chunk offset minus the stuffed bytes before it) through LDS.  Streams with anything else behind an FF (restart
-// markers, fill bytes) never get here (gpu_entropy_eligible()).
+// position (chunk offset minus the stuffed bytes before it) through LDS.  Fill bytes (FF FF) never get here (gpu_entropy_eligible()).
+// Restart markers do, in images with a restart interval and only there: the parser notes every FF D0..D7 of a scan (ScanWalk::visit,
+// rst_after), and a scan whose markers are not exactly the ones its restart interval calls for -- none without an interval -- is not
+// eligible.  So an image without a restart interval has nothing but FF 00 to drop, which is what the parser counted for it
+// (ScanHeader::chunk_drops), and its chunks take the mask of the stuffed zeros alone: one byte test per word instead of five.
 
-// 0x80 in every byte of x (little-endian dword) that is 0x00 and whose predecessor byte is 0xFF; prev = the byte before x.
 __device__ __forceinline__ uint32_t zero_bytes(uint32_t v) { return ~(((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v | 0x7F7F7F7Fu); }  // 0x80 per zero byte
 
-// Bytes of x to drop: a 0x00 behind an 0xFF (stuffing), and both bytes of a restart marker FF D0..D7.  prev = the byte in
-// front of x, next = the byte behind it.
-__device__ __forceinline__ uint32_t stuffed_mask(uint32_t x, uint32_t prev, uint32_t next)
+// 0x80 in every byte of x (little-endian dword) that is 0x00 and whose predecessor byte is 0xFF; prev = the byte in front of x.
+// (A byte is 0x00 behind 0xFF exactly where "the byte, or its predecessor's complement" is zero: one byte test for both conditions.)
+__device__ __forceinline__ uint32_t stuffed_zero_mask(uint32_t x, uint32_t prev) { return zero_bytes(x | ~((x << 8) | prev)); }
+
+// 0x80 in both bytes of every restart marker FF D0..D7 that has a byte in x; prev = the byte in front of x, next = the byte behind it.
+__device__ __forceinline__ uint32_t marker_mask(uint32_t x, uint32_t prev, uint32_t next)
 {
-    const uint32_t ff_before = zero_bytes(~((x << 8) | prev));        // predecessor is 0xFF
+    const uint32_t ff_x = zero_bytes(~x);                                // x's byte is 0xFF
     const uint32_t rst_x = zero_bytes((x & 0xF8F8F8F8u) ^ 0xD0D0D0D0u);  // x's byte is D0..D7
-    const uint32_t second = (zero_bytes(x) | rst_x) & ff_before;      // stuffed zero, or the marker's second byte
-    const uint32_t after = (x >> 8) | (next << 24);                   // successor of each byte
-    const uint32_t first = zero_bytes(~x) & zero_bytes((after & 0xF8F8F8F8u) ^ 0xD0D0D0D0u);  // an FF in front of D0..D7
-    return second | first;
+    const uint32_t ff_before = (ff_x << 8) | (prev == 0xFFu ? 0x80u : 0u);
+    const uint32_t after = (x >> 8) | (next << 24);                      // successor of each byte
+    return (rst_x & ff_before) | (ff_x & zero_bytes((after & 0xF8F8F8F8u) ^ 0xD0D0D0D0u));
+}
+
+// Bytes of x to drop: a 0x00 behind an 0xFF (stuffing) and, with `markers` (images with a restart interval), both bytes of a restart
+// marker.
+__device__ __forceinline__ uint32_t stuffed_mask(uint32_t x, uint32_t prev, uint32_t next, bool markers)
+{
+    const uint32_t d = stuffed_zero_mask(x, prev);
+    return markers ? d | marker_mask(x, prev, next) : d;
 }
 
 // stuffed-byte masks of the 64 bytes at p (16-byte aligned); returns the count
-__device__ __forceinline__ uint32_t lane_masks(const uint8_t* p, bool has_prev, uint32_t m[16], uint32_t x[16])
+__device__ __forceinline__ uint32_t lane_masks(const uint8_t* p, bool has_prev, bool markers, uint32_t m[16], uint32_t x[16])
 {
     const uint4* q = reinterpret_cast<const uint4*>(p);
     uint32_t prev = has_prev ? p[-1] : 0u;
@@ -321,7 +333,7 @@ __device__ __forceinline__ uint32_t lane_masks(const uint8_t* p, bool has_prev, 
     const uint32_t behind = p[64];  // the raw copy is padded with 16 neutral bytes: always readable
 #pragma unroll
     for (int i = 0; i < 16; i++) {
-        m[i] = stuffed_mask(x[i], prev, i < 15 ? (x[i < 15 ? i + 1 : 15] & 0xFFu) : behind);
+        m[i] = stuffed_mask(x[i], prev, i < 15 ? (x[i < 15 ? i + 1 : 15] & 0xFFu) : behind, markers);
         prev = x[i] >> 24;
         n += __popc(m[i]);
     }
@@ -346,18 +358,19 @@ __global__ __launch_bounds__(kThreads) void destuff_count_kernel(const HuffImage
     const HuffUnit u = units[blockIdx.x];
     const HuffImage& im = images[u.image];
     const uint32_t off = u.first * kDestuffChunk + threadIdx.x * 64;
+    const bool markers = im.restart_interval != 0;  // (the compact kernel's rule)
     uint32_t n = 0;
     if (off < im.raw_bytes) {  // the raw copy is padded to 16 bytes with a neutral value; whole 16-byte pieces are readable
         uint32_t m[16], x[16];
         const uint32_t pieces = min(4u, (im.raw_bytes - off + 15) / 16);
         if (pieces == 4) {
-            n = lane_masks(im.raw + off, off > 0, m, x);
+            n = lane_masks(im.raw + off, off > 0, markers, m, x);
         } else {
             uint32_t prev = off > 0 ? im.raw[off - 1] : 0u;
             const uint32_t* words = reinterpret_cast<const uint32_t*>(im.raw + off);  // 16 neutral bytes of padding follow the data
             for (uint32_t i = 0; i < pieces * 4; i++) {
                 const uint32_t w = words[i];
-                n += __popc(stuffed_mask(w, prev, words[i + 1] & 0xFFu));
+                n += __popc(stuffed_mask(w, prev, words[i + 1] & 0xFFu, markers));
                 prev = w >> 24;
             }
         }
@@ -368,7 +381,10 @@ __global__ __launch_bounds__(kThreads) void destuff_count_kernel(const HuffImage
 
 // (256 x 1080p: 94 us for 2,048 chunks, eight resident per CU.  The time is the chunks' work, not their number: two chunks per workgroup 147 us,
 // four 149.  Per CU and launch the LDS pipeline was busy 33 us -- 64 single-byte stores per lane then -- and the vector ALUs 20.  With the
-// loads in flight together 70 us; with the compaction in dwords 68, six resident per CU: profiles/entropy_residue/.)
+// loads in flight together 70 us; with the compaction in dwords 68, six resident per CU: profiles/entropy_residue/.  That version
+// issued 1,544 vector instructions per lane, which is what its time was.  With the mask of the stuffed zeros alone for images
+// without a restart interval, one byte permute for the squeeze and a one-register accumulator about 900 of 1,172 run: 51 us, 61
+// registers, eight resident per CU: profiles/entropy_residue2/.)
 __global__ __launch_bounds__(kThreads) void destuff_compact_kernel(HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
                                                                    const uint32_t* __restrict__ drops, unsigned int* __restrict__ counters)
 {
@@ -382,11 +398,25 @@ __global__ __launch_bounds__(kThreads) void destuff_compact_kernel(HuffImage* __
     // neighbour the next 64, and without the padding the lanes of a wave would all hit the same two banks (round 2's version did: 55 % of
     // its LDS cycles were bank conflicts, and its global loads touched 64 lines per instruction).
     __shared__ uint32_t buf[kDestuffChunk / 4 + kDestuffChunk / 64 + 8];
+    // squeeze_sel[m]: the byte selector (v_perm_b32) that takes the bytes whose bit is set in m out of a word, packs the others to the
+    // bottom and puts zeros above them (selector byte 0x0C)
+    __shared__ uint32_t squeeze_sel[16];
     HJ_LDS uint8_t* bytes = (HJ_LDS uint8_t*)buf;
     const HuffUnit u = units[blockIdx.x];
     HuffImage& im = images[u.image];
     const int t = threadIdx.x;
+    if (t < 16) {
+        uint32_t sel = 0x0C0C0C0Cu, j = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < 4; b++)
+            if (!((uint32_t)t >> b & 1u)) {
+                sel = (sel & ~(0xFFu << (8 * j))) | (b << (8 * j));
+                j++;
+            }
+        squeeze_sel[t] = sel;
+    }
     const uint32_t raw_bytes = im.raw_bytes;
+    const bool markers = im.restart_interval != 0;  // workgroup-uniform: see the comment above zero_bytes()
     // stuffed bytes in the chunks before this one
     uint32_t before = 0;
     for (uint32_t c = t; c < u.first; c += kThreads) before += drops[im.first_chunk + c];
@@ -422,34 +452,44 @@ __global__ __launch_bounds__(kThreads) void destuff_compact_kernel(HuffImage* __
 
     const uint32_t off = chunk_begin + t * 64;
     // The lane's 64 bytes, word by word: the mask of the bytes to drop, their count, and the word SQUEEZED -- its dropped bytes taken
-    // out, the kept ones packed to the bottom, zeros above them -- with the number of kept bytes in three bits of `kept`.  One code
-    // path for words with and without drops.  (The bytes behind the stream's end count as dropped in the squeeze, not in n.)
+    // out, the kept ones packed to the bottom, zeros above them: one byte permute, its selector looked up by the mask's four bits -- with
+    // eight times the number of dropped bytes (bits of a shift) in six bits of `gone`.  One code path for words with and without
+    // drops.  The stream's last lane squeezes the neutral bytes behind the stream's end like data: they land behind the last kept byte,
+    // inside the buffer (a lane never stores more than its 64 bytes), where no lane has bytes of its own and the copy-out, which goes
+    // by the counts, does not look.
     uint32_t x[16];
-    unsigned long long kept = 0;
+    uint32_t gone[4] = {0, 0, 0, 0};  // five words each
     uint32_t n = 0, len = 0;
     if (off < raw_bytes) {
         len = min(64u, raw_bytes - off);
         const uint32_t pieces = (len + 15) / 16;
-        uint32_t prev = t > 0 ? buf[(t - 1) * 17 + 15] >> 24 : before_chunk;
+        const uint32_t before_lane = t > 0 ? buf[(t - 1) * 17 + 15] >> 24 : before_chunk;
 #pragma unroll
         for (uint32_t i = 0; i < 16; i++) x[i] = i < pieces * 4 ? buf[t * 17 + i] : 0x01010101u;
-        const uint32_t behind = pieces == 4 ? (t < kThreads - 1 ? buf[(t + 1) * 17] & 0xFFu : behind_chunk) : 0x01u;
+        uint32_t d[16];
+        uint32_t prev = before_lane;
 #pragma unroll
         for (uint32_t i = 0; i < 16; i++) {
-            uint32_t w = x[i];
-            uint32_t d = stuffed_mask(w, prev, i < 15 ? (x[i < 15 ? i + 1 : 15] & 0xFFu) : behind);
-            prev = w >> 24;
-            n += __popc(d);
-            if (len < 64) {  // the stream's last lane
-                const uint32_t in = len > i * 4 ? min(len - i * 4, 4u) : 0u;
-                if (in < 4) d |= 0x80808080u << (8 * in);
+            d[i] = stuffed_zero_mask(x[i], prev);
+            prev = x[i] >> 24;
+        }
+        if (markers) {
+            const uint32_t behind = pieces == 4 ? (t < kThreads - 1 ? buf[(t + 1) * 17] & 0xFFu : behind_chunk) : 0x01u;
+            prev = before_lane;
+#pragma unroll
+            for (uint32_t i = 0; i < 16; i++) {
+                d[i] |= marker_mask(x[i], prev, i < 15 ? (x[i < 15 ? i + 1 : 15] & 0xFFu) : behind);
+                prev = x[i] >> 24;
             }
-            w = (d & 0x80000000u) ? (w & 0x00FFFFFFu) : w;
-            w = (d & 0x00800000u) ? ((w & 0xFFFFu) | ((w >> 8) & 0xFF0000u)) : w;
-            w = (d & 0x00008000u) ? ((w & 0xFFu) | ((w >> 8) & 0xFFFF00u)) : w;
-            w = (d & 0x00000080u) ? (w >> 8) : w;
-            x[i] = w;
-            kept |= (unsigned long long)(4 - __popc(d)) << (3 * i);
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < 16; i++) {
+            const uint32_t p = __popc(d[i]);
+            n += p;
+            gone[i / 5] |= p << (6 * (i % 5) + 3);
+            // the mask's bytes are 0x80 or 0: their dot product with (1, 2, 4, 8) is 0x80 times the four bits as a number
+            const uint32_t m = __builtin_amdgcn_udot4(d[i], 0x08040201u, 0u, false) >> 7;
+            x[i] = __builtin_amdgcn_perm(x[i], x[i], squeeze_sel[m]);
         }
     }
     // exclusive scan of the per-lane counts: inside the wave by shuffles, across the four waves through LDS
@@ -470,24 +510,26 @@ __global__ __launch_bounds__(kThreads) void destuff_compact_kernel(HuffImage* __
     // full, and the lanes in front of it have left that one to their byte stores.
     auto padded = [](uint32_t k) { return k + ((k >> 6) << 2); };
     const uint32_t o0 = a + t * 64 - excl, cnt0 = o0 & 3;
-    uint32_t o = o0 & ~3u, cnt = cnt0;
-    unsigned long long acc = 0;
+    // (The accumulator is one register: below its cnt < 4 bytes nothing is set, so a word shifted up by cnt bytes fills it and leaves
+    // its own top bytes for the next dword.  Only the store depends on whether the dword is full; the rest are selects.)
+    uint32_t slot = o0 >> 2, bits = 8 * cnt0, acc = 0;  // bits: eight times the bytes the accumulator holds
     if (len) {
 #pragma unroll
         for (uint32_t i = 0; i < 16; i++) {
-            acc |= (unsigned long long)x[i] << (8 * cnt);
-            cnt += (uint32_t)(kept >> (3 * i)) & 7u;
-            if (cnt >= 4) {
-                buf[(o >> 2) + (o >> 6)] = (uint32_t)acc;
-                acc >>= 32;
-                cnt -= 4;
-                o += 4;
-            }
+            const unsigned long long w = (unsigned long long)x[i] << bits;
+            const uint32_t p = (gone[i / 5] >> (6 * (i % 5))) & 63u;
+            const bool full = bits >= p;  // bits / 8 + (4 - p / 8) kept bytes make a dword
+            acc |= (uint32_t)w;
+            if (full) buf[slot + (slot >> 4)] = acc;
+            acc = full ? (uint32_t)(w >> 32) : acc;
+            slot += full ? 1u : 0u;
+            bits = (bits - p) & 24u;
         }
     }
+    const uint32_t o = slot * 4, cnt = bits / 8;
     __syncthreads();
     {  // what the accumulator still holds (in front of it the neighbours' bytes, if the lane never filled a dword)
-        const uint32_t from = o == (o0 & ~3u) ? cnt0 : 0u;
+        const uint32_t from = slot == (o0 >> 2) ? cnt0 : 0u;
 #pragma unroll
         for (uint32_t b = 0; b < 3; b++)
             if (b >= from && b < cnt) bytes[padded(o + b)] = (uint8_t)((uint32_t)acc >> (8 * b));
@@ -1397,18 +1439,74 @@ __global__ __launch_bounds__(kThreads) void huff_dcdiff_kernel(HuffImage* __rest
 // ---- DC differences -> DC values ------------------------------------------------------------------------------------------
 // Images without restart intervals: one workgroup per block-pass unit (kHuffMcusPerWg MCUs).  The predictor value a group
 // starts from is the sum of the group sums in front of it (the block pass left them: a few dozen numbers), so every group
-// integrates its own MCUs without waiting for anybody; wave c takes component c and scans its entries 64 at a time.
+// integrates its own MCUs without waiting for anybody.  A lane takes whole consecutive MCUs of one component: it adds their entries
+// serially, ONE wave scan runs over the lane totals, and the lane walks its entries again to store them -- no division per entry (the
+// block's place inside the MCU advances with the entry, the MCU's place in the image is divided out once per lane), and the scan's
+// six shuffle steps once per wave instead of once per 64 entries (at 4:2:0 the luma wave ran eight scans and three divisions per
+// entry back to back, 50 us per 256 x 1080p; 38 us with the lanes' MCUs, 31 with the group's loads in flight together:
+// profiles/entropy_residue2/).
 //
 // This is the last kernel of the stage that every image passes, and nothing behind it changes a verdict: the group at an image's MCU 0
 // reports the image (huff_verdict(): status, gave_up), the first workgroup the stage's convergence counters, into
 // `verdicts` -- the host's pinned memory where that is mapped (kHuffVerdictCounters words of counters, then a word per image), so that
 // no copy command has to follow the stage.
+constexpr bool kDcSplit = kHuffMcusPerWg % 128 == 0;  // component 0's MCUs can go to two waves, whole MCUs to every lane
+constexpr uint32_t kDcLaneMcus = kHuffMcusPerWg / 64;  // MCUs a lane takes at most
+static_assert(kHuffMcusPerWg % 64 == 0, "huff_dc_group_kernel: the same number of MCUs for every lane of a wave");
+
+// The lane's `live` MCUs of one component, `bpc` entries each (BPC: the same at compile time, 0 = any), the first at d, the next bpm
+// entries on: their sum ...
+template <uint32_t BPC>
+__device__ __forceinline__ int dc_lane_total(const int16_t* d, uint32_t live, uint32_t bpc, uint32_t bpm)
+{
+    const uint32_t nb = BPC ? BPC : bpc;
+    int sum = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < kDcLaneMcus; q++) {
+        if (q < live) {
+#pragma unroll
+            for (uint32_t jj = 0; jj < nb; jj++) sum += d[q * bpm + jj];
+        }
+    }
+    return sum;
+}
+
+// ... and their running sums from `run` on, stored to the component's DC plane (h x v blocks per MCU, row-major; the lane's first MCU
+// is (mx, my) of the image's mcus_x columns).
+template <uint32_t BPC>
+__device__ __forceinline__ void dc_lane_store(const int16_t* d, HJ_GLOBAL int16_t* plane, int run, uint32_t live, uint32_t bpc, uint32_t bpm,
+                                              uint32_t h, uint32_t v, uint32_t bw, uint32_t mx, uint32_t my, uint32_t mcus_x)
+{
+    const uint32_t nb = BPC ? BPC : bpc;
+#pragma unroll
+    for (uint32_t q = 0; q < kDcLaneMcus; q++) {
+        if (q < live) {
+            HJ_GLOBAL int16_t* p = plane + (my * v) * bw + mx * h;  // the MCU's first block; dx counts along its row of h blocks
+            uint32_t dx = 0;
+#pragma unroll
+            for (uint32_t jj = 0; jj < nb; jj++) {
+                run += d[q * bpm + jj];
+                p[dx] = (int16_t)run;
+                if (++dx == h) {
+                    dx = 0;
+                    p += bw;
+                }
+            }
+            if (++mx == mcus_x) {
+                mx = 0;
+                my++;
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void huff_dc_group_kernel(const HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
                                                                  const int32_t* __restrict__ group_sums, const unsigned int* __restrict__ counters,
                                                                  unsigned int* __restrict__ verdicts)
 {
     __shared__ int16_t s_diff[kHuffMcusPerWg * 10];
     __shared__ int s_base[4];
+    __shared__ int s_half;
     const HuffUnit u = units[blockIdx.x];  // first = first MCU of the group
     const HuffImage& im = images[u.image];
     if (verdicts) {
@@ -1418,48 +1516,65 @@ __global__ __launch_bounds__(kThreads) void huff_dc_group_kernel(const HuffImage
     if (im.restart_interval != 0) return;  // uniform: huff_dc_kernel takes those
     const int t = threadIdx.x;
     const uint32_t bpm = im.blocks_per_mcu;
-    const uint32_t total_mcus = im.mcus_x * im.mcus_y;
+    const uint32_t mcus_x = im.mcus_x, total_mcus = mcus_x * im.mcus_y;
     const uint32_t mcus = min((uint32_t)kHuffMcusPerWg, total_mcus - u.first);
     const uint32_t n = mcus * bpm;
     const uint32_t g = u.first / kHuffMcusPerWg;  // groups in front of this one: units blockIdx.x - g .. blockIdx.x - 1
     if (t < 4) s_base[t] = 0;
+    // (the group sums are fetched beside the differences, one round of memory latency for both; they meet in s_base behind the
+    // barrier and are read behind the next one, the one the lane totals need anyway)
+    const HJ_GLOBAL int32_t* sums = (const HJ_GLOBAL int32_t*)group_sums + (size_t)(blockIdx.x - g) * 4;
+    int part = (uint32_t)t < g * 4 ? sums[t] : 0;  // i & 3 = t & 3: a lane stays with one component
     {
+        // all of a lane's loads in flight together (a loop of load and store waited for every one of them in turn)
         const HJ_GLOBAL int16_t* diff = (const HJ_GLOBAL int16_t*)im.dc_diff + (size_t)u.first * bpm;
-        for (uint32_t i = t; i < n; i += kThreads) s_diff[i] = diff[i];
-    }
-    __syncthreads();
-    {
-        const HJ_GLOBAL int32_t* sums = (const HJ_GLOBAL int32_t*)group_sums + (size_t)(blockIdx.x - g) * 4;
-        int part = 0;
-        for (uint32_t i = t; i < g * 4; i += kThreads) part += sums[i];  // i & 3 = t & 3: a lane stays with one component
-        if (part != 0) atomicAdd(&s_base[t & 3], part);
-    }
-    __syncthreads();
-    const int c = t >> 6, lane = t & 63;
-    if (c >= (int)im.ncomp) return;
-    const uint32_t h = im.comp_h[c], v = im.comp_v[c], bpc = h * v, k0 = im.comp_k0[c];
-    const uint32_t bw = im.blocks_w[c], mcus_x = im.mcus_x;
-    HJ_GLOBAL int16_t* plane = (HJ_GLOBAL int16_t*)im.dc_plane[c];
-    int run = s_base[c];
-    const uint32_t nc = mcus * bpc;
-    for (uint32_t s0 = 0; s0 < nc; s0 += 64) {
-        const uint32_t s = s0 + lane;
-        const bool live = s < nc;
-        const uint32_t m = s / bpc, jj = s - m * bpc;
-        int x = live ? (int)s_diff[m * bpm + k0 + jj] : 0;
+        constexpr uint32_t kLoads = (kHuffMcusPerWg * 10 + kThreads - 1) / kThreads;
+        int16_t e[kLoads];
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int y = __shfl_up(x, d, 64);
-            if (lane >= d) x += y;
-        }
-        if (live) {
-            const uint32_t mcu = u.first + m;
-            const uint32_t my = mcu / mcus_x, mx = mcu - my * mcus_x;
-            const uint32_t dy = jj / h, dx = jj - dy * h;
-            plane[(my * v + dy) * bw + (mx * h + dx)] = (int16_t)(run + x);
-        }
-        run += __shfl(x, 63, 64);
+        for (uint32_t k = 0; k < kLoads; k++) e[k] = k * kThreads + t < n ? diff[k * kThreads + t] : (int16_t)0;
+#pragma unroll
+        for (uint32_t k = 0; k < kLoads; k++)
+            if (k * kThreads + t < n) s_diff[k * kThreads + t] = e[k];
     }
+    for (uint32_t i = t + kThreads; i < g * 4; i += kThreads) part += sums[i];  // (images of more than 64 groups)
+    __syncthreads();
+    if (part != 0) atomicAdd(&s_base[t & 3], part);
+    // Wave w takes component w; where the frame leaves the fourth wave free (up to three components) it takes the second half of
+    // component 0's MCUs -- at 4:2:0 luma has four of an MCU's six entries.  A lane owns whole, consecutive MCUs.
+    const int wave = t >> 6, lane = t & 63;
+    const bool split = kDcSplit && im.ncomp <= 3;
+    const bool helper = split && wave == 3;
+    const int c = helper ? 0 : wave;
+    const bool active = c < (int)im.ncomp;
+    const uint32_t per_lane = split && c == 0 ? kHuffMcusPerWg / 128 : kHuffMcusPerWg / 64;
+    const uint32_t m0 = ((helper ? 64u : 0u) + (uint32_t)lane) * per_lane;
+    const uint32_t live = active && m0 < mcus ? min(per_lane, mcus - m0) : 0u;
+    uint32_t h = 1, v = 1, bpc = 1, bw = 0, mx = 0, my = 0;
+    const int16_t* d = s_diff;
+    HJ_GLOBAL int16_t* plane = nullptr;
+    int x = 0;
+    if (active) {
+        h = im.comp_h[c], v = im.comp_v[c], bpc = h * v, bw = im.blocks_w[c];
+        d = s_diff + m0 * bpm + im.comp_k0[c];
+        plane = (HJ_GLOBAL int16_t*)im.dc_plane[c];
+        my = (u.first + m0) / mcus_x, mx = (u.first + m0) - my * mcus_x;
+        x = bpc == 1 ? dc_lane_total<1>(d, live, bpc, bpm) : bpc == 2 ? dc_lane_total<2>(d, live, bpc, bpm)
+          : bpc == 4 ? dc_lane_total<4>(d, live, bpc, bpm) : dc_lane_total<0>(d, live, bpc, bpm);
+    }
+    const int own = x;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const int y = __shfl_up(x, s, 64);
+        if (lane >= s) x += y;
+    }
+    if (split && wave == 0 && lane == 63) s_half = x;  // component 0's first half, for the wave that takes the second
+    __syncthreads();
+    if (!active) return;
+    const int run = s_base[c] + (helper ? s_half : 0) + (x - own);
+    if (bpc == 1) dc_lane_store<1>(d, plane, run, live, bpc, bpm, h, v, bw, mx, my, mcus_x);
+    else if (bpc == 2) dc_lane_store<2>(d, plane, run, live, bpc, bpm, h, v, bw, mx, my, mcus_x);
+    else if (bpc == 4) dc_lane_store<4>(d, plane, run, live, bpc, bpm, h, v, bw, mx, my, mcus_x);
+    else dc_lane_store<0>(d, plane, run, live, bpc, bpm, h, v, bw, mx, my, mcus_x);
 }
 
 // Images with restart intervals (the predictor starts over inside the image): one workgroup per (image, component)
