@@ -1158,7 +1158,8 @@ hipjpegStatus_t DecodeBatch::transfer(void* stream, bool kernels_on_other_stream
 
 // GPU entropy stage: remove the byte stuffing, synchronise the subsequence decoders, scan block counts, write the
 // coefficient blocks, integrate DC.  The common case is enqueued without any host round trip: launch 1 leaves every workgroup in
-// a local fixpoint, launch 2 repairs the workgroup boundaries and counts the workgroups whose outgoing state moved; when
+// a local fixpoint (its tail kernel already enters every workgroup with the state in front of it as it is by then, so most
+// boundaries are settled too), launch 2 repairs the remaining workgroup boundaries and counts the workgroups whose outgoing state moved; when
 // that count is zero the states are the global fixpoint (no workgroup consumed a state that changed afterwards).  Only if
 // it is not zero -- a correction crossed a whole workgroup -- more launches follow and the write passes are repeated.
 // Blocks at the end: the host needs the per-image status to fall back to its own entropy decoder for streams the kernels

@@ -26,7 +26,9 @@ int launch_destuff(HuffImage* images, const HuffUnit* chunk_units, int nchunks, 
 // units[i].first = first owned subsequence of workgroup i, a multiple of kHuffOwn; incoming = one uint64 per unit
 // max_rounds / tail_tasks / tail_count: after max_rounds correction rounds the workgroup hands what is left (tail_tasks:
 // kTailTaskBytes per unit, tail_count: one uint32 per unit) to the tail kernel, launched right behind it; tail_count == nullptr:
-// the workgroup iterates to its fixpoint itself.
+// the workgroup iterates to its fixpoint itself.  The tail kernel enters a group with the state that lies in front of it at that
+// moment, not with pass 0's guess (incoming[] then holds the state that was used): most corrections across group borders are
+// made there already, and the ripple launch finds little.
 // first_pass == 0: a ripple launch (corrections across group borders), pass_id = its number (1, 2, ...): HuffImage::moved_pass
 // receives it for every image in which a group's own last end state still changed.  HuffImage::gave_up is set for images with a
 // group that exceeded its round budget (periodic streams); such images are skipped by later ripple launches.

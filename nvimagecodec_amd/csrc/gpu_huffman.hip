@@ -736,6 +736,19 @@ __device__ __forceinline__ void wave_sync()
 // RIPPLE mode (the launches behind the first): nothing is handed over by the sync kernel; a group whose predecessor's last end state
 // is no longer the state it was entered with starts over at its first subsequence, and the correction runs as far as it changes
 // anything.  counters[0] counts the groups whose own last end state moved -- zero: the batch has converged.
+//
+// The first launch enters the same way.  When it starts the sync kernel is done, and the state in front of every group has two
+// correction rounds behind it; pass 0's guess (the halo lane's decode from an assumed state), which the group's first subsequence
+// was decoded from, is wrong for one group in three.  So the group takes the state in front as it is when its wave gets there, and
+// if that is not the guess, its first subsequence joins the first round as one more chain beside the ones handed over.  When its
+// lists are empty the wave looks in front once more (kTailReentries times at most) and follows what it finds as a single chain; it
+// never waits -- not every batch has all its groups resident -- and a group that is done before the one in front of it moved is
+// left to the ripple launch, as before.
+// The read is no snapshot: the wave of the group in front may already have stored a newer last end state, or store one a moment
+// later.  Whatever is read is a state that group had at some time; incoming[] records exactly the state that was used; the ripple
+// launch behind compares it with the final one and starts the group over if they differ.  So the result does not depend on timing,
+// only the split of the work between the two launches does.  This rests on two facts: one wave alone writes a group's states and
+// records, and a subsequence's last decode is the one from its converged start state, so its record is final.
 
 // the state in front of group `u` as it is now (0 for the first group of an image)
 __device__ __forceinline__ unsigned long long state_in_front(const unsigned long long* states, const HuffImage& im, const HuffUnit u)
@@ -793,7 +806,16 @@ constexpr int kTailRoundBudget = 192, kRippleRoundBudget = 192;
 #define HJ_COOP_CHAINS 2
 #endif
 constexpr int kCoopChains = HJ_COOP_CHAINS;  // chains a round may have left for the wave to take them one by one (0: never)
+#ifndef HJ_TAIL_REENTRIES
+#define HJ_TAIL_REENTRIES 4
+#endif
+constexpr uint32_t kTailEnter = 1u << 31;  // huff_tail_kernel's work word of a group: the state in front of it has moved
+constexpr int kTailReentries = HJ_TAIL_REENTRIES;  // times a group of the first tail launch looks in front again when its lists are empty
+                                                   // (2, 4 and 8 measure the same: profiles/tail_entry/README.md)
 
+// Both builds enter with state_in_front() as it reads at that moment and store what they used to incoming[ui]; why a read that
+// races with the wave of the group in front cannot change the result is argued under "RIPPLE mode" above (one wave alone writes a
+// group's states and records; a subsequence's last decode is the one from its converged start state).
 template <bool RIPPLE>
 __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage& im, const HuffUnit u, uint32_t ui, int lane,
                                            unsigned long long* __restrict__ states, unsigned long long* __restrict__ incoming,
@@ -805,16 +827,25 @@ __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage&
     if (u.first >= nsub) return;
     unsigned long long* gstate = states + im.first_subseq;
     const int n_rows = (int)min((uint32_t)kSyncThreads, nsub - u.first + 1);
-    unsigned long long entering;  // the state the group is entered with ([0] of its rows)
+    // the state the group is entered with ([0] of its rows): the one in front of it now, read once
+    unsigned long long entering = state_in_front(states, im, u);
     if (RIPPLE) {
-        entering = state_in_front(states, im, u);
         if (lane == 0) {
             incoming[ui] = entering;
             ws.list[0][0] = 1;
         }
     } else {
-        entering = incoming[ui];
         for (uint32_t i = lane; i < pending; i += 64) ws.list[0][i] = tail_tasks[(size_t)ui * kSyncThreads + i];
+        // The sync kernel's rounds moved the state in front since pass 0 guessed it: row 1 is decoded again, an ordinary member of
+        // the first Jacobi round.  Task 1 is never among the tasks handed over -- row 0 does not move in the first launch, so the
+        // sync kernel decodes row 1 once, in its round 1, and hands over successors of rows that moved: 2 and up.
+        if (entering != incoming[ui]) {  // uniform
+            if (lane == 0) {
+                incoming[ui] = entering;
+                ws.list[0][pending] = 1;
+            }
+            pending++;
+        }
     }
     if (lane == 0) ws.count[0] = pending;
     wave_sync();
@@ -824,12 +855,29 @@ __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage&
     const HJ_GLOBAL uint32_t* g = (const HJ_GLOBAL uint32_t*)im.stream;
     const uint32_t gwords = im.stream_words;
     env.row_base = (uint32_t)(uintptr_t)(HJ_LDS uint32_t*)&ws.rows[lane & (kTailSlots - 1)];  // word k of slot s at index k * kTailSlots + s
-    int rounds = 0, cur = 0;
+    int rounds = 0, cur = 0, reentries = 0;
     bool unfinished = false;
-    for (int round = 0;; round++) {
-        const uint32_t n = ws.count[cur];
-        if (n == 0) break;
-        if (round >= (RIPPLE ? kRippleRoundBudget : kTailRoundBudget)) {
+    for (;;) {
+        uint32_t n = ws.count[cur];
+        if (n == 0) {
+            // Nothing left: look in front once more before leaving.  The group in front may have moved on meanwhile; what it has
+            // now is taken like the state at entry, as one chain from row 1.  No waiting: a group that is done before its
+            // predecessor moved is left to the ripple launch.  The round count carries on.
+            if (RIPPLE || reentries >= kTailReentries || rounds >= kTailRoundBudget) break;
+            const unsigned long long front = state_in_front(states, im, u);
+            if (front == entering) break;  // uniform
+            reentries++;
+            entering = front;
+            wave_sync();  // every lane has read the count
+            if (lane == 0) {
+                incoming[ui] = entering;
+                ws.list[cur][0] = 1;
+                ws.count[cur] = 1;
+            }
+            wave_sync();
+            n = 1;
+        }
+        if (rounds >= (RIPPLE ? kRippleRoundBudget : kTailRoundBudget)) {
             unfinished = true;
             break;
         }
@@ -880,7 +928,9 @@ __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage&
                     }
                 }
             }
-            break;  // every chain has been followed to its end (or the budget is spent)
+            if (unfinished) break;
+            cur ^= 1;  // every chain has been followed to its end: the list for the next round is empty
+            continue;
         }
         for (uint32_t base = 0; base < n; base += kTailSlots) {
             const bool busy = lane < kTailSlots && base + lane < n;
@@ -955,23 +1005,49 @@ __global__ __launch_bounds__(kTailThreads, 5) void huff_tail_kernel(HuffImage* _
     const HuffUnit u = units[valid ? ui : ui0];
     // what every group of the workgroup has to do (uniform: every lane looks at all of them)
     uint32_t todo[kTailWaves];
+    // Most workgroups of the ripple launch find nothing to do, and the way out is a chain of dependent loads: unit -> descriptor ->
+    // state in front.  The four groups' loads of a level go out together (clamped indices instead of branches), so a workgroup
+    // pays the chain once, not four times.
+    {
+        HuffUnit uq[kTailWaves];
+        uint32_t bits[kTailWaves], gave[kTailWaves], base[kTailWaves];
+        unsigned long long front[kTailWaves], came[kTailWaves];
 #pragma unroll
-    for (int q = 0; q < kTailWaves; q++) {
-        todo[q] = 0;
-        if (ui0 + q < (uint32_t)nunits) {
-            if (RIPPLE) {
-                const HuffUnit uq = units[ui0 + q];
-                const HuffImage& iq = images[uq.image];
-                const uint32_t nsub = (iq.total_bits + kSubseqBits - 1) / kSubseqBits;
-                todo[q] = (uq.first < nsub && iq.gave_up == 0 && state_in_front(states, iq, uq) != incoming[ui0 + q]) ? 1u : 0u;
-            } else {
-                todo[q] = tail_count[ui0 + q];
-            }
+        for (int q = 0; q < kTailWaves; q++) {
+            const uint32_t i = min(ui0 + q, (uint32_t)nunits - 1);
+            uq[q] = units[i];
+            came[q] = incoming[i];
+            todo[q] = RIPPLE ? 0u : tail_count[i];  // the sync kernel left tasks (at most kHuffOwn)
         }
+#pragma unroll
+        for (int q = 0; q < kTailWaves; q++) {
+            const HuffImage& iq = images[uq[q].image];
+            bits[q] = iq.total_bits;
+            gave[q] = iq.gave_up;
+            base[q] = iq.first_subseq;
+        }
+#pragma unroll
+        for (int q = 0; q < kTailWaves; q++) {
+            const uint32_t nsub = (bits[q] + kSubseqBits - 1) / kSubseqBits;
+            const bool inside = uq[q].first != 0 && uq[q].first < nsub;  // (a group past the stream's end is never entered)
+            front[q] = __hip_atomic_load(&states[inside ? base[q] + uq[q].first - 1 : 0u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kSyncMask;
+            if (uq[q].first == 0) front[q] = 0;
+            if (uq[q].first >= nsub || gave[q] != 0) front[q] = came[q];
+        }
+#pragma unroll
+        for (int q = 0; q < kTailWaves; q++) {
+            // or the state in front is no longer the one the group was entered with (the first launch: pass 0's guess)
+            if (front[q] != came[q]) todo[q] |= kTailEnter;
+            if (ui0 + q >= (uint32_t)nunits) todo[q] = 0;
+        }
+        if ((todo[0] | todo[1] | todo[2] | todo[3]) == 0) return;  // uniform, before anything is staged
     }
+    static_assert(kTailWaves == 4, "the work test above");
     uint32_t pending = 0;
 #pragma unroll
     for (int q = 0; q < kTailWaves; q++) pending = q == wave ? todo[q] : pending;
+    const bool work_here = pending != 0;
+    pending = RIPPLE ? pending >> 31 : pending & ~kTailEnter;  // the tasks handed to tail_group, which looks in front itself
     // the groups of a workgroup usually belong to one image; where an image ends inside it, its tables are staged in turn
 #pragma unroll 1
     for (int s = 0; s < kTailWaves; s++) {
@@ -988,7 +1064,7 @@ __global__ __launch_bounds__(kTailThreads, 5) void huff_tail_kernel(HuffImage* _
         stage_pool<kTailThreads>(pool, im);
         stage_constants(sh.tsel, nullptr, nullptr, im, false);
         __syncthreads();
-        if (valid && u.image == image && pending != 0) {
+        if (valid && u.image == image && work_here) {
             TailEnv env;
             env.row_base = 0;
             env.word0 = 0;
