@@ -68,6 +68,40 @@ __device__ __forceinline__ uint32_t load_boundary(const uint32_t* boundaries, ui
 {
     return i < n ? ((const HJ_GLOBAL uint32_t*)boundaries)[i] : 0xFFFFFFFFu;
 }
+// How the lane walks take a block's end and a long code (WalkPolicy, huffman_gpu_core.h).  huff_sync_kernel, whose waves have
+// every lane busy, takes both as selects, with the table selection in registers and a long code as a step of its own.  The lane
+// mode of the tail kernels and huff_pos_kernel keep the branches, tsel[] in LDS and the second-level read inside the branch:
+// with a few lanes busy, often one, a branch that is not taken is the cheapest form, and each of the three changes made these
+// kernels slower (profiles/walk_steps/README.md).
+// A/B switch (tools/build_variant.sh) for the builds that were measured: bit 0 = table selection from registers, bit 1 = a long
+// code is a step of its own, bit 2 = both events as selects in huff_sync_kernel, bit 3 = bits 0 and 1 in huff_sync_kernel only.
+#ifndef HJ_WALK_PARTS
+#define HJ_WALK_PARTS 15
+#endif
+constexpr int kWalkParts = HJ_WALK_PARTS;
+static_assert((kWalkParts & 4) == 0 || (kWalkParts & 3) == 3, "the select form needs the registers and the long step");
+constexpr bool kLaneRegisters = (kWalkParts & 9) == 1, kLaneLongStep = (kWalkParts & 10) == 2;
+typedef WalkPolicy<(kWalkParts & 2) != 0, (kWalkParts & 4) != 0> SyncWalk;
+typedef WalkPolicy<kLaneLongStep, false> LaneWalk;
+
+// The image's table selection as wave-uniform values (byte offsets, as tsel[] holds them): a few dozen scalar instructions once
+// per wave.  in_vgprs: the pairs are held in vector registers -- a select between two of them is then one v_bfi_b32, where two
+// scalar operands would cost a second instruction (for the walks that select in every step; the measured builds that selected
+// inside the tail kernels' rare branch kept them scalar, those kernels have no registers to spare).
+template <bool IN_VGPRS>
+__device__ __forceinline__ TableClasses table_classes(const HuffImage& im)
+{
+    TableClasses c = make_table_classes(im.blocks_per_mcu, [&](uint32_t q) { return ((uint32_t)im.k[q].tdc * 2) | ((uint32_t)im.k[q].tac * 2 << 16); });
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        c.pair[i] = HJ_UNIFORM(c.pair[i]);
+        if (IN_VGPRS) asm("" : "+v"(c.pair[i]));
+    }
+    c.bit0 = HJ_UNIFORM(c.bit0);
+    c.bit1 = HJ_UNIFORM(c.bit1);
+    return c;
+}
+
 // LDS accessors for decode_subsequence.
 struct DevEnv {
     uint32_t stream_base;  // LDS byte address of the staged words
@@ -76,6 +110,7 @@ struct DevEnv {
     uint32_t row_word0;    // ... and the image word index of that word (set_row)
     uint32_t pool;         // LDS byte address of the lookup tables
     const HJ_LDS uint32_t* tsel;  // per MCU position: BYTE offsets of the DC / AC first-level tables, packed lo/hi
+    TableClasses classes;         // the same selection from registers (table_classes), for the walks that select in every step
     const uint32_t* boundaries;
     uint32_t num_boundaries;
     __device__ __forceinline__ uint32_t boundary(uint32_t i) const { return load_boundary(boundaries, num_boundaries, i); }
@@ -87,7 +122,7 @@ struct DevEnv {
     }
     __device__ __forceinline__ uint32_t cursor(uint32_t i) const { return row_addr + (i - row_word0) * kCursorStep; }
     __device__ __forceinline__ uint32_t fetch(uint32_t c) const { return *(const HJ_LDS uint32_t*)(uintptr_t)c; }
-    __device__ __forceinline__ uint32_t tables(int k) const { return tsel[k]; }
+    __device__ __forceinline__ uint32_t tables(int k) const { return kLaneRegisters ? select_tables(classes, (uint32_t)k) : tsel[k]; }
     __device__ __forceinline__ uint32_t lookup1(uint32_t t, uint32_t w) const
     {
         return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + t + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
@@ -96,6 +131,7 @@ struct DevEnv {
     {
         return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + ((e & 0x1FFu) << 7) + ((w >> 15) & ((2u << kHuffSubBits) - 2)));
     }
+    __device__ __forceinline__ uint32_t second_table(uint32_t e) const { return (e & 0x1FFu) << 7; }  // pool offset / 64 entries -> bytes
     __device__ __forceinline__ uint32_t lookup_pair(uint32_t t, uint32_t w) const  // lookup1's address + a constant: one more LDS read, no more arithmetic
     {
         return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + t + 2 * kPairOffset + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
@@ -135,12 +171,36 @@ __device__ __forceinline__ void put_mark(const SlotRecorder& r, uint32_t begin, 
 
 // decode_subsequence with or without restart handling (wave-uniform choice: one image per workgroup), with or without records
 // (uniform too; never across restart boundaries)
+template <class Policy, class Env>
+__device__ __forceinline__ SubseqState walk_with(bool rst, bool record, const HuffGeom& geom, const Env& env, uint32_t begin, uint32_t limit, int z, int k,
+                                                 uint32_t boundary0, const SlotRecorder& rec)
+{
+    if (rst) return decode_subsequence<true, Env, NoRecord, Policy>(geom, env, begin, limit, z, k, boundary0);
+    return record ? decode_subsequence<false, Env, SlotRecorder, Policy>(geom, env, begin, limit, z, k, 0, rec)
+                  : decode_subsequence<false, Env, NoRecord, Policy>(geom, env, begin, limit, z, k);
+}
+// an environment that selects the tables from registers: four classes, or at most two
 template <class Env>
+struct FourClasses : Env {
+    __device__ __forceinline__ explicit FourClasses(const Env& e) : Env(e) {}
+    __device__ __forceinline__ uint32_t tables(int k) const { return select_tables(this->classes, (uint32_t)k); }
+};
+template <class Env>
+struct TwoClasses : Env {
+    __device__ __forceinline__ explicit TwoClasses(const Env& e) : Env(e) {}
+    __device__ __forceinline__ uint32_t tables(int k) const { return select_tables2(this->classes, (uint32_t)k); }
+};
+template <class Policy, class Env>
 __device__ __forceinline__ SubseqState walk_subsequence(bool rst, bool record, const HuffGeom& geom, const Env& env, uint32_t begin, uint32_t limit, int z,
                                                         int k, uint32_t boundary0, const SlotRecorder& rec)
 {
-    if (rst) return decode_subsequence<true>(geom, env, begin, limit, z, k, boundary0);
-    return record ? decode_subsequence<false>(geom, env, begin, limit, z, k, 0, rec) : decode_subsequence<false>(geom, env, begin, limit, z, k);
+    // the select form looks the tables up in every step: from registers, and the everyday scan's two classes get the short
+    // selection (a uniform choice)
+    if (Policy::kSelects) {
+        if (env.classes.bit1 == 0) return walk_with<Policy>(rst, record, geom, TwoClasses<Env>(env), begin, limit, z, k, boundary0, rec);
+        return walk_with<Policy>(rst, record, geom, FourClasses<Env>(env), begin, limit, z, k, boundary0, rec);
+    }
+    return walk_with<Policy>(rst, record, geom, env, begin, limit, z, k, boundary0, rec);
 }
 
 // Cooperative staging of stream words: lane t brings in row t = subsequence first_row + t of the image (first_row may be -1:
@@ -223,7 +283,7 @@ __device__ __forceinline__ void stage_constants(uint32_t* tsel, KSlot* kslot, ui
     }
 }
 
-__device__ __forceinline__ DevEnv make_env(WgShared& sh, HJ_LDS uint16_t* pool, uint32_t first, const HuffGeom& geom)
+__device__ __forceinline__ DevEnv make_env(WgShared& sh, HJ_LDS uint16_t* pool, uint32_t first, const HuffGeom& geom, const HuffImage& im)
 {
     DevEnv env;
     env.stream_base = (uint32_t)(uintptr_t)(HJ_LDS uint32_t*)sh.stream;
@@ -232,6 +292,7 @@ __device__ __forceinline__ DevEnv make_env(WgShared& sh, HJ_LDS uint16_t* pool, 
     env.row_word0 = env.word0;
     env.pool = (uint32_t)(uintptr_t)pool;
     env.tsel = (const HJ_LDS uint32_t*)sh.tsel;
+    env.classes = table_classes<true>(im);
     env.boundaries = geom.boundaries;
     env.num_boundaries = geom.num_boundaries;
     return env;
@@ -599,7 +660,7 @@ __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage
     stage_constants(sh.tsel, nullptr, nullptr, im, false);
     __syncthreads();
 
-    DevEnv env = make_env(sh, pool, u.first, geom);
+    DevEnv env = make_env(sh, pool, u.first, geom, im);
     const bool rst = im.restart_interval != 0;
     unsigned long long old_global = ~0ull;
     int task = -1;
@@ -611,7 +672,7 @@ __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage
         if (owner || (t == 0 && u.first > 0)) {
             const uint32_t bidx0 = boundary0_of(im, j);
             env.set_row(t);
-            mine = pack_state(walk_subsequence(rst, false, geom, env, j * kSubseqBits, (j + 1) * kSubseqBits, 0, 0, bidx0, SlotRecorder()));
+            mine = pack_state(walk_subsequence<SyncWalk>(rst, false, geom, env, j * kSubseqBits, (j + 1) * kSubseqBits, 0, 0, bidx0, SlotRecorder()));
         }
         sh.end[t] = mine;
         __syncthreads();
@@ -635,7 +696,7 @@ __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage
             env.set_row(task);  // the predecessor's walk ended on a symbol that starts in this row
             const uint32_t jt = u.first - 1 + task;
             const SlotRecorder rec = slot_recorder(records, im, jt);
-            const SubseqState st = walk_subsequence(rst, recording, geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
+            const SubseqState st = walk_subsequence<SyncWalk>(rst, recording, geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
             if (recording) put_mark(rec, p.end_bit, (jt + 1) * kSubseqBits, geom.total_bits, p.zk & 255, st);
             now = pack_state(st);
             moved = ((now ^ sh.end[task]) & kSyncMask) != 0;
@@ -704,14 +765,15 @@ struct TailEnv {
     uint32_t row_base;  // LDS byte address of this lane's row buffer
     uint32_t word0;     // image word index of its first word
     uint32_t pool;
-    const HJ_LDS uint32_t* tsel;
+    const HJ_LDS uint32_t* tsel;  // for the whole-wave mode (CoopWindow)
+    TableClasses classes;         // (measurement builds only: kLaneRegisters)
     const uint32_t* boundaries;
     uint32_t num_boundaries;
     __device__ __forceinline__ uint32_t boundary(uint32_t i) const { return load_boundary(boundaries, num_boundaries, i); }
     static constexpr uint32_t kCursorStep = (uint32_t)kTailSlots * 4u;  // the slots are transposed like the rows of the sync kernel
     __device__ __forceinline__ uint32_t cursor(uint32_t i) const { return row_base + (i - word0) * kCursorStep; }
     __device__ __forceinline__ uint32_t fetch(uint32_t c) const { return *(const HJ_LDS uint32_t*)(uintptr_t)c; }
-    __device__ __forceinline__ uint32_t tables(int k) const { return tsel[k]; }
+    __device__ __forceinline__ uint32_t tables(int k) const { return kLaneRegisters ? select_tables(classes, (uint32_t)k) : tsel[k]; }
     __device__ __forceinline__ uint32_t lookup1(uint32_t t, uint32_t w) const
     {
         return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + t + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
@@ -720,6 +782,7 @@ struct TailEnv {
     {
         return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + ((e & 0x1FFu) << 7) + ((w >> 15) & ((2u << kHuffSubBits) - 2)));
     }
+    __device__ __forceinline__ uint32_t second_table(uint32_t e) const { return (e & 0x1FFu) << 7; }  // pool offset / 64 entries -> bytes
     __device__ __forceinline__ uint32_t lookup_pair(uint32_t t, uint32_t w) const  // lookup1's address + a constant: one more LDS read, no more arithmetic
     {
         return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + t + 2 * kPairOffset + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
@@ -958,7 +1021,7 @@ __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage&
                 const SubseqState p = unpack_state(before);
                 const uint32_t jt = u.first - 1 + task;
                 const SlotRecorder rec = slot_recorder(records, im, jt);
-                const SubseqState st = walk_subsequence(rst, recording, geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
+                const SubseqState st = walk_subsequence<LaneWalk>(rst, recording, geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
                 if (recording) put_mark(rec, p.end_bit, (jt + 1) * kSubseqBits, geom.total_bits, p.zk & 255, st);
                 now = pack_state(st);
                 moved = ((now ^ old) & kSyncMask) != 0;
@@ -1070,6 +1133,7 @@ __global__ __launch_bounds__(kTailThreads, 5) void huff_tail_kernel(HuffImage* _
             env.word0 = 0;
             env.pool = (uint32_t)(uintptr_t)pool;
             env.tsel = (const HJ_LDS uint32_t*)sh.tsel;
+            env.classes = kLaneRegisters ? table_classes<false>(im) : TableClasses();
             env.boundaries = im.boundaries;
             env.num_boundaries = im.num_boundaries;
             tail_group<RIPPLE>(sh.wave[wave], env, im, u, ui, lane, states, incoming, counters, tail_tasks, pending, pass_id, records);
@@ -1223,7 +1287,7 @@ __global__ __launch_bounds__(kSyncThreads) void huff_pos_kernel(HuffImage* __res
     stage_constants(sh.tsel, nullptr, nullptr, im, false);
     __syncthreads();
     if (!walk) return;
-    DevEnv env = make_env(sh, pool, u.first, geom);
+    DevEnv env = make_env(sh, pool, u.first, geom, im);
     env.set_row(t);
     const unsigned long long* st = states + im.first_subseq;
     uint32_t begin = 0;

@@ -271,6 +271,7 @@ struct HostEnv {
     uint32_t boundary(uint32_t i) const { return i < im->num_boundaries ? im->boundaries[i] : 0xFFFFFFFFu; }
     uint32_t lookup1(uint32_t t, uint32_t w) const { return im->pool[t + (w >> (32 - kHuffFastBits))]; }
     uint32_t lookup2(uint32_t e, uint32_t w) const { return im->pool[(e & 0x1FFu) * 64u + ((w >> 16) & ((1u << kHuffSubBits) - 1))]; }
+    uint32_t second_table(uint32_t e) const { return (e & 0x1FFu) * 64u; }
     uint32_t lookup_pair(uint32_t t, uint32_t w) const
     {
         const size_t i = (size_t)t + kPairOffset + (w >> (32 - kHuffFastBits));
@@ -363,16 +364,46 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
     // (in pass 0 only subsequence 0, whose start state is exact: the kernels decode it once more in round 1, from the same state).
     // Not for restart intervals.
     std::vector<uint16_t> records((size_t)ns * kRecShorts, 0);
+    // The kernels select the tables of an MCU position from registers (TableClasses): the same builder, here, must reproduce the
+    // array for every position (else return 5).
+    {
+        const TableClasses classes = make_table_classes(im.blocks_per_mcu, [&](uint32_t q) { return env.tables((int)q); });
+        if (!classes.complete) return 5;
+        for (uint32_t q = 0; q < im.blocks_per_mcu; q++)
+            if (select_tables(classes, q) != env.tables((int)q)) return 5;
+    }
+    // Every walk runs in the form huff_sync_kernel uses (WalkSelects) and again in the form of the tail kernels' lanes and the
+    // position kernel (WalkBranches), and in the long-step branch form: same end state and same record, from true and from wrong
+    // start states, or `policies_differ` (return 5).
+    bool policies_differ = false;
+    uint16_t other[kRecShorts];
     auto walk = [&](uint32_t i, uint32_t begin, int z, int k, bool record) {
         const uint32_t limit = (i + 1) * kSubseqBits;
         uint16_t* rec = &records[(size_t)i * kRecShorts];
         if (rst) {
             rec[kRecMark] = (uint16_t)kRecInvalid;
-            return decode_subsequence<true>(geom, env, begin, limit, z, k, 0);
+            const SubseqState st = decode_subsequence<true, HostEnv, NoRecord, WalkSelects>(geom, env, begin, limit, z, k, 0);
+            if (pack_state(st) != pack_state(decode_subsequence<true, HostEnv, NoRecord, WalkBranches>(geom, env, begin, limit, z, k, 0)) ||
+                pack_state(st) != pack_state(decode_subsequence<true, HostEnv, NoRecord, WalkLongBranches>(geom, env, begin, limit, z, k, 0)))
+                policies_differ = true;
+            return st;
         }
-        const SubseqState st = record ? decode_subsequence<false>(geom, env, begin, limit, z, k, 0, HostRecorder{rec, i * kSubseqBits})
-                                      : decode_subsequence<false>(geom, env, begin, limit, z, k);
-        rec[kRecMark] = (uint16_t)(record ? record_mark(begin, limit < geom.total_bits ? limit : geom.total_bits, (uint32_t)z, st) : kRecInvalid);
+        if (!record) {
+            const SubseqState st = decode_subsequence<false, HostEnv, NoRecord, WalkSelects>(geom, env, begin, limit, z, k);
+            if (pack_state(st) != pack_state(decode_subsequence<false, HostEnv, NoRecord, WalkBranches>(geom, env, begin, limit, z, k)) ||
+                pack_state(st) != pack_state(decode_subsequence<false, HostEnv, NoRecord, WalkLongBranches>(geom, env, begin, limit, z, k)))
+                policies_differ = true;
+            rec[kRecMark] = (uint16_t)kRecInvalid;
+            return st;
+        }
+        const SubseqState st = decode_subsequence<false, HostEnv, HostRecorder, WalkSelects>(geom, env, begin, limit, z, k, 0, HostRecorder{rec, i * kSubseqBits});
+        const uint32_t mark = record_mark(begin, limit < geom.total_bits ? limit : geom.total_bits, (uint32_t)z, st);
+        const size_t named = mark_valid(mark) ? 2 * (mark & (kRecFresh - 1)) : 0;
+        const SubseqState sb = decode_subsequence<false, HostEnv, HostRecorder, WalkBranches>(geom, env, begin, limit, z, k, 0, HostRecorder{other, i * kSubseqBits});
+        if (pack_state(st) != pack_state(sb) || memcmp(other, rec, named) != 0) policies_differ = true;
+        const SubseqState sl = decode_subsequence<false, HostEnv, HostRecorder, WalkLongBranches>(geom, env, begin, limit, z, k, 0, HostRecorder{other, i * kSubseqBits});
+        if (pack_state(st) != pack_state(sl) || memcmp(other, rec, named) != 0) policies_differ = true;
+        rec[kRecMark] = (uint16_t)mark;
         return st;
     };
     // pass 0
@@ -392,6 +423,7 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
         if (passes > (int)ns + 2) return 3;  // cannot happen: the wave of corrections advances one subsequence per pass
     }
     if (sync_passes) *sync_passes = passes;
+    if (policies_differ) return 5;
     if (!rst) {
         // The kernels follow the last links of a correction chain with the whole wave on one subsequence (cooperative_subsequence):
         // the same routine, here, must reproduce the lane decoder's end state for every subsequence -- from its true start state and

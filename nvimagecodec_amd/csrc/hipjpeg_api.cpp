@@ -246,7 +246,8 @@ hipjpegStatus_t hipjpegEntropyDecodeGpuAlgorithmHost(const uint8_t* data, size_t
     int passes = 0;
     int rc = progressive ? emulate_gpu_progressive(data, length, f, ptr) : emulate_gpu_entropy(data, length, f, ptr, &passes);
     if (sync_passes) *sync_passes = passes;
-    // rc 5: a block-start record disagrees with the position walk (a self-check of the emulation, not a property of the stream)
+    // rc 5: a block-start record disagrees with the position walk, or the walk forms or table classes disagree (self-checks of the
+    // emulation, not properties of the stream)
     if (rc == 5) return HIPJPEG_STATUS_INTERNAL_ERROR;
     return rc == 0 ? HIPJPEG_STATUS_SUCCESS : (rc == 2 ? HIPJPEG_STATUS_TRUNCATED : HIPJPEG_STATUS_CORRUPT);
     });

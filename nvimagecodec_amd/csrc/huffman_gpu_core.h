@@ -312,6 +312,88 @@ HJ_HD uint32_t record_mark(uint32_t begin, uint32_t end, uint32_t z0, const Subs
     return n > (uint32_t)kRecSlots ? kRecOverflow : n | (z0 == 0 ? kRecFresh : 0u);
 }
 
+// Table selection from registers.  tables(k) is the (DC, AC) table pair of the component MCU position k belongs to; a scan has at
+// most four components, so its blocks_per_mcu <= 10 positions share at most four distinct pairs.  TableClasses holds the distinct
+// pairs and a two-bit class per position, as two masks (bit k of bit0 / bit1 = low / high bit of position k's class): in the
+// kernels six wave-uniform values, and the selection is two bit-field extracts and three bitwise selects -- no memory read in the
+// walks' end-of-block path.  (Five or more distinct pairs would need a fifth component in one scan; the class builder then keeps
+// the first four, and `complete` is false -- no eligible scan gets there.)
+struct TableClasses {
+    uint32_t pair[4];     // the distinct values of tables(k), in order of first appearance; unused ones repeat pair[0]
+    uint32_t bit0, bit1;  // per position k: bits of its class
+    bool complete;
+};
+// of(k) = tables(k) as the walks want it (k < blocks_per_mcu)
+template <class TablesOf>
+HJ_HD TableClasses make_table_classes(uint32_t blocks_per_mcu, const TablesOf& of)
+{
+    TableClasses c;
+    c.pair[0] = c.pair[1] = c.pair[2] = c.pair[3] = of(0u);
+    c.bit0 = c.bit1 = 0;
+    c.complete = true;
+    uint32_t n = 1;
+    for (uint32_t q = 1; q < 10; q++) {
+        if (q >= blocks_per_mcu) break;
+        const uint32_t t = of(q);
+        uint32_t cls = n;
+        for (uint32_t i = 4; i-- > 0;)
+            if (i < n && c.pair[i] == t) cls = i;
+        if (cls == n) {
+            if (n == 4) {
+                c.complete = false;
+                cls = 3;
+            } else {
+                for (uint32_t i = 0; i < 4; i++) c.pair[i] = i == n ? t : c.pair[i];  // (no indexed store: the pairs stay in registers)
+                n++;
+            }
+        }
+        c.bit0 |= (cls & 1u) << q;
+        c.bit1 |= (cls >> 1) << q;
+    }
+    return c;
+}
+HJ_HD uint32_t bit_select(uint32_t mask, uint32_t ones, uint32_t zeros) { return (mask & ones) | (~mask & zeros); }  // v_bfi_b32
+HJ_HD uint32_t bit_mask(uint32_t bits, uint32_t k)  // all ones if bit k of `bits` is set, else zero
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__builtin_amdgcn_sbfe((int)bits, k, 1u);
+#else
+    return 0u - ((bits >> k) & 1u);
+#endif
+}
+HJ_HD uint32_t select_tables(const TableClasses& c, uint32_t k)
+{
+    const uint32_t a = bit_mask(c.bit0, k), b = bit_mask(c.bit1, k);
+    return bit_select(b, bit_select(a, c.pair[3], c.pair[2]), bit_select(a, c.pair[1], c.pair[0]));
+}
+// the everyday case, at most two classes (bit1 == 0; luma and chroma, or one component): a bit mask and one select
+HJ_HD uint32_t select_tables2(const TableClasses& c, uint32_t k) { return bit_select(bit_mask(c.bit0, k), c.pair[1], c.pair[0]); }
+
+// How decode_subsequence treats its two rare events, the end of a block and a code longer than kHuffFastBits.  Rare for a lane --
+// 6 % and 2 % of a q90 photograph's symbols -- and almost certain for a wave of 64 lanes at independent places of the stream.
+//   kLongStep  a long code is a step of its own: the step that meets the first-level entry "continues in a second-level table"
+//              consumes nothing and changes no state; it points the next step's lookup at the second-level table and at the
+//              kHuffSubBits bits behind the first kHuffFastBits, and that step's ordinary lookup completes the symbol.  No table
+//              read inside a branch.  false: the second-level entry is read inside the rare branch (Env::lookup2).
+//   kSelects   both events are predicated straight-line code (only the record store stays conditional), the tables of the MCU
+//              position are looked up in every step (Env::tables from registers: TableClasses): for huff_sync_kernel, whose
+//              waves have every lane busy.
+// A lone lane gains from a branch that is not taken, and from the table read that hides inside it: the lane mode of the tail
+// kernels and the position kernel keep WalkBranches, the walk as it was before there were policies.  (A long step in the branch
+// form, WalkLongBranches, is slower than either in every kernel; it is kept as the measured middle step and checked with the
+// others by the host emulation.)
+template <bool LONG_STEP, bool SELECTS>
+struct WalkPolicy {
+    static constexpr bool kLongStep = LONG_STEP, kSelects = SELECTS;
+    static_assert(LONG_STEP || !SELECTS, "the select form has no memory read to predicate");
+};
+typedef WalkPolicy<false, false> WalkBranches;
+typedef WalkPolicy<true, false> WalkLongBranches;
+typedef WalkPolicy<true, true> WalkSelects;
+// the window that indexes a second-level table through lookup1: its kHuffFastBits top bits = the kHuffSubBits bits behind the
+// first kHuffFastBits of w
+HJ_HD uint32_t sub_window(uint32_t w) { return (w << kHuffFastBits) >> (kHuffFastBits - kHuffSubBits); }
+
 // Synchronisation decode: the symbols that START in [begin, limit) (and before total_bits), beginning in state (z, k).
 // Tracks the decoder state and counts the blocks completed; rec(i, pos) is told where each block starts (see the block-start records
 // above -- not for restart intervals, whose positions the position pass finds together with the damage check).
@@ -323,8 +405,12 @@ HJ_HD uint32_t record_mark(uint32_t begin, uint32_t end, uint32_t z0, const Subs
 //   uint32_t lookup1(uint32_t t, w)      first-level entry of table t for window w (index = top kHuffFastBits bits)
 //   uint32_t lookup2(uint32_t e, w)      second-level entry behind first-level entry e (index = next kHuffSubBits bits)
 //   uint32_t lookup_pair(uint32_t t, w)  pair-table entry of table t for window w (same index as lookup1, kPairOffset entries on)
+//   uint32_t second_table(uint32_t e)    the second-level table behind first-level entry e, as lookup1 wants a table
 // RST: the scan has restart intervals; boundary0 = index of the first boundary at or behind the subsequence's first bit.
-template <bool RST, class Env, class Rec = NoRecord>
+// Policy: WalkPolicy above.  Every policy gives the same state after every completed symbol, from true and from wrong start
+// states alike; a second-level step (kLongStep) never takes a pair, and as it follows its first half without moving `pos`, a long
+// code whose first half starts below `end` is finished by the same walk.
+template <bool RST, class Env, class Rec = NoRecord, class Policy = WalkBranches>
 HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_t begin, uint32_t limit, int z, int k, uint32_t boundary0 = 0,
                                      Rec rec = Rec())
 {
@@ -350,38 +436,89 @@ HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_
     }
     const uint32_t fresh = z == 0 ? 1u : 0u;  // records: index of the next block to start = nblocks + fresh
     if (fresh && pos < end) rec(0u, pos);
+    // kLongStep: `sub` = this step is the second half of a long code: its table is a second-level one and its window `win` the
+    // bits behind the first kHuffFastBits; every other step looks at br.hi
+    uint32_t win = br.hi;
+    bool sub = false;
     while (pos < end) {
         const uint32_t fetched = env.fetch(br.next);
-        uint32_t e = env.lookup1(tcur, br.hi);
-        const uint32_t pr = env.lookup_pair(tcur, br.hi);  // means something behind an AC table only (z != 0)
-        const bool two = z != 0 && (uint32_t)z < (pr >> 10) && pos < pair_end;
+        uint32_t e = env.lookup1(tcur, win);
+        const uint32_t pr = env.lookup_pair(tcur, win);  // means something behind an AC table only (z != 0)
+        const bool two = z != 0 && (uint32_t)z < (pr >> 10) && pos < pair_end && !sub;
         uint32_t tot = two ? (pr & 15u) : (e & 31u);
-        tcur = tsel >> 16;
-        z += two ? (int)((pr >> 4) & 63u) : (int)(e >> 9);
         bool mcu_done = false;
-        if (z >= 64) {  // end of a block, or a code that continues in a second-level table
-            if (!two && (e >> 9) == kZadvLong) {
-                e = env.lookup2(e, br.hi);
-                z += (int)(e >> 9) - (int)kZadvLong;
-                tot = e & 31u;
+        if (Policy::kSelects) {
+            // a first-level entry "long code": nothing moves but the table and the window (a second-level entry never says so)
+            // (every value is computed first and chosen afterwards, one choice per statement: that stays straight-line code)
+            const uint32_t zadv1 = e >> 9, zadv2 = (pr >> 4) & 63u, t2 = env.second_table(e);
+            const bool lng = !two & (zadv1 == kZadvLong) & !sub;
+            tot = lng ? 0u : tot;
+            uint32_t zadv = two ? zadv2 : zadv1;
+            zadv = lng ? 0u : zadv;
+            z += (int)zadv;
+            const bool done = z >= 64;
+            if (done) rec(nblocks + fresh, pos + tot);
+            z = done ? 0 : z;
+            nblocks += done ? 1u : 0u;
+            int k1 = k + 1;
+            k1 = k1 == bpm ? 0 : k1;
+            k = done ? k1 : k;
+            tsel = env.tables(k);  // (of an unchanged k: unchanged)
+            const uint32_t tdc = tsel & 0xFFFFu, tac = tsel >> 16;
+            tcur = lng ? t2 : tac;
+            tcur = done ? tdc : tcur;
+            mcu_done = done & (k == 0);
+            sub = lng;
+        } else if (Policy::kLongStep) {
+            const bool was_sub = sub;
+            sub = false;
+            tcur = tsel >> 16;
+            z += two ? (int)((pr >> 4) & 63u) : (int)(e >> 9);
+            if (z >= 64) {  // end of a block, or a code that continues in a second-level table
+                if (!two && (e >> 9) == kZadvLong && !was_sub) {
+                    z -= (int)kZadvLong;
+                    tot = 0;
+                    tcur = env.second_table(e);
+                    sub = true;
+                } else {
+                    z = 0;
+                    rec(nblocks + fresh, pos + tot);
+                    nblocks++;
+                    if (++k == bpm) k = 0;
+                    tsel = env.tables(k);
+                    tcur = tsel & 0xFFFFu;
+                    mcu_done = k == 0;
+                }
             }
-            if (z >= 64) {
-                z = 0;
-                rec(nblocks + fresh, pos + tot);
-                nblocks++;
-                if (++k == bpm) k = 0;
-                tsel = env.tables(k);
-                tcur = tsel & 0xFFFFu;
-                mcu_done = k == 0;
+        } else {
+            tcur = tsel >> 16;
+            z += two ? (int)((pr >> 4) & 63u) : (int)(e >> 9);
+            if (z >= 64) {  // end of a block, or a code that continues in a second-level table
+                if (!two && (e >> 9) == kZadvLong) {
+                    e = env.lookup2(e, br.hi);
+                    z += (int)(e >> 9) - (int)kZadvLong;
+                    tot = e & 31u;
+                }
+                if (z >= 64) {
+                    z = 0;
+                    rec(nblocks + fresh, pos + tot);
+                    nblocks++;
+                    if (++k == bpm) k = 0;
+                    tsel = env.tables(k);
+                    tcur = tsel & 0xFFFFu;
+                    mcu_done = k == 0;
+                }
             }
         }
         pos += tot;
-        br.consume(tot, fetched);
+        br.consume(tot, fetched);  // (a long code's first half: nothing, the reader stays where it is)
         if (RST && mcu_done && rc.normalise(env, br.hi, &pos, &z, &k)) {
             tsel = env.tables(k);
             tcur = tsel & 0xFFFFu;
             br.start(env, pos);
         }
+        const uint32_t behind = sub_window(br.hi);
+        win = sub ? behind : br.hi;
     }
     SubseqState st;
     st.end_bit = pos;
