@@ -136,6 +136,11 @@ HIPJPEG_API int32_t hipjpegTestFusedUnits(hipjpegHandle_t handle);
  * chunks of the entropy-coded segment; the GPU entropy stage's compact kernel works from them).  Returns the number of chunks, or a
  * negative value when the file does not parse / has no such scan; at most `capacity` counts are written. */
 HIPJPEG_API int32_t hipjpegTestScanChunkDrops(const uint8_t* data, size_t length, int scan_index, uint32_t* drops, int32_t capacity);
+/* Test hook (host only): the steps the GPU entropy stage's position walks take over one AC Huffman table (bits[16], vals[nvals] as in
+ * a DHT segment), from the table's first-level and pair entries: steps[w * 64 + z] for every 10-bit window w and zigzag position z =
+ * bits consumed | zigzag advance << 8 | (two symbols taken as a pair) << 16 | (w opens a code longer than 10 bits) << 17.
+ * steps: 65,536 entries.  Returns 0, or a negative value for a table the stage does not accept. */
+HIPJPEG_API int32_t hipjpegTestPairSteps(const uint8_t bits[16], const uint8_t* vals, int32_t nvals, uint32_t* steps);
 
 /* ---- host-only entry points (usable without a GPU) ---- */
 HIPJPEG_API hipjpegStatus_t hipjpegGetImageInfo(const uint8_t* data, size_t length, hipjpegImageInfo_t* info);

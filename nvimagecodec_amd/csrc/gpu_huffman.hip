@@ -72,7 +72,9 @@ __device__ __forceinline__ uint32_t load_boundary(const uint32_t* boundaries, ui
 // every lane busy, takes both as selects, with the table selection in registers and a long code as a step of its own.  The lane
 // mode of the tail kernels and huff_pos_kernel keep the branches, tsel[] in LDS and the second-level read inside the branch:
 // with a few lanes busy, often one, a branch that is not taken is the cheapest form, and each of the three changes made these
-// kernels slower (profiles/walk_steps/README.md).
+// kernels slower (profiles/walk_steps/README.md).  The select form has a step of its own (select_walk: the MCU position as a
+// countdown, the tables as two halves with the pool's base inside, the chosen entry taken apart once;
+// profiles/walk_step_diet/README.md); what all forms share by construction is the pair table's layout.
 // A/B switch (tools/build_variant.sh) for the builds that were measured: bit 0 = table selection from registers, bit 1 = a long
 // code is a step of its own, bit 2 = both events as selects in huff_sync_kernel, bit 3 = bits 0 and 1 in huff_sync_kernel only.
 #ifndef HJ_WALK_PARTS
@@ -88,10 +90,12 @@ typedef WalkPolicy<kLaneLongStep, false> LaneWalk;
 // per wave.  in_vgprs: the pairs are held in vector registers -- a select between two of them is then one v_bfi_b32, where two
 // scalar operands would cost a second instruction (for the walks that select in every step; the measured builds that selected
 // inside the tail kernels' rare branch kept them scalar, those kernels have no registers to spare).
-template <bool IN_VGPRS>
+// COUNTDOWN: in the order of the select step's position count (make_countdown_classes).
+template <bool IN_VGPRS, bool COUNTDOWN = false>
 __device__ __forceinline__ TableClasses table_classes(const HuffImage& im)
 {
-    TableClasses c = make_table_classes(im.blocks_per_mcu, [&](uint32_t q) { return ((uint32_t)im.k[q].tdc * 2) | ((uint32_t)im.k[q].tac * 2 << 16); });
+    const auto of = [&](uint32_t q) { return ((uint32_t)im.k[q].tdc * 2) | ((uint32_t)im.k[q].tac * 2 << 16); };
+    TableClasses c = COUNTDOWN ? make_countdown_classes(im.blocks_per_mcu, of) : make_table_classes(im.blocks_per_mcu, of);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         c.pair[i] = HJ_UNIFORM(c.pair[i]);
@@ -111,6 +115,7 @@ struct DevEnv {
     uint32_t pool;         // LDS byte address of the lookup tables
     const HJ_LDS uint32_t* tsel;  // per MCU position: BYTE offsets of the DC / AC first-level tables, packed lo/hi
     TableClasses classes;         // the same selection from registers (table_classes), for the walks that select in every step
+    StepTables step;              // ... as the select step takes it: DC and AC halves as LDS addresses (split_classes)
     const uint32_t* boundaries;
     uint32_t num_boundaries;
     __device__ __forceinline__ uint32_t boundary(uint32_t i) const { return load_boundary(boundaries, num_boundaries, i); }
@@ -179,16 +184,21 @@ __device__ __forceinline__ SubseqState walk_with(bool rst, bool record, const Hu
     return record ? decode_subsequence<false, Env, SlotRecorder, Policy>(geom, env, begin, limit, z, k, 0, rec)
                   : decode_subsequence<false, Env, NoRecord, Policy>(geom, env, begin, limit, z, k);
 }
-// an environment that selects the tables from registers: four classes, or at most two
-template <class Env>
-struct FourClasses : Env {
-    __device__ __forceinline__ explicit FourClasses(const Env& e) : Env(e) {}
-    __device__ __forceinline__ uint32_t tables(int k) const { return select_tables(this->classes, (uint32_t)k); }
-};
-template <class Env>
-struct TwoClasses : Env {
-    __device__ __forceinline__ explicit TwoClasses(const Env& e) : Env(e) {}
-    __device__ __forceinline__ uint32_t tables(int k) const { return select_tables2(this->classes, (uint32_t)k); }
+// The environment of the select step (select_walk): the tables of an MCU position from registers -- four classes, or at most two --
+// as LDS addresses with the pool's base inside, so that a lookup adds nothing but the window's index.
+template <class Env, bool FOUR>
+struct StepEnv : Env {
+    __device__ __forceinline__ explicit StepEnv(const Env& e) : Env(e) {}
+    __device__ __forceinline__ void step_tables(uint32_t d, uint32_t* tdc, uint32_t* tac) const { select_halves<FOUR>(this->step, d, tdc, tac); }
+    __device__ __forceinline__ uint32_t step_entry(uint32_t t, uint32_t w) const
+    {
+        return *(const HJ_LDS uint16_t*)(uintptr_t)(t + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
+    }
+    __device__ __forceinline__ uint32_t step_pair(uint32_t t, uint32_t w) const  // the same address + a constant
+    {
+        return *(const HJ_LDS uint16_t*)(uintptr_t)(t + 2 * kPairOffset + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
+    }
+    __device__ __forceinline__ uint32_t step_second(uint32_t e) const { return second_table_of(e, 7u, this->pool); }  // / 64 entries -> bytes
 };
 template <class Policy, class Env>
 __device__ __forceinline__ SubseqState walk_subsequence(bool rst, bool record, const HuffGeom& geom, const Env& env, uint32_t begin, uint32_t limit, int z,
@@ -196,11 +206,12 @@ __device__ __forceinline__ SubseqState walk_subsequence(bool rst, bool record, c
 {
     // the select form looks the tables up in every step: from registers, and the everyday scan's two classes get the short
     // selection (a uniform choice)
-    if (Policy::kSelects) {
-        if (env.classes.bit1 == 0) return walk_with<Policy>(rst, record, geom, TwoClasses<Env>(env), begin, limit, z, k, boundary0, rec);
-        return walk_with<Policy>(rst, record, geom, FourClasses<Env>(env), begin, limit, z, k, boundary0, rec);
+    if constexpr (Policy::kSelects) {
+        if (env.classes.bit1 == 0) return walk_with<Policy>(rst, record, geom, StepEnv<Env, false>(env), begin, limit, z, k, boundary0, rec);
+        return walk_with<Policy>(rst, record, geom, StepEnv<Env, true>(env), begin, limit, z, k, boundary0, rec);
+    } else {
+        return walk_with<Policy>(rst, record, geom, env, begin, limit, z, k, boundary0, rec);
     }
-    return walk_with<Policy>(rst, record, geom, env, begin, limit, z, k, boundary0, rec);
 }
 
 // Cooperative staging of stream words: lane t brings in row t = subsequence first_row + t of the image (first_row may be -1:
@@ -292,7 +303,16 @@ __device__ __forceinline__ DevEnv make_env(WgShared& sh, HJ_LDS uint16_t* pool, 
     env.row_word0 = env.word0;
     env.pool = (uint32_t)(uintptr_t)pool;
     env.tsel = (const HJ_LDS uint32_t*)sh.tsel;
-    env.classes = table_classes<true>(im);
+    // (tables(k) reads the classes only in the measurement builds with kLaneRegisters, and wants them in order of k there; everywhere
+    // else they say how many there are, which the countdown order says as well)
+    const TableClasses down = table_classes<true, true>(im);
+    env.classes = kLaneRegisters ? table_classes<true>(im) : down;
+    env.step = split_classes(down, 1u, env.pool);  // (the classes hold byte offsets)
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        asm("" : "+v"(env.step.dc[i]));
+        asm("" : "+v"(env.step.ac[i]));
+    }
     env.boundaries = geom.boundaries;
     env.num_boundaries = geom.num_boundaries;
     return env;

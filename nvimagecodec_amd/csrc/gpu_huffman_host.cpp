@@ -159,12 +159,12 @@ size_t expand_table(const HuffSpec& s, bool is_dc, uint16_t* pool, size_t base)
         // pair table (huffman_gpu_core.h): window w = a first symbol of t1 bits and, in the 10 - t1 bits behind it, a whole second one
         uint16_t* pair = first + kPairOffset;
         for (uint32_t w = 0; w < (1u << kHuffFastBits); w++) {
-            pair[w] = 0;
             const uint32_t e1 = first[w], t1 = e1 & 31u, z1 = e1 >> 9;
+            pair[w] = (uint16_t)e1;  // no pair here: the single step
             if (e1 == kEntryInvalid || z1 == kZadvLong || z1 == 64u || t1 + 2 > (uint32_t)kHuffFastBits) continue;
             const uint32_t e2 = first[(w << t1) & ((1u << kHuffFastBits) - 1)], t2 = e2 & 31u, z2 = e2 >> 9;
             if (e2 == kEntryInvalid || z2 == kZadvLong || t1 + t2 > (uint32_t)kHuffFastBits) continue;
-            pair[w] = (uint16_t)make_pair_entry(t1 + t2, z2 == 64u ? 63u : z1 + z2, 64u - z1);
+            pair[w] = (uint16_t)make_pair_entry(t1 + t2, z2 == 64u ? 63u : z1 + z2);
         }
     }
     return used;
@@ -223,6 +223,22 @@ void build_gpu_pool(const ScanHeader& sc, HuffImage* im, uint16_t* pool)
         im->k[k].tdc = (uint16_t)dc_off[sc.td[c]];
         im->k[k].tac = (uint16_t)ac_off[sc.ta[c]];
     }
+}
+
+bool pair_table_steps(const HuffSpec& ac, uint32_t* out)
+{
+    const size_t words = table_words(ac, false);
+    if (!words || words > (size_t)kMaxPoolWords) return false;
+    std::vector<uint16_t> pool(words);
+    expand_table(ac, false, pool.data(), 0);
+    for (uint32_t w = 0; w < (1u << kHuffFastBits); w++)
+        for (uint32_t z = 0; z < 64; z++) {
+            const uint32_t e = pool[w], pr = pool[kPairOffset + w];
+            const bool two = pair_fits(z, e), lng = e >= (kZadvLong << 9);
+            const uint32_t x = lng ? 0u : two ? pr : e;
+            out[w * 64 + z] = (x & 31u) | ((x >> 9) << 8) | ((two && pr != e ? 1u : 0u) << 16) | ((lng ? 1u : 0u) << 17);
+        }
+    return true;
 }
 
 void fill_huff_image(const FrameInfo& f, const ScanHeader& sc, uint32_t stream_bytes, HuffImage* im)
@@ -286,6 +302,16 @@ struct HostEnv {
     int zigzag(int z) const { return kZigzagDeviceGpuHost[z]; }
     int16_t* buf;  // block buffer: 64 coefficients
     void put(int index, int value) const { buf[index] = (int16_t)value; }
+    // the select step (select_walk): the tables from the classes as the kernels hold them, in the step's own position count
+    TableClasses classes;
+    StepTables step;
+    void step_tables(uint32_t d, uint32_t* tdc, uint32_t* tac) const
+    {
+        select_halves<true>(step, d, tdc, tac);
+    }
+    uint32_t step_entry(uint32_t t, uint32_t w) const { return lookup1(t, w); }
+    uint32_t step_pair(uint32_t t, uint32_t w) const { return lookup_pair(t, w); }
+    uint32_t step_second(uint32_t e) const { return second_table_of(e, 6u, 0u); }
 };
 
 // The window of cooperative_subsequence (huffman_gpu_core.h) on the host: what the 64 lanes of the kernel's wave look up at once.
@@ -355,7 +381,9 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
         for (size_t y = 0; y < rows; y++) memset(coef + y * bw * 64, 0x5A, cols * 128);
     }
     int16_t block_buffer[64] = {0};
-    const HostEnv env{&im, block_buffer};
+    HostEnv env{&im, block_buffer, TableClasses(), StepTables()};
+    env.classes = make_countdown_classes(im.blocks_per_mcu, [&](uint32_t q) { return env.tables((int)q); });
+    env.step = split_classes(env.classes, 1u, 0u);
     const HuffGeom geom = make_geom(im);
     const uint32_t ns = im.num_subseq;
     std::vector<SubseqState> cur(ns), nxt(ns);
@@ -371,6 +399,15 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
         if (!classes.complete) return 5;
         for (uint32_t q = 0; q < im.blocks_per_mcu; q++)
             if (select_tables(classes, q) != env.tables((int)q)) return 5;
+        // ... and the select step's own form of them: halves, by the position as that step counts it, downwards.  (The step's
+        // count itself is checked with every walk below: its end state carries the position counted upwards again, recomputed from
+        // the countdown, and must equal that of the branch forms, which count upwards.)
+        if (!env.classes.complete) return 5;
+        for (uint32_t q = 0; q < im.blocks_per_mcu; q++) {
+            uint32_t tdc, tac;
+            env.step_tables(im.blocks_per_mcu - 1u - q, &tdc, &tac);
+            if ((tdc | (tac << 16)) != env.tables((int)q)) return 5;
+        }
     }
     // Every walk runs in the form huff_sync_kernel uses (WalkSelects) and again in the form of the tail kernels' lanes and the
     // position kernel (WalkBranches), and in the long-step branch form: same end state and same record, from true and from wrong

@@ -38,6 +38,12 @@ size_t gpu_pool_words(const ScanHeader& sc);
 // Call after fill_huff_image().
 void build_gpu_pool(const ScanHeader& sc, HuffImage* im, uint16_t* pool);
 
+// Test support (hipjpegTestPairSteps): the step a position walk takes at every 10-bit window w of AC table `ac` from every zigzag
+// position z, from the table's first-level and pair entries as build_gpu_pool() lays them out and with the walks' own test
+// (pair_fits): out[w * 64 + z] = bits consumed | zigzag advance << 8 | (a pair was taken) << 16 | (the window opens a long code, which
+// the step leaves to the second level: nothing consumed) << 17.  False for a table the stage would refuse.
+bool pair_table_steps(const HuffSpec& ac, uint32_t* out);
+
 // Describes scan `sc` of frame `f`: every field except the pointers (stream, pool, coef, dc_diff, dc_plane), first_subseq and the
 // table offsets.  Slot i of the per-component arrays (coef, dc_plane, blocks_w, comp_h/v/k0, HuffK::comp) is the scan's i-th
 // component, frame component sc.comp_index[i].

@@ -535,6 +535,21 @@ int32_t hipjpegTestScanChunkDrops(const uint8_t* data, size_t length, int scan_i
     return result;
 }
 
+int32_t hipjpegTestPairSteps(const uint8_t bits[16], const uint8_t* vals, int32_t nvals, uint32_t* steps)
+{
+    int32_t result = -1;
+    if (!test_hooks_enabled() || !bits || !vals || !steps || nvals < 0 || nvals > 256) return result;
+    (void)guarded([&]() -> hipjpegStatus_t {
+        hipjpeg::HuffSpec spec;
+        for (int l = 1; l <= 16; l++) spec.bits[l] = bits[l - 1];
+        for (int32_t i = 0; i < nvals; i++) spec.vals[i] = vals[i];
+        spec.present = true;
+        if (hipjpeg::pair_table_steps(spec, steps)) result = 0;
+        return HIPJPEG_STATUS_SUCCESS;
+    });
+    return result;
+}
+
 int32_t hipjpegTestHostFallbacks(hipjpegHandle_t handle)
 {
     // the batch the last Wait settled, if no batch has been planned since; else the current page's

@@ -69,15 +69,24 @@ constexpr int kMaxPoolWords = 12288;   // uint16 entries of lookup tables per im
 HJ_HD constexpr uint32_t make_entry(uint32_t total, uint32_t nb, uint32_t zadv) { return total | (nb << 5) | (zadv << 9); }
 // PAIR table of an AC table (directly behind its first level, same index): the walks that only track positions -- the
 // synchronisation passes and the position pass, 2/3 of the stage's time -- take two AC symbols per step where the window holds
-// both completely (half of all steps on a q90 photo).  Entry: bits 0-3 = bits of both symbols together (<= kHuffFastBits),
-// bits 4-9 = zigzag advance of both (63 when the second one is EOB: enough to end any block from an AC position), bits 10-15 =
-// the zigzag positions from which the pair may be taken: z < that many, i.e. 64 - the first symbol's own advance, so that the
-// first symbol keeps the block open; 0 = no pair here (first symbol EOB / long code / no second symbol in the window).  The
-// walker also wants the second symbol to start inside its range -- then the result is exactly that of two single steps.
+// both completely (half of all steps on a q90 photo).  A pair entry has the layout of a first-level entry, so that a step chooses
+// the entry first and takes it apart once:
+//   bits 0-4   bits of both symbols together (<= kHuffFastBits)
+//   bits 5-8   0
+//   bits 9-15  zigzag advance of both (63 when the second one is EOB: enough to end any block from an AC position)
+// "No pair here" (first symbol EOB / long code / no code / no second symbol in the window) is the first-level entry itself: taking
+// it is the single step.  A pair may be taken where its first symbol keeps the block open -- z + (the first-level entry's own
+// advance) < 64, pair_fits below; the first-level entry is read in every step anyway, so the pair entry carries no limit of its
+// own -- and where the second symbol starts inside the walker's range: then the result is exactly that of two single steps.
 constexpr uint32_t kPairOffset = 1u << kHuffFastBits;  // entries between an AC table's first level and its pair table
-HJ_HD constexpr uint32_t make_pair_entry(uint32_t total, uint32_t zadv, uint32_t z_below) { return total | (zadv << 4) | (z_below << 10); }
-constexpr uint32_t kEntryInvalid = 1u | (15u << 5) | (1u << 9);
 constexpr uint32_t kZadvLong = 127;
+HJ_HD constexpr uint32_t make_pair_entry(uint32_t total, uint32_t zadv) { return make_entry(total, 0u, zadv); }
+// May a walk at zigzag position z take the pair entry beside the first-level entry e?  1 <= z (an AC position: behind a DC table
+// there is no pair table) and z + zadv(e) < 64, as ONE unsigned compare on the entry itself:
+// (z - 1) * 512 < (63 - zadv) * 512 - (bits 0-8 of e).  z = 0 wraps the left side to the top and is refused (no entry has zadv 63,
+// so no limit gets as far).  An entry with zadv 64 or 127 wraps the limit and is accepted, harmlessly: its pair entry is itself.
+HJ_HD bool pair_fits(uint32_t z, uint32_t e) { return (z << 9) - 512u < 0x7E00u - e; }
+constexpr uint32_t kEntryInvalid = 1u | (15u << 5) | (1u << 9);
 
 // One block position k inside the MCU (k < blocks_per_mcu <= 10).
 struct HuffK {
@@ -368,6 +377,49 @@ HJ_HD uint32_t select_tables(const TableClasses& c, uint32_t k)
 }
 // the everyday case, at most two classes (bit1 == 0; luma and chroma, or one component): a bit mask and one select
 HJ_HD uint32_t select_tables2(const TableClasses& c, uint32_t k) { return bit_select(bit_mask(c.bit0, k), c.pair[1], c.pair[0]); }
+// The select step (select_walk below) keeps the MCU position as a COUNTDOWN d = blocks_per_mcu - 1 - k and wants the DC and the AC
+// table of a position as two values, each as its lookup takes a table (on the device an LDS address, the pool's base included):
+// the classes are built in countdown order (bit d of bit0 / bit1 = class of position blocks_per_mcu - 1 - d) and split once, outside
+// the loop; a selection is then the mask and one bitwise select per half.
+struct StepTables {
+    uint32_t dc[4], ac[4];
+    uint32_t bit0, bit1;
+};
+// of(k) as for make_table_classes
+template <class TablesOf>
+HJ_HD TableClasses make_countdown_classes(uint32_t blocks_per_mcu, const TablesOf& of)
+{
+    return make_table_classes(blocks_per_mcu, [&](uint32_t q) { return of(blocks_per_mcu - 1u - q); });
+}
+// unit = what one count of a table offset is in the lookup's terms, base = the pool's place there
+HJ_HD StepTables split_classes(const TableClasses& c, uint32_t unit, uint32_t base)
+{
+    StepTables s;
+    for (int i = 0; i < 4; i++) {
+        s.dc[i] = base + (c.pair[i] & 0xFFFFu) * unit;
+        s.ac[i] = base + (c.pair[i] >> 16) * unit;
+    }
+    s.bit0 = c.bit0;
+    s.bit1 = c.bit1;
+    return s;
+}
+// FOUR: up to four classes; else the everyday case, at most two (bit1 == 0)
+template <bool FOUR>
+HJ_HD void select_halves(const StepTables& s, uint32_t d, uint32_t* tdc, uint32_t* tac)
+{
+    const uint32_t a = bit_mask(s.bit0, d);
+    if (FOUR) {
+        const uint32_t b = bit_mask(s.bit1, d);
+        *tdc = bit_select(b, bit_select(a, s.dc[3], s.dc[2]), bit_select(a, s.dc[1], s.dc[0]));
+        *tac = bit_select(b, bit_select(a, s.ac[3], s.ac[2]), bit_select(a, s.ac[1], s.ac[0]));
+    } else {
+        *tdc = bit_select(a, s.dc[1], s.dc[0]);
+        *tac = bit_select(a, s.ac[1], s.ac[0]);
+    }
+}
+// The second-level table behind a first-level entry "long code", in units of 64 >> shift entries from `base`.  Such an entry has
+// all of bits 9-15 set, so its pool offset / 64 (bits 0-8), scaled, is the whole entry shifted minus a constant: one shift-add.
+HJ_HD uint32_t second_table_of(uint32_t e, uint32_t shift, uint32_t base) { return (e << shift) + (base - (kZadvLong << (9u + shift))); }
 
 // How decode_subsequence treats its two rare events, the end of a block and a code longer than kHuffFastBits.  Rare for a lane --
 // 6 % and 2 % of a q90 photograph's symbols -- and almost certain for a wave of 64 lanes at independent places of the stream.
@@ -376,8 +428,9 @@ HJ_HD uint32_t select_tables2(const TableClasses& c, uint32_t k) { return bit_se
 //              kHuffSubBits bits behind the first kHuffFastBits, and that step's ordinary lookup completes the symbol.  No table
 //              read inside a branch.  false: the second-level entry is read inside the rare branch (Env::lookup2).
 //   kSelects   both events are predicated straight-line code (only the record store stays conditional), the tables of the MCU
-//              position are looked up in every step (Env::tables from registers: TableClasses): for huff_sync_kernel, whose
-//              waves have every lane busy.
+//              position are looked up in every step (from registers: StepTables): for huff_sync_kernel, whose waves have every
+//              lane busy.  This form is a routine of its own, select_walk, with its own bookkeeping (the MCU position counts
+//              down); decode_subsequence hands over to it.
 // A lone lane gains from a branch that is not taken, and from the table read that hides inside it: the lane mode of the tail
 // kernels and the position kernel keep WalkBranches, the walk as it was before there were policies.  (A long step in the branch
 // form, WalkLongBranches, is slower than either in every kernel; it is kept as the measured middle step and checked with the
@@ -393,6 +446,95 @@ typedef WalkPolicy<true, true> WalkSelects;
 // the window that indexes a second-level table through lookup1: its kHuffFastBits top bits = the kHuffSubBits bits behind the
 // first kHuffFastBits of w
 HJ_HD uint32_t sub_window(uint32_t w) { return (w << kHuffFastBits) >> (kHuffFastBits - kHuffSubBits); }
+
+// The select form of the synchronisation decode (WalkSelects: huff_sync_kernel, whose vector unit is the limiter -- every
+// instruction of this loop is worth several microseconds per 256-picture batch; DESIGN.md 3.2 has each part's measurement).  Same
+// contract as decode_subsequence below.  One step:
+//   entries   the first-level entry e and the pair entry pr of the current table for the reader's window; behind a long code the
+//             table is a second-level one and the window the kHuffSubBits bits behind the first kHuffFastBits;
+//   choice    x = pr where the pair may be taken (pair_fits, the second symbol starts inside the range, not a second half), else
+//             e; x = 0 where e says "long code" -- nothing is consumed, nothing advances.  The total and the zigzag advance are
+//             extracted from x, once;
+//   block end z past 63: the block is counted and recorded, and the countdown d moves on: a subtract with borrow, and an unsigned
+//             minimum with blocks_per_mcu - 1 as the wrap (behind position 0 it reads 0xFFFFFFFF);
+//   tables    the DC and AC table of position d from registers (StepTables); the next table is the second-level one behind e,
+//             the DC table behind a block end, else the AC table.
+// Env supplies, beside cursor / fetch / boundary:
+//   void     step_tables(uint32_t d, uint32_t* tdc, uint32_t* tac)   the tables of countdown position d
+//   uint32_t step_entry(t, w), step_pair(t, w)                       lookup1 / lookup_pair for a table as step_tables gives it
+//   uint32_t step_second(uint32_t e)                                 the second-level table behind the long entry e, likewise
+template <bool RST, class Env, class Rec>
+HJ_HD SubseqState select_walk(const HuffGeom& im, const Env& env, uint32_t begin, uint32_t limit, int z0, int k0, uint32_t boundary0, Rec rec)
+{
+    uint32_t pos = begin, nblocks = 0, z = (uint32_t)z0;
+    const uint32_t end = limit < im.total_bits ? limit : im.total_bits;
+    const uint32_t pair_end = end > (uint32_t)kHuffFastBits - 2 ? end - ((uint32_t)kHuffFastBits - 2) : 0;  // see decode_subsequence
+    const uint32_t bpm1 = im.blocks_per_mcu - 1u;
+    uint32_t d = bpm1 - (uint32_t)k0;
+    uint32_t tdc, tac;
+    env.step_tables(d, &tdc, &tac);
+    uint32_t tcur = z == 0 ? tdc : tac;
+    BitReader br;
+    br.start(env, pos);
+    RestartCursor rc;
+    if (RST) {
+        rc.start(env, boundary0, pos);
+        int zi = (int)z, ki = k0;
+        if (rc.normalise(env, br.hi, &pos, &zi, &ki)) {
+            z = (uint32_t)zi;
+            d = bpm1 - (uint32_t)ki;
+            env.step_tables(d, &tdc, &tac);
+            tcur = tdc;
+            br.start(env, pos);
+        }
+    }
+    const uint32_t fresh = z == 0 ? 1u : 0u;
+    if (fresh && pos < end) rec(0u, pos);
+    uint32_t win = br.hi;  // the reader's window; in the second half of a long code the bits behind the first kHuffFastBits
+    bool sub = false;      // this step is the second half of a long code
+    while (pos < end) {
+        const uint32_t fetched = env.fetch(br.next);
+        const uint32_t e = env.step_entry(tcur, win);
+        const uint32_t pr = env.step_pair(tcur, win);  // means something behind an AC table only
+        const bool two = pair_fits(z, e) & (pos < pair_end) & !sub;
+        const bool lng = (e >= (kZadvLong << 9)) & !sub;  // (beside a long entry the pair entry is that entry itself)
+        uint32_t x = two ? pr : e;
+        x = lng ? 0u : x;
+        const uint32_t tot = x & 31u, zadv = x >> 9;
+        const uint32_t t2 = env.step_second(e);
+        z += zadv;
+        const bool done = z >= 64u;
+        if (done) rec(nblocks + fresh, pos + tot);
+        z = done ? 0u : z;
+        nblocks += done ? 1u : 0u;
+        d -= done ? 1u : 0u;
+        d = d < bpm1 ? d : bpm1;
+        const bool mcu_done = done & (d == bpm1);
+        env.step_tables(d, &tdc, &tac);  // (of an unchanged position: unchanged)
+        tcur = lng ? t2 : tac;
+        tcur = done ? tdc : tcur;
+        sub = lng;
+        pos += tot;
+        br.consume(tot, fetched);  // (a long code's first half: nothing, the reader stays where it is)
+        if (RST && mcu_done) {
+            int zi = (int)z, ki = 0;
+            if (rc.normalise(env, br.hi, &pos, &zi, &ki)) {
+                z = (uint32_t)zi;
+                d = bpm1;
+                env.step_tables(d, &tdc, &tac);
+                tcur = tdc;
+                br.start(env, pos);
+            }
+        }
+        const uint32_t behind = sub_window(br.hi);
+        win = sub ? behind : br.hi;
+    }
+    SubseqState st;
+    st.end_bit = pos;
+    st.zk = (uint16_t)(((bpm1 - d) << 8) | z);  // the position, counted upwards again
+    st.nblocks = (uint16_t)(nblocks > 0xFFFF ? 0xFFFF : nblocks);
+    return st;
+}
 
 // Synchronisation decode: the symbols that START in [begin, limit) (and before total_bits), beginning in state (z, k).
 // Tracks the decoder state and counts the blocks completed; rec(i, pos) is told where each block starts (see the block-start records
@@ -415,6 +557,7 @@ HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_
                                      Rec rec = Rec())
 {
     static_assert(!RST || std::is_same<Rec, NoRecord>::value, "records are not taken across restart boundaries");
+    if constexpr (Policy::kSelects) return select_walk<RST>(im, env, begin, limit, z, k, boundary0, rec);
     uint32_t pos = begin, nblocks = 0;
     const uint32_t end = limit < im.total_bits ? limit : im.total_bits;
     // a pair's first symbol has at most kHuffFastBits - 2 bits: from here on the second one might start outside the range
@@ -442,43 +585,23 @@ HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_
     bool sub = false;
     while (pos < end) {
         const uint32_t fetched = env.fetch(br.next);
-        uint32_t e = env.lookup1(tcur, win);
+        const uint32_t e = env.lookup1(tcur, win);
         const uint32_t pr = env.lookup_pair(tcur, win);  // means something behind an AC table only (z != 0)
-        const bool two = z != 0 && (uint32_t)z < (pr >> 10) && pos < pair_end && !sub;
-        uint32_t tot = two ? (pr & 15u) : (e & 31u);
+        const bool two = pair_fits((uint32_t)z, e) && pos < pair_end && !sub;
+        // the entry the step takes: beside "long code" and "end of block" the pair entry is the single entry itself
+        const uint32_t x = two ? pr : e;
+        uint32_t tot = x & 31u;
         bool mcu_done = false;
-        if (Policy::kSelects) {
-            // a first-level entry "long code": nothing moves but the table and the window (a second-level entry never says so)
-            // (every value is computed first and chosen afterwards, one choice per statement: that stays straight-line code)
-            const uint32_t zadv1 = e >> 9, zadv2 = (pr >> 4) & 63u, t2 = env.second_table(e);
-            const bool lng = !two & (zadv1 == kZadvLong) & !sub;
-            tot = lng ? 0u : tot;
-            uint32_t zadv = two ? zadv2 : zadv1;
-            zadv = lng ? 0u : zadv;
-            z += (int)zadv;
-            const bool done = z >= 64;
-            if (done) rec(nblocks + fresh, pos + tot);
-            z = done ? 0 : z;
-            nblocks += done ? 1u : 0u;
-            int k1 = k + 1;
-            k1 = k1 == bpm ? 0 : k1;
-            k = done ? k1 : k;
-            tsel = env.tables(k);  // (of an unchanged k: unchanged)
-            const uint32_t tdc = tsel & 0xFFFFu, tac = tsel >> 16;
-            tcur = lng ? t2 : tac;
-            tcur = done ? tdc : tcur;
-            mcu_done = done & (k == 0);
-            sub = lng;
-        } else if (Policy::kLongStep) {
+        tcur = tsel >> 16;
+        z += (int)(x >> 9);
+        if (Policy::kLongStep) {
             const bool was_sub = sub;
             sub = false;
-            tcur = tsel >> 16;
-            z += two ? (int)((pr >> 4) & 63u) : (int)(e >> 9);
             if (z >= 64) {  // end of a block, or a code that continues in a second-level table
-                if (!two && (e >> 9) == kZadvLong && !was_sub) {
+                if ((x >> 9) == kZadvLong && !was_sub) {
                     z -= (int)kZadvLong;
                     tot = 0;
-                    tcur = env.second_table(e);
+                    tcur = env.second_table(x);
                     sub = true;
                 } else {
                     z = 0;
@@ -491,13 +614,11 @@ HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_
                 }
             }
         } else {
-            tcur = tsel >> 16;
-            z += two ? (int)((pr >> 4) & 63u) : (int)(e >> 9);
             if (z >= 64) {  // end of a block, or a code that continues in a second-level table
-                if (!two && (e >> 9) == kZadvLong) {
-                    e = env.lookup2(e, br.hi);
-                    z += (int)(e >> 9) - (int)kZadvLong;
-                    tot = e & 31u;
+                if ((x >> 9) == kZadvLong) {
+                    const uint32_t e2 = env.lookup2(x, br.hi);
+                    z += (int)(e2 >> 9) - (int)kZadvLong;
+                    tot = e2 & 31u;
                 }
                 if (z >= 64) {
                     z = 0;
@@ -517,8 +638,12 @@ HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_
             tcur = tsel & 0xFFFFu;
             br.start(env, pos);
         }
-        const uint32_t behind = sub_window(br.hi);
-        win = sub ? behind : br.hi;
+        if (Policy::kLongStep) {
+            const uint32_t behind = sub_window(br.hi);
+            win = sub ? behind : br.hi;
+        } else {
+            win = br.hi;
+        }
     }
     SubseqState st;
     st.end_bit = pos;
@@ -641,12 +766,13 @@ HJ_HD void position_subsequence(const HuffGeom& im, const Env& env, uint32_t beg
         const uint32_t fetched = env.fetch(br.next);
         uint32_t e = env.lookup1(tcur, br.hi);
         const uint32_t pr = env.lookup_pair(tcur, br.hi);
-        const bool two = z != 0 && (uint32_t)z < (pr >> 10) && pos < pair_end;
-        if (!two && (e >> 9) == kZadvLong) e = env.lookup2(e, br.hi);
-        const uint32_t tot = two ? (pr & 15u) : (e & 31u);
+        const bool two = pair_fits((uint32_t)z, e) && pos < pair_end;
+        e = two ? pr : e;  // (the pair entry of a long code: itself)
+        if ((e >> 9) == kZadvLong) e = env.lookup2(e, br.hi);
+        const uint32_t tot = e & 31u;
         pos += tot;
         br.consume(tot, fetched);
-        z += two ? (int)((pr >> 4) & 63u) : (int)(e >> 9);
+        z += (int)(e >> 9);
         tcur = tsel >> 16;
         if (z >= 64) {
             z = 0;
