@@ -71,7 +71,8 @@ typedef enum {
 #define HIPJPEG_FLAG_GPU_HUFFMAN 2u      /* entropy-decode eligible streams on the GPU (sequential Huffman in up to 4 scans that code every
                                             component once, in any component order, each scan a stream of its own, with or without restart
                                             intervals; progressive SOF2 with up to 24 scans); the host then only finds the scans.  Other
-                                            streams keep the host entropy stage.  Encoding: entropy-code on the GPU every image without a
+                                            streams keep the host entropy stage -- progressive files with restart intervals among them,
+                                            unless HIPJPEG_FLAG_GPU_PROGRESSIVE_INTERVALS is set too.  Encoding: entropy-code on the GPU every image without a
                                             restart interval -- baseline with Annex-K or optimized tables, or progressive output -- see
                                             hipjpegEncodeBatchEntropy; images with a restart interval stay with the host coder unless
                                             HIPJPEG_FLAG_GPU_RESTART_INTERVALS is set too. */
@@ -79,6 +80,15 @@ typedef enum {
                                             selects JDCT_IFAST): the pixels are those of libjpeg-turbo's x86-64 SIMD routine
                                             jsimd_idct_ifast_sse2, which differs from jidctfst.c only on streams whose samples leave the
                                             gamut.  Without the flag: JDCT_ISLOW (jsimd_idct_islow), the library's default. */
+#define HIPJPEG_FLAG_GPU_PROGRESSIVE_INTERVALS 16u /* decoding, together with HIPJPEG_FLAG_GPU_HUFFMAN (alone it means nothing): progressive
+                                            files in which EVERY scan has a restart interval take the GPU entropy stage too, a lane per
+                                            restart interval (csrc/progressive_interval_core.h).  Rules: those of progressive files without
+                                            restart intervals, and every scan's interval is 1..65535 with each interval but the last closed by
+                                            its marker, and the AC scans of a component share one interval; other such files keep the host
+                                            entropy stage.  Honoured by hipjpegDecodeBatch / Host / Submit, hipjpegDecodeCoefficientsBatch and
+                                            hipjpegTranscodeBatch; plugin option hipjpeg_decoder:gpu_progressive_intervals=1.  Default off:
+                                            without it such files decode on the host entropy stage as before.  (8u is
+                                            HIPJPEG_FLAG_GPU_RESTART_INTERVALS of the coder, ignored when decoding.) */
 
 typedef struct {
     int32_t width, height, num_components;
@@ -170,6 +180,15 @@ HIPJPEG_API hipjpegStatus_t hipjpegEntropyDecodeGpuAlgorithmHost(const uint8_t* 
                                                                  size_t coef_capacity_bytes, uint64_t comp_offsets[4],
                                                                  int32_t* sync_passes);
 
+/* The algorithm of HIPJPEG_FLAG_GPU_PROGRESSIVE_INTERVALS (a lane per restart interval for the block start positions and the DC
+ * planes, csrc/progressive_interval_core.h, then the replay of csrc/progressive_gpu_core.h) executed on the host with the very code the
+ * kernels run.  Same output layout as hipjpegEntropyDecodeHost.  HIPJPEG_STATUS_UNSUPPORTED for everything the interval kernels do not
+ * take: sequential streams, progressive files without restart intervals, a scan whose markers do not close every interval but the
+ * last, AC scans of one component with different restart intervals.  hipjpegEntropyDecodeGpuAlgorithmHost keeps answering
+ * UNSUPPORTED for progressive files with restart intervals. */
+HIPJPEG_API hipjpegStatus_t hipjpegEntropyDecodeGpuIntervalAlgorithmHost(const uint8_t* data, size_t length, int16_t* coef,
+                                                                         size_t coef_capacity_bytes, uint64_t comp_offsets[4]);
+
 /* ---- device pipeline ---- */
 /* num_host_threads: CPU threads for the entropy stage (0 = hardware concurrency). */
 HIPJPEG_API hipjpegStatus_t hipjpegCreate(hipjpegHandle_t* handle, int device_id, int num_host_threads);
@@ -210,6 +229,14 @@ HIPJPEG_API hipjpegStatus_t hipjpegDecodeBatchWait(hipjpegHandle_t handle, hipjp
  * input pointer; HIPJPEG_NO_ZERO_COPY=1 in the environment switches it off.  The caller keeps the memory valid until the batch has been
  * waited for (as for every Submit).  Returns how many images of the handle's current batch went that way (after Transfer / Submit). */
 HIPJPEG_API int32_t hipjpegDecodeBatchZeroCopyImages(hipjpegHandle_t handle);
+/* Images of the handle's current batch that took the interval kernels (HIPJPEG_FLAG_GPU_PROGRESSIVE_INTERVALS); they are counted among
+ * the GPU-decoded images of hipjpegDecodeBatchEntropyStats too.  Negative without a handle. */
+HIPJPEG_API int32_t hipjpegDecodeBatchIntervalImages(hipjpegHandle_t handle);
+/* ... of which the interval kernels or the replay flagged (a stream they could not vouch for: damaged data) so that the host entropy
+ * decoder decoded the image again and its verdict became the image's status.  Of the batch the last hipjpegDecodeBatchWait settled if no
+ * batch has been planned since, else of the current batch once its statuses are final (hipjpegDecodeBatchGetStatuses, a blocking
+ * hipjpegDecodeBatch / hipjpegDecodeCoefficientsBatch / hipjpegTranscodeBatch).  0 for undamaged files.  Negative without a handle. */
+HIPJPEG_API int32_t hipjpegDecodeBatchIntervalTakeovers(hipjpegHandle_t handle);
 /* What the current batch's transfer puts on PCIe (descriptors, tables, bitstreams of GPU-decoded pictures, coefficients of host-decoded ones)
  * and how many host-decoded pictures went as zero-run-compressed streams rather than dense blocks (HIPJPEG_DENSE_STAGING=1 switches that off). */
 HIPJPEG_API hipjpegStatus_t hipjpegDecodeBatchTransferStats(hipjpegHandle_t handle, uint64_t* h2d_bytes, int32_t* sparse_images);

@@ -14,6 +14,7 @@ OUTPUT_RGBI, OUTPUT_BGRI, OUTPUT_RGB_PLANAR, OUTPUT_BGR_PLANAR, OUTPUT_Y, OUTPUT
 FLAG_FANCY_UPSAMPLING = 1
 FLAG_GPU_HUFFMAN = 2
 FLAG_GPU_RESTART_INTERVALS = 8
+FLAG_GPU_PROGRESSIVE_INTERVALS = 16
 TRANSCODE_ORIENTATION_FROM_EXIF = 0x10000  # or-ed into TranscodeParams.orientation
 TRANSCODE_TRIM = 0x20000
 TRANSCODE_GRAYSCALE = 0x80000
@@ -116,6 +117,7 @@ def load():
     L.hipjpegGetImageInfo.argtypes = [vp, sz, ctypes.POINTER(ImageInfo)]
     L.hipjpegEntropyDecodeHost.argtypes = [vp, sz, vp, sz, vp, vp]
     L.hipjpegEntropyDecodeGpuAlgorithmHost.argtypes = [vp, sz, vp, sz, vp, ctypes.POINTER(ctypes.c_int32)]
+    L.hipjpegEntropyDecodeGpuIntervalAlgorithmHost.argtypes = [vp, sz, vp, sz, vp]
     L.hipjpegCreate.argtypes = [ctypes.POINTER(vp), i32, i32]
     L.hipjpegDestroy.argtypes = [vp]
     L.hipjpegDecodeBatch.argtypes = [vp, vp, vp, i32, vp, i32, ctypes.c_uint, vp, vp]
@@ -134,6 +136,10 @@ def load():
     L.hipjpegEntropyDecodeHostSparse.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz), vp]
     L.hipjpegDecodeBatchZeroCopyImages.argtypes = [vp]
     L.hipjpegDecodeBatchZeroCopyImages.restype = i32
+    L.hipjpegDecodeBatchIntervalImages.argtypes = [vp]
+    L.hipjpegDecodeBatchIntervalImages.restype = i32
+    L.hipjpegDecodeBatchIntervalTakeovers.argtypes = [vp]
+    L.hipjpegDecodeBatchIntervalTakeovers.restype = i32
     L.hipjpegTestHostFallbacks.argtypes = [vp]
     L.hipjpegTestHostFallbacks.restype = i32
     L.hipjpegTestScanChunkDrops.argtypes = [vp, ctypes.c_size_t, i32, ctypes.POINTER(ctypes.c_uint32), i32]

@@ -211,7 +211,7 @@ struct DecodeBatch::Sizing {
     std::vector<size_t> plane_off, xform_plane_off;  // per image x component ((size_t)-1: no plane); per TransformImage plane, in order
     // GPU entropy stage: staging area (scans, tables, boundaries), device-only scratch (streams, DC values, positions), chunks (a count)
     Carve raw, pools, boundaries, streams, blocks, block_pos, prog_pos, chunks;
-    size_t subseq = 0, huff_wunits = 0, prog_units = 0, prog_scans = 0;
+    size_t subseq = 0, huff_wunits = 0, prog_units = 0, prog_scans = 0, prog_iv_units = 0;
     size_t tensor_units = 0;  // plan_tensors(): RelayoutUnit slots of coef_to_decoder_kernel
 
     // One scan: its staged bytes (padded, see entropy_stage), its destuffed stream, its destuff chunks.  Returns the stream's capacity.
@@ -256,7 +256,7 @@ hipjpegStatus_t DecodeBatch::plan_coefficients(const uint8_t* const* data, const
     pool_ = pool;
     coef_only_ = true;
     tensor_source_ = false;
-    return plan_attempts(PlanArgs{data, lengths, nullptr, HIPJPEG_OUTPUT_RGBI, flags & HIPJPEG_FLAG_GPU_HUFFMAN, nullptr, nullptr, nullptr, params, any_frame}, n,
+    return plan_attempts(PlanArgs{data, lengths, nullptr, HIPJPEG_OUTPUT_RGBI, flags & (HIPJPEG_FLAG_GPU_HUFFMAN | HIPJPEG_FLAG_GPU_PROGRESSIVE_INTERVALS), nullptr, nullptr, nullptr, params, any_frame}, n,
                          statuses);
 }
 
@@ -305,6 +305,8 @@ hipjpegStatus_t DecodeBatch::plan_once(const PlanArgs& a, int n, hipjpegStatus_t
     seq_gpu_images_ = 0;
     prog_images_.clear();
     prog_to_image_.clear();
+    prog_walk_images_ = 0;
+    interval_takeover_images_ = 0;
     xform_desc_.clear();
     prog_slot_words_ = 0;
     max_huff_units_ = max_pool_words_ = 0;
@@ -314,6 +316,17 @@ hipjpegStatus_t DecodeBatch::plan_once(const PlanArgs& a, int n, hipjpegStatus_t
     else
         for (int i = 0; i < n; i++) prepare(i, a);
     demote_progressive_lds();
+    // progressive images in descriptor order: those of the walk, then those of the interval kernels (a tail prog_walk_kernel is not
+    // launched over)
+    for (int tail = 0; tail < 2; tail++) {
+        for (int i = 0; i < n; i++) {
+            PlannedImage& im = images_[i];
+            if (im.status != HIPJPEG_STATUS_SUCCESS || !im.gpu_prog || (int)im.gpu_prog_intervals != tail) continue;
+            im.prog_index = (int)prog_to_image_.size();
+            prog_to_image_.push_back(i);
+        }
+        if (tail == 0) prog_walk_images_ = prog_to_image_.size();
+    }
     Sizing s(n);
     for (int i = 0; i < n; i++) size_image(i, s);
     layout(s);
@@ -383,6 +396,11 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
     } else if (im.status == HIPJPEG_STATUS_SUCCESS && want_gpu_entropy && big_enough && gpu_progressive_eligible(f)) {
         im.gpu_entropy = im.gpu_prog = true;
         im.pool_words = prog_pool_words(f);
+    } else if (im.status == HIPJPEG_STATUS_SUCCESS && want_gpu_entropy && big_enough && (a.flags & HIPJPEG_FLAG_GPU_PROGRESSIVE_INTERVALS) != 0 &&
+               gpu_progressive_interval_eligible(f)) {
+        // every scan has a restart interval: staged like any progressive image, a lane per interval in place of the walk
+        im.gpu_entropy = im.gpu_prog = im.gpu_prog_intervals = true;
+        im.pool_words = prog_pool_words(f);
     }
     if (im.status != HIPJPEG_STATUS_SUCCESS) return;
     // the part of the device descriptor that does not depend on where things will lie in the arenas
@@ -441,21 +459,25 @@ void DecodeBatch::demote_progressive_lds()
         return (size_t)v;
     }();
     for (;;) {
-        ProgLdsShape all;
+        // `all`: every progressive image (the table slots of all launches are sized for the batch's largest table); `walk`: the images
+        // of the walk alone -- the interval kernels stand in for it and take table slots only, like the replay
+        ProgLdsShape all, walk;
         int worst = -1;
         size_t worst_need = 0;
         for (int i = 0; i < (int)images_.size(); i++) {
             if (!images_[i].gpu_prog) continue;
             const ProgLdsShape sh = prog_lds_shape(images_[i].frame);
             all.merge(sh);
-            const size_t need = std::max(prog_walk_lds_bytes(sh), prog_replay_lds_bytes(sh));
+            if (!images_[i].gpu_prog_intervals) walk.merge(sh);
+            const size_t need = std::max(images_[i].gpu_prog_intervals ? prog_interval_lds_bytes(sh) : prog_walk_lds_bytes(sh), prog_replay_lds_bytes(sh));
             if (need > worst_need) {
                 worst_need = need;
                 worst = i;
             }
         }
-        if (worst < 0 || std::max(prog_walk_lds_bytes(all), prog_replay_lds_bytes(all)) <= lds_limit) return;
-        images_[worst].gpu_entropy = images_[worst].gpu_prog = false;
+        walk.slot_words = all.slot_words;
+        if (worst < 0 || std::max({prog_walk_lds_bytes(walk), prog_interval_lds_bytes(all), prog_replay_lds_bytes(all)}) <= lds_limit) return;
+        images_[worst].gpu_entropy = images_[worst].gpu_prog = images_[worst].gpu_prog_intervals = false;
         images_[worst].pool_words = 0;
     }
 }
@@ -530,9 +552,7 @@ void DecodeBatch::size_image(int i, Sizing& s)
     }
     if (im.gpu_prog) {
         // progressive: every scan is staged and destuffed like a baseline scan; the walk and replay kernels take it from there
-        im.prog_index = (int)prog_to_image_.size();
-        prog_to_image_.push_back(i);
-        im.prog_huff_first = (uint32_t)s.prog_scans;
+        im.prog_huff_first = (uint32_t)s.prog_scans;  // (prog_index: plan_once)
         s.prog_scans += f.scans.size();
         for (size_t sidx = 0; sidx < f.scans.size(); sidx++) {
             const ScanHeader& sc = f.scans[sidx];
@@ -546,6 +566,20 @@ void DecodeBatch::size_image(int i, Sizing& s)
                 for (int k = 0; k < sc.ncomp; k++)
                     prog_slot_words_ = std::max<unsigned>(prog_slot_words_, (unsigned)prog_table_words(sc.dc[sc.td[k]]));
             }
+        }
+        if (im.gpu_prog_intervals) {
+            // interval kernels: every scan's interval starts, a workgroup per kProgIntervalLanes intervals of a component's AC chain and
+            // of every DC scan, a bitmap per block of the components that have more than one AC scan
+            int ac_scans[4] = {0, 0, 0, 0};
+            for (size_t sidx = 0; sidx < f.scans.size(); sidx++) {
+                const ScanHeader& sc = f.scans[sidx];
+                const size_t count = sc.rst_after.size() + 1;
+                im.prog_start_offset[sidx] = s.boundaries.take(align_up(sc.rst_after.size() * 4, 64), 1);
+                if (sc.ss == 0 || ac_scans[sc.comp_index[0]]++ == 0) s.prog_iv_units += (count + kProgIntervalLanes - 1) / kProgIntervalLanes;
+            }
+            for (int c = 0; c < f.ncomp; c++)
+                if (ac_scans[c] > 1)
+                    im.prog_hist_offset[c] = s.prog_pos.take((size_t)((f.comp[c].samp_w + 7) / 8) * (size_t)((f.comp[c].samp_h + 7) / 8) * 8, 8);
         }
         return;
     }
@@ -590,6 +624,8 @@ void DecodeBatch::layout(const Sizing& s)
     L.xform_units = c.take(sizeof(WorkUnit) * s.xform_units);
     L.prog_desc = c.take(sizeof(ProgImage) * prog_to_image_.size());
     L.prog_units = c.take(sizeof(HuffUnit) * s.prog_units);
+    L.prog_iv_desc = c.take(sizeof(ProgIntervalImage) * (prog_to_image_.size() - prog_walk_images_));
+    L.prog_iv_units = c.take(sizeof(HuffUnit) * s.prog_iv_units);
     L.tensor_planes = c.take(tensor_source_ ? sizeof(CoefPlane) * 4 * images_.size() : 0);
     L.tensor_units = c.take(sizeof(RelayoutUnit) * s.tensor_units);
     L.tables = c.take(s.pools.end);
@@ -613,6 +649,7 @@ void DecodeBatch::layout(const Sizing& s)
             if (im.gpu_prog) {
                 im.tables_offset += L.tables;
                 for (size_t sidx = 0; sidx < im.frame.scans.size(); sidx++) im.prog_raw_offset[sidx] += L.streams;
+                for (size_t sidx = 0; sidx < im.frame.scans.size() && im.gpu_prog_intervals; sidx++) im.prog_start_offset[sidx] += L.boundaries;
             } else {
                 for (int sidx = 0; sidx < im.huff_count; sidx++) {
                     im.seq[sidx].raw_offset += L.streams;
@@ -664,6 +701,7 @@ void DecodeBatch::bind_pointers(const Sizing& s)
 {
     huff_images_.assign(huff_to_image_.size() + s.prog_scans, HuffImage());
     prog_images_.assign(prog_to_image_.size(), ProgImage());
+    prog_iv_images_.assign(prog_to_image_.size() - prog_walk_images_, ProgIntervalImage());
     size_t k = 0;  // next TransformImage plane
     for (size_t i = 0; i < images_.size(); i++) {
         const PlannedImage& im = images_[i];
@@ -717,7 +755,15 @@ void DecodeBatch::entropy_stage(int i)
             h.first_chunk = im.prog_first_chunk[sidx];
             im.stream_bytes += (uint32_t)len;
             stage_chunk_drops(sc, h.first_chunk);
+            if (im.gpu_prog_intervals) {
+                // the destuff kernels drop the restart markers too (their rule: a restart interval other than 0); where the intervals
+                // start in what is left, in bits
+                h.restart_interval = (uint32_t)sc.restart_interval;
+                uint32_t* starts = at<uint32_t>(pinned_, im.prog_start_offset[sidx]);
+                for (size_t b = 0; b < sc.rst_after.size(); b++) starts[b] = sc.rst_after[b] * 8u;
+            }
         }
+        if (im.gpu_prog_intervals) fill_prog_interval_image(f, &prog_iv_images_[(size_t)im.prog_index - prog_walk_images_]);
         fill_prog_image(f, &prog_images_[im.prog_index], at<uint16_t>(pinned_, im.tables_offset));
         for (int c = 0; c < f.ncomp; c++) im.coef_or[c] = 32767u;  // successive approximation: any int16 may come out
         return;
@@ -1002,6 +1048,34 @@ void DecodeBatch::build_entropy_units()
         }
         stream_bytes_total_ += im.stream_bytes;
     }
+    // the interval kernels' share: where each scan's interval starts lie in the batch-wide array, the bitmaps, the units -- AC units
+    // first, then the DC units by DC-scan index (one launch per index: enqueue_progressive)
+    prog_iv_units_.clear();
+    prog_iv_dc_first_.clear();
+    uint32_t dc_scans = 0;
+    for (size_t q = prog_walk_images_; q < prog_images_.size(); q++) {
+        const PlannedImage& im = images_[prog_to_image_[q]];
+        if (im.status != HIPJPEG_STATUS_SUCCESS) continue;
+        const uint32_t rel = (uint32_t)(q - prog_walk_images_);
+        ProgIntervalImage& iv = prog_iv_images_[rel];
+        for (size_t sidx = 0; sidx < im.frame.scans.size(); sidx++) iv.scan[sidx].first_start = (uint32_t)((im.prog_start_offset[sidx] - staging_.boundaries) / 4);
+        for (int c = 0; c < im.frame.ncomp; c++) {
+            iv.hist[c] = prog_images_[q].chain_len[c] > 1 ? at<unsigned long long>(work_, scratch_.prog_pos + im.prog_hist_offset[c]) : nullptr;
+            for (uint32_t first = 0; prog_images_[q].chain_len[c] > 0 && first < iv.ac_count[c]; first += kProgIntervalLanes)
+                prog_iv_units_.push_back(HuffUnit{rel, ((uint32_t)c << 28) | first});
+        }
+        dc_scans = std::max(dc_scans, prog_images_[q].dc_len);
+    }
+    for (uint32_t d = 0; d < dc_scans; d++) {
+        prog_iv_dc_first_.push_back(prog_iv_units_.size());
+        for (size_t q = prog_walk_images_; q < prog_images_.size(); q++) {
+            const ProgImage& pi = prog_images_[q];
+            if (pi.dc_len <= d) continue;  // (an image that failed on the host has none)
+            const uint32_t count = prog_iv_images_[q - prog_walk_images_].scan[pi.dc_chain[d]].count;
+            for (uint32_t first = 0; first < count; first += kProgIntervalLanes) prog_iv_units_.push_back(HuffUnit{(uint32_t)(q - prog_walk_images_), first});
+        }
+    }
+    prog_iv_dc_first_.push_back(prog_iv_units_.size());
 }
 
 // The padding fills of a batch of pictures alike are evenly spaced, in two interleaved series (coefficients, DC planes): each series
@@ -1099,6 +1173,8 @@ void DecodeBatch::stage_tables()
     copy_table(pinned_, staging_.tensor_units, tensor_units_);
     copy_table(pinned_, staging_.prog_desc, prog_images_);
     copy_table(pinned_, staging_.prog_units, prog_units_);
+    copy_table(pinned_, staging_.prog_iv_desc, prog_iv_images_);
+    copy_table(pinned_, staging_.prog_iv_units, prog_iv_units_);
     copy_table(pinned_, staging_.huff_desc, huff_images_);
     copy_table(pinned_, staging_.huff_units, huff_units_);
     copy_table(pinned_, staging_.huff_wunits, huff_wunits_);
@@ -1218,7 +1294,8 @@ hipjpegStatus_t DecodeBatch::enqueue_progressive(void* stream)
     const HuffImage* dimg = at<const HuffImage>(device_, staging_.huff_desc);
     const unsigned slot = (unsigned)align_up(std::max<unsigned>(prog_slot_words_, 256u), 64);
     unsigned dc_slots = 1, ac_waves = 0, rings = 0;  // per workgroup (= image): DC table slots, AC scans (one wave each), hand-over rings
-    for (const ProgImage& pi : prog_images_) {
+    for (size_t q = 0; q < prog_walk_images_; q++) {  // the walk's images: the head of the array
+        const ProgImage& pi = prog_images_[q];
         unsigned scans = 0, handovers = 0;
         for (int c = 0; c < 4; c++) {
             scans += pi.chain_len[c];
@@ -1231,9 +1308,21 @@ hipjpegStatus_t DecodeBatch::enqueue_progressive(void* stream)
     }
     static const bool debug_stats = getenv("HIPJPEG_DEBUG_TIMING") != nullptr;
     if (debug_stats)
-        fprintf(stderr, "[hipjpeg] progressive walk: %zu images, %u + 1 waves per workgroup, %u table slots of %u entries, %u rings\n", prog_images_.size(),
-                ac_waves, dc_slots + ac_waves, slot, rings);
-    if (launch_prog_walk(dprog, dimg, (int)prog_images_.size(), slot, dc_slots, ac_waves, rings, stream) != 0) return HIPJPEG_STATUS_HIP_ERROR;
+        fprintf(stderr, "[hipjpeg] progressive walk: %zu images, %u + 1 waves per workgroup, %u table slots of %u entries, %u rings; interval kernels: %zu images\n",
+                prog_walk_images_, ac_waves, dc_slots + ac_waves, slot, rings, prog_images_.size() - prog_walk_images_);
+    if (launch_prog_walk(dprog, dimg, (int)prog_walk_images_, slot, dc_slots, ac_waves, rings, stream) != 0) return HIPJPEG_STATUS_HIP_ERROR;
+    if (!prog_iv_units_.empty()) {
+        // the tail of the array: a lane per restart interval -- the AC chains in one launch, the DC scans in one launch per DC-scan index
+        ProgImage* tail = dprog + prog_walk_images_;
+        const ProgIntervalImage* ivs = at<const ProgIntervalImage>(device_, staging_.prog_iv_desc);
+        const uint32_t* starts = at<const uint32_t>(device_, staging_.boundaries);
+        const HuffUnit* units = at<const HuffUnit>(device_, staging_.prog_iv_units);
+        if (launch_prog_interval_ac(tail, ivs, dimg, starts, units, (int)prog_iv_dc_first_[0], slot, stream) != 0) return HIPJPEG_STATUS_HIP_ERROR;
+        for (size_t d = 0; d + 1 < prog_iv_dc_first_.size(); d++)
+            if (launch_prog_interval_dc(tail, ivs, dimg, starts, units + prog_iv_dc_first_[d], (int)(prog_iv_dc_first_[d + 1] - prog_iv_dc_first_[d]), (unsigned)d,
+                                        slot, stream) != 0)
+                return HIPJPEG_STATUS_HIP_ERROR;
+    }
     if (launch_prog_replay(dprog, dimg, at<const HuffUnit>(device_, staging_.prog_units), (int)prog_units_.size(), slot, stream) != 0)
         return HIPJPEG_STATUS_HIP_ERROR;
     if (hipMemcpyAsync(pinned_.data() + staging_.prog_desc, dprog, sizeof(ProgImage) * prog_images_.size(), hipMemcpyDeviceToHost,
@@ -1357,8 +1446,12 @@ hipjpegStatus_t DecodeBatch::resolve(void* stream)
     host_fallback_images_ = (int)takeover.size();
     const ProgImage* hprog = at<const ProgImage>(pinned_, staging_.prog_desc);
     if (debug_stats && !prog_to_image_.empty()) print_progressive_timing(hprog);
+    interval_takeover_images_ = 0;
     for (size_t q = 0; q < prog_to_image_.size(); q++)
-        if (images_[prog_to_image_[q]].status == HIPJPEG_STATUS_SUCCESS && hprog[q].status != 0) takeover.push_back(prog_to_image_[q]);
+        if (images_[prog_to_image_[q]].status == HIPJPEG_STATUS_SUCCESS && hprog[q].status != 0) {
+            takeover.push_back(prog_to_image_[q]);
+            interval_takeover_images_ += q >= prog_walk_images_ ? 1 : 0;
+        }
     const hipjpegStatus_t st = take_over_on_host(takeover, &redo_pixels);
     if (st != HIPJPEG_STATUS_SUCCESS) return st;
     if (redo_pixels && pixels_launched_) {

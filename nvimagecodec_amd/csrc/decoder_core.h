@@ -78,6 +78,11 @@ struct PlannedImage {
     size_t prog_stream_offset[kProgMaxScans] = {0};  // destuffed streams (device-only scratch)
     uint32_t prog_first_chunk[kProgMaxScans] = {0};
     size_t prog_pos_offset[kProgMaxScans] = {0};     // block positions of the AC scans (device-only scratch)
+    // ... every scan of which has a restart interval (HIPJPEG_FLAG_GPU_PROGRESSIVE_INTERVALS, progressive_interval_core.h): gpu_prog is
+    // set as well; the interval kernels stand in for the walk
+    bool gpu_prog_intervals = false;
+    size_t prog_start_offset[kProgMaxScans] = {0};   // interval starts of each scan (staging area, the sequential path's boundaries region)
+    size_t prog_hist_offset[4] = {0, 0, 0, 0};       // non-zero bitmaps of a component with several AC scans (device-only scratch)
 };
 
 class DecodeBatch {
@@ -153,6 +158,9 @@ public:
     int last_sync_launches() const { return last_sync_launches_; }
     int host_fallback_images() const { return host_fallback_images_; }  // GPU-entropy images the host decoder took over in resolve()
     bool has_progressive() const { return !prog_to_image_.empty(); }
+    int interval_images() const { return (int)(prog_to_image_.size() - prog_walk_images_); }  // progressive images on the interval kernels
+    // ... of which the kernels flagged (a stream they could not vouch for) and the host decoder took over in resolve()
+    int interval_takeover_images() const { return interval_takeover_images_; }
     uint64_t stream_bytes() const { return stream_bytes_total_; }
     // images of the current batch whose bitstream went to the device from the caller's own (pinned) memory
     int zero_copy_images() const { return zero_copy_images_; }
@@ -197,7 +205,7 @@ private:
     // GPU-decoded images.  The pinned side keeps 256 spare bytes and verdict_bytes() behind h2d_bytes (entropy_launch_args).
     struct StagingLayout {
         size_t desc, units, huff_desc, huff_units, huff_wunits, huff_dc_units, huff_chunk_units, huff_drops, xform_desc, xform_units,
-            prog_desc, prog_units, tensor_planes, tensor_units, tables, boundaries, streams, coef, h2d_bytes, gpu_coef_begin, total;
+            prog_desc, prog_units, prog_iv_desc, prog_iv_units, tensor_planes, tensor_units, tables, boundaries, streams, coef, h2d_bytes, gpu_coef_begin, total;
     } staging_{};
     // Device-only scratch of the entropy kernels (work_): subsequence states (at 0) | first block indices | change counters | ...
     struct WorkLayout {
@@ -253,6 +261,12 @@ private:
     std::vector<int> prog_to_image_;
     std::vector<HuffUnit> prog_units_;  // replay kernel: {ProgImage index, component << 28 | first block}
     unsigned prog_slot_words_ = 0;
+    // prog_images_ / prog_to_image_ hold the images of the walk first, [0, prog_walk_images_), then those of the interval kernels; the
+    // replay kernel takes them all
+    size_t prog_walk_images_ = 0;
+    std::vector<ProgIntervalImage> prog_iv_images_;  // beside prog_images_[prog_walk_images_ ...]
+    std::vector<HuffUnit> prog_iv_units_;            // AC units, then the DC units of DC-scan index 0, 1, ... (image relative to the tail)
+    std::vector<size_t> prog_iv_dc_first_;           // prog_iv_units_ index of the first DC unit of index d; one entry more than indices
     uint64_t stream_bytes_total_ = 0;
     // ---- transfer(), launch(), resolve()
     struct EntropyLaunch {
@@ -289,7 +303,7 @@ private:
     void* entropy_event_ = nullptr;  // hipEvent_t: entropy stage finished on its own stream
     void* done_event_ = nullptr;     // hipEvent_t recorded after the last launch that reads this batch's buffers
     bool in_flight_ = false;
-    int last_sync_launches_ = 0, host_fallback_images_ = 0;
+    int last_sync_launches_ = 0, host_fallback_images_ = 0, interval_takeover_images_ = 0;
 };
 
 // status helpers

@@ -253,6 +253,27 @@ hipjpegStatus_t hipjpegEntropyDecodeGpuAlgorithmHost(const uint8_t* data, size_t
     });
 }
 
+hipjpegStatus_t hipjpegEntropyDecodeGpuIntervalAlgorithmHost(const uint8_t* data, size_t length, int16_t* coef, size_t coef_capacity_bytes,
+                                                             uint64_t comp_offsets[4])
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!data || !coef) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    FrameInfo f;
+    ParseStatus ps = parse_jpeg(data, length, &f);
+    if (ps != kParseOk) return status_from_parse(ps);
+    if (!gpu_progressive_interval_eligible(f)) return HIPJPEG_STATUS_UNSUPPORTED;
+    if (f.total_blocks() * 128 > coef_capacity_bytes) return HIPJPEG_STATUS_BUFFER_TOO_SMALL;
+    int16_t* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t off = 0;
+    for (int c = 0; c < f.ncomp; c++) {
+        ptr[c] = coef + off;
+        if (comp_offsets) comp_offsets[c] = off;
+        off += (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 64;
+    }
+    return emulate_gpu_progressive_intervals(data, length, f, ptr) == 0 ? HIPJPEG_STATUS_SUCCESS : HIPJPEG_STATUS_CORRUPT;
+    });
+}
+
 hipjpegStatus_t hipjpegCreate(hipjpegHandle_t* handle, int device_id, int num_host_threads)
 {
     return guarded([&]() -> hipjpegStatus_t {
@@ -509,6 +530,15 @@ hipjpegStatus_t hipjpegDecodeBatchEntropyStats(hipjpegHandle_t handle, int32_t* 
 }
 
 int32_t hipjpegDecodeBatchZeroCopyImages(hipjpegHandle_t handle) { return handle ? handle->cur().zero_copy_images() : -1; }
+
+int32_t hipjpegDecodeBatchIntervalImages(hipjpegHandle_t handle) { return handle ? handle->cur().interval_images() : -1; }
+
+int32_t hipjpegDecodeBatchIntervalTakeovers(hipjpegHandle_t handle)
+{
+    // the batch the last Wait settled, if no batch has been planned since; else the current page's
+    if (!handle) return -1;
+    return handle->batches[handle->settled >= 0 ? handle->settled : handle->current]->interval_takeover_images();
+}
 
 hipjpegStatus_t hipjpegDecodeBatchTransferStats(hipjpegHandle_t handle, uint64_t* h2d_bytes, int32_t* sparse_images)
 {
@@ -799,6 +829,7 @@ hipjpegStatus_t hipjpegTranscodeBatch(hipjpegHandle_t handle, const uint8_t* con
     if (handle->num_submitted != 0 || handle->encode_in_flight != 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
     handle->transcode_gpu_decoded = handle->transcode_gpu_coded = handle->transcode_blocks = 0;
+    handle->settled = -1;  // a batch is planned on the current page
     // the regions belong to this batch alone, whatever becomes of it
     std::vector<hipjpegTranscodeRegion_t> regions;
     regions.swap(handle->transcode_regions);
@@ -883,6 +914,7 @@ hipjpegStatus_t hipjpegDecodeCoefficientsBatch(hipjpegHandle_t handle, const uin
     if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
     handle->coefficients_gpu_decoded = 0;
     handle->coefficients_blocks = 0;
+    handle->settled = -1;  // a batch is planned on the current page
     DecodeBatch& d = handle->cur();
     hipjpegStatus_t st = d.plan_coefficients(data, lengths, batch_size, flags, nullptr, handle->pool.get(), nullptr, /*any_frame=*/true);
     if (st != HIPJPEG_STATUS_SUCCESS) return st;

@@ -128,6 +128,7 @@ private:
     MemoryHooks hooks_;
     bool fancy_ = true;  // same default as the reference plugins (nvjpeg_utils.cpp:46, libjpeg_turbo_decoder.cpp:253)
     bool gpu_huffman_ = true;  // entropy-decode eligible streams on the GPU (the reference's GPU_HYBRID backend analogue)
+    bool gpu_progressive_intervals_ = false;  // ... progressive files whose scans all have restart intervals too (HIPJPEG_FLAG_GPU_PROGRESSIVE_INTERVALS)
     uint64_t hybrid_huffman_threshold_ = 0;  // ... those of more than this many pixels (cuda_decoder.cpp:188-209; 0 = all of them)
     // fast_idct (JDCT_FASTEST, libjpeg_turbo_decoder.cpp:250-276).  A key without a module name is the chain's setting: it hands every
     // sample to the next decoder (fast_idct_, see canDecode).  hipjpeg_decoder:fast_idct=1 opts in to this decoder's own IFAST kernels
@@ -166,6 +167,7 @@ HipJpegDecoder::HipJpegDecoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgc
         named_seen = addressed_keys_.size();
         if (key == "fancy_upsampling") v >> fancy_;
         else if (key == "gpu_huffman") v >> gpu_huffman_;
+        else if (key == "gpu_progressive_intervals") v >> gpu_progressive_intervals_;
         else if (key == "pipeline_chunks") v >> pipeline_chunks_;
         else if (key == "hybrid_huffman_threshold") v >> hybrid_huffman_threshold_;
         else if (key == "fast_idct" && named) {
@@ -181,7 +183,7 @@ HipJpegDecoder::HipJpegDecoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgc
     // plugin of the chain and is passed over in silence, as the reference's plugins do)
     for (const std::string& k : unknown_keys_)
         if (std::find(addressed_keys_.begin(), addressed_keys_.end(), k) != addressed_keys_.end())
-            HJ_LOG_WARNING(fw_, kDecoderId, "unknown option '" << k << "' ignored (known: fancy_upsampling, gpu_huffman, hybrid_huffman_threshold, pipeline_chunks, fast_idct)");
+            HJ_LOG_WARNING(fw_, kDecoderId, "unknown option '" << k << "' ignored (known: fancy_upsampling, gpu_huffman, gpu_progressive_intervals, hybrid_huffman_threshold, pipeline_chunks, fast_idct)");
     if (fast_idct_)
         HJ_LOG_WARNING(fw_, kDecoderId, "fast_idct=1 without a module name: canDecode hands every sample to the next decoder of the chain; "
                                         "hipjpeg_decoder:fast_idct=1 decodes them here with the fast integer IDCT (libjpeg-turbo's JDCT_IFAST SIMD routine)");
@@ -669,7 +671,7 @@ nvimgcodecStatus_t HipJpegDecoder::decode_chunk(nvimgcodecCodeStreamDesc_t** cod
         const bool planned = hipSetDevice(device_) == hipSuccess &&
                              job->batch.plan(data.data(), sizes.data(), n, outs.data(), HIPJPEG_OUTPUT_RGBI,
                                              (fancy_ ? HIPJPEG_FLAG_FANCY_UPSAMPLING : 0u) | (gpu_huffman_ ? HIPJPEG_FLAG_GPU_HUFFMAN : 0u) |
-                                                 (ifast_ ? HIPJPEG_FLAG_FAST_IDCT : 0u),
+                                                 (ifast_ ? HIPJPEG_FLAG_FAST_IDCT : 0u) | (gpu_progressive_intervals_ ? HIPJPEG_FLAG_GPU_PROGRESSIVE_INTERVALS : 0u),
                                              job->statuses.data(), formats.data(), parse_pool_.get(),
                                              any_geometry ? geometry.data() : nullptr) == HIPJPEG_STATUS_SUCCESS;
         if (!planned) throw std::runtime_error("could not plan the decode batch");

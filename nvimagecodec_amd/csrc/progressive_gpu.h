@@ -4,6 +4,7 @@
 
 #include "gpu_huffman.h"
 #include "progressive_gpu_core.h"
+#include "progressive_interval_core.h"
 
 namespace hipjpeg {
 
@@ -17,5 +18,15 @@ int launch_prog_walk(ProgImage* images, const HuffImage* himgs, int nimages, uns
                      void* stream);
 // units[i] = {image, (component << 28) | first block of the component's allocation grid}; 256 blocks per unit.
 int launch_prog_replay(ProgImage* images, const HuffImage* himgs, const HuffUnit* units, int nunits, unsigned slot_words, void* stream);
+
+// progressive_intervals.hip -- images whose scans all have restart intervals: a lane per interval in place of the walk
+// (progressive_interval_core.h).  images[k] / ivs[k] describe the same picture; starts = the batch-wide array of interval starts.
+// AC: units[i] = {image, (component << 28) | first interval}, kProgIntervalLanes intervals of the component's chain per unit.
+int launch_prog_interval_ac(ProgImage* images, const ProgIntervalImage* ivs, const HuffImage* himgs, const uint32_t* starts, const HuffUnit* units,
+                            int nunits, unsigned slot_words, void* stream);
+// DC: units[i] = {image, first interval} of the image's dc_index-th DC scan.  One launch per dc_index, in order: a later DC scan may
+// cut the blocks of an earlier one into other intervals.
+int launch_prog_interval_dc(ProgImage* images, const ProgIntervalImage* ivs, const HuffImage* himgs, const uint32_t* starts, const HuffUnit* units,
+                            int nunits, unsigned dc_index, unsigned slot_words, void* stream);
 
 }  // namespace hipjpeg

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "gpu_huffman_host.h"
+#include "progressive_interval_core.h"
 
 namespace hipjpeg {
 
@@ -67,7 +68,10 @@ void build_prog_table(const HuffSpec& s, uint16_t* out)
     });
 }
 
-bool gpu_progressive_eligible(const FrameInfo& f)
+namespace {
+
+// What gpu_progressive_eligible() and gpu_progressive_interval_eligible() share: everything but the rule about restart intervals.
+bool prog_script_eligible(const FrameInfo& f)
 {
     if (!f.progressive() || f.scans.empty() || f.scans.size() > (size_t)kProgMaxScans) return false;
     if (f.ncomp < 1 || f.ncomp > 4) return false;
@@ -76,7 +80,6 @@ bool gpu_progressive_eligible(const FrameInfo& f)
         for (int& b : c) b = -1;
     int stages[4] = {0, 0, 0, 0};
     for (const ScanHeader& sc : f.scans) {
-        if (!sc.plain_stuffing || sc.restart_interval != 0 || !sc.rst_after.empty()) return false;
         if ((sc.data_end - sc.data_begin) >= (1ull << 27)) return false;  // bit positions below 2^30: bit 31 flags end-of-band runs
         // a scan without a single entropy-coded byte (a file cut right behind an SOS header, a marker directly after one): no destuff
         // chunk would be queued for it, its stream descriptor would stay empty -- the host decoder names the error (TRUNCATED)
@@ -114,6 +117,48 @@ bool gpu_progressive_eligible(const FrameInfo& f)
         if ((size_t)((f.comp[c].samp_w + 7) / 8) * (size_t)((f.comp[c].samp_h + 7) / 8) >= (1u << 24)) return false;
     }
     return true;
+}
+
+}  // namespace
+
+bool gpu_progressive_eligible(const FrameInfo& f)
+{
+    for (const ScanHeader& sc : f.scans)
+        if (!sc.plain_stuffing || sc.restart_interval != 0 || !sc.rst_after.empty()) return false;
+    return prog_script_eligible(f);
+}
+
+bool gpu_progressive_interval_eligible(const FrameInfo& f)
+{
+    if (!prog_script_eligible(f)) return false;
+    int ac_interval[4] = {0, 0, 0, 0};
+    for (const ScanHeader& sc : f.scans) {
+        if (!sc.plain_stuffing || sc.restart_interval < 1 || sc.restart_interval > 65535) return false;
+        // every interval but the last closed by its marker (the rule of the sequential path's gpu_scan_eligible)
+        const size_t mcus = (size_t)scan_mcus_x(f, sc) * scan_mcus_y(f, sc);
+        if (sc.rst_after.size() != (mcus + (size_t)sc.restart_interval - 1) / (size_t)sc.restart_interval - 1) return false;
+        if (sc.ss != 0) {
+            // interval i must cover the same blocks in every AC scan of the component
+            int& n = ac_interval[sc.comp_index[0]];
+            if (n != 0 && n != sc.restart_interval) return false;
+            n = sc.restart_interval;
+        }
+    }
+    return true;
+}
+
+void fill_prog_interval_image(const FrameInfo& f, ProgIntervalImage* iv)
+{
+    memset(iv, 0, sizeof *iv);
+    for (size_t s = 0; s < f.scans.size(); s++) {
+        const ScanHeader& sc = f.scans[s];
+        iv->scan[s].interval = (uint32_t)sc.restart_interval;
+        iv->scan[s].count = (uint32_t)sc.rst_after.size() + 1u;
+        if (sc.ss != 0) {
+            iv->ac_interval[sc.comp_index[0]] = iv->scan[s].interval;
+            iv->ac_count[sc.comp_index[0]] = iv->scan[s].count;
+        }
+    }
 }
 
 ProgLdsShape prog_lds_shape(const FrameInfo& f)
@@ -407,6 +452,87 @@ int emulate_gpu_progressive(const uint8_t* data, size_t size, const FrameInfo& f
                     }
         }
         if (!ok || p > total_bits[s]) return 1;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------- restart intervals
+namespace {
+
+// what a lane of the interval kernels sees (progressive_interval_core.h), on the host
+struct HostIntervalEnv {
+    const HostStream* streams;       // per scan
+    const uint32_t* total_bits;      // per scan
+    const std::vector<uint32_t>* starts;  // per scan: bit offsets behind the restart markers
+    const uint16_t* pool;
+    const ProgImage* im;
+    uint64_t* hist_all = nullptr;    // the component's bitmaps
+    int16_t* const* coef = nullptr;
+    uint32_t word(const ProgScan& sc, uint32_t i) const { return streams[&sc - im->scan].word(i); }
+    uint32_t lookup(const ProgScan& sc, uint32_t w) const { return host_lookup(pool + sc.table[0], w); }
+    uint32_t dc_lookup(const ProgScan& sc, uint32_t slot, uint32_t w) const { return host_lookup(pool + sc.table[slot], w); }
+    uint32_t bound(uint32_t s, uint32_t k) const { return k == 0 ? 0u : k <= starts[s].size() ? starts[s][k - 1] : total_bits[s]; }
+    uint64_t hist(uint32_t b) const { return hist_all[b]; }
+    void set_hist(uint32_t b, uint64_t h) const { hist_all[b] = h; }
+    void set_pos(const ProgScan& sc, uint32_t b, uint32_t v) const { sc.block_pos[b] = v; }
+    void dc_store(uint32_t c, uint32_t index, int v) const { coef[c][(size_t)index * 64] = (int16_t)v; }
+    void dc_or(uint32_t c, uint32_t index, int bits) const { coef[c][(size_t)index * 64] = (int16_t)(coef[c][(size_t)index * 64] | bits); }
+};
+
+}  // namespace
+
+int emulate_gpu_progressive_intervals(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4])
+{
+    (void)size;
+    std::vector<uint16_t> pool(prog_pool_words(f) + 64);
+    ProgImage im;
+    fill_prog_image(f, &im, pool.data());
+    im.pool = pool.data();
+    ProgIntervalImage iv;
+    fill_prog_interval_image(f, &iv);
+    // destuffed copies of every scan (the restart markers dropped), the interval starts in bits
+    std::vector<std::vector<uint8_t>> bytes(f.scans.size());
+    std::vector<HostStream> streams(f.scans.size());
+    std::vector<uint32_t> total_bits(f.scans.size());
+    std::vector<std::vector<uint32_t>> starts(f.scans.size());
+    for (size_t s = 0; s < f.scans.size(); s++) {
+        bytes[s].resize(destuffed_capacity(f.scans[s]) + 8);
+        const size_t n = destuff_scan(data, f.scans[s], bytes[s].data());
+        streams[s].bytes = bytes[s].data();
+        streams[s].nwords = (uint32_t)((((n + 3) & ~(size_t)3) + kStreamSlackBytes) / 4);
+        total_bits[s] = (uint32_t)n * 8u;
+        for (uint32_t b : f.scans[s].rst_after) starts[s].push_back(b * 8u);
+    }
+    for (int c = 0; c < f.ncomp; c++) memset(coef[c], 0, (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 128);
+    HostIntervalEnv ienv{streams.data(), total_bits.data(), starts.data(), pool.data(), &im};
+    ienv.coef = coef;
+    // ---- AC items: block start positions of every AC scan, one item per (component, interval)
+    std::vector<std::vector<uint32_t>> block_pos(f.scans.size());
+    for (int c = 0; c < f.ncomp; c++) {
+        const size_t nb = (size_t)im.nbx[c] * im.nby[c];
+        std::vector<uint64_t> hist(nb, 0);
+        for (int stg = 0; stg < (int)im.chain_len[c]; stg++) {
+            const int s = im.chain[c][stg];
+            block_pos[s].assign(nb, 0);
+            im.scan[s].block_pos = block_pos[s].data();
+        }
+        ienv.hist_all = hist.data();
+        for (uint32_t i = 0; i < iv.ac_count[c]; i++)
+            if (!prog_interval_ac(ienv, im, iv, c, i)) return 1;
+    }
+    // ---- replay: every block of every component
+    for (int c = 0; c < f.ncomp; c++) {
+        for (uint32_t by = 0; by < im.nby[c]; by++)
+            for (uint32_t bx = 0; bx < im.nbx[c]; bx++) {
+                HostReplayEnv env{streams.data(), pool.data(), &im, coef[c] + ((size_t)by * im.blocks_w[c] + bx) * 64};
+                if (!prog_replay_block(env, im, c, by * im.nbx[c] + bx)) return 1;
+            }
+    }
+    // ---- DC items: the DC scans in file order, one item per interval
+    for (int d = 0; d < (int)im.dc_len; d++) {
+        const uint32_t s = im.dc_chain[d];
+        for (uint32_t i = 0; i < iv.scan[s].count; i++)
+            if (!prog_interval_dc(ienv, im, iv, s, i)) return 1;
     }
     return 0;
 }

@@ -8,6 +8,7 @@
 
 #include "jpeg_syntax.h"
 #include "progressive_gpu_core.h"
+#include "progressive_interval_core.h"
 
 namespace hipjpeg {
 
@@ -53,5 +54,17 @@ void fill_prog_image(const FrameInfo& f, ProgImage* im, uint16_t* pool);
 // coef[c] = device-layout blocks with the DC coefficient in place (as entropy_decode.h).  Returns 0 on success, 1 when the
 // walk or the replay rejects the stream.
 int emulate_gpu_progressive(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4]);
+
+// ---- progressive scans with restart intervals (progressive_interval_core.h): a lane per interval in place of the walk
+// The rules of gpu_progressive_eligible() except the one about restart intervals, and: every scan has a restart interval of 1..65535,
+// plain stuffing and exactly ceil(MCUs of the scan / interval) - 1 markers; all AC scans of a component share one restart interval
+// (interval i then covers the same blocks in each of them).  Everything else keeps the host entropy stage.
+bool gpu_progressive_interval_eligible(const FrameInfo& f);
+// Fills every field of *iv except scan[].first_start and the hist pointers.
+void fill_prog_interval_image(const FrameInfo& f, ProgIntervalImage* iv);
+// Dynamic LDS of the interval kernels: the table slots of a component's chain (a DC first scan needs at most four of them).
+inline size_t prog_interval_lds_bytes(const ProgLdsShape& s) { return prog_slot_words(s) * 2 * kProgMaxStages; }
+// The interval kernels' algorithm + prog_replay_block on the host; result and return value as emulate_gpu_progressive.
+int emulate_gpu_progressive_intervals(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4]);
 
 }  // namespace hipjpeg

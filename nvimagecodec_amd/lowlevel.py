@@ -102,9 +102,28 @@ def entropy_decode_gpu_algorithm_host(data):
     return coefs, passes.value
 
 
+def entropy_decode_gpu_interval_algorithm_host(data):
+    """The interval algorithm of gpu_progressive_intervals (a lane per restart interval, then the replay) emulated on the host (no GPU).
+    Returns the coefficients in natural order; HipJpegError UNSUPPORTED for anything that is not a progressive file whose scans all have
+    restart intervals the kernels take."""
+    a = _as_u8(data)
+    info = get_image_info(a)
+    buf = np.zeros(info["coef_bytes"] // 2, dtype=np.int16)
+    offs = (ctypes.c_uint64 * 4)()
+    st = N.load().hipjpegEntropyDecodeGpuIntervalAlgorithmHost(a.ctypes.data, a.size, buf.ctypes.data, buf.nbytes, ctypes.addressof(offs))
+    if st:
+        raise N.HipJpegError(st, "hipjpegEntropyDecodeGpuIntervalAlgorithmHost")
+    coefs = []
+    for c in range(info["num_components"]):
+        n = info["blocks_w"][c] * info["blocks_h"][c]
+        blk = buf[offs[c]: offs[c] + n * 64].reshape(info["blocks_h"][c], info["blocks_w"][c], 8, 8)
+        coefs.append(np.ascontiguousarray(blk.transpose(0, 1, 3, 2)).reshape(info["blocks_h"][c], info["blocks_w"][c], 64))
+    return coefs
 
-def _decode_flags(fancy, gpu_huffman, fast_idct):
-    return (N.FLAG_FANCY_UPSAMPLING if fancy else 0) | (N.FLAG_GPU_HUFFMAN if gpu_huffman else 0) | (N.FLAG_FAST_IDCT if fast_idct else 0)
+
+def _decode_flags(fancy, gpu_huffman, fast_idct, gpu_progressive_intervals=False):
+    return ((N.FLAG_FANCY_UPSAMPLING if fancy else 0) | (N.FLAG_GPU_HUFFMAN if gpu_huffman else 0) | (N.FLAG_FAST_IDCT if fast_idct else 0) |
+            (N.FLAG_GPU_PROGRESSIVE_INTERVALS if gpu_progressive_intervals else 0))
 
 
 class BatchDecoder:
@@ -215,8 +234,10 @@ class BatchDecoder:
         if st:
             raise N.HipJpegError(st, "hipjpegDecodeBatchSetTransforms")
 
-    def decode(self, jpegs, fmt="rgb", fancy=True, outs=None, stream=None, check=True, gpu_huffman=False, transforms=None, fast_idct=False):
+    def decode(self, jpegs, fmt="rgb", fancy=True, outs=None, stream=None, check=True, gpu_huffman=False, transforms=None, fast_idct=False,
+               gpu_progressive_intervals=False):
         """Full pipeline.  Returns (outputs, statuses).  gpu_huffman=True: entropy-decode eligible streams on the GPU.
+        gpu_progressive_intervals=True (with gpu_huffman): progressive files whose scans all have restart intervals too, a lane per interval.
         fast_idct=True: the fast integer IDCT (JDCT_IFAST of libjpeg-turbo's x86-64 SIMD routine) instead of the default ISLOW one.
         transforms: per-image (roi, orientation) or None -- region of interest and EXIF orientation applied on the device."""
         if outs is None:
@@ -224,7 +245,7 @@ class BatchDecoder:
         if transforms is not None:
             self.set_transforms(transforms, len(jpegs))
         ptrs, lens, O, statuses = self._marshal(jpegs, outs, fmt)
-        flags = _decode_flags(fancy, gpu_huffman, fast_idct)
+        flags = _decode_flags(fancy, gpu_huffman, fast_idct, gpu_progressive_intervals)
         st = N.load().hipjpegDecodeBatch(self._h, ptrs, lens, len(jpegs), O, _FORMATS[fmt], flags, statuses, self._stream_ptr(stream))
         if st:
             raise N.HipJpegError(st, "hipjpegDecodeBatch")
@@ -266,9 +287,9 @@ class BatchDecoder:
         if st:
             raise N.HipJpegError(st, "hipjpegSetPipelineDepth")
 
-    def submit(self, jpegs, outs, fmt="rgb", fancy=True, stream=None, gpu_huffman=True, fast_idct=False):
+    def submit(self, jpegs, outs, fmt="rgb", fancy=True, stream=None, gpu_huffman=True, fast_idct=False, gpu_progressive_intervals=False):
         ptrs, lens, O, statuses = self._marshal(jpegs, outs, fmt)
-        flags = _decode_flags(fancy, gpu_huffman, fast_idct)
+        flags = _decode_flags(fancy, gpu_huffman, fast_idct, gpu_progressive_intervals)
         st = N.load().hipjpegDecodeBatchSubmit(self._h, ptrs, lens, len(jpegs), O, _FORMATS[fmt], flags, self._stream_ptr(stream))
         if st:
             raise N.HipJpegError(st, "hipjpegDecodeBatchSubmit")
@@ -288,9 +309,9 @@ class BatchDecoder:
         return statuses
 
     # -- the three phases separately (bench.py times device_stage with coefficients resident in HBM)
-    def host_stage(self, jpegs, outs, fmt="rgb", fancy=True, gpu_huffman=False, fast_idct=False):
+    def host_stage(self, jpegs, outs, fmt="rgb", fancy=True, gpu_huffman=False, fast_idct=False, gpu_progressive_intervals=False):
         ptrs, lens, O, statuses = self._marshal(jpegs, outs, fmt)
-        flags = _decode_flags(fancy, gpu_huffman, fast_idct)
+        flags = _decode_flags(fancy, gpu_huffman, fast_idct, gpu_progressive_intervals)
         st = N.load().hipjpegDecodeBatchHost(self._h, ptrs, lens, len(jpegs), O, _FORMATS[fmt], flags, statuses)
         if st:
             raise N.HipJpegError(st, "hipjpegDecodeBatchHost")
@@ -321,7 +342,8 @@ class BatchDecoder:
         N.load().hipjpegDecodeBatchTransferStats(self._h, ctypes.byref(h2d), ctypes.byref(sp))
         return dict(units=list(units), coef_bytes=cb.value, output_bytes=ob.value, gpu_entropy_images=gi.value, sync_launches=sl.value,
                     stream_bytes=sb.value, zero_copy_images=int(N.load().hipjpegDecodeBatchZeroCopyImages(self._h)), h2d_bytes=h2d.value,
-                    sparse_images=sp.value)
+                    sparse_images=sp.value, interval_images=int(N.load().hipjpegDecodeBatchIntervalImages(self._h)),
+                    interval_takeovers=int(N.load().hipjpegDecodeBatchIntervalTakeovers(self._h)))
 
     def statuses(self, n):
         st = (ctypes.c_int * n)()
@@ -600,14 +622,17 @@ def transcode_host(data, optimized_huffman=False, progressive=False, restart_int
 class BatchTranscoder:
     """hipjpegTranscodeBatch on one device: entropy decode, coefficient relayout kernel and entropy coder in one blocking call.
     gpu_huffman: both entropy stages on the GPU for every image each of them takes; gpu_restart: with gpu_huffman, the GPU coder also
-    takes baseline output with a restart interval (FLAG_GPU_RESTART_INTERVALS).  The bytes do not depend on either."""
+    takes baseline output with a restart interval (FLAG_GPU_RESTART_INTERVALS); gpu_progressive_intervals: with gpu_huffman, the GPU
+    decoder also takes progressive sources whose scans all have restart intervals (FLAG_GPU_PROGRESSIVE_INTERVALS).  The bytes do not
+    depend on any of them."""
 
-    def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False):
+    def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False, gpu_progressive_intervals=False):
         import torch
         self._torch = torch
         self.device = int(device)
         self.gpu_huffman = bool(gpu_huffman)
         self.gpu_restart = bool(gpu_restart)
+        self.gpu_progressive_intervals = bool(gpu_progressive_intervals)
         self._h = ctypes.c_void_p()
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
         if st:
@@ -638,7 +663,8 @@ class BatchTranscoder:
         n = len(jpegs)
         if gpu_huffman is None:
             gpu_huffman = self.gpu_huffman
-        flags = (N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0)) if gpu_huffman else 0
+        flags = (N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0) |
+                 (N.FLAG_GPU_PROGRESSIVE_INTERVALS if self.gpu_progressive_intervals else 0)) if gpu_huffman else 0
         per = [v if isinstance(v, (list, tuple)) else [v] * n for v in (optimized_huffman, progressive, restart_interval, orientation, grayscale,
                                                                          copy_markers)]
         P = (N.TranscodeParams * n)()
@@ -669,7 +695,8 @@ class BatchTranscoder:
     def stats(self):
         d, c, b = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         N.load().hipjpegTranscodeBatchStats(self._h, ctypes.byref(d), ctypes.byref(c), ctypes.byref(b))
-        return dict(gpu_decoded_images=d.value, gpu_coded_images=c.value, relayout_blocks=b.value)
+        return dict(gpu_decoded_images=d.value, gpu_coded_images=c.value, relayout_blocks=b.value,
+                    interval_takeovers=int(N.load().hipjpegDecodeBatchIntervalTakeovers(self._h)))
 
 
 # ---------------------------------------------------------------- coefficient tensors
@@ -798,14 +825,16 @@ class CoefficientImage:
 class BatchCoefficients:
     """hipjpegDecodeCoefficientsBatch / hipjpegEncodeCoefficientsBatch on one device: JPEG files to coefficient tensors and back, the
     tensors never leaving the device.  gpu_huffman: the entropy stage on the GPU for every image it takes; gpu_restart: with gpu_huffman,
-    the GPU coder also takes baseline output with a restart interval.  Neither the tensors nor the bytes depend on either."""
+    the GPU coder also takes baseline output with a restart interval; gpu_progressive_intervals: with gpu_huffman, the GPU decoder also
+    takes progressive files whose scans all have restart intervals.  Neither the tensors nor the bytes depend on any of them."""
 
-    def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False):
+    def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False, gpu_progressive_intervals=False):
         import torch
         self._torch = torch
         self.device = int(device)
         self.gpu_huffman = bool(gpu_huffman)
         self.gpu_restart = bool(gpu_restart)
+        self.gpu_progressive_intervals = bool(gpu_progressive_intervals)
         self._h = ctypes.c_void_p()
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
         if st:
@@ -828,7 +857,8 @@ class BatchCoefficients:
             raise N.HipJpegError(st, "hipjpegSetHybridHuffmanThreshold")
 
     def _flags(self):
-        return (N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0)) if self.gpu_huffman else 0
+        return (N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0) |
+                (N.FLAG_GPU_PROGRESSIVE_INTERVALS if self.gpu_progressive_intervals else 0)) if self.gpu_huffman else 0
 
     def _stream_ptr(self, stream):
         s = stream if stream is not None else self._torch.cuda.current_stream(self.device)
@@ -1038,4 +1068,5 @@ class BatchCoefficients:
     def stats(self):
         d, c, b = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
         N.load().hipjpegCoefficientsBatchStats(self._h, ctypes.byref(d), ctypes.byref(c), ctypes.byref(b))
-        return dict(gpu_decoded_images=d.value, gpu_coded_images=c.value, moved_blocks=b.value)
+        return dict(gpu_decoded_images=d.value, gpu_coded_images=c.value, moved_blocks=b.value,
+                    interval_takeovers=int(N.load().hipjpegDecodeBatchIntervalTakeovers(self._h)))
