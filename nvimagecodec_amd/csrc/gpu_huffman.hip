@@ -68,54 +68,62 @@ __device__ __forceinline__ uint32_t load_boundary(const uint32_t* boundaries, ui
 {
     return i < n ? ((const HJ_GLOBAL uint32_t*)boundaries)[i] : 0xFFFFFFFFu;
 }
-// How the lane walks take a block's end and a long code (WalkPolicy, huffman_gpu_core.h).  huff_sync_kernel, whose waves have
-// every lane busy, takes both as selects, with the table selection in registers and a long code as a step of its own.  The lane
-// mode of the tail kernels and huff_pos_kernel keep the branches, tsel[] in LDS and the second-level read inside the branch:
-// with a few lanes busy, often one, a branch that is not taken is the cheapest form, and each of the three changes made these
-// kernels slower (profiles/walk_steps/README.md).  The select form has a step of its own (select_walk: the MCU position as a
-// countdown, the tables as two halves with the pool's base inside, the chosen entry taken apart once;
-// profiles/walk_step_diet/README.md); what all forms share by construction is the pair table's layout.
-// A/B switch (tools/build_variant.sh) for the builds that were measured: bit 0 = table selection from registers, bit 1 = a long
-// code is a step of its own, bit 2 = both events as selects in huff_sync_kernel, bit 3 = bits 0 and 1 in huff_sync_kernel only.
-#ifndef HJ_WALK_PARTS
-#define HJ_WALK_PARTS 15
-#endif
-constexpr int kWalkParts = HJ_WALK_PARTS;
-static_assert((kWalkParts & 4) == 0 || (kWalkParts & 3) == 3, "the select form needs the registers and the long step");
-constexpr bool kLaneRegisters = (kWalkParts & 9) == 1, kLaneLongStep = (kWalkParts & 10) == 2;
-typedef WalkPolicy<(kWalkParts & 2) != 0, (kWalkParts & 4) != 0> SyncWalk;
-typedef WalkPolicy<kLaneLongStep, false> LaneWalk;
+// How the lane walks take a block's end and a long code (huffman_gpu_core.h has both routines).  huff_sync_kernel, whose waves
+// have every lane busy, takes both as selects (select_walk: the table selection in registers, a long code as a step of its own,
+// the MCU position as a countdown, the tables as two halves with the pool's base inside; profiles/walk_step_diet/README.md).  The
+// lane mode of the tail kernels and huff_pos_kernel keep the branches (decode_subsequence, position_subsequence), tsel[] in LDS
+// and the second-level read inside the branch: with a few lanes busy, often one, a branch that is not taken is the cheapest form
+// (profiles/walk_steps/README.md).  What both forms share by construction is the pair table's layout.
 
-// The image's table selection as wave-uniform values (byte offsets, as tsel[] holds them): a few dozen scalar instructions once
-// per wave.  in_vgprs: the pairs are held in vector registers -- a select between two of them is then one v_bfi_b32, where two
-// scalar operands would cost a second instruction (for the walks that select in every step; the measured builds that selected
-// inside the tail kernels' rare branch kept them scalar, those kernels have no registers to spare).
-// COUNTDOWN: in the order of the select step's position count (make_countdown_classes).
-template <bool IN_VGPRS, bool COUNTDOWN = false>
-__device__ __forceinline__ TableClasses table_classes(const HuffImage& im)
+// The image's lookup tables in LDS as every walk reads them: one definition of the accessors huffman_gpu_core.h asks an Env for.
+struct LdsTables {
+    uint32_t pool;                // LDS byte address of the lookup tables
+    const HJ_LDS uint32_t* tsel;  // per MCU position: BYTE offsets of the DC / AC first-level tables, packed lo/hi
+    // byte offset of the window's entry inside a first-level (or pair) table, inside a second-level table
+    static __device__ __forceinline__ uint32_t index1(uint32_t w) { return (w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2); }
+    static __device__ __forceinline__ uint32_t index2(uint32_t w) { return (w >> 15) & ((2u << kHuffSubBits) - 2); }
+    __device__ __forceinline__ uint32_t tables(int k) const { return tsel[k]; }
+    __device__ __forceinline__ uint32_t lookup1(uint32_t t, uint32_t w) const { return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + t + index1(w)); }
+    __device__ __forceinline__ uint32_t lookup2(uint32_t e, uint32_t w) const  // (pool offset / 64 entries -> bytes)
+    {
+        return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + ((e & 0x1FFu) << 7) + index2(w));
+    }
+    __device__ __forceinline__ uint32_t lookup_pair(uint32_t t, uint32_t w) const  // lookup1's address + a constant: one more LDS read, no more arithmetic
+    {
+        return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + t + 2 * kPairOffset + index1(w));
+    }
+};
+
+// The table selection of the select step (select_walk) as wave-uniform values: a few dozen scalar instructions once per wave.  The
+// classes in countdown order, of byte offsets as tsel[] holds them; pairs and halves are held in vector registers -- a select between two of
+// them is then one v_bfi_b32, where two scalar operands would cost a second instruction.  pool: LDS byte address of the tables.
+__device__ __forceinline__ StepTables make_step_tables(const HuffImage& im, uint32_t pool)
 {
     const auto of = [&](uint32_t q) { return ((uint32_t)im.k[q].tdc * 2) | ((uint32_t)im.k[q].tac * 2 << 16); };
-    TableClasses c = COUNTDOWN ? make_countdown_classes(im.blocks_per_mcu, of) : make_table_classes(im.blocks_per_mcu, of);
+    TableClasses c = make_countdown_classes(im.blocks_per_mcu, of);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         c.pair[i] = HJ_UNIFORM(c.pair[i]);
-        if (IN_VGPRS) asm("" : "+v"(c.pair[i]));
+        asm("" : "+v"(c.pair[i]));
     }
     c.bit0 = HJ_UNIFORM(c.bit0);
     c.bit1 = HJ_UNIFORM(c.bit1);
-    return c;
+    StepTables s = split_classes(c, 1u, pool);  // (the classes hold byte offsets)
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        asm("" : "+v"(s.dc[i]));
+        asm("" : "+v"(s.ac[i]));
+    }
+    return s;
 }
 
-// LDS accessors for decode_subsequence.
-struct DevEnv {
+// The sync and position kernels' environment: a lane's row of the staged stream, the tables.
+struct DevEnv : LdsTables {
     uint32_t stream_base;  // LDS byte address of the staged words
     uint32_t word0;        // image word index of the first word of staged row 0
     uint32_t row_addr;     // this lane's walk: LDS byte address of word 0 of its row ...
     uint32_t row_word0;    // ... and the image word index of that word (set_row)
-    uint32_t pool;         // LDS byte address of the lookup tables
-    const HJ_LDS uint32_t* tsel;  // per MCU position: BYTE offsets of the DC / AC first-level tables, packed lo/hi
-    TableClasses classes;         // the same selection from registers (table_classes), for the walks that select in every step
-    StepTables step;              // ... as the select step takes it: DC and AC halves as LDS addresses (split_classes)
+    StepTables step;       // for huff_sync_kernel: the table selection as the select step takes it (make_step_tables)
     const uint32_t* boundaries;
     uint32_t num_boundaries;
     __device__ __forceinline__ uint32_t boundary(uint32_t i) const { return load_boundary(boundaries, num_boundaries, i); }
@@ -127,20 +135,6 @@ struct DevEnv {
     }
     __device__ __forceinline__ uint32_t cursor(uint32_t i) const { return row_addr + (i - row_word0) * kCursorStep; }
     __device__ __forceinline__ uint32_t fetch(uint32_t c) const { return *(const HJ_LDS uint32_t*)(uintptr_t)c; }
-    __device__ __forceinline__ uint32_t tables(int k) const { return kLaneRegisters ? select_tables(classes, (uint32_t)k) : tsel[k]; }
-    __device__ __forceinline__ uint32_t lookup1(uint32_t t, uint32_t w) const
-    {
-        return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + t + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
-    }
-    __device__ __forceinline__ uint32_t lookup2(uint32_t e, uint32_t w) const
-    {
-        return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + ((e & 0x1FFu) << 7) + ((w >> 15) & ((2u << kHuffSubBits) - 2)));
-    }
-    __device__ __forceinline__ uint32_t second_table(uint32_t e) const { return (e & 0x1FFu) << 7; }  // pool offset / 64 entries -> bytes
-    __device__ __forceinline__ uint32_t lookup_pair(uint32_t t, uint32_t w) const  // lookup1's address + a constant: one more LDS read, no more arithmetic
-    {
-        return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + t + 2 * kPairOffset + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
-    }
 };
 
 __device__ __forceinline__ uint32_t boundary0_of(const HuffImage& im, uint32_t subseq)
@@ -174,44 +168,31 @@ __device__ __forceinline__ void put_mark(const SlotRecorder& r, uint32_t begin, 
     *(HJ_GLOBAL uint16_t*)(r.records + (r.off + 2 * kRecMark)) = (uint16_t)record_mark(begin, min(limit, total_bits), z0, st);
 }
 
-// decode_subsequence with or without restart handling (wave-uniform choice: one image per workgroup), with or without records
-// (uniform too; never across restart boundaries)
-template <class Policy, class Env>
-__device__ __forceinline__ SubseqState walk_with(bool rst, bool record, const HuffGeom& geom, const Env& env, uint32_t begin, uint32_t limit, int z, int k,
-                                                 uint32_t boundary0, const SlotRecorder& rec)
-{
-    if (rst) return decode_subsequence<true, Env, NoRecord, Policy>(geom, env, begin, limit, z, k, boundary0);
-    return record ? decode_subsequence<false, Env, SlotRecorder, Policy>(geom, env, begin, limit, z, k, 0, rec)
-                  : decode_subsequence<false, Env, NoRecord, Policy>(geom, env, begin, limit, z, k);
-}
 // The environment of the select step (select_walk): the tables of an MCU position from registers -- four classes, or at most two --
 // as LDS addresses with the pool's base inside, so that a lookup adds nothing but the window's index.
-template <class Env, bool FOUR>
-struct StepEnv : Env {
-    __device__ __forceinline__ explicit StepEnv(const Env& e) : Env(e) {}
-    __device__ __forceinline__ void step_tables(uint32_t d, uint32_t* tdc, uint32_t* tac) const { select_halves<FOUR>(this->step, d, tdc, tac); }
-    __device__ __forceinline__ uint32_t step_entry(uint32_t t, uint32_t w) const
-    {
-        return *(const HJ_LDS uint16_t*)(uintptr_t)(t + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
-    }
+template <bool FOUR>
+struct StepEnv : DevEnv {
+    __device__ __forceinline__ explicit StepEnv(const DevEnv& e) : DevEnv(e) {}
+    __device__ __forceinline__ void step_tables(uint32_t d, uint32_t* tdc, uint32_t* tac) const { select_halves<FOUR>(step, d, tdc, tac); }
+    __device__ __forceinline__ uint32_t step_entry(uint32_t t, uint32_t w) const { return *(const HJ_LDS uint16_t*)(uintptr_t)(t + index1(w)); }
     __device__ __forceinline__ uint32_t step_pair(uint32_t t, uint32_t w) const  // the same address + a constant
     {
-        return *(const HJ_LDS uint16_t*)(uintptr_t)(t + 2 * kPairOffset + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
+        return *(const HJ_LDS uint16_t*)(uintptr_t)(t + 2 * kPairOffset + index1(w));
     }
-    __device__ __forceinline__ uint32_t step_second(uint32_t e) const { return second_table_of(e, 7u, this->pool); }  // / 64 entries -> bytes
+    __device__ __forceinline__ uint32_t step_second(uint32_t e) const { return second_table_of(e, 7u, pool); }  // / 64 entries -> bytes
 };
-template <class Policy, class Env>
-__device__ __forceinline__ SubseqState walk_subsequence(bool rst, bool record, const HuffGeom& geom, const Env& env, uint32_t begin, uint32_t limit, int z,
-                                                        int k, uint32_t boundary0, const SlotRecorder& rec)
+// huff_sync_kernel's walk: the select form, with or without restart handling (a wave-uniform choice: one image per workgroup), with
+// or without records (uniform too; never across restart boundaries).  The everyday scan's two table classes get the short
+// selection (uniform as well).
+__device__ __forceinline__ SubseqState sync_walk(bool rst, bool record, const HuffGeom& geom, const DevEnv& env, uint32_t begin, uint32_t limit, int z, int k,
+                                                 uint32_t boundary0, const SlotRecorder& rec)
 {
-    // the select form looks the tables up in every step: from registers, and the everyday scan's two classes get the short
-    // selection (a uniform choice)
-    if constexpr (Policy::kSelects) {
-        if (env.classes.bit1 == 0) return walk_with<Policy>(rst, record, geom, StepEnv<Env, false>(env), begin, limit, z, k, boundary0, rec);
-        return walk_with<Policy>(rst, record, geom, StepEnv<Env, true>(env), begin, limit, z, k, boundary0, rec);
-    } else {
-        return walk_with<Policy>(rst, record, geom, env, begin, limit, z, k, boundary0, rec);
-    }
+    const auto walk = [&](const auto& senv) {
+        if (rst) return select_walk<true>(geom, senv, begin, limit, z, k, boundary0);
+        return record ? select_walk<false>(geom, senv, begin, limit, z, k, 0, rec) : select_walk<false>(geom, senv, begin, limit, z, k);
+    };
+    if (env.step.bit1 == 0) return walk(StepEnv<false>(env));
+    return walk(StepEnv<true>(env));
 }
 
 // Cooperative staging of stream words: lane t brings in row t = subsequence first_row + t of the image (first_row may be -1:
@@ -303,16 +284,10 @@ __device__ __forceinline__ DevEnv make_env(WgShared& sh, HJ_LDS uint16_t* pool, 
     env.row_word0 = env.word0;
     env.pool = (uint32_t)(uintptr_t)pool;
     env.tsel = (const HJ_LDS uint32_t*)sh.tsel;
-    // (tables(k) reads the classes only in the measurement builds with kLaneRegisters, and wants them in order of k there; everywhere
-    // else they say how many there are, which the countdown order says as well)
-    const TableClasses down = table_classes<true, true>(im);
-    env.classes = kLaneRegisters ? table_classes<true>(im) : down;
-    env.step = split_classes(down, 1u, env.pool);  // (the classes hold byte offsets)
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        asm("" : "+v"(env.step.dc[i]));
-        asm("" : "+v"(env.step.ac[i]));
-    }
+    // (huff_pos_kernel never takes the select step, but the compiler keeps some ninety scalar instructions of the class builder in
+    // it: the tables move out of that kernel together with a change that is allowed to move its code;
+    // profiles/walk_two_forms/README.md)
+    env.step = make_step_tables(im, env.pool);
     env.boundaries = geom.boundaries;
     env.num_boundaries = geom.num_boundaries;
     return env;
@@ -692,7 +667,7 @@ __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage
         if (owner || (t == 0 && u.first > 0)) {
             const uint32_t bidx0 = boundary0_of(im, j);
             env.set_row(t);
-            mine = pack_state(walk_subsequence<SyncWalk>(rst, false, geom, env, j * kSubseqBits, (j + 1) * kSubseqBits, 0, 0, bidx0, SlotRecorder()));
+            mine = pack_state(sync_walk(rst, false,geom, env, j * kSubseqBits, (j + 1) * kSubseqBits, 0, 0, bidx0, SlotRecorder()));
         }
         sh.end[t] = mine;
         __syncthreads();
@@ -716,7 +691,7 @@ __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage
             env.set_row(task);  // the predecessor's walk ended on a symbol that starts in this row
             const uint32_t jt = u.first - 1 + task;
             const SlotRecorder rec = slot_recorder(records, im, jt);
-            const SubseqState st = walk_subsequence<SyncWalk>(rst, recording, geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
+            const SubseqState st = sync_walk(rst, recording,geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
             if (recording) put_mark(rec, p.end_bit, (jt + 1) * kSubseqBits, geom.total_bits, p.zk & 255, st);
             now = pack_state(st);
             moved = ((now ^ sh.end[task]) & kSyncMask) != 0;
@@ -781,33 +756,24 @@ struct TailShared {
     uint32_t tsel[10];
 };
 
-struct TailEnv {
+struct TailEnv : LdsTables {
     uint32_t row_base;  // LDS byte address of this lane's row buffer
     uint32_t word0;     // image word index of its first word
-    uint32_t pool;
-    const HJ_LDS uint32_t* tsel;  // for the whole-wave mode (CoopWindow)
-    TableClasses classes;         // (measurement builds only: kLaneRegisters)
     const uint32_t* boundaries;
     uint32_t num_boundaries;
     __device__ __forceinline__ uint32_t boundary(uint32_t i) const { return load_boundary(boundaries, num_boundaries, i); }
     static constexpr uint32_t kCursorStep = (uint32_t)kTailSlots * 4u;  // the slots are transposed like the rows of the sync kernel
     __device__ __forceinline__ uint32_t cursor(uint32_t i) const { return row_base + (i - word0) * kCursorStep; }
     __device__ __forceinline__ uint32_t fetch(uint32_t c) const { return *(const HJ_LDS uint32_t*)(uintptr_t)c; }
-    __device__ __forceinline__ uint32_t tables(int k) const { return kLaneRegisters ? select_tables(classes, (uint32_t)k) : tsel[k]; }
-    __device__ __forceinline__ uint32_t lookup1(uint32_t t, uint32_t w) const
-    {
-        return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + t + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
-    }
-    __device__ __forceinline__ uint32_t lookup2(uint32_t e, uint32_t w) const
-    {
-        return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + ((e & 0x1FFu) << 7) + ((w >> 15) & ((2u << kHuffSubBits) - 2)));
-    }
-    __device__ __forceinline__ uint32_t second_table(uint32_t e) const { return (e & 0x1FFu) << 7; }  // pool offset / 64 entries -> bytes
-    __device__ __forceinline__ uint32_t lookup_pair(uint32_t t, uint32_t w) const  // lookup1's address + a constant: one more LDS read, no more arithmetic
-    {
-        return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + t + 2 * kPairOffset + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
-    }
 };
+// The walk of a tail lane: the branch form, with or without restart handling (a wave-uniform choice: one image per wave), with or
+// without records (uniform too; never across restart boundaries).
+__device__ __forceinline__ SubseqState lane_walk(bool rst, bool record, const HuffGeom& geom, const TailEnv& env, uint32_t begin, uint32_t limit, int z, int k,
+                                                 uint32_t boundary0, const SlotRecorder& rec)
+{
+    if (rst) return decode_subsequence<true>(geom, env, begin, limit, z, k, boundary0);
+    return record ? decode_subsequence<false>(geom, env, begin, limit, z, k, 0, rec) : decode_subsequence<false>(geom, env, begin, limit, z, k);
+}
 
 // orders a wave's own LDS / global traffic between its lanes (the waves of the tail kernel run on their own)
 __device__ __forceinline__ void wave_sync()
@@ -855,17 +821,14 @@ __device__ __forceinline__ uint32_t lane_read(uint32_t v, uint32_t lane) { retur
 // row: the wave's row buffer (word j of the subsequence at row[j * kTailSlots], kTailRowWords of them), staged by the caller
 // The window of cooperative_subsequence (huffman_gpu_core.h) on a wave: lane l holds the entries for bit offset l.
 // row: the wave's row buffer (word j of the subsequence at row[j * kTailSlots], kTailRowWords of them), staged by the caller.
-struct CoopWindow {
-    uint32_t pool;
-    const HJ_LDS uint32_t* tsel;
+struct CoopWindow : LdsTables {
     const HJ_LDS uint32_t* row;
     uint32_t row_bit0, lane;
     uint32_t edc, eac;
-    __device__ __forceinline__ uint32_t tables(uint32_t k) const { return tsel[k]; }
     __device__ __forceinline__ uint32_t entry(uint32_t table, uint32_t w) const
     {
-        uint32_t e = *(const HJ_LDS uint16_t*)(uintptr_t)(pool + table + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
-        if ((e >> 9) == kZadvLong) e = *(const HJ_LDS uint16_t*)(uintptr_t)(pool + ((e & 0x1FFu) << 7) + ((w >> 15) & ((2u << kHuffSubBits) - 2)));
+        uint32_t e = lookup1(table, w);
+        if ((e >> 9) == kZadvLong) e = lookup2(e, w);
         return e;
     }
     __device__ __forceinline__ void open(uint32_t pos, uint32_t ts)
@@ -971,8 +934,7 @@ __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage&
         if (kCoopChains > 0 && n <= (uint32_t)kCoopChains && !rst) {
             // the few chains that are left, one after the other, each followed to its end by the whole wave (cooperative_subsequence)
             CoopWindow win;
-            win.pool = env.pool;
-            win.tsel = env.tsel;
+            static_cast<LdsTables&>(win) = env;
             win.row = (const HJ_LDS uint32_t*)&ws.rows[0];
             win.lane = (uint32_t)lane;
             win.edc = win.eac = 0;
@@ -1041,7 +1003,7 @@ __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage&
                 const SubseqState p = unpack_state(before);
                 const uint32_t jt = u.first - 1 + task;
                 const SlotRecorder rec = slot_recorder(records, im, jt);
-                const SubseqState st = walk_subsequence<LaneWalk>(rst, recording, geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
+                const SubseqState st = lane_walk(rst, recording,geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
                 if (recording) put_mark(rec, p.end_bit, (jt + 1) * kSubseqBits, geom.total_bits, p.zk & 255, st);
                 now = pack_state(st);
                 moved = ((now ^ old) & kSyncMask) != 0;
@@ -1153,7 +1115,6 @@ __global__ __launch_bounds__(kTailThreads, 5) void huff_tail_kernel(HuffImage* _
             env.word0 = 0;
             env.pool = (uint32_t)(uintptr_t)pool;
             env.tsel = (const HJ_LDS uint32_t*)sh.tsel;
-            env.classes = kLaneRegisters ? table_classes<false>(im) : TableClasses();
             env.boundaries = im.boundaries;
             env.num_boundaries = im.num_boundaries;
             tail_group<RIPPLE>(sh.wave[wave], env, im, u, ui, lane, states, incoming, counters, tail_tasks, pending, pass_id, records);
@@ -1385,11 +1346,10 @@ constexpr unsigned lds_allocated(unsigned bytes) { return (bytes + kLdsGranule -
 static_assert(2 * lds_allocated((unsigned)sizeof(BlockShared) + kStandardPoolBytes) <= kLdsBytesPerCu,
               "two 512-lane workgroups of the block pass per CU (16 waves) with the standard lookup tables");
 
-struct BlockEnv {
+struct BlockEnv : LdsTables {
     const uint32_t* gstream;
     uint32_t gwords;
-    uint32_t pool, buf;  // LDS byte addresses: lookup tables; this lane's block buffer with its swizzle, (L * 128 | (L & 7) << 4)
-    const HJ_LDS uint32_t* tsel;
+    uint32_t buf;  // LDS byte address of this lane's block buffer with its swizzle, (L * 128 | (L & 7) << 4)
     const HJ_LDS KSlot* kslot;
     const HJ_LDS uint8_t* zz;
     static constexpr uint32_t kCursorStep = 1;  // the cursor is the word index
@@ -1405,15 +1365,6 @@ struct BlockEnv {
         // (byte offset in 32 bits -- a stream is far below 4 GB: SGPR base + VGPR offset addressing)
         const uint32_t x = *(const HJ_GLOBAL uint32_t*)((const HJ_GLOBAL char*)gstream + (min(i, gwords - 1) << 2));
         return i < gwords ? __builtin_bswap32(x) : ~0u;
-    }
-    __device__ __forceinline__ uint32_t tables(int k) const { return tsel[k]; }
-    __device__ __forceinline__ uint32_t lookup1(uint32_t t, uint32_t w) const
-    {
-        return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + t + ((w >> (31 - kHuffFastBits)) & ((2u << kHuffFastBits) - 2)));
-    }
-    __device__ __forceinline__ uint32_t lookup2(uint32_t e, uint32_t w) const
-    {
-        return *(const HJ_LDS uint16_t*)(uintptr_t)(pool + ((e & 0x1FFu) << 7) + ((w >> 15) & ((2u << kHuffSubBits) - 2)));
     }
     __device__ __forceinline__ int16_t* block_ptr(int k, uint32_t mx, uint32_t my) const
     {

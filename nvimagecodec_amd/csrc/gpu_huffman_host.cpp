@@ -287,7 +287,6 @@ struct HostEnv {
     uint32_t boundary(uint32_t i) const { return i < im->num_boundaries ? im->boundaries[i] : 0xFFFFFFFFu; }
     uint32_t lookup1(uint32_t t, uint32_t w) const { return im->pool[t + (w >> (32 - kHuffFastBits))]; }
     uint32_t lookup2(uint32_t e, uint32_t w) const { return im->pool[(e & 0x1FFu) * 64u + ((w >> 16) & ((1u << kHuffSubBits) - 1))]; }
-    uint32_t second_table(uint32_t e) const { return (e & 0x1FFu) * 64u; }
     uint32_t lookup_pair(uint32_t t, uint32_t w) const
     {
         const size_t i = (size_t)t + kPairOffset + (w >> (32 - kHuffFastBits));
@@ -303,12 +302,8 @@ struct HostEnv {
     int16_t* buf;  // block buffer: 64 coefficients
     void put(int index, int value) const { buf[index] = (int16_t)value; }
     // the select step (select_walk): the tables from the classes as the kernels hold them, in the step's own position count
-    TableClasses classes;
     StepTables step;
-    void step_tables(uint32_t d, uint32_t* tdc, uint32_t* tac) const
-    {
-        select_halves<true>(step, d, tdc, tac);
-    }
+    void step_tables(uint32_t d, uint32_t* tdc, uint32_t* tac) const { select_halves<true>(step, d, tdc, tac); }
     uint32_t step_entry(uint32_t t, uint32_t w) const { return lookup1(t, w); }
     uint32_t step_pair(uint32_t t, uint32_t w) const { return lookup_pair(t, w); }
     uint32_t step_second(uint32_t e) const { return second_table_of(e, 6u, 0u); }
@@ -381,9 +376,21 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
         for (size_t y = 0; y < rows; y++) memset(coef + y * bw * 64, 0x5A, cols * 128);
     }
     int16_t block_buffer[64] = {0};
-    HostEnv env{&im, block_buffer, TableClasses(), StepTables()};
-    env.classes = make_countdown_classes(im.blocks_per_mcu, [&](uint32_t q) { return env.tables((int)q); });
-    env.step = split_classes(env.classes, 1u, 0u);
+    HostEnv env{&im, block_buffer, StepTables()};
+    // The kernels select the tables of an MCU position from registers (TableClasses, in the select step's countdown order, split into
+    // halves): the same builder, here, must reproduce env.tables() for every position (else return 5).  (The step's count itself is
+    // checked with every walk below: its end state carries the position counted upwards again, recomputed from the countdown, and
+    // must equal that of the branch form, which counts upwards.)
+    {
+        const TableClasses classes = make_countdown_classes(im.blocks_per_mcu, [&](uint32_t q) { return env.tables((int)q); });
+        if (!classes.complete) return 5;
+        env.step = split_classes(classes, 1u, 0u);
+        for (uint32_t q = 0; q < im.blocks_per_mcu; q++) {
+            uint32_t tdc, tac;
+            env.step_tables(im.blocks_per_mcu - 1u - q, &tdc, &tac);
+            if ((tdc | (tac << 16)) != env.tables((int)q)) return 5;
+        }
+    }
     const HuffGeom geom = make_geom(im);
     const uint32_t ns = im.num_subseq;
     std::vector<SubseqState> cur(ns), nxt(ns);
@@ -392,54 +399,29 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
     // (in pass 0 only subsequence 0, whose start state is exact: the kernels decode it once more in round 1, from the same state).
     // Not for restart intervals.
     std::vector<uint16_t> records((size_t)ns * kRecShorts, 0);
-    // The kernels select the tables of an MCU position from registers (TableClasses): the same builder, here, must reproduce the
-    // array for every position (else return 5).
-    {
-        const TableClasses classes = make_table_classes(im.blocks_per_mcu, [&](uint32_t q) { return env.tables((int)q); });
-        if (!classes.complete) return 5;
-        for (uint32_t q = 0; q < im.blocks_per_mcu; q++)
-            if (select_tables(classes, q) != env.tables((int)q)) return 5;
-        // ... and the select step's own form of them: halves, by the position as that step counts it, downwards.  (The step's
-        // count itself is checked with every walk below: its end state carries the position counted upwards again, recomputed from
-        // the countdown, and must equal that of the branch forms, which count upwards.)
-        if (!env.classes.complete) return 5;
-        for (uint32_t q = 0; q < im.blocks_per_mcu; q++) {
-            uint32_t tdc, tac;
-            env.step_tables(im.blocks_per_mcu - 1u - q, &tdc, &tac);
-            if ((tdc | (tac << 16)) != env.tables((int)q)) return 5;
-        }
-    }
-    // Every walk runs in the form huff_sync_kernel uses (WalkSelects) and again in the form of the tail kernels' lanes and the
-    // position kernel (WalkBranches), and in the long-step branch form: same end state and same record, from true and from wrong
-    // start states, or `policies_differ` (return 5).
-    bool policies_differ = false;
+    // Every walk runs in the form huff_sync_kernel uses (select_walk) and again in the form of the tail kernels' lanes
+    // (decode_subsequence): same end state and same record, from true and from wrong start states, or `forms_differ` (return 5).
+    bool forms_differ = false;
     uint16_t other[kRecShorts];
     auto walk = [&](uint32_t i, uint32_t begin, int z, int k, bool record) {
         const uint32_t limit = (i + 1) * kSubseqBits;
         uint16_t* rec = &records[(size_t)i * kRecShorts];
+        SubseqState st, sb;
+        uint32_t mark = kRecInvalid;
+        size_t named = 0;  // bytes of the record the mark vouches for
         if (rst) {
-            rec[kRecMark] = (uint16_t)kRecInvalid;
-            const SubseqState st = decode_subsequence<true, HostEnv, NoRecord, WalkSelects>(geom, env, begin, limit, z, k, 0);
-            if (pack_state(st) != pack_state(decode_subsequence<true, HostEnv, NoRecord, WalkBranches>(geom, env, begin, limit, z, k, 0)) ||
-                pack_state(st) != pack_state(decode_subsequence<true, HostEnv, NoRecord, WalkLongBranches>(geom, env, begin, limit, z, k, 0)))
-                policies_differ = true;
-            return st;
+            st = select_walk<true>(geom, env, begin, limit, z, k, 0);
+            sb = decode_subsequence<true>(geom, env, begin, limit, z, k, 0);
+        } else if (!record) {
+            st = select_walk<false>(geom, env, begin, limit, z, k);
+            sb = decode_subsequence<false>(geom, env, begin, limit, z, k);
+        } else {
+            st = select_walk<false>(geom, env, begin, limit, z, k, 0, HostRecorder{rec, i * kSubseqBits});
+            sb = decode_subsequence<false>(geom, env, begin, limit, z, k, 0, HostRecorder{other, i * kSubseqBits});
+            mark = record_mark(begin, limit < geom.total_bits ? limit : geom.total_bits, (uint32_t)z, st);
+            named = mark_valid(mark) ? 2 * (mark & (kRecFresh - 1)) : 0;
         }
-        if (!record) {
-            const SubseqState st = decode_subsequence<false, HostEnv, NoRecord, WalkSelects>(geom, env, begin, limit, z, k);
-            if (pack_state(st) != pack_state(decode_subsequence<false, HostEnv, NoRecord, WalkBranches>(geom, env, begin, limit, z, k)) ||
-                pack_state(st) != pack_state(decode_subsequence<false, HostEnv, NoRecord, WalkLongBranches>(geom, env, begin, limit, z, k)))
-                policies_differ = true;
-            rec[kRecMark] = (uint16_t)kRecInvalid;
-            return st;
-        }
-        const SubseqState st = decode_subsequence<false, HostEnv, HostRecorder, WalkSelects>(geom, env, begin, limit, z, k, 0, HostRecorder{rec, i * kSubseqBits});
-        const uint32_t mark = record_mark(begin, limit < geom.total_bits ? limit : geom.total_bits, (uint32_t)z, st);
-        const size_t named = mark_valid(mark) ? 2 * (mark & (kRecFresh - 1)) : 0;
-        const SubseqState sb = decode_subsequence<false, HostEnv, HostRecorder, WalkBranches>(geom, env, begin, limit, z, k, 0, HostRecorder{other, i * kSubseqBits});
-        if (pack_state(st) != pack_state(sb) || memcmp(other, rec, named) != 0) policies_differ = true;
-        const SubseqState sl = decode_subsequence<false, HostEnv, HostRecorder, WalkLongBranches>(geom, env, begin, limit, z, k, 0, HostRecorder{other, i * kSubseqBits});
-        if (pack_state(st) != pack_state(sl) || memcmp(other, rec, named) != 0) policies_differ = true;
+        if (pack_state(st) != pack_state(sb) || memcmp(other, rec, named) != 0) forms_differ = true;
         rec[kRecMark] = (uint16_t)mark;
         return st;
     };
@@ -460,7 +442,7 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
         if (passes > (int)ns + 2) return 3;  // cannot happen: the wave of corrections advances one subsequence per pass
     }
     if (sync_passes) *sync_passes = passes;
-    if (policies_differ) return 5;
+    if (forms_differ) return 5;
     if (!rst) {
         // The kernels follow the last links of a correction chain with the whole wave on one subsequence (cooperative_subsequence):
         // the same routine, here, must reproduce the lane decoder's end state for every subsequence -- from its true start state and

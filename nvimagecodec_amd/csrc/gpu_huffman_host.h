@@ -52,8 +52,9 @@ void fill_huff_image(const FrameInfo& f, const ScanHeader& sc, uint32_t stream_b
 // Runs pass 0, the synchronisation passes, the block-count scan, the write pass and the DC integration on the host, one
 // "lane" after the other, scan by scan (blocks no scan codes are left zero).  coef[c] = device-layout blocks (as entropy_decode.h).  Returns 0 on success, else the status the
 // kernels would report; *sync_passes receives the number of passes until the fixpoint.  Self-checks: 4 = the cooperative walk
-// disagrees with the lane walk, 5 = a block-start record disagrees with the position walk, the two forms of the lane walk (WalkPolicy)
-// disagree with each other, or the table classes do not reproduce the per-position table selection.
+// disagrees with the lane walk, 5 = a block-start record disagrees with the position walk, the two forms of the lane walk
+// (select_walk and decode_subsequence) disagree in end state or record, or the table classes do not reproduce the per-position
+// table selection.
 int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4], int* sync_passes);
 
 }  // namespace hipjpeg

@@ -370,13 +370,6 @@ HJ_HD uint32_t bit_mask(uint32_t bits, uint32_t k)  // all ones if bit k of `bit
     return 0u - ((bits >> k) & 1u);
 #endif
 }
-HJ_HD uint32_t select_tables(const TableClasses& c, uint32_t k)
-{
-    const uint32_t a = bit_mask(c.bit0, k), b = bit_mask(c.bit1, k);
-    return bit_select(b, bit_select(a, c.pair[3], c.pair[2]), bit_select(a, c.pair[1], c.pair[0]));
-}
-// the everyday case, at most two classes (bit1 == 0; luma and chroma, or one component): a bit mask and one select
-HJ_HD uint32_t select_tables2(const TableClasses& c, uint32_t k) { return bit_select(bit_mask(c.bit0, k), c.pair[1], c.pair[0]); }
 // The select step (select_walk below) keeps the MCU position as a COUNTDOWN d = blocks_per_mcu - 1 - k and wants the DC and the AC
 // table of a position as two values, each as its lookup takes a table (on the device an LDS address, the pool's base included):
 // the classes are built in countdown order (bit d of bit0 / bit1 = class of position blocks_per_mcu - 1 - d) and split once, outside
@@ -421,35 +414,30 @@ HJ_HD void select_halves(const StepTables& s, uint32_t d, uint32_t* tdc, uint32_
 // all of bits 9-15 set, so its pool offset / 64 (bits 0-8), scaled, is the whole entry shifted minus a constant: one shift-add.
 HJ_HD uint32_t second_table_of(uint32_t e, uint32_t shift, uint32_t base) { return (e << shift) + (base - (kZadvLong << (9u + shift))); }
 
-// How decode_subsequence treats its two rare events, the end of a block and a code longer than kHuffFastBits.  Rare for a lane --
-// 6 % and 2 % of a q90 photograph's symbols -- and almost certain for a wave of 64 lanes at independent places of the stream.
-//   kLongStep  a long code is a step of its own: the step that meets the first-level entry "continues in a second-level table"
-//              consumes nothing and changes no state; it points the next step's lookup at the second-level table and at the
-//              kHuffSubBits bits behind the first kHuffFastBits, and that step's ordinary lookup completes the symbol.  No table
-//              read inside a branch.  false: the second-level entry is read inside the rare branch (Env::lookup2).
-//   kSelects   both events are predicated straight-line code (only the record store stays conditional), the tables of the MCU
-//              position are looked up in every step (from registers: StepTables): for huff_sync_kernel, whose waves have every
-//              lane busy.  This form is a routine of its own, select_walk, with its own bookkeeping (the MCU position counts
-//              down); decode_subsequence hands over to it.
-// A lone lane gains from a branch that is not taken, and from the table read that hides inside it: the lane mode of the tail
-// kernels and the position kernel keep WalkBranches, the walk as it was before there were policies.  (A long step in the branch
-// form, WalkLongBranches, is slower than either in every kernel; it is kept as the measured middle step and checked with the
-// others by the host emulation.)
-template <bool LONG_STEP, bool SELECTS>
-struct WalkPolicy {
-    static constexpr bool kLongStep = LONG_STEP, kSelects = SELECTS;
-    static_assert(LONG_STEP || !SELECTS, "the select form has no memory read to predicate");
-};
-typedef WalkPolicy<false, false> WalkBranches;
-typedef WalkPolicy<true, false> WalkLongBranches;
-typedef WalkPolicy<true, true> WalkSelects;
+// The synchronisation decode has two rare events, the end of a block and a code longer than kHuffFastBits.  Rare for a lane -- 6 %
+// and 2 % of a q90 photograph's symbols -- and almost certain for a wave of 64 lanes at independent places of the stream.  So the
+// walk is written twice, same contract:
+//   select_walk         both events are predicated straight-line code (only the record store stays conditional).  The tables of the
+//                       MCU position are looked up in every step, from registers (StepTables), and a long code is a step of its own:
+//                       the step that meets the first-level entry "continues in a second-level table" consumes nothing and changes
+//                       no state; it points the next step's lookup at the second-level table and at the kHuffSubBits bits behind the
+//                       first kHuffFastBits, and that step's ordinary lookup completes the symbol.  No table read inside a branch.
+//                       For huff_sync_kernel, whose waves have every lane busy.
+//   decode_subsequence  both events are branches; the tables of the next MCU position (Env::tables) and the second-level entry
+//                       (Env::lookup2) are read inside them.  For the lane mode of the tail kernels; position_subsequence, the walk
+//                       of huff_pos_kernel, has the same shape.  A lone lane gains from a branch that is not taken, and from the
+//                       table read that hides inside it (DESIGN.md 3.2 has the measurements).
+// Both give the same state after every completed symbol, from true and from wrong start states alike, and the same records; the host
+// emulation runs every walk in both and compares.  A second-level step of select_walk never takes a pair, and as it follows its first
+// half without moving `pos`, a long code whose first half starts below `end` is finished by the same walk.
+
 // the window that indexes a second-level table through lookup1: its kHuffFastBits top bits = the kHuffSubBits bits behind the
 // first kHuffFastBits of w
 HJ_HD uint32_t sub_window(uint32_t w) { return (w << kHuffFastBits) >> (kHuffFastBits - kHuffSubBits); }
 
-// The select form of the synchronisation decode (WalkSelects: huff_sync_kernel, whose vector unit is the limiter -- every
-// instruction of this loop is worth several microseconds per 256-picture batch; DESIGN.md 3.2 has each part's measurement).  Same
-// contract as decode_subsequence below.  One step:
+// The select form of the synchronisation decode (huff_sync_kernel, whose vector unit is the limiter -- every instruction of this
+// loop is worth several microseconds per 256-picture batch; DESIGN.md 3.2 has each part's measurement).  Same contract as
+// decode_subsequence below.  One step:
 //   entries   the first-level entry e and the pair entry pr of the current table for the reader's window; behind a long code the
 //             table is a second-level one and the window the kHuffSubBits bits behind the first kHuffFastBits;
 //   choice    x = pr where the pair may be taken (pair_fits, the second symbol starts inside the range, not a second half), else
@@ -463,9 +451,10 @@ HJ_HD uint32_t sub_window(uint32_t w) { return (w << kHuffFastBits) >> (kHuffFas
 //   void     step_tables(uint32_t d, uint32_t* tdc, uint32_t* tac)   the tables of countdown position d
 //   uint32_t step_entry(t, w), step_pair(t, w)                       lookup1 / lookup_pair for a table as step_tables gives it
 //   uint32_t step_second(uint32_t e)                                 the second-level table behind the long entry e, likewise
-template <bool RST, class Env, class Rec>
-HJ_HD SubseqState select_walk(const HuffGeom& im, const Env& env, uint32_t begin, uint32_t limit, int z0, int k0, uint32_t boundary0, Rec rec)
+template <bool RST, class Env, class Rec = NoRecord>
+HJ_HD SubseqState select_walk(const HuffGeom& im, const Env& env, uint32_t begin, uint32_t limit, int z0, int k0, uint32_t boundary0 = 0, Rec rec = Rec())
 {
+    static_assert(!RST || std::is_same<Rec, NoRecord>::value, "records are not taken across restart boundaries");
     uint32_t pos = begin, nblocks = 0, z = (uint32_t)z0;
     const uint32_t end = limit < im.total_bits ? limit : im.total_bits;
     const uint32_t pair_end = end > (uint32_t)kHuffFastBits - 2 ? end - ((uint32_t)kHuffFastBits - 2) : 0;  // see decode_subsequence
@@ -536,9 +525,9 @@ HJ_HD SubseqState select_walk(const HuffGeom& im, const Env& env, uint32_t begin
     return st;
 }
 
-// Synchronisation decode: the symbols that START in [begin, limit) (and before total_bits), beginning in state (z, k).
-// Tracks the decoder state and counts the blocks completed; rec(i, pos) is told where each block starts (see the block-start records
-// above -- not for restart intervals, whose positions the position pass finds together with the damage check).
+// The branch form of the synchronisation decode: the symbols that START in [begin, limit) (and before total_bits), beginning in
+// state (z, k).  Tracks the decoder state and counts the blocks completed; rec(i, pos) is told where each block starts (see the
+// block-start records above -- not for restart intervals, whose positions the position pass finds together with the damage check).
 // Env supplies the memory accessors:
 //   uint32_t cursor(uint32_t i), fetch(cursor), kCursorStep   32-bit word i of the stream, first byte in the most significant
 //                                        position, through a cursor (see BitReader)
@@ -547,17 +536,12 @@ HJ_HD SubseqState select_walk(const HuffGeom& im, const Env& env, uint32_t begin
 //   uint32_t lookup1(uint32_t t, w)      first-level entry of table t for window w (index = top kHuffFastBits bits)
 //   uint32_t lookup2(uint32_t e, w)      second-level entry behind first-level entry e (index = next kHuffSubBits bits)
 //   uint32_t lookup_pair(uint32_t t, w)  pair-table entry of table t for window w (same index as lookup1, kPairOffset entries on)
-//   uint32_t second_table(uint32_t e)    the second-level table behind first-level entry e, as lookup1 wants a table
 // RST: the scan has restart intervals; boundary0 = index of the first boundary at or behind the subsequence's first bit.
-// Policy: WalkPolicy above.  Every policy gives the same state after every completed symbol, from true and from wrong start
-// states alike; a second-level step (kLongStep) never takes a pair, and as it follows its first half without moving `pos`, a long
-// code whose first half starts below `end` is finished by the same walk.
-template <bool RST, class Env, class Rec = NoRecord, class Policy = WalkBranches>
+template <bool RST, class Env, class Rec = NoRecord>
 HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_t begin, uint32_t limit, int z, int k, uint32_t boundary0 = 0,
                                      Rec rec = Rec())
 {
     static_assert(!RST || std::is_same<Rec, NoRecord>::value, "records are not taken across restart boundaries");
-    if constexpr (Policy::kSelects) return select_walk<RST>(im, env, begin, limit, z, k, boundary0, rec);
     uint32_t pos = begin, nblocks = 0;
     const uint32_t end = limit < im.total_bits ? limit : im.total_bits;
     // a pair's first symbol has at most kHuffFastBits - 2 bits: from here on the second one might start outside the range
@@ -579,70 +563,39 @@ HJ_HD SubseqState decode_subsequence(const HuffGeom& im, const Env& env, uint32_
     }
     const uint32_t fresh = z == 0 ? 1u : 0u;  // records: index of the next block to start = nblocks + fresh
     if (fresh && pos < end) rec(0u, pos);
-    // kLongStep: `sub` = this step is the second half of a long code: its table is a second-level one and its window `win` the
-    // bits behind the first kHuffFastBits; every other step looks at br.hi
-    uint32_t win = br.hi;
-    bool sub = false;
     while (pos < end) {
         const uint32_t fetched = env.fetch(br.next);
-        const uint32_t e = env.lookup1(tcur, win);
-        const uint32_t pr = env.lookup_pair(tcur, win);  // means something behind an AC table only (z != 0)
-        const bool two = pair_fits((uint32_t)z, e) && pos < pair_end && !sub;
+        const uint32_t e = env.lookup1(tcur, br.hi);
+        const uint32_t pr = env.lookup_pair(tcur, br.hi);  // means something behind an AC table only (z != 0)
+        const bool two = pair_fits((uint32_t)z, e) && pos < pair_end;
         // the entry the step takes: beside "long code" and "end of block" the pair entry is the single entry itself
         const uint32_t x = two ? pr : e;
         uint32_t tot = x & 31u;
         bool mcu_done = false;
         tcur = tsel >> 16;
         z += (int)(x >> 9);
-        if (Policy::kLongStep) {
-            const bool was_sub = sub;
-            sub = false;
-            if (z >= 64) {  // end of a block, or a code that continues in a second-level table
-                if ((x >> 9) == kZadvLong && !was_sub) {
-                    z -= (int)kZadvLong;
-                    tot = 0;
-                    tcur = env.second_table(x);
-                    sub = true;
-                } else {
-                    z = 0;
-                    rec(nblocks + fresh, pos + tot);
-                    nblocks++;
-                    if (++k == bpm) k = 0;
-                    tsel = env.tables(k);
-                    tcur = tsel & 0xFFFFu;
-                    mcu_done = k == 0;
-                }
+        if (z >= 64) {  // end of a block, or a code that continues in a second-level table
+            if ((x >> 9) == kZadvLong) {
+                const uint32_t e2 = env.lookup2(x, br.hi);
+                z += (int)(e2 >> 9) - (int)kZadvLong;
+                tot = e2 & 31u;
             }
-        } else {
-            if (z >= 64) {  // end of a block, or a code that continues in a second-level table
-                if ((x >> 9) == kZadvLong) {
-                    const uint32_t e2 = env.lookup2(x, br.hi);
-                    z += (int)(e2 >> 9) - (int)kZadvLong;
-                    tot = e2 & 31u;
-                }
-                if (z >= 64) {
-                    z = 0;
-                    rec(nblocks + fresh, pos + tot);
-                    nblocks++;
-                    if (++k == bpm) k = 0;
-                    tsel = env.tables(k);
-                    tcur = tsel & 0xFFFFu;
-                    mcu_done = k == 0;
-                }
+            if (z >= 64) {
+                z = 0;
+                rec(nblocks + fresh, pos + tot);
+                nblocks++;
+                if (++k == bpm) k = 0;
+                tsel = env.tables(k);
+                tcur = tsel & 0xFFFFu;
+                mcu_done = k == 0;
             }
         }
         pos += tot;
-        br.consume(tot, fetched);  // (a long code's first half: nothing, the reader stays where it is)
+        br.consume(tot, fetched);
         if (RST && mcu_done && rc.normalise(env, br.hi, &pos, &z, &k)) {
             tsel = env.tables(k);
             tcur = tsel & 0xFFFFu;
             br.start(env, pos);
-        }
-        if (Policy::kLongStep) {
-            const uint32_t behind = sub_window(br.hi);
-            win = sub ? behind : br.hi;
-        } else {
-            win = br.hi;
         }
     }
     SubseqState st;

@@ -1,6 +1,6 @@
 """Long codes in the GPU entropy walks, WITHOUT a GPU.  A code longer than the ten bits of the first-level lookup is, in
 huff_sync_kernel's walk, a step of its own: the step that meets it consumes nothing and points the next step's ordinary lookup at
-the second-level table and the six bits behind the first ten (WalkPolicy, csrc/huffman_gpu_core.h).  The streams
+the second-level table and the six bits behind the first ten (select_walk, csrc/huffman_gpu_core.h).  The streams
 (helpers/walk_files.py: one component, EOB, ZRL, four coefficient symbols and one DC category with codes of 11 to 16 bits) put such
 a code where the two halves can come apart: across a subsequence seam and the sync workgroup's seam, first behind a block end, as
 the EOB that ends a block exactly on a seam, as the stream's last symbol, twice in a row -- each without and with a restart

@@ -1,6 +1,6 @@
 """The select step of the synchronisation walk (csrc/huffman_gpu_core.h select_walk), WITHOUT a GPU: the MCU position kept as a
 countdown, the pair entry in the single entry's layout behind the test z + z1 < 64, a long code that zeroes the chosen entry.
-hipjpegEntropyDecodeGpuAlgorithmHost runs every walk in that form and in the tail kernels' two branch forms, which count the MCU
+hipjpegEntropyDecodeGpuAlgorithmHost runs every walk in that form and in the tail kernels' branch form, which counts the MCU
 position upwards, and returns INTERNAL_ERROR where end states (the position recovered from the countdown among them) or block-start
 records differ.  The files (helpers/walk_step_files.py) put the step on its edges: every wrap of the countdown (1, 3, 4, 6 and 10
 blocks per MCU; two, three and four table classes), first symbols that take z + z1 to 62, 63 and 64, EOB and ZRL as the second
