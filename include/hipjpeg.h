@@ -283,7 +283,14 @@ typedef struct {
 #define HIPJPEG_FLAG_GPU_RESTART_INTERVALS 8u /* encoding, together with HIPJPEG_FLAG_GPU_HUFFMAN in hipjpegEncodeBatchEntropy and
                                             hipjpegEncodeBatchSubmit: the GPU coder also takes baseline images (Annex-K or optimized tables)
                                             whose restart_interval is not 0.  Progressive output with a restart interval stays with the host
-                                            coder.  No meaning alone; the decode entry points ignore it. */
+                                            coder unless HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART is set.  No meaning alone; the decode entry
+                                            points ignore it. */
+#define HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART 32u /* encoding, together with HIPJPEG_FLAG_GPU_HUFFMAN in hipjpegEncodeBatchEntropy,
+                                            hipjpegEncodeBatchSubmit, hipjpegTranscodeBatch and hipjpegEncodeCoefficientsBatch: the GPU coder
+                                            also takes progressive output whose restart_interval is not 0 (jcphuff.c emit_restart on the
+                                            device: the EOB run flushed at every interval end, predictor reset, byte alignment, RSTn).
+                                            Independent of HIPJPEG_FLAG_GPU_RESTART_INTERVALS, which keeps meaning baseline images only.
+                                            No meaning alone; the decode entry points ignore it. */
 
 /* Device stage only: colour conversion + downsampling + FDCT + quantization for the whole batch (asynchronous). */
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchDevice(hipjpegHandle_t handle, const hipjpegEncodeInput_t* inputs,
@@ -300,7 +307,8 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchHost(hipjpegHandle_t handle, hipjp
  * go through the host coder as in hipjpegEncodeBatchHost, and so does everything when flags = 0.  flags = HIPJPEG_FLAG_GPU_HUFFMAN |
  * HIPJPEG_FLAG_GPU_RESTART_INTERVALS: the GPU coder takes baseline images with a restart interval too (predictor reset, byte alignment
  * and RSTn markers on the device, the markers exempt from byte stuffing; byte-identical to the host coder's files); progressive output
- * with a restart interval still goes to the host coder.  Blocking. */
+ * with a restart interval still goes to the host coder unless HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART is set as well (or instead: the two
+ * are independent), which sends it to the GPU coder with the same files.  Blocking. */
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchEntropy(hipjpegHandle_t handle, unsigned flags, hipjpegStatus_t* statuses);
 /* Both of the above. */
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatch(hipjpegHandle_t handle, const hipjpegEncodeInput_t* inputs, const hipjpegEncodeParams_t* params,
@@ -323,8 +331,8 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeGetCoefficients(hipjpegHandle_t handle,
                                                          int32_t grid[4] /* blocks_w, blocks_h, real_w, real_h */);
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeBatchStats(hipjpegHandle_t handle, int32_t* num_units, uint64_t* pixel_bytes, uint64_t* coef_bytes);
 /* How many images of the handle's last entropy stage the GPU entropy coder took (baseline with Annex-K or optimized tables, and
- * progressive output; with a restart interval only baseline images, and only under HIPJPEG_FLAG_GPU_RESTART_INTERVALS); the others were
- * coded by the host coder. */
+ * progressive output; with a restart interval baseline images under HIPJPEG_FLAG_GPU_RESTART_INTERVALS and progressive ones under
+ * HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART); the others were coded by the host coder. */
 HIPJPEG_API int32_t hipjpegEncodeBatchGpuEntropyImages(hipjpegHandle_t handle);
 /* Host-only: entropy-code given coefficient grids (zigzag order, MCU-padded grids as above) into a JFIF file.
  * Returns HIPJPEG_STATUS_BUFFER_TOO_SMALL with *length = needed size if capacity is insufficient. */
@@ -333,10 +341,17 @@ HIPJPEG_API hipjpegStatus_t hipjpegEncodeFromCoefficientsHost(int32_t width, int
 /* The GPU entropy coder's progressive algorithm (csrc/progressive_encode_core.h: block summaries, EOB-run resolution, lengths, bit
  * emission) executed on the host, block by block, with the very code the kernels run: lets the algorithm be verified without a GPU.
  * Same signature and output as hipjpegEncodeFromCoefficientsHost; HIPJPEG_STATUS_UNSUPPORTED for what the GPU coder's progressive path
- * does not take (baseline output, restart intervals). */
+ * does not take without HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART (baseline output, restart intervals). */
 HIPJPEG_API hipjpegStatus_t hipjpegEncodeFromCoefficientsGpuAlgorithmHost(int32_t width, int32_t height, const hipjpegEncodeParams_t* params,
                                                                           const int16_t* const coef[3], uint8_t* out, size_t capacity,
                                                                           size_t* length);
+/* The same with any restart_interval (0..65535, 0 = none: the bytes of the function above): what the GPU coder's progressive path does
+ * under HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART -- the interval-end flush of the EOB run, the segmented scan of the bit offsets, padding,
+ * restart-marker placement, byte stuffing that spares the markers -- executed on the host with the very code the kernels run.
+ * HIPJPEG_STATUS_UNSUPPORTED for baseline output. */
+HIPJPEG_API hipjpegStatus_t hipjpegEncodeProgressiveGpuAlgorithmHost(int32_t width, int32_t height, const hipjpegEncodeParams_t* params,
+                                                                     const int16_t* const coef[3], uint8_t* out, size_t capacity,
+                                                                     size_t* length);
 /* The GPU entropy coder's baseline algorithm (csrc/huffman_encode_core.h: per-block coding, the segmented scan of the bit offsets,
  * padding, restart-marker placement, byte stuffing that spares the markers) executed on the host with the very code the kernels run.
  * Any restart_interval (0..65535, 0 = none), Annex-K or optimized tables.  Same signature and output as
@@ -431,7 +446,8 @@ HIPJPEG_API hipjpegStatus_t hipjpegTranscodeBatchSetRegions(hipjpegHandle_t hand
  * the image's status for an image without a file.  `params`: one per image (turned images, and images cropped at an origin other than (0, 0), go
  * through coef_transform_kernel of the same file, the others through coef_relayout_kernel: one launch each).  `flags`: HIPJPEG_FLAG_GPU_HUFFMAN puts both entropy stages
  * on the device for every image each of them takes (the decode side honours hipjpegSetHybridHuffmanThreshold; progressive output with a
- * restart interval goes to the host coder), HIPJPEG_FLAG_GPU_RESTART_INTERVALS as in hipjpegEncodeBatchEntropy; 0 = both stages on the
+ * restart interval goes to the host coder unless HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART is set), HIPJPEG_FLAG_GPU_RESTART_INTERVALS and
+ * HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART as in hipjpegEncodeBatchEntropy; 0 = both stages on the
  * host pool.  The bytes do not depend on the flags.  A failing image leaves the rest of the batch alone.  The call occupies a decode page
  * and the encode batch of the handle: it must not overlap a hipjpegDecodeBatchSubmit / hipjpegEncodeBatchSubmit still in flight on the
  * same handle (HIPJPEG_STATUS_INVALID_ARGUMENT). */

@@ -14,6 +14,7 @@ OUTPUT_RGBI, OUTPUT_BGRI, OUTPUT_RGB_PLANAR, OUTPUT_BGR_PLANAR, OUTPUT_Y, OUTPUT
 FLAG_FANCY_UPSAMPLING = 1
 FLAG_GPU_HUFFMAN = 2
 FLAG_GPU_RESTART_INTERVALS = 8
+FLAG_GPU_PROGRESSIVE_RESTART = 32
 FLAG_GPU_PROGRESSIVE_INTERVALS = 16
 TRANSCODE_ORIENTATION_FROM_EXIF = 0x10000  # or-ed into TranscodeParams.orientation
 TRANSCODE_TRIM = 0x20000
@@ -163,6 +164,7 @@ def load():
     L.hipjpegEncodeFromCoefficientsHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
     L.hipjpegEncodeFromCoefficientsGpuAlgorithmHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
     L.hipjpegEncodeBaselineGpuAlgorithmHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
+    L.hipjpegEncodeProgressiveGpuAlgorithmHost.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), vp, vp, sz, ctypes.POINTER(sz)]
     L.hipjpegTranscodeHost.argtypes = [vp, sz, ctypes.POINTER(TranscodeParams), vp, sz, ctypes.POINTER(sz)]
     L.hipjpegTranscodeHostRegion.argtypes = [vp, sz, ctypes.POINTER(TranscodeParams), ctypes.POINTER(TranscodeRegion), vp, sz, ctypes.POINTER(sz)]
     L.hipjpegTranscodeBatchSetRegions.argtypes = [vp, vp, i32]

@@ -431,11 +431,11 @@ hipjpegStatus_t EncodeBatch::fetch_coefficients()
 }
 
 // ---------------------------------------------------------------- entropy coding
-hipjpegStatus_t EncodeBatch::route_entropy(bool gpu_huffman, bool gpu_restart)
+hipjpegStatus_t EncodeBatch::route_entropy(bool gpu_huffman, bool gpu_restart, bool gpu_progressive_restart)
 {
     for (size_t i = 0; i < images_.size(); i++) host_coder_[i] = images_[i].status == HIPJPEG_STATUS_SUCCESS;
     hipjpegStatus_t st;
-    if (gpu_huffman && (st = gpu_entropy_stage(gpu_restart)) != HIPJPEG_STATUS_SUCCESS) return st;
+    if (gpu_huffman && (st = gpu_entropy_stage(gpu_restart, gpu_progressive_restart)) != HIPJPEG_STATUS_SUCCESS) return st;
     host_images_ = (int)std::count(host_coder_.begin(), host_coder_.end(), 1);
     // the host coder needs the coefficients on its side of PCIe
     return host_images_ ? fetch_coefficients() : HIPJPEG_STATUS_SUCCESS;
@@ -517,18 +517,19 @@ struct EncodeBatch::PencPlan : SegmentPlan {
     std::vector<PencScan> scans;     // every scan of the images taken, one per segment (device pointers inside)
     std::vector<HencUnit> units;     // length / write units (256 blocks of one scan, image = scan)
     std::vector<uint32_t> ac_scans;  // scans with end-of-band runs
+    bool restart = false;            // an image has restart intervals: every launch takes the kernels' flavour that carries them
     size_t total_blocks = 0;
     PencLayout1 d1{};
 };
 
-hipjpegStatus_t EncodeBatch::gpu_entropy_stage(bool gpu_restart)
+hipjpegStatus_t EncodeBatch::gpu_entropy_stage(bool gpu_restart, bool gpu_progressive_restart)
 {
     gpu_entropy_images_ = 0;
     if (!launched_) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (hipSetDevice(device_id_) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
     HencPlan p;
     PencPlan q;
-    henc_choose(p, q, gpu_restart);
+    henc_choose(p, q, gpu_restart, gpu_progressive_restart);
     hipjpegStatus_t st;
     if (!p.idx.empty()) {
         const HencLayout1& d1 = p.d1;
@@ -552,27 +553,28 @@ hipjpegStatus_t EncodeBatch::gpu_entropy_stage(bool gpu_restart)
             const PencBlockArrays a{at<const uint8_t>(dev, d1.sum),    at<const uint32_t>(dev, d1.pre),     at<const uint32_t>(dev, d1.post),
                                     at<const uint32_t>(dev, d1.piece), at<const uint32_t>(dev, d1.flusher), at<const uint16_t>(dev, d1.rel),
                                     at<const uint16_t>(dev, d1.own),   at<const uint16_t>(dev, d1.bits),    at<const uint32_t>(dev, d1.off)};
-            return launch_penc_write(at<const PencScan>(dev, d1.scans), dsegs, at<const HencUnit>(dev, d1.units), (int)q.units.size(), a, stream_);
+            return launch_penc_write(at<const PencScan>(dev, d1.scans), dsegs, at<const HencUnit>(dev, d1.units), (int)q.units.size(), a, stream_, q.restart);
         };
         bool direct = false;
         penc_describe(q);
         if ((st = penc_statistics(q)) != HIPJPEG_STATUS_SUCCESS || (st = penc_lengths(q)) != HIPJPEG_STATUS_SUCCESS) return st;
         henc_chunks(q, penc_);
-        if ((st = henc_assemble(q, penc_, write, &direct)) != HIPJPEG_STATUS_SUCCESS || (st = henc_collect(q, penc_, direct)) != HIPJPEG_STATUS_SUCCESS) return st;
+        if ((st = henc_assemble(q, penc_, write, &direct, q.restart)) != HIPJPEG_STATUS_SUCCESS || (st = henc_collect(q, penc_, direct)) != HIPJPEG_STATUS_SUCCESS) return st;
     }
     return HIPJPEG_STATUS_SUCCESS;
 }
 
 // Every image the host coder would code and the GPU coder takes: baseline ones into p, progressive ones into q.  Restart intervals:
-// baseline images when the caller asked for them (HIPJPEG_FLAG_GPU_RESTART_INTERVALS), progressive ones never (jcphuff.c emit_restart
-// flushes the EOB run, which the run walk of progressive_encode.hip does not do).
-void EncodeBatch::henc_choose(HencPlan& p, PencPlan& q, bool gpu_restart)
+// baseline images when the caller asked for them (HIPJPEG_FLAG_GPU_RESTART_INTERVALS), progressive ones when the caller asked for those
+// (HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART: jcphuff.c emit_restart also flushes the EOB run, progressive_encode_core.h); the two switches
+// are independent.
+void EncodeBatch::henc_choose(HencPlan& p, PencPlan& q, bool gpu_restart, bool gpu_progressive_restart)
 {
     for (int i = 0; i < (int)images_.size(); i++) {
         PlannedEncode& im = images_[i];
         im.gpu_bitstream = nullptr;
         im.gpu_bitstream_len = 0;
-        if (!host_coder_[i] || (im.params.restart_interval != 0 && (!gpu_restart || im.params.progressive))) continue;
+        if (!host_coder_[i] || (im.params.restart_interval != 0 && !(im.params.progressive ? gpu_progressive_restart : gpu_restart))) continue;
         host_coder_[i] = 0;
         (im.params.progressive ? q.idx : p.idx).push_back(i);
     }
@@ -703,7 +705,8 @@ void EncodeBatch::penc_describe(PencPlan& q)
         const int16_t* coef[3] = {desc_[q.idx[g]].coef[0], desc_[q.idx[g]].coef[1], desc_[q.idx[g]].coef[2]};
         const size_t s0 = q.scans.size();
         q.first_seg.push_back((int)s0);
-        q.total_blocks += hipjpeg::penc_describe(im.geom, coef, q.total_blocks, &q.scans);
+        q.total_blocks += hipjpeg::penc_describe(im.geom, coef, q.total_blocks, &q.scans, im.params.restart_interval);
+        if (im.params.restart_interval) q.restart = true;
         for (size_t k = s0; k < q.scans.size(); k++) {
             const PencScan& sc = q.scans[k];
             for (uint32_t b = 0; b < sc.nblocks; b += 256) q.units.push_back(HencUnit{(uint32_t)k, b});
@@ -712,6 +715,9 @@ void EncodeBatch::penc_describe(PencPlan& q)
             memset(&h, 0, sizeof h);
             h.total_blocks = sc.nblocks;  // what henc_scan reads
             h.first_block = sc.first_block;
+            // what henc_scan, henc_chunks (the marker bitmap behind the bit buffer) and count / expand read: a segment that writes
+            // markers without it would write past its buffer
+            h.rst_blocks = sc.rst_blocks;
             h.nseg = k == s0 ? (uint32_t)(q.scans.size() - s0) : 0u;
             h.last_seg = k + 1 == q.scans.size() ? 1u : 0u;
             q.segs.push_back(h);
@@ -765,18 +771,19 @@ hipjpegStatus_t EncodeBatch::penc_statistics(PencPlan& q)
     if (hipMemcpyAsync(dev, penc_.pinned.data(), d1.codes, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemsetAsync(dev + d1.hist, 0, 1024 * ns, s) != hipSuccess || hipMemsetAsync(dev + d1.pre, 0, 4 * nb, s) != hipSuccess ||
         hipMemsetAsync(dev + d1.post, 0, 4 * nb, s) != hipSuccess ||
-        launch_penc_summary(dscans, at<const HencUnit>(penc_.dev, d1.units), (int)q.units.size(), dev + d1.sum, stream_) != 0 ||
+        launch_penc_summary(dscans, at<const HencUnit>(penc_.dev, d1.units), (int)q.units.size(), dev + d1.sum, stream_, q.restart) != 0 ||
         launch_penc_runs(dscans, at<const uint32_t>(penc_.dev, d1.ac), (int)q.ac_scans.size(), dev + d1.sum, at<uint32_t>(penc_.dev, d1.pre),
                          at<uint32_t>(penc_.dev, d1.post), at<uint32_t>(penc_.dev, d1.piece), at<uint32_t>(penc_.dev, d1.flusher),
-                         at<uint16_t>(penc_.dev, d1.rel), stream_) != 0 ||
+                         at<uint16_t>(penc_.dev, d1.rel), stream_, q.restart) != 0 ||
         hipMemcpyAsync(penc_.pinned.data() + q.pin.hist, dev + d1.hist, 1024 * ns, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;
     for (size_t g = 0; g + 1 < q.first_seg.size(); g++) {
         const std::vector<ScanSpec> script = simple_progression(images_[q.idx[g]].geom.ncomp);
-        for (int k = q.first_seg[g]; k < q.first_seg[g + 1]; k++)
+        for (int k = q.first_seg[g]; k < q.first_seg[g + 1]; k++)  // DRI once, in the first scan's header
             progressive_scan_header(script[k - q.first_seg[g]], at<const uint32_t>(penc_.pinned, q.pin.hist + 1024 * (size_t)k),
-                                    at<uint32_t>(penc_.pinned, d1.codes + 1024 * (size_t)k), &q.headers[k]);
+                                    at<uint32_t>(penc_.pinned, d1.codes + 1024 * (size_t)k), &q.headers[k],
+                                    k == q.first_seg[g] ? images_[q.idx[g]].params.restart_interval : 0);
     }
     return HIPJPEG_STATUS_SUCCESS;
 }
@@ -790,9 +797,9 @@ hipjpegStatus_t EncodeBatch::penc_lengths(PencPlan& q)
     if (hipMemcpyAsync(penc_.dev.data() + d1.codes, penc_.pinned.data() + d1.codes, d1.hist - d1.codes, hipMemcpyHostToDevice, s) != hipSuccess ||
         launch_penc_length(at<const PencScan>(penc_.dev, d1.scans), at<const HencUnit>(penc_.dev, d1.units), (int)q.units.size(),
                            at<const uint32_t>(penc_.dev, d1.pre), at<const uint32_t>(penc_.dev, d1.post), at<uint16_t>(penc_.dev, d1.own),
-                           at<uint16_t>(penc_.dev, d1.bits), stream_) != 0 ||
+                           at<uint16_t>(penc_.dev, d1.bits), stream_, q.restart) != 0 ||
         launch_henc_scan(at<const HencImage>(penc_.dev, d1.segs), ns, at<const uint16_t>(penc_.dev, d1.bits), at<uint32_t>(penc_.dev, d1.off),
-                         at<uint32_t>(penc_.dev, d1.totals), stream_) != 0 ||
+                         at<uint32_t>(penc_.dev, d1.totals), stream_, q.restart) != 0 ||
         hipMemcpyAsync(penc_.pinned.data() + q.pin.totals, penc_.dev.data() + d1.totals, (size_t)ns * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         return HIPJPEG_STATUS_HIP_ERROR;

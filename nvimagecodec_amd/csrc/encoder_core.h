@@ -77,9 +77,9 @@ public:
     // Coefficients D2H (on the stream used by device_stage), wait.
     hipjpegStatus_t fetch_coefficients();
     // Decides who entropy-codes each planned image: with gpu_huffman the GPU coder (blocking) takes every image it can -- Annex-K
-    // or optimized tables or progressive output, no restart markers -- and the rest is flagged for the host coder (every planned
-    // image without gpu_huffman).  Fetches the coefficients when the host coder has anything to do.
-    hipjpegStatus_t route_entropy(bool gpu_huffman, bool gpu_restart = false);
+    // or optimized tables or progressive output; with a restart interval baseline images under gpu_restart and progressive ones under
+    // gpu_progressive_restart -- and the rest is flagged for the host coder (every planned image without gpu_huffman).  Fetches the coefficients when the host coder has anything to do.
+    hipjpegStatus_t route_entropy(bool gpu_huffman, bool gpu_restart = false, bool gpu_progressive_restart = false);
     // Host coder: Huffman + markers for image i when route_entropy() left it to the host; otherwise nothing.  Thread-safe for distinct i.
     void entropy_stage(int i);
     int host_images() const { return host_images_; }  // images route_entropy() left to the host coder
@@ -147,8 +147,8 @@ private:
             : dev(Buffer::kDevice, hooks), dev2(Buffer::kDevice, hooks), pinned(Buffer::kPinned, hooks), out(Buffer::kPinned, hooks) {}
         Buffer dev, dev2, pinned, out;
     };
-    hipjpegStatus_t gpu_entropy_stage(bool gpu_restart);
-    void henc_choose(HencPlan& p, PencPlan& q, bool gpu_restart);
+    hipjpegStatus_t gpu_entropy_stage(bool gpu_restart, bool gpu_progressive_restart);
+    void henc_choose(HencPlan& p, PencPlan& q, bool gpu_restart, bool gpu_progressive_restart);
     // baseline output, Annex-K or optimized tables: one host round trip more when any image wants tables of its own
     void henc_describe(HencPlan& p);
     hipjpegStatus_t henc_stage_phase1(HencPlan& p);

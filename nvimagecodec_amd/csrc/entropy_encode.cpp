@@ -741,7 +741,7 @@ void write_progressive_frame_header(const EncodeGeometry& g, const uint16_t qlum
     write_frame_header(g, qlum, qchr, 0xFFC2, out, markers);
 }
 
-void progressive_scan_header(const ScanSpec& sc, const uint32_t counts[256], uint32_t codes[256], std::vector<uint8_t>* out)
+void progressive_scan_header(const ScanSpec& sc, const uint32_t counts[256], uint32_t codes[256], std::vector<uint8_t>* out, int restart_interval)
 {
     if (sc.ss != 0 || sc.ah == 0) {
         const bool dc_scan = sc.ss == 0;
@@ -758,6 +758,11 @@ void progressive_scan_header(const ScanSpec& sc, const uint32_t counts[256], uin
                 const int k = dc_scan ? t * 16 + s : s;
                 if (dc_scan || t == (sc.comp[0] == 0 ? 0 : 1)) codes[k] = tables[t].code[s] | ((uint32_t)tables[t].size[s] << 16);
             }
+    }
+    if (restart_interval) {  // as encode_progressive: once, in front of the first SOS
+        put16(out, 0xFFDD);
+        put16(out, 4);
+        put16(out, restart_interval);
     }
     write_sos(sc, out);
 }

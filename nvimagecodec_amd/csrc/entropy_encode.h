@@ -72,9 +72,11 @@ std::vector<ScanSpec> simple_progression(int ncomp);
 // SOI, APP0, DQT.., SOF2 -- what precedes the first scan's tables.
 void write_progressive_frame_header(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_t qchr[64], std::vector<uint8_t>* out,
                                     const std::vector<uint8_t>* markers = nullptr);
-// One scan's optimal table(s) from its symbol counts, and its DHT segments and SOS as the host coder writes them (no DRI).  Layout of
+// One scan's optimal table(s) from its symbol counts, and its DHT segments and SOS as the host coder writes them; restart_interval != 0
+// (the file's first scan only): with the DRI segment where jcmarker.c write_scan_header puts it, between DHT and SOS.  Layout of
 // `counts` and `codes` (code | length << 16): DC first scans [t * 16 + category] (t = 0 luma, 1 chroma); AC scans [run/size symbol].
 // DC refinement scans use no table: counts are ignored and `codes` is left alone.
-void progressive_scan_header(const ScanSpec& sc, const uint32_t counts[256], uint32_t codes[256], std::vector<uint8_t>* out);
+void progressive_scan_header(const ScanSpec& sc, const uint32_t counts[256], uint32_t codes[256], std::vector<uint8_t>* out,
+                             int restart_interval = 0);
 
 }  // namespace hipjpeg

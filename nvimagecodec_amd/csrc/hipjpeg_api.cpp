@@ -622,7 +622,8 @@ hipjpegStatus_t hipjpegEncodeBatchEntropy(hipjpegHandle_t handle, unsigned flags
     return guarded([&]() -> hipjpegStatus_t {
     if (!handle) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     EncodeBatch& b = *handle->encode;
-    const hipjpegStatus_t st = b.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0, (flags & HIPJPEG_FLAG_GPU_RESTART_INTERVALS) != 0);
+    const hipjpegStatus_t st = b.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0, (flags & HIPJPEG_FLAG_GPU_RESTART_INTERVALS) != 0,
+                                  (flags & HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART) != 0);
     if (st != HIPJPEG_STATUS_SUCCESS) return st;
     if (b.host_images()) handle->pool->parallel_for(b.size(), [&](int i, int) { b.entropy_stage(i); });
     if (statuses)
@@ -669,7 +670,8 @@ hipjpegStatus_t hipjpegEncodeBatchSubmit(hipjpegHandle_t handle, const hipjpegEn
         EncodeBatch& b = *page->batch;
         hipjpegStatus_t st = b.device_stage(page->inputs.data(), page->params.data(), (int)page->inputs.size(), nullptr, page->stream);
         if (st != HIPJPEG_STATUS_SUCCESS) return st;
-        if ((st = b.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0, (flags & HIPJPEG_FLAG_GPU_RESTART_INTERVALS) != 0)) != HIPJPEG_STATUS_SUCCESS) return st;
+        if ((st = b.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0, (flags & HIPJPEG_FLAG_GPU_RESTART_INTERVALS) != 0,
+                                  (flags & HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART) != 0)) != HIPJPEG_STATUS_SUCCESS) return st;
         for (int i = 0; i < b.size(); i++) b.entropy_stage(i);
         return HIPJPEG_STATUS_SUCCESS;
     });
@@ -775,7 +777,29 @@ hipjpegStatus_t hipjpegEncodeFromCoefficientsGpuAlgorithmHost(int32_t width, int
         if (!coef[c]) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (!params->progressive || params->restart_interval != 0) return HIPJPEG_STATUS_UNSUPPORTED;  // what the GPU coder's progressive path takes
     std::vector<uint8_t> bytes;
-    encode_progressive_gpu_algorithm(g, ql, qc, coef, &bytes);
+    encode_progressive_gpu_algorithm(g, ql, qc, coef, 0, &bytes);
+    *length = bytes.size();
+    if (!out || capacity < bytes.size()) return HIPJPEG_STATUS_BUFFER_TOO_SMALL;
+    memcpy(out, bytes.data(), bytes.size());
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+hipjpegStatus_t hipjpegEncodeProgressiveGpuAlgorithmHost(int32_t width, int32_t height, const hipjpegEncodeParams_t* params,
+                                                         const int16_t* const coef[3], uint8_t* out, size_t capacity, size_t* length)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!params || !coef || !length || width < 1 || height < 1 || width > 65535 || height > 65535) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    EncodeGeometry g;
+    uint16_t ql[64], qc[64];
+    hipjpegStatus_t st = picture_setup(*params, width, height, &g, ql, qc);
+    if (st != HIPJPEG_STATUS_SUCCESS) return st;
+    for (int c = 0; c < g.ncomp; c++)
+        if (!coef[c]) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (params->restart_interval < 0 || params->restart_interval > 65535) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (!params->progressive) return HIPJPEG_STATUS_UNSUPPORTED;  // the progressive plan of the GPU coder
+    std::vector<uint8_t> bytes;
+    encode_progressive_gpu_algorithm(g, ql, qc, coef, params->restart_interval, &bytes);
     *length = bytes.size();
     if (!out || capacity < bytes.size()) return HIPJPEG_STATUS_BUFFER_TOO_SMALL;
     memcpy(out, bytes.data(), bytes.size());
@@ -880,7 +904,8 @@ hipjpegStatus_t hipjpegTranscodeBatch(hipjpegHandle_t handle, const uint8_t* con
         (void)hipStreamSynchronize((hipStream_t)stream);
         return st;
     }
-    if ((st = e.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0, (flags & HIPJPEG_FLAG_GPU_RESTART_INTERVALS) != 0)) != HIPJPEG_STATUS_SUCCESS) return st;
+    if ((st = e.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0, (flags & HIPJPEG_FLAG_GPU_RESTART_INTERVALS) != 0,
+                                  (flags & HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART) != 0)) != HIPJPEG_STATUS_SUCCESS) return st;
     if (e.host_images()) handle->pool->parallel_for(e.size(), [&](int i, int) { e.entropy_stage(i); });
     if (statuses)
         for (int i = 0; i < batch_size; i++) statuses[i] = e.image(i).status;
@@ -967,7 +992,8 @@ hipjpegStatus_t hipjpegEncodeCoefficientsBatch(hipjpegHandle_t handle, const hip
         (void)hipStreamSynchronize((hipStream_t)stream);
         return st;
     }
-    if ((st = e.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0, (flags & HIPJPEG_FLAG_GPU_RESTART_INTERVALS) != 0)) != HIPJPEG_STATUS_SUCCESS) return st;
+    if ((st = e.route_entropy((flags & HIPJPEG_FLAG_GPU_HUFFMAN) != 0, (flags & HIPJPEG_FLAG_GPU_RESTART_INTERVALS) != 0,
+                                  (flags & HIPJPEG_FLAG_GPU_PROGRESSIVE_RESTART) != 0)) != HIPJPEG_STATUS_SUCCESS) return st;
     if (e.host_images()) handle->pool->parallel_for(e.size(), [&](int i, int) { e.entropy_stage(i); });
     if (statuses)
         for (int i = 0; i < batch_size; i++) statuses[i] = e.image(i).status;

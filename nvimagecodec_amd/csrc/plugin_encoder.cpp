@@ -76,11 +76,14 @@ public:
         // "hipjpeg_encoder:gpu_huffman=0" keeps the entropy coder on the executor threads (default: on the GPU);
         // "hipjpeg_encoder:restart_interval=N" asks for a restart marker every N MCUs (0..65535, 0: none), "hipjpeg_encoder:restart_rows=R"
         // for one every R MCU rows (libjpeg's restart_in_rows; it wins over restart_interval).  A value that does not parse or is out
-        // of range is logged and ignored.
+        // of range is logged and ignored.  "hipjpeg_encoder:gpu_progressive_restart=1" lets the GPU coder take progressive output with a
+        // restart interval too (default: the host coder codes it).
         for_each_option(options, kEncoderId, [&](const std::string& key, const std::string& value) {
             std::istringstream v(value);
             if (key == "gpu_huffman") {
                 v >> gpu_huffman_;
+            } else if (key == "gpu_progressive_restart") {
+                v >> gpu_progressive_restart_;
             } else if (key == "restart_interval" || key == "restart_rows") {
                 long long x = -1;
                 char rest;
@@ -142,6 +145,7 @@ private:
     bool ok_ = false;
     bool gpu_huffman_ = true;       // entropy-code on the GPU what it can take (Annex-K or optimized tables, with or without restart intervals, or
                                     // progressive output without them)
+    bool gpu_progressive_restart_ = false;  // with gpu_huffman_: progressive output with a restart interval on the GPU coder too
     int restart_interval_ = 0;      // in MCUs
     int restart_rows_ = 0;          // in MCU rows: per image min(rows x MCUs per row, 65535); 0: restart_interval_ holds
     hipStream_t stream_ = nullptr;
@@ -341,7 +345,7 @@ nvimgcodecStatus_t HipJpegEncoder::encode(nvimgcodecImageDesc_t** images, nvimgc
     std::vector<hipjpegStatus_t> statuses(n, HIPJPEG_STATUS_SUCCESS);
     if (gpu_ok) gpu_ok = batch_->device_stage(inputs.data(), eparams.data(), n, statuses.data(), stream_) == HIPJPEG_STATUS_SUCCESS;
     // blocks: the GPU coder, or the coefficients' way down for the host coder (like cudaEventSynchronize in cuda_encoder.cpp:374-375)
-    if (gpu_ok) gpu_ok = batch_->route_entropy(gpu_huffman_, gpu_huffman_) == HIPJPEG_STATUS_SUCCESS;  // the GPU coder takes restart intervals too
+    if (gpu_ok) gpu_ok = batch_->route_entropy(gpu_huffman_, gpu_huffman_, gpu_progressive_restart_) == HIPJPEG_STATUS_SUCCESS;  // the GPU coder takes restart intervals too
     } catch (...) {
         gpu_ok = false;  // an exception while marshalling or in the device stage: the whole batch is reported failed below
     }

@@ -14,6 +14,14 @@
 // then has a position that one lane per block can compute, and the block's lane writes what it owns:
 //   [pre: EOBn code, n bits, the piece's buffered bits] own symbols [post: EOBn code, n bits, the piece's buffered bits]
 // A flush's buffered bits are written by the blocks that buffered them, each at flush position + EOBn length + rel.
+//
+// Restart intervals (jcphuff.c emit_restart; PencScan::rst_blocks, template <bool RST>) add three things and keep that shape:
+//   predictor  DC first scans: the first block of each component in the MCU that opens an interval has no previous block
+//   run        the last block of an interval that another one follows flushes what is pending behind its own tail step: a post
+//              flush like a cut's, so that a run piece never spans an interval
+//   marker     that block's lane also pads the byte behind everything it lays down and writes FF Dn there (huffman_encode_core.h has
+//              the segmented offsets, the marker bitmap and the stuffing that spares the markers; they work per segment and are shared)
+// RST = false compiles all of it away: scans without an interval run the code they always ran.
 #pragma once
 #include <cstdint>
 
@@ -40,7 +48,23 @@ struct alignas(16) PencScan {
     uint32_t nblocks;        // blocks in scan order: MCU order with the padding's dummy blocks (DC), real blocks in raster order (AC)
     uint32_t first_block;    // into the batch-wide per-block arrays
     uint32_t vs;
+    uint32_t rst_blocks;     // the restart interval in blocks of this scan: restart_interval * bpm (interleaved DC scans), restart_interval
+                             // (one block per MCU: AC scans, one-component frames); 0: none
 };
+
+// Block i opens an interval (i: the first block of its MCU in DC scans).
+template <bool RST>
+HJ_HD bool penc_starts_interval(const PencScan& sc, uint32_t i)
+{
+    return RST && sc.rst_blocks != 0 && i % sc.rst_blocks == 0;
+}
+
+// Block i is the last of an interval that another one follows (the scan's last block never is).
+template <bool RST>
+HJ_HD bool penc_ends_interval(uint32_t rst_blocks, uint32_t nblocks, uint32_t i)
+{
+    return RST && rst_blocks != 0 && i + 1 < nblocks && (i + 1) % rst_blocks == 0;
+}
 
 HJ_HD int penc_bit_length(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
 
@@ -67,6 +91,7 @@ HJ_HD int penc_dc_value(const PencScan& sc, int c, uint32_t bx, uint32_t by)
     return p[((size_t)by * bw + bx) * 64];
 }
 
+template <bool RST>
 HJ_HD PencDcRef penc_dc_locate(const PencScan& sc, uint32_t s)
 {
     PencDcRef r;
@@ -89,7 +114,7 @@ HJ_HD PencDcRef penc_dc_locate(const PencScan& sc, uint32_t s)
     if (j > 0) {
         const uint32_t pj = j - 1, pdy = pj / mh, pdx = pj - pdy * mh;
         r.prev = penc_dc_value(sc, r.c, mx * mh + pdx, my * mv + pdy);
-    } else if (mcu > 0) {
+    } else if (mcu > 0 && !penc_starts_interval<RST>(sc, s - k)) {
         const uint32_t pm = mcu - 1, pmy = pm / sc.mcus_x, pmx = pm - pmy * sc.mcus_x;
         r.prev = penc_dc_value(sc, r.c, pmx * mh + (mh - 1), pmy * mv + (mv - 1));
     } else {
@@ -184,7 +209,24 @@ struct PencStep {
     uint32_t rel, ps;        // tail blocks: bits buffered in front of this block's own, and the piece it joins
 };
 
-HJ_HD PencStep penc_run_step(PencRun& r, uint32_t i, uint32_t summary)
+// The interval ends of a scan for a walk in scan order, without a division per block: at(i) for rising i says whether block i ends
+// an interval (penc_ends_interval); blocks may be skipped as long as none in front of the next one asked for ends one (before).
+template <bool RST>
+struct PencIntervalEnds {
+    uint32_t next, rst, n;  // next: the first block not yet passed that is the last of its interval
+    HJ_HD PencIntervalEnds(uint32_t rst_blocks, uint32_t nblocks) : next(RST && rst_blocks ? rst_blocks - 1 : ~0u), rst(rst_blocks), n(nblocks) {}
+    HJ_HD bool before(uint32_t end) const { return RST && next < end && next + 1 < n; }
+    HJ_HD bool at(uint32_t i)
+    {
+        if (!RST || i != next) return false;
+        next += rst;
+        return i + 1 < n;
+    }
+};
+
+// ends: block i ends an interval that another one follows (PencIntervalEnds::at); read with RST only.
+template <bool RST>
+HJ_HD PencStep penc_run_step(PencRun& r, uint32_t i, uint32_t summary, bool ends)
 {
     PencStep o{0, 0, 0, 0, 0, 0};
     if (summary & 1) {
@@ -205,6 +247,12 @@ HJ_HD PencStep penc_run_step(PencRun& r, uint32_t i, uint32_t summary)
             o.post_ps = r.ps;
             r.n = r.be = 0;
         }
+    }
+    // emit_restart flushes the run in front of the next interval's first block; after a cut nothing is pending, so one post at most
+    if (RST && ends && r.n) {
+        o.post = r.n | (r.be << 16);
+        o.post_ps = r.ps;
+        r.n = r.be = 0;
     }
     return o;
 }
@@ -292,21 +340,22 @@ struct PencDcSymbol {
     int sym, nb;
     uint32_t bits;
 };
+template <bool RST>
 HJ_HD PencDcSymbol penc_dc_symbol(const PencScan& sc, uint32_t i)
 {
-    const PencDcRef r = penc_dc_locate(sc, i);
+    const PencDcRef r = penc_dc_locate<RST>(sc, i);
     const int d = (r.dc >> sc.al) - (r.prev >> sc.al);  // arithmetic shifts (IRIGHT_SHIFT)
     const int nb = penc_bit_length((uint32_t)(d < 0 ? -d : d));
     return PencDcSymbol{(r.c ? 16 : 0) + nb, nb, (uint32_t)(d < 0 ? d - 1 : d)};
 }
 
 // Symbol statistics of block i (Count: sym(symbol), bits() ignored); returns the summary of an AC-scan block (0 for DC scans).
-template <class Count>
+template <bool RST, class Count>
 HJ_HD uint32_t penc_block_summary(const PencScan& sc, uint32_t i, Count& cnt)
 {
     if (sc.kind == kPencDcRefine) return 0;
     if (sc.kind == kPencDcFirst) {
-        cnt.sym(penc_dc_symbol(sc, i).sym);
+        cnt.sym(penc_dc_symbol<RST>(sc, i).sym);
         return 0;
     }
     uint32_t w[32];
@@ -330,6 +379,7 @@ struct PencBlockArrays {
 };
 
 // Bits of block i: own symbols (*own) plus the flushes in front of and behind them.
+template <bool RST>
 HJ_HD uint32_t penc_block_length(const PencScan& sc, uint32_t i, const uint32_t* codes, uint32_t pre, uint32_t post, uint32_t* own)
 {
     if (sc.kind == kPencDcRefine) {
@@ -337,7 +387,7 @@ HJ_HD uint32_t penc_block_length(const PencScan& sc, uint32_t i, const uint32_t*
         return 1;
     }
     if (sc.kind == kPencDcFirst) {
-        const PencDcSymbol d = penc_dc_symbol(sc, i);
+        const PencDcSymbol d = penc_dc_symbol<RST>(sc, i);
         *own = (codes[d.sym] >> 16) + d.nb;
         return *own;
     }
@@ -353,18 +403,21 @@ HJ_HD uint32_t penc_block_length(const PencScan& sc, uint32_t i, const uint32_t*
     return penc_flush_len(codes, pre) + o.len + penc_flush_len(codes, post);
 }
 
-// Writes everything block i owns into the scan's zeroed bit buffer (W: or_word), the final byte's padding included.
-template <class W>
-HJ_HD void penc_block_write(const PencScan& sc, uint32_t i, const uint32_t* codes, const W& words, const PencBlockArrays& a)
+// Writes everything block i owns into the scan's zeroed bit buffer (W: or_word), the final byte's padding included.  RST: the last
+// block of an interval pads behind all it lays down (its flushes and the buffered bits other lanes OR into them lie in front of
+// off + bits[i]) and writes RSTn at the byte boundary (jcphuff.c emit_restart).  Returns the byte of the bit buffer that holds the
+// marker's FF, or ~0u when there is none.
+template <bool RST, class W>
+HJ_HD uint32_t penc_block_write(const PencScan& sc, uint32_t i, const uint32_t* codes, const W& words, const PencBlockArrays& a)
 {
     PencBits<W> em{words, codes, 0, 0, 0};
     const uint32_t off = a.off[i];
     if (sc.kind == kPencDcRefine) {
         em.start(off);
-        em.put((uint32_t)(penc_dc_locate(sc, i).dc >> sc.al) & 1u, 1);
+        em.put((uint32_t)(penc_dc_locate<false>(sc, i).dc >> sc.al) & 1u, 1);
         em.finish();
     } else if (sc.kind == kPencDcFirst) {
-        const PencDcSymbol d = penc_dc_symbol(sc, i);
+        const PencDcSymbol d = penc_dc_symbol<RST>(sc, i);
         em.start(off);
         em.sym(d.sym);
         em.put(d.bits, d.nb);
@@ -400,14 +453,17 @@ HJ_HD void penc_block_write(const PencScan& sc, uint32_t i, const uint32_t* code
             em.finish();
         }
     }
-    if (i == sc.nblocks - 1) {  // jchuff.c flush_bits: the scan's last byte is filled up with one-bits
-        const uint32_t end = off + a.bits[i], padn = (8 - (end & 7)) & 7;
-        if (padn) {
-            em.start(end);
-            em.put((1u << padn) - 1, (int)padn);
-            em.finish();
-        }
+    const bool ends = penc_ends_interval<RST>(sc.rst_blocks, sc.nblocks, i);
+    if (!ends && i != sc.nblocks - 1) return ~0u;
+    // jchuff.c flush_bits: the last byte of the scan -- and of every restart interval -- is filled up with one-bits
+    const uint32_t end = off + a.bits[i], padn = (8 - (end & 7)) & 7;
+    if (padn || ends) {
+        em.start(end);
+        if (padn) em.put((1u << padn) - 1, (int)padn);
+        if (ends) em.put(0xFF00u | (0xD0u + ((i / sc.rst_blocks) & 7u)), 16);  // n = interval index mod 8 (henc_marker_number)
+        em.finish();
     }
+    return ends ? (end + padn) >> 3 : ~0u;
 }
 
 }  // namespace hipjpeg

@@ -388,8 +388,18 @@ def encode_from_coefficients_gpu_algorithm_host(width, height, coefs_natural, su
                                                 progressive=True):
     """The GPU entropy coder's progressive algorithm run on the host with the kernels' per-block code (no GPU): the file
     encode_from_coefficients_host(..., progressive=True) writes.  Raises HipJpegError (UNSUPPORTED) for baseline output and restart
-    intervals, which the GPU coder's progressive path does not take."""
+    intervals, which the GPU coder's progressive path does not take without FLAG_GPU_PROGRESSIVE_RESTART."""
     return _encode_coefficients("hipjpegEncodeFromCoefficientsGpuAlgorithmHost", width, height, coefs_natural, subsampling, quality,
+                                restart_interval, False, progressive)
+
+
+def encode_from_coefficients_progressive_gpu_algorithm_host(width, height, coefs_natural, subsampling="420", quality=90, restart_interval=0,
+                                                            progressive=True):
+    """The GPU entropy coder's progressive algorithm with restart intervals (FLAG_GPU_PROGRESSIVE_RESTART) run on the host with the
+    kernels' own code (no GPU): the interval-end flush of the EOB run, the segmented scan of the bit offsets, padding, restart markers
+    and the byte stuffing that spares them.  Any restart_interval: the file encode_from_coefficients_host(..., progressive=True)
+    writes for it.  Raises HipJpegError (UNSUPPORTED) for baseline output."""
+    return _encode_coefficients("hipjpegEncodeProgressiveGpuAlgorithmHost", width, height, coefs_natural, subsampling, quality,
                                 restart_interval, False, progressive)
 
 
@@ -406,14 +416,16 @@ def encode_from_coefficients_baseline_gpu_algorithm_host(width, height, coefs_na
 class BatchEncoder:
     """hipjpegEncodeBatch* on one device; inputs are torch CUDA uint8 tensors ([H, W, 3] interleaved, [3, H, W] planar or [H, W] gray).
     gpu_huffman: the entropy stage's default route; gpu_restart: with gpu_huffman, the GPU coder also takes baseline images with a restart
-    interval (FLAG_GPU_RESTART_INTERVALS)."""
+    interval (FLAG_GPU_RESTART_INTERVALS); gpu_progressive_restart: with gpu_huffman, the GPU coder also takes progressive images with
+    a restart interval (FLAG_GPU_PROGRESSIVE_RESTART)."""
 
-    def __init__(self, device=0, num_threads=0, gpu_huffman=False, gpu_restart=False):
+    def __init__(self, device=0, num_threads=0, gpu_huffman=False, gpu_restart=False, gpu_progressive_restart=False):
         import torch
         self._torch = torch
         self.device = int(device)
         self.gpu_huffman = bool(gpu_huffman)
         self.gpu_restart = bool(gpu_restart)
+        self.gpu_progressive_restart = bool(gpu_progressive_restart)
         self._inflight = []
         self._h = ctypes.c_void_p()
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
@@ -440,7 +452,8 @@ class BatchEncoder:
     def _entropy_flags(self, gpu_huffman):
         if not gpu_huffman:
             return 0
-        return N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0)
+        return (N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0) |
+                (N.FLAG_GPU_PROGRESSIVE_RESTART if self.gpu_progressive_restart else 0))
 
     def _marshal(self, images, subsampling, quality, input_format, restart_interval, optimized_huffman, progressive=False):
         n = len(images)
@@ -513,8 +526,8 @@ class BatchEncoder:
     def host_stage(self, gpu_huffman=None):
         """Entropy stage of the prepared batch.  gpu_huffman (default: the encoder's setting): code on the GPU what it can take --
         baseline output with Annex-K or optimized tables and progressive output, without a restart interval; with the encoder's
-        gpu_restart=True also baseline output with a restart interval -- and the rest (progressive output with a restart interval
-        always), or everything when False, on the host thread pool."""
+        gpu_restart=True also baseline output with a restart interval, with gpu_progressive_restart=True also progressive output
+        with one -- and the rest, or everything when False, on the host thread pool."""
         if gpu_huffman is None:
             gpu_huffman = self.gpu_huffman
         st_arr = (ctypes.c_int * self._n)()
@@ -623,16 +636,19 @@ class BatchTranscoder:
     """hipjpegTranscodeBatch on one device: entropy decode, coefficient relayout kernel and entropy coder in one blocking call.
     gpu_huffman: both entropy stages on the GPU for every image each of them takes; gpu_restart: with gpu_huffman, the GPU coder also
     takes baseline output with a restart interval (FLAG_GPU_RESTART_INTERVALS); gpu_progressive_intervals: with gpu_huffman, the GPU
-    decoder also takes progressive sources whose scans all have restart intervals (FLAG_GPU_PROGRESSIVE_INTERVALS).  The bytes do not
-    depend on any of them."""
+    decoder also takes progressive sources whose scans all have restart intervals (FLAG_GPU_PROGRESSIVE_INTERVALS);
+    gpu_progressive_restart: with gpu_huffman, the GPU coder also takes progressive output with a restart interval
+    (FLAG_GPU_PROGRESSIVE_RESTART).  The bytes do not depend on any of them."""
 
-    def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False, gpu_progressive_intervals=False):
+    def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False, gpu_progressive_intervals=False,
+                 gpu_progressive_restart=False):
         import torch
         self._torch = torch
         self.device = int(device)
         self.gpu_huffman = bool(gpu_huffman)
         self.gpu_restart = bool(gpu_restart)
         self.gpu_progressive_intervals = bool(gpu_progressive_intervals)
+        self.gpu_progressive_restart = bool(gpu_progressive_restart)
         self._h = ctypes.c_void_p()
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
         if st:
@@ -664,7 +680,8 @@ class BatchTranscoder:
         if gpu_huffman is None:
             gpu_huffman = self.gpu_huffman
         flags = (N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0) |
-                 (N.FLAG_GPU_PROGRESSIVE_INTERVALS if self.gpu_progressive_intervals else 0)) if gpu_huffman else 0
+                 (N.FLAG_GPU_PROGRESSIVE_INTERVALS if self.gpu_progressive_intervals else 0) |
+                 (N.FLAG_GPU_PROGRESSIVE_RESTART if self.gpu_progressive_restart else 0)) if gpu_huffman else 0
         per = [v if isinstance(v, (list, tuple)) else [v] * n for v in (optimized_huffman, progressive, restart_interval, orientation, grayscale,
                                                                          copy_markers)]
         P = (N.TranscodeParams * n)()
@@ -826,15 +843,18 @@ class BatchCoefficients:
     """hipjpegDecodeCoefficientsBatch / hipjpegEncodeCoefficientsBatch on one device: JPEG files to coefficient tensors and back, the
     tensors never leaving the device.  gpu_huffman: the entropy stage on the GPU for every image it takes; gpu_restart: with gpu_huffman,
     the GPU coder also takes baseline output with a restart interval; gpu_progressive_intervals: with gpu_huffman, the GPU decoder also
-    takes progressive files whose scans all have restart intervals.  Neither the tensors nor the bytes depend on any of them."""
+    takes progressive files whose scans all have restart intervals; gpu_progressive_restart: with gpu_huffman, the GPU coder also takes
+    progressive output with a restart interval.  Neither the tensors nor the bytes depend on any of them."""
 
-    def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False, gpu_progressive_intervals=False):
+    def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False, gpu_progressive_intervals=False,
+                 gpu_progressive_restart=False):
         import torch
         self._torch = torch
         self.device = int(device)
         self.gpu_huffman = bool(gpu_huffman)
         self.gpu_restart = bool(gpu_restart)
         self.gpu_progressive_intervals = bool(gpu_progressive_intervals)
+        self.gpu_progressive_restart = bool(gpu_progressive_restart)
         self._h = ctypes.c_void_p()
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
         if st:
@@ -858,7 +878,8 @@ class BatchCoefficients:
 
     def _flags(self):
         return (N.FLAG_GPU_HUFFMAN | (N.FLAG_GPU_RESTART_INTERVALS if self.gpu_restart else 0) |
-                (N.FLAG_GPU_PROGRESSIVE_INTERVALS if self.gpu_progressive_intervals else 0)) if self.gpu_huffman else 0
+                (N.FLAG_GPU_PROGRESSIVE_INTERVALS if self.gpu_progressive_intervals else 0) |
+                (N.FLAG_GPU_PROGRESSIVE_RESTART if self.gpu_progressive_restart else 0)) if self.gpu_huffman else 0
 
     def _stream_ptr(self, stream):
         s = stream if stream is not None else self._torch.cuda.current_stream(self.device)
