@@ -46,6 +46,7 @@ def test_every_progressive_golden_in_one_batch_with_baseline_neighbours(dec):
     assert all(s == 0 for s in st)
     n_gpu_prog = sum(1 for e in _PROG if "_rst" not in e["name"])
     assert dec.stats()["gpu_entropy_images"] >= n_gpu_prog
+    assert dec.host_fallbacks() == 0
     for e, (jpeg, rgb), o in zip(entries, cases, outs):
         ref = rgb if rgb is not None else oracle.decode(jpeg)
         assert np.array_equal(o.cpu().numpy(), ref), e["name"]
@@ -58,6 +59,7 @@ def test_progressive_output_formats(dec, fmt):
     outs, _ = dec.decode(jpegs, fmt=fmt, gpu_huffman=True)
     _sync()
     assert dec.stats()["gpu_entropy_images"] == len(jpegs)
+    assert dec.host_fallbacks() == 0
     for n, j, o in zip(names, jpegs, outs):
         if fmt == "yuv_planar":
             for a, b in zip(o, oracle.decode_planes(j)):
@@ -97,6 +99,7 @@ def test_progressive_shapes_qualities_and_long_end_of_band_runs(dec):
     outs, st = dec.decode(jpegs, fmt="rgb", gpu_huffman=True)
     _sync()
     assert all(s == 0 for s in st) and dec.stats()["gpu_entropy_images"] == len(jpegs)
+    assert dec.host_fallbacks() == 0
     for j, o in zip(jpegs, outs):
         assert np.array_equal(o.cpu().numpy(), oracle.decode(j))
 
@@ -140,8 +143,11 @@ def test_progressive_through_the_pipelined_entry_points(dec):
         dec.submit(jpegs, ring[k % 3], gpu_huffman=True)
         if k >= 2:
             assert all(s == 0 for s in dec.wait())
+            assert dec.host_fallbacks() == 0
     dec.wait()
+    assert dec.host_fallbacks() == 0
     dec.wait()
+    assert dec.host_fallbacks() == 0
     torch.cuda.synchronize()
     for outs in ring:
         for r, o in zip(refs, outs):
@@ -169,6 +175,7 @@ def test_deeper_pipeline_for_progressive_batches(dec):
             dec.submit(batches[0], ring[0], gpu_huffman=True)  # every page is taken
         for k in range(depth):
             assert all(s == 0 for s in dec.wait())
+            assert dec.host_fallbacks() == 0
         torch.cuda.synchronize()
         for rb, outs in zip(refs, ring):
             for r, o in zip(rb, outs):

@@ -81,6 +81,7 @@ def test_gpu_decodes_the_scan_scripts():
         assert all(s == 0 for s in st)
         if gh:
             assert dec.stats()["gpu_entropy_images"] == len(jpegs)
+            assert dec.host_fallbacks() == 0
         for case, j, o in zip(CASES, jpegs, outs):
             assert np.array_equal(o.cpu().numpy(), oracle.decode(j)), (_ids(case), gh)
     dec.close()
