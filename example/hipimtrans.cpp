@@ -7,7 +7,7 @@
 // the API route of DESIGN.md, measured without any Python in the way.
 //
 //   hipimtrans -i <file|dir> [-o <dir>] [-b batch] [-w warmup batches] [-r repeats] [-q quality] [-s 444|422|420|gray]
-//              [-d device] [-t cpu threads] [-p batches in flight (decode only)] [--skip_encode] [--options "<plugin options>"] [-v]
+//              [-d device] [-t cpu threads] [-p batches in flight (decode only)] [--skip_encode] [--options "<plugin options>"] [--scale 1/2|1/4|1/8] [-v]
 //              [--jpeg_encoding baseline_dct|progressive_dct] [--optimized_huffman true|false]
 //              [--devices a,b,...] [--checksums file] [--lossless [--orientation 1..8|exif] [--trim] [--crop WxH+X+Y] [--expand]
 //              [--grayscale] [--copy-markers]]
@@ -82,6 +82,7 @@ struct Params {
     std::string subsampling = "420";
     bool progressive = false, optimized_huffman = false;  // nvimtrans --jpeg_encoding / --optimized_huffman (command_line_params.h:195-207)
     bool skip_encode = false;
+    int scale_denom = 1;  // --scale 1/2 | 1/4 | 1/8 (decode route only); 0 = a value that is none of them
     bool lossless = false, quality_given = false, subsampling_given = false;
     // --lossless only: the files come out brought upright for this EXIF orientation (jpegtran -flip / -transpose / -rotate), "exif" =
     // for each source's own tag; --trim cuts partial iMCUs off the mirrored axes instead of refusing the image (jpegtran -trim)
@@ -91,6 +92,17 @@ struct Params {
     hipjpegTranscodeRegion_t crop{0, 0, 0, 0};
     bool crop_given = false, crop_bad = false, expand = false, grayscale = false, copy_markers = false;
 };
+
+// --scale 1/N: the decoder plugin decodes every image at 1/N (its option scale_denom), so the image it is handed has
+// hipjpegGetScaledImageSize's size, ceil(extent * (8 / N) / 8).  Sets plane 0 of `info` (the code stream's) to it.
+void scale_plane_size(const Params& p, nvimgcodecImageInfo_t& info, uint32_t* w, uint32_t* h)
+{
+    const uint64_t k = (uint64_t)(8 / p.scale_denom);
+    *w = (uint32_t)(((uint64_t)info.plane_info[0].width * k + 7) / 8);
+    *h = (uint32_t)(((uint64_t)info.plane_info[0].height * k + 7) / 8);
+    info.plane_info[0].width = *w;
+    info.plane_info[0].height = *h;
+}
 
 bool is_dir(const std::string& p)
 {
@@ -235,7 +247,8 @@ void run_device_queue(nvimgcodecInstance_t instance, const Params& p, int device
                 info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
                 info.struct_size = sizeof info;
                 if (nvimgcodecCodeStreamGetImageInfo(sl.streams[(size_t)i], &info) != NVIMGCODEC_STATUS_SUCCESS) return fail("nvimgcodecCodeStreamGetImageInfo");
-                const uint32_t w = info.plane_info[0].width, h = info.plane_info[0].height;
+                uint32_t w = 0, h = 0;
+                scale_plane_size(p, info, &w, &h);
                 info.sample_format = NVIMGCODEC_SAMPLEFORMAT_I_RGB;
                 info.color_spec = NVIMGCODEC_COLORSPEC_SRGB;
                 info.chroma_subsampling = NVIMGCODEC_SAMPLING_NONE;
@@ -556,6 +569,10 @@ int main(int argc, char** argv)
         else if (a == "-p") p.in_flight = std::max(1, std::min(6, atoi(next())));
         else if (a == "--options") p.options = next();
         else if (a == "--skip_encode") p.skip_encode = true;
+        else if (a == "--scale") {
+            const std::string v = next();
+            p.scale_denom = v == "1/2" ? 2 : v == "1/4" ? 4 : v == "1/8" ? 8 : v == "1" || v == "1/1" ? 1 : 0;
+        }
         else if (a == "--jpeg_encoding") p.progressive = std::string(next()) == "progressive_dct";
         else if (a == "--optimized_huffman") p.optimized_huffman = std::string(next()) == "true";
         else if (a == "--devices") {
@@ -571,7 +588,7 @@ int main(int argc, char** argv)
         else {
             fprintf(stderr, "usage: %s -i <file|dir> [-o dir] [-b batch] [-w warmup] [-r repeats] [-q quality] [-s 444|422|420|gray] [-d device] "
                             "[-t threads] [-p batches in flight] [--skip_encode] [--jpeg_encoding baseline_dct|progressive_dct] [--optimized_huffman true|false] "
-                            "[--options str] [--devices a,b,...] [--checksums file] [--lossless [--orientation 1..8|exif] [--trim] [--crop WxH+X+Y] [--expand] "
+                            "[--options str] [--scale 1/2|1/4|1/8] [--devices a,b,...] [--checksums file] [--lossless [--orientation 1..8|exif] [--trim] [--crop WxH+X+Y] [--expand] "
                             "[--grayscale] [--copy-markers]] [-v]\n", argv[0]);
             return EXIT_FAILURE;
         }
@@ -584,6 +601,17 @@ int main(int argc, char** argv)
         fprintf(stderr, "--lossless keeps the coefficients and sampling of the sources: it goes with --jpeg_encoding, --optimized_huffman, -b and -p 1 only "
                         "(not with -q, -s, -p > 1, --devices, --skip_encode)\n");
         return EXIT_FAILURE;
+    }
+    if (p.scale_denom == 0) {
+        fprintf(stderr, "--scale takes 1/2, 1/4 or 1/8\n");
+        return EXIT_FAILURE;
+    }
+    if (p.scale_denom != 1 && p.lossless) {
+        fprintf(stderr, "--scale makes smaller pixels, --lossless keeps the coefficients: they do not go together\n");
+        return EXIT_FAILURE;
+    }
+    if (p.scale_denom != 1) {
+        p.options += (p.options.empty() ? "" : " ") + std::string("hipjpeg_decoder:scale_denom=") + std::to_string(p.scale_denom);
     }
     if ((p.orientation_given || p.trim) && !p.lossless) {
         fprintf(stderr, "--orientation and --trim turn the coefficients themselves: they go with --lossless only\n");
@@ -710,7 +738,8 @@ int main(int argc, char** argv)
                 info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
                 info.struct_size = sizeof info;
                 CHECK_API(nvimgcodecCodeStreamGetImageInfo(sl.streams[i], &info));
-                const uint32_t w = info.plane_info[0].width, h = info.plane_info[0].height;
+                uint32_t w = 0, h = 0;
+                scale_plane_size(p, info, &w, &h);
                 info.sample_format = NVIMGCODEC_SAMPLEFORMAT_I_RGB;
                 info.color_spec = NVIMGCODEC_COLORSPEC_SRGB;
                 info.chroma_subsampling = NVIMGCODEC_SAMPLING_NONE;
@@ -782,7 +811,8 @@ int main(int argc, char** argv)
             info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
             info.struct_size = sizeof info;
             CHECK_API(nvimgcodecCodeStreamGetImageInfo(in_streams[i], &info));
-            const uint32_t w = info.plane_info[0].width, h = info.plane_info[0].height;
+            uint32_t w = 0, h = 0;
+            scale_plane_size(p, info, &w, &h);
             info.sample_format = NVIMGCODEC_SAMPLEFORMAT_I_RGB;
             info.color_spec = NVIMGCODEC_COLORSPEC_SRGB;
             info.chroma_subsampling = NVIMGCODEC_SAMPLING_NONE;

@@ -204,6 +204,26 @@ HIPJPEG_API hipjpegStatus_t hipjpegDecodeBatch(hipjpegHandle_t handle, const uin
  * batch_size entries (copied), or NULL to go back to plain decoding.  Consumed by that one batch. */
 HIPJPEG_API hipjpegStatus_t hipjpegDecodeBatchSetTransforms(hipjpegHandle_t handle, const hipjpegTransform_t* transforms, int batch_size);
 
+/* Decoding at 1/2, 1/4 or 1/8 scale: libjpeg's scale_num / scale_denom = 1 / denominator (the reference's UncompressFlags::ratio), a smaller
+ * IDCT per block.  Host only: the size of a width x height picture decoded at 1 / scale_denom -- ceil(extent * (8 / scale_denom) / 8), what
+ * libjpeg-turbo reports as output_width / output_height.  Denominators 1, 2, 4, 8; anything else is HIPJPEG_STATUS_INVALID_ARGUMENT. */
+HIPJPEG_API hipjpegStatus_t hipjpegGetScaledImageSize(int32_t width, int32_t height, int32_t scale_denom, int32_t* scaled_width,
+                                                      int32_t* scaled_height);
+/* Scale denominators for the NEXT batch handed to hipjpegDecodeBatch / Host / Submit: `scale_denoms` = batch_size entries (copied), or NULL
+ * for none.  Consumed by that one batch; a count other than that batch's size makes that call HIPJPEG_STATUS_INVALID_ARGUMENT.  Per image:
+ * 1 = today's path and bytes; 2, 4, 8 = the picture libjpeg-turbo decodes with that scale_denom, bit for bit (tests/golden/
+ * manifest_scaled.json), written by kernels of their own; any other value gives that image HIPJPEG_STATUS_INVALID_ARGUMENT.  Outputs,
+ * pitches and transforms of a scaled image are judged at its scaled size (hipjpegGetScaledImageSize), and the region of a
+ * hipjpegTransform_t is in scaled-picture coordinates.  HIPJPEG_FLAG_FAST_IDCT then reaches only the components libjpeg still gives the
+ * full 8x8 transform (the chroma of a 4:2:0 file at 1/2); the 4x4, 2x2 and 1x1 transforms have one arithmetic.
+ * HIPJPEG_FLAG_FANCY_UPSAMPLING filters what is left to upsample, except at 1/8, where libjpeg replicates.  HIPJPEG_STATUS_UNSUPPORTED for
+ * a scaled image: HIPJPEG_OUTPUT_YUV_PLANAR and four-component frames.  hipjpegCoefficientsToPixelsBatch, hipjpegDecodeCoefficientsBatch
+ * and hipjpegTranscodeBatch take no scales: called with scales pending they return HIPJPEG_STATUS_INVALID_ARGUMENT and drop them.
+ * Scaled images never take the FUSED kernel builds (the HIPJPEG_FUSED_DECODE=1 experiment, off by default), and because those builds are
+ * all or nothing per batch, one scaled image puts the whole batch -- its denominator-1 images too -- on the default route, the block
+ * pass through HBM: the same bytes, the default route's time. */
+HIPJPEG_API hipjpegStatus_t hipjpegDecodeBatchSetScales(hipjpegHandle_t handle, const int32_t* scale_denoms, int batch_size);
+
 /* The three phases separately (what hipjpegDecodeBatch does internally); used by bench.py to time the device
  * stage with the coefficient blocks already resident in HBM. */
 HIPJPEG_API hipjpegStatus_t hipjpegDecodeBatchHost(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,

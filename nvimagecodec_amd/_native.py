@@ -129,6 +129,8 @@ def load():
     L.hipjpegDecodeBatchStats.argtypes = [vp, vp, vp, vp]
     L.hipjpegDecodeBatchGetStatuses.argtypes = [vp, vp, i32]
     L.hipjpegDecodeBatchSetTransforms.argtypes = [vp, vp, i32]
+    L.hipjpegDecodeBatchSetScales.argtypes = [vp, vp, i32]
+    L.hipjpegGetScaledImageSize.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     L.hipjpegDecodeBatchSubmit.argtypes = [vp, vp, vp, i32, vp, i32, ctypes.c_uint, vp]
     L.hipjpegDecodeBatchWait.argtypes = [vp, vp, i32]
     L.hipjpegSetPipelineDepth.argtypes = [vp, i32]

@@ -261,6 +261,22 @@ class _ExecMixin:
         return ep
 
 
+def _scale_denom_option(options):
+    """The scale_denom the HIP decoder plugin reads out of an option string, read the way it reads it (plugin_common.h for_each_option,
+    then an istream >> int): tokens between spaces, module before the first ':', key up to the first '=', the leading integer of the
+    value ("2x" is 2, no digits is 0); unnamed or addressed to hipjpeg_decoder, the last one counts; anything but 2, 4, 8 is 1."""
+    import re
+    denom = 1
+    for token in options.split(" "):
+        colon, equal = token.find(":"), token.find("=")
+        if colon < 0 or equal < 0 or colon > equal or token[:colon] not in ("", "hipjpeg_decoder"):
+            continue
+        if token[colon + 1:equal] == "scale_denom":
+            m = re.match(r"\s*[+-]?\d+", token[equal + 1:])
+            denom = int(m.group(0)) if m else 0
+    return denom if denom in (1, 2, 4, 8) else 1
+
+
 class Decoder(_ExecMixin):
     """nvimgcodec.Decoder (python/decoder.cpp:262-300).  Note one deliberate difference in defaults: the reference's Python
     layer passes options=":fancy_upsampling=0" (decoder.cpp:283); here the default is the plugins' own default (fancy on),
@@ -268,7 +284,9 @@ class Decoder(_ExecMixin):
 
     options reach the plugins as they are.  options="hipjpeg_decoder:fast_idct=1" makes the HIP decoder use the fast integer IDCT
     (JDCT_IFAST, the pixels of libjpeg-turbo's x86-64 SIMD routine, what the reference's libjpeg_turbo_decoder gives with fast_idct=1);
-    an unnamed ":fast_idct=1" is the chain's setting and hands every sample to the next decoder of the chain instead."""
+    an unnamed ":fast_idct=1" is the chain's setting and hands every sample to the next decoder of the chain instead.
+    options=":scale_denom=N" or "hipjpeg_decoder:scale_denom=N" (N = 2, 4, 8) decodes every image at 1/N of its size, libjpeg's
+    scale_denom; the images this class allocates then have hipjpegGetScaledImageSize's size."""
 
     def __init__(self, device_id=A.DEVICE_CURRENT, max_num_cpu_threads=0, backends=None, options=""):
         import torch
@@ -280,6 +298,7 @@ class Decoder(_ExecMixin):
         ep = self._make_exec_params(device_id, max_num_cpu_threads, backends)
         self._h = C.c_void_p()
         _check(lib.nvimgcodecDecoderCreate(inst, C.byref(self._h), C.byref(ep), options.encode()), "nvimgcodecDecoderCreate")
+        self._scale_denom = _scale_denom_option(options)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -336,6 +355,9 @@ class Decoder(_ExecMixin):
             info = A.init(A.ImageInfo, A.ST_IMAGE_INFO)
             _check(lib.nvimgcodecCodeStreamGetImageInfo(cs, C.byref(info)), "nvimgcodecCodeStreamGetImageInfo")
             h, w = info.plane_info[0].height, info.plane_info[0].width
+            if self._scale_denom != 1:  # the plugin decodes at 1 / scale_denom: ceil(extent * (8 / denominator) / 8)
+                k = 8 // self._scale_denom
+                h, w = (h * k + 7) // 8, (w * k + 7) // 8
             # python/decoder.cpp:202-205: a quarter-turn orientation swaps the output's width and height
             if params.apply_exif_orientation and (info.orientation.rotated // 90) % 2:
                 h, w = w, h

@@ -27,6 +27,13 @@ int launch_luma_color_fused(int layout, int hs, int vs, const DecodeImage* image
 int launch_generic_color(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream);
 // Four-component frames (CMYK / YCCK): upsampling + the reference's CMYK -> RGB step, one WorkUnit per pixel row.
 int launch_cmyk_color(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream);
+// Scaled decode (DecodeImage::scale_k != 0), kernels of their own beside K1 / K2 / K3:
+// the reduced IDCTs of libjpeg-turbo (jsimd_idct_4x4_sse2, jsimd_idct_2x2_sse2, jpeg_idct_1x1 restated) of a component whose
+// DecodeComponent::scaled is 4, 2 or 1, into its plane; one WorkUnit = 128 blocks, as for K1.  Components with scaled == 8 take K1.
+int launch_idct_reduced_plane(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream);
+// ... and from the planes to the output: jdsample.c's upsampler choice on the scaled groups, YCbCr / RGB / gray, any format but the raw
+// planes; one WorkUnit = kScaledRowsPerUnit pixel rows of the scaled picture (block_base = the first).
+int launch_scaled_color(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream);
 // Geometry pass (region of interest + EXIF orientation): WorkUnit{image = TransformImage index, block_base = first output row}.
 int launch_transform(const TransformImage* images, const WorkUnit* units, int nunits, void* stream);
 

@@ -1233,6 +1233,407 @@ __global__ __launch_bounds__(kThreads) void cmyk_color_kernel(const DecodeImage*
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Scaled decode (hipjpegDecodeBatchSetScales: 1/2, 1/4, 1/8 -- libjpeg's scale_num / scale_denom).  Kernels of their own beside K1 / K2 /
+// K3, whose code stays as it is.  A component of DCT_scaled_size s (DecodeComponent::scaled) turns every block into s x s samples:
+//   s = 8  K1 (idct_plane_kernel, kToPlane): the routine of dct_method
+//   s = 4  jsimd_idct_4x4_sse2 restated: pmullw dequantization (low 16 bits, ISLOW tables whatever dct_method says), 32-bit
+//          multiply-adds that WRAP (paddd / psubd; the C routine's 64-bit sums do not), packssdw between the passes; a block whose rows
+//          1, 2, 3, 5, 6, 7 are zero in all eight columns -- row 4 is not looked at, the routine never reads it -- skips pass 1: row 0 << 2
+//          in 16-bit lanes (psllw wraps where the full pass would saturate); packsswb + 128 at the end
+//   s = 2  jsimd_idct_2x2_sse2 restated: columns 0, 1, 3, 5, 7 and the same rows; pass 1 keeps 32 bits, pass 2 shifts column 0 left in 32
+//          bits (pslld wraps) and saturates the odd columns to int16 (packssdw) before its multiply-adds
+//   s = 1  jpeg_idct_1x1 (plain C in the library too): (DC x q + 4) >> 3 through the range-limit table, indexed & 1023 -- far out of
+//          gamut it wraps and does not clamp
+// tests/golden/manifest_scaled.json pins all of it from the library itself, the out-of-gamut vectors included.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int s16_lo(unsigned v) { return (int)(short)(v & 0xFFFFu); }
+__device__ __forceinline__ int s16_hi(unsigned v) { return (int)v >> 16; }
+// paddd / psubd: sums wrap in 32 bits (signed overflow is not defined in C++, hence unsigned)
+__device__ __forceinline__ int wadd(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
+__device__ __forceinline__ int wsub(int a, int b) { return (int)((unsigned)a - (unsigned)b); }
+__device__ __forceinline__ int sat_i16(int v) { return min(max(v, -32768), 32767); }
+__device__ __forceinline__ int sample_s8(int v) { return min(max(v, -128), 127) + 128; }  // packsswb, paddb 128
+
+// One 1-D pass of the 4x4 routine on int16 inputs i0 i1 i2 i3 i5 i6 i7 (i4 is never used); o[k] = output k, descaled by SHIFT.
+template <int SHIFT>
+__device__ __forceinline__ void reduced4_1d(int i0, int i1, int i2, int i3, int i5, int i6, int i7, int (&o)[4])
+{
+    const int t0 = (int)((unsigned)i0 << 14);
+    const int t2 = wsub(i2 * F_1_847, i6 * F_0_765);
+    const int t10 = wadd(t0, t2), t12 = wsub(t0, t2);
+    const int o0 = wadd(wsub(i5 * 11893, i7 * 1730), wsub(i1 * 8697, i3 * 17799));
+    const int o2 = wadd(wsub(i3 * 7373, i7 * 4176), wsub(i1 * 20995, i5 * 4926));
+    constexpr int rnd = 1 << (SHIFT - 1);
+    o[0] = wadd(wadd(t10, o2), rnd) >> SHIFT;
+    o[1] = wadd(wadd(t12, o0), rnd) >> SHIFT;
+    o[2] = wadd(wsub(t12, o0), rnd) >> SHIFT;
+    o[3] = wadd(wsub(t10, o2), rnd) >> SHIFT;
+}
+
+// The 4x4 transform by a lane pair: lane p runs pass 1 on columns 4p .. 4p+3 and pass 2 on rows 2p, 2p+1; px[r] = the four bytes of row 2p+r.
+__device__ __forceinline__ void reduced4_block(const u32x4 (&cols)[4], const unsigned* __restrict__ qp, bool p, unsigned (&px)[2])
+{
+    int ws[4][4];  // [row][own column]
+    unsigned ac = 0, d0[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const u32x4 q4 = *reinterpret_cast<const u32x4*>(qp + j * 4);
+        const unsigned dx = pk_mul16(cols[j].x, q4.x), dy = pk_mul16(cols[j].y, q4.y), dz = pk_mul16(cols[j].z, q4.z), dw = pk_mul16(cols[j].w, q4.w);
+        ac |= (cols[j].x & 0xFFFF0000u) | cols[j].y | (cols[j].z & 0xFFFF0000u) | cols[j].w;
+        d0[j] = dx;
+        int o[4];
+        reduced4_1d<12>(s16_lo(dx), s16_hi(dx), s16_lo(dy), s16_hi(dy), s16_hi(dz), s16_lo(dw), s16_hi(dw), o);
+#pragma unroll
+        for (int r = 0; r < 4; r++) ws[r][j] = sat_i16(o[r]);
+    }
+    ac |= (unsigned)pair_swap((int)ac);
+    unsigned W[4][2];
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int jj = 0; jj < 2; jj++) {
+            const unsigned full = lo_pair(ws[r][2 * jj], ws[r][2 * jj + 1]);
+            const unsigned dc_only = pk_shl16_2(lo_pair((int)d0[2 * jj], (int)d0[2 * jj + 1]));
+            W[r][jj] = ac == 0 ? dc_only : full;
+        }
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        unsigned left[2], right[2];  // columns 0..3, columns 4..7 of row 2p+r
+#pragma unroll
+        for (int jj = 0; jj < 2; jj++) {
+            const unsigned recv = (unsigned)pair_swap((int)(p ? W[r][jj] : W[2 + r][jj])), own = p ? W[2 + r][jj] : W[r][jj];
+            left[jj] = p ? recv : own;
+            right[jj] = p ? own : recv;
+        }
+        int o[4];
+        reduced4_1d<19>(s16_lo(left[0]), s16_hi(left[0]), s16_lo(left[1]), s16_hi(left[1]), s16_hi(right[0]), s16_lo(right[1]), s16_hi(right[1]), o);
+        px[r] = pack4(sample_s8(o[0]), sample_s8(o[1]), sample_s8(o[2]), sample_s8(o[3]));
+    }
+}
+
+__device__ __forceinline__ int reduced2_odd(int i1, int i3, int i5, int i7) { return wadd(wsub(i5 * 6967, i7 * 5906), wsub(i1 * 29692, i3 * 10426)); }
+
+// The 2x2 transform by a lane pair: lane 0 runs pass 1 on columns 0, 1, 3, lane 1 on columns 5, 7; lane p runs pass 2 on row p.  Returns
+// the two bytes of row p.
+__device__ __forceinline__ unsigned reduced2_block(const u32x4 (&cols)[4], const unsigned* __restrict__ qp, bool p)
+{
+    int A[4], B[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        if (j == 2) continue;
+        const u32x4 q4 = *reinterpret_cast<const u32x4*>(qp + j * 4);
+        const unsigned dx = pk_mul16(cols[j].x, q4.x), dy = pk_mul16(cols[j].y, q4.y), dz = pk_mul16(cols[j].z, q4.z), dw = pk_mul16(cols[j].w, q4.w);
+        const int t10 = (int)((unsigned)s16_lo(dx) << 15), t0 = reduced2_odd(s16_hi(dx), s16_hi(dy), s16_hi(dz), s16_hi(dw));
+        A[j] = wadd(wadd(t10, t0), 1 << 12) >> 13;
+        B[j] = wadd(wsub(t10, t0), 1 << 12) >> 13;
+    }
+    // lane 0 (row A) wants A5, A7 of lane 1; lane 1 (row B) wants B0, B1, B3 of lane 0
+    const int r0 = pair_swap(p ? A[1] : B[0]), r1 = pair_swap(p ? A[3] : B[1]), r2 = pair_swap(B[3]);
+    const int c0 = p ? r0 : A[0], c1 = p ? r1 : A[1], c3 = p ? r2 : A[3], c5 = p ? B[1] : r0, c7 = p ? B[3] : r1;
+    const int e = (int)((unsigned)c0 << 15), t = reduced2_odd(sat_i16(c1), sat_i16(c3), sat_i16(c5), sat_i16(c7));
+    const int o0 = wadd(wadd(e, t), 1 << 19) >> 20, o1 = wadd(wsub(e, t), 1 << 19) >> 20;
+    return (unsigned)sample_s8(o0) | ((unsigned)sample_s8(o1) << 8);
+}
+
+// fetch_half_block for a routine that reads only the columns of `colmask`: the other 16-byte column chunks are not fetched (zeros in LDS).
+// The 2x2 routine reads columns 0, 1, 3, 5, 7; the 4x4 one computes on all but column 4, yet its zero test looks at that one too.
+__device__ __forceinline__ void fetch_half_block_cols(const DecodeComponent& cd, int wave_first_block, int block_limit, char* lds_wave, int lane, unsigned colmask,
+                                                      u32x4 (&cols)[4])
+{
+    if (cd.block_off) {  // (wave-uniform: a property of the picture)
+        const int mine = wave_first_block + (lane >> 1);
+        sparse_expand_slots(cd, mine < block_limit, (unsigned)mine, lds_wave, lane);
+        read_half_block(lds_wave, lane, 0u, false, cols);
+        return;
+    }
+    const u32x4* src = reinterpret_cast<const u32x4*>(cd.coef) + (size_t)wave_first_block * 8;
+    const int nchunks = min(kBlocksPerWave, block_limit - wave_first_block) * 8;  // valid 16-byte chunks (may be <= 0)
+    const int my_block = wave_first_block + (lane >> 1);
+    const bool dc_apart = cd.dc_stride != 64;
+    unsigned dc = 0;
+    if (dc_apart && my_block < block_limit) dc = ((const HJ_GLOBAL unsigned short*)cd.dc)[my_block];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int g = k * 64 + lane;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (g < nchunks && ((colmask >> (g & 7)) & 1u)) v = __builtin_nontemporal_load((const HJ_GLOBAL u32x4*)src + g);
+        *reinterpret_cast<u32x4*>(lds_wave + (g >> 3) * kLdsBlockStride + (g & 7) * 16) = v;
+    }
+    wave_lds_fence();
+    read_half_block(lds_wave, lane, dc, dc_apart, cols);
+}
+
+__global__ __launch_bounds__(kThreads) void idct_reduced_plane_kernel(const DecodeImage* __restrict__ images, const WorkUnit* __restrict__ units)
+{
+    __shared__ __attribute__((aligned(16))) char lds[4 * kBlocksPerWave * kLdsBlockStride];
+    const WorkUnit u = units[blockIdx.x];
+    const DecodeImage& im = images[u.image];
+    const DecodeComponent& cd = im.comp[u.comp];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = (int)cd.scaled, bw = cd.blocks_w, nblocks = bw * cd.blocks_h;
+    uint8_t* plane = cd.plane;
+    const unsigned pitch = cd.plane_pitch;
+    if (s == 1) {
+        // one lane per block, nothing but the DC value is read
+        const int b = (int)u.block_base + tid;
+        if (tid >= kBlocksPerUnit || b >= nblocks) return;
+        int dc;
+        if (cd.block_off) {
+            const unsigned off = ((const HJ_GLOBAL unsigned*)cd.block_off)[b];
+            const HJ_GLOBAL unsigned char* rec = (const HJ_GLOBAL unsigned char*)cd.coef + off;
+            dc = off ? (int)(short)((unsigned)rec[1] | ((unsigned)rec[2] << 8)) : 0;
+        } else
+            dc = ((const HJ_GLOBAL short*)cd.dc)[(size_t)b * cd.dc_stride];
+        const int i = ((dc * (int)(cd.qpk[0][0] & 0xFFFFu) + 4) >> 3) & 1023;  // range_limit[... & RANGE_MASK]
+        const int v = i < 128 ? 128 + i : i < 512 ? 255 : i < 896 ? 0 : i - 896;
+        const int by = b / bw, bx = b - by * bw;
+        plane[(size_t)by * pitch + bx] = (uint8_t)v;
+        return;
+    }
+    const bool p = lane & 1;
+    const int wave_first = (int)u.block_base + wave * kBlocksPerWave;
+    u32x4 cols[4];
+    fetch_half_block_cols(cd, wave_first, nblocks, lds + wave * kBlocksPerWave * kLdsBlockStride, lane, s == 4 ? 0xFFu : 0xABu, cols);
+    const int b = wave_first + (lane >> 1);
+    if (b >= nblocks) return;  // whole pairs leave together
+    const int by = b / bw, bx = b - by * bw;
+    if (s == 4) {
+        unsigned px[2];
+        reduced4_block(cols, cd.qpk[p], p, px);
+        uint8_t* base = plane + (size_t)(by * 4 + 2 * (int)p) * pitch + bx * 4;  // (pitch is a multiple of 16: aligned 4-byte rows)
+        *reinterpret_cast<unsigned*>(base) = px[0];
+        *reinterpret_cast<unsigned*>(base + pitch) = px[1];
+    } else {
+        const unsigned px = reduced2_block(cols, cd.qpk[p], p);
+        *reinterpret_cast<unsigned short*>(plane + (size_t)(by * 2 + (int)p) * pitch + bx * 2) = (unsigned short)px;
+    }
+}
+
+// From the planes of a scaled image to its output.  jdsample.c jinit_upsampler on the scaled groups: a component of DCT_scaled_size s
+// has h_in = h s / k samples per group against h_out = hmax, so its factors are fx = hmax k / (h s), fy = vmax k / (v s); the filter
+// choice is upsampled_sample()'s (the host has cleared kFlagFancyUpsampling where k = 1: libjpeg does no fancy upsampling there).
+struct ScaledPlane {
+    const uint8_t* plane;
+    unsigned pitch;
+    int dw, dh, fx, fy;
+};
+// (the component index is a compile-time constant: a run-time one would reach the descriptor through a scalar load with a register offset)
+template <int C>
+__device__ __forceinline__ ScaledPlane scaled_plane(const DecodeImage& im)
+{
+    const DecodeComponent& k = im.comp[C];
+    // (a gray image's unused components are zeros: max keeps the divisions defined)
+    return ScaledPlane{k.plane, k.plane_pitch, (int)k.samp_w, (int)k.samp_h, (int)(im.hmax * im.scale_k) / max((int)(k.h * k.scaled), 1),
+                       (int)(im.vmax * im.scale_k) / max((int)(k.v * k.scaled), 1)};
+}
+__device__ __forceinline__ int scaled_sample(const ScaledPlane& k, int x, int y, bool fancy)
+{
+    const int fx = k.fx, fy = k.fy, dw = k.dw, dh = k.dh;
+    const uint8_t* plane = k.plane;
+    const size_t pitch = k.pitch;
+    if (fx == 1 && fy == 1) return plane[(size_t)y * pitch + x];
+    if (fx == 2 && fy == 1 && fancy && dw > 2) {
+        const uint8_t* p = plane + (size_t)y * pitch;
+        const int i = x >> 1;
+        if (x == 0) return p[0];
+        if (x == 2 * dw - 1) return p[dw - 1];
+        return (x & 1) ? (3 * p[i] + p[i + 1] + 2) >> 2 : (3 * p[i] + p[i - 1] + 1) >> 2;
+    }
+    if (fx == 2 && fy == 2 && fancy && dw > 2) {
+        const int r0 = y >> 1, r1 = min(max((y & 1) ? r0 + 1 : r0 - 1, 0), dh - 1);
+        const uint8_t* p0 = plane + (size_t)r0 * pitch;
+        const uint8_t* p1 = plane + (size_t)r1 * pitch;
+        const int i = x >> 1, cs = 3 * p0[i] + p1[i];
+        if (x == 0) return (cs * 4 + 8) >> 4;
+        if (x == 2 * dw - 1) return (cs * 4 + 7) >> 4;
+        return (x & 1) ? (3 * cs + (3 * p0[i + 1] + p1[i + 1]) + 7) >> 4 : (3 * cs + (3 * p0[i - 1] + p1[i - 1]) + 8) >> 4;
+    }
+    if (fx == 1 && fy == 2 && fancy) {
+        const int r0 = y >> 1, r1 = min(max((y & 1) ? r0 + 1 : r0 - 1, 0), dh - 1);
+        return (3 * plane[(size_t)r0 * pitch + x] + plane[(size_t)r1 * pitch + x] + ((y & 1) ? 2 : 1)) >> 2;
+    }
+    return plane[(size_t)(y / fy) * pitch + x / fx];
+}
+
+// Three samples of one pixel -> its three output channels in store order
+__device__ __forceinline__ void scaled_pixel(int s0, int s1, int s2, bool gray, bool ycc, bool bgr, int& a, int& b, int& c)
+{
+    int R = s0, G = s0, B = s0;
+    if (!gray) {
+        if (ycc) {
+            const int rr = (s2 * 91881 + (32768 - 128 * 91881)) >> 16;
+            const int bb = (s1 * 116130 + (32768 - 128 * 116130)) >> 16;
+            const int gg = (s1 * -22554 + s2 * -46802 + (32768 + 128 * 22554 + 128 * 46802)) >> 16;
+            R = min(max(s0 + rr, 0), 255);
+            G = min(max(s0 + gg, 0), 255);
+            B = min(max(s0 + bb, 0), 255);
+        } else {
+            G = s1;
+            B = s2;
+        }
+    }
+    a = bgr ? B : R;
+    b = G;
+    c = bgr ? R : B;
+}
+
+// four bytes to dst: one dword where the row is 4-byte aligned and all four belong to the picture, single bytes at a ragged edge
+__device__ __forceinline__ void store_px4(uint8_t* dst, unsigned v, bool whole)
+{
+    if (whole)
+        *reinterpret_cast<unsigned*>(dst) = v;
+    else
+        dst[0] = (uint8_t)v;  // (the caller has shifted the byte it wants into place)
+}
+
+// One workgroup = kScaledRowsPerUnit pixel rows, a wave per row in turn.  Where no component is left to upsample (gray, 4:4:4 and 4:2:0
+// at every scale: libjpeg gives the chroma the larger IDCT instead) and the caller's rows are 16-byte aligned, a lane takes SIXTEEN
+// pixels: one 16-byte load per plane, three 16-byte stores (interleaved) or one per plane -- the kernel is bound by the bytes it has in
+// flight, not by arithmetic.  What is left of the row, and every other picture, goes in groups of FOUR pixels: a dword load per plane or
+// scaled_sample() per pixel, dword stores where the rows are 4-byte aligned, single bytes at a ragged edge.  Everything that picks a
+// path -- format, colour model, filter, alignment -- is the same for the whole workgroup.
+__global__ __launch_bounds__(kThreads) void scaled_color_kernel(const DecodeImage* __restrict__ images, const WorkUnit* __restrict__ units)
+{
+    const WorkUnit u = units[blockIdx.x];
+    const DecodeImage& im = images[u.image];
+    const int W = im.width, H = im.height;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fmt = im.out_format;
+    const bool planar = fmt == kOutPlanarRGB || fmt == kOutPlanarBGR, only_y = fmt == kOutY;
+    const bool bgr = fmt == kOutInterleavedBGR || fmt == kOutPlanarBGR;
+    const bool fancy = (im.flags & kFlagFancyUpsampling) != 0;
+    const bool gray = im.ncomp == 1 || only_y, ycc = im.color_model == 1;
+    const ScaledPlane k0 = scaled_plane<0>(im), k1 = scaled_plane<1>(im), k2 = scaled_plane<2>(im);
+    const bool direct = k0.fx == 1 && k0.fy == 1 && (gray || (k1.fx == 1 && k1.fy == 1 && k2.fx == 1 && k2.fy == 1));
+    uint8_t* const out0 = im.out[0];
+    uint8_t* const out1 = im.out[1];
+    uint8_t* const out2 = im.out[2];
+    const unsigned op0 = im.out_pitch[0], op1 = im.out_pitch[1], op2 = im.out_pitch[2];
+    const bool aligned = planar ? ((((uintptr_t)out0 | (uintptr_t)out1 | (uintptr_t)out2 | op0 | op1 | op2) & 3) == 0) : ((((uintptr_t)out0 | op0) & 3) == 0);
+    const bool aligned16 = planar ? ((((uintptr_t)out0 | (uintptr_t)out1 | (uintptr_t)out2 | op0 | op1 | op2) & 15) == 0) : ((((uintptr_t)out0 | op0) & 15) == 0);
+    const int wide_groups = (direct && aligned16) ? (W >> 4) : 0;
+    const int groups = (W + 3) >> 2, row_end = min((int)u.block_base + kScaledRowsPerUnit, H);
+    for (int y = (int)u.block_base + wave; y < row_end; y += kThreads / 64) {
+        for (int g = lane; g < wide_groups; g += 64) {
+            const int x = g * 16;
+            // (planes are 16-byte aligned, pitch included, and x + 16 <= W lies inside the row)
+            const u32x4 v0 = *reinterpret_cast<const u32x4*>(k0.plane + (size_t)y * k0.pitch + x);
+            if (only_y) {
+                *reinterpret_cast<u32x4*>(out0 + (size_t)y * op0 + x) = v0;
+                continue;
+            }
+            u32x4 v1 = {0u, 0u, 0u, 0u}, v2 = {0u, 0u, 0u, 0u};
+            if (!gray) {
+                v1 = *reinterpret_cast<const u32x4*>(k1.plane + (size_t)y * k1.pitch + x);
+                v2 = *reinterpret_cast<const u32x4*>(k2.plane + (size_t)y * k2.pitch + x);
+            }
+            const unsigned w0[4] = {v0.x, v0.y, v0.z, v0.w}, w1[4] = {v1.x, v1.y, v1.z, v1.w}, w2[4] = {v2.x, v2.y, v2.z, v2.w};
+            unsigned o[12];  // interleaved: the 48 bytes in order; planar: [0..3] first plane, [4..7] second, [8..11] third
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                int a[4], b[4], c[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    scaled_pixel((int)((w0[q] >> (8 * i)) & 255u), (int)((w1[q] >> (8 * i)) & 255u), (int)((w2[q] >> (8 * i)) & 255u), gray, ycc, bgr, a[i], b[i], c[i]);
+                if (planar) {
+                    o[q] = pack4(a[0], a[1], a[2], a[3]);
+                    o[4 + q] = pack4(b[0], b[1], b[2], b[3]);
+                    o[8 + q] = pack4(c[0], c[1], c[2], c[3]);
+                } else {
+                    o[3 * q] = pack4(a[0], b[0], c[0], a[1]);
+                    o[3 * q + 1] = pack4(b[1], c[1], a[2], b[2]);
+                    o[3 * q + 2] = pack4(c[2], a[3], b[3], c[3]);
+                }
+            }
+            const u32x4 s0 = {o[0], o[1], o[2], o[3]}, s1 = {o[4], o[5], o[6], o[7]}, s2 = {o[8], o[9], o[10], o[11]};
+            if (planar) {
+                *reinterpret_cast<u32x4*>(out0 + (size_t)y * op0 + x) = s0;
+                *reinterpret_cast<u32x4*>(out1 + (size_t)y * op1 + x) = s1;
+                *reinterpret_cast<u32x4*>(out2 + (size_t)y * op2 + x) = s2;
+            } else {
+                u32x4* q = reinterpret_cast<u32x4*>(out0 + (size_t)y * op0 + (size_t)x * 3);  // (x * 3 is a multiple of 48)
+                q[0] = s0;
+                q[1] = s1;
+                q[2] = s2;
+            }
+        }
+        for (int g = wide_groups * 4 + lane; g < groups; g += 64) {
+            const int x = g * 4, n = min(4, W - x);
+            int s0[4], s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+            if (direct) {
+                // (planes are 16-byte aligned with 16 bytes of slack per row: an aligned dword that starts inside the row is in bounds)
+                const unsigned v0 = *reinterpret_cast<const unsigned*>(k0.plane + (size_t)y * k0.pitch + x);
+                unsigned v1 = 0, v2 = 0;
+                if (!gray) {
+                    v1 = *reinterpret_cast<const unsigned*>(k1.plane + (size_t)y * k1.pitch + x);
+                    v2 = *reinterpret_cast<const unsigned*>(k2.plane + (size_t)y * k2.pitch + x);
+                }
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    s0[i] = (int)((v0 >> (8 * i)) & 255u);
+                    s1[i] = (int)((v1 >> (8 * i)) & 255u);
+                    s2[i] = (int)((v2 >> (8 * i)) & 255u);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const int xi = min(x + i, W - 1);  // (past the right edge: a pixel that exists, its value is not stored)
+                    s0[i] = scaled_sample(k0, xi, y, fancy);
+                    if (!gray) {
+                        s1[i] = scaled_sample(k1, xi, y, fancy);
+                        s2[i] = scaled_sample(k2, xi, y, fancy);
+                    }
+                }
+            }
+            const bool whole = aligned && n == 4;
+            if (only_y) {
+                uint8_t* d = out0 + (size_t)y * op0 + x;
+                const unsigned v = pack4(s0[0], s0[1], s0[2], s0[3]);
+                store_px4(d, v, whole);
+#pragma unroll
+                for (int i = 1; i < 4; i++)
+                    if (!whole && i < n) d[i] = (uint8_t)(v >> (8 * i));
+                continue;
+            }
+            int a[4], b[4], c[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) scaled_pixel(s0[i], s1[i], s2[i], gray, ycc, bgr, a[i], b[i], c[i]);
+            if (planar) {
+                uint8_t* d0 = out0 + (size_t)y * op0 + x;
+                uint8_t* d1 = out1 + (size_t)y * op1 + x;
+                uint8_t* d2 = out2 + (size_t)y * op2 + x;
+                const unsigned va = pack4(a[0], a[1], a[2], a[3]), vb = pack4(b[0], b[1], b[2], b[3]), vc = pack4(c[0], c[1], c[2], c[3]);
+                store_px4(d0, va, whole);
+                store_px4(d1, vb, whole);
+                store_px4(d2, vc, whole);
+#pragma unroll
+                for (int i = 1; i < 4; i++)
+                    if (!whole && i < n) {
+                        d0[i] = (uint8_t)(va >> (8 * i));
+                        d1[i] = (uint8_t)(vb >> (8 * i));
+                        d2[i] = (uint8_t)(vc >> (8 * i));
+                    }
+            } else {
+                uint8_t* d = out0 + (size_t)y * op0 + (size_t)x * 3;
+                if (whole) {
+                    unsigned* q = reinterpret_cast<unsigned*>(d);  // (x * 3 is a multiple of 12)
+                    q[0] = pack4(a[0], b[0], c[0], a[1]);
+                    q[1] = pack4(b[1], c[1], a[2], b[2]);
+                    q[2] = pack4(c[2], a[3], b[3], c[3]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++)
+                        if (i < n) {
+                            d[3 * i] = (uint8_t)a[i];
+                            d[3 * i + 1] = (uint8_t)b[i];
+                            d[3 * i + 2] = (uint8_t)c[i];
+                        }
+                }
+            }
+        }
+    }
+}
 
 // Geometry pass: region of interest + EXIF orientation (DecodeBatch plans it for the images that ask for it; the pixel
 // kernels have written those images into an intermediate buffer in stored-image coordinates).
@@ -1382,6 +1783,20 @@ int launch_cmyk_color(const DecodeImage* images, const WorkUnit* units, int nuni
 {
     if (nunits <= 0) return 0;
     hipLaunchKernelGGL(cmyk_color_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
+    return (int)hipGetLastError();
+}
+
+int launch_idct_reduced_plane(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream)
+{
+    if (nunits <= 0) return 0;
+    hipLaunchKernelGGL(idct_reduced_plane_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
+    return (int)hipGetLastError();
+}
+
+int launch_scaled_color(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream)
+{
+    if (nunits <= 0) return 0;
+    hipLaunchKernelGGL(scaled_color_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
     return (int)hipGetLastError();
 }
 

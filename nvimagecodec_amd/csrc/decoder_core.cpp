@@ -158,6 +158,27 @@ bool choose_variant(const FrameInfo& f, OutFormat fmt, bool fancy, int* variant)
     return true;
 }
 
+
+// libjpeg's jpeg_calc_output_dimensions (jdmaster.c) for scale 1 / denom: k = min_DCT_scaled_size
+int scaled_extent(int extent, int k) { return (int)(((int64_t)extent * k + 7) / 8); }
+
+// A scaled image: every component's DCT_scaled_size (jdmaster.c: doubled from k while the component's group still divides the
+// largest one), and whether scaled_color_kernel covers the frame -- one or three components, integral upsampling ratios on the scaled
+// groups (jdsample.c refuses the others), no raw planes; `y` as at full size.
+bool choose_scaled(const FrameInfo& f, OutFormat fmt, int k, int scaled_size[4])
+{
+    if (f.color == ColorModel::CMYK || f.color == ColorModel::YCCK || (f.ncomp != 1 && f.ncomp != 3) || fmt == kOutPlanarYUV) return false;
+    for (int c = 0; c < f.ncomp; c++) {
+        int s = k;
+        while (s < 8 && (f.hmax * k) % (f.comp[c].h * s * 2) == 0 && (f.vmax * k) % (f.comp[c].v * s * 2) == 0) s *= 2;
+        scaled_size[c] = s;
+        const int h_in = f.comp[c].h * s / k, v_in = f.comp[c].v * s / k;
+        if (f.hmax % h_in || f.vmax % v_in) return false;
+        if (fmt == kOutY && c == 0 && (f.color == ColorModel::RGB || h_in != f.hmax || v_in != f.vmax)) return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 // Largest frame the decoder takes: the reference's CPU path refuses width x height x components >= 2^29 before it allocates
@@ -177,15 +198,15 @@ static uint64_t max_image_samples()
 // extensions/libjpeg_turbo/libjpeg_turbo_decoder.cpp:355-370: the region must lie inside the image)
 static hipjpegStatus_t normalise_transform(PlannedImage& im, const hipjpegTransform_t& requested, OutFormat fmt)
 {
-    const FrameInfo& f = im.frame;
+    const int width = im.pic_w, height = im.pic_h;  // (a scaled image: the region is in scaled-picture coordinates)
     hipjpegTransform_t t = requested;
     if (t.x0 == 0 && t.y0 == 0 && t.x1 == 0 && t.y1 == 0) {
-        t.x1 = f.width;
-        t.y1 = f.height;
+        t.x1 = width;
+        t.y1 = height;
     }
     if (t.orientation == 0) t.orientation = 1;
-    const bool whole = t.x0 == 0 && t.y0 == 0 && t.x1 == f.width && t.y1 == f.height;
-    if (t.orientation < 1 || t.orientation > 8 || t.x0 < 0 || t.y0 < 0 || t.x1 > f.width || t.y1 > f.height || t.x1 <= t.x0 || t.y1 <= t.y0)
+    const bool whole = t.x0 == 0 && t.y0 == 0 && t.x1 == width && t.y1 == height;
+    if (t.orientation < 1 || t.orientation > 8 || t.x0 < 0 || t.y0 < 0 || t.x1 > width || t.y1 > height || t.x1 <= t.x0 || t.y1 <= t.y0)
         return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (whole && t.orientation == 1) return HIPJPEG_STATUS_SUCCESS;
     if (fmt == kOutPlanarYUV) return HIPJPEG_STATUS_UNSUPPORTED;  // geometry on subsampled planes is not defined
@@ -201,6 +222,7 @@ struct DecodeBatch::PlanArgs {  // plan()'s arguments; give_up: per image, given
     bool any_frame = false;                               // plan_coefficients(): the coder's rules are not asked
     const hipjpegCoefficientInfo_t* infos = nullptr;      // plan_tensors(): the pictures, in place of data / lengths
     const hipjpegCoefficientPlanes_t* tensors = nullptr;
+    const int32_t* scales = nullptr;                      // plan(): one denominator per image, or nullptr
 };
 
 // What the per-image sizing adds up, in bytes unless noted; every region is carved in image order.
@@ -227,12 +249,15 @@ struct DecodeBatch::Sizing {
 
 hipjpegStatus_t DecodeBatch::plan(const uint8_t* const* data, const size_t* lengths, int n, const hipjpegOutput_t* outputs,
                                   hipjpegOutputFormat_t format, unsigned flags, hipjpegStatus_t* statuses,
-                                  const hipjpegOutputFormat_t* formats, ForkJoinPool* pool, const hipjpegTransform_t* transforms)
+                                  const hipjpegOutputFormat_t* formats, ForkJoinPool* pool, const hipjpegTransform_t* transforms,
+                                  const int32_t* scale_denoms)
 {
     pool_ = pool;
     coef_only_ = false;
     tensor_source_ = false;
-    return plan_attempts(PlanArgs{data, lengths, outputs, format, flags, formats, transforms, nullptr}, n, statuses);
+    PlanArgs a{data, lengths, outputs, format, flags, formats, transforms, nullptr};
+    a.scales = scale_denoms;
+    return plan_attempts(a, n, statuses);
 }
 
 hipjpegStatus_t DecodeBatch::plan_tensors(const hipjpegCoefficientInfo_t* infos, const hipjpegCoefficientPlanes_t* planes, int n,
@@ -353,8 +378,14 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
         return;
     }
     const OutFormat fmt = (OutFormat)(a.formats ? a.formats[i] : a.format);
-    const bool fancy = (a.flags & HIPJPEG_FLAG_FANCY_UPSAMPLING) != 0;
+    bool fancy = (a.flags & HIPJPEG_FLAG_FANCY_UPSAMPLING) != 0;
     const FrameInfo& f = im.frame;
+    const int denom = a.scales ? a.scales[i] : 1;
+    if (denom != 1 && denom != 2 && denom != 4 && denom != 8) {
+        im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
+        return;
+    }
+    im.scale_k = 8 / denom;
     if (a.infos)  // the picture is described, not parsed
         im.status = coefficient_frame(a.infos[i], a.tensors[i], &im.frame);
     else
@@ -368,7 +399,17 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
         const bool grayscale = a.transcode && (a.transcode[i].orientation & HIPJPEG_TRANSCODE_GRAYSCALE) != 0;
         if (im.status == HIPJPEG_STATUS_SUCCESS && !a.any_frame) im.status = transcode_picture(f, grayscale, &pic);
     } else {
-        if (im.status == HIPJPEG_STATUS_SUCCESS && !choose_variant(f, fmt, fancy, &im.variant)) im.status = HIPJPEG_STATUS_UNSUPPORTED;
+        im.pic_w = f.width;
+        im.pic_h = f.height;
+        if (im.status == HIPJPEG_STATUS_SUCCESS && im.scale_k != 8) {
+            // kernels of their own (decode_kernels.hip, scaled decode); libjpeg does no fancy upsampling at 1/8 (jdsample.c)
+            im.variant = -5;
+            im.pic_w = scaled_extent(f.width, im.scale_k);
+            im.pic_h = scaled_extent(f.height, im.scale_k);
+            fancy = fancy && im.scale_k > 1;
+            if (!choose_scaled(f, fmt, im.scale_k, im.scaled_size)) im.status = HIPJPEG_STATUS_UNSUPPORTED;
+        } else if (im.status == HIPJPEG_STATUS_SUCCESS && !choose_variant(f, fmt, fancy, &im.variant))
+            im.status = HIPJPEG_STATUS_UNSUPPORTED;
         for (int p = 0; im.status == HIPJPEG_STATUS_SUCCESS && p < (fmt == kOutPlanarYUV ? f.ncomp : out_planes(fmt)); p++)
             if (!a.outputs[i].plane[p]) im.status = HIPJPEG_STATUS_INVALID_ARGUMENT;
         if (im.status == HIPJPEG_STATUS_SUCCESS && a.transforms) im.status = normalise_transform(im, a.transforms[i], fmt);
@@ -405,8 +446,10 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
     if (im.status != HIPJPEG_STATUS_SUCCESS) return;
     // the part of the device descriptor that does not depend on where things will lie in the arenas
     DecodeImage& d = desc_[i];
-    d.width = (uint32_t)f.width;
-    d.height = (uint32_t)f.height;
+    const bool scaled = im.variant == -5;
+    d.width = (uint32_t)(scaled ? im.pic_w : f.width);
+    d.height = (uint32_t)(scaled ? im.pic_h : f.height);
+    d.scale_k = scaled ? (uint32_t)im.scale_k : 0u;
     d.ncomp = (uint32_t)f.ncomp;
     d.hmax = (uint32_t)f.hmax;
     d.vmax = (uint32_t)f.vmax;
@@ -426,7 +469,14 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
         dc.samp_h = (uint16_t)k.samp_h;
         dc.h = (uint16_t)k.h;
         dc.v = (uint16_t)k.v;
-        pack_qpk(f.qtab[c], fast_idct_, dc.qpk);
+        if (scaled) {
+            // the component at the scale (jdmaster.c downsampled_width / height); the reduced IDCTs take ISLOW tables whatever dct_method says
+            const int s = im.scaled_size[c];
+            dc.scaled = (uint32_t)s;
+            dc.samp_w = (uint16_t)(((int64_t)f.width * k.h * s + (int64_t)f.hmax * 8 - 1) / ((int64_t)f.hmax * 8));
+            dc.samp_h = (uint16_t)(((int64_t)f.height * k.v * s + (int64_t)f.vmax * 8 - 1) / ((int64_t)f.vmax * 8));
+        }
+        pack_qpk(f.qtab[c], fast_idct_ && (!scaled || im.scaled_size[c] == 8), dc.qpk);
     }
 }
 
@@ -497,13 +547,13 @@ void DecodeBatch::size_image(int i, Sizing& s)
         memset(&t, 0, sizeof t);
         t.nplanes = out_planes(fmt);
         t.bpp = out_bpp(fmt);
-        const uint32_t ipitch = (uint32_t)align_up((size_t)f.width * t.bpp, 16);
+        const uint32_t ipitch = (uint32_t)align_up((size_t)im.pic_w * t.bpp, 16);
         for (int p = 0; p < t.nplanes; p++) {
             t.dst[p] = d.out[p];
             t.dst_pitch[p] = d.out_pitch[p];
             t.src_pitch[p] = ipitch;
             d.out_pitch[p] = ipitch;
-            s.xform_plane_off.push_back(s.planes.take(align_up((size_t)ipitch * f.height + 16, 256)));
+            s.xform_plane_off.push_back(s.planes.take(align_up((size_t)ipitch * im.pic_h + 16, 256)));
         }
         t.x0 = im.transform.x0;
         t.y0 = im.transform.y0;
@@ -517,7 +567,17 @@ void DecodeBatch::size_image(int i, Sizing& s)
         xform_desc_.push_back(t);
         s.xform_units += (size_t)(t.out_h + kTransformRowsPerUnit - 1) / kTransformRowsPerUnit;
     }
-    for (int c = 0; c < f.ncomp; c++) {
+    for (int c = 0; c < f.ncomp && im.variant == -5; c++) {
+        // a scaled image: every component through a plane of blocks_w s x blocks_h s samples (K1 for s = 8, the reduced kernel else)
+        const Component& k = f.comp[c];
+        DecodeComponent& dc = d.comp[c];
+        const size_t sz = (size_t)im.scaled_size[c];
+        dc.plane_pitch = (uint32_t)align_up((size_t)k.blocks_w * sz + 16, 16);
+        s.plane_off[(size_t)i * 4 + c] = s.planes.take(align_up((size_t)dc.plane_pitch * k.blocks_h * sz + 16, 256));
+        s.units += ((size_t)k.blocks_w * k.blocks_h + kBlocksPerUnit - 1) / kBlocksPerUnit;
+    }
+    if (im.variant == -5) s.units += ((size_t)im.pic_h + kScaledRowsPerUnit - 1) / kScaledRowsPerUnit;
+    for (int c = 0; c < f.ncomp && im.variant != -5; c++) {
         const Component& k = f.comp[c];
         const Route route = component_route(im.variant, fmt, c);
         if (route == kRoutePlane) {
@@ -535,7 +595,7 @@ void DecodeBatch::size_image(int i, Sizing& s)
     if (fmt == kOutPlanarYUV)
         for (int c = 0; c < f.ncomp; c++) output_bytes_ += (uint64_t)f.comp[c].samp_w * f.comp[c].samp_h;
     else
-        output_bytes_ += (uint64_t)f.width * f.height * (fmt == kOutY ? 1 : 3);
+        output_bytes_ += (uint64_t)im.pic_w * im.pic_h * (fmt == kOutY ? 1 : 3);
     if (!im.gpu_entropy) return;
     // the GPU entropy stage's share; offsets into the staging area are relative to their region here, layout() rebases them
     if (im.gpu_prog) im.tables_offset = s.pools.take(align_up(im.pool_words * 2, 64), 1);
@@ -873,6 +933,9 @@ void DecodeBatch::finalize(hipjpegStatus_t* statuses)
     // unchecked
     for (const PlannedImage& im : images_)
         if (im.status == HIPJPEG_STATUS_SUCCESS && im.gpu_entropy && !im.gpu_prog && im.has_transform) fused_ = false;
+    // likewise a scaled image: its kernels read coefficient blocks from HBM, which only the block pass writes
+    for (const PlannedImage& im : images_)
+        if (im.status == HIPJPEG_STATUS_SUCCESS && im.variant == -5) fused_ = false;
     // likewise a picture the FUSED builds cannot decode from one HuffImage: several scans, or one scan in another component order
     for (const PlannedImage& im : images_)
         if (im.status == HIPJPEG_STATUS_SUCCESS && im.gpu_entropy && !im.gpu_prog && !im.fused_layout) fused_ = false;
@@ -891,7 +954,7 @@ void DecodeBatch::finalize(hipjpegStatus_t* statuses)
 // Units of the pixel kernels (K1 idct_plane, K2 luma_color, K3 generic / CMYK colour) and of the geometry pass, image by image.
 void DecodeBatch::build_pixel_units()
 {
-    for (UnitList* l : {&plane_units_, &fused_plane_units_, &generic_units_, &cmyk_units_, &xform_units_}) l->units.clear();
+    for (UnitList* l : {&plane_units_, &fused_plane_units_, &generic_units_, &cmyk_units_, &xform_units_, &reduced_units_, &scaled_color_units_}) l->units.clear();
     for (auto* lists : {&luma_units_, &fused_luma_units_})
         for (auto& row : *lists)
             for (UnitList& l : row) l.units.clear();
@@ -920,7 +983,13 @@ void DecodeBatch::build_pixel_units()
         const OutFormat fmt = (OutFormat)d.out_format;
         const bool fused = fused_ && im.gpu_entropy && !im.gpu_prog;
         d.huff_index = fused ? (uint32_t)im.huff_index : 0u;
-        for (int c = 0; c < f.ncomp; c++) {
+        for (int c = 0; c < f.ncomp && im.variant == -5; c++) {
+            const uint32_t nblk = (uint32_t)f.comp[c].blocks_w * f.comp[c].blocks_h;
+            std::vector<WorkUnit>& list = (im.scaled_size[c] == 8 ? plane_units_ : reduced_units_).units;
+            for (uint32_t b = 0; b < nblk; b += kBlocksPerUnit) list.push_back(WorkUnit{(uint32_t)i, b, (uint32_t)c, (uint32_t)kToPlane});
+        }
+        for (int y = 0; y < im.pic_h && im.variant == -5; y += kScaledRowsPerUnit) scaled_color_units_.units.push_back(WorkUnit{(uint32_t)i, (uint32_t)y, 0u, 0u});
+        for (int c = 0; c < f.ncomp && im.variant != -5; c++) {
             const Route route = component_route(im.variant, fmt, c);
             if (route == kRouteNone) continue;
             const uint32_t nblk = (uint32_t)f.comp[c].blocks_w * f.comp[c].blocks_h;
@@ -1166,6 +1235,8 @@ void DecodeBatch::stage_tables()
         for (UnitList& l : lists) stage(l, units);
     stage(generic_units_, units);
     stage(cmyk_units_, units);
+    stage(reduced_units_, units);
+    stage(scaled_color_units_, units);
     Carve xform{staging_.xform_units};
     stage(xform_units_, xform);
     copy_table(pinned_, staging_.xform_desc, xform_desc_);
@@ -1596,6 +1667,8 @@ int DecodeBatch::launch_pixel_kernels(void* stream, int which)
         debug_check(stream, "idct_plane", count(plane_units_));
         if (rc == 0) rc = launch_idct_plane_fused(dimg, dev(fused_plane_units_), count(fused_plane_units_), himg, pool_bytes, stream);
         debug_check(stream, "idct_plane_fused", count(fused_plane_units_));
+        if (rc == 0) rc = launch_idct_reduced_plane(dimg, dev(reduced_units_), count(reduced_units_), stream);
+        debug_check(stream, "idct_reduced_plane", count(reduced_units_));
     }
     for (int e = 0; e < kNumLumaLayouts; e++)
         for (int k = 0; k < kNumLumaVariants && rc == 0 && (which < 0 || which == 1); k++) {
@@ -1614,6 +1687,10 @@ int DecodeBatch::launch_pixel_kernels(void* stream, int which)
     if (rc == 0 && (which < 0 || which == 2)) {
         rc = launch_cmyk_color(dimg, dev(cmyk_units_), count(cmyk_units_), stream);
         debug_check(stream, "cmyk_color", count(cmyk_units_));
+    }
+    if (rc == 0 && (which < 0 || which == 2)) {  // scaled images: behind K1 and the reduced kernel, which filled their planes
+        rc = launch_scaled_color(dimg, dev(scaled_color_units_), count(scaled_color_units_), stream);
+        debug_check(stream, "scaled_color", count(scaled_color_units_));
     }
     if (rc == 0 && (which < 0 || which == 4)) {
         rc = launch_transform(at<const TransformImage>(device_, staging_.xform_desc), dev(xform_units_), count(xform_units_), stream);
@@ -1784,7 +1861,7 @@ hipjpegStatus_t DecodeBatch::export_coefficients(const hipjpegCoefficientPlanes_
 void DecodeBatch::output_size(int i, int* w, int* h) const
 {
     const PlannedImage& im = images_[i];
-    int ow = im.frame.width, oh = im.frame.height;
+    int ow = im.pic_w, oh = im.pic_h;
     if (im.has_transform) {
         const int rw = im.transform.x1 - im.transform.x0, rh = im.transform.y1 - im.transform.y0;
         ow = im.transform.orientation >= 5 ? rh : rw;

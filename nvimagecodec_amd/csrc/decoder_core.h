@@ -37,7 +37,12 @@ struct PlannedImage {
     const uint8_t* data = nullptr;
     size_t size = 0;
     size_t coef_offset[4] = {0, 0, 0, 0};  // byte offset of component c inside the staging area
-    int variant = -1;                      // KernelVariant, or -1 = generic colour path, -2 = planes-to-output only, -3 = CMYK / YCCK
+    int variant = -1;                      // KernelVariant, or -1 = generic colour path, -2 = planes-to-output only, -3 = CMYK / YCCK, -5 = scaled
+    // Scaled decode (hipjpegDecodeBatchSetScales): scale_k = libjpeg's min_DCT_scaled_size = 8 / denominator, 8 = full size; scaled_size[c] =
+    // component c's DCT_scaled_size.  pic_w x pic_h is the picture the pixel kernels write (the frame's size, or the scaled one): outputs,
+    // pitches and transforms are judged against it.  The entropy stage and the coefficient layout know nothing of the scale.
+    int scale_k = 8, scaled_size[4] = {8, 8, 8, 8};
+    int pic_w = 0, pic_h = 0;
     uint32_t coef_or[4] = {0, 0, 0, 0};    // OR of |coefficient| per component (from the entropy stage)
     uint32_t ac_bound[4] = {32768, 32768, 32768, 32768};  // upper bound of |AC coefficient| per component (packed IDCT pass 1 decision); default: any int16, -32768 included
     // GPU entropy decoding (flag HIPJPEG_FLAG_GPU_HUFFMAN and an eligible stream): the host only stages the scans
@@ -92,10 +97,11 @@ public:
 
     // Phase 0: parse headers, choose kernels, lay out staging memory.  Per-image problems land in statuses[i].
     // `formats` (optional) gives one output format per image; otherwise `format` applies to all.
+    // `scale_denoms` (optional) gives one denominator per image: 1 (full size), 2, 4 or 8; see hipjpegDecodeBatchSetScales.
     hipjpegStatus_t plan(const uint8_t* const* data, const size_t* lengths, int n, const hipjpegOutput_t* outputs,
                          hipjpegOutputFormat_t format, unsigned flags, hipjpegStatus_t* statuses,
                          const hipjpegOutputFormat_t* formats = nullptr, ForkJoinPool* pool = nullptr,
-                         const hipjpegTransform_t* transforms = nullptr);
+                         const hipjpegTransform_t* transforms = nullptr, const int32_t* scale_denoms = nullptr);
     // Lossless transcode (hipjpegTranscodeBatch): plans the entropy stage alone -- no outputs, no pixel kernels, no geometry; the
     // coefficients stay in HBM in the decoder's layout, host-decoded pictures as dense blocks.  Of `flags` only
     // HIPJPEG_FLAG_GPU_HUFFMAN counts.  Sources the coder cannot take (transcode_core.h transcode_picture) are UNSUPPORTED.
@@ -233,6 +239,8 @@ private:
     void merge_zero_fills();
     void unit_counts(bool plain, int32_t* plane, int32_t luma[kNumLumaLayouts]) const;
     UnitList plane_units_, luma_units_[kNumLumaLayouts][kNumLumaVariants], generic_units_, cmyk_units_, xform_units_;  // luma: [layout of K2][sampling]
+    // scaled images: components of DCT_scaled_size 8 have their units in plane_units_ (K1, kToPlane), the others here; then a unit per row
+    UnitList reduced_units_, scaled_color_units_;
     // Images of the GPU entropy stage (baseline): their K1 / K2 units go to the FUSED kernel builds, which Huffman-decode the blocks
     // themselves (decode_kernels.hip) -- same unit geometry.  host_taken_: such images the host entropy decoder took over in resolve()
     // (damaged / periodic streams): their coefficients then lie in HBM and the plain builds run for them (launch_taken_pixels).

@@ -42,7 +42,10 @@ struct alignas(16) DecodeComponent {
     // Where the DC coefficient of block b is.  Host entropy stage: inside the block (dc_stride == 64, dc unused); GPU entropy
     // stage: dc[b] in a compact plane of DC values (dc_stride == 1), position 0 of the blocks holds zero.
     const int16_t* dc;
-    uint32_t dc_stride, pad0;
+    uint32_t dc_stride;
+    // Scaled decode (hipjpegDecodeBatchSetScales): the component's DCT_scaled_size s = 8, 4, 2 or 1 -- every block gives s x s samples, the
+    // plane holds blocks_w * s x blocks_h * s of them and samp_w / samp_h are the component's size at the scale; 0 = full-size image
+    uint32_t scaled;
     // Zero-run-compressed staging (host entropy stage, entropy_decode.h): non-null = `coef` is the start of the picture's SPARSE stream and
     // block_off[b] the byte offset of block b's record in it (0 = all-zero block); null = dense blocks at coef + 64 b.
     const uint32_t* block_off;
@@ -60,7 +63,9 @@ struct alignas(16) DecodeImage {
     uint32_t width, height;
     uint32_t ncomp, hmax, vmax, color_model;  // color_model: hipjpeg::ColorModel
     uint32_t out_format, flags;
-    uint32_t huff_index, pad1[3];  // GPU entropy stage: index of the image's HuffImage (the FUSED kernels decode from it)
+    uint32_t huff_index;  // GPU entropy stage: index of the image's HuffImage (the FUSED kernels decode from it)
+    uint32_t scale_k;     // scaled decode: libjpeg's min_DCT_scaled_size = 8 / denominator (4, 2, 1); width / height are the scaled size.  0 = full size
+    uint32_t pad1[2];
 };
 
 // One workgroup's worth of work: 256 consecutive blocks (raster order) of one component of one image.
@@ -91,8 +96,9 @@ struct alignas(16) TransformImage {
     int32_t pad;
 };
 constexpr int kTransformRowsPerUnit = 8;
+constexpr int kScaledRowsPerUnit = 8;  // scaled_color_kernel: pixel rows per workgroup (a wave per row, two turns)
 
-constexpr int kBlocksPerUnit = 128;  // idct_plane_kernel: 256 lanes, two lanes per block
+constexpr int kBlocksPerUnit = 128;  // idct_plane_kernel, idct_reduced_plane_kernel: 256 lanes, two lanes per block
 constexpr int kLumaTileW = 32, kLumaTileH = 4;  // luma_color_kernel tile in blocks (one block row per wave)
 
 }  // namespace hipjpeg

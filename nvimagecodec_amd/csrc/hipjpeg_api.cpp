@@ -58,6 +58,14 @@ struct hipjpegHandle {
     DecodeBatch& cur() { return *batches[current]; }
     // pipelined submission (hipjpegDecodeBatchSubmit / Wait): pages in flight, oldest first, with the stream each runs on
     std::vector<hipjpegTransform_t> transforms;  // geometry for the next batch (hipjpegDecodeBatchSetTransforms)
+    std::vector<int32_t> scales;                 // scale denominators for the next batch (hipjpegDecodeBatchSetScales)
+    // the three batch calls that take no scales: pending ones are dropped and the call refused
+    bool drop_pending_scales()
+    {
+        const bool pending = !scales.empty();
+        scales.clear();
+        return pending;
+    }
     int submitted[kMaxPages] = {-1, -1, -1, -1, -1, -1, -1, -1};
     void* submitted_stream[kMaxPages] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int num_submitted = 0;
@@ -330,14 +338,16 @@ hipjpegStatus_t hipjpegDecodeBatchHost(hipjpegHandle_t handle, const uint8_t* co
     DecodeBatch& b = handle->cur();
     static const bool timing = getenv("HIPJPEG_DEBUG_TIMING") != nullptr;  // debug aid: host-stage phase times on stderr
     const auto t0 = std::chrono::steady_clock::now();
-    const bool geometry = !handle->transforms.empty();
-    if (geometry && (int)handle->transforms.size() != batch_size) {
+    const bool geometry = !handle->transforms.empty(), scaled = !handle->scales.empty();
+    if ((geometry && (int)handle->transforms.size() != batch_size) || (scaled && (int)handle->scales.size() != batch_size)) {
         handle->transforms.clear();
+        handle->scales.clear();
         return HIPJPEG_STATUS_INVALID_ARGUMENT;
     }
     hipjpegStatus_t st = b.plan(data, lengths, batch_size, outputs, format, flags, statuses, nullptr, handle->pool.get(),
-                                geometry ? handle->transforms.data() : nullptr);
+                                geometry ? handle->transforms.data() : nullptr, scaled ? handle->scales.data() : nullptr);
     handle->transforms.clear();
+    handle->scales.clear();
     if (st != HIPJPEG_STATUS_SUCCESS) return st;
     const auto t1 = std::chrono::steady_clock::now();
     handle->pool->parallel_for(batch_size, [&](int i, int) { b.entropy_stage(i); });
@@ -361,6 +371,31 @@ hipjpegStatus_t hipjpegDecodeBatchSetTransforms(hipjpegHandle_t handle, const hi
         handle->transforms.assign(transforms, transforms + batch_size);
     else
         handle->transforms.clear();
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+hipjpegStatus_t hipjpegDecodeBatchSetScales(hipjpegHandle_t handle, const int32_t* scale_denoms, int batch_size)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle || batch_size < 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (scale_denoms)
+        handle->scales.assign(scale_denoms, scale_denoms + batch_size);
+    else
+        handle->scales.clear();
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+hipjpegStatus_t hipjpegGetScaledImageSize(int32_t width, int32_t height, int32_t scale_denom, int32_t* scaled_width, int32_t* scaled_height)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (width <= 0 || height <= 0 || !scaled_width || !scaled_height) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (scale_denom != 1 && scale_denom != 2 && scale_denom != 4 && scale_denom != 8) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    // jdmaster.c jpeg_calc_output_dimensions: ceil(extent * k / 8) with k = 8 / denominator
+    const int64_t k = 8 / scale_denom;
+    *scaled_width = (int32_t)(((int64_t)width * k + 7) / 8);
+    *scaled_height = (int32_t)(((int64_t)height * k + 7) / 8);
     return HIPJPEG_STATUS_SUCCESS;
     });
 }
@@ -848,6 +883,7 @@ hipjpegStatus_t hipjpegTranscodeBatch(hipjpegHandle_t handle, const uint8_t* con
                                       const hipjpegTranscodeParams_t* params, unsigned flags, hipjpegStatus_t* statuses, void* stream)
 {
     return guarded([&]() -> hipjpegStatus_t {
+    if (handle && handle->drop_pending_scales()) return HIPJPEG_STATUS_INVALID_ARGUMENT;  // no scaled transcode
     if (!handle || batch_size < 0 || (batch_size > 0 && (!data || !lengths || !params))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     // the call takes a decode page and the encode batch for itself: nothing submitted may still be using either
     if (handle->num_submitted != 0 || handle->encode_in_flight != 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
@@ -933,6 +969,7 @@ hipjpegStatus_t hipjpegDecodeCoefficientsBatch(hipjpegHandle_t handle, const uin
                                                const hipjpegCoefficientPlanes_t* planes, unsigned flags, hipjpegStatus_t* statuses, void* stream)
 {
     return guarded([&]() -> hipjpegStatus_t {
+    if (handle && handle->drop_pending_scales()) return HIPJPEG_STATUS_INVALID_ARGUMENT;  // coefficients have no scale
     if (!handle || batch_size < 0 || (batch_size > 0 && (!data || !lengths || !planes))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     // the call takes the current decode page for itself: nothing submitted may still be using it
     if (handle->num_submitted != 0 || handle->encode_in_flight != 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;
@@ -1012,6 +1049,7 @@ hipjpegStatus_t hipjpegCoefficientsToPixelsBatch(hipjpegHandle_t handle, const h
     // the transforms belong to this batch alone, whatever becomes of it
     std::vector<hipjpegTransform_t> transforms;
     transforms.swap(handle->transforms);
+    if (handle->drop_pending_scales()) return HIPJPEG_STATUS_INVALID_ARGUMENT;  // scaling from coefficient tensors: not in this version
     if (batch_size < 0 || (batch_size > 0 && (!infos || !planes || !outputs))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     // the call takes the current decode page for itself: nothing submitted may still be using it
     if (handle->num_submitted != 0 || handle->encode_in_flight != 0) return HIPJPEG_STATUS_INVALID_ARGUMENT;

@@ -135,6 +135,10 @@ private:
     // (ifast_; HIPJPEG_FLAG_FAST_IDCT) and takes the samples; the named key wins over an unnamed one.
     bool fast_idct_ = false;
     bool ifast_ = false;
+    // scale_denom=N (1, 2, 4, 8): every sample is decoded at 1/N of its size (hipjpegDecodeBatchSetScales; libjpeg's scale_denom, the
+    // reference's UncompressFlags::ratio).  The caller's image then holds hipjpegGetScaledImageSize's picture.  Regions of the
+    // nvImageCodec ABI are in code-stream coordinates, so a sample with one is declined (ROI_UNSUPPORTED), as are raw planes.
+    int scale_denom_ = 1;
     bool ok_ = false;
     int device_ = 0;
     static constexpr int kJobPages = 6;  // batches (or pieces of one) in flight: each has its own page (arenas), stream and event; arenas are sized on first use
@@ -170,6 +174,7 @@ HipJpegDecoder::HipJpegDecoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgc
         else if (key == "gpu_progressive_intervals") v >> gpu_progressive_intervals_;
         else if (key == "pipeline_chunks") v >> pipeline_chunks_;
         else if (key == "hybrid_huffman_threshold") v >> hybrid_huffman_threshold_;
+        else if (key == "scale_denom") v >> scale_denom_;
         else if (key == "fast_idct" && named) {
             v >> named_fast_idct;
             named_fast_idct_given = true;
@@ -183,7 +188,11 @@ HipJpegDecoder::HipJpegDecoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgc
     // plugin of the chain and is passed over in silence, as the reference's plugins do)
     for (const std::string& k : unknown_keys_)
         if (std::find(addressed_keys_.begin(), addressed_keys_.end(), k) != addressed_keys_.end())
-            HJ_LOG_WARNING(fw_, kDecoderId, "unknown option '" << k << "' ignored (known: fancy_upsampling, gpu_huffman, gpu_progressive_intervals, hybrid_huffman_threshold, pipeline_chunks, fast_idct)");
+            HJ_LOG_WARNING(fw_, kDecoderId, "unknown option '" << k << "' ignored (known: fancy_upsampling, gpu_huffman, gpu_progressive_intervals, hybrid_huffman_threshold, pipeline_chunks, fast_idct, scale_denom)");
+    if (scale_denom_ != 1 && scale_denom_ != 2 && scale_denom_ != 4 && scale_denom_ != 8) {
+        HJ_LOG_WARNING(fw_, kDecoderId, "scale_denom=" << scale_denom_ << " ignored: the denominators are 1, 2, 4 and 8");
+        scale_denom_ = 1;
+    }
     if (fast_idct_)
         HJ_LOG_WARNING(fw_, kDecoderId, "fast_idct=1 without a module name: canDecode hands every sample to the next decoder of the chain; "
                                         "hipjpeg_decoder:fast_idct=1 decodes them here with the fast integer IDCT (libjpeg-turbo's JDCT_IFAST SIMD routine)");
@@ -367,6 +376,11 @@ void HipJpegDecoder::single_can_decode(nvimgcodecProcessingStatus_t* status, nvi
     const int geometry = sample_transform(info, cs_info, params, &t);
     if (geometry & 1) *status |= NVIMGCODEC_PROCESSING_STATUS_ROI_UNSUPPORTED;
     if (geometry & 2) *status |= NVIMGCODEC_PROCESSING_STATUS_ORIENTATION_UNSUPPORTED;
+    if (scale_denom_ != 1) {
+        // a region is in code-stream coordinates, the scaled decode takes it in scaled-picture ones; no raw planes at a scale
+        if (params->enable_roi && info.region.ndim > 0) *status |= NVIMGCODEC_PROCESSING_STATUS_ROI_UNSUPPORTED;
+        if (fmt_ok && fmt == HIPJPEG_OUTPUT_YUV_PLANAR) *status |= NVIMGCODEC_PROCESSING_STATUS_SAMPLE_FORMAT_UNSUPPORTED;
+    }
     if (!geometry && fmt_ok && fmt == HIPJPEG_OUTPUT_YUV_PLANAR && (t.orientation != 1 || t.x1 != 0)) {
         if (t.x1 != 0) *status |= NVIMGCODEC_PROCESSING_STATUS_ROI_UNSUPPORTED;
         if (t.orientation != 1) *status |= NVIMGCODEC_PROCESSING_STATUS_ORIENTATION_UNSUPPORTED;
@@ -601,6 +615,12 @@ nvimgcodecStatus_t HipJpegDecoder::decode_chunk(nvimgcodecCodeStreamDesc_t** cod
                 s.early_status = NVIMGCODEC_PROCESSING_STATUS_SAMPLE_FORMAT_UNSUPPORTED;
                 return;
             }
+            if (scale_denom_ != 1 && (formats[i] == HIPJPEG_OUTPUT_YUV_PLANAR || (params->enable_roi && info.region.ndim > 0))) {
+                // canDecode said so already (scale_denom_)
+                s.early_status = formats[i] == HIPJPEG_OUTPUT_YUV_PLANAR ? NVIMGCODEC_PROCESSING_STATUS_SAMPLE_FORMAT_UNSUPPORTED
+                                                                         : NVIMGCODEC_PROCESSING_STATUS_ROI_UNSUPPORTED;
+                return;
+            }
             if ((params->enable_roi && info.region.ndim > 0) || params->apply_exif_orientation) {
                 nvimgcodecImageInfo_t cs_info;
                 memset(&cs_info, 0, sizeof cs_info);
@@ -667,13 +687,14 @@ nvimgcodecStatus_t HipJpegDecoder::decode_chunk(nvimgcodecCodeStreamDesc_t** cod
             }
         }
 
+        const std::vector<int32_t> scales(scale_denom_ != 1 ? (size_t)n : 0, scale_denom_);
         const auto t_marshal = std::chrono::steady_clock::now();
         const bool planned = hipSetDevice(device_) == hipSuccess &&
                              job->batch.plan(data.data(), sizes.data(), n, outs.data(), HIPJPEG_OUTPUT_RGBI,
                                              (fancy_ ? HIPJPEG_FLAG_FANCY_UPSAMPLING : 0u) | (gpu_huffman_ ? HIPJPEG_FLAG_GPU_HUFFMAN : 0u) |
                                                  (ifast_ ? HIPJPEG_FLAG_FAST_IDCT : 0u) | (gpu_progressive_intervals_ ? HIPJPEG_FLAG_GPU_PROGRESSIVE_INTERVALS : 0u),
                                              job->statuses.data(), formats.data(), parse_pool_.get(),
-                                             any_geometry ? geometry.data() : nullptr) == HIPJPEG_STATUS_SUCCESS;
+                                             any_geometry ? geometry.data() : nullptr, scales.empty() ? nullptr : scales.data()) == HIPJPEG_STATUS_SUCCESS;
         if (!planned) throw std::runtime_error("could not plan the decode batch");
 
         // The caller's image descriptor must be able to hold what will be written: plane sizes and buffer_size against the

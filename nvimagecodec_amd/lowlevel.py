@@ -126,6 +126,45 @@ def _decode_flags(fancy, gpu_huffman, fast_idct, gpu_progressive_intervals=False
             (N.FLAG_GPU_PROGRESSIVE_INTERVALS if gpu_progressive_intervals else 0))
 
 
+def scaled_image_size(width, height, scale_denom):
+    """(width, height) of a picture decoded at 1 / scale_denom (1, 2, 4, 8): hipjpegGetScaledImageSize, host only."""
+    w, h = ctypes.c_int32(), ctypes.c_int32()
+    st = N.load().hipjpegGetScaledImageSize(int(width), int(height), int(scale_denom), ctypes.byref(w), ctypes.byref(h))
+    if st:
+        raise N.HipJpegError(st, "hipjpegGetScaledImageSize")
+    return w.value, h.value
+
+
+def output_shapes(jpegs, fmt="rgb", transforms=None, scales=None):
+    """The shapes BatchDecoder.allocate_outputs gives its tensors (host only): per image a shape, a list of plane shapes (yuv_planar),
+    or None for a file whose header cannot be read or whose scale denominator is none of 1, 2, 4, 8."""
+    shapes = []
+    for i, j in enumerate(jpegs):
+        try:
+            info = get_image_info(j)
+            h, w = info["height"], info["width"]
+            if scales is not None and scales[i] != 1:
+                w, h = scaled_image_size(w, h, scales[i])
+        except N.HipJpegError:
+            shapes.append(None)
+            continue
+        if transforms is not None and transforms[i] is not None:
+            roi, orientation = transforms[i]
+            if roi is not None:
+                w, h = roi[2] - roi[0], roi[3] - roi[1]
+            if orientation >= 5:
+                w, h = h, w
+        if fmt in ("rgb", "bgr"):
+            shapes.append((h, w, 3))
+        elif fmt in ("rgb_planar", "bgr_planar"):
+            shapes.append((3, h, w))
+        elif fmt == "y":
+            shapes.append((h, w))
+        else:  # (hipjpegOutput_t holds three planes: four-component frames have no raw planes and are declined)
+            shapes.append([(info["samp_h"][c], info["samp_w"][c]) for c in range(min(info["num_components"], 3))])
+    return shapes
+
+
 class BatchDecoder:
     """hipjpegCreate / hipjpegDecodeBatch* on one device."""
 
@@ -152,34 +191,21 @@ class BatchDecoder:
             pass
 
     # -- output allocation mirrors python/decoder.cpp:179-225 of the reference: I_RGB u8, row_stride = w*3
-    def allocate_outputs(self, jpegs, fmt="rgb", transforms=None):
+    def allocate_outputs(self, jpegs, fmt="rgb", transforms=None, scales=None):
         """transforms: optional list with one entry per image, None or (roi, orientation) with roi = (x0, y0, x1, y1) or
-        None and orientation = EXIF 1..8; the output then has the size of the region, turned upright."""
+        None and orientation = EXIF 1..8; the output then has the size of the region, turned upright.
+        scales: optional list with one denominator per image (1, 2, 4, 8): the picture then has hipjpegGetScaledImageSize's size, and a
+        region is in its coordinates."""
         torch = self._torch
         dev = torch.device("cuda", self.device)
         outs = []
-        for i, j in enumerate(jpegs):
-            try:
-                info = get_image_info(j)
-            except N.HipJpegError:
+        for shape in output_shapes(jpegs, fmt, transforms, scales):
+            if shape is None:
                 outs.append(None)
-                continue
-            h, w = info["height"], info["width"]
-            if transforms is not None and transforms[i] is not None:
-                roi, orientation = transforms[i]
-                if roi is not None:
-                    w, h = roi[2] - roi[0], roi[3] - roi[1]
-                if orientation >= 5:
-                    w, h = h, w
-            if fmt in ("rgb", "bgr"):
-                outs.append(torch.empty((h, w, 3), dtype=torch.uint8, device=dev))
-            elif fmt in ("rgb_planar", "bgr_planar"):
-                outs.append(torch.empty((3, h, w), dtype=torch.uint8, device=dev))
-            elif fmt == "y":
-                outs.append(torch.empty((h, w), dtype=torch.uint8, device=dev))
-            else:  # (hipjpegOutput_t holds three planes: four-component frames have no raw planes and are declined)
-                outs.append([torch.empty((info["samp_h"][c], info["samp_w"][c]), dtype=torch.uint8, device=dev)
-                             for c in range(min(info["num_components"], 3))])
+            elif isinstance(shape, list):
+                outs.append([torch.empty(s, dtype=torch.uint8, device=dev) for s in shape])
+            else:
+                outs.append(torch.empty(shape, dtype=torch.uint8, device=dev))
         return outs
 
     def _marshal(self, jpegs, outs, fmt):
@@ -234,16 +260,28 @@ class BatchDecoder:
         if st:
             raise N.HipJpegError(st, "hipjpegDecodeBatchSetTransforms")
 
+    def set_scales(self, scales, n):
+        """Scale denominators (1, 2, 4, 8) for the next batch, one per image; None clears them."""
+        if scales is None:
+            st = N.load().hipjpegDecodeBatchSetScales(self._h, None, 0)
+        else:
+            st = N.load().hipjpegDecodeBatchSetScales(self._h, (ctypes.c_int32 * n)(*[int(v) for v in scales]), n)
+        if st:
+            raise N.HipJpegError(st, "hipjpegDecodeBatchSetScales")
+
     def decode(self, jpegs, fmt="rgb", fancy=True, outs=None, stream=None, check=True, gpu_huffman=False, transforms=None, fast_idct=False,
-               gpu_progressive_intervals=False):
+               gpu_progressive_intervals=False, scales=None):
         """Full pipeline.  Returns (outputs, statuses).  gpu_huffman=True: entropy-decode eligible streams on the GPU.
         gpu_progressive_intervals=True (with gpu_huffman): progressive files whose scans all have restart intervals too, a lane per interval.
         fast_idct=True: the fast integer IDCT (JDCT_IFAST of libjpeg-turbo's x86-64 SIMD routine) instead of the default ISLOW one.
-        transforms: per-image (roi, orientation) or None -- region of interest and EXIF orientation applied on the device."""
+        transforms: per-image (roi, orientation) or None -- region of interest and EXIF orientation applied on the device.
+        scales: per-image denominator 1, 2, 4 or 8 -- decode at that fraction of the size (libjpeg's scale_denom)."""
         if outs is None:
-            outs = self.allocate_outputs(jpegs, fmt, transforms)
+            outs = self.allocate_outputs(jpegs, fmt, transforms, scales)
         if transforms is not None:
             self.set_transforms(transforms, len(jpegs))
+        if scales is not None:
+            self.set_scales(scales, len(scales))
         ptrs, lens, O, statuses = self._marshal(jpegs, outs, fmt)
         flags = _decode_flags(fancy, gpu_huffman, fast_idct, gpu_progressive_intervals)
         st = N.load().hipjpegDecodeBatch(self._h, ptrs, lens, len(jpegs), O, _FORMATS[fmt], flags, statuses, self._stream_ptr(stream))
@@ -287,7 +325,10 @@ class BatchDecoder:
         if st:
             raise N.HipJpegError(st, "hipjpegSetPipelineDepth")
 
-    def submit(self, jpegs, outs, fmt="rgb", fancy=True, stream=None, gpu_huffman=True, fast_idct=False, gpu_progressive_intervals=False):
+    def submit(self, jpegs, outs, fmt="rgb", fancy=True, stream=None, gpu_huffman=True, fast_idct=False, gpu_progressive_intervals=False,
+               scales=None):
+        if scales is not None:
+            self.set_scales(scales, len(scales))
         ptrs, lens, O, statuses = self._marshal(jpegs, outs, fmt)
         flags = _decode_flags(fancy, gpu_huffman, fast_idct, gpu_progressive_intervals)
         st = N.load().hipjpegDecodeBatchSubmit(self._h, ptrs, lens, len(jpegs), O, _FORMATS[fmt], flags, self._stream_ptr(stream))
@@ -309,7 +350,9 @@ class BatchDecoder:
         return statuses
 
     # -- the three phases separately (bench.py times device_stage with coefficients resident in HBM)
-    def host_stage(self, jpegs, outs, fmt="rgb", fancy=True, gpu_huffman=False, fast_idct=False, gpu_progressive_intervals=False):
+    def host_stage(self, jpegs, outs, fmt="rgb", fancy=True, gpu_huffman=False, fast_idct=False, gpu_progressive_intervals=False, scales=None):
+        if scales is not None:
+            self.set_scales(scales, len(scales))
         ptrs, lens, O, statuses = self._marshal(jpegs, outs, fmt)
         flags = _decode_flags(fancy, gpu_huffman, fast_idct, gpu_progressive_intervals)
         st = N.load().hipjpegDecodeBatchHost(self._h, ptrs, lens, len(jpegs), O, _FORMATS[fmt], flags, statuses)
