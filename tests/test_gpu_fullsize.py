@@ -90,7 +90,7 @@ def _strided(torch, h, w, ch, pitch, offset):
 @pytest.mark.parametrize("sub", ["420", "422", "444"])
 def test_generic_kernel_flavours_at_full_size(torch_mod, dec, shape, sub):
     """Everything that is NOT the COMMON flavour of the luma/colour kernel, at 1080p and 4K: BGR, planar RGB/BGR, an
-    interleaved output that is not 16-byte aligned (odd offset, odd pitch), luma only, raw YUV planes, and
+    interleaved output that is not 16-byte aligned (odd offset, odd pitch; every byte of the gap behind each row stays untouched), luma only, raw YUV planes, and
     fancy_upsampling=0 (against the oracle's replication path, which tests/golden/manifest_plain.json pins to the real library)."""
     torch = torch_mod
     w, h = shape
@@ -113,6 +113,10 @@ def test_generic_kernel_flavours_at_full_size(torch_mod, dec, shape, sub):
         torch.cuda.synchronize()
         assert np.array_equal(view.cpu().numpy(), rgb), gh
         assert int(buf[:3].min()) == 0xAB and int(buf[-200:].min()) == 0xAB
+        # ... and every byte that is not a pixel: the 7 bytes behind each row (a store past a row's end lands there), the lead, the tail
+        pitch = w * 3 + 7
+        gaps = torch.as_strided(buf, (h, 7), (pitch, 1), storage_offset=3 + w * 3)
+        assert bool((gaps == 0xAB).all()) and bool((buf[:3] == 0xAB).all()) and bool((buf[3 + h * pitch:] == 0xAB).all()), gh
         # replication instead of the triangle filter
         outs, _ = dec.decode([jpeg], fmt="rgb", fancy=False, gpu_huffman=gh)
         torch.cuda.synchronize()
