@@ -34,7 +34,8 @@ typedef enum {
     HIPJPEG_STATUS_SUCCESS = 0,
     HIPJPEG_STATUS_INVALID_ARGUMENT = 1,
     HIPJPEG_STATUS_BAD_JPEG = 2,         /* not a JPEG or malformed marker segment */
-    HIPJPEG_STATUS_UNSUPPORTED = 3,      /* valid JPEG outside this decoder's scope (arithmetic, 12-bit, CMYK, ...) */
+    HIPJPEG_STATUS_UNSUPPORTED = 3,      /* valid JPEG outside the entry point's scope (arithmetic, 12-bit DCT, hierarchical, ...; a lossless
+                                            frame anywhere but in the hipjpeg*Lossless* calls, and there one outside their rules) */
     HIPJPEG_STATUS_TRUNCATED = 4,        /* entropy-coded data ends early */
     HIPJPEG_STATUS_CORRUPT = 5,          /* invalid Huffman code / restart marker / coefficient index */
     HIPJPEG_STATUS_ALLOC_FAILED = 6,
@@ -582,6 +583,59 @@ HIPJPEG_API hipjpegStatus_t hipjpegPixelsToCoefficientsBatch(hipjpegHandle_t han
  * hipjpegPixelsToCoefficientsBatch) moved (the real blocks of every image that reached its kernel). */
 HIPJPEG_API hipjpegStatus_t hipjpegCoefficientsBatchStats(hipjpegHandle_t handle, int32_t* gpu_decoded_images, int32_t* gpu_coded_images,
                                                           int64_t* moved_blocks);
+
+/* ---------------------------------------------------------------- lossless JPEG (SOF3, Huffman): decoding
+ * Entry points of their own: every call above still answers HIPJPEG_STATUS_UNSUPPORTED for a lossless frame.  A frame is taken when
+ * its precision is 2..16, it has 1..4 components that all have h = v = 1, one scan holds them all, Ss (the predictor) is 1..7,
+ * Se = Ah = 0, Al (the point transform) < precision, every table the scan names is there and has no symbol above 16, and the
+ * restart interval is 0 or a multiple of the width.  A valid file outside these rules (subsampled components, a scan per component, a
+ * restart interval that is not whole rows) is UNSUPPORTED, a malformed one BAD_JPEG.
+ * The samples come out as stored: no colour conversion, no clamp.  A sample is the low 16 bits of state << Al, or its low 8 bits when
+ * precision <= 8 (libjpeg-turbo's jdlossls.c gives exactly these values). */
+typedef struct {
+    int32_t width, height, num_components;
+    int32_t precision;        /* 2..16 */
+    int32_t predictor;        /* Ss: 1..7 */
+    int32_t point_transform;  /* Al */
+    int32_t restart_rows;     /* rows per restart interval, 0 = none */
+    int32_t component_id[4];
+} hipjpegLosslessInfo_t;
+
+typedef struct {
+    void* plane[4];        /* planar: one pointer per component; interleaved: plane[0] only */
+    uint32_t pitch[4];     /* bytes per row; any value that holds a row, any alignment */
+    int32_t sample_bytes;  /* 2: uint16 samples; 1: uint8 samples, for precision <= 8 only (else the image is UNSUPPORTED) */
+    int32_t planar;        /* 0: H x W x N interleaved; 1: N planes of H x W */
+} hipjpegLosslessOutput_t;
+
+/* The reconstruction kernels' shape, for tests that place pictures on their seams: rows of a band and columns of an LDS tile of
+ * lossless_wavefront_kernel (predictors 2..7, one wave per component), samples of a row chunk of lossless_rows_kernel (predictor 1,
+ * one workgroup per row, a carried sum from chunk to chunk), and the width below which predictor 1 takes the wavefront kernel too. */
+typedef struct {
+    int32_t band_rows, tile_columns, chunk_samples, rows_min_width;
+} hipjpegLosslessKernelShape_t;
+HIPJPEG_API hipjpegStatus_t hipjpegLosslessKernelShape(hipjpegLosslessKernelShape_t* shape);
+
+HIPJPEG_API hipjpegStatus_t hipjpegGetLosslessInfo(const uint8_t* data, size_t length, hipjpegLosslessInfo_t* info);
+/* Entropy stage and reconstruction on the CPU, into host memory. */
+HIPJPEG_API hipjpegStatus_t hipjpegDecodeLosslessHost(const uint8_t* data, size_t length, const hipjpegLosslessOutput_t* output);
+/* The same result by the kernels' own schedule run on the host, lane by lane (bands, skew and tiles; column sums, chunks and carried
+ * sums).  kernel: 0 = the one the planner picks for this picture, 1 = lossless_rows_kernel (predictor 1 only, else INVALID_ARGUMENT),
+ * 2 = lossless_wavefront_kernel. */
+HIPJPEG_API hipjpegStatus_t hipjpegLosslessReconstructAlgorithmHost(const uint8_t* data, size_t length, const hipjpegLosslessOutput_t* output,
+                                                                    int kernel);
+/* Decodes a batch into device memory, asynchronously on `stream`: the entropy stage runs on the handle's host threads, the
+ * differences travel in one copy, the reconstruction kernels write the caller's layout.  statuses[i] is final on return; a failing
+ * image leaves its output untouched and does not disturb the others.  The outputs may be used once `stream` has reached this point. */
+HIPJPEG_API hipjpegStatus_t hipjpegDecodeLosslessBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
+                                                       const hipjpegLosslessOutput_t* outputs, hipjpegStatus_t* statuses, void* stream);
+/* Measurement aid, like hipjpegDecodeBatchDeviceKernel: queues one part of the handle's last hipjpegDecodeLosslessBatch again on `stream`
+ * (which: 0 = the host-to-device copy, 1 = the column sums and lossless_rows_kernel, 2 = lossless_wavefront_kernel).  The outputs of
+ * that batch must still exist; they are rewritten with the same samples. */
+HIPJPEG_API hipjpegStatus_t hipjpegDecodeLosslessBatchDeviceKernel(hipjpegHandle_t handle, int which, void* stream);
+/* Of the handle's last hipjpegDecodeLosslessBatch: images through lossless_rows_kernel, images through lossless_wavefront_kernel,
+ * bytes of the host-to-device copy. */
+HIPJPEG_API hipjpegStatus_t hipjpegDecodeLosslessBatchStats(hipjpegHandle_t handle, int32_t images_per_kernel[2], uint64_t* h2d_bytes);
 
 #ifdef __cplusplus
 }

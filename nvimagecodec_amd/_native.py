@@ -67,6 +67,22 @@ class CoefficientPlanes(ctypes.Structure):
     _fields_ = [("coef", ctypes.c_void_p * 4), ("pitch_blocks", ctypes.c_uint32 * 4)]
 
 
+class LosslessInfo(ctypes.Structure):
+    """hipjpegLosslessInfo_t"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("width", "height", "num_components", "precision", "predictor", "point_transform",
+                                              "restart_rows")] + [("component_id", ctypes.c_int32 * 4)]
+
+
+class LosslessOutput(ctypes.Structure):
+    """hipjpegLosslessOutput_t: interleaved (plane[0] only) or one plane per component; uint16 samples, or uint8 when precision <= 8"""
+    _fields_ = [("plane", ctypes.c_void_p * 4), ("pitch", ctypes.c_uint32 * 4), ("sample_bytes", ctypes.c_int32), ("planar", ctypes.c_int32)]
+
+
+class LosslessKernelShape(ctypes.Structure):
+    """hipjpegLosslessKernelShape_t"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("band_rows", "tile_columns", "chunk_samples", "rows_min_width")]
+
+
 CSS = {"444": 0, "422": 1, "420": 2, "440": 3, "411": 4, "410": 5, "gray": 6}
 
 
@@ -183,5 +199,12 @@ def load():
     L.hipjpegGetEncodeCoefficientInfo.argtypes = [i32, i32, ctypes.POINTER(EncodeParams), ctypes.POINTER(CoefficientInfo)]
     L.hipjpegPixelsToCoefficientsBatch.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.hipjpegCoefficientsBatchStats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)]
+    L.hipjpegLosslessKernelShape.argtypes = [ctypes.POINTER(LosslessKernelShape)]
+    L.hipjpegGetLosslessInfo.argtypes = [vp, sz, ctypes.POINTER(LosslessInfo)]
+    L.hipjpegDecodeLosslessHost.argtypes = [vp, sz, ctypes.POINTER(LosslessOutput)]
+    L.hipjpegLosslessReconstructAlgorithmHost.argtypes = [vp, sz, ctypes.POINTER(LosslessOutput), i32]
+    L.hipjpegDecodeLosslessBatch.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    L.hipjpegDecodeLosslessBatchDeviceKernel.argtypes = [vp, i32, vp]
+    L.hipjpegDecodeLosslessBatchStats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64)]
     _lib = L
     return L

@@ -33,6 +33,7 @@ COLORSPEC_UNCHANGED, COLORSPEC_SRGB, COLORSPEC_GRAY, COLORSPEC_SYCC, COLORSPEC_C
 BUFFER_KIND_STRIDED_DEVICE, BUFFER_KIND_STRIDED_HOST = 1, 2
 
 JPEG_ENCODING_BASELINE_DCT, JPEG_ENCODING_EXTENDED_SEQUENTIAL_DCT_HUFFMAN, JPEG_ENCODING_PROGRESSIVE_DCT_HUFFMAN = 0xC0, 0xC1, 0xC2
+JPEG_ENCODING_LOSSLESS_HUFFMAN = 0xC3
 
 BACKEND_KIND_CPU_ONLY, BACKEND_KIND_GPU_ONLY, BACKEND_KIND_HYBRID_CPU_GPU, BACKEND_KIND_HW_GPU_ONLY = 1, 2, 3, 4
 

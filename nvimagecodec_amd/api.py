@@ -104,9 +104,10 @@ def _api():
 class Image:
     """Decoded (or to-be-encoded) image: a uint8 HxWxC tensor on the GPU (torch) or on the host (numpy)."""
 
-    def __init__(self, array, buffer_kind):
+    def __init__(self, array, buffer_kind, precision=0):
         self._array = array
         self.buffer_kind = ImageBufferKind(buffer_kind)
+        self._precision = int(precision)
 
     @property
     def shape(self):
@@ -131,7 +132,8 @@ class Image:
 
     @property
     def precision(self):
-        return 0
+        """Significant bits per sample where they are fewer than the type's (a lossless decode of 2..16 bits into uint16); 0 = all of them"""
+        return self._precision
 
     @property
     def __cuda_array_interface__(self):
@@ -161,7 +163,7 @@ class Image:
     def cpu(self):
         if self.buffer_kind == ImageBufferKind.STRIDED_HOST:
             return self
-        return Image(self._array.cpu().numpy(), ImageBufferKind.STRIDED_HOST)
+        return Image(self._array.cpu().numpy(), ImageBufferKind.STRIDED_HOST, self._precision)
 
     def cuda(self, synchronize=True):
         if self.buffer_kind == ImageBufferKind.STRIDED_DEVICE:
@@ -337,7 +339,7 @@ class Decoder(_ExecMixin):
         lib, inst = _api()
         params = params or DecodeParams()
         n = len(sources)
-        keep, streams, images, outs = [], [], [], []
+        keep, streams, images, outs, precisions = [], [], [], [], []
         dev = torch.device("cuda", self.device_id)
         for kind, src in sources:
             cs = C.c_void_p()
@@ -351,10 +353,31 @@ class Decoder(_ExecMixin):
                 streams.append(None)
                 images.append(None)
                 outs.append(None)
+                precisions.append(0)
                 continue
-            info = A.init(A.ImageInfo, A.ST_IMAGE_INFO)
+            jpeg_info = A.init(A.JpegImageInfo, A.ST_JPEG_IMAGE_INFO)
+            info = A.init(A.ImageInfo, A.ST_IMAGE_INFO, struct_next=C.addressof(jpeg_info))
             _check(lib.nvimgcodecCodeStreamGetImageInfo(cs, C.byref(info)), "nvimgcodecCodeStreamGetImageInfo")
             h, w = info.plane_info[0].height, info.plane_info[0].width
+            if (jpeg_info.encoding == A.JPEG_ENCODING_LOSSLESS_HUFFMAN and params.allow_any_depth and params.color_spec == ColorSpec.UNCHANGED
+                    and h > 0 and w > 0):
+                # a lossless stream, asked for as stored and at its own depth: H x W x C uint16, the components untouched (the HIP decoder's
+                # lossless route; python/decoder.cpp:179-225 sizes the samples by allow_any_depth the same way)
+                ch = info.num_planes
+                t = torch.empty((h, w, ch), dtype=torch.uint16, device=dev)
+                out_info = A.ImageInfo()
+                _fill_image_info(out_info, h, w, ch, A.SAMPLEFORMAT_I_UNCHANGED, A.COLORSPEC_UNCHANGED, t.data_ptr(), t.stride(0) * 2,
+                                 A.BUFFER_KIND_STRIDED_DEVICE, cuda_stream or torch.cuda.current_stream(self.device_id).cuda_stream)
+                out_info.plane_info[0].sample_type = A.SAMPLE_DATA_TYPE_UINT16
+                out_info.plane_info[0].precision = info.plane_info[0].precision
+                out_info.orientation = info.orientation
+                im = C.c_void_p()
+                _check(lib.nvimgcodecImageCreate(inst, C.byref(im), C.byref(out_info)), "nvimgcodecImageCreate")
+                streams.append(cs)
+                images.append(im)
+                outs.append(t)
+                precisions.append(int(info.plane_info[0].precision))
+                continue
             if self._scale_denom != 1:  # the plugin decodes at 1 / scale_denom: ceil(extent * (8 / denominator) / 8)
                 k = 8 // self._scale_denom
                 h, w = (h * k + 7) // 8, (w * k + 7) // 8
@@ -375,6 +398,7 @@ class Decoder(_ExecMixin):
             streams.append(cs)
             images.append(im)
             outs.append(t)
+            precisions.append(0)
         valid = [i for i in range(n) if streams[i] is not None]
         _t1 = _t.perf_counter()
         results = [None] * n
@@ -394,7 +418,7 @@ class Decoder(_ExecMixin):
             # failed samples are dropped from the result list like the reference does (python/decoder.cpp:230-242): None here
             for k, i in enumerate(valid):
                 if st[k] == A.PS_SUCCESS:
-                    results[i] = Image(outs[i], ImageBufferKind.STRIDED_DEVICE)
+                    results[i] = Image(outs[i], ImageBufferKind.STRIDED_DEVICE, precisions[i])
         for i in valid:
             lib.nvimgcodecImageDestroy(images[i])
             lib.nvimgcodecCodeStreamDestroy(streams[i])

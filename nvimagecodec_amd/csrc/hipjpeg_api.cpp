@@ -14,6 +14,7 @@
 #include "entropy_decode.h"
 #include "gpu_huffman_encode.h"
 #include "gpu_huffman_host.h"
+#include "lossless_batch.h"
 #include "progressive_encode.h"
 #include "progressive_gpu_host.h"
 #include "thread_pool.h"
@@ -99,6 +100,7 @@ struct hipjpegHandle {
     // last of the four coefficient-tensor calls moved
     int32_t coefficients_gpu_decoded = 0, coefficients_gpu_coded = 0;
     int64_t coefficients_blocks = 0;
+    std::unique_ptr<LosslessBatch> lossless;  // hipjpegDecodeLosslessBatch: staging pages of its own, made at the first call
 };
 
 extern "C" {
@@ -1100,6 +1102,41 @@ hipjpegStatus_t hipjpegCoefficientsBatchStats(hipjpegHandle_t handle, int32_t* g
     if (gpu_decoded_images) *gpu_decoded_images = handle->coefficients_gpu_decoded;
     if (gpu_coded_images) *gpu_coded_images = handle->coefficients_gpu_coded;
     if (moved_blocks) *moved_blocks = handle->coefficients_blocks;
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+// ---------------------------------------------------------------- lossless JPEG
+// (hipjpegGetLosslessInfo / hipjpegDecodeLosslessHost / hipjpegLosslessReconstructAlgorithmHost: lossless_core.cpp, with the rules)
+hipjpegStatus_t hipjpegDecodeLosslessBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
+                                           const hipjpegLosslessOutput_t* outputs, hipjpegStatus_t* statuses, void* stream)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle || batch_size < 0 || (batch_size > 0 && (!data || !lengths || !outputs))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    if (!handle->lossless) handle->lossless.reset(new LosslessBatch(handle->device_id, &handle->hooks));
+    return handle->lossless->decode(data, lengths, batch_size, outputs, statuses, handle->pool.get(), (hipStream_t)stream);
+    });
+}
+
+hipjpegStatus_t hipjpegDecodeLosslessBatchDeviceKernel(hipjpegHandle_t handle, int which, void* stream)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle || !handle->lossless) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    return handle->lossless->relaunch(which, (hipStream_t)stream);
+    });
+}
+
+hipjpegStatus_t hipjpegDecodeLosslessBatchStats(hipjpegHandle_t handle, int32_t images_per_kernel[2], uint64_t* h2d_bytes)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (images_per_kernel) {
+        images_per_kernel[0] = handle->lossless ? handle->lossless->rows_images() : 0;
+        images_per_kernel[1] = handle->lossless ? handle->lossless->wavefront_images() : 0;
+    }
+    if (h2d_bytes) *h2d_bytes = handle->lossless ? handle->lossless->h2d_bytes() : 0;
     return HIPJPEG_STATUS_SUCCESS;
     });
 }

@@ -426,7 +426,8 @@ struct nvimgcodecCodeStream {
         if (ps != kParseOk && f.width == 0) {
             // not a JPEG (or a SOF type we cannot even read dimensions from)
             if (ps == kParseUnsupported && f.sof != 0) {
-                // arithmetic / lossless / 12-bit: still a jpeg code stream; dimensions unknown to this minimal parser
+                // arithmetic / hierarchical: still a jpeg code stream; dimensions unknown to this minimal parser (a lossless frame's
+                // are read: it goes on below like a 12-bit one)
                 strcpy(info.codec_name, "jpeg");
                 jpeg_info.encoding = (nvimgcodecJpegEncoding_t)f.sof;
                 has_jpeg_info = true;

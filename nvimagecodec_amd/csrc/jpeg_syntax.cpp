@@ -176,7 +176,8 @@ ParseStatus finish_frame(FrameInfo* f)
 
 }  // namespace
 
-ParseStatus parse_jpeg(const uint8_t* data, size_t size, FrameInfo* f, bool headers_only)
+namespace {
+ParseStatus parse_markers(const uint8_t* data, size_t size, FrameInfo* f, bool headers_only, bool lossless)
 {
     *f = FrameInfo();
     if (!data || size < 4 || data[0] != 0xFF || data[1] != 0xD8) return kParseBadStream;
@@ -284,12 +285,46 @@ ParseStatus parse_jpeg(const uint8_t* data, size_t size, FrameInfo* f, bool head
             got_sof = true;
             break;
         }
-        case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
-            // lossless / hierarchical / arithmetic: a different decoder's job
+        case 0xC3: {
+            // lossless Huffman: the frame header is read (size, precision 2..16, components), so that the header-only parse can
+            // report them; the DCT entry points still hear "unsupported", parse_lossless_jpeg goes on to the scan
+            f->sof = m;
+            if (got_sof || L < 8) return lossless ? kParseBadStream : kParseUnsupported;
+            const int precision = seg[0], height = be16(seg + 1), width = be16(seg + 3), ncomp = seg[5];
+            if (precision < 2 || precision > 16 || ncomp < 1 || ncomp > 4 || L != 8 + 3 * ncomp)
+                return lossless ? kParseBadStream : kParseUnsupported;
+            if (width == 0 || height == 0) return kParseUnsupported;  // DNL-defined height: not handled
+            f->precision = precision;
+            f->height = height;
+            f->width = width;
+            f->ncomp = ncomp;
+            for (int c = 0; c < ncomp; c++) {
+                Component& k = f->comp[c];
+                k.id = seg[6 + 3 * c];
+                k.h = seg[7 + 3 * c] >> 4;
+                k.v = seg[7 + 3 * c] & 15;
+                k.tq = seg[8 + 3 * c];
+                if (k.h > f->hmax) f->hmax = k.h;
+                if (k.v > f->vmax) f->vmax = k.v;
+            }
+            for (int c = 0; c < ncomp; c++) {
+                Component& k = f->comp[c];
+                if (k.h < 1 || k.h > 4 || k.v < 1 || k.v > 4) return lossless ? kParseBadStream : kParseUnsupported;
+                k.samp_w = (width * k.h + f->hmax - 1) / f->hmax;
+                k.samp_h = (height * k.v + f->vmax - 1) / f->vmax;
+            }
+            f->color = ncomp == 1 ? ColorModel::Gray : ColorModel::RGB;  // stored components, never converted
+            if (!lossless) return kParseUnsupported;
+            got_sof = true;
+            break;
+        }
+        case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
+            // hierarchical / arithmetic: a different decoder's job
             f->sof = m;
             return kParseUnsupported;
         case 0xDA: {
             if (!got_sof) return kParseBadStream;
+            if (lossless != (f->sof == 0xC3)) return kParseUnsupported;
             if (headers_only) return kParseOk;
             if (L < 8) return kParseBadStream;  // shortest SOS: one component; also keeps seg[0] inside the segment
             ScanHeader sc;
@@ -306,7 +341,7 @@ ParseStatus parse_jpeg(const uint8_t* data, size_t size, FrameInfo* f, bool head
                 sc.td[i] = seg[2 + 2 * i] >> 4;
                 sc.ta[i] = seg[2 + 2 * i] & 15;
                 if (sc.td[i] > 3 || sc.ta[i] > 3) return kParseBadStream;
-                if (!comp_q_latched[found]) {
+                if (!lossless && !comp_q_latched[found]) {
                     // jdinput.c latch_quant_tables: the table in force at the component's first scan sticks
                     int tq = f->comp[found].tq;
                     if (!qt_present[tq]) return kParseBadStream;
@@ -319,7 +354,10 @@ ParseStatus parse_jpeg(const uint8_t* data, size_t size, FrameInfo* f, bool head
             sc.se = seg[2 + 2 * sc.ncomp];
             sc.ah = seg[3 + 2 * sc.ncomp] >> 4;
             sc.al = seg[3 + 2 * sc.ncomp] & 15;
-            if (!f->progressive()) {
+            if (lossless) {
+                // Ss is the predictor, Al the point transform; what this decoder takes of them is lossless_core.cpp's business
+                if (sc.ah > 15 || sc.al > 15) return kParseBadStream;
+            } else if (!f->progressive()) {
                 sc.ss = 0;
                 sc.se = 63;
                 sc.ah = sc.al = 0;
@@ -356,6 +394,11 @@ ParseStatus parse_jpeg(const uint8_t* data, size_t size, FrameInfo* f, bool head
     if (!headers_only && f->scans.empty()) return kParseBadStream;
     return kParseOk;
 }
+}  // namespace
+
+ParseStatus parse_jpeg(const uint8_t* data, size_t size, FrameInfo* f, bool headers_only) { return parse_markers(data, size, f, headers_only, false); }
+
+ParseStatus parse_lossless_jpeg(const uint8_t* data, size_t size, FrameInfo* f, bool headers_only) { return parse_markers(data, size, f, headers_only, true); }
 
 // The sampling layout as the API names it (the reference's parser does the same from the SOF factors, src/parsers/jpeg.cpp:262-330).
 // ---------------------------------------------------------------------------------------------- EXIF orientation (APP1)

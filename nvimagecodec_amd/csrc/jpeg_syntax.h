@@ -17,7 +17,7 @@ enum class ColorModel : int { Gray = 0, YCbCr = 1, RGB = 2, CMYK = 3, YCCK = 4 }
 enum ParseStatus : int {
     kParseOk = 0,
     kParseBadStream = -1,    // not a JPEG / malformed segment
-    kParseUnsupported = -2,  // valid JPEG we do not decode (arithmetic, lossless, 12-bit, hierarchical)
+    kParseUnsupported = -2,  // valid JPEG we do not decode (arithmetic, 12-bit, hierarchical; lossless outside parse_lossless_jpeg)
     kParseTruncated = -3,
 };
 
@@ -55,7 +55,7 @@ constexpr size_t kScanChunkBytes = 16384;
 
 struct FrameInfo {
     int width = 0, height = 0, precision = 8, ncomp = 0;
-    int sof = 0;  // 0xC0 / 0xC1 / 0xC2
+    int sof = 0;  // 0xC0 / 0xC1 / 0xC2; 0xC3 from parse_lossless_jpeg
     int hmax = 1, vmax = 1, mcus_x = 0, mcus_y = 0;
     bool saw_jfif = false, saw_adobe = false;
     int adobe_transform = -1;
@@ -75,6 +75,11 @@ struct FrameInfo {
 
 // Parses every marker segment up to EOI (or end of data).  `headers_only` stops at the first SOS.
 ParseStatus parse_jpeg(const uint8_t* data, size_t size, FrameInfo* out, bool headers_only = false);
+
+// The same walk for a lossless Huffman frame (SOF3): precision 2..16, 1..4 components, no quantization tables; a scan's Ss is its
+// predictor and Al its point transform.  Any other frame type is kParseUnsupported here, as SOF3 is in parse_jpeg -- which still fills
+// width, height, precision and the components of a SOF3 frame before it says so.
+ParseStatus parse_lossless_jpeg(const uint8_t* data, size_t size, FrameInfo* out, bool headers_only = false);
 
 extern const uint8_t kZigzagNatural[64];  // zigzag index -> natural (row-major) position
 

@@ -28,6 +28,7 @@
 
 #include "decoder_core.h"
 #include "diagnostics.h"
+#include "lossless_batch.h"
 #include "plugin_common.h"
 #include "thread_pool.h"
 #include "plugin_objects.h"
@@ -115,6 +116,11 @@ private:
 
     void single_can_decode(nvimgcodecProcessingStatus_t* status, nvimgcodecCodeStreamDesc_t* cs, nvimgcodecImageDesc_t* image,
                            const nvimgcodecDecodeParams_t* params);
+    // lossless Huffman streams (SOF3): rules and route of their own (hipjpegDecodeLosslessBatch's machinery)
+    void lossless_can_decode(nvimgcodecProcessingStatus_t* status, const nvimgcodecImageInfo_t& cs_info, nvimgcodecImageDesc_t* image,
+                             const nvimgcodecDecodeParams_t* params);
+    void decode_lossless(nvimgcodecCodeStreamDesc_t** code_streams, nvimgcodecImageDesc_t** images, int batch_size,
+                         const nvimgcodecDecodeParams_t* params);
     static void host_task(int tid, int sample_idx, void* ctx);
     void issue(Job* job);      // last host task of a job: descriptors, H2D copy, kernels -- nothing here waits for the device
     void complete(Job* job);   // completion thread: device verdicts, user-stream ordering, imageReady, page release
@@ -149,6 +155,9 @@ private:
     // Header parsing of a batch (a marker walk through every file) runs on these threads inside decode(): the framework's
     // executor only takes per-sample tasks that report through imageReady, and the batch layout needs every header first.
     std::unique_ptr<hipjpeg::ForkJoinPool> parse_pool_;
+    std::unique_ptr<hipjpeg::LosslessBatch> lossless_;  // made by the first lossless sample
+    hipStream_t lossless_stream_ = nullptr;
+    hipEvent_t lossless_event_ = nullptr;
     std::mutex decode_mutex_;  // decode() may be entered from the framework's worker thread and from a fallback re-dispatch
     // Jobs whose device work is queued wait here for the completion thread: no executor thread ever blocks on the GPU, and
     // decode() has long returned when the verdicts of the GPU entropy stage arrive (the host future only means "host work
@@ -226,6 +235,13 @@ HipJpegDecoder::HipJpegDecoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgc
 
 HipJpegDecoder::~HipJpegDecoder()
 {
+    if (lossless_stream_) {
+        (void)hipSetDevice(device_);
+        (void)hipStreamSynchronize(lossless_stream_);
+        lossless_.reset();
+        if (lossless_event_) (void)hipEventDestroy(lossless_event_);
+        (void)hipStreamDestroy(lossless_stream_);
+    }
     for (auto& j : jobs_) {
         if (!j) continue;
         std::unique_lock<std::mutex> lk(j->m);
@@ -313,6 +329,10 @@ void HipJpegDecoder::single_can_decode(nvimgcodecProcessingStatus_t* status, nvi
         return;
     }
     const nvimgcodecJpegImageInfo_t* ji = find_in_chain<nvimgcodecJpegImageInfo_t>(cs_info.struct_next, NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO);
+    if (ji && ji->encoding == NVIMGCODEC_JPEG_ENCODING_LOSSLESS_HUFFMAN && scale_denom_ == 1) {
+        lossless_can_decode(status, cs_info, image, params);
+        return;
+    }
     if (ji && ji->encoding != NVIMGCODEC_JPEG_ENCODING_UNKNOWN && ji->encoding != NVIMGCODEC_JPEG_ENCODING_BASELINE_DCT &&
         ji->encoding != NVIMGCODEC_JPEG_ENCODING_EXTENDED_SEQUENTIAL_DCT_HUFFMAN && ji->encoding != NVIMGCODEC_JPEG_ENCODING_PROGRESSIVE_DCT_HUFFMAN) {
         *status = NVIMGCODEC_PROCESSING_STATUS_ENCODING_UNSUPPORTED;
@@ -421,6 +441,194 @@ void HipJpegDecoder::report(Job* job, int i, nvimgcodecProcessingStatus_t ps)
     if (ps != NVIMGCODEC_PROCESSING_STATUS_SUCCESS)
         HJ_LOG_WARNING(fw_, kDecoderId, "sample " << i << " not decoded, processing status 0x" << std::hex << ps);
     s.image->imageReady(s.image->instance, ps);
+}
+
+// Lossless Huffman streams, under the rules of the reference's lossless decoder (extensions/nvjpeg/lossless_decoder.cpp:82-103) widened
+// by what hipjpegDecodeLosslessBatch does: P_Y for one component, I_UNCHANGED and P_UNCHANGED for any number; UINT16 always and UINT8 for
+// precisions up to 8; the stored components, so no colour request but UNCHANGED (or GRAY for one component); no region, no turning.
+void HipJpegDecoder::lossless_can_decode(nvimgcodecProcessingStatus_t* status, const nvimgcodecImageInfo_t& cs_info, nvimgcodecImageDesc_t* image,
+                                         const nvimgcodecDecodeParams_t* params)
+{
+    *status = NVIMGCODEC_PROCESSING_STATUS_SUCCESS;
+    if (cs_info.num_planes < 1 || cs_info.plane_info[0].width == 0) {  // the header parse could not read the frame
+        *status = NVIMGCODEC_PROCESSING_STATUS_CODESTREAM_UNSUPPORTED;
+        return;
+    }
+    nvimgcodecImageInfo_t info;
+    memset(&info, 0, sizeof info);
+    info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
+    info.struct_size = sizeof info;
+    if (image->getImageInfo(image->instance, &info) != NVIMGCODEC_STATUS_SUCCESS) {
+        *status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+        return;
+    }
+    const uint32_t ncomp = cs_info.num_planes, precision = cs_info.plane_info[0].precision;
+    if (!(info.color_spec == NVIMGCODEC_COLORSPEC_UNCHANGED || (info.color_spec == NVIMGCODEC_COLORSPEC_GRAY && ncomp == 1)))
+        *status |= NVIMGCODEC_PROCESSING_STATUS_COLOR_SPEC_UNSUPPORTED;
+    switch (info.sample_format) {
+    case NVIMGCODEC_SAMPLEFORMAT_P_Y:
+        if (ncomp != 1) *status |= NVIMGCODEC_PROCESSING_STATUS_SAMPLE_FORMAT_UNSUPPORTED;
+        else if (info.num_planes != 1) *status |= NVIMGCODEC_PROCESSING_STATUS_NUM_PLANES_UNSUPPORTED;
+        else if (info.plane_info[0].num_channels != 1) *status |= NVIMGCODEC_PROCESSING_STATUS_NUM_CHANNELS_UNSUPPORTED;
+        break;
+    case NVIMGCODEC_SAMPLEFORMAT_I_UNCHANGED:
+        if (info.num_planes != 1) *status |= NVIMGCODEC_PROCESSING_STATUS_NUM_PLANES_UNSUPPORTED;
+        if (info.plane_info[0].num_channels != ncomp) *status |= NVIMGCODEC_PROCESSING_STATUS_NUM_CHANNELS_UNSUPPORTED;
+        break;
+    case NVIMGCODEC_SAMPLEFORMAT_P_UNCHANGED:
+        if (info.num_planes != ncomp) *status |= NVIMGCODEC_PROCESSING_STATUS_NUM_PLANES_UNSUPPORTED;
+        break;
+    default: *status |= NVIMGCODEC_PROCESSING_STATUS_SAMPLE_FORMAT_UNSUPPORTED;
+    }
+    for (uint32_t p = 0; p < info.num_planes && p < NVIMGCODEC_MAX_NUM_PLANES; ++p) {
+        const nvimgcodecSampleDataType_t t = info.plane_info[p].sample_type;
+        if (!(t == NVIMGCODEC_SAMPLE_DATA_TYPE_UINT16 || (t == NVIMGCODEC_SAMPLE_DATA_TYPE_UINT8 && precision <= 8)))
+            *status |= NVIMGCODEC_PROCESSING_STATUS_SAMPLE_TYPE_UNSUPPORTED;
+    }
+    if (params->enable_roi && info.region.ndim > 0) *status |= NVIMGCODEC_PROCESSING_STATUS_ROI_UNSUPPORTED;
+    if (params->apply_exif_orientation && (cs_info.orientation.rotated != 0 || cs_info.orientation.flip_x || cs_info.orientation.flip_y))
+        *status |= NVIMGCODEC_PROCESSING_STATUS_ORIENTATION_UNSUPPORTED;
+}
+
+// The lossless samples of a decode() call: the entropy stage runs here, on the header-parsing threads; the copy and the
+// reconstruction kernels are queued on a stream of this decoder, each consumer's stream is ordered behind them, and every sample
+// reports once.  A caller that insists on what canDecode declined gets the same verdict.
+void HipJpegDecoder::decode_lossless(nvimgcodecCodeStreamDesc_t** code_streams, nvimgcodecImageDesc_t** images, int batch_size,
+                                     const nvimgcodecDecodeParams_t* params)
+{
+    const int n = batch_size;
+    std::vector<nvimgcodecProcessingStatus_t> verdict((size_t)n, NVIMGCODEC_PROCESSING_STATUS_SUCCESS);
+    std::vector<bool> reported((size_t)n, false);
+    auto report_all = [&]() {
+        for (int i = 0; i < n; i++) {
+            if (reported[(size_t)i]) continue;
+            reported[(size_t)i] = true;
+            if (verdict[(size_t)i] != NVIMGCODEC_PROCESSING_STATUS_SUCCESS)
+                HJ_LOG_WARNING(fw_, kDecoderId, "lossless sample " << i << " not decoded, processing status 0x" << std::hex << verdict[(size_t)i]);
+            try {
+                images[i]->imageReady(images[i]->instance, verdict[(size_t)i]);
+            } catch (...) {
+            }
+        }
+    };
+    struct Input {
+        void* mapped = nullptr;
+        size_t size = 0;
+        std::vector<uint8_t> owned;
+        void* user_stream = nullptr;
+    };
+    std::vector<Input> inputs((size_t)n);
+    auto release = [&]() {
+        for (int i = 0; i < n; i++)
+            if (inputs[(size_t)i].mapped) {
+                nvimgcodecIoStreamDesc_t* io = code_streams[i]->io_stream;
+                io->unmap(io->instance, inputs[(size_t)i].mapped, inputs[(size_t)i].size);
+                inputs[(size_t)i].mapped = nullptr;
+            }
+    };
+    try {
+        std::vector<const uint8_t*> data((size_t)n, nullptr);
+        std::vector<size_t> sizes((size_t)n, 0);
+        std::vector<hipjpegLosslessOutput_t> outs((size_t)n);
+        memset(outs.data(), 0, sizeof(hipjpegLosslessOutput_t) * (size_t)n);
+        for (int i = 0; i < n; i++) {
+            nvimgcodecProcessingStatus_t& v = verdict[(size_t)i];
+            try {
+                nvimgcodecJpegImageInfo_t jpeg_info{NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO, sizeof(nvimgcodecJpegImageInfo_t), nullptr,
+                                                    NVIMGCODEC_JPEG_ENCODING_UNKNOWN};
+                nvimgcodecImageInfo_t cs_info, info;
+                memset(&cs_info, 0, sizeof cs_info);
+                cs_info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
+                cs_info.struct_size = sizeof cs_info;
+                cs_info.struct_next = &jpeg_info;
+                memset(&info, 0, sizeof info);
+                info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
+                info.struct_size = sizeof info;
+                if (code_streams[i]->getImageInfo(code_streams[i]->instance, &cs_info) != NVIMGCODEC_STATUS_SUCCESS ||
+                    images[i]->getImageInfo(images[i]->instance, &info) != NVIMGCODEC_STATUS_SUCCESS) {
+                    v = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+                    continue;
+                }
+                lossless_can_decode(&v, cs_info, images[i], params);
+                if (v != NVIMGCODEC_PROCESSING_STATUS_SUCCESS) continue;
+                if (info.buffer_kind != NVIMGCODEC_IMAGE_BUFFER_KIND_STRIDED_DEVICE || !info.buffer) {
+                    v = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+                    continue;
+                }
+                inputs[(size_t)i].user_stream = info.cuda_stream;
+                // the caller's planes: back to back inside `buffer`, each large enough for the picture
+                hipjpegLosslessOutput_t& o = outs[(size_t)i];
+                o.sample_bytes = info.plane_info[0].sample_type == NVIMGCODEC_SAMPLE_DATA_TYPE_UINT8 ? 1 : 2;
+                o.planar = info.sample_format == NVIMGCODEC_SAMPLEFORMAT_I_UNCHANGED ? 0 : 1;
+                uint8_t* p = static_cast<uint8_t*>(info.buffer);
+                size_t need = 0;
+                bool fits = true;
+                for (uint32_t pl = 0; pl < info.num_planes && pl < 4; pl++) {
+                    const nvimgcodecImagePlaneInfo_t& pi = info.plane_info[pl];
+                    if (pi.row_stride > 0xFFFFFFFFull || pi.width < cs_info.plane_info[0].width || pi.height < cs_info.plane_info[0].height) fits = false;
+                    o.plane[pl] = p;
+                    o.pitch[pl] = (uint32_t)pi.row_stride;
+                    p += pi.row_stride * pi.height;
+                    need += pi.row_stride * pi.height;
+                }
+                if (!fits || (info.buffer_size != 0 && info.buffer_size < need)) {
+                    v = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+                    continue;
+                }
+                nvimgcodecIoStreamDesc_t* io = code_streams[i]->io_stream;
+                size_t size = 0;
+                if (io->size(io->instance, &size) != NVIMGCODEC_STATUS_SUCCESS || size == 0) {
+                    v = NVIMGCODEC_PROCESSING_STATUS_IMAGE_CORRUPTED;
+                    continue;
+                }
+                void* mapped = nullptr;
+                if (io->map(io->instance, &mapped, 0, size) == NVIMGCODEC_STATUS_SUCCESS && mapped) {
+                    inputs[(size_t)i].mapped = mapped;
+                    data[(size_t)i] = static_cast<const uint8_t*>(mapped);
+                } else {
+                    inputs[(size_t)i].owned.resize(size);
+                    size_t got = 0;
+                    io->seek(io->instance, 0, SEEK_SET);
+                    if (io->read(io->instance, &got, inputs[(size_t)i].owned.data(), size) != NVIMGCODEC_STATUS_SUCCESS || got != size) {
+                        v = NVIMGCODEC_PROCESSING_STATUS_IMAGE_CORRUPTED;
+                        continue;
+                    }
+                    data[(size_t)i] = inputs[(size_t)i].owned.data();
+                }
+                inputs[(size_t)i].size = sizes[(size_t)i] = size;
+            } catch (...) {
+                v = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+                data[(size_t)i] = nullptr;
+            }
+        }
+        bool ok = hipSetDevice(device_) == hipSuccess;
+        if (ok && !lossless_stream_)
+            ok = hipStreamCreateWithFlags(&lossless_stream_, hipStreamNonBlocking) == hipSuccess &&
+                 hipEventCreateWithFlags(&lossless_event_, hipEventDisableTiming) == hipSuccess;
+        if (ok && !lossless_) lossless_.reset(new hipjpeg::LosslessBatch(device_, &hooks_));
+        std::vector<hipjpegStatus_t> statuses((size_t)n, HIPJPEG_STATUS_INTERNAL_ERROR);
+        // (samples declined above have no data: the batch calls them INVALID_ARGUMENT, their verdict stands)
+        if (ok) ok = lossless_->decode(data.data(), sizes.data(), n, outs.data(), statuses.data(), parse_pool_.get(), lossless_stream_) == HIPJPEG_STATUS_SUCCESS;
+        if (ok) ok = hipEventRecord(lossless_event_, lossless_stream_) == hipSuccess;
+        if (!ok && lossless_stream_) (void)hipStreamSynchronize(lossless_stream_);
+        release();
+        for (int i = 0; i < n; i++) {
+            nvimgcodecProcessingStatus_t& v = verdict[(size_t)i];
+            if (v != NVIMGCODEC_PROCESSING_STATUS_SUCCESS) continue;
+            v = ok ? to_processing_status(statuses[(size_t)i]) : (nvimgcodecProcessingStatus_t)NVIMGCODEC_PROCESSING_STATUS_FAIL;
+            // the consumer's stream must not run ahead of the decode
+            if (v == NVIMGCODEC_PROCESSING_STATUS_SUCCESS && hipStreamWaitEvent((hipStream_t)inputs[(size_t)i].user_stream, lossless_event_, 0) != hipSuccess)
+                v = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+        }
+    } catch (...) {
+        if (lossless_stream_) (void)hipStreamSynchronize(lossless_stream_);
+        try {
+            release();
+        } catch (...) {
+        }
+        for (int i = 0; i < n; i++) verdict[(size_t)i] = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+    }
+    report_all();
 }
 
 void HipJpegDecoder::release_job(Job* job)
@@ -540,6 +748,47 @@ nvimgcodecStatus_t HipJpegDecoder::decode(nvimgcodecCodeStreamDesc_t** code_stre
     if (!code_streams || !images || !params) return NVIMGCODEC_STATUS_EXTENSION_INVALID_PARAMETER;
     if (batch_size < 1) return NVIMGCODEC_STATUS_INVALID_PARAMETER;
     std::lock_guard<std::mutex> serial(decode_mutex_);
+    // lossless Huffman samples take their own route; the others (all of them, in the everyday batch) go on as before
+    std::vector<nvimgcodecCodeStreamDesc_t*> lossless_streams, other_streams;
+    std::vector<nvimgcodecImageDesc_t*> lossless_images, other_images;
+    if (scale_denom_ == 1 && !fast_idct_) {
+        for (int i = 0; i < batch_size; i++) {
+            bool lossless = false;
+            try {
+                nvimgcodecJpegImageInfo_t jpeg_info{NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO, sizeof(nvimgcodecJpegImageInfo_t), nullptr,
+                                                    NVIMGCODEC_JPEG_ENCODING_UNKNOWN};
+                nvimgcodecImageInfo_t cs_info;
+                memset(&cs_info, 0, sizeof cs_info);
+                cs_info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
+                cs_info.struct_size = sizeof cs_info;
+                cs_info.struct_next = &jpeg_info;
+                if (code_streams[i] && code_streams[i]->getImageInfo(code_streams[i]->instance, &cs_info) == NVIMGCODEC_STATUS_SUCCESS) {
+                    const nvimgcodecJpegImageInfo_t* ji = find_in_chain<nvimgcodecJpegImageInfo_t>(cs_info.struct_next, NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO);
+                    lossless = ji && ji->encoding == NVIMGCODEC_JPEG_ENCODING_LOSSLESS_HUFFMAN;
+                }
+            } catch (...) {
+                lossless = false;
+            }
+            if (lossless && lossless_streams.empty()) {
+                other_streams.assign(code_streams, code_streams + i);
+                other_images.assign(images, images + i);
+            }
+            if (lossless) {
+                lossless_streams.push_back(code_streams[i]);
+                lossless_images.push_back(images[i]);
+            } else if (!lossless_streams.empty()) {
+                other_streams.push_back(code_streams[i]);
+                other_images.push_back(images[i]);
+            }
+        }
+    }
+    if (!lossless_streams.empty()) {
+        decode_lossless(lossless_streams.data(), lossless_images.data(), (int)lossless_streams.size(), params);
+        if (other_streams.empty()) return NVIMGCODEC_STATUS_SUCCESS;
+        code_streams = other_streams.data();
+        images = other_images.data();
+        batch_size = (int)other_streams.size();
+    }
     int chunks = pipeline_chunks_ > 0 ? pipeline_chunks_ : (batch_size >= 192 ? 3 : batch_size >= 96 ? 2 : 1);
     if (pipeline_chunks_ <= 0) {
         // a caller that keeps several decode() calls outstanding already has what the pieces are for -- the host stage and copy of

@@ -1134,3 +1134,162 @@ class BatchCoefficients:
         N.load().hipjpegCoefficientsBatchStats(self._h, ctypes.byref(d), ctypes.byref(c), ctypes.byref(b))
         return dict(gpu_decoded_images=d.value, gpu_coded_images=c.value, moved_blocks=b.value,
                     interval_takeovers=int(N.load().hipjpegDecodeBatchIntervalTakeovers(self._h)))
+
+
+# ---------------------------------------------------------------------------------------------- lossless JPEG (SOF3)
+def lossless_kernel_shape():
+    """hipjpegLosslessKernelShape: the seams of the two reconstruction kernels, as a dict"""
+    k = N.LosslessKernelShape()
+    st = N.load().hipjpegLosslessKernelShape(ctypes.byref(k))
+    if st:
+        raise N.HipJpegError(st, "hipjpegLosslessKernelShape")
+    return {n: getattr(k, n) for n, _ in N.LosslessKernelShape._fields_}
+
+
+def lossless_info(data):
+    """hipjpegGetLosslessInfo as a dict: width, height, num_components, precision, predictor, point_transform, restart_rows,
+    component_id.  Raises HipJpegError (UNSUPPORTED: not a lossless frame, or one outside the rules; BAD_JPEG; TRUNCATED)."""
+    arr = _as_u8(data)
+    li = N.LosslessInfo()
+    st = N.load().hipjpegGetLosslessInfo(arr.ctypes.data, arr.size, ctypes.byref(li))
+    if st:
+        raise N.HipJpegError(st, "hipjpegGetLosslessInfo")
+    d = {n: getattr(li, n) for n in ("width", "height", "num_components", "precision", "predictor", "point_transform", "restart_rows")}
+    d["component_id"] = list(li.component_id)[:li.num_components]
+    return d
+
+
+def _lossless_host_output(info, dtype, planar):
+    h, w, n = info["height"], info["width"], info["num_components"]
+    out = np.zeros((n, h, w) if planar else (h, w, n), dtype=dtype)
+    o = N.LosslessOutput()
+    o.sample_bytes = out.itemsize
+    o.planar = 1 if planar else 0
+    for c in range(n if planar else 1):
+        o.plane[c] = out.ctypes.data + (c * h * w * out.itemsize if planar else 0)
+        o.pitch[c] = w * out.itemsize * (1 if planar else n)
+    return out, o
+
+
+def decode_lossless_host(data, dtype=np.uint16, planar=False, algorithm=None):
+    """hipjpegDecodeLosslessHost (algorithm=None) or hipjpegLosslessReconstructAlgorithmHost (algorithm = 0: the planner's kernel,
+    1: the rows kernel's schedule, 2: the wavefront kernel's): an H x W x N array (N x H x W when planar) of uint16, or of uint8 for
+    files of precision <= 8."""
+    arr = _as_u8(data)
+    info = lossless_info(arr)
+    out, o = _lossless_host_output(info, np.dtype(dtype), planar)
+    L = N.load()
+    if algorithm is None:
+        st, what = L.hipjpegDecodeLosslessHost(arr.ctypes.data, arr.size, ctypes.byref(o)), "hipjpegDecodeLosslessHost"
+    else:
+        st, what = (L.hipjpegLosslessReconstructAlgorithmHost(arr.ctypes.data, arr.size, ctypes.byref(o), int(algorithm)),
+                    "hipjpegLosslessReconstructAlgorithmHost")
+    if st:
+        raise N.HipJpegError(st, what)
+    return out
+
+
+class BatchLosslessDecoder:
+    """hipjpegDecodeLosslessBatch on one device: lossless JPEG files (SOF3, 2..16 bit, predictors 1..7) to torch tensors of the stored
+    samples, uint16 (or uint8 for files of precision <= 8), H x W x N or N x H x W.  The entropy stage runs on host threads; prediction
+    runs on the GPU."""
+
+    def __init__(self, device=0, num_threads=0):
+        import torch
+        self._torch = torch
+        self.device = int(device)
+        self._h = ctypes.c_void_p()
+        st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
+        if st:
+            raise N.HipJpegError(st, "hipjpegCreate")
+
+    def close(self):
+        if self._h:
+            N.load().hipjpegDestroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream_ptr(self, stream):
+        s = stream if stream is not None else self._torch.cuda.current_stream(self.device)
+        return ctypes.c_void_p(s.cuda_stream)
+
+    def allocate(self, info, dtype=None, planar=False):
+        torch = self._torch
+        dtype = dtype or torch.uint16
+        h, w, n = info["height"], info["width"], info["num_components"]
+        return torch.empty((n, h, w) if planar else (h, w, n), dtype=dtype, device=torch.device("cuda", self.device))
+
+    def output(self, tensor, info, planar=False):
+        """hipjpegLosslessOutput_t over a tensor on this device: uint16 or uint8, [H, W, N] (or [N, H, W] when planar) with the last
+        dimension(s) of a row contiguous; the row stride is the pitch, and the tensor may start at any byte."""
+        torch = self._torch
+        if not isinstance(tensor, torch.Tensor) or tensor.device.type != "cuda" or tensor.device.index != self.device:
+            raise TypeError(f"lossless output must be a tensor on cuda:{self.device}")
+        if tensor.dtype not in (torch.uint16, torch.uint8) or tensor.dim() != 3:
+            raise TypeError("lossless output must be a uint16 or uint8 tensor of three dimensions")
+        h, w, n = info["height"], info["width"], info["num_components"]
+        size = tensor.element_size()
+        o = N.LosslessOutput()
+        o.sample_bytes = size
+        o.planar = 1 if planar else 0
+        if planar:
+            if tuple(tensor.shape) != (n, h, w) or tensor.stride(2) != 1 or tensor.stride(1) < w:
+                raise TypeError(f"planar lossless output must be [{n}, {h}, {w}] with contiguous rows")
+            for c in range(n):
+                o.plane[c] = tensor.data_ptr() + c * tensor.stride(0) * size
+                o.pitch[c] = tensor.stride(1) * size
+        else:
+            if tuple(tensor.shape) != (h, w, n) or tensor.stride(2) != 1 or tensor.stride(1) != n or tensor.stride(0) < w * n:
+                raise TypeError(f"interleaved lossless output must be [{h}, {w}, {n}] with contiguous rows")
+            o.plane[0] = tensor.data_ptr()
+            o.pitch[0] = tensor.stride(0) * size
+        return o
+
+    def decode(self, jpegs, dtype=None, planar=False, outs=None, raw_outputs=None, stream=None):
+        """Returns (statuses, tensors): tensors[i] is None where statuses[i] != 0 and no tensor was given.  Queued on `stream` (default:
+        the current one).  outs: per image None or a tensor to fill (see output()); raw_outputs: per image None or a ready
+        N.LosslessOutput (any pitch, any byte offset) that takes the place of a tensor."""
+        n = len(jpegs)
+        arrs = [_as_u8(j) for j in jpegs]
+        ptrs = (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
+        lens = (ctypes.c_size_t * n)(*[a.size for a in arrs])
+        O = (N.LosslessOutput * max(n, 1))()
+        tensors = []
+        for i, a in enumerate(arrs):
+            if raw_outputs is not None and raw_outputs[i] is not None:
+                O[i] = raw_outputs[i]
+                tensors.append(None)
+                continue
+            try:
+                info = lossless_info(a)
+            except N.HipJpegError:
+                tensors.append(None)  # the batch call reports why; the output stays null and is never looked at
+                continue
+            t = outs[i] if outs is not None and outs[i] is not None else self.allocate(info, dtype, planar)
+            O[i] = self.output(t, info, planar)
+            tensors.append(t)
+        statuses = (ctypes.c_int * n)()
+        st = N.load().hipjpegDecodeLosslessBatch(self._h, ptrs, lens, n, O, statuses, self._stream_ptr(stream))
+        if st:
+            raise N.HipJpegError(st, "hipjpegDecodeLosslessBatch")
+        given = outs if outs is not None else [None] * n
+        return list(statuses), [tensors[i] if statuses[i] == 0 or given[i] is not None else None for i in range(n)]
+
+    def device_stage(self, which, stream=None):
+        """hipjpegDecodeLosslessBatchDeviceKernel: one part of the last decode() again (0 upload, 1 rows kernels, 2 wavefront kernel)"""
+        st = N.load().hipjpegDecodeLosslessBatchDeviceKernel(self._h, int(which), self._stream_ptr(stream))
+        if st:
+            raise N.HipJpegError(st, "hipjpegDecodeLosslessBatchDeviceKernel")
+
+    def stats(self):
+        k = (ctypes.c_int32 * 2)()
+        b = ctypes.c_uint64()
+        st = N.load().hipjpegDecodeLosslessBatchStats(self._h, k, ctypes.byref(b))
+        if st:
+            raise N.HipJpegError(st, "hipjpegDecodeLosslessBatchStats")
+        return {"rows_images": k[0], "wavefront_images": k[1], "h2d_bytes": b.value}
