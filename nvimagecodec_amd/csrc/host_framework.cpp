@@ -34,6 +34,7 @@
 #include "../../include/nvimgcodec_abi.h"
 #include "../../include/hipjpeg.h"
 #include "jpeg_syntax.h"
+#include "plugin_common.h"
 
 using namespace hipjpeg;
 
@@ -420,9 +421,7 @@ struct nvimgcodecCodeStream {
         }
         FrameInfo f;
         ParseStatus ps = parse_jpeg(p, n, &f, /*headers_only=*/true);
-        memset(&info, 0, sizeof info);
-        info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
-        info.struct_size = sizeof info;
+        hipjpeg_ext::init_info(&info);
         if (ps != kParseOk && f.width == 0) {
             // not a JPEG (or a SOF type we cannot even read dimensions from)
             if (ps == kParseUnsupported && f.sof != 0) {

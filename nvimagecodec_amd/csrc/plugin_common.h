@@ -1,5 +1,6 @@
 // plugin_common.h -- helpers shared by the nvImageCodec plugin objects of this extension.
 #pragma once
+#include <cstring>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -82,6 +83,24 @@ inline T* find_in_chain(void* next, nvimgcodecStructureType_t type)
     Head* h = static_cast<Head*>(next);
     while (h && h->struct_type != type) h = static_cast<Head*>(h->struct_next);
     return reinterpret_cast<T*>(h);
+}
+
+// An image info struct as getImageInfo wants to be handed one: zeroed, typed, sized, `next` chained behind it.
+inline void init_info(nvimgcodecImageInfo_t* info, void* next = nullptr)
+{
+    memset(info, 0, sizeof *info);
+    info->struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
+    info->struct_size = sizeof *info;
+    info->struct_next = next;
+}
+
+// What a code stream says it is: its image info with the JPEG info struct chained behind it (encoding UNKNOWN where the stream fills none).
+inline nvimgcodecStatus_t stream_info(nvimgcodecCodeStreamDesc_t* cs, nvimgcodecImageInfo_t* cs_info, nvimgcodecJpegImageInfo_t* jpeg_info)
+{
+    *jpeg_info = nvimgcodecJpegImageInfo_t{NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO, sizeof(nvimgcodecJpegImageInfo_t), nullptr,
+                                           NVIMGCODEC_JPEG_ENCODING_UNKNOWN};
+    init_info(cs_info, jpeg_info);
+    return cs->getImageInfo(cs->instance, cs_info);
 }
 
 }  // namespace hipjpeg_ext

@@ -7,7 +7,7 @@
 //   * canDecode() fills every status; acceptance rules follow cuda_decoder.cpp:52-122 minus what this decoder hands
 //     to the fallback chain (12-bit, arithmetic coding, regions that leave the image)
 //   * decode() is asynchronous and calls imageReady exactly once per sample; the user's stream is ordered after our
-//     work with an event before imageReady(SUCCESS) (cuda_decoder.cpp:552-558)
+//     work with an event before imageReady says SUCCESS (cuda_decoder.cpp:552-558)
 // What is different by design: the reference issues one nvJPEG device call per image from per-thread streams; here the
 // executor threads only run the Huffman host stage, and the last one to finish issues ONE H2D copy and ONE launch per
 // kernel for the whole batch (three job pages rotate so the next batch's -- or the next piece's -- host stage and H2D copy
@@ -83,21 +83,28 @@ public:
                               const nvimgcodecDecodeParams_t* params);
 
 private:
-    nvimgcodecStatus_t decode_chunk(nvimgcodecCodeStreamDesc_t** code_streams, nvimgcodecImageDesc_t** images, int batch_size,
-                                    const nvimgcodecDecodeParams_t* params);
+    // What decode() learns from the code stream, in one getImageInfo per sample per call; both routes work from these.
+    struct StreamFacts {
+        bool known = false;     // the code stream answered
+        bool lossless = false;  // LOSSLESS_HUFFMAN (SOF3)
+        uint32_t width = 0, height = 0, ncomp = 0, precision = 0;
+        nvimgcodecOrientation_t orientation{};
+        bool frame_read() const { return ncomp >= 1 && width != 0; }  // the header parse could read the frame
+    };
     struct Sample {
         nvimgcodecCodeStreamDesc_t* code_stream = nullptr;
         nvimgcodecImageDesc_t* image = nullptr;
+        StreamFacts stream;
         void* user_stream = nullptr;
         const uint8_t* data = nullptr;
         size_t size = 0;
         void* mapped = nullptr;           // non-null if io_stream->map succeeded (must be unmapped)
         std::vector<uint8_t> owned;       // bitstream copy when map() is not available
-        nvimgcodecProcessingStatus_t early_status = NVIMGCODEC_PROCESSING_STATUS_SUCCESS;  // set when the sample is rejected before planning
+        nvimgcodecProcessingStatus_t early_status = NVIMGCODEC_PROCESSING_STATUS_SUCCESS;  // set when the sample is rejected before its batch runs
         bool reported = false;            // imageReady has been called (exactly once per sample, whatever happens)
         // what the caller's image descriptor says it can hold
-        uint32_t nplanes = 0, plane_w[3] = {0, 0, 0}, plane_h[3] = {0, 0, 0};
-        size_t buffer_size = 0, buffer_needed = 0;
+        uint32_t nplanes = 0, plane_w[4] = {0, 0, 0, 0}, plane_h[4] = {0, 0, 0, 0};
+        size_t buffer_size = 0;
     };
     struct Job {
         explicit Job(int device, const MemoryHooks* hooks) : batch(device, hooks) {}
@@ -117,16 +124,23 @@ private:
     void single_can_decode(nvimgcodecProcessingStatus_t* status, nvimgcodecCodeStreamDesc_t* cs, nvimgcodecImageDesc_t* image,
                            const nvimgcodecDecodeParams_t* params);
     // lossless Huffman streams (SOF3): rules and route of their own (hipjpegDecodeLosslessBatch's machinery)
-    void lossless_can_decode(nvimgcodecProcessingStatus_t* status, const nvimgcodecImageInfo_t& cs_info, nvimgcodecImageDesc_t* image,
+    bool lossless_route(const StreamFacts& f) const { return f.lossless && scale_denom_ == 1 && !fast_idct_; }
+    void lossless_can_decode(nvimgcodecProcessingStatus_t* status, const StreamFacts& stream, const nvimgcodecImageInfo_t& info,
                              const nvimgcodecDecodeParams_t* params);
-    void decode_lossless(nvimgcodecCodeStreamDesc_t** code_streams, nvimgcodecImageDesc_t** images, int batch_size,
-                         const nvimgcodecDecodeParams_t* params);
+    void decode_lossless(std::vector<Sample>& samples, const nvimgcodecDecodeParams_t* params);
+    nvimgcodecStatus_t decode_chunk(const Sample* samples, int batch_size, const nvimgcodecDecodeParams_t* params);
+    // the steps both routes take with a sample; the bool ones return false with early_status set
+    static StreamFacts stream_facts(const nvimgcodecImageInfo_t& cs_info);
+    bool read_image(Sample& s, nvimgcodecImageInfo_t* info);
+    static bool caller_planes(const nvimgcodecImageInfo_t& info, uint32_t max_planes, Sample& s, void** plane, uint32_t* pitch);
+    static bool fits(const Sample& s, const uint32_t* pitch, int planes, const int* pw, const int* ph);
+    static bool fetch_bitstream(Sample& s);
+    static void release_inputs(std::vector<Sample>& samples);
+    void report(Sample& s, int i, nvimgcodecProcessingStatus_t ps, const char* what = "sample");
     static void host_task(int tid, int sample_idx, void* ctx);
     void issue(Job* job);      // last host task of a job: descriptors, H2D copy, kernels -- nothing here waits for the device
     void complete(Job* job);   // completion thread: device verdicts, user-stream ordering, imageReady, page release
-    void report(Job* job, int i, nvimgcodecProcessingStatus_t ps);
     void release_job(Job* job);
-    void release_inputs(Job* job);
     void completion_loop();
 
     const nvimgcodecFrameworkDesc_t* fw_;
@@ -268,14 +282,12 @@ HipJpegDecoder::~HipJpegDecoder()
 // one of the eight EXIF ones; *t = the transform to apply (x1 == 0: whole image, orientation 1: as stored).
 // nvimgcodecOrientation_t <-> EXIF: reference src/parsers/exif_orientation.h:36-57 (rotated counts counter-clockwise there)
 // and extensions/nvjpeg/type_convert.cpp:43-64; region = {start (y, x), end (y, x)}: cuda_decoder.cpp:469-476.
-static int sample_transform(const nvimgcodecImageInfo_t& info, const nvimgcodecImageInfo_t& cs_info, const nvimgcodecDecodeParams_t* params,
-                            hipjpegTransform_t* t)
+static int sample_transform(const nvimgcodecImageInfo_t& info, int W, int H, const nvimgcodecDecodeParams_t* params, hipjpegTransform_t* t)
 {
     *t = hipjpegTransform_t{0, 0, 0, 0, 1};
     int bad = 0;
     if (params->enable_roi && info.region.ndim > 0) {
         const nvimgcodecRegion_t& r = info.region;
-        const int W = (int)cs_info.plane_info[0].width, H = (int)cs_info.plane_info[0].height;
         if (r.ndim != 2 || r.start[0] < 0 || r.start[1] < 0 || r.end[0] > H || r.end[1] > W || r.end[0] <= r.start[0] || r.end[1] <= r.start[1]) {
             bad |= 1;
         } else {
@@ -313,14 +325,9 @@ void HipJpegDecoder::single_can_decode(nvimgcodecProcessingStatus_t* status, nvi
         *status = NVIMGCODEC_PROCESSING_STATUS_BACKEND_UNSUPPORTED;
         return;
     }
-    nvimgcodecJpegImageInfo_t jpeg_info{NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO, sizeof(nvimgcodecJpegImageInfo_t), nullptr,
-                                        NVIMGCODEC_JPEG_ENCODING_UNKNOWN};
-    nvimgcodecImageInfo_t cs_info;
-    memset(&cs_info, 0, sizeof cs_info);
-    cs_info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
-    cs_info.struct_size = sizeof cs_info;
-    cs_info.struct_next = &jpeg_info;
-    if (cs->getImageInfo(cs->instance, &cs_info) != NVIMGCODEC_STATUS_SUCCESS) {
+    nvimgcodecJpegImageInfo_t jpeg_info;
+    nvimgcodecImageInfo_t cs_info, info;
+    if (stream_info(cs, &cs_info, &jpeg_info) != NVIMGCODEC_STATUS_SUCCESS) {
         *status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
         return;
     }
@@ -328,11 +335,15 @@ void HipJpegDecoder::single_can_decode(nvimgcodecProcessingStatus_t* status, nvi
         *status = NVIMGCODEC_PROCESSING_STATUS_CODEC_UNSUPPORTED;
         return;
     }
-    const nvimgcodecJpegImageInfo_t* ji = find_in_chain<nvimgcodecJpegImageInfo_t>(cs_info.struct_next, NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO);
-    if (ji && ji->encoding == NVIMGCODEC_JPEG_ENCODING_LOSSLESS_HUFFMAN && scale_denom_ == 1) {
-        lossless_can_decode(status, cs_info, image, params);
+    init_info(&info);
+    const StreamFacts stream = stream_facts(cs_info);
+    if (lossless_route(stream)) {
+        // (a frame the header parse could not read is declined before the image is looked at)
+        if (stream.frame_read() && image->getImageInfo(image->instance, &info) != NVIMGCODEC_STATUS_SUCCESS) *status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+        else lossless_can_decode(status, stream, info, params);
         return;
     }
+    const nvimgcodecJpegImageInfo_t* ji = find_in_chain<nvimgcodecJpegImageInfo_t>(cs_info.struct_next, NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO);
     if (ji && ji->encoding != NVIMGCODEC_JPEG_ENCODING_UNKNOWN && ji->encoding != NVIMGCODEC_JPEG_ENCODING_BASELINE_DCT &&
         ji->encoding != NVIMGCODEC_JPEG_ENCODING_EXTENDED_SEQUENTIAL_DCT_HUFFMAN && ji->encoding != NVIMGCODEC_JPEG_ENCODING_PROGRESSIVE_DCT_HUFFMAN) {
         *status = NVIMGCODEC_PROCESSING_STATUS_ENCODING_UNSUPPORTED;
@@ -349,10 +360,6 @@ void HipJpegDecoder::single_can_decode(nvimgcodecProcessingStatus_t* status, nvi
     // the framework's parser names no sampling for four components (reference src/parsers/jpeg.cpp:70-114 returns UNSUPPORTED)
     if (!four_components && cs_info.chroma_subsampling == NVIMGCODEC_SAMPLING_UNSUPPORTED) *status |= NVIMGCODEC_PROCESSING_STATUS_SAMPLING_UNSUPPORTED;
 
-    nvimgcodecImageInfo_t info;
-    memset(&info, 0, sizeof info);
-    info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
-    info.struct_size = sizeof info;
     if (image->getImageInfo(image->instance, &info) != NVIMGCODEC_STATUS_SUCCESS) {
         *status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
         return;
@@ -393,7 +400,7 @@ void HipJpegDecoder::single_can_decode(nvimgcodecProcessingStatus_t* status, nvi
     // libjpeg_turbo_decoder.cpp:355-370), orientations outside the eight EXIF ones (extensions/nvjpeg/type_convert.cpp:43-64),
     // and either of them on subsampled planes.
     hipjpegTransform_t t;
-    const int geometry = sample_transform(info, cs_info, params, &t);
+    const int geometry = sample_transform(info, (int)stream.width, (int)stream.height, params, &t);
     if (geometry & 1) *status |= NVIMGCODEC_PROCESSING_STATUS_ROI_UNSUPPORTED;
     if (geometry & 2) *status |= NVIMGCODEC_PROCESSING_STATUS_ORIENTATION_UNSUPPORTED;
     if (scale_denom_ != 1) {
@@ -421,9 +428,101 @@ nvimgcodecStatus_t HipJpegDecoder::canDecode(nvimgcodecProcessingStatus_t* statu
     return NVIMGCODEC_STATUS_SUCCESS;
 }
 
-void HipJpegDecoder::release_inputs(Job* job)
+// ------------------------------------------------------------------------------------------------ the steps both routes take with a sample
+// What a code stream said about itself: the facts both routes work from.
+HipJpegDecoder::StreamFacts HipJpegDecoder::stream_facts(const nvimgcodecImageInfo_t& cs_info)
 {
-    for (Sample& s : job->samples) {
+    const nvimgcodecJpegImageInfo_t* ji = find_in_chain<nvimgcodecJpegImageInfo_t>(cs_info.struct_next, NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO);
+    StreamFacts f;
+    f.known = true;
+    f.lossless = ji && ji->encoding == NVIMGCODEC_JPEG_ENCODING_LOSSLESS_HUFFMAN;
+    f.width = cs_info.plane_info[0].width;
+    f.height = cs_info.plane_info[0].height;
+    f.ncomp = cs_info.num_planes;
+    f.precision = cs_info.plane_info[0].precision;
+    f.orientation = cs_info.orientation;
+    return f;
+}
+
+// The caller's image descriptor, and the stream its consumer works on.
+bool HipJpegDecoder::read_image(Sample& s, nvimgcodecImageInfo_t* info)
+{
+    hipjpeg::fault_point("marshal");
+    init_info(info);
+    if (s.image->getImageInfo(s.image->instance, info) != NVIMGCODEC_STATUS_SUCCESS) {
+        s.early_status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+        return false;
+    }
+    s.user_stream = info->cuda_stream;
+    return true;
+}
+
+// the framework bounces host buffers for GPU backends (reference src/work.h:144-169); a host pointer here is a caller bug
+static bool on_device(const nvimgcodecImageInfo_t& info) { return info.buffer_kind == NVIMGCODEC_IMAGE_BUFFER_KIND_STRIDED_DEVICE && info.buffer; }
+
+// The caller's planes are laid out back to back inside `buffer` (reference cuda_decoder.cpp:532-538).
+bool HipJpegDecoder::caller_planes(const nvimgcodecImageInfo_t& info, uint32_t max_planes, Sample& s, void** plane, uint32_t* pitch)
+{
+    uint8_t* p = static_cast<uint8_t*>(info.buffer);
+    s.nplanes = std::min<uint32_t>(info.num_planes, max_planes);
+    s.buffer_size = info.buffer_size;
+    for (uint32_t pl = 0; pl < s.nplanes; pl++) {
+        const nvimgcodecImagePlaneInfo_t& pi = info.plane_info[pl];
+        if (pi.row_stride > 0xFFFFFFFFull) {  // the kernels address rows with 32-bit pitches
+            s.early_status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+            return false;
+        }
+        plane[pl] = p;
+        pitch[pl] = (uint32_t)pi.row_stride;
+        s.plane_w[pl] = pi.width;
+        s.plane_h[pl] = pi.height;
+        p += pi.row_stride * pi.height;
+    }
+    return true;
+}
+
+// Can the first `planes` of the caller's planes hold pictures of pw[pl] x ph[pl], and its buffer those planes?
+bool HipJpegDecoder::fits(const Sample& s, const uint32_t* pitch, int planes, const int* pw, const int* ph)
+{
+    if ((int)s.nplanes < planes) return false;
+    size_t need = 0;
+    for (int pl = 0; pl < planes; pl++) {
+        if ((int64_t)s.plane_w[pl] < pw[pl] || (int64_t)s.plane_h[pl] < ph[pl]) return false;
+        need += (size_t)pitch[pl] * s.plane_h[pl];
+    }
+    return s.buffer_size == 0 || s.buffer_size >= need;
+}
+
+// bitstream: zero-copy map when the stream offers it, else read into our own buffer (cuda_decoder.cpp:480-500)
+bool HipJpegDecoder::fetch_bitstream(Sample& s)
+{
+    nvimgcodecIoStreamDesc_t* io = s.code_stream->io_stream;
+    size_t size = 0;
+    void* mapped = nullptr;
+    if (io->size(io->instance, &size) != NVIMGCODEC_STATUS_SUCCESS || size == 0) {
+        s.early_status = NVIMGCODEC_PROCESSING_STATUS_IMAGE_CORRUPTED;
+        return false;
+    }
+    if (io->map(io->instance, &mapped, 0, size) == NVIMGCODEC_STATUS_SUCCESS && mapped) {
+        s.mapped = mapped;
+        s.data = static_cast<const uint8_t*>(mapped);
+    } else {
+        s.owned.resize(size);
+        size_t got = 0;
+        io->seek(io->instance, 0, SEEK_SET);
+        if (io->read(io->instance, &got, s.owned.data(), size) != NVIMGCODEC_STATUS_SUCCESS || got != size) {
+            s.early_status = NVIMGCODEC_PROCESSING_STATUS_IMAGE_CORRUPTED;
+            return false;
+        }
+        s.data = s.owned.data();
+    }
+    s.size = size;
+    return true;
+}
+
+void HipJpegDecoder::release_inputs(std::vector<Sample>& samples)
+{
+    for (Sample& s : samples) {
         if (s.mapped) {
             nvimgcodecIoStreamDesc_t* io = s.code_stream->io_stream;
             io->unmap(io->instance, s.mapped, s.size);
@@ -432,37 +531,55 @@ void HipJpegDecoder::release_inputs(Job* job)
     }
 }
 
-// Exactly one imageReady per sample: every path that reports goes through here.
-void HipJpegDecoder::report(Job* job, int i, nvimgcodecProcessingStatus_t ps)
+// Exactly one imageReady per sample: every path that reports goes through here.  A framework whose imageReady throws (double set) must not
+// take the route's other samples, or a job page, down with it.
+void HipJpegDecoder::report(Sample& s, int i, nvimgcodecProcessingStatus_t ps, const char* what)
 {
-    Sample& s = job->samples[i];
     if (s.reported) return;
     s.reported = true;
-    if (ps != NVIMGCODEC_PROCESSING_STATUS_SUCCESS)
-        HJ_LOG_WARNING(fw_, kDecoderId, "sample " << i << " not decoded, processing status 0x" << std::hex << ps);
-    s.image->imageReady(s.image->instance, ps);
+    try {
+        if (ps != NVIMGCODEC_PROCESSING_STATUS_SUCCESS)
+            HJ_LOG_WARNING(fw_, kDecoderId, what << " " << i << " not decoded, processing status 0x" << std::hex << ps);
+        s.image->imageReady(s.image->instance, ps);
+    } catch (...) {
+    }
 }
 
+namespace {
+// The consumers' streams must not run ahead of the decode (reference cuda_decoder.cpp:552-556): one wait per DISTINCT stream -- a
+// batch's samples nearly always share one, and 256 runtime calls per batch were a quarter of the completion thread's time.
+struct ConsumerStreams {
+    hipEvent_t decoded;  // recorded behind the decode
+    void* waited[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool waited_ok[4] = {false, false, false, false};
+    int nwaited = 0;
+    bool wait_for_decode(void* user_stream)
+    {
+        for (int k = 0; k < nwaited; k++)
+            if (waited[k] == user_stream) return waited_ok[k];
+        const bool ok = hipStreamWaitEvent((hipStream_t)user_stream, decoded, 0) == hipSuccess;
+        if (nwaited < 4) {
+            waited[nwaited] = user_stream;
+            waited_ok[nwaited++] = ok;
+        }
+        return ok;
+    }
+};
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------ the lossless route
 // Lossless Huffman streams, under the rules of the reference's lossless decoder (extensions/nvjpeg/lossless_decoder.cpp:82-103) widened
 // by what hipjpegDecodeLosslessBatch does: P_Y for one component, I_UNCHANGED and P_UNCHANGED for any number; UINT16 always and UINT8 for
 // precisions up to 8; the stored components, so no colour request but UNCHANGED (or GRAY for one component); no region, no turning.
-void HipJpegDecoder::lossless_can_decode(nvimgcodecProcessingStatus_t* status, const nvimgcodecImageInfo_t& cs_info, nvimgcodecImageDesc_t* image,
+void HipJpegDecoder::lossless_can_decode(nvimgcodecProcessingStatus_t* status, const StreamFacts& stream, const nvimgcodecImageInfo_t& info,
                                          const nvimgcodecDecodeParams_t* params)
 {
     *status = NVIMGCODEC_PROCESSING_STATUS_SUCCESS;
-    if (cs_info.num_planes < 1 || cs_info.plane_info[0].width == 0) {  // the header parse could not read the frame
+    if (!stream.frame_read()) {
         *status = NVIMGCODEC_PROCESSING_STATUS_CODESTREAM_UNSUPPORTED;
         return;
     }
-    nvimgcodecImageInfo_t info;
-    memset(&info, 0, sizeof info);
-    info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
-    info.struct_size = sizeof info;
-    if (image->getImageInfo(image->instance, &info) != NVIMGCODEC_STATUS_SUCCESS) {
-        *status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
-        return;
-    }
-    const uint32_t ncomp = cs_info.num_planes, precision = cs_info.plane_info[0].precision;
+    const uint32_t ncomp = stream.ncomp, precision = stream.precision;
     if (!(info.color_spec == NVIMGCODEC_COLORSPEC_UNCHANGED || (info.color_spec == NVIMGCODEC_COLORSPEC_GRAY && ncomp == 1)))
         *status |= NVIMGCODEC_PROCESSING_STATUS_COLOR_SPEC_UNSUPPORTED;
     switch (info.sample_format) {
@@ -486,119 +603,43 @@ void HipJpegDecoder::lossless_can_decode(nvimgcodecProcessingStatus_t* status, c
             *status |= NVIMGCODEC_PROCESSING_STATUS_SAMPLE_TYPE_UNSUPPORTED;
     }
     if (params->enable_roi && info.region.ndim > 0) *status |= NVIMGCODEC_PROCESSING_STATUS_ROI_UNSUPPORTED;
-    if (params->apply_exif_orientation && (cs_info.orientation.rotated != 0 || cs_info.orientation.flip_x || cs_info.orientation.flip_y))
+    if (params->apply_exif_orientation && (stream.orientation.rotated != 0 || stream.orientation.flip_x || stream.orientation.flip_y))
         *status |= NVIMGCODEC_PROCESSING_STATUS_ORIENTATION_UNSUPPORTED;
 }
 
 // The lossless samples of a decode() call: the entropy stage runs here, on the header-parsing threads; the copy and the
 // reconstruction kernels are queued on a stream of this decoder, each consumer's stream is ordered behind them, and every sample
 // reports once.  A caller that insists on what canDecode declined gets the same verdict.
-void HipJpegDecoder::decode_lossless(nvimgcodecCodeStreamDesc_t** code_streams, nvimgcodecImageDesc_t** images, int batch_size,
-                                     const nvimgcodecDecodeParams_t* params)
+void HipJpegDecoder::decode_lossless(std::vector<Sample>& samples, const nvimgcodecDecodeParams_t* params)
 {
-    const int n = batch_size;
-    std::vector<nvimgcodecProcessingStatus_t> verdict((size_t)n, NVIMGCODEC_PROCESSING_STATUS_SUCCESS);
-    std::vector<bool> reported((size_t)n, false);
-    auto report_all = [&]() {
-        for (int i = 0; i < n; i++) {
-            if (reported[(size_t)i]) continue;
-            reported[(size_t)i] = true;
-            if (verdict[(size_t)i] != NVIMGCODEC_PROCESSING_STATUS_SUCCESS)
-                HJ_LOG_WARNING(fw_, kDecoderId, "lossless sample " << i << " not decoded, processing status 0x" << std::hex << verdict[(size_t)i]);
-            try {
-                images[i]->imageReady(images[i]->instance, verdict[(size_t)i]);
-            } catch (...) {
-            }
-        }
-    };
-    struct Input {
-        void* mapped = nullptr;
-        size_t size = 0;
-        std::vector<uint8_t> owned;
-        void* user_stream = nullptr;
-    };
-    std::vector<Input> inputs((size_t)n);
-    auto release = [&]() {
-        for (int i = 0; i < n; i++)
-            if (inputs[(size_t)i].mapped) {
-                nvimgcodecIoStreamDesc_t* io = code_streams[i]->io_stream;
-                io->unmap(io->instance, inputs[(size_t)i].mapped, inputs[(size_t)i].size);
-                inputs[(size_t)i].mapped = nullptr;
-            }
-    };
+    const int n = (int)samples.size();
     try {
         std::vector<const uint8_t*> data((size_t)n, nullptr);
         std::vector<size_t> sizes((size_t)n, 0);
         std::vector<hipjpegLosslessOutput_t> outs((size_t)n);
         memset(outs.data(), 0, sizeof(hipjpegLosslessOutput_t) * (size_t)n);
         for (int i = 0; i < n; i++) {
-            nvimgcodecProcessingStatus_t& v = verdict[(size_t)i];
-            try {
-                nvimgcodecJpegImageInfo_t jpeg_info{NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO, sizeof(nvimgcodecJpegImageInfo_t), nullptr,
-                                                    NVIMGCODEC_JPEG_ENCODING_UNKNOWN};
-                nvimgcodecImageInfo_t cs_info, info;
-                memset(&cs_info, 0, sizeof cs_info);
-                cs_info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
-                cs_info.struct_size = sizeof cs_info;
-                cs_info.struct_next = &jpeg_info;
-                memset(&info, 0, sizeof info);
-                info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
-                info.struct_size = sizeof info;
-                if (code_streams[i]->getImageInfo(code_streams[i]->instance, &cs_info) != NVIMGCODEC_STATUS_SUCCESS ||
-                    images[i]->getImageInfo(images[i]->instance, &info) != NVIMGCODEC_STATUS_SUCCESS) {
-                    v = NVIMGCODEC_PROCESSING_STATUS_FAIL;
-                    continue;
-                }
-                lossless_can_decode(&v, cs_info, images[i], params);
-                if (v != NVIMGCODEC_PROCESSING_STATUS_SUCCESS) continue;
-                if (info.buffer_kind != NVIMGCODEC_IMAGE_BUFFER_KIND_STRIDED_DEVICE || !info.buffer) {
-                    v = NVIMGCODEC_PROCESSING_STATUS_FAIL;
-                    continue;
-                }
-                inputs[(size_t)i].user_stream = info.cuda_stream;
-                // the caller's planes: back to back inside `buffer`, each large enough for the picture
+            Sample& s = samples[(size_t)i];
+            try {  // one sample's trouble stays that sample's
+                nvimgcodecImageInfo_t info;
+                if (!read_image(s, &info)) continue;
+                lossless_can_decode(&s.early_status, s.stream, info, params);
+                if (s.early_status != NVIMGCODEC_PROCESSING_STATUS_SUCCESS) continue;
                 hipjpegLosslessOutput_t& o = outs[(size_t)i];
                 o.sample_bytes = info.plane_info[0].sample_type == NVIMGCODEC_SAMPLE_DATA_TYPE_UINT8 ? 1 : 2;
                 o.planar = info.sample_format == NVIMGCODEC_SAMPLEFORMAT_I_UNCHANGED ? 0 : 1;
-                uint8_t* p = static_cast<uint8_t*>(info.buffer);
-                size_t need = 0;
-                bool fits = true;
-                for (uint32_t pl = 0; pl < info.num_planes && pl < 4; pl++) {
-                    const nvimgcodecImagePlaneInfo_t& pi = info.plane_info[pl];
-                    if (pi.row_stride > 0xFFFFFFFFull || pi.width < cs_info.plane_info[0].width || pi.height < cs_info.plane_info[0].height) fits = false;
-                    o.plane[pl] = p;
-                    o.pitch[pl] = (uint32_t)pi.row_stride;
-                    p += pi.row_stride * pi.height;
-                    need += pi.row_stride * pi.height;
-                }
-                if (!fits || (info.buffer_size != 0 && info.buffer_size < need)) {
-                    v = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+                // every plane the caller offers holds the whole picture
+                const int w[4] = {(int)s.stream.width, (int)s.stream.width, (int)s.stream.width, (int)s.stream.width};
+                const int h[4] = {(int)s.stream.height, (int)s.stream.height, (int)s.stream.height, (int)s.stream.height};
+                if (!on_device(info) || !caller_planes(info, 4, s, o.plane, o.pitch) || !fits(s, o.pitch, (int)s.nplanes, w, h)) {
+                    s.early_status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
                     continue;
                 }
-                nvimgcodecIoStreamDesc_t* io = code_streams[i]->io_stream;
-                size_t size = 0;
-                if (io->size(io->instance, &size) != NVIMGCODEC_STATUS_SUCCESS || size == 0) {
-                    v = NVIMGCODEC_PROCESSING_STATUS_IMAGE_CORRUPTED;
-                    continue;
-                }
-                void* mapped = nullptr;
-                if (io->map(io->instance, &mapped, 0, size) == NVIMGCODEC_STATUS_SUCCESS && mapped) {
-                    inputs[(size_t)i].mapped = mapped;
-                    data[(size_t)i] = static_cast<const uint8_t*>(mapped);
-                } else {
-                    inputs[(size_t)i].owned.resize(size);
-                    size_t got = 0;
-                    io->seek(io->instance, 0, SEEK_SET);
-                    if (io->read(io->instance, &got, inputs[(size_t)i].owned.data(), size) != NVIMGCODEC_STATUS_SUCCESS || got != size) {
-                        v = NVIMGCODEC_PROCESSING_STATUS_IMAGE_CORRUPTED;
-                        continue;
-                    }
-                    data[(size_t)i] = inputs[(size_t)i].owned.data();
-                }
-                inputs[(size_t)i].size = sizes[(size_t)i] = size;
+                if (!fetch_bitstream(s)) continue;
+                data[(size_t)i] = s.data;
+                sizes[(size_t)i] = s.size;
             } catch (...) {
-                v = NVIMGCODEC_PROCESSING_STATUS_FAIL;
-                data[(size_t)i] = nullptr;
+                s.early_status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
             }
         }
         bool ok = hipSetDevice(device_) == hipSuccess;
@@ -610,27 +651,27 @@ void HipJpegDecoder::decode_lossless(nvimgcodecCodeStreamDesc_t** code_streams, 
         // (samples declined above have no data: the batch calls them INVALID_ARGUMENT, their verdict stands)
         if (ok) ok = lossless_->decode(data.data(), sizes.data(), n, outs.data(), statuses.data(), parse_pool_.get(), lossless_stream_) == HIPJPEG_STATUS_SUCCESS;
         if (ok) ok = hipEventRecord(lossless_event_, lossless_stream_) == hipSuccess;
-        if (!ok && lossless_stream_) (void)hipStreamSynchronize(lossless_stream_);
-        release();
+        if (!ok && lossless_stream_) (void)hipStreamSynchronize(lossless_stream_);  // whatever was queued must not outlive the caller's buffers
+        release_inputs(samples);
+        ConsumerStreams consumers{lossless_event_};
         for (int i = 0; i < n; i++) {
-            nvimgcodecProcessingStatus_t& v = verdict[(size_t)i];
+            nvimgcodecProcessingStatus_t& v = samples[(size_t)i].early_status;  // from here on the sample's verdict
             if (v != NVIMGCODEC_PROCESSING_STATUS_SUCCESS) continue;
             v = ok ? to_processing_status(statuses[(size_t)i]) : (nvimgcodecProcessingStatus_t)NVIMGCODEC_PROCESSING_STATUS_FAIL;
-            // the consumer's stream must not run ahead of the decode
-            if (v == NVIMGCODEC_PROCESSING_STATUS_SUCCESS && hipStreamWaitEvent((hipStream_t)inputs[(size_t)i].user_stream, lossless_event_, 0) != hipSuccess)
-                v = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+            if (v == NVIMGCODEC_PROCESSING_STATUS_SUCCESS && !consumers.wait_for_decode(samples[(size_t)i].user_stream)) v = NVIMGCODEC_PROCESSING_STATUS_FAIL;
         }
     } catch (...) {
         if (lossless_stream_) (void)hipStreamSynchronize(lossless_stream_);
         try {
-            release();
+            release_inputs(samples);
         } catch (...) {
         }
-        for (int i = 0; i < n; i++) verdict[(size_t)i] = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+        for (Sample& s : samples) s.early_status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
     }
-    report_all();
+    for (int i = 0; i < n; i++) report(samples[(size_t)i], i, samples[(size_t)i].early_status, "lossless sample");
 }
 
+// ------------------------------------------------------------------------------------------------ the DCT route
 void HipJpegDecoder::release_job(Job* job)
 {
     {
@@ -706,35 +747,18 @@ void HipJpegDecoder::complete(Job* job)
     }
     if (!gpu_ok) (void)hipStreamSynchronize(job->stream);  // whatever was queued must not outlive the caller's buffers
     try {
-        release_inputs(job);
+        release_inputs(job->samples);
     } catch (...) {
     }
-    // the consumers' streams must not run ahead of the decode (reference cuda_decoder.cpp:552-556): one wait per DISTINCT stream of
-    // the job -- a batch's samples nearly always share one, and 256 runtime calls per batch were a quarter of this thread's time
-    void* waited[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool waited_ok[4] = {false, false, false, false};
-    int nwaited = 0;
-    auto order_after_decode = [&](void* user_stream) {
-        for (int k = 0; k < nwaited; k++)
-            if (waited[k] == user_stream) return waited_ok[k];
-        const bool ok = hipStreamWaitEvent((hipStream_t)user_stream, job->event, 0) == hipSuccess;
-        if (nwaited < 4) {
-            waited[nwaited] = user_stream;
-            waited_ok[nwaited++] = ok;
-        }
-        return ok;
-    };
+    ConsumerStreams consumers{job->event};
     for (int i = 0; i < n; i++) {
         Sample& s = job->samples[i];
         nvimgcodecProcessingStatus_t ps = s.early_status;
         if (ps == NVIMGCODEC_PROCESSING_STATUS_SUCCESS) {
             ps = gpu_ok ? to_processing_status(job->statuses[i]) : (nvimgcodecProcessingStatus_t)NVIMGCODEC_PROCESSING_STATUS_FAIL;
-            if (ps == NVIMGCODEC_PROCESSING_STATUS_SUCCESS && !order_after_decode(s.user_stream)) ps = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+            if (ps == NVIMGCODEC_PROCESSING_STATUS_SUCCESS && !consumers.wait_for_decode(s.user_stream)) ps = NVIMGCODEC_PROCESSING_STATUS_FAIL;
         }
-        try {
-            report(job, i, ps);
-        } catch (...) {  // a framework whose imageReady throws (double set) must not take the page down with it
-        }
+        report(s, i, ps);
     }
     release_job(job);
 }
@@ -748,47 +772,25 @@ nvimgcodecStatus_t HipJpegDecoder::decode(nvimgcodecCodeStreamDesc_t** code_stre
     if (!code_streams || !images || !params) return NVIMGCODEC_STATUS_EXTENSION_INVALID_PARAMETER;
     if (batch_size < 1) return NVIMGCODEC_STATUS_INVALID_PARAMETER;
     std::lock_guard<std::mutex> serial(decode_mutex_);
-    // lossless Huffman samples take their own route; the others (all of them, in the everyday batch) go on as before
-    std::vector<nvimgcodecCodeStreamDesc_t*> lossless_streams, other_streams;
-    std::vector<nvimgcodecImageDesc_t*> lossless_images, other_images;
-    if (scale_denom_ == 1 && !fast_idct_) {
-        for (int i = 0; i < batch_size; i++) {
-            bool lossless = false;
-            try {
-                nvimgcodecJpegImageInfo_t jpeg_info{NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO, sizeof(nvimgcodecJpegImageInfo_t), nullptr,
-                                                    NVIMGCODEC_JPEG_ENCODING_UNKNOWN};
-                nvimgcodecImageInfo_t cs_info;
-                memset(&cs_info, 0, sizeof cs_info);
-                cs_info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
-                cs_info.struct_size = sizeof cs_info;
-                cs_info.struct_next = &jpeg_info;
-                if (code_streams[i] && code_streams[i]->getImageInfo(code_streams[i]->instance, &cs_info) == NVIMGCODEC_STATUS_SUCCESS) {
-                    const nvimgcodecJpegImageInfo_t* ji = find_in_chain<nvimgcodecJpegImageInfo_t>(cs_info.struct_next, NVIMGCODEC_STRUCTURE_TYPE_JPEG_IMAGE_INFO);
-                    lossless = ji && ji->encoding == NVIMGCODEC_JPEG_ENCODING_LOSSLESS_HUFFMAN;
-                }
-            } catch (...) {
-                lossless = false;
-            }
-            if (lossless && lossless_streams.empty()) {
-                other_streams.assign(code_streams, code_streams + i);
-                other_images.assign(images, images + i);
-            }
-            if (lossless) {
-                lossless_streams.push_back(code_streams[i]);
-                lossless_images.push_back(images[i]);
-            } else if (!lossless_streams.empty()) {
-                other_streams.push_back(code_streams[i]);
-                other_images.push_back(images[i]);
-            }
+    // One question to each code stream sorts the batch: lossless Huffman samples take their own route, the others (all of them, in the
+    // everyday batch) the DCT one.  A stream that does not answer goes the DCT way, which wants its facts for a region or a turn only.
+    std::vector<Sample> lossless, dct;
+    dct.reserve((size_t)batch_size);
+    for (int i = 0; i < batch_size; i++) {
+        Sample s;
+        s.code_stream = code_streams[i];
+        s.image = images[i];
+        try {
+            nvimgcodecJpegImageInfo_t jpeg_info;
+            nvimgcodecImageInfo_t cs_info;
+            if (s.code_stream && stream_info(s.code_stream, &cs_info, &jpeg_info) == NVIMGCODEC_STATUS_SUCCESS) s.stream = stream_facts(cs_info);
+        } catch (...) {
         }
+        (lossless_route(s.stream) ? lossless : dct).push_back(std::move(s));
     }
-    if (!lossless_streams.empty()) {
-        decode_lossless(lossless_streams.data(), lossless_images.data(), (int)lossless_streams.size(), params);
-        if (other_streams.empty()) return NVIMGCODEC_STATUS_SUCCESS;
-        code_streams = other_streams.data();
-        images = other_images.data();
-        batch_size = (int)other_streams.size();
-    }
+    if (!lossless.empty()) decode_lossless(lossless, params);
+    if (dct.empty()) return NVIMGCODEC_STATUS_SUCCESS;
+    batch_size = (int)dct.size();
     int chunks = pipeline_chunks_ > 0 ? pipeline_chunks_ : (batch_size >= 192 ? 3 : batch_size >= 96 ? 2 : 1);
     if (pipeline_chunks_ <= 0) {
         // a caller that keeps several decode() calls outstanding already has what the pieces are for -- the host stage and copy of
@@ -803,14 +805,13 @@ nvimgcodecStatus_t HipJpegDecoder::decode(nvimgcodecCodeStreamDesc_t** code_stre
     nvimgcodecStatus_t result = NVIMGCODEC_STATUS_SUCCESS;
     for (int c = 0; c < chunks; c++) {
         const int lo = (int)((long long)batch_size * c / chunks), hi = (int)((long long)batch_size * (c + 1) / chunks);
-        const nvimgcodecStatus_t st = decode_chunk(code_streams + lo, images + lo, hi - lo, params);
+        const nvimgcodecStatus_t st = decode_chunk(dct.data() + lo, hi - lo, params);
         if (st != NVIMGCODEC_STATUS_SUCCESS) result = st;  // that piece's samples have been reported failed; the others go on
     }
     return result;
 }
 
-nvimgcodecStatus_t HipJpegDecoder::decode_chunk(nvimgcodecCodeStreamDesc_t** code_streams, nvimgcodecImageDesc_t** images, int batch_size,
-                                                const nvimgcodecDecodeParams_t* params)
+nvimgcodecStatus_t HipJpegDecoder::decode_chunk(const Sample* samples, int batch_size, const nvimgcodecDecodeParams_t* params)
 {
     static const bool timing = getenv("HIPJPEG_DEBUG_TIMING") != nullptr;  // debug aid: phase times of decode() on stderr
     const auto t_enter = std::chrono::steady_clock::now();
@@ -829,11 +830,8 @@ nvimgcodecStatus_t HipJpegDecoder::decode_chunk(nvimgcodecCodeStreamDesc_t** cod
     bool scheduled = false;
     try {
         job->issued = false;
-        job->samples.assign(n, Sample());
-        for (int i = 0; i < n; i++) {
-            job->samples[i].code_stream = code_streams[i];
-            job->samples[i].image = images[i];
-        }
+        job->samples.clear();
+        job->samples.assign(samples, samples + n);
         job->statuses.assign(n, HIPJPEG_STATUS_SUCCESS);
         std::vector<const uint8_t*> data(n, nullptr);
         std::vector<size_t> sizes(n, 0);
@@ -845,18 +843,9 @@ nvimgcodecStatus_t HipJpegDecoder::decode_chunk(nvimgcodecCodeStreamDesc_t** cod
 
         auto marshal = [&](int i) {
             Sample& s = job->samples[i];
-            hipjpeg::fault_point("marshal");
             nvimgcodecImageInfo_t info;
-            memset(&info, 0, sizeof info);
-            info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
-            info.struct_size = sizeof info;
-            if (s.image->getImageInfo(s.image->instance, &info) != NVIMGCODEC_STATUS_SUCCESS) {
-                s.early_status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
-                return;
-            }
-            s.user_stream = info.cuda_stream;
-            if (info.buffer_kind != NVIMGCODEC_IMAGE_BUFFER_KIND_STRIDED_DEVICE || !info.buffer) {
-                // the framework bounces host buffers for GPU backends (reference src/work.h:144-169); a host pointer here is a caller bug
+            if (!read_image(s, &info)) return;
+            if (!on_device(info)) {
                 s.early_status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
                 return;
             }
@@ -871,68 +860,26 @@ nvimgcodecStatus_t HipJpegDecoder::decode_chunk(nvimgcodecCodeStreamDesc_t** cod
                 return;
             }
             if ((params->enable_roi && info.region.ndim > 0) || params->apply_exif_orientation) {
-                nvimgcodecImageInfo_t cs_info;
-                memset(&cs_info, 0, sizeof cs_info);
-                cs_info.struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
-                cs_info.struct_size = sizeof cs_info;
-                if (s.code_stream->getImageInfo(s.code_stream->instance, &cs_info) != NVIMGCODEC_STATUS_SUCCESS) {
+                if (!s.stream.known) {  // the region is checked against the stream's size
                     s.early_status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
                     return;
                 }
-                const int bad = sample_transform(info, cs_info, params, &geometry[i]);
+                const int bad = sample_transform(info, (int)s.stream.width, (int)s.stream.height, params, &geometry[i]);
                 if (bad) {  // canDecode said so already; a caller that insists gets the same verdict (cuda_decoder.cpp:452-461)
                     s.early_status = (bad & 1) ? NVIMGCODEC_PROCESSING_STATUS_ROI_UNSUPPORTED : NVIMGCODEC_PROCESSING_STATUS_ORIENTATION_UNSUPPORTED;
                     return;
                 }
                 any_geometry = any_geometry || geometry[i].x1 != 0 || geometry[i].orientation != 1;
             }
-            // planes are laid out back to back inside `buffer` (reference cuda_decoder.cpp:532-538)
-            uint8_t* p = static_cast<uint8_t*>(info.buffer);
-            s.nplanes = std::min<uint32_t>(info.num_planes, 3u);
-            s.buffer_size = info.buffer_size;
-            for (uint32_t pl = 0; pl < s.nplanes; pl++) {
-                if (info.plane_info[pl].row_stride > 0xFFFFFFFFull) {  // the kernels address rows with 32-bit pitches
-                    s.early_status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
-                    return;
-                }
-                outs[i].plane[pl] = p;
-                outs[i].pitch[pl] = (uint32_t)info.plane_info[pl].row_stride;
-                s.plane_w[pl] = info.plane_info[pl].width;
-                s.plane_h[pl] = info.plane_info[pl].height;
-                p += info.plane_info[pl].row_stride * info.plane_info[pl].height;
-            }
-            // bitstream: zero-copy map when the stream offers it, else read into our own buffer (cuda_decoder.cpp:480-500)
-            nvimgcodecIoStreamDesc_t* io = s.code_stream->io_stream;
-            size_t size = 0;
-            if (io->size(io->instance, &size) != NVIMGCODEC_STATUS_SUCCESS || size == 0) {
-                s.early_status = NVIMGCODEC_PROCESSING_STATUS_IMAGE_CORRUPTED;
-                return;
-            }
-            void* mapped = nullptr;
-            if (io->map(io->instance, &mapped, 0, size) == NVIMGCODEC_STATUS_SUCCESS && mapped) {
-                s.mapped = mapped;
-                s.data = static_cast<const uint8_t*>(mapped);
-            } else {
-                s.owned.resize(size);
-                size_t got = 0;
-                io->seek(io->instance, 0, SEEK_SET);
-                if (io->read(io->instance, &got, s.owned.data(), size) != NVIMGCODEC_STATUS_SUCCESS || got != size) {
-                    s.early_status = NVIMGCODEC_PROCESSING_STATUS_IMAGE_CORRUPTED;
-                    return;
-                }
-                s.data = s.owned.data();
-            }
-            s.size = size;
+            if (!caller_planes(info, 3, s, outs[i].plane, outs[i].pitch) || !fetch_bitstream(s)) return;
             data[i] = s.data;
-            sizes[i] = size;
+            sizes[i] = s.size;
         };
         for (int i = 0; i < n; i++) {
             try {  // one sample's trouble (a throwing getImageInfo, no memory for its bitstream copy) stays that sample's
                 marshal(i);
             } catch (...) {
-                job->samples[i].early_status = NVIMGCODEC_PROCESSING_STATUS_FAIL;
-                data[i] = nullptr;
-                sizes[i] = 0;
+                job->samples[i].early_status = NVIMGCODEC_PROCESSING_STATUS_FAIL;  // (its data[i] is still null: set last)
             }
         }
 
@@ -954,19 +901,14 @@ nvimgcodecStatus_t HipJpegDecoder::decode_chunk(nvimgcodecCodeStreamDesc_t** cod
             const hipjpeg::PlannedImage& im = job->batch.image(i);
             int ow = 0, oh = 0;
             job->batch.output_size(i, &ow, &oh);
-            bool fits = true;
-            size_t need = 0;
-            const int planes = formats[i] == HIPJPEG_OUTPUT_YUV_PLANAR ? im.frame.ncomp
-                               : (formats[i] == HIPJPEG_OUTPUT_RGB_PLANAR || formats[i] == HIPJPEG_OUTPUT_BGR_PLANAR) ? 3 : 1;
-            if ((int)s.nplanes < planes) fits = false;
-            for (int pl = 0; pl < planes && fits; pl++) {
-                const int pw = formats[i] == HIPJPEG_OUTPUT_YUV_PLANAR ? im.frame.comp[pl].samp_w : ow;
-                const int ph = formats[i] == HIPJPEG_OUTPUT_YUV_PLANAR ? im.frame.comp[pl].samp_h : oh;
-                if ((int64_t)s.plane_w[pl] < pw || (int64_t)s.plane_h[pl] < ph) fits = false;
-                need += (size_t)outs[i].pitch[pl] * s.plane_h[pl];
+            const bool raw = formats[i] == HIPJPEG_OUTPUT_YUV_PLANAR;  // the stored components, each at its own size
+            const int planes = raw ? im.frame.ncomp : (formats[i] == HIPJPEG_OUTPUT_RGB_PLANAR || formats[i] == HIPJPEG_OUTPUT_BGR_PLANAR) ? 3 : 1;
+            int pw[3] = {ow, ow, ow}, ph[3] = {oh, oh, oh};
+            for (int pl = 0; raw && pl < planes && pl < 3; pl++) {
+                pw[pl] = im.frame.comp[pl].samp_w;
+                ph[pl] = im.frame.comp[pl].samp_h;
             }
-            if (fits && s.buffer_size != 0 && s.buffer_size < need) fits = false;
-            if (!fits) {
+            if (!fits(s, outs[i].pitch, planes, pw, ph)) {
                 job->batch.reject(i, HIPJPEG_STATUS_INVALID_ARGUMENT);
                 job->statuses[i] = HIPJPEG_STATUS_INVALID_ARGUMENT;
             }
@@ -999,17 +941,13 @@ nvimgcodecStatus_t HipJpegDecoder::decode_chunk(nvimgcodecCodeStreamDesc_t** cod
     } catch (...) {
         if (scheduled) return NVIMGCODEC_STATUS_SUCCESS;  // every sample is in the hands of a host task: they report
         try {
-            release_inputs(job);
+            release_inputs(job->samples);
         } catch (...) {
         }
-        for (int i = 0; i < n && i < (int)job->samples.size(); i++) {
-            try {
-                if (job->samples[i].image) report(job, i, NVIMGCODEC_PROCESSING_STATUS_FAIL);
-            } catch (...) {
-            }
-        }
+        for (int i = 0; i < n && i < (int)job->samples.size(); i++)
+            if (job->samples[i].image) report(job->samples[i], i, NVIMGCODEC_PROCESSING_STATUS_FAIL);
         if ((int)job->samples.size() < n)  // not even the sample table could be built: report straight from the arguments
-            for (int i = (int)job->samples.size(); i < n; i++) images[i]->imageReady(images[i]->instance, NVIMGCODEC_PROCESSING_STATUS_FAIL);
+            for (int i = (int)job->samples.size(); i < n; i++) samples[i].image->imageReady(samples[i].image->instance, NVIMGCODEC_PROCESSING_STATUS_FAIL);
         release_job(job);
         HJ_LOG_ERROR(fw_, kDecoderId, "decode batch of " << n << " samples failed before it was scheduled on device " << device_);
         return NVIMGCODEC_STATUS_EXTENSION_EXECUTION_FAILED;

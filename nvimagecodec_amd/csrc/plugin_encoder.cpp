@@ -58,14 +58,6 @@ bool map_css(nvimgcodecChromaSubsampling_t c, int* css)
     }
 }
 
-void init_info(nvimgcodecImageInfo_t* info, void* next = nullptr)
-{
-    memset(info, 0, sizeof *info);
-    info->struct_type = NVIMGCODEC_STRUCTURE_TYPE_IMAGE_INFO;
-    info->struct_size = sizeof *info;
-    info->struct_next = next;
-}
-
 }  // namespace
 
 class HipJpegEncoder {

@@ -247,34 +247,48 @@ def test_batches_follow_each_other_on_a_stream_without_waiting(torch, decoder):
 
 
 # ------------------------------------------------------------------------------------------------------------- the plugin route
-def plugin_decode(lib, dec, inst, data, h, w, fmt, planes, channels, sample_type, buffer_ptr, pitch, color_spec=None, params=None, region=None):
+def plugin_decode_batch(lib, dec, inst, samples, params=None):
+    """One nvimgcodecDecoderDecode call.  samples: (data, h, w, fmt, planes, channels, sample_type, buffer_ptr, pitch, color_spec, region)
+    each, the last two None for COLORSPEC_UNCHANGED and no region; -> one processing status per sample"""
     from nvimagecodec_amd import abi as A
     C = ctypes
-    arr = np.frombuffer(data, dtype=np.uint8)
-    cs = C.c_void_p()
-    assert lib.nvimgcodecCodeStreamCreateFromHostMem(inst, C.byref(cs), arr.ctypes.data, arr.size) == 0
-    info = A.init(A.ImageInfo, A.ST_IMAGE_INFO, sample_format=fmt, color_spec=A.COLORSPEC_UNCHANGED if color_spec is None else color_spec,
-                  num_planes=planes, buffer=buffer_ptr, buffer_size=pitch * h * planes, buffer_kind=A.BUFFER_KIND_STRIDED_DEVICE, cuda_stream=0)
-    for p in range(planes):
-        pi = info.plane_info[p]
-        pi.width, pi.height, pi.row_stride, pi.num_channels, pi.sample_type = w, h, pitch, channels, sample_type
-    if region is not None:
-        info.region.struct_type, info.region.struct_size = A.ST_REGION, C.sizeof(A.Region)
-        info.region.ndim = 2
-        info.region.start[0], info.region.start[1], info.region.end[0], info.region.end[1] = region
-    im = C.c_void_p()
-    assert lib.nvimgcodecImageCreate(inst, C.byref(im), C.byref(info)) == 0
+    n = len(samples)
+    keep, css, ims = [], [], []
+    for data, h, w, fmt, planes, channels, sample_type, buffer_ptr, pitch, color_spec, region in samples:
+        arr = np.frombuffer(data, dtype=np.uint8)
+        keep.append(arr)
+        cs = C.c_void_p()
+        assert lib.nvimgcodecCodeStreamCreateFromHostMem(inst, C.byref(cs), arr.ctypes.data, arr.size) == 0
+        info = A.init(A.ImageInfo, A.ST_IMAGE_INFO, sample_format=fmt, color_spec=A.COLORSPEC_UNCHANGED if color_spec is None else color_spec,
+                      num_planes=planes, buffer=buffer_ptr, buffer_size=pitch * h * planes, buffer_kind=A.BUFFER_KIND_STRIDED_DEVICE, cuda_stream=0)
+        for p in range(planes):
+            pi = info.plane_info[p]
+            pi.width, pi.height, pi.row_stride, pi.num_channels, pi.sample_type = w, h, pitch, channels, sample_type
+        if region is not None:
+            info.region.struct_type, info.region.struct_size = A.ST_REGION, C.sizeof(A.Region)
+            info.region.ndim = 2
+            info.region.start[0], info.region.start[1], info.region.end[0], info.region.end[1] = region
+        im = C.c_void_p()
+        assert lib.nvimgcodecImageCreate(inst, C.byref(im), C.byref(info)) == 0
+        css.append(cs)
+        ims.append(im)
     dp = params or A.init(A.DecodeParams, A.ST_DECODE_PARAMS)
     fut = C.c_void_p()
-    assert lib.nvimgcodecDecoderDecode(dec, (C.c_void_p * 1)(cs), (C.c_void_p * 1)(im), 1, C.byref(dp), C.byref(fut)) == 0
+    assert lib.nvimgcodecDecoderDecode(dec, (C.c_void_p * n)(*css), (C.c_void_p * n)(*ims), n, C.byref(dp), C.byref(fut)) == 0
     assert lib.nvimgcodecFutureWaitForAll(fut) == 0
-    st = (C.c_uint32 * 1)()
-    n = C.c_size_t()
-    lib.nvimgcodecFutureGetProcessingStatus(fut, st, C.byref(n))
+    st = (C.c_uint32 * n)()
+    cnt = C.c_size_t()
+    lib.nvimgcodecFutureGetProcessingStatus(fut, st, C.byref(cnt))
+    assert cnt.value == n
     lib.nvimgcodecFutureDestroy(fut)
-    lib.nvimgcodecImageDestroy(im)
-    lib.nvimgcodecCodeStreamDestroy(cs)
-    return st[0]
+    for im, cs in zip(ims, css):
+        lib.nvimgcodecImageDestroy(im)
+        lib.nvimgcodecCodeStreamDestroy(cs)
+    return list(st)
+
+
+def plugin_decode(lib, dec, inst, data, h, w, fmt, planes, channels, sample_type, buffer_ptr, pitch, color_spec=None, params=None, region=None):
+    return plugin_decode_batch(lib, dec, inst, [(data, h, w, fmt, planes, channels, sample_type, buffer_ptr, pitch, color_spec, region)], params)[0]
 
 
 @pytest.fixture(scope="module")
@@ -325,6 +339,70 @@ def test_the_plugin_decodes_lossless_streams_and_says_what_it_does_not(torch, pl
     assert plugin_decode(lib, dec, inst, rgb, 66, 70, A.SAMPLEFORMAT_I_UNCHANGED, 1, 3, U16, ptr, 420, color_spec=A.COLORSPEC_SRGB) & A.PS_COLOR_SPEC_UNSUPPORTED == A.PS_COLOR_SPEC_UNSUPPORTED
     roi = A.init(A.DecodeParams, A.ST_DECODE_PARAMS, enable_roi=1)
     assert plugin_decode(lib, dec, inst, gray, 70, 90, A.SAMPLEFORMAT_P_Y, 1, 1, U16, ptr, 180, params=roi, region=(0, 0, 8, 8)) & A.PS_ROI_UNSUPPORTED == A.PS_ROI_UNSUPPORTED
+
+
+def test_one_call_holds_dct_and_lossless_samples(torch, plugin):
+    """Both kinds interleaved in one nvimgcodecDecoderDecode call, good samples and declined ones: each is reported once, with the status
+    and the pixels it has in a call of its own, and a second identical call repeats the first."""
+    from conftest import load_decode_case
+    from nvimagecodec_amd import abi as A
+    lib, inst, dec = plugin
+    U16, U8 = A.SAMPLE_DATA_TYPE_UINT16, A.SAMPLE_DATA_TYPE_UINT8
+    entries = json.load(open(os.path.join(GOLDEN, "manifest.json")))["decode"]
+    (dct_a, want_a), (dct_b, want_b) = (load_decode_case(next(e for e in entries if e["name"] == name))
+                                        for name in ("s64x48_420_base_q90", "s50x37_420_base_q90"))
+    gray, want_gray = noise_file(71, 70, 90, 1, 4, precision=12)
+    rgb, want_rgb = noise_file(72, 66, 70, 3, 1)
+    small, want_small = noise_file(73, 9, 20, 1, 7, precision=8)
+    cut = gray[:(gray.index(b"\xff\xda") + len(gray)) // 2]  # ends in the middle of the scan
+    rgb_of = (A.SAMPLEFORMAT_I_RGB, 1, 3, U8)
+
+    def one_call():
+        outs = [torch.zeros(shape, dtype=dtype, device="cuda:0")
+                for shape, dtype in (((48, 64, 3), torch.uint8), ((70, 90), torch.uint16), ((66, 70, 3), torch.uint16), ((37, 50, 3), torch.uint8),
+                                     ((3, 66, 70), torch.uint16), ((9, 20), torch.uint8), ((70, 90), torch.uint16), ((70, 90), torch.uint16))]
+        ptr = [o.data_ptr() for o in outs]
+        statuses = plugin_decode_batch(lib, dec, inst, [
+            (dct_a, 48, 64) + rgb_of + (ptr[0], 192, A.COLORSPEC_SRGB, None),
+            (gray, 70, 90, A.SAMPLEFORMAT_P_Y, 1, 1, U16, ptr[1], 180, None, None),
+            (rgb, 66, 70, A.SAMPLEFORMAT_I_UNCHANGED, 1, 3, U16, ptr[2], 420, None, None),
+            (dct_b, 37, 50) + rgb_of + (ptr[3], 150, A.COLORSPEC_SRGB, None),
+            (rgb, 66, 70, A.SAMPLEFORMAT_P_UNCHANGED, 3, 1, U16, ptr[4], 140, None, None),
+            (small, 9, 20, A.SAMPLEFORMAT_P_Y, 1, 1, U8, ptr[5], 20, None, None),
+            (gray, 70, 90, A.SAMPLEFORMAT_P_Y, 1, 1, U8, ptr[6], 180, None, None),   # twelve bits are not offered as bytes
+            (cut, 70, 90, A.SAMPLEFORMAT_P_Y, 1, 1, U16, ptr[7], 180, None, None)])
+        torch.cuda.synchronize()
+        return statuses, [o.cpu().numpy() for o in outs]
+
+    double_reports = lib.hipjpegTestDoubleReports()
+    statuses, outs = one_call()
+    assert statuses[:6] == [A.PS_SUCCESS] * 6
+    assert statuses[6] & A.PS_SAMPLE_TYPE_UNSUPPORTED == A.PS_SAMPLE_TYPE_UNSUPPORTED
+    assert statuses[7] == A.PS_IMAGE_CORRUPTED  # what the decoder said of it before both routes shared their sample path
+    assert np.array_equal(outs[0], want_a) and np.array_equal(outs[3], want_b)
+    assert np.array_equal(outs[1], want_gray[:, :, 0])
+    assert np.array_equal(outs[2], want_rgb) and np.array_equal(np.moveaxis(outs[4], 0, 2), want_rgb)
+    assert np.array_equal(outs[5], want_small[:, :, 0])
+    assert not outs[6].any()  # a declined sample writes nothing
+    again, outs_again = one_call()
+    assert again == statuses
+    for a, b in zip(outs, outs_again):
+        assert np.array_equal(a, b)
+    assert lib.hipjpegTestDoubleReports() == double_reports
+
+
+def test_a_lossless_file_is_read_through_the_read_fallback(torch, tmp_path):
+    """File streams offer no map(): the lossless route reads the bitstream into a copy of its own, as the DCT route does
+    (test_gpu_plugin.py::test_read_from_file_uses_read_fallback)."""
+    from nvimagecodec_amd import api
+    rgb, want_rgb = noise_file(72, 66, 70, 3, 1)
+    p = tmp_path / "x.jpg"
+    p.write_bytes(rgb)
+    with api.Decoder() as dec:
+        im = dec.read(str(p), params=api.DecodeParams(allow_any_depth=True, color_spec=api.ColorSpec.UNCHANGED))
+        torch.cuda.synchronize()
+        assert im is not None and im.dtype == np.uint16
+        assert np.array_equal(im.cpu()._array, want_rgb)
 
 
 def test_api_decoder_with_allow_any_depth(torch):
