@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "coefficient_kernels.h"
+#include "kernel_common.h"
 
 namespace hipjpeg {
 
@@ -73,30 +74,6 @@ constexpr PieceOffsets make_row_offsets_zigzag()
     return t;
 }
 __device__ const PieceOffsets kRowOffsetsZigzag = make_row_offsets_zigzag();
-
-using lds_char = __attribute__((address_space(3))) char;
-using lds_u16 = __attribute__((address_space(3))) unsigned short;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-using lds_u32x4 = __attribute__((address_space(3))) u32x4;
-// the descriptors' pointers come out of memory as generic ones: say that they point into global memory, so that the loads and stores
-// are global_* instructions (flat ones also count as LDS operations and would tie the two waits together)
-using gbl_u32x4 = __attribute__((address_space(1))) u32x4;
-using gbl_i16 = __attribute__((address_space(1))) int16_t;
-
-// LDS operations of one wave execute in order; only the compiler has to be kept from reordering across the hand-off
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// is either half of a dword, as int16, outside [-1023, 1023]?  (no branches: bitwise ors)
-__device__ __forceinline__ unsigned pair_outside(unsigned w)
-{
-    const int a = (int)(short)(w & 0xFFFFu), b = (int)w >> 16;
-    return (unsigned)(a < -1023) | (unsigned)(a > 1023) | (unsigned)(b < -1023) | (unsigned)(b > 1023);
-}
 
 struct Fetched {
     u32x4 v;

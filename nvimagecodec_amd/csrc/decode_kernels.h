@@ -1,4 +1,5 @@
-// decode_kernels.h -- host-callable launchers of the decode kernels (implemented in decode_kernels.hip).
+// decode_kernels.h -- host-callable launchers of the decode kernels (implemented in decode_kernels.hip; those of the kernels that read
+// finished planes -- K3, CMYK, scaled colour, geometry -- in plane_color_kernels.hip).
 // `stream` is a hipStream_t passed as void* so that plain C++ translation units need no HIP headers.
 #pragma once
 #include "device_layout.h"

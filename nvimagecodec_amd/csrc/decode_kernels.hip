@@ -17,20 +17,20 @@
 //     (libjpeg "fancy" triangle filters), YCbCr->RGB and the output store; interleaved RGB rows are staged in LDS and
 //     leave the wave as fully coalesced 16-byte stores.
 //   * work is described by WorkUnit tables so a batch of different-shaped images is ONE launch per kernel.
+// This file holds the kernels that take coefficient blocks: K1, K2, their fast-IDCT and FUSED builds and the reduced IDCTs.  The
+// kernels that read finished planes (K3, CMYK, the scaled colour stage, the geometry pass) are in plane_color_kernels.hip.
 //
 // Arithmetic is the integer arithmetic of libjpeg-turbo's jidctint-{sse2,avx2}.asm / jdsample.c / jdcolor.c, restated; results
 // are compared bit-for-bit with the CPU oracle and with vectors from the library itself in tests/.
 #include <hip/hip_runtime.h>
 
-#include "decode_kernels.h"
-#include "device_layout.h"
+#include "decode_kernel_common.h"
 #include "huffman_gpu_core.h"
 
 namespace hipjpeg {
 
 namespace {
 
-constexpr int kThreads = 256;
 #ifndef HJ_MIN_WAVES
 #define HJ_MIN_WAVES 4
 #endif
@@ -39,12 +39,6 @@ constexpr int kThreads = 256;
 #endif
 constexpr int kBlocksPerWave = 32;     // two lanes per block
 constexpr int kLdsBlockStride = 144;   // 128 B of coefficients + 16 B pad -> conflict-free ds_read_b128 at this lane stride
-
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned int;
-// Explicitly GLOBAL pointers for the hot loads and stores: through the generic pointers of the descriptors hipcc emits FLAT
-// instructions (64-bit address arithmetic per access, and they count against the LDS counter as well).
-#define HJ_GLOBAL __attribute__((address_space(1)))
 
 constexpr int F_0_298 = 2446, F_0_390 = 3196, F_0_541 = 4433, F_0_765 = 6270, F_0_899 = 7373, F_1_175 = 9633;
 constexpr int F_1_501 = 12299, F_1_847 = 15137, F_1_961 = 16069, F_2_053 = 16819, F_2_562 = 20995, F_3_072 = 25172;
@@ -83,18 +77,8 @@ __device__ __forceinline__ unsigned sat_pk4(unsigned a, unsigned b)
     return r;
 }
 
-__device__ __forceinline__ unsigned pack4(int a, int b, int c, int d) { return (unsigned)a | ((unsigned)b << 8) | ((unsigned)c << 16) | ((unsigned)d << 24); }
-
 // value held by the other lane of the pair (quad_perm [1,0,3,2])
 __device__ __forceinline__ int pair_swap(int v) { return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true); }
-
-__device__ __forceinline__ void wave_lds_fence()
-{
-    // LDS operations of one wave execute in order; only the compiler has to be kept from reordering across the hand-off
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ---- FUSED builds (round 3): the coefficient blocks come straight from the bitstream ------------------------------------------
 // For images whose entropy stage runs on the GPU the block pass of gpu_huffman.hip used to write every coefficient block to HBM
@@ -103,7 +87,6 @@ __device__ __forceinline__ void wave_lds_fence()
 // (huffman_gpu_core.h decode_block: one lane per block from the start position the position pass recorded; bitstream through the
 // vector cache, lookup tables in LDS), and everything behind the slots -- the two-lane IDCT, upsampling, colour, stores -- is the
 // same code.  DC values come from the compact DC planes as for every GPU-decoded image (the DC pass has run before).
-#define HJ_LDS __attribute__((address_space(3)))
 struct FusedShared {
     uint32_t tsel[10];
     uint32_t zz[16];
@@ -1073,169 +1056,9 @@ __global__ __launch_bounds__(kThreads, HJ_MIN_WAVES_FUSED) void luma_color_fused
 }
 
 // ------------------------------------------------------------------------------------------------
-// K3: generic colour stage for layouts the fused kernel does not cover (4:1:1, 4:1:0, ...): every component is in a
-// plane already; libjpeg upsamples those by plain replication (jdsample.c int_upsample).  One thread = one pixel.
-// The unit table is reused: block_base = pixel row, comp unused.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void generic_color_kernel(const DecodeImage* __restrict__ images, const WorkUnit* __restrict__ units)
-{
-    const WorkUnit u = units[blockIdx.x];
-    const DecodeImage& im = images[u.image];
-    const int W = im.width, H = im.height;
-    const int y = u.block_base;
-    if (y >= H) return;
-    const int fmt = im.out_format;
-    const bool planar = fmt == kOutPlanarRGB || fmt == kOutPlanarBGR;
-    const bool bgr = fmt == kOutInterleavedBGR || fmt == kOutPlanarBGR;
-    // Only three-component images take this path (gray goes through luma_color_kernel<0,0>), so the component
-    // index is a compile-time constant everywhere below.
-    const int hmax = im.hmax, vmax = im.vmax;
-    const uint8_t* row0 = im.comp[0].plane + (size_t)(y * im.comp[0].v / vmax) * im.comp[0].plane_pitch;
-    const uint8_t* row1 = im.comp[1].plane + (size_t)(y * im.comp[1].v / vmax) * im.comp[1].plane_pitch;
-    const uint8_t* row2 = im.comp[2].plane + (size_t)(y * im.comp[2].v / vmax) * im.comp[2].plane_pitch;
-    const int h0 = im.comp[0].h, h1 = im.comp[1].h, h2 = im.comp[2].h;
-    for (int x = threadIdx.x; x < W; x += kThreads) {
-        int s[3];
-        s[0] = row0[x * h0 / hmax];
-        s[1] = row1[x * h1 / hmax];
-        s[2] = row2[x * h2 / hmax];
-        int R, G, B;
-        if (im.color_model == 1) {
-            int rr = (s[2] * 91881 + (32768 - 128 * 91881)) >> 16;
-            int bb = (s[1] * 116130 + (32768 - 128 * 116130)) >> 16;
-            int gg = (s[1] * -22554 + s[2] * -46802 + (32768 + 128 * 22554 + 128 * 46802)) >> 16;
-            R = min(max(s[0] + rr, 0), 255);
-            G = min(max(s[0] + gg, 0), 255);
-            B = min(max(s[0] + bb, 0), 255);
-        } else {
-            R = s[0];
-            G = s[1];
-            B = s[2];
-        }
-        if (bgr) {
-            int t = R;
-            R = B;
-            B = t;
-        }
-        if (planar) {
-            im.out[0][(size_t)y * im.out_pitch[0] + x] = (uint8_t)R;
-            im.out[1][(size_t)y * im.out_pitch[1] + x] = (uint8_t)G;
-            im.out[2][(size_t)y * im.out_pitch[2] + x] = (uint8_t)B;
-        } else {
-            uint8_t* p = im.out[0] + (size_t)y * im.out_pitch[0] + (size_t)x * 3;
-            p[0] = (uint8_t)R;
-            p[1] = (uint8_t)G;
-            p[2] = (uint8_t)B;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Four-component frames (CMYK, YCCK): every component sits in its plane; the kernel brings each to full size the way
-// libjpeg-turbo does (jdsample.c: h2v1 / h2v2 / h1v2 triangle filters when fancy upsampling is on and they apply, else
-// replication), turns a YCCK frame into CMYK (jdcolor.c ycck_cmyk_convert) and then applies the reference extension's own
-// CMYK -> RGB step (extensions/libjpeg_turbo/jpeg_mem.cpp:292-337): with an Adobe marker r = k*c/255, without one
-// r = (255-k)*(255-c)/255; P_Y = (uint8)(0.299f r + 0.587f g + 0.114f b).  One thread = one pixel; rare path.
-// ------------------------------------------------------------------------------------------------
-template <int C>
-__device__ __forceinline__ int upsampled_sample(const DecodeImage& im, int x, int y, bool fancy)
-{
-    const DecodeComponent& k = im.comp[C];
-    const int fx = (int)im.hmax / (int)k.h, fy = (int)im.vmax / (int)k.v;
-    const int dw = k.samp_w, dh = k.samp_h;
-    const uint8_t* plane = k.plane;
-    const size_t pitch = k.plane_pitch;
-    if (fx == 1 && fy == 1) return plane[(size_t)y * pitch + x];
-    if (fx == 2 && fy == 1 && fancy && dw > 2) {
-        const uint8_t* p = plane + (size_t)y * pitch;
-        const int i = x >> 1;
-        if (x == 0) return p[0];
-        if (x == 2 * dw - 1) return p[dw - 1];
-        return (x & 1) ? (3 * p[i] + p[i + 1] + 2) >> 2 : (3 * p[i] + p[i - 1] + 1) >> 2;
-    }
-    if (fx == 2 && fy == 2 && fancy && dw > 2) {
-        const int r0 = y >> 1, r1 = min(max((y & 1) ? r0 + 1 : r0 - 1, 0), dh - 1);
-        const uint8_t* p0 = plane + (size_t)r0 * pitch;
-        const uint8_t* p1 = plane + (size_t)r1 * pitch;
-        const int i = x >> 1, cs = 3 * p0[i] + p1[i];
-        if (x == 0) return (cs * 4 + 8) >> 4;
-        if (x == 2 * dw - 1) return (cs * 4 + 7) >> 4;
-        return (x & 1) ? (3 * cs + (3 * p0[i + 1] + p1[i + 1]) + 7) >> 4 : (3 * cs + (3 * p0[i - 1] + p1[i - 1]) + 8) >> 4;
-    }
-    if (fx == 1 && fy == 2 && fancy) {
-        const int r0 = y >> 1, r1 = min(max((y & 1) ? r0 + 1 : r0 - 1, 0), dh - 1);
-        return (3 * plane[(size_t)r0 * pitch + x] + plane[(size_t)r1 * pitch + x] + ((y & 1) ? 2 : 1)) >> 2;
-    }
-    return plane[(size_t)(y / fy) * pitch + x / fx];
-}
-
-__global__ __launch_bounds__(kThreads) void cmyk_color_kernel(const DecodeImage* __restrict__ images, const WorkUnit* __restrict__ units)
-{
-    const WorkUnit u = units[blockIdx.x];
-    const DecodeImage& im = images[u.image];
-    const int W = im.width, H = im.height;
-    const int y = u.block_base;
-    if (y >= H) return;
-    const int fmt = im.out_format;
-    const bool planar = fmt == kOutPlanarRGB || fmt == kOutPlanarBGR;
-    const bool bgr = fmt == kOutInterleavedBGR || fmt == kOutPlanarBGR;
-    const bool fancy = (im.flags & kFlagFancyUpsampling) != 0, adobe = (im.flags & kFlagAdobeMarker) != 0;
-    const bool ycck = im.color_model == 4;
-    for (int x = threadIdx.x; x < W; x += kThreads) {
-        int c = upsampled_sample<0>(im, x, y, fancy), m = upsampled_sample<1>(im, x, y, fancy), ye = upsampled_sample<2>(im, x, y, fancy);
-        const int k = upsampled_sample<3>(im, x, y, fancy);
-        if (ycck) {
-            const int rr = (ye * 91881 + (32768 - 128 * 91881)) >> 16;
-            const int bb = (m * 116130 + (32768 - 128 * 116130)) >> 16;
-            const int gg = (m * -22554 + ye * -46802 + (32768 + 128 * 22554 + 128 * 46802)) >> 16;
-            const int r = min(max(c + rr, 0), 255), g = min(max(c + gg, 0), 255), b = min(max(c + bb, 0), 255);
-            c = 255 - r;
-            m = 255 - g;
-            ye = 255 - b;
-        }
-        int R, G, B;
-        if (adobe) {
-            R = (k * c) / 255;
-            G = (k * m) / 255;
-            B = (k * ye) / 255;
-        } else {
-            R = (255 - k) * (255 - c) / 255;
-            G = (255 - k) * (255 - m) / 255;
-            B = (255 - k) * (255 - ye) / 255;
-        }
-        if (fmt == kOutY) {
-            // three products and two sums, each rounded to float on its own, as the reference's x86 build computes them
-            // (a fused multiply-add would round differently)
-            float yf;
-            {
-#pragma clang fp contract(off)
-                const float pr = 0.299f * (float)R, pg = 0.587f * (float)G, pb = 0.114f * (float)B;
-                yf = (pr + pg) + pb;
-            }
-            im.out[0][(size_t)y * im.out_pitch[0] + x] = (uint8_t)yf;
-            continue;
-        }
-        if (bgr) {
-            const int t = R;
-            R = B;
-            B = t;
-        }
-        if (planar) {
-            im.out[0][(size_t)y * im.out_pitch[0] + x] = (uint8_t)R;
-            im.out[1][(size_t)y * im.out_pitch[1] + x] = (uint8_t)G;
-            im.out[2][(size_t)y * im.out_pitch[2] + x] = (uint8_t)B;
-        } else {
-            uint8_t* p = im.out[0] + (size_t)y * im.out_pitch[0] + (size_t)x * 3;
-            p[0] = (uint8_t)R;
-            p[1] = (uint8_t)G;
-            p[2] = (uint8_t)B;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Scaled decode (hipjpegDecodeBatchSetScales: 1/2, 1/4, 1/8 -- libjpeg's scale_num / scale_denom).  Kernels of their own beside K1 / K2 /
-// K3, whose code stays as it is.  A component of DCT_scaled_size s (DecodeComponent::scaled) turns every block into s x s samples:
+// Scaled decode (hipjpegDecodeBatchSetScales: 1/2, 1/4, 1/8 -- libjpeg's scale_num / scale_denom).  A kernel of its own beside K1 / K2,
+// whose code stays as it is (scaled_color_kernel of plane_color_kernels.hip then brings the planes to the output).
+// A component of DCT_scaled_size s (DecodeComponent::scaled) turns every block into s x s samples:
 //   s = 8  K1 (idct_plane_kernel, kToPlane): the routine of dct_method
 //   s = 4  jsimd_idct_4x4_sse2 restated: pmullw dequantization (low 16 bits, ISLOW tables whatever dct_method says), 32-bit
 //          multiply-adds that WRAP (paddd / psubd; the C routine's 64-bit sums do not), packssdw between the passes; a block whose rows
@@ -1410,273 +1233,6 @@ __global__ __launch_bounds__(kThreads) void idct_reduced_plane_kernel(const Deco
     }
 }
 
-// From the planes of a scaled image to its output.  jdsample.c jinit_upsampler on the scaled groups: a component of DCT_scaled_size s
-// has h_in = h s / k samples per group against h_out = hmax, so its factors are fx = hmax k / (h s), fy = vmax k / (v s); the filter
-// choice is upsampled_sample()'s (the host has cleared kFlagFancyUpsampling where k = 1: libjpeg does no fancy upsampling there).
-struct ScaledPlane {
-    const uint8_t* plane;
-    unsigned pitch;
-    int dw, dh, fx, fy;
-};
-// (the component index is a compile-time constant: a run-time one would reach the descriptor through a scalar load with a register offset)
-template <int C>
-__device__ __forceinline__ ScaledPlane scaled_plane(const DecodeImage& im)
-{
-    const DecodeComponent& k = im.comp[C];
-    // (a gray image's unused components are zeros: max keeps the divisions defined)
-    return ScaledPlane{k.plane, k.plane_pitch, (int)k.samp_w, (int)k.samp_h, (int)(im.hmax * im.scale_k) / max((int)(k.h * k.scaled), 1),
-                       (int)(im.vmax * im.scale_k) / max((int)(k.v * k.scaled), 1)};
-}
-__device__ __forceinline__ int scaled_sample(const ScaledPlane& k, int x, int y, bool fancy)
-{
-    const int fx = k.fx, fy = k.fy, dw = k.dw, dh = k.dh;
-    const uint8_t* plane = k.plane;
-    const size_t pitch = k.pitch;
-    if (fx == 1 && fy == 1) return plane[(size_t)y * pitch + x];
-    if (fx == 2 && fy == 1 && fancy && dw > 2) {
-        const uint8_t* p = plane + (size_t)y * pitch;
-        const int i = x >> 1;
-        if (x == 0) return p[0];
-        if (x == 2 * dw - 1) return p[dw - 1];
-        return (x & 1) ? (3 * p[i] + p[i + 1] + 2) >> 2 : (3 * p[i] + p[i - 1] + 1) >> 2;
-    }
-    if (fx == 2 && fy == 2 && fancy && dw > 2) {
-        const int r0 = y >> 1, r1 = min(max((y & 1) ? r0 + 1 : r0 - 1, 0), dh - 1);
-        const uint8_t* p0 = plane + (size_t)r0 * pitch;
-        const uint8_t* p1 = plane + (size_t)r1 * pitch;
-        const int i = x >> 1, cs = 3 * p0[i] + p1[i];
-        if (x == 0) return (cs * 4 + 8) >> 4;
-        if (x == 2 * dw - 1) return (cs * 4 + 7) >> 4;
-        return (x & 1) ? (3 * cs + (3 * p0[i + 1] + p1[i + 1]) + 7) >> 4 : (3 * cs + (3 * p0[i - 1] + p1[i - 1]) + 8) >> 4;
-    }
-    if (fx == 1 && fy == 2 && fancy) {
-        const int r0 = y >> 1, r1 = min(max((y & 1) ? r0 + 1 : r0 - 1, 0), dh - 1);
-        return (3 * plane[(size_t)r0 * pitch + x] + plane[(size_t)r1 * pitch + x] + ((y & 1) ? 2 : 1)) >> 2;
-    }
-    return plane[(size_t)(y / fy) * pitch + x / fx];
-}
-
-// Three samples of one pixel -> its three output channels in store order
-__device__ __forceinline__ void scaled_pixel(int s0, int s1, int s2, bool gray, bool ycc, bool bgr, int& a, int& b, int& c)
-{
-    int R = s0, G = s0, B = s0;
-    if (!gray) {
-        if (ycc) {
-            const int rr = (s2 * 91881 + (32768 - 128 * 91881)) >> 16;
-            const int bb = (s1 * 116130 + (32768 - 128 * 116130)) >> 16;
-            const int gg = (s1 * -22554 + s2 * -46802 + (32768 + 128 * 22554 + 128 * 46802)) >> 16;
-            R = min(max(s0 + rr, 0), 255);
-            G = min(max(s0 + gg, 0), 255);
-            B = min(max(s0 + bb, 0), 255);
-        } else {
-            G = s1;
-            B = s2;
-        }
-    }
-    a = bgr ? B : R;
-    b = G;
-    c = bgr ? R : B;
-}
-
-// four bytes to dst: one dword where the row is 4-byte aligned and all four belong to the picture, single bytes at a ragged edge
-__device__ __forceinline__ void store_px4(uint8_t* dst, unsigned v, bool whole)
-{
-    if (whole)
-        *reinterpret_cast<unsigned*>(dst) = v;
-    else
-        dst[0] = (uint8_t)v;  // (the caller has shifted the byte it wants into place)
-}
-
-// One workgroup = kScaledRowsPerUnit pixel rows, a wave per row in turn.  Where no component is left to upsample (gray, 4:4:4 and 4:2:0
-// at every scale: libjpeg gives the chroma the larger IDCT instead) and the caller's rows are 16-byte aligned, a lane takes SIXTEEN
-// pixels: one 16-byte load per plane, three 16-byte stores (interleaved) or one per plane -- the kernel is bound by the bytes it has in
-// flight, not by arithmetic.  What is left of the row, and every other picture, goes in groups of FOUR pixels: a dword load per plane or
-// scaled_sample() per pixel, dword stores where the rows are 4-byte aligned, single bytes at a ragged edge.  Everything that picks a
-// path -- format, colour model, filter, alignment -- is the same for the whole workgroup.
-__global__ __launch_bounds__(kThreads) void scaled_color_kernel(const DecodeImage* __restrict__ images, const WorkUnit* __restrict__ units)
-{
-    const WorkUnit u = units[blockIdx.x];
-    const DecodeImage& im = images[u.image];
-    const int W = im.width, H = im.height;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int fmt = im.out_format;
-    const bool planar = fmt == kOutPlanarRGB || fmt == kOutPlanarBGR, only_y = fmt == kOutY;
-    const bool bgr = fmt == kOutInterleavedBGR || fmt == kOutPlanarBGR;
-    const bool fancy = (im.flags & kFlagFancyUpsampling) != 0;
-    const bool gray = im.ncomp == 1 || only_y, ycc = im.color_model == 1;
-    const ScaledPlane k0 = scaled_plane<0>(im), k1 = scaled_plane<1>(im), k2 = scaled_plane<2>(im);
-    const bool direct = k0.fx == 1 && k0.fy == 1 && (gray || (k1.fx == 1 && k1.fy == 1 && k2.fx == 1 && k2.fy == 1));
-    uint8_t* const out0 = im.out[0];
-    uint8_t* const out1 = im.out[1];
-    uint8_t* const out2 = im.out[2];
-    const unsigned op0 = im.out_pitch[0], op1 = im.out_pitch[1], op2 = im.out_pitch[2];
-    const bool aligned = planar ? ((((uintptr_t)out0 | (uintptr_t)out1 | (uintptr_t)out2 | op0 | op1 | op2) & 3) == 0) : ((((uintptr_t)out0 | op0) & 3) == 0);
-    const bool aligned16 = planar ? ((((uintptr_t)out0 | (uintptr_t)out1 | (uintptr_t)out2 | op0 | op1 | op2) & 15) == 0) : ((((uintptr_t)out0 | op0) & 15) == 0);
-    const int wide_groups = (direct && aligned16) ? (W >> 4) : 0;
-    const int groups = (W + 3) >> 2, row_end = min((int)u.block_base + kScaledRowsPerUnit, H);
-    for (int y = (int)u.block_base + wave; y < row_end; y += kThreads / 64) {
-        for (int g = lane; g < wide_groups; g += 64) {
-            const int x = g * 16;
-            // (planes are 16-byte aligned, pitch included, and x + 16 <= W lies inside the row)
-            const u32x4 v0 = *reinterpret_cast<const u32x4*>(k0.plane + (size_t)y * k0.pitch + x);
-            if (only_y) {
-                *reinterpret_cast<u32x4*>(out0 + (size_t)y * op0 + x) = v0;
-                continue;
-            }
-            u32x4 v1 = {0u, 0u, 0u, 0u}, v2 = {0u, 0u, 0u, 0u};
-            if (!gray) {
-                v1 = *reinterpret_cast<const u32x4*>(k1.plane + (size_t)y * k1.pitch + x);
-                v2 = *reinterpret_cast<const u32x4*>(k2.plane + (size_t)y * k2.pitch + x);
-            }
-            const unsigned w0[4] = {v0.x, v0.y, v0.z, v0.w}, w1[4] = {v1.x, v1.y, v1.z, v1.w}, w2[4] = {v2.x, v2.y, v2.z, v2.w};
-            unsigned o[12];  // interleaved: the 48 bytes in order; planar: [0..3] first plane, [4..7] second, [8..11] third
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                int a[4], b[4], c[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-                    scaled_pixel((int)((w0[q] >> (8 * i)) & 255u), (int)((w1[q] >> (8 * i)) & 255u), (int)((w2[q] >> (8 * i)) & 255u), gray, ycc, bgr, a[i], b[i], c[i]);
-                if (planar) {
-                    o[q] = pack4(a[0], a[1], a[2], a[3]);
-                    o[4 + q] = pack4(b[0], b[1], b[2], b[3]);
-                    o[8 + q] = pack4(c[0], c[1], c[2], c[3]);
-                } else {
-                    o[3 * q] = pack4(a[0], b[0], c[0], a[1]);
-                    o[3 * q + 1] = pack4(b[1], c[1], a[2], b[2]);
-                    o[3 * q + 2] = pack4(c[2], a[3], b[3], c[3]);
-                }
-            }
-            const u32x4 s0 = {o[0], o[1], o[2], o[3]}, s1 = {o[4], o[5], o[6], o[7]}, s2 = {o[8], o[9], o[10], o[11]};
-            if (planar) {
-                *reinterpret_cast<u32x4*>(out0 + (size_t)y * op0 + x) = s0;
-                *reinterpret_cast<u32x4*>(out1 + (size_t)y * op1 + x) = s1;
-                *reinterpret_cast<u32x4*>(out2 + (size_t)y * op2 + x) = s2;
-            } else {
-                u32x4* q = reinterpret_cast<u32x4*>(out0 + (size_t)y * op0 + (size_t)x * 3);  // (x * 3 is a multiple of 48)
-                q[0] = s0;
-                q[1] = s1;
-                q[2] = s2;
-            }
-        }
-        for (int g = wide_groups * 4 + lane; g < groups; g += 64) {
-            const int x = g * 4, n = min(4, W - x);
-            int s0[4], s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-            if (direct) {
-                // (planes are 16-byte aligned with 16 bytes of slack per row: an aligned dword that starts inside the row is in bounds)
-                const unsigned v0 = *reinterpret_cast<const unsigned*>(k0.plane + (size_t)y * k0.pitch + x);
-                unsigned v1 = 0, v2 = 0;
-                if (!gray) {
-                    v1 = *reinterpret_cast<const unsigned*>(k1.plane + (size_t)y * k1.pitch + x);
-                    v2 = *reinterpret_cast<const unsigned*>(k2.plane + (size_t)y * k2.pitch + x);
-                }
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    s0[i] = (int)((v0 >> (8 * i)) & 255u);
-                    s1[i] = (int)((v1 >> (8 * i)) & 255u);
-                    s2[i] = (int)((v2 >> (8 * i)) & 255u);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const int xi = min(x + i, W - 1);  // (past the right edge: a pixel that exists, its value is not stored)
-                    s0[i] = scaled_sample(k0, xi, y, fancy);
-                    if (!gray) {
-                        s1[i] = scaled_sample(k1, xi, y, fancy);
-                        s2[i] = scaled_sample(k2, xi, y, fancy);
-                    }
-                }
-            }
-            const bool whole = aligned && n == 4;
-            if (only_y) {
-                uint8_t* d = out0 + (size_t)y * op0 + x;
-                const unsigned v = pack4(s0[0], s0[1], s0[2], s0[3]);
-                store_px4(d, v, whole);
-#pragma unroll
-                for (int i = 1; i < 4; i++)
-                    if (!whole && i < n) d[i] = (uint8_t)(v >> (8 * i));
-                continue;
-            }
-            int a[4], b[4], c[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) scaled_pixel(s0[i], s1[i], s2[i], gray, ycc, bgr, a[i], b[i], c[i]);
-            if (planar) {
-                uint8_t* d0 = out0 + (size_t)y * op0 + x;
-                uint8_t* d1 = out1 + (size_t)y * op1 + x;
-                uint8_t* d2 = out2 + (size_t)y * op2 + x;
-                const unsigned va = pack4(a[0], a[1], a[2], a[3]), vb = pack4(b[0], b[1], b[2], b[3]), vc = pack4(c[0], c[1], c[2], c[3]);
-                store_px4(d0, va, whole);
-                store_px4(d1, vb, whole);
-                store_px4(d2, vc, whole);
-#pragma unroll
-                for (int i = 1; i < 4; i++)
-                    if (!whole && i < n) {
-                        d0[i] = (uint8_t)(va >> (8 * i));
-                        d1[i] = (uint8_t)(vb >> (8 * i));
-                        d2[i] = (uint8_t)(vc >> (8 * i));
-                    }
-            } else {
-                uint8_t* d = out0 + (size_t)y * op0 + (size_t)x * 3;
-                if (whole) {
-                    unsigned* q = reinterpret_cast<unsigned*>(d);  // (x * 3 is a multiple of 12)
-                    q[0] = pack4(a[0], b[0], c[0], a[1]);
-                    q[1] = pack4(b[1], c[1], a[2], b[2]);
-                    q[2] = pack4(c[2], a[3], b[3], c[3]);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; i++)
-                        if (i < n) {
-                            d[3 * i] = (uint8_t)a[i];
-                            d[3 * i + 1] = (uint8_t)b[i];
-                            d[3 * i + 2] = (uint8_t)c[i];
-                        }
-                }
-            }
-        }
-    }
-}
-
-// Geometry pass: region of interest + EXIF orientation (DecodeBatch plans it for the images that ask for it; the pixel
-// kernels have written those images into an intermediate buffer in stored-image coordinates).
-// Upright pixel (ox, oy) comes from region pixel (u, v):
-//   1: (ox, oy)            2: (rw-1-ox, oy)        3: (rw-1-ox, rh-1-oy)   4: (ox, rh-1-oy)
-//   5: (oy, ox)            6: (oy, rh-1-ox)        7: (rw-1-oy, rh-1-ox)   8: (rw-1-oy, ox)
-// (EXIF 2.32 orientation tag; 5 = transpose, 6 = stored picture must be turned 90 degrees clockwise, 7 = transverse,
-//  8 = 270 degrees clockwise).  One workgroup = kTransformRowsPerUnit output rows; lanes walk along output rows, so the
-// writes are coalesced whatever the reads look like.
-__global__ __launch_bounds__(kThreads) void transform_kernel(const TransformImage* __restrict__ images, const WorkUnit* __restrict__ units)
-{
-    const WorkUnit wu = units[blockIdx.x];
-    const TransformImage& t = images[wu.image];
-    const int rw = t.rw, rh = t.rh, ow = t.out_w, o = t.orientation;
-    const int row_end = min((int)wu.block_base + kTransformRowsPerUnit, t.out_h);
-    for (int oy = (int)wu.block_base; oy < row_end; oy++) {
-        for (int ox = threadIdx.x; ox < ow; ox += kThreads) {
-            int u, v;
-            switch (o) {
-            case 2: u = rw - 1 - ox; v = oy; break;
-            case 3: u = rw - 1 - ox; v = rh - 1 - oy; break;
-            case 4: u = ox; v = rh - 1 - oy; break;
-            case 5: u = oy; v = ox; break;
-            case 6: u = oy; v = rh - 1 - ox; break;
-            case 7: u = rw - 1 - oy; v = rh - 1 - ox; break;
-            case 8: u = rw - 1 - oy; v = ox; break;
-            default: u = ox; v = oy; break;
-            }
-            const int sx = t.x0 + u, sy = t.y0 + v;
-            if (t.bpp == 3) {
-                const uint8_t* s = t.src[0] + (size_t)sy * t.src_pitch[0] + (size_t)sx * 3;
-                uint8_t* d = t.dst[0] + (size_t)oy * t.dst_pitch[0] + (size_t)ox * 3;
-                d[0] = s[0];
-                d[1] = s[1];
-                d[2] = s[2];
-            } else {
-                for (int p = 0; p < t.nplanes; p++)
-                    t.dst[p][(size_t)oy * t.dst_pitch[p] + ox] = t.src[p][(size_t)sy * t.src_pitch[p] + sx];
-            }
-        }
-    }
-}
-
 }  // namespace
 
 int launch_idct_plane(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream, bool fast_idct)
@@ -1696,114 +1252,74 @@ int launch_idct_plane_fused(const DecodeImage* images, const WorkUnit* units, in
     return (int)hipGetLastError();
 }
 
-template <int LAYOUT>
-static int launch_luma_fused_t(int hs, int vs, const DecodeImage* images, const WorkUnit* units, int nunits, HuffImage* himages, unsigned pool_bytes, hipStream_t s)
+// K2 comes in three builds, each a kernel template over <HS, VS, LAYOUT>.  The FUSED one takes dynamic LDS and, behind images and
+// units, the HuffImage array: `tail` carries whatever follows.
+enum LumaBuild : int { kBuildIslow, kBuildIfast, kBuildFused };
+
+template <LumaBuild BUILD, int HS, int VS, int LAYOUT, typename... Tail>
+static void launch_luma_one(const DecodeImage* images, const WorkUnit* units, int nunits, unsigned lds_bytes, hipStream_t s, Tail... tail)
+{
+    if constexpr (BUILD == kBuildFused)
+        hipLaunchKernelGGL((luma_color_fused_kernel<HS, VS, LAYOUT>), dim3(nunits), dim3(kThreads), lds_bytes, s, images, units, tail...);
+    else if constexpr (BUILD == kBuildIfast)
+        hipLaunchKernelGGL((luma_color_ifast_kernel<HS, VS, LAYOUT>), dim3(nunits), dim3(kThreads), lds_bytes, s, images, units, tail...);
+    else
+        hipLaunchKernelGGL((luma_color_kernel<HS, VS, LAYOUT>), dim3(nunits), dim3(kThreads), lds_bytes, s, images, units, tail...);
+}
+
+// the run-time chroma factors -> the instantiation
+template <LumaBuild BUILD, int LAYOUT, typename... Tail>
+static int launch_luma_sampling(int hs, int vs, const DecodeImage* images, const WorkUnit* units, int nunits, unsigned lds_bytes, hipStream_t s, Tail... tail)
 {
     if (hs == 0) {
-        if constexpr (LAYOUT != kLayoutAny) return (int)hipErrorInvalidValue;
-        else hipLaunchKernelGGL((luma_color_fused_kernel<0, 0, kLayoutAny>), dim3(nunits), dim3(kThreads), pool_bytes, s, images, units, himages);
+        if constexpr (LAYOUT != kLayoutAny) return (int)hipErrorInvalidValue;  // gray sources have no colour conversion to specialise
+        else launch_luma_one<BUILD, 0, 0, kLayoutAny>(images, units, nunits, lds_bytes, s, tail...);
     } else if (hs == 1 && vs == 1)
-        hipLaunchKernelGGL((luma_color_fused_kernel<1, 1, LAYOUT>), dim3(nunits), dim3(kThreads), pool_bytes, s, images, units, himages);
+        launch_luma_one<BUILD, 1, 1, LAYOUT>(images, units, nunits, lds_bytes, s, tail...);
     else if (hs == 2 && vs == 1)
-        hipLaunchKernelGGL((luma_color_fused_kernel<2, 1, LAYOUT>), dim3(nunits), dim3(kThreads), pool_bytes, s, images, units, himages);
+        launch_luma_one<BUILD, 2, 1, LAYOUT>(images, units, nunits, lds_bytes, s, tail...);
     else if (hs == 2 && vs == 2)
-        hipLaunchKernelGGL((luma_color_fused_kernel<2, 2, LAYOUT>), dim3(nunits), dim3(kThreads), pool_bytes, s, images, units, himages);
+        launch_luma_one<BUILD, 2, 2, LAYOUT>(images, units, nunits, lds_bytes, s, tail...);
     else if (hs == 1 && vs == 2)
-        hipLaunchKernelGGL((luma_color_fused_kernel<1, 2, LAYOUT>), dim3(nunits), dim3(kThreads), pool_bytes, s, images, units, himages);
+        launch_luma_one<BUILD, 1, 2, LAYOUT>(images, units, nunits, lds_bytes, s, tail...);
     else
         return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
+}
+
+// the run-time layout -> the instantiation
+template <LumaBuild BUILD, typename... Tail>
+static int launch_luma_layout(int layout, int hs, int vs, const DecodeImage* images, const WorkUnit* units, int nunits, unsigned lds_bytes, hipStream_t s,
+                              Tail... tail)
+{
+    switch (layout) {
+    case 0: return launch_luma_sampling<BUILD, kLayoutAny>(hs, vs, images, units, nunits, lds_bytes, s, tail...);
+    case 1: return launch_luma_sampling<BUILD, kLayoutInterleaved>(hs, vs, images, units, nunits, lds_bytes, s, tail...);
+    case 2: return launch_luma_sampling<BUILD, kLayoutPlanar>(hs, vs, images, units, nunits, lds_bytes, s, tail...);
+    default: return (int)hipErrorInvalidValue;
+    }
 }
 
 int launch_luma_color_fused(int layout, int hs, int vs, const DecodeImage* images, const WorkUnit* units, int nunits, HuffImage* himages, unsigned pool_bytes,
                             void* stream)
 {
     if (nunits <= 0) return 0;
-    switch (layout) {
-    case 0: return launch_luma_fused_t<kLayoutAny>(hs, vs, images, units, nunits, himages, pool_bytes, (hipStream_t)stream);
-    case 1: return launch_luma_fused_t<kLayoutInterleaved>(hs, vs, images, units, nunits, himages, pool_bytes, (hipStream_t)stream);
-    case 2: return launch_luma_fused_t<kLayoutPlanar>(hs, vs, images, units, nunits, himages, pool_bytes, (hipStream_t)stream);
-    default: return (int)hipErrorInvalidValue;
-    }
-}
-
-// one instantiation of K2: the default (ISLOW) kernel or its fast-IDCT twin
-template <int HS, int VS, int LAYOUT, bool IFAST>
-static void launch_luma_one(const DecodeImage* images, const WorkUnit* units, int nunits, hipStream_t s)
-{
-    if constexpr (IFAST)
-        hipLaunchKernelGGL((luma_color_ifast_kernel<HS, VS, LAYOUT>), dim3(nunits), dim3(kThreads), 0, s, images, units);
-    else
-        hipLaunchKernelGGL((luma_color_kernel<HS, VS, LAYOUT>), dim3(nunits), dim3(kThreads), 0, s, images, units);
-}
-
-template <int LAYOUT, bool IFAST>
-static int launch_luma_color_t(int hs, int vs, const DecodeImage* images, const WorkUnit* units, int nunits, hipStream_t s)
-{
-    if (hs == 0) {
-        if constexpr (LAYOUT != kLayoutAny) return (int)hipErrorInvalidValue;  // gray sources have no colour conversion to specialise
-        else launch_luma_one<0, 0, kLayoutAny, IFAST>(images, units, nunits, s);
-    } else if (hs == 1 && vs == 1)
-        launch_luma_one<1, 1, LAYOUT, IFAST>(images, units, nunits, s);
-    else if (hs == 2 && vs == 1)
-        launch_luma_one<2, 1, LAYOUT, IFAST>(images, units, nunits, s);
-    else if (hs == 2 && vs == 2)
-        launch_luma_one<2, 2, LAYOUT, IFAST>(images, units, nunits, s);
-    else if (hs == 1 && vs == 2)
-        launch_luma_one<1, 2, LAYOUT, IFAST>(images, units, nunits, s);
-    else
-        return (int)hipErrorInvalidValue;
-    return (int)hipGetLastError();
+    return launch_luma_layout<kBuildFused>(layout, hs, vs, images, units, nunits, pool_bytes, (hipStream_t)stream, himages);
 }
 
 int launch_luma_color(int layout, int hs, int vs, const DecodeImage* images, const WorkUnit* units, int nunits, void* stream, bool fast_idct)
 {
     if (nunits <= 0) return 0;
     const hipStream_t s = (hipStream_t)stream;
-    switch (layout) {
-    case 0: return fast_idct ? launch_luma_color_t<kLayoutAny, true>(hs, vs, images, units, nunits, s) : launch_luma_color_t<kLayoutAny, false>(hs, vs, images, units, nunits, s);
-    case 1:
-        return fast_idct ? launch_luma_color_t<kLayoutInterleaved, true>(hs, vs, images, units, nunits, s)
-                         : launch_luma_color_t<kLayoutInterleaved, false>(hs, vs, images, units, nunits, s);
-    case 2:
-        return fast_idct ? launch_luma_color_t<kLayoutPlanar, true>(hs, vs, images, units, nunits, s)
-                         : launch_luma_color_t<kLayoutPlanar, false>(hs, vs, images, units, nunits, s);
-    default: return (int)hipErrorInvalidValue;
-    }
+    return fast_idct ? launch_luma_layout<kBuildIfast>(layout, hs, vs, images, units, nunits, 0u, s)
+                     : launch_luma_layout<kBuildIslow>(layout, hs, vs, images, units, nunits, 0u, s);
 }
 
-int launch_generic_color(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream)
-{
-    if (nunits <= 0) return 0;
-    hipLaunchKernelGGL(generic_color_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
-    return (int)hipGetLastError();
-}
-
-int launch_cmyk_color(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream)
-{
-    if (nunits <= 0) return 0;
-    hipLaunchKernelGGL(cmyk_color_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
-    return (int)hipGetLastError();
-}
 
 int launch_idct_reduced_plane(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream)
 {
     if (nunits <= 0) return 0;
     hipLaunchKernelGGL(idct_reduced_plane_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
-    return (int)hipGetLastError();
-}
-
-int launch_scaled_color(const DecodeImage* images, const WorkUnit* units, int nunits, void* stream)
-{
-    if (nunits <= 0) return 0;
-    hipLaunchKernelGGL(scaled_color_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
-    return (int)hipGetLastError();
-}
-
-int launch_transform(const TransformImage* images, const WorkUnit* units, int nunits, void* stream)
-{
-    if (nunits <= 0) return 0;
-    hipLaunchKernelGGL(transform_kernel, dim3(nunits), dim3(kThreads), 0, (hipStream_t)stream, images, units);
     return (int)hipGetLastError();
 }
 

@@ -402,7 +402,7 @@ void DecodeBatch::prepare(int i, const PlanArgs& a)
         im.pic_w = f.width;
         im.pic_h = f.height;
         if (im.status == HIPJPEG_STATUS_SUCCESS && im.scale_k != 8) {
-            // kernels of their own (decode_kernels.hip, scaled decode); libjpeg does no fancy upsampling at 1/8 (jdsample.c)
+            // kernels of their own (decode_kernels.hip, plane_color_kernels.hip: scaled decode); libjpeg does no fancy upsampling at 1/8 (jdsample.c)
             im.variant = -5;
             im.pic_w = scaled_extent(f.width, im.scale_k);
             im.pic_h = scaled_extent(f.height, im.scale_k);

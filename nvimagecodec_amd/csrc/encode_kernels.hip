@@ -16,6 +16,7 @@
 
 #include "encode_kernels.h"
 #include "encode_layout.h"
+#include "kernel_common.h"
 
 namespace hipjpeg {
 
@@ -24,9 +25,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kTileBX = 32, kTileBY = 8;  // luma blocks per workgroup tile
 constexpr int kLdsBlockStride = 144;      // 128 B block + 16 B pad (same conflict-free stride as the decoder)
-
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned int;
 
 constexpr int F_0_298 = 2446, F_0_390 = 3196, F_0_541 = 4433, F_0_765 = 6270, F_0_899 = 7373, F_1_175 = 9633;
 constexpr int F_1_501 = 12299, F_1_847 = 15137, F_1_961 = 16069, F_2_053 = 16819, F_2_562 = 20995, F_3_072 = 25172;
@@ -313,8 +311,6 @@ __device__ __forceinline__ void pair_lds_fence()
 
 __device__ __forceinline__ unsigned pack16(int a, int b) { return __builtin_amdgcn_perm((unsigned)b, (unsigned)a, 0x05040100u); }  // a[15:0] | b[15:0] << 16
 __device__ __forceinline__ unsigned hi16_pair(int a, int b) { return __builtin_amdgcn_perm((unsigned)b, (unsigned)a, 0x07060302u); }  // a[31:16] | b[31:16] << 16
-
-using lds_char = __attribute__((address_space(3))) char;
 
 // ---- FDCT passes on int16 pairs ------------------------------------------------------------------------------------------
 // jfdctint.c's pass 2 is a linear map with integer coefficients in front of its descale (every input meets ONE constant on the

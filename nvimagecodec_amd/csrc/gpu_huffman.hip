@@ -25,6 +25,7 @@
 
 #include "gpu_huffman.h"
 #include "huffman_gpu_core.h"
+#include "kernel_common.h"
 
 namespace hipjpeg {
 
@@ -34,10 +35,6 @@ constexpr int kThreads = 256;
 
 constexpr int kRowShift = kSubseqWords == 32 ? 5 : kSubseqWords == 16 ? 4 : kSubseqWords == 64 ? 6 : -1;  // log2(words per subsequence)
 static_assert(kRowShift > 0, "subsequences of 512, 1024 or 2048 bits");
-
-#define HJ_LDS __attribute__((address_space(3)))
-#define HJ_GLOBAL __attribute__((address_space(1)))
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));  // plain vector type: usable behind address-space pointers
 
 struct KSlot {
     int16_t* base;  // coef[comp] + blk0 * 64

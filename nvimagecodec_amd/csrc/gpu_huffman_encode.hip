@@ -5,14 +5,13 @@
 
 #include "gpu_huffman_encode.h"
 #include "huffman_encode_core.h"
+#include "kernel_common.h"
 
 namespace hipjpeg {
 
 namespace {
 
 constexpr int kThreads = 256;
-
-#define HJ_LDS __attribute__((address_space(3)))
 
 struct LdsTables {
     uint16_t dc_code[2][16];

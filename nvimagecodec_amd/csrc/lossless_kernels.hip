@@ -15,26 +15,16 @@
 // Both apply the point transform and the 8-bit truncation on the way out and write the caller's layout; nothing is read back from it.
 #include <hip/hip_runtime.h>
 
+#include "kernel_common.h"
 #include "lossless_kernels.h"
 
 namespace hipjpeg {
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 using gbl_u8 = __attribute__((address_space(1))) uint8_t;
 using gbl_u16 = __attribute__((address_space(1))) uint16_t;
 using gbl_u32x2 = __attribute__((address_space(1))) u32x2;
-using gbl_u32x4 = __attribute__((address_space(1))) u32x4;
-
-// LDS operations of one wave execute in order; only the compiler has to be kept from reordering across the hand-off
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // one sample at any address: a halfword where it is aligned, bytes where it is not
 __device__ __forceinline__ void store_sample(uint64_t addr, uint32_t v, uint32_t out_bytes)

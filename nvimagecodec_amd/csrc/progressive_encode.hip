@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "huffman_encode_core.h"  // henc_map_offset
+#include "kernel_common.h"
 #include "progressive_encode.h"
 
 namespace hipjpeg {
@@ -10,8 +11,6 @@ namespace hipjpeg {
 namespace {
 
 constexpr int kThreads = 256;
-
-#define HJ_LDS __attribute__((address_space(3)))
 
 struct LdsCount {  // symbol counts of one workgroup
     HJ_LDS uint32_t* h;

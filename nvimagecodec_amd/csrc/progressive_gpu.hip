@@ -14,16 +14,13 @@
 #include <hip/hip_runtime.h>
 
 #include "gpu_huffman.h"
+#include "kernel_common.h"
 #include "progressive_gpu.h"
 #include "progressive_gpu_core.h"
 
 namespace hipjpeg {
 
 namespace {
-
-#define HJ_LDS __attribute__((address_space(3)))
-#define HJ_GLOBAL __attribute__((address_space(1)))
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // How long a wave that waits for its pipeline neighbour sleeps between two looks at the counter, in units of 64 cycles.  A poll is a dozen
 // instructions through the compute unit's one scalar ALU, which the walking waves of up to three images share.

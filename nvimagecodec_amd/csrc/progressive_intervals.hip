@@ -9,16 +9,13 @@
 #include <hip/hip_runtime.h>
 
 #include "gpu_huffman.h"
+#include "kernel_common.h"
 #include "progressive_gpu.h"
 #include "progressive_interval_core.h"
 
 namespace hipjpeg {
 
 namespace {
-
-#define HJ_LDS __attribute__((address_space(3)))
-#define HJ_GLOBAL __attribute__((address_space(1)))
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct IntervalEnv {
     const HuffImage* himgs;

@@ -25,6 +25,7 @@
 // unit's component rides behind the turn in RelayoutUnit::pad.
 #include <hip/hip_runtime.h>
 
+#include "kernel_common.h"
 #include "transcode_kernels.h"
 
 namespace hipjpeg {
@@ -91,29 +92,6 @@ constexpr PieceMasks make_piece_masks()
 }
 __device__ const PieceMasks kPieceMasks = make_piece_masks();
 
-using lds_char = __attribute__((address_space(3))) char;
-using lds_u16 = __attribute__((address_space(3))) unsigned short;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-using lds_u32x4 = __attribute__((address_space(3))) u32x4;
-// the descriptors' pointers come out of memory as generic ones: say that they point into global memory, so that the loads and stores
-// are global_* instructions (flat ones also count as LDS operations and would tie the two waits together)
-using gbl_u32x4 = __attribute__((address_space(1))) u32x4;
-using gbl_i16 = __attribute__((address_space(1))) int16_t;
-
-// LDS operations of one wave execute in order; only the compiler has to be kept from reordering across the hand-off
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// is either half of a dword, as int16, outside [-1023, 1023]?  (no branches: bitwise ors)
-__device__ __forceinline__ unsigned pair_outside(unsigned w)
-{
-    const int a = (int)(short)(w & 0xFFFFu), b = (int)w >> 16;
-    return (unsigned)(a < -1023) | (unsigned)(a > 1023) | (unsigned)(b < -1023) | (unsigned)(b > 1023);
-}
 }  // namespace
 
 __global__ __launch_bounds__(kThreads) void coef_relayout_kernel(const DecodeImage* __restrict__ src, const EncodeImage* __restrict__ dst,

@@ -1,4 +1,5 @@
-"""Test helper: decode cases steered onto the seams of the pixel stage's STORES (csrc/decode_kernels.hip), the way steered_streams.py,
+"""Test helper: decode cases steered onto the seams of the pixel stage's STORES (csrc/decode_kernels.hip: K1, K2; csrc/plane_color_kernels.hip: the
+kernels that read planes), the way steered_streams.py,
 progressive_seams.py and coder_seams.py steer files onto the entropy kernels'.
 
 The store code picks its path from the pointer, the pitch and the width together; a tightly packed output ties the three, so a case
@@ -42,7 +43,7 @@ SOURCE_TEXT = {
     "UNIT_BLOCKS": [("device_layout.h", "constexpr int kBlocksPerUnit = %d;" % UNIT_BLOCKS)],
     "XFORM_ROWS": [("device_layout.h", "constexpr int kTransformRowsPerUnit = %d;" % XFORM_ROWS)],
     "SCALED_ROWS": [("device_layout.h", "constexpr int kScaledRowsPerUnit = %d;" % SCALED_ROWS)],
-    "THREADS": [("decode_kernels.hip", "constexpr int kThreads = %d;" % THREADS)],
+    "THREADS": [("decode_kernel_common.h", "constexpr int kThreads = %d;" % THREADS)],
     "NARROW_ROW_BYTES": [("decode_kernels.hip", "constexpr int kNarrowRowBytes = 16 * 24;")],
     # DecodeBatch::build_pixel_units: luma_tiles() below
     "tiles": [("decoder_core.cpp", "first_row = (uint32_t)im.transform.y0 / 8 / kLumaTileH * kLumaTileH;"),
@@ -67,11 +68,11 @@ SOURCE_TEXT = {
     "k1": [("decode_kernels.hip", "const bool fast = (x0 + 8 <= lim_w) && (((uintptr_t)base | pitch) & 7) == 0;"),
            ("decode_kernels.hip", "const int lim_w = to_out ? cd.samp_w : bw * 8;")],
     # scaled_color_kernel: scaled_paths() below
-    "scaled": [("decode_kernels.hip", "const int wide_groups = (direct && aligned16) ? (W >> 4) : 0;"),
-               ("decode_kernels.hip", "for (int g = wide_groups * 4 + lane; g < groups; g += 64) {"),
-               ("decode_kernels.hip", "const bool whole = aligned && n == 4;"),
-               ("decode_kernels.hip", "const int x = g * 4, n = min(4, W - x);"),
-               ("decode_kernels.hip", "const bool direct = k0.fx == 1 && k0.fy == 1 && (gray || (k1.fx == 1 && k1.fy == 1 && k2.fx == 1 && k2.fy == 1));")],
+    "scaled": [("plane_color_kernels.hip", "const int wide_groups = (direct && aligned16) ? (W >> 4) : 0;"),
+               ("plane_color_kernels.hip", "for (int g = wide_groups * 4 + lane; g < groups; g += 64) {"),
+               ("plane_color_kernels.hip", "const bool whole = aligned && n == 4;"),
+               ("plane_color_kernels.hip", "const int x = g * 4, n = min(4, W - x);"),
+               ("plane_color_kernels.hip", "const bool direct = k0.fx == 1 && k0.fy == 1 && (gray || (k1.fx == 1 && k1.fy == 1 && k2.fx == 1 && k2.fy == 1));")],
 }
 
 SAMPLING = {"444": (1, 1), "422": (2, 1), "420": (2, 2), "440": (1, 2), "gray": (1, 1), "411": (4, 1), "410": (4, 2)}
