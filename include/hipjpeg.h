@@ -637,6 +637,48 @@ HIPJPEG_API hipjpegStatus_t hipjpegDecodeLosslessBatchDeviceKernel(hipjpegHandle
  * bytes of the host-to-device copy. */
 HIPJPEG_API hipjpegStatus_t hipjpegDecodeLosslessBatchStats(hipjpegHandle_t handle, int32_t images_per_kernel[2], uint64_t* h2d_bytes);
 
+/* ---- the same with the entropy stage on the GPU, opt-in.  hipjpegDecodeLosslessBatch is flags = 0.
+ * HIPJPEG_FLAG_GPU_HUFFMAN sends every frame the lossless decoder takes through GPU kernels that remove the byte stuffing, find the
+ * samples of the scan with a self-synchronising walk (one lane per subsequence of the destuffed stream, restart intervals apart) and
+ * write the difference planes the host stage would have uploaded: only the compressed scans travel to the device.
+ * The contract is that of hipjpegDecodeLosslessBatch: statuses[i] is final on return, a failing image leaves its output untouched and
+ * does not disturb the others.  To keep it the call WAITS ONCE per batch, on `stream`, for the verdict words of the entropy kernels,
+ * before any reconstruction kernel is queued.  An image whose walk did not converge within the round budget, or that the device
+ * flagged (a code no table holds, a scan that ends inside a sample, an interval with too many or too few samples), is decoded again by
+ * the host stage, which yields its exact status and, if it succeeds, its differences; those are then uploaded.  The host stage also
+ * takes, from the start, an image whose restart markers are not RST0..7 in turn, one with an empty interval, one with a table of
+ * more than 32 symbols, and one whose scan is 2^29 bytes or longer: bit positions and sample counts are 32-bit in the kernels, and
+ * the bound is taken on the stuffed bytes, so no destuffed scan of 2^32 bits or more reaches them.  Other flags are ignored. */
+HIPJPEG_API hipjpegStatus_t hipjpegDecodeLosslessBatchFlags(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
+                                                            const hipjpegLosslessOutput_t* outputs, hipjpegStatus_t* statuses, unsigned int flags,
+                                                            void* stream);
+/* hipjpegDecodeLosslessBatchDeviceKernel also takes which = 3 (destuffing, pass 0 and the ripple launches of the GPU entropy stage) and
+ * which = 4 (its write pass) behind a call with HIPJPEG_FLAG_GPU_HUFFMAN in which no image went to the host stage (else
+ * INVALID_ARGUMENT: the write pass would store over the differences the host stage uploaded). */
+/* Of the handle's last lossless batch call: images whose differences the entropy kernels made, images the host stage decoded although
+ * the flag was set, ripple launches in which a workgroup had a correction to carry.  All 0 behind a call without the flag. */
+HIPJPEG_API hipjpegStatus_t hipjpegDecodeLosslessBatchEntropyStats(hipjpegHandle_t handle, int32_t* gpu_images, int32_t* host_fallback_images,
+                                                                   int32_t* ripple_launches);
+/* The entropy kernels' shape, for tests that steer streams onto their seams: bits of a subsequence (one lane's share of a destuffed
+ * interval), subsequences of a workgroup, correction rounds a workgroup runs per launch, and launches behind the first that carry
+ * corrections across workgroup borders. */
+typedef struct {
+    int32_t subsequence_bits, subsequences_per_workgroup, max_rounds, max_ripple_launches;
+} hipjpegLosslessEntropyShape_t;
+HIPJPEG_API hipjpegStatus_t hipjpegLosslessEntropyShape(hipjpegLosslessEntropyShape_t* shape);
+/* The entropy kernels' schedule run on the CPU, lane by lane: destuffing, pass 0, rounds, ripple launches, checks, sums and stores.
+ * Needs no GPU.  planes[c]: differences of frame component c, `pitch` samples (uint16) per row, pitch >= width.  *converged = 0: the
+ * rounds did not converge within the budget.  Like the batch call, it then -- and when the walk flagged the image or the marker scan
+ * turned it away -- lets the host stage decode, and returns that stage's status and differences. */
+HIPJPEG_API hipjpegStatus_t hipjpegLosslessEntropyAlgorithmHost(const uint8_t* data, size_t length, uint16_t* const planes[4], size_t pitch,
+                                                                int32_t* converged);
+/* The plugin decoder's lossless route (option hipjpeg_decoder:gpu_lossless_entropy=1 sets the flag there): images whose differences
+ * the entropy kernels made and images the host stage decoded although the option was set, summed over every decode call of every
+ * plugin decoder of this process.  Both stay as they are while the option is off. */
+HIPJPEG_API hipjpegStatus_t hipjpegPluginLosslessEntropyStats(int64_t* gpu_images, int64_t* host_fallback_images);
+/* The host entropy stage alone (what hipjpegDecodeLosslessBatch runs on its threads): the same planes, for comparison. */
+HIPJPEG_API hipjpegStatus_t hipjpegLosslessEntropyHost(const uint8_t* data, size_t length, uint16_t* const planes[4], size_t pitch);
+
 #ifdef __cplusplus
 }
 #endif

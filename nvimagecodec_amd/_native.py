@@ -83,6 +83,11 @@ class LosslessKernelShape(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("band_rows", "tile_columns", "chunk_samples", "rows_min_width")]
 
 
+class LosslessEntropyShape(ctypes.Structure):
+    """hipjpegLosslessEntropyShape_t"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("subsequence_bits", "subsequences_per_workgroup", "max_rounds", "max_ripple_launches")]
+
+
 CSS = {"444": 0, "422": 1, "420": 2, "440": 3, "411": 4, "410": 5, "gray": 6}
 
 
@@ -206,5 +211,11 @@ def load():
     L.hipjpegDecodeLosslessBatch.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.hipjpegDecodeLosslessBatchDeviceKernel.argtypes = [vp, i32, vp]
     L.hipjpegDecodeLosslessBatchStats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64)]
+    L.hipjpegDecodeLosslessBatchFlags.argtypes = [vp, vp, vp, i32, vp, vp, ctypes.c_uint, vp]
+    L.hipjpegDecodeLosslessBatchEntropyStats.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int32)] * 3
+    L.hipjpegLosslessEntropyShape.argtypes = [ctypes.POINTER(LosslessEntropyShape)]
+    L.hipjpegLosslessEntropyAlgorithmHost.argtypes = [vp, sz, ctypes.POINTER(vp), sz, ctypes.POINTER(ctypes.c_int32)]
+    L.hipjpegLosslessEntropyHost.argtypes = [vp, sz, ctypes.POINTER(vp), sz]
+    L.hipjpegPluginLosslessEntropyStats.argtypes = [ctypes.POINTER(ctypes.c_int64)] * 2
     _lib = L
     return L

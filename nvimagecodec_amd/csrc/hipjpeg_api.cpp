@@ -1108,14 +1108,31 @@ hipjpegStatus_t hipjpegCoefficientsBatchStats(hipjpegHandle_t handle, int32_t* g
 
 // ---------------------------------------------------------------- lossless JPEG
 // (hipjpegGetLosslessInfo / hipjpegDecodeLosslessHost / hipjpegLosslessReconstructAlgorithmHost: lossless_core.cpp, with the rules)
-hipjpegStatus_t hipjpegDecodeLosslessBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
-                                           const hipjpegLosslessOutput_t* outputs, hipjpegStatus_t* statuses, void* stream)
+hipjpegStatus_t hipjpegDecodeLosslessBatchFlags(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
+                                                const hipjpegLosslessOutput_t* outputs, hipjpegStatus_t* statuses, unsigned int flags, void* stream)
 {
     return guarded([&]() -> hipjpegStatus_t {
     if (!handle || batch_size < 0 || (batch_size > 0 && (!data || !lengths || !outputs))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
     if (!handle->lossless) handle->lossless.reset(new LosslessBatch(handle->device_id, &handle->hooks));
-    return handle->lossless->decode(data, lengths, batch_size, outputs, statuses, handle->pool.get(), (hipStream_t)stream);
+    return handle->lossless->decode(data, lengths, batch_size, outputs, statuses, flags, handle->pool.get(), (hipStream_t)stream);
+    });
+}
+
+hipjpegStatus_t hipjpegDecodeLosslessBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
+                                           const hipjpegLosslessOutput_t* outputs, hipjpegStatus_t* statuses, void* stream)
+{
+    return hipjpegDecodeLosslessBatchFlags(handle, data, lengths, batch_size, outputs, statuses, 0u, stream);
+}
+
+hipjpegStatus_t hipjpegDecodeLosslessBatchEntropyStats(hipjpegHandle_t handle, int32_t* gpu_images, int32_t* host_fallback_images, int32_t* ripple_launches)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (gpu_images) *gpu_images = handle->lossless ? handle->lossless->gpu_images() : 0;
+    if (host_fallback_images) *host_fallback_images = handle->lossless ? handle->lossless->host_fallback_images() : 0;
+    if (ripple_launches) *ripple_launches = handle->lossless ? handle->lossless->ripple_launches() : 0;
+    return HIPJPEG_STATUS_SUCCESS;
     });
 }
 

@@ -149,6 +149,7 @@ private:
     bool fancy_ = true;  // same default as the reference plugins (nvjpeg_utils.cpp:46, libjpeg_turbo_decoder.cpp:253)
     bool gpu_huffman_ = true;  // entropy-decode eligible streams on the GPU (the reference's GPU_HYBRID backend analogue)
     bool gpu_progressive_intervals_ = false;  // ... progressive files whose scans all have restart intervals too (HIPJPEG_FLAG_GPU_PROGRESSIVE_INTERVALS)
+    bool gpu_lossless_entropy_ = false;  // lossless streams: the entropy stage on the GPU too (hipjpegDecodeLosslessBatchFlags, HIPJPEG_FLAG_GPU_HUFFMAN)
     uint64_t hybrid_huffman_threshold_ = 0;  // ... those of more than this many pixels (cuda_decoder.cpp:188-209; 0 = all of them)
     // fast_idct (JDCT_FASTEST, libjpeg_turbo_decoder.cpp:250-276).  A key without a module name is the chain's setting: it hands every
     // sample to the next decoder (fast_idct_, see canDecode).  hipjpeg_decoder:fast_idct=1 opts in to this decoder's own IFAST kernels
@@ -195,6 +196,7 @@ HipJpegDecoder::HipJpegDecoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgc
         if (key == "fancy_upsampling") v >> fancy_;
         else if (key == "gpu_huffman") v >> gpu_huffman_;
         else if (key == "gpu_progressive_intervals") v >> gpu_progressive_intervals_;
+        else if (key == "gpu_lossless_entropy") v >> gpu_lossless_entropy_;
         else if (key == "pipeline_chunks") v >> pipeline_chunks_;
         else if (key == "hybrid_huffman_threshold") v >> hybrid_huffman_threshold_;
         else if (key == "scale_denom") v >> scale_denom_;
@@ -211,7 +213,7 @@ HipJpegDecoder::HipJpegDecoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgc
     // plugin of the chain and is passed over in silence, as the reference's plugins do)
     for (const std::string& k : unknown_keys_)
         if (std::find(addressed_keys_.begin(), addressed_keys_.end(), k) != addressed_keys_.end())
-            HJ_LOG_WARNING(fw_, kDecoderId, "unknown option '" << k << "' ignored (known: fancy_upsampling, gpu_huffman, gpu_progressive_intervals, hybrid_huffman_threshold, pipeline_chunks, fast_idct, scale_denom)");
+            HJ_LOG_WARNING(fw_, kDecoderId, "unknown option '" << k << "' ignored (known: fancy_upsampling, gpu_huffman, gpu_progressive_intervals, gpu_lossless_entropy, hybrid_huffman_threshold, pipeline_chunks, fast_idct, scale_denom)");
     if (scale_denom_ != 1 && scale_denom_ != 2 && scale_denom_ != 4 && scale_denom_ != 8) {
         HJ_LOG_WARNING(fw_, kDecoderId, "scale_denom=" << scale_denom_ << " ignored: the denominators are 1, 2, 4 and 8");
         scale_denom_ = 1;
@@ -568,6 +570,16 @@ struct ConsumerStreams {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ the lossless route
+// what the GPU entropy stage did for the lossless samples of this process's plugin decoders (hipjpegPluginLosslessEntropyStats)
+static std::atomic<int64_t> g_lossless_gpu_images{0}, g_lossless_host_fallback_images{0};
+
+extern "C" hipjpegStatus_t hipjpegPluginLosslessEntropyStats(int64_t* gpu_images, int64_t* host_fallback_images)
+{
+    if (gpu_images) *gpu_images = g_lossless_gpu_images.load();
+    if (host_fallback_images) *host_fallback_images = g_lossless_host_fallback_images.load();
+    return HIPJPEG_STATUS_SUCCESS;
+}
+
 // Lossless Huffman streams, under the rules of the reference's lossless decoder (extensions/nvjpeg/lossless_decoder.cpp:82-103) widened
 // by what hipjpegDecodeLosslessBatch does: P_Y for one component, I_UNCHANGED and P_UNCHANGED for any number; UINT16 always and UINT8 for
 // precisions up to 8; the stored components, so no colour request but UNCHANGED (or GRAY for one component); no region, no turning.
@@ -649,7 +661,12 @@ void HipJpegDecoder::decode_lossless(std::vector<Sample>& samples, const nvimgco
         if (ok && !lossless_) lossless_.reset(new hipjpeg::LosslessBatch(device_, &hooks_));
         std::vector<hipjpegStatus_t> statuses((size_t)n, HIPJPEG_STATUS_INTERNAL_ERROR);
         // (samples declined above have no data: the batch calls them INVALID_ARGUMENT, their verdict stands)
-        if (ok) ok = lossless_->decode(data.data(), sizes.data(), n, outs.data(), statuses.data(), parse_pool_.get(), lossless_stream_) == HIPJPEG_STATUS_SUCCESS;
+        if (ok) ok = lossless_->decode(data.data(), sizes.data(), n, outs.data(), statuses.data(), gpu_lossless_entropy_ ? HIPJPEG_FLAG_GPU_HUFFMAN : 0u,
+                                       parse_pool_.get(), lossless_stream_) == HIPJPEG_STATUS_SUCCESS;
+        if (ok) {
+            g_lossless_gpu_images += lossless_->gpu_images();
+            g_lossless_host_fallback_images += lossless_->host_fallback_images();
+        }
         if (ok) ok = hipEventRecord(lossless_event_, lossless_stream_) == hipSuccess;
         if (!ok && lossless_stream_) (void)hipStreamSynchronize(lossless_stream_);  // whatever was queued must not outlive the caller's buffers
         release_inputs(samples);

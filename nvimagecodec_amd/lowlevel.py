@@ -1189,15 +1189,59 @@ def decode_lossless_host(data, dtype=np.uint16, planar=False, algorithm=None):
     return out
 
 
+def lossless_entropy_shape():
+    """hipjpegLosslessEntropyShape: the seams of the GPU entropy stage of the lossless decoder, as a dict"""
+    k = N.LosslessEntropyShape()
+    st = N.load().hipjpegLosslessEntropyShape(ctypes.byref(k))
+    if st:
+        raise N.HipJpegError(st, "hipjpegLosslessEntropyShape")
+    return {n: getattr(k, n) for n, _ in N.LosslessEntropyShape._fields_}
+
+
+def _lossless_difference_planes(data):
+    arr = _as_u8(data)
+    info = lossless_info(arr)
+    planes = np.zeros((info["num_components"], info["height"], info["width"]), dtype=np.uint16)
+    ptrs = (ctypes.c_void_p * 4)(*[planes[c].ctypes.data for c in range(info["num_components"])])
+    return arr, planes, ptrs, info["width"]
+
+
+def lossless_entropy_algorithm_host(data):
+    """hipjpegLosslessEntropyAlgorithmHost: the GPU entropy stage's schedule run on the CPU.  -> (status, N x H x W uint16 differences,
+    converged); the status and, where the walk did not vouch for the image, the differences are the host stage's, as in the batch call.
+    Raises HipJpegError where the file is no lossless frame the decoder takes."""
+    arr, planes, ptrs, pitch = _lossless_difference_planes(data)
+    converged = ctypes.c_int32(-1)
+    st = N.load().hipjpegLosslessEntropyAlgorithmHost(arr.ctypes.data, arr.size, ptrs, pitch, ctypes.byref(converged))
+    return st, planes, bool(converged.value)
+
+
+def lossless_entropy_host(data):
+    """hipjpegLosslessEntropyHost: the host entropy stage alone.  -> (status, N x H x W uint16 differences)"""
+    arr, planes, ptrs, pitch = _lossless_difference_planes(data)
+    st = N.load().hipjpegLosslessEntropyHost(arr.ctypes.data, arr.size, ptrs, pitch)
+    return st, planes
+
+
+def plugin_lossless_entropy_stats():
+    """hipjpegPluginLosslessEntropyStats: what the plugin decoders of this process sent through the GPU entropy stage so far"""
+    g, f = ctypes.c_int64(), ctypes.c_int64()
+    st = N.load().hipjpegPluginLosslessEntropyStats(ctypes.byref(g), ctypes.byref(f))
+    if st:
+        raise N.HipJpegError(st, "hipjpegPluginLosslessEntropyStats")
+    return {"gpu_images": g.value, "host_fallback_images": f.value}
+
+
 class BatchLosslessDecoder:
     """hipjpegDecodeLosslessBatch on one device: lossless JPEG files (SOF3, 2..16 bit, predictors 1..7) to torch tensors of the stored
     samples, uint16 (or uint8 for files of precision <= 8), H x W x N or N x H x W.  The entropy stage runs on host threads; prediction
-    runs on the GPU."""
+    runs on the GPU.  gpu_entropy=True: hipjpegDecodeLosslessBatchFlags with HIPJPEG_FLAG_GPU_HUFFMAN, the entropy stage on the GPU too."""
 
-    def __init__(self, device=0, num_threads=0):
+    def __init__(self, device=0, num_threads=0, gpu_entropy=False):
         import torch
         self._torch = torch
         self.device = int(device)
+        self.gpu_entropy = bool(gpu_entropy)
         self._h = ctypes.c_void_p()
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
         if st:
@@ -1274,14 +1318,19 @@ class BatchLosslessDecoder:
             O[i] = self.output(t, info, planar)
             tensors.append(t)
         statuses = (ctypes.c_int * n)()
-        st = N.load().hipjpegDecodeLosslessBatch(self._h, ptrs, lens, n, O, statuses, self._stream_ptr(stream))
+        if self.gpu_entropy:
+            st, what = (N.load().hipjpegDecodeLosslessBatchFlags(self._h, ptrs, lens, n, O, statuses, N.FLAG_GPU_HUFFMAN, self._stream_ptr(stream)),
+                        "hipjpegDecodeLosslessBatchFlags")
+        else:
+            st, what = N.load().hipjpegDecodeLosslessBatch(self._h, ptrs, lens, n, O, statuses, self._stream_ptr(stream)), "hipjpegDecodeLosslessBatch"
         if st:
-            raise N.HipJpegError(st, "hipjpegDecodeLosslessBatch")
+            raise N.HipJpegError(st, what)
         given = outs if outs is not None else [None] * n
         return list(statuses), [tensors[i] if statuses[i] == 0 or given[i] is not None else None for i in range(n)]
 
     def device_stage(self, which, stream=None):
-        """hipjpegDecodeLosslessBatchDeviceKernel: one part of the last decode() again (0 upload, 1 rows kernels, 2 wavefront kernel)"""
+        """hipjpegDecodeLosslessBatchDeviceKernel: one part of the last decode() again (0 upload, 1 rows kernels, 2 wavefront kernel; behind a
+        decode() with gpu_entropy in which no image went to the host stage also 3 destuffing and synchronisation, 4 the write pass)"""
         st = N.load().hipjpegDecodeLosslessBatchDeviceKernel(self._h, int(which), self._stream_ptr(stream))
         if st:
             raise N.HipJpegError(st, "hipjpegDecodeLosslessBatchDeviceKernel")
@@ -1292,4 +1341,9 @@ class BatchLosslessDecoder:
         st = N.load().hipjpegDecodeLosslessBatchStats(self._h, k, ctypes.byref(b))
         if st:
             raise N.HipJpegError(st, "hipjpegDecodeLosslessBatchStats")
-        return {"rows_images": k[0], "wavefront_images": k[1], "h2d_bytes": b.value}
+        e = [ctypes.c_int32() for _ in range(3)]
+        st = N.load().hipjpegDecodeLosslessBatchEntropyStats(self._h, *[ctypes.byref(x) for x in e])
+        if st:
+            raise N.HipJpegError(st, "hipjpegDecodeLosslessBatchEntropyStats")
+        return {"rows_images": k[0], "wavefront_images": k[1], "h2d_bytes": b.value, "gpu_images": e[0].value,
+                "host_fallback_images": e[1].value, "ripple_launches": e[2].value}

@@ -12,6 +12,10 @@ files in 16 processes.
 
     python tools/prof_lossless_decode.py --files DIR [--make] [--out profiles/lossless/prof_lossless_decode.json]
 
+--gpu-entropy measures the GPU entropy stage instead: both workloads with the flag off and with the flag on, in the
+same process -- host part of the call, bytes of the host-to-device copies, the entropy kernels' parts (which = 3: destuffing and
+synchronisation, which = 4: the write pass) and the whole call -- into profiles/lossless/prof_lossless_gpu_entropy.json.
+
 --make writes the workload files into DIR (a few distinct pictures per workload; the batch repeats them) and stops: the writer is
 numpy and slow, so this is done once, away from the GPU.
 """
@@ -151,15 +155,85 @@ def measure(directory, name):
     return result
 
 
+def measure_gpu_entropy(directory, name):
+    """flag off, then flag on, in this process: {"flag_off": ..., "flag_on": ...}; the outputs of the two must be the same bytes"""
+    import torch
+    from nvimagecodec_amd import lowlevel
+    w = WORKLOADS[name]
+    files = load_files(directory, name)
+    info = lowlevel.lossless_info(files[0])
+    busy = torch.empty(64 << 20, dtype=torch.uint8, device="cuda:0")
+
+    def timed(fn):
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        busy.fill_(1)
+        busy.fill_(2)
+        start.record()
+        fn()
+        stop.record()
+        stop.synchronize()
+        return start.elapsed_time(stop)
+
+    result, first = {"workload": {k: w[k] for k in ("batch", "height", "width", "precision", "ps")}, "file_bytes_per_batch": sum(len(f) for f in files)}, None
+    for key, flag in (("flag_off", False), ("flag_on", True)):
+        dec = lowlevel.BatchLosslessDecoder(device=0, num_threads=THREADS, gpu_entropy=flag)
+        outs = [dec.allocate(info) for _ in files]
+        host_s, call_s = [], []
+        for r in range(WARMUPS + 6):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            statuses, _ = dec.decode(files, outs=outs)
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            assert not any(statuses)
+            if r >= WARMUPS:
+                host_s.append(t1 - t0)
+                call_s.append(t2 - t0)
+        stats = dec.stats()
+        r = {"stats": stats, "h2d_bytes": stats["h2d_bytes"], "host_part_ms": summary([s * 1e3 for s in host_s]),
+             "whole_call_ms": summary([s * 1e3 for s in call_s]), "whole_call_images_per_s": round(w["batch"] / statistics.median(call_s), 1)}
+        if flag:
+            assert stats["host_fallback_images"] == 0, stats
+            sync, write = [], []
+            for k in range(WARMUPS + ROUNDS):
+                a = timed(lambda: dec.device_stage(3))
+                b = timed(lambda: dec.device_stage(4))
+                if k >= WARMUPS:
+                    sync.append(a)
+                    write.append(b)
+            r["destuff_and_sync_ms"] = summary(sync)
+            r["write_pass_ms"] = summary(write)
+        got = [outs[0].cpu().numpy(), outs[-1].cpu().numpy()]
+        if first is None:
+            first = got
+        else:
+            assert all(np.array_equal(a, b) for a, b in zip(first, got)), "flag on and flag off differ"
+        dec.close()
+        result[key] = r
+    result["flag_on_over_flag_off_whole_call"] = round(result["flag_on"]["whole_call_ms"]["median"] / result["flag_off"]["whole_call_ms"]["median"], 2)
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--files", required=True)
     ap.add_argument("--make", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lossless", "prof_lossless_decode.json"))
     ap.add_argument("--skip-library", action="store_true")
+    ap.add_argument("--gpu-entropy", action="store_true")
     args = ap.parse_args()
     if args.make:
         make_files(args.files)
+        return
+    if args.gpu_entropy:
+        out = {"tool": "tools/prof_lossless_decode.py --gpu-entropy", "rounds": ROUNDS, "warmups": WARMUPS, "call_rounds": 6, "host_threads": THREADS}
+        for name in WORKLOADS:
+            out[name] = measure_gpu_entropy(args.files, name)
+            print(name, json.dumps(out[name]), flush=True)
+        path = args.out if args.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "lossless", "prof_lossless_gpu_entropy.json")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        json.dump(out, open(path, "w"), indent=1)
         return
     out = {"tool": "tools/prof_lossless_decode.py", "rounds": ROUNDS, "warmups": WARMUPS}
     for name in WORKLOADS:
