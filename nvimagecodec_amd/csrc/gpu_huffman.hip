@@ -1302,7 +1302,8 @@ __global__ __launch_bounds__(kSyncThreads) void huff_pos_kernel(HuffImage* __res
 // that bought no lanes.  Per 512 lanes: 2 x 32 KB of block buffers + the tables (13,824 B for the standard ones) + 384 B of constants
 // = 79,744 B, so two workgroups fit the CU's 160 KiB -- 16 waves per CU, four per SIMD, where 256-lane workgroups with a table copy
 // each stopped at three (static_assert below).  Larger tables (up to 24 KB): one workgroup per CU, 8 waves, as two 256-lane ones had
-// before.  Measured on 256 x 1080p: 576 us against 600 (profiles/block_pass_teams/).
+// before.  Measured on 256 x 1080p: 576 us against 600 (profiles/block_pass_teams/), 486 since the zero fill goes through the
+// swizzle too (profiles/block_pass_residency/).
 //   * The units of an image are consecutive in `units`, unit j of the image covering MCUs j * kHuffMcusPerWg ...; the grid has one
 //     workgroup per unit, and the workgroup that looks at unit j works only if j is a multiple of kBTeams: it takes units j .. j +
 //     kBTeams - 1 as far as the image has them.  The others leave at once, whole workgroups, in front of every barrier (which
@@ -1313,7 +1314,7 @@ __global__ __launch_bounds__(kSyncThreads) void huff_pos_kernel(HuffImage* __res
 //     No lane returns between the two barriers.
 //   * Each unit keeps its own four group sums: the DC pass sees what it saw with one unit per workgroup.
 constexpr int kBTeamThreads = kHuffBlocksPerWg;  // lanes of a team (one block per lane per round)
-constexpr int kBTeams = 2;                       // measured: 1 team (3 workgroups per CU) 651 us, 2: 576, 4 (one 1024-lane workgroup): 634 -- DESIGN.md §3.2
+constexpr int kBTeams = 2;                       // measured: 1 team (3 workgroups per CU) 564 us, 2: 486 (651 / 576 / 4 teams, one 1024-lane workgroup: 634, with the unswizzled zero fill) -- DESIGN.md §3.2
 constexpr int kBThreads = kBTeams * kBTeamThreads;
 static_assert((kBTeams & (kBTeams - 1)) == 0, "unit j starts a workgroup when j % kBTeams == 0");
 // 128-byte buffers, lane L's at byte L * 128.  The starts of a wave's buffers would all fall on bank 0; instead of padding the
@@ -1321,6 +1322,7 @@ static_assert((kBTeams & (kBTeams - 1)) == 0, "unit j starts a workgroup when j 
 // byte x of lane L's block lives at (L * 128 | (L & 7) << 4) ^ x.  For equal x the lanes of a wave then hit eight distinct 16-byte
 // offsets of the 128 bytes the 32 banks of a 2-byte store span -- the same spread as stride 144 (L * 144 mod 128 = (L & 7) * 16) --
 // and the store's address is one XOR of a per-lane constant with the byte offset, which the zigzag table holds ready (doubled).
+// Every access takes the swizzle: put(), the flush reads (chunk c of lane L at unit c ^ (L & 7)) and the zero fill.
 constexpr int kBlockBufBytes = 128;
 
 struct BlockShared {
@@ -1409,15 +1411,22 @@ __global__ __launch_bounds__(kBThreads, 4) void huff_blocks_kernel(HuffImage* __
     if (t >= 32 && t < 42) sh.kcomp[t - 32] = im.k[t - 32].comp & 3;
     stage_pool<kBThreads>(pool, im);
     stage_constants(sh.tsel, sh.kslot, sh.zz, im, true);
-    HJ_LDS u32x4* my_buf = (HJ_LDS u32x4*)&sh.blocks[t * kBlockBufBytes];
+    // The zero fill goes through the swizzle like every other access to the buffers: step i clears chunk i ^ (t & 7).  A 16-byte LDS
+    // store is served in groups of eight consecutive lanes on 32 banks (128 bytes): chunk i of every lane, 128 bytes apart, puts the
+    // eight lanes of a group on the same four banks -- 64 LDS cycles per store where the swizzled one takes 8, eight stores per round
+    // (profiles/block_pass_residency/).
+    const uint32_t my_buf = (uint32_t)(uintptr_t)(HJ_LDS uint8_t*)sh.blocks + (((uint32_t)t * kBlockBufBytes) | (((uint32_t)t & 7u) << 4));
+    auto zero_fill = [my_buf] {
 #pragma unroll
-    for (int i = 0; i < kBlockBufBytes / 16; i++) my_buf[i] = u32x4{0u, 0u, 0u, 0u};
+        for (uint32_t i = 0; i < kBlockBufBytes / 16; i++) *(HJ_LDS u32x4*)(uintptr_t)(my_buf ^ (i << 4)) = u32x4{0u, 0u, 0u, 0u};
+    };
+    zero_fill();
     __syncthreads();  // barrier 1 of 2: tables, constants and zeroed sums are in place
     BlockEnv env;
     env.gstream = reinterpret_cast<const uint32_t*>(im.stream);
     env.gwords = im.stream_words;
     env.pool = (uint32_t)(uintptr_t)pool;
-    env.buf = (uint32_t)(uintptr_t)(HJ_LDS uint8_t*)sh.blocks + (((uint32_t)t * kBlockBufBytes) | (((uint32_t)t & 7u) << 4));
+    env.buf = my_buf;
     env.tsel = (const HJ_LDS uint32_t*)sh.tsel;
     env.kslot = (const HJ_LDS KSlot*)sh.kslot;
     env.zz = (const HJ_LDS uint8_t*)sh.zz;
@@ -1474,8 +1483,7 @@ __global__ __launch_bounds__(kBThreads, 4) void huff_blocks_kernel(HuffImage* __
             if (p[i]) __builtin_nontemporal_store(v[i], (HJ_GLOBAL u32x4*)p[i] + chunk);
         if (base + kBTeamThreads < items) {
             wave_sync();
-#pragma unroll
-            for (int i = 0; i < 8; i++) my_buf[i] = u32x4{0u, 0u, 0u, 0u};
+            zero_fill();
         }
     }
     if (err) im.status = 1;  // benign race: every writer stores the same value
