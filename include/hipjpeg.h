@@ -153,6 +153,13 @@ HIPJPEG_API int32_t hipjpegTestScanChunkDrops(const uint8_t* data, size_t length
  * steps: 65,536 entries.  Returns 0, or a negative value for a table the stage does not accept. */
 HIPJPEG_API int32_t hipjpegTestPairSteps(const uint8_t bits[16], const uint8_t* vals, int32_t nvals, uint32_t* steps);
 
+/* Test hook (host only): the byte the host twins of the GPU algorithms (hipjpegEntropyDecodeGpuAlgorithmHost,
+ * hipjpegEntropyDecodeGpuIntervalAlgorithmHost, hipjpegLosslessEntropyAlgorithmHost, hipjpegEncodeBaselineGpuAlgorithmHost,
+ * hipjpegEncodeProgressiveGpuAlgorithmHost) fill their stand-ins for device scratch with, 0..255, from now on and process-wide; 0 is the
+ * default (csrc/scratch_fill.h).  Their results must not depend on it: a kernel reads nothing its batch did not write
+ * (docs/arena_regions.md; tests/test_twin_scratch_fill.py). */
+HIPJPEG_API hipjpegStatus_t hipjpegTestSetScratchFill(int byte);
+
 /* ---- host-only entry points (usable without a GPU) ---- */
 HIPJPEG_API hipjpegStatus_t hipjpegGetImageInfo(const uint8_t* data, size_t length, hipjpegImageInfo_t* info);
 
@@ -194,6 +201,28 @@ HIPJPEG_API hipjpegStatus_t hipjpegEntropyDecodeGpuIntervalAlgorithmHost(const u
 /* num_host_threads: CPU threads for the entropy stage (0 = hardware concurrency). */
 HIPJPEG_API hipjpegStatus_t hipjpegCreate(hipjpegHandle_t* handle, int device_id, int num_host_threads);
 HIPJPEG_API hipjpegStatus_t hipjpegDestroy(hipjpegHandle_t handle);
+
+/* Caller-supplied allocators for everything the handle stages its batches in (the grow-only device and pinned arenas of its decode pages,
+ * encode batch and encode pages, lossless pages, and through them the transcode and coefficient calls) -- what the plugin takes from
+ * nvimgcodecExecutionParams_t::device_allocator / pinned_allocator (reference include/nvimgcodec.h, nvimgcodecDeviceAllocator_t /
+ * nvimgcodecPinnedAllocator_t: the same signatures).  malloc returns 0 and a pointer in *ptr on success; free gets the size malloc was
+ * asked for; `stream` is always NULL (the arenas are allocated and released outside any stream order).  A pair counts only when both of
+ * its functions are set; either pair may be null, and that kind of memory then comes from hipMalloc / hipHostMalloc as before.  The
+ * memory need not be cleared: nothing a kernel reads from an arena before its own batch wrote it can reach an output, a status or an
+ * address (docs/arena_regions.md).  Device
+ * scratch that is not an arena (a few words the entropy stage allocates once per handle) stays with hipMalloc. */
+typedef struct {
+    int (*device_malloc)(void* ctx, void** ptr, size_t size, void* stream);
+    int (*device_free)(void* ctx, void* ptr, size_t size, void* stream);
+    void* device_ctx;
+    int (*pinned_malloc)(void* ctx, void** ptr, size_t size, void* stream);
+    int (*pinned_free)(void* ctx, void* ptr, size_t size, void* stream);
+    void* pinned_ctx;
+} hipjpegAllocators_t;
+/* Accepted only before the handle's first batch of any kind (nothing has been allocated yet); afterwards, or with a null argument,
+ * HIPJPEG_STATUS_INVALID_ARGUMENT and nothing changes.  The functions and contexts must stay valid until hipjpegDestroy, which hands
+ * every allocation back. */
+HIPJPEG_API hipjpegStatus_t hipjpegSetAllocators(hipjpegHandle_t handle, const hipjpegAllocators_t* allocators);
 
 /* One call = host entropy stage (thread pool) + H2D staging + batched device stage, asynchronous on `stream`
  * (the call returns after the last kernel is enqueued; per-image host failures are reported in `statuses`). */

@@ -100,6 +100,17 @@ class Output(ctypes.Structure):
     _fields_ = [("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_uint32 * 3)]
 
 
+# int malloc(void* ctx, void** ptr, size_t size, void* stream) / int free(void* ctx, void* ptr, size_t size, void* stream)
+AllocatorMalloc = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_void_p)
+AllocatorFree = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p)
+
+
+class Allocators(ctypes.Structure):
+    """hipjpegAllocators_t (hipjpegSetAllocators); a null function pointer is a CFUNCTYPE left unset"""
+    _fields_ = [("device_malloc", AllocatorMalloc), ("device_free", AllocatorFree), ("device_ctx", ctypes.c_void_p),
+                ("pinned_malloc", AllocatorMalloc), ("pinned_free", AllocatorFree), ("pinned_ctx", ctypes.c_void_p)]
+
+
 HOST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libhipjpeg_host.so")
 _lib = None
 _host = None
@@ -136,6 +147,7 @@ def load():
     L.hipjpegStatusString.argtypes = [i32]
     L.hipjpegVersion.restype = i32
     L.hipjpegTestSetFault.argtypes = [ctypes.c_char_p, i32]
+    L.hipjpegTestSetScratchFill.argtypes = [i32]
     L.hipjpegGetImageInfo.argtypes = [vp, sz, ctypes.POINTER(ImageInfo)]
     L.hipjpegEntropyDecodeHost.argtypes = [vp, sz, vp, sz, vp, vp]
     L.hipjpegEntropyDecodeGpuAlgorithmHost.argtypes = [vp, sz, vp, sz, vp, ctypes.POINTER(ctypes.c_int32)]
@@ -155,6 +167,7 @@ def load():
     L.hipjpegDecodeBatchSubmit.argtypes = [vp, vp, vp, i32, vp, i32, ctypes.c_uint, vp]
     L.hipjpegDecodeBatchWait.argtypes = [vp, vp, i32]
     L.hipjpegSetPipelineDepth.argtypes = [vp, i32]
+    L.hipjpegSetAllocators.argtypes = [vp, ctypes.POINTER(Allocators)]
     L.hipjpegSetHybridHuffmanThreshold.argtypes = [vp, ctypes.c_uint64]
     L.hipjpegDecodeBatchTransferStats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int32)]
     L.hipjpegEntropyDecodeHostSparse.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz), vp]

@@ -332,6 +332,7 @@ hipjpegStatus_t DecodeBatch::plan_once(const PlanArgs& a, int n, hipjpegStatus_t
     prog_to_image_.clear();
     prog_walk_images_ = 0;
     interval_takeover_images_ = 0;
+    host_fallback_images_ = 0;  // (resolve() counts only for a batch with GPU-decoded streams: any other must not report its page's last one)
     xform_desc_.clear();
     prog_slot_words_ = 0;
     max_huff_units_ = max_pool_words_ = 0;

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "huffman_encode_core.h"
+#include "scratch_fill.h"
 
 namespace hipjpeg {
 
@@ -60,7 +61,7 @@ void encode(HencImage im, const EncodeGeometry& g, const uint16_t qlum[64], cons
     StandardCodeTables T;
     if (optimized) {
         uint32_t counts[2][2][256];
-        memset(counts, 0, sizeof counts);
+        memset(counts, 0, sizeof counts);  // (stands for EncodeBatch::henc_histograms()'s hipMemsetAsync of HencLayout1::hist, encoder_core.cpp)
         for (uint32_t s = 0; s < n; s++) {
             const Fetched f = fetch_block<RST>(im, s);
             henc_count_block(f.w, f.real, f.diff, HostCount{counts[f.ti]});
@@ -71,13 +72,13 @@ void encode(HencImage im, const EncodeGeometry& g, const uint16_t qlum[64], cons
         write_standard_headers(g, qlum, qchr, out, restart_interval);
     }
     // length: lane per block
-    std::vector<uint16_t> bits(n);
+    std::vector<uint16_t> bits = device_scratch<uint16_t>(n);  // HencLayout1::bits: henc_length_kernel stores every block's
     for (uint32_t s = 0; s < n; s++) {
         const Fetched f = fetch_block<RST>(im, s);
         bits[s] = (uint16_t)henc_code_block<false>(f.w, f.real, f.diff, &T, f.ti, (HencEmitter<HostWords>*)nullptr);
     }
     // scan: every lane's range, the workgroup's doubling steps over the lanes' spans, every lane's range again
-    std::vector<uint32_t> off(n);
+    std::vector<uint32_t> off = device_scratch<uint32_t>(n);  // HencLayout1::off: the scan kernels store every block's
     const uint32_t per = (n + kLanes - 1) / kLanes;
     HencSpan sum[kLanes];
     for (uint32_t t = 0; t < kLanes; t++) {
@@ -100,7 +101,8 @@ void encode(HencImage im, const EncodeGeometry& g, const uint16_t qlum[64], cons
         }
     }
     const uint32_t total = henc_span_apply(0u, sum[kLanes - 1]);
-    // write: lane per block into the zeroed bit buffer, the marker bitmap behind it
+    // write: lane per block into the zeroed bit buffer, the marker bitmap behind it (the zero stands for henc_zero_kernel,
+    // gpu_huffman_encode.hip, which EncodeBatch::henc_assemble() launches over all of HencLayout2::raw: bit buffers and bitmaps)
     im.raw_bytes = (total + 7) / 8;
     std::vector<uint8_t> raw((size_t)henc_map_offset(im.raw_bytes) + henc_map_bytes(im.raw_bytes), 0);
     im.raw = raw.data();

@@ -1,5 +1,6 @@
 // gpu_huffman_host.cpp -- see gpu_huffman_host.h
 #include "gpu_huffman_host.h"
+#include "scratch_fill.h"
 
 #include <algorithm>
 #include <cstring>
@@ -349,13 +350,14 @@ namespace {
 // One scan of the frame, as the kernels decode it from its own HuffImage.  Returns 0 or the status the kernels would report.
 int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, int16_t* const frame_coef[4], int* sync_passes)
 {
-    std::vector<uint8_t> stream(destuffed_capacity(sc));
+    // (device scratch: destuff_compact_kernel writes the kept bytes and the 0xFF slack behind them, nothing else)
+    std::vector<uint8_t> stream = device_scratch<uint8_t>(destuffed_capacity(sc));
     const size_t n = destuff_scan(data, sc, stream.data());
     std::vector<uint16_t> pool(gpu_pool_words(sc));
     HuffImage im;
     fill_huff_image(f, sc, (uint32_t)n, &im);
     build_gpu_pool(sc, &im, pool.data());
-    std::vector<int16_t> dc_diff(im.total_blocks);
+    std::vector<int16_t> dc_diff = device_scratch<int16_t>(im.total_blocks);  // WorkLayout::dc_diff: the block pass writes every block's
     std::vector<uint32_t> boundaries;
     for (uint32_t b : sc.rst_after) boundaries.push_back(b * 8u);
     im.stream = stream.data();
@@ -370,9 +372,16 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
         int16_t* const coef = frame_coef[c];
         im.coef[i] = coef;
         // every coded block must be written by the write pass; a one-component scan codes the real blocks only (T.81 A.2.2), the
-        // padding blocks of its MCU-padded grid stay zero as in the host decoder
-        const size_t bw = (size_t)f.comp[c].blocks_w, rows = sc.ncomp == 1 ? im.mcus_y : (size_t)f.comp[c].blocks_h;
+        // padding blocks of its MCU-padded grid are zero as in the host decoder: the zero stands for the fills of
+        // DecodeBatch::build_entropy_units() (decoder_core.cpp: huff_zero_, merged by merge_zero_fills(), issued as hipMemsetAsync /
+        // hipMemset2DAsync in enqueue_gpu_entropy()) and covers what they cover -- the bottom rows alone when the real blocks fill whole
+        // rows, else the whole component
+        const size_t bw = (size_t)f.comp[c].blocks_w, bh = (size_t)f.comp[c].blocks_h, rows = sc.ncomp == 1 ? im.mcus_y : bh;
         const size_t cols = sc.ncomp == 1 ? im.mcus_x : bw;
+        if (sc.ncomp == 1 && (im.mcus_x < bw || im.mcus_y < bh)) {
+            const size_t first = im.mcus_x < bw ? 0 : (size_t)im.mcus_y * bw;
+            memset(coef + first * 64, 0, (bw * bh - first) * 128);
+        }
         for (size_t y = 0; y < rows; y++) memset(coef + y * bw * 64, 0x5A, cols * 128);
     }
     int16_t block_buffer[64] = {0};
@@ -393,12 +402,12 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
     }
     const HuffGeom geom = make_geom(im);
     const uint32_t ns = im.num_subseq;
-    std::vector<SubseqState> cur(ns), nxt(ns);
+    std::vector<SubseqState> cur = device_scratch<SubseqState>(ns), nxt = device_scratch<SubseqState>(ns);  // the states, at 0 of work_
     uint32_t err = 0;
     // Block-start records, as the kernels take them: every decode from a start state that can be final records and writes the mark
     // (in pass 0 only subsequence 0, whose start state is exact: the kernels decode it once more in round 1, from the same state).
     // Not for restart intervals.
-    std::vector<uint16_t> records((size_t)ns * kRecShorts, 0);
+    std::vector<uint16_t> records = device_scratch<uint16_t>((size_t)ns * kRecShorts);  // WorkLayout::records
     // Every walk runs in the form huff_sync_kernel uses (select_walk) and again in the form of the tail kernels' lanes
     // (decode_subsequence): same end state and same record, from true and from wrong start states, or `forms_differ` (return 5).
     bool forms_differ = false;
@@ -468,7 +477,7 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
         }
     }
     // block index of each subsequence's first symbol
-    std::vector<uint32_t> first_block(ns);
+    std::vector<uint32_t> first_block = device_scratch<uint32_t>(ns);  // WorkLayout::first_block
     uint32_t acc = 0;
     for (uint32_t i = 0; i < ns; i++) {
         first_block[i] = acc;
@@ -477,6 +486,8 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
     if (acc < im.total_blocks) return 2;
     // write pass, step 1: block start positions.  A usable record must name exactly the blocks the position walk finds, at the
     // same positions (the kernels copy it instead of walking: huff_pos_kernel); else return 5.
+    // (not scratch contents but a detector the kernels do not have: a block nobody positioned is reported below instead of decoded
+    // from whatever WorkLayout::block_pos held)
     std::vector<uint32_t> block_pos(im.total_blocks, 0xFFFFFFFFu);
     std::vector<uint32_t> found_block, found_pos;
     for (uint32_t i = 0; i < ns; i++) {
@@ -540,8 +551,9 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
 int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4], int* sync_passes)
 {
     (void)size;
-    // the blocks no scan codes (padding of a one-component scan's grid) stay zero
-    for (int c = 0; c < f.ncomp; c++) memset(coef[c], 0, (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 128);
+    // the coefficient blocks of a GPU-decoded picture lie in the device-only part of the arena, which nobody clears: emulate_scan()
+    // zeroes what the planner's fills zero (the padding of a one-component scan's grid), the write pass writes every coded block
+    for (int c = 0; c < f.ncomp; c++) fill_device_scratch(coef[c], (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 128);
     int passes = 0;
     for (const ScanHeader& sc : f.scans) {  // the scans are independent: each on its own, as the batched launches take them
         int p = 0;

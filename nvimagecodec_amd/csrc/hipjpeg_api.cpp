@@ -17,6 +17,7 @@
 #include "lossless_batch.h"
 #include "progressive_encode.h"
 #include "progressive_gpu_host.h"
+#include "scratch_fill.h"
 #include "thread_pool.h"
 #include "transcode_core.h"
 
@@ -153,6 +154,13 @@ hipjpegStatus_t hipjpegTestSetFault(const char* site, int countdown)
         set_fault(site, countdown);
         return HIPJPEG_STATUS_SUCCESS;
     });
+}
+
+hipjpegStatus_t hipjpegTestSetScratchFill(int byte)
+{
+    if (!test_hooks_enabled() || byte < 0 || byte > 255) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    scratch_fill_byte().store(byte);
+    return HIPJPEG_STATUS_SUCCESS;
 }
 
 hipjpegStatus_t hipjpegGetImageInfo(const uint8_t* data, size_t length, hipjpegImageInfo_t* info)
@@ -507,6 +515,25 @@ hipjpegStatus_t hipjpegSetHybridHuffmanThreshold(hipjpegHandle_t handle, uint64_
     if (!handle) return HIPJPEG_STATUS_INVALID_ARGUMENT;
     for (auto& b : handle->batches)
         if (b) b->set_gpu_entropy_threshold(pixels);
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+hipjpegStatus_t hipjpegSetAllocators(hipjpegHandle_t handle, const hipjpegAllocators_t* allocators)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    // every Buffer of the handle (decode pages, encode batch and pages, lossless pages) points at handle->hooks and marks it used at
+    // its first allocation: until then no memory exists that another allocator would have to take back
+    if (!handle || !allocators || handle->hooks.used.load()) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    MemoryHooks& k = handle->hooks;
+    const bool device = allocators->device_malloc && allocators->device_free;
+    const bool pinned = allocators->pinned_malloc && allocators->pinned_free;
+    k.device_malloc = device ? allocators->device_malloc : nullptr;
+    k.device_free = device ? allocators->device_free : nullptr;
+    k.device_ctx = device ? allocators->device_ctx : nullptr;
+    k.pinned_malloc = pinned ? allocators->pinned_malloc : nullptr;
+    k.pinned_free = pinned ? allocators->pinned_free : nullptr;
+    k.pinned_ctx = pinned ? allocators->pinned_ctx : nullptr;
     return HIPJPEG_STATUS_SUCCESS;
     });
 }

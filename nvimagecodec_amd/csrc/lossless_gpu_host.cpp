@@ -1,5 +1,6 @@
 // lossless_gpu_host.cpp -- see lossless_gpu_host.h
 #include "lossless_gpu_host.h"
+#include "scratch_fill.h"
 
 #include <cstring>
 #include <new>
@@ -99,16 +100,20 @@ uint32_t segment_schedule(const uint8_t* raw, uint32_t raw_bytes, const uint32_t
 {
     // ---- destuff: count per chunk, then compact
     const uint32_t nchunks = (raw_bytes + kLlDestuffChunk - 1) / kLlDestuffChunk;
-    std::vector<uint32_t> drops(nchunks, 0u);
+    std::vector<uint32_t> drops = device_scratch<uint32_t>(nchunks);  // ll_destuff_count_kernel stores every chunk's count
     const auto byte = [&](uint32_t i) -> uint32_t { return i < raw_bytes ? raw[i] : 0x01u; };
     const auto lane_mask = [&](uint32_t off) -> uint32_t {
         if (off >= raw_bytes) return 0u;
         const uint32_t len = raw_bytes - off < kLlDestuffLaneBytes ? raw_bytes - off : kLlDestuffLaneBytes;
         return ll_destuff_mask(byte, off, kLlDestuffLaneBytes) & ((1u << len) - 1u);
     };
-    for (uint32_t c = 0; c < nchunks; c++)
-        for (uint32_t t = 0; t < kLlLanes; t++) drops[c] += (uint32_t)__builtin_popcount(lane_mask(c * kLlDestuffChunk + t * kLlDestuffLaneBytes));
-    std::vector<uint8_t> stream(((size_t)raw_bytes + 3) & ~(size_t)3, 0xFF);
+    for (uint32_t c = 0; c < nchunks; c++) {
+        uint32_t total = 0;  // (the workgroup's sum: registers and LDS)
+        for (uint32_t t = 0; t < kLlLanes; t++) total += (uint32_t)__builtin_popcount(lane_mask(c * kLlDestuffChunk + t * kLlDestuffLaneBytes));
+        drops[c] = total;
+    }
+    // the destuffed stream: the kept bytes, and ones up to the end of the last word (ll_destuff_compact_kernel's last chunk, below)
+    std::vector<uint8_t> stream = device_scratch<uint8_t>(((size_t)raw_bytes + 3) & ~(size_t)3);
     uint32_t before = 0;
     for (uint32_t c = 0; c < nchunks; c++) {
         uint32_t excl = 0;
@@ -125,12 +130,15 @@ uint32_t segment_schedule(const uint8_t* raw, uint32_t raw_bytes, const uint32_t
         before += drops[c];
     }
     const uint32_t total_bits = (raw_bytes - before) * 8u;
+    for (uint32_t b = raw_bytes - before; b < ((raw_bytes - before + 3u) & ~3u); b++) stream[b] = 0xFF;
 
     // ---- pass 0, rounds, ripple launches
     const uint32_t nsub = ll_num_subseq(total_bits);
     const uint32_t nunits = (nsub + kLlLanes - 1) / kLlLanes;
-    std::vector<uint64_t> start(nsub), end(nsub), unit_out(2 * (size_t)nunits, 0ull);
-    std::vector<uint32_t> count(nsub), unit_count(nunits, 0u);
+    // (device scratch, all five: launch 0 writes start / end / count of every subsequence, and unit_out[0 ..] and unit_count of every unit)
+    std::vector<uint64_t> start = device_scratch<uint64_t>(nsub), end = device_scratch<uint64_t>(nsub),
+                          unit_out = device_scratch<uint64_t>(2 * (size_t)nunits);
+    std::vector<uint32_t> count = device_scratch<uint32_t>(nsub), unit_count = device_scratch<uint32_t>(nunits);
     HostEnv env{stream.data(), (total_bits + 31u) / 32u, tables};
     const bool shared = ntables == 1u;
     const uint32_t phases = shared ? 1u : ncomp;

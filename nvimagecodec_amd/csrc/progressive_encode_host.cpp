@@ -5,6 +5,7 @@
 
 #include "huffman_encode_core.h"
 #include "progressive_encode.h"
+#include "scratch_fill.h"
 
 namespace hipjpeg {
 
@@ -74,12 +75,18 @@ void encode_scan(PencScan sc, const ScanSpec& spec, int dri, std::vector<uint8_t
 {
     sc.first_block = 0;
     const uint32_t n = sc.nblocks;
+    // hist: the zero stands for EncodeBatch::penc_statistics()'s hipMemsetAsync of PencLayout1::hist (encoder_core.cpp); codes is the
+    // host's own table, uploaded whole
     uint32_t hist[256], codes[256];
     memset(hist, 0, sizeof hist);
     memset(codes, 0, sizeof codes);
-    std::vector<uint8_t> sum(n);
-    std::vector<uint32_t> pre(n), post(n), piece(n), flusher(n), off(n);
-    std::vector<uint16_t> rel(n), own(n), bits(n);
+    // pre, post: the zeros stand for the hipMemsetAsync of PencLayout1::pre / post in the same place (the run kernel stores only where a
+    // run is flushed, every later kernel reads every block's).  Everything else is device scratch: sum, own, bits and off are written
+    // for every block; piece, flusher and rel only where a block has them, and are read only there.
+    std::vector<uint8_t> sum = device_scratch<uint8_t>(n);
+    std::vector<uint32_t> pre(n), post(n);
+    std::vector<uint32_t> piece = device_scratch<uint32_t>(n), flusher = device_scratch<uint32_t>(n), off = device_scratch<uint32_t>(n);
+    std::vector<uint16_t> rel = device_scratch<uint16_t>(n), own = device_scratch<uint16_t>(n), bits = device_scratch<uint16_t>(n);
     // summary: lane per block
     const HostCount cnt{hist};
     for (uint32_t i = 0; i < n; i++) sum[i] = (uint8_t)penc_block_summary<RST>(sc, i, cnt);
@@ -150,7 +157,8 @@ void encode_scan(PencScan sc, const ScanSpec& spec, int dri, std::vector<uint8_t
         }
         total = henc_span_apply(0u, span[kLanes - 1]);
     }
-    // write: lane per block into the zeroed bit buffer, the marker bitmap behind it
+    // write: lane per block into the zeroed bit buffer, the marker bitmap behind it (the zero stands for henc_zero_kernel,
+    // gpu_huffman_encode.hip, which EncodeBatch::henc_assemble() launches over all of HencLayout2::raw: bit buffers and bitmaps)
     const uint32_t raw_bytes = (total + 7) / 8;
     std::vector<uint8_t> raw((size_t)henc_map_offset(raw_bytes) + henc_map_bytes(raw_bytes), 0);
     uint8_t* map = raw.data() + henc_map_offset(raw_bytes);

@@ -1,5 +1,6 @@
 // progressive_gpu_host.cpp -- see progressive_gpu_host.h
 #include "progressive_gpu_host.h"
+#include "scratch_fill.h"
 
 #include <algorithm>
 
@@ -372,16 +373,20 @@ int emulate_gpu_progressive(const uint8_t* data, size_t size, const FrameInfo& f
         streams[s].nwords = (uint32_t)((((n + 3) & ~(size_t)3) + kStreamSlackBytes) / 4);
         total_bits[s] = (uint32_t)n * 8u;
     }
+    // (the zero stands for prog_replay_kernel's zeroed LDS buffers, progressive_gpu.hip: it stores EVERY block of the allocation grid,
+    // the blocks of the MCU padding as zeros; the replay below writes into the blocks themselves)
     for (int c = 0; c < f.ncomp; c++) memset(coef[c], 0, (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 128);
     // ---- walk: block start positions of every AC scan, stage after stage per component
     std::vector<std::vector<uint32_t>> block_pos(f.scans.size());
     for (int c = 0; c < f.ncomp; c++) {
         const size_t nb = (size_t)im.nbx[c] * im.nby[c];
+        // (the zero stands for DevWalker::group_begin()'s hlo = hhi = 0, progressive_gpu.hip: the walk's histories are registers and LDS
+        // rings, never arena memory, and a component's first scan starts every group from empty ones)
         std::vector<uint64_t> hist((nb + kProgGroup) & ~(size_t)(kProgGroup - 1), 0);
         for (int stg = 0; stg < (int)im.chain_len[c]; stg++) {
             const int s = im.chain[c][stg];
             ProgScan& sc = im.scan[s];
-            block_pos[s].assign((nb + kProgGroup) & ~(size_t)(kProgGroup - 1), 0);
+            block_pos[s] = device_scratch<uint32_t>((nb + kProgGroup) & ~(size_t)(kProgGroup - 1));  // WorkLayout::prog_pos: group_end() stores blocks < nblocks
             sc.block_pos = block_pos[s].data();
             HostWalker w;
             w.st = streams[s];
@@ -503,17 +508,19 @@ int emulate_gpu_progressive_intervals(const uint8_t* data, size_t size, const Fr
         total_bits[s] = (uint32_t)n * 8u;
         for (uint32_t b : f.scans[s].rst_after) starts[s].push_back(b * 8u);
     }
-    for (int c = 0; c < f.ncomp; c++) memset(coef[c], 0, (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 128);
+    for (int c = 0; c < f.ncomp; c++) memset(coef[c], 0, (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 128);  // (prog_replay_kernel, as above)
     HostIntervalEnv ienv{streams.data(), total_bits.data(), starts.data(), pool.data(), &im};
     ienv.coef = coef;
     // ---- AC items: block start positions of every AC scan, one item per (component, interval)
     std::vector<std::vector<uint32_t>> block_pos(f.scans.size());
     for (int c = 0; c < f.ncomp; c++) {
         const size_t nb = (size_t)im.nbx[c] * im.nby[c];
-        std::vector<uint64_t> hist(nb, 0);
+        // (device scratch, both: ProgIntervalImage::hist and the scans' block_pos lie in WorkLayout::prog_pos; the first stage of
+        // prog_interval_ac() starts from h = 0 without reading, every stage stores every block of its interval)
+        std::vector<uint64_t> hist = device_scratch<uint64_t>(nb);
         for (int stg = 0; stg < (int)im.chain_len[c]; stg++) {
             const int s = im.chain[c][stg];
-            block_pos[s].assign(nb, 0);
+            block_pos[s] = device_scratch<uint32_t>(nb);
             im.scan[s].block_pos = block_pos[s].data();
         }
         ienv.hist_all = hist.data();

@@ -11,6 +11,7 @@ hipjpegStatus_t Buffer::reserve(size_t bytes)
     release();
     size_t want = align_up(bytes + bytes / 8, 1 << 20);  // headroom so a slightly bigger next batch does not reallocate
     void* p = nullptr;
+    if (hooks_) hooks_->used.store(true);
     if (kind_ == kDevice && hooks_ && hooks_->device_malloc) {
         if (hooks_->device_malloc(hooks_->device_ctx, &p, want, nullptr) != 0 || !p) return HIPJPEG_STATUS_ALLOC_FAILED;
         custom_ = true;

@@ -1,6 +1,7 @@
 // staging.h -- the memory every batch (decode and encode) stages its tables in: grow-only device / pinned buffers, allocated
 // through the caller's hooks when there are any, and the bump allocator that lays out an arena inside one of them.
 #pragma once
+#include <atomic>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -18,6 +19,16 @@ struct MemoryHooks {
     int (*pinned_malloc)(void* ctx, void** ptr, size_t size, void* stream) = nullptr;
     int (*pinned_free)(void* ctx, void* ptr, size_t size, void* stream) = nullptr;
     void* pinned_ctx = nullptr;
+    // Set by the first Buffer that allocates with these hooks (any kind, custom or not): from then on the functions may not change,
+    // or a buffer would be handed back to another allocator than the one it came from (hipjpegSetAllocators).
+    mutable std::atomic<bool> used{false};
+    MemoryHooks() = default;
+    MemoryHooks(const MemoryHooks& o)
+        : device_malloc(o.device_malloc), device_free(o.device_free), device_ctx(o.device_ctx), pinned_malloc(o.pinned_malloc),
+          pinned_free(o.pinned_free), pinned_ctx(o.pinned_ctx), used(o.used.load())
+    {
+    }
+    MemoryHooks& operator=(const MemoryHooks&) = delete;
 };
 
 class Buffer {

@@ -50,6 +50,14 @@ def entropy_decode_host_sparse(data):
     return out, int(n.value)
 
 
+def set_twin_scratch_fill(byte):
+    """hipjpegTestSetScratchFill: the byte the host twins of the GPU algorithms fill their stand-ins for device scratch with
+    (process-wide, 0 = the default; test hook)."""
+    st = N.load().hipjpegTestSetScratchFill(int(byte))
+    if st:
+        raise N.HipJpegError(st, "hipjpegTestSetScratchFill")
+
+
 def get_image_info(data):
     a = _as_u8(data)
     info = N.ImageInfo()
@@ -165,10 +173,22 @@ def output_shapes(jpegs, fmt="rgb", transforms=None, scales=None):
     return shapes
 
 
-class BatchDecoder:
-    """hipjpegCreate / hipjpegDecodeBatch* on one device."""
+def _set_allocators(handle, allocators):
+    """hipjpegSetAllocators on a fresh handle.  `allocators`: None, an _native.Allocators structure, or an object whose
+    hipjpeg_allocators() returns one (it is kept alive with the handle: the library calls its functions until hipjpegDestroy)."""
+    if allocators is None:
+        return None
+    table = allocators.hipjpeg_allocators() if hasattr(allocators, "hipjpeg_allocators") else allocators
+    st = N.load().hipjpegSetAllocators(handle, ctypes.byref(table))
+    if st:
+        raise N.HipJpegError(st, "hipjpegSetAllocators")
+    return (allocators, table)
 
-    def __init__(self, device=0, num_threads=0):
+
+class BatchDecoder:
+    """hipjpegCreate / hipjpegDecodeBatch* on one device.  allocators (every Batch* class here takes it): see _set_allocators."""
+
+    def __init__(self, device=0, num_threads=0, allocators=None):
         import torch
         self._torch = torch
         self.device = int(device)
@@ -176,6 +196,7 @@ class BatchDecoder:
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
         if st:
             raise N.HipJpegError(st, "hipjpegCreate")
+        self._allocators = _set_allocators(self._h, allocators)
         self._keep = None
         self._inflight = []
 
@@ -462,7 +483,7 @@ class BatchEncoder:
     interval (FLAG_GPU_RESTART_INTERVALS); gpu_progressive_restart: with gpu_huffman, the GPU coder also takes progressive images with
     a restart interval (FLAG_GPU_PROGRESSIVE_RESTART)."""
 
-    def __init__(self, device=0, num_threads=0, gpu_huffman=False, gpu_restart=False, gpu_progressive_restart=False):
+    def __init__(self, device=0, num_threads=0, gpu_huffman=False, gpu_restart=False, gpu_progressive_restart=False, allocators=None):
         import torch
         self._torch = torch
         self.device = int(device)
@@ -474,6 +495,7 @@ class BatchEncoder:
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
         if st:
             raise N.HipJpegError(st, "hipjpegCreate")
+        self._allocators = _set_allocators(self._h, allocators)
         self._keep = None
         self._n = 0
 
@@ -684,7 +706,7 @@ class BatchTranscoder:
     (FLAG_GPU_PROGRESSIVE_RESTART).  The bytes do not depend on any of them."""
 
     def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False, gpu_progressive_intervals=False,
-                 gpu_progressive_restart=False):
+                 gpu_progressive_restart=False, allocators=None):
         import torch
         self._torch = torch
         self.device = int(device)
@@ -696,6 +718,7 @@ class BatchTranscoder:
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
         if st:
             raise N.HipJpegError(st, "hipjpegCreate")
+        self._allocators = _set_allocators(self._h, allocators)
 
     def close(self):
         if self._h:
@@ -890,7 +913,7 @@ class BatchCoefficients:
     progressive output with a restart interval.  Neither the tensors nor the bytes depend on any of them."""
 
     def __init__(self, device=0, num_threads=0, gpu_huffman=True, gpu_restart=False, gpu_progressive_intervals=False,
-                 gpu_progressive_restart=False):
+                 gpu_progressive_restart=False, allocators=None):
         import torch
         self._torch = torch
         self.device = int(device)
@@ -902,6 +925,7 @@ class BatchCoefficients:
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
         if st:
             raise N.HipJpegError(st, "hipjpegCreate")
+        self._allocators = _set_allocators(self._h, allocators)
 
     def close(self):
         if self._h:
@@ -1237,7 +1261,7 @@ class BatchLosslessDecoder:
     samples, uint16 (or uint8 for files of precision <= 8), H x W x N or N x H x W.  The entropy stage runs on host threads; prediction
     runs on the GPU.  gpu_entropy=True: hipjpegDecodeLosslessBatchFlags with HIPJPEG_FLAG_GPU_HUFFMAN, the entropy stage on the GPU too."""
 
-    def __init__(self, device=0, num_threads=0, gpu_entropy=False):
+    def __init__(self, device=0, num_threads=0, gpu_entropy=False, allocators=None):
         import torch
         self._torch = torch
         self.device = int(device)
@@ -1246,6 +1270,7 @@ class BatchLosslessDecoder:
         st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
         if st:
             raise N.HipJpegError(st, "hipjpegCreate")
+        self._allocators = _set_allocators(self._h, allocators)
 
     def close(self):
         if self._h:

@@ -31,6 +31,7 @@ def test_libraries_export_every_declared_symbol_and_nothing_of_each_others():
     ext, host = _exported(_native.LIB_PATH), _exported(_native.HOST_LIB_PATH)
     hip_decl, nv_decl = _declared_functions("hipjpeg.h"), _declared_functions("nvimgcodec_abi.h")
     assert "nvimgcodecExtensionModuleEntry" in nv_decl and "hipjpegDecodeBatch" in hip_decl
+    assert {"hipjpegSetAllocators", "hipjpegTestSetScratchFill"} <= hip_decl and {"hipjpegSetAllocators", "hipjpegTestSetScratchFill"} <= ext
     harness_only = {"hipjpegTestDoubleReports"}  # counted by the harness's future objects
     missing = [n for n in sorted(hip_decl - harness_only) if n not in ext]
     assert not missing, f"declared in include/hipjpeg.h but not exported by the extension: {missing}"
@@ -49,6 +50,17 @@ def test_ctypes_mirror_matches_reference_layout():
     assert A.ImageInfo.buffer.offset == 2208 and A.ImageInfo.cuda_stream.offset == 2232 and A.ImageInfo.plane_info.offset == 416
     assert A.DecoderDesc.canDecode.offset == 72 and A.DecoderDesc.decode.offset == 80
     assert A.FrameworkDesc.registerDecoder.offset == 80 and A.ExecutionParams.device_id.offset == 56
+
+
+def test_allocators_structure_and_argument_rules():
+    """hipjpegAllocators_t: six pointers, the plugin's function signatures (one ctypes prototype serves both); without a handle or a
+    table the call is refused (the rule about the first batch needs a device: tests/test_gpu_poisoned_arenas.py)"""
+    assert C.sizeof(_native.Allocators) == 6 * C.sizeof(C.c_void_p)
+    assert [n for n, _ in _native.Allocators._fields_] == ["device_malloc", "device_free", "device_ctx", "pinned_malloc", "pinned_free", "pinned_ctx"]
+    assert _native.AllocatorMalloc is A.DeviceMalloc and _native.AllocatorFree is A.DeviceFree
+    lib = _native.load()
+    table = _native.Allocators()
+    assert lib.hipjpegSetAllocators(None, C.byref(table)) == 1 and lib.hipjpegSetAllocators(None, None) == 1
 
 
 def test_extension_module_entry_contract():
