@@ -153,6 +153,14 @@ HIPJPEG_API int32_t hipjpegTestScanChunkDrops(const uint8_t* data, size_t length
  * steps: 65,536 entries.  Returns 0, or a negative value for a table the stage does not accept. */
 HIPJPEG_API int32_t hipjpegTestPairSteps(const uint8_t bits[16], const uint8_t* vals, int32_t nvals, uint32_t* steps);
 
+/* Test hook (host only): how much the first synchronisation launch of the GPU entropy stage decodes, counted by the host twin
+ * (hipjpegEntropyDecodeGpuAlgorithmHost, whose self-checks run as well and answer INTERNAL_ERROR) for both of its schedules, summed over
+ * the file's scans.  counts[0..4]: one sync unit per workgroup -- subsequence decodes of pass 0, 0, of correction round 1, of round 2,
+ * and the tasks left for the tail kernel behind round 2.  counts[5..9]: two units per workgroup, the schedule the kernels run -- decodes
+ * of phase A (even rows from the assumed state), phase B (odd rows from their neighbour's end state), round 1, round 2, and the tasks
+ * left for the tail kernel.  Halo rows count as decodes. */
+HIPJPEG_API hipjpegStatus_t hipjpegTestSyncScheduleCounts(const uint8_t* data, size_t length, uint64_t counts[10]);
+
 /* Test hook (host only): the byte the host twins of the GPU algorithms (hipjpegEntropyDecodeGpuAlgorithmHost,
  * hipjpegEntropyDecodeGpuIntervalAlgorithmHost, hipjpegLosslessEntropyAlgorithmHost, hipjpegEncodeBaselineGpuAlgorithmHost,
  * hipjpegEncodeProgressiveGpuAlgorithmHost) fill their stand-ins for device scratch with, 0..255, from now on and process-wide; 0 is the

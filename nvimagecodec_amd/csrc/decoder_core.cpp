@@ -335,7 +335,7 @@ hipjpegStatus_t DecodeBatch::plan_once(const PlanArgs& a, int n, hipjpegStatus_t
     host_fallback_images_ = 0;  // (resolve() counts only for a batch with GPU-decoded streams: any other must not report its page's last one)
     xform_desc_.clear();
     prog_slot_words_ = 0;
-    max_huff_units_ = max_pool_words_ = 0;
+    max_huff_units_ = max_huff_pairs_ = max_pool_words_ = 0;
     coef_bytes_ = output_bytes_ = 0;
     if (pool_ && n > 1)
         pool_->parallel_for(n, [&](int i, int) { prepare(i, a); });
@@ -656,7 +656,9 @@ void DecodeBatch::size_image(int i, Sizing& s)
         const size_t nsub = (s.scan(sc, &q.raw_offset, &q.stream_offset, &q.first_chunk) * 8 + kSubseqBits - 1) / kSubseqBits;
         const size_t mcus = (size_t)scan_mcus_x(f, sc) * scan_mcus_y(f, sc);
         s.subseq += nsub;
-        max_huff_units_ += std::max<size_t>((nsub + kHuffOwn - 1) / kHuffOwn, 1);  // (an empty stream keeps the unit at 0: it reports the image)
+        const size_t sync_units = std::max<size_t>((nsub + kHuffOwn - 1) / kHuffOwn, 1);  // (an empty stream keeps the unit at 0: it reports the image)
+        max_huff_units_ += sync_units;
+        max_huff_pairs_ += (sync_units + 1) / 2;
         q.pool_words = gpu_pool_words(sc);
         q.tables_offset = s.pools.take(align_up(q.pool_words * 2, 64), 1);
         max_pool_words_ = std::max(max_pool_words_, q.pool_words);
@@ -677,6 +679,7 @@ void DecodeBatch::layout(const Sizing& s)
     L.units = c.take(sizeof(WorkUnit) * s.units);
     L.huff_desc = c.take(sizeof(HuffImage) * (ng + s.prog_scans));
     L.huff_units = c.take(sizeof(HuffUnit) * max_huff_units_);
+    L.huff_pairs = c.take(sizeof(uint32_t) * max_huff_pairs_);
     L.huff_wunits = c.take(sizeof(HuffUnit) * s.huff_wunits);
     L.huff_dc_units = c.take(sizeof(HuffUnit) * ng * 4);
     L.huff_chunk_units = c.take(sizeof(HuffUnit) * chunks);
@@ -1036,6 +1039,7 @@ void DecodeBatch::build_pixel_units()
 void DecodeBatch::build_entropy_units()
 {
     for (std::vector<HuffUnit>* v : {&huff_units_, &huff_wunits_, &huff_chunk_units_, &huff_dc_units_, &prog_units_}) v->clear();
+    huff_pairs_.clear();
     uint32_t first_subseq = 0;
     stream_bytes_total_ = 0;
     huff_zero_.clear();
@@ -1080,7 +1084,10 @@ void DecodeBatch::build_entropy_units()
         h.first_subseq = first_subseq;
         first_subseq += h.num_subseq;
         // (the unit at 0 also for an empty stream: its workgroup of the position kernel flags the image)
+        const size_t first_unit = huff_units_.size();
         for (uint32_t j = 0; j == 0 || j < h.num_subseq; j += kHuffOwn) huff_units_.push_back(HuffUnit{(uint32_t)g, j});
+        // the first sync launch takes the image's units two at a time (an odd count: the last one alone)
+        for (size_t i = first_unit; i < huff_units_.size(); i += 2) huff_pairs_.push_back(huff_pair_entry((uint32_t)i, i + 1 < huff_units_.size()));
         if (h.restart_interval)  // the predictor starts over inside the scan: the per-component scan (everything else: per MCU group)
             for (uint32_t i = 0; i < h.ncomp; i++) huff_dc_units_.push_back(HuffUnit{(uint32_t)g, i});
         stream_bytes_total_ += q.stream_bytes;
@@ -1249,6 +1256,7 @@ void DecodeBatch::stage_tables()
     copy_table(pinned_, staging_.prog_iv_units, prog_iv_units_);
     copy_table(pinned_, staging_.huff_desc, huff_images_);
     copy_table(pinned_, staging_.huff_units, huff_units_);
+    copy_table(pinned_, staging_.huff_pairs, huff_pairs_);
     copy_table(pinned_, staging_.huff_wunits, huff_wunits_);
     copy_table(pinned_, staging_.huff_dc_units, huff_dc_units_);
     copy_table(pinned_, staging_.huff_chunk_units, huff_chunk_units_);
@@ -1342,10 +1350,11 @@ hipjpegStatus_t DecodeBatch::enqueue_gpu_entropy(void* stream)
     static const int tail_after = getenv("HIPJPEG_TAIL_AFTER") ? atoi(getenv("HIPJPEG_TAIL_AFTER")) : 2;  // tuning aid; 0 = no tail kernel
     uint16_t* tail_tasks = at<uint16_t>(work_, scratch_.tail);
     uint32_t* tail_count = at<uint32_t>(work_, scratch_.tail + (size_t)max_huff_units_ * kTailTaskBytes);
-    if (launch_huff_sync(L.dimg, L.dunits, L.nunits, L.states, L.incoming, L.changed, 1, tail_after > 0 ? tail_after : 1 << 20,
+    if (launch_huff_sync(L.dimg, L.dunits, L.nunits, at<const uint32_t>(device_, staging_.huff_pairs), (int)huff_pairs_.size(), L.states, L.incoming,
+                         L.changed, 1, tail_after > 0 ? tail_after : 1 << 20,
                          tail_after > 0 ? tail_tasks : nullptr, tail_after > 0 ? tail_count : nullptr, L.records, L.pool_bytes, stream) != 0)
         return HIPJPEG_STATUS_HIP_ERROR;
-    if (launch_huff_sync(L.dimg, L.dunits, L.nunits, L.states, L.incoming, L.changed, 0, 1 << 20, nullptr, nullptr, L.records, L.pool_bytes, stream, 1) != 0)
+    if (launch_huff_sync(L.dimg, L.dunits, L.nunits, nullptr, 0, L.states, L.incoming, L.changed, 0, 1 << 20, nullptr, nullptr, L.records, L.pool_bytes, stream, 1) != 0)
         return HIPJPEG_STATUS_HIP_ERROR;
     // The verdicts resolve() reads are stored by the stage's last kernel, into the pinned side itself: no copy command between the
     // entropy kernels and the pixel kernels.  Pinned memory from a caller's allocator may not be mapped into the device's address
@@ -1480,7 +1489,7 @@ hipjpegStatus_t DecodeBatch::resolve(void* stream)
         from_desc = true;
         for (int pass = 0; pass < kExtraRippleLaunches && !converged; pass++) {
             if (hipMemsetAsync(L.changed, 0, sizeof(unsigned int), s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
-            if (launch_huff_sync(L.dimg, L.dunits, L.nunits, L.states, L.incoming, L.changed, 0, 1 << 20, nullptr, nullptr, L.records, L.pool_bytes, stream, ++last_pass) != 0)
+            if (launch_huff_sync(L.dimg, L.dunits, L.nunits, nullptr, 0, L.states, L.incoming, L.changed, 0, 1 << 20, nullptr, nullptr, L.records, L.pool_bytes, stream, ++last_pass) != 0)
                 return HIPJPEG_STATUS_HIP_ERROR;
             if (hipMemcpyAsync(L.host_changed, L.changed, sizeof(unsigned int), hipMemcpyDeviceToHost, s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;
             if (hipStreamSynchronize(s) != hipSuccess) return HIPJPEG_STATUS_HIP_ERROR;

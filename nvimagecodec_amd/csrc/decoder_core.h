@@ -210,7 +210,7 @@ private:
     // tables | staged bitstreams [streams, coef) | coefficients of host-decoded images  ||  (device only from h2d_bytes) coefficients of
     // GPU-decoded images.  The pinned side keeps 256 spare bytes and verdict_bytes() behind h2d_bytes (entropy_launch_args).
     struct StagingLayout {
-        size_t desc, units, huff_desc, huff_units, huff_wunits, huff_dc_units, huff_chunk_units, huff_drops, xform_desc, xform_units,
+        size_t desc, units, huff_desc, huff_units, huff_pairs, huff_wunits, huff_dc_units, huff_chunk_units, huff_drops, xform_desc, xform_units,
             prog_desc, prog_units, prog_iv_desc, prog_iv_units, tensor_planes, tensor_units, tables, boundaries, streams, coef, h2d_bytes, gpu_coef_begin, total;
     } staging_{};
     // Device-only scratch of the entropy kernels (work_): subsequence states (at 0) | first block indices | change counters | ...
@@ -251,6 +251,7 @@ private:
     // GPU entropy stage: one HuffImage per scan of the sequential images first, then one per scan of the progressive images
     std::vector<HuffImage> huff_images_;
     std::vector<HuffUnit> huff_units_, huff_dc_units_;
+    std::vector<uint32_t> huff_pairs_;  // the first sync launch's workgroups: huff_pair_entry()
     std::vector<int> huff_to_image_;  // sequential HuffImage -> image
     int seq_gpu_images_ = 0;          // sequential images among them
     // blocks of GPU-decoded sequential pictures that no scan codes (padding of a one-component scan's grid): zeroed before the
@@ -262,7 +263,7 @@ private:
     std::vector<ZeroFill> huff_zero_;
     std::vector<HuffUnit> huff_wunits_;       // block kernel: kHuffMcusPerWg MCUs per workgroup
     std::vector<HuffUnit> huff_chunk_units_;  // destuff kernels: one per kDestuffChunk bytes of a scan
-    size_t total_subseq_ = 0, max_huff_units_ = 0, max_pool_words_ = 0;
+    size_t total_subseq_ = 0, max_huff_units_ = 0, max_huff_pairs_ = 0, max_pool_words_ = 0;
     std::atomic<bool> host_drops_missing_{false};  // set by a host task that found a scan without counts: the device counts instead
     // progressive images of the batch
     std::vector<ProgImage> prog_images_;

@@ -34,11 +34,15 @@ int launch_destuff(HuffImage* images, const HuffUnit* chunk_units, int nchunks, 
 // group that exceeded its round budget (periodic streams); such images are skipped by later ripple launches.
 // records: block-start records of the synchronisation decodes (huffman_gpu_core.h), kRecShorts uint16 per subsequence, batch-wide
 // like the end states (index HuffImage::first_subseq + subsequence).  Every correction decode of an owned subsequence records
-// where its blocks start and writes its mark (not in streams with restart intervals); pass 0 records nothing, and round 1 decodes
-// every owned subsequence again.
-int launch_huff_sync(HuffImage* images, const HuffUnit* units, int nunits, unsigned long long* states, unsigned long long* incoming,
-                     unsigned int* changed, int first_pass, int max_rounds, uint16_t* tail_tasks, uint32_t* tail_count, uint16_t* records,
-                     unsigned pool_bytes, void* stream, unsigned pass_id = 0);
+// where its blocks start and writes its mark (not in streams with restart intervals), and so do the first launch's decodes from a
+// neighbour's end state (phase B of the paired schedule); decodes from the assumed state record nothing.
+// pairs (first_pass only): the first launch's workgroups take two consecutive units of an image each -- pairs[i] = index of the first
+// unit, bit 31 set where the next unit belongs to the same image and is taken along (huff_pair_entry); what the launch leaves is per
+// unit all the same.
+constexpr uint32_t huff_pair_entry(uint32_t first_unit, bool with_next) { return first_unit | (with_next ? 0x80000000u : 0u); }
+int launch_huff_sync(HuffImage* images, const HuffUnit* units, int nunits, const uint32_t* pairs, int npairs, unsigned long long* states,
+                     unsigned long long* incoming, unsigned int* changed, int first_pass, int max_rounds, uint16_t* tail_tasks, uint32_t* tail_count,
+                     uint16_t* records, unsigned pool_bytes, void* stream, unsigned pass_id = 0);
 // Write pass: the block positions over the sync units, then the block kernel over block_units ({image, first MCU}, kHuffMcusPerWg
 // MCUs each).  One kernel numbers the blocks (the block in progress where every subsequence begins: first_block, written for the
 // subsequences that are walked; HuffImage::decoded_blocks and the "stream ends before the last block" status) and puts every usable

@@ -4,7 +4,7 @@
 // (extensions/nvjpeg/cuda_decoder.cpp:512-521): the Huffman stage moves to the device, so neither the host cores nor the
 // PCIe copy of 6 MB of coefficients per image sit on the critical path any more -- only the ~0.5 MB bitstream crosses.
 //
-// Mapping: one lane decodes one 1024-bit subsequence; a workgroup owns 256 consecutive subsequences of ONE image.
+// Mapping: one lane decodes one 1024-bit subsequence; a workgroup owns 255 (the first launch: 510) consecutive subsequences of ONE image.
 // Decoding is inherently serial per lane (data-dependent code lengths); parallelism comes from the number of subsequences
 // (4096 per 0.5 MB image, ~1M per 256-image batch).  Everything a lane touches per symbol lives in LDS:
 //   * the workgroup's 32 KB of bitstream, loaded once with coalesced dword loads, byte-swapped to MSB-first words and stored
@@ -13,8 +13,10 @@
 //   * the image's two-level Huffman lookup tables (uint16 entries, typically ~10 KB);
 //   * per-MCU-position table offsets and block addressing constants, the zigzag permutation.
 // Kernels:
-//   huff_sync_kernel   pass 0 + workgroup-local synchronisation loop in LDS; publishes end states; counts the workgroups
-//                      whose LAST end state moved (the only state another workgroup consumes)
+//   huff_sync_pair_kernel  the first launch: two sync units per workgroup, the paired schedule and the workgroup-local
+//                      synchronisation rounds in LDS; publishes end states, hands what is left to huff_tail_kernel
+//   huff_sync_kernel   the ripple over single units as a launch of its own (an A/B aid; huff_tail_kernel<true> otherwise): counts the
+//                      workgroups whose LAST end state moved (the only state another workgroup consumes)
 //   huff_copy_records_kernel  where every block starts: first block index of every subsequence (sums and scans the completed-block
 //                      counts), then copies the records the last synchronisation decodes took
 //   huff_pos_kernel    walks from the converged states the subsequences without a usable record
@@ -22,6 +24,8 @@
 //                      two 256-lane teams per workgroup share one copy of the tables: 16 waves per CU
 //   huff_dc_kernel     per (image, component): DC differences -> DC values, stored into the blocks
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "gpu_huffman.h"
 #include "huffman_gpu_core.h"
@@ -58,6 +62,21 @@ struct WgShared {
     uint32_t queue[kSyncThreads];
     uint32_t wave_count[kSyncThreads / 64];
 };
+
+// The first sync launch's workgroup (huff_sync_pair_kernel): two sync units of an image, 2 * kHuffOwn subsequences and the halo.  The
+// staged rows hold one parity of them at a time (column t: the row lane t is about to decode), the end states all of them.
+constexpr int kPairRows = 2 * kHuffOwn + 1;
+struct PairShared {
+    uint32_t stream[staged_lds_words(kSyncThreads)];
+    unsigned long long end[2 * kSyncThreads];  // end state of local row r ([0] = halo = state entering the workgroup)
+    unsigned long long second_from;            // the state the second unit's first subsequence was last decoded from
+    uint32_t tsel[10];
+    uint32_t wave_count[kSyncThreads / 64];
+    uint16_t queue[kSyncThreads];  // a round's tasks are rows of one parity: at most one per lane, below 2 * kSyncThreads
+};
+// Three workgroups per CU beside the standard tables (13,824 B), LDS handed out in 1,280-byte granules
+// (profiles/block_pass_teams/lds_granule.txt): 160 KB / 3 = 54,613 -> 42 granules = 53,760 B each.
+static_assert(kSyncThreads != 256 || sizeof(PairShared) + 13824 <= 53760, "huff_sync_pair_kernel: three workgroups per CU");
 
 // restart boundaries live in global memory (a handful of reads per decode; the destuffed positions come from the host's
 // marker walk)
@@ -130,6 +149,12 @@ struct DevEnv : LdsTables {
         row_addr = stream_base + ((uint32_t)row << 2);
         row_word0 = word0 + ((uint32_t)row << kRowShift);
     }
+    // row `row` staged in column `column` (huff_sync_pair_kernel: a lane's own column holds whatever row it decodes next)
+    __device__ __forceinline__ void set_column_row(int column, int row)
+    {
+        row_addr = stream_base + ((uint32_t)column << 2);
+        row_word0 = word0 + ((uint32_t)row << kRowShift);
+    }
     __device__ __forceinline__ uint32_t cursor(uint32_t i) const { return row_addr + (i - row_word0) * kCursorStep; }
     __device__ __forceinline__ uint32_t fetch(uint32_t c) const { return *(const HJ_LDS uint32_t*)(uintptr_t)c; }
 };
@@ -192,16 +217,16 @@ __device__ __forceinline__ SubseqState sync_walk(bool rst, bool record, const Hu
     return walk(StepEnv<true>(env));
 }
 
-// Cooperative staging of stream words: lane t brings in row t = subsequence first_row + t of the image (first_row may be -1:
-// that row is filled with ones) and the kStagedExtra words behind it, transposed (see WgShared).  16-byte global loads, all of
-// a lane's loads in flight together; words behind the end of the stream read as ones.
+// Staging of stream words: lane t brings subsequence `row` of the image (-1: filled with ones) and the kStagedExtra words behind
+// it into column t of the transposed rows (see WgShared).  16-byte global loads, all of a lane's loads in flight together; words
+// behind the end of the stream read as ones.  stage_rows: the cooperative form, lane t takes row first_row + t.
 template <int ROWS>
-__device__ __forceinline__ void stage_rows(uint32_t* lds_stream, const HuffImage& im, int first_row)
+__device__ __forceinline__ void stage_row(uint32_t* lds_stream, const HuffImage& im, int row)
 {
     const int t = threadIdx.x;
     const HJ_GLOBAL uint32_t* g = (const HJ_GLOBAL uint32_t*)im.stream;
     const int nwords = (int)im.stream_words;
-    const int w0 = (first_row + t) * kSubseqWords;
+    const int w0 = row * kSubseqWords;
     constexpr int kGroups = kSubseqWords / 4;  // 16-byte groups per row; the look-ahead words are one 8-byte group more
     u32x4 v[kGroups];
     typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -231,6 +256,11 @@ __device__ __forceinline__ void stage_rows(uint32_t* lds_stream, const HuffImage
     }
     dst[(kSubseqWords + 0) * ROWS] = __builtin_bswap32(tail.x);
     dst[(kSubseqWords + 1) * ROWS] = __builtin_bswap32(tail.y);
+}
+template <int ROWS>
+__device__ __forceinline__ void stage_rows(uint32_t* lds_stream, const HuffImage& im, int first_row)
+{
+    stage_row<ROWS>(lds_stream, im, first_row + (int)threadIdx.x);
 }
 
 // lookup tables -> LDS
@@ -272,7 +302,8 @@ __device__ __forceinline__ void stage_constants(uint32_t* tsel, KSlot* kslot, ui
     }
 }
 
-__device__ __forceinline__ DevEnv make_env(WgShared& sh, HJ_LDS uint16_t* pool, uint32_t first, const HuffGeom& geom, const HuffImage& im)
+template <class Shared>
+__device__ __forceinline__ DevEnv make_env(Shared& sh, HJ_LDS uint16_t* pool, uint32_t first, const HuffGeom& geom, const HuffImage& im)
 {
     DevEnv env;
     env.stream_base = (uint32_t)(uintptr_t)(HJ_LDS uint32_t*)sh.stream;
@@ -292,7 +323,8 @@ __device__ __forceinline__ DevEnv make_env(WgShared& sh, HJ_LDS uint16_t* pool, 
 
 // Packs the lanes with has == true to the front: returns how many there are; *task = value of the t-th of them for the
 // lanes t below that count, -1 for the others.  Contains barriers: call from uniform control flow.
-__device__ __forceinline__ int compact_tasks(WgShared& sh, bool has, int value, int* task)
+template <class Shared>
+__device__ __forceinline__ int compact_tasks(Shared& sh, bool has, int value, int* task)
 {
     const int t = threadIdx.x;
     const unsigned long long mask = __ballot(has);
@@ -306,7 +338,7 @@ __device__ __forceinline__ int compact_tasks(WgShared& sh, bool has, int value, 
         if (w < (t >> 6)) base += c;
         n += c;
     }
-    if (has) sh.queue[base + below] = (uint32_t)value;
+    if (has) sh.queue[base + below] = (std::remove_reference_t<decltype(sh.queue[0])>)value;
     __syncthreads();
     *task = t < n ? (int)sh.queue[t] : -1;
     return n;
@@ -613,21 +645,18 @@ __global__ __launch_bounds__(kThreads) void destuff_compact_kernel(HuffImage* __
 }
 
 // states[]: one 8-byte record per subsequence (batch-wide indexing through HuffImage::first_subseq).
-// incoming[]: per workgroup, the state it assumed to enter with the last time it ran.
+// incoming[]: per sync unit, the state it was entered with the last time it ran.
 // counters[0] += 1 for every workgroup whose outgoing state (end state of its last subsequence) differs from the published
-// one (counters[1] in the first pass, where every state is new); counters[2..5] = statistics.
+// one; counters[2..5] = statistics (2, 3: the first launch, huff_sync_pair_kernel below; 4, 5: the later ones).
 //
-// first_pass: every lane decodes its subsequence from the assumed state "a block of MCU position 0 starts at the boundary";
-// lane 0 does so for the LAST subsequence of the predecessor workgroup (the halo), whose end state is the workgroup's guess
-// of the state it is entered with.  Then corrections ripple: a subsequence whose predecessor's end state differs from the
-// one it was decoded from is decoded again.  Every round packs the subsequences to redo into the lowest lanes, so that the
-// long tail of rounds with a handful of corrections occupies one wave instead of four.
-// later passes: a workgroup whose incoming state still equals its guess has nothing to do and leaves before staging
-// anything; otherwise the ripple starts from its first subsequence.
+// The ripple over single units as a sync-kernel launch (HIPJPEG_RIPPLE_IN_SYNC=1, an A/B aid: the launches behind the first are
+// huff_tail_kernel<true>'s otherwise).  A workgroup whose incoming state still equals the one it was entered with has nothing to do
+// and leaves before staging anything; otherwise the ripple starts from its first subsequence: a subsequence whose predecessor's end
+// state differs from the one it was decoded from is decoded again, to the workgroup's fixpoint.  Every round packs the subsequences to
+// redo into the lowest lanes.
 __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
                                                              unsigned long long* __restrict__ states, unsigned long long* __restrict__ incoming,
-                                                             unsigned int* __restrict__ counters, int first_pass, int max_rounds,
-                                                             uint16_t* __restrict__ tail_tasks, uint32_t* __restrict__ tail_count, uint16_t* records)
+                                                             unsigned int* __restrict__ counters, uint16_t* records)
 {
     __shared__ WgShared sh;
     extern __shared__ uint16_t dyn_pool[];
@@ -642,11 +671,8 @@ __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage
     const uint32_t j = u.first - 1 + t;  // subsequence of lane t (lane 0: the halo; none for the first workgroup of an image)
     const bool owner = t >= 1 && j < nsub;
     const int n_rows = (int)min((uint32_t)kSyncThreads, nsub - u.first + 1);  // rows 1 .. n_rows-1 are owned
-    unsigned long long in_state = 0;
-    if (!first_pass) {
-        in_state = u.first ? __hip_atomic_load(&gstate[u.first - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kSyncMask : 0ull;
-        if (in_state == incoming[blockIdx.x]) return;  // uniform
-    }
+    const unsigned long long in_state = u.first ? __hip_atomic_load(&gstate[u.first - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kSyncMask : 0ull;
+    if (in_state == incoming[blockIdx.x]) return;  // uniform
     stage_rows<kSyncThreads>(sh.stream, im, (int)u.first - 1);
     stage_pool<kSyncThreads>(pool, im);
     stage_constants(sh.tsel, nullptr, nullptr, im, false);
@@ -654,29 +680,11 @@ __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage
 
     DevEnv env = make_env(sh, pool, u.first, geom, im);
     const bool rst = im.restart_interval != 0;
-    unsigned long long old_global = ~0ull;
-    int task = -1;
     // block-start records: every correction decode takes them (not across restart boundaries)
     const bool recording = !rst;
-    if (first_pass) {
-        const unsigned long long assumed = (unsigned long long)j * kSubseqBits;
-        unsigned long long mine = 0;  // first workgroup of an image, lane 0: the exact initial state (bit 0, z 0, k 0)
-        if (owner || (t == 0 && u.first > 0)) {
-            const uint32_t bidx0 = boundary0_of(im, j);
-            env.set_row(t);
-            mine = pack_state(sync_walk(rst, false,geom, env, j * kSubseqBits, (j + 1) * kSubseqBits, 0, 0, bidx0, SlotRecorder()));
-        }
-        sh.end[t] = mine;
-        __syncthreads();
-        // A wrong guess is decoded again.  With records, so is every other subsequence: pass 0 records nothing (its guesses are
-        // throughput-bound work, and almost all of them are wrong), and round 1 keeps almost every lane busy anyway -- the ones
-        // that guessed right (about one in 300, and subsequence 0) are decoded again from the same state, record, and stop there.
-        if (owner && ((sh.end[t - 1] & kSyncMask) != assumed || recording)) task = t;
-    } else {
-        if (owner) old_global = gstate[j];
-        sh.end[t] = t == 0 ? in_state : old_global;
-        if (t == 1) task = 1;
-    }
+    const unsigned long long old_global = owner ? gstate[j] : ~0ull;
+    sh.end[t] = t == 0 ? in_state : old_global;
+    int task = t == 1 ? 1 : -1;
     int rounds = 0;
     for (int round = 0; round < kSyncThreads + 2; round++) {
         __syncthreads();
@@ -688,37 +696,146 @@ __global__ __launch_bounds__(kSyncThreads) void huff_sync_kernel(const HuffImage
             env.set_row(task);  // the predecessor's walk ended on a symbol that starts in this row
             const uint32_t jt = u.first - 1 + task;
             const SlotRecorder rec = slot_recorder(records, im, jt);
-            const SubseqState st = sync_walk(rst, recording,geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
+            const SubseqState st = sync_walk(rst, recording, geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
             if (recording) put_mark(rec, p.end_bit, (jt + 1) * kSubseqBits, geom.total_bits, p.zk & 255, st);
             now = pack_state(st);
             moved = ((now ^ sh.end[task]) & kSyncMask) != 0;
         }
         __syncthreads();  // every start state has been read before any end state is replaced
         if (task >= 0) sh.end[task] = now;
-        const int pending = compact_tasks(sh, moved && task + 1 < n_rows, task + 1, &task);
-        if (pending == 0 || rounds >= max_rounds) {
-            // what is left goes to the tail kernel: few subsequences per round, one lane busy per chain -- not worth holding
-            // 47 KB of LDS for
-            if (tail_count) {
-                if (t < pending) tail_tasks[(size_t)blockIdx.x * kSyncThreads + t] = (uint16_t)task;
-                if (t == 0) tail_count[blockIdx.x] = (uint32_t)pending;
-            }
-            break;
-        }
+        if (compact_tasks(sh, moved && task + 1 < n_rows, task + 1, &task) == 0) break;
     }
     __syncthreads();
     if (owner) {
         const unsigned long long mine = sh.end[t];
         if (mine != old_global) {
             __hip_atomic_store(&gstate[j], mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (t == n_rows - 1 && ((mine ^ old_global) & kSyncMask) != 0) atomicAdd(counters + (first_pass ? 1 : 0), 1u);
+            if (t == n_rows - 1 && ((mine ^ old_global) & kSyncMask) != 0) atomicAdd(counters + 0, 1u);
         }
     }
     if (t == 0) {
-        incoming[blockIdx.x] = first_pass ? (sh.end[0] & kSyncMask) : in_state;
-        // statistics: correction rounds (sum, maximum) of the first launch / of the later launches
-        atomicAdd(counters + (first_pass ? 2 : 4), (unsigned)rounds);
-        atomicMax(counters + (first_pass ? 3 : 5), (unsigned)rounds);
+        incoming[blockIdx.x] = in_state;
+        // statistics: correction rounds (sum, maximum) of the later launches
+        atomicAdd(counters + 4, (unsigned)rounds);
+        atomicMax(counters + 5, (unsigned)rounds);
+    }
+}
+
+// The first launch in pairs: a workgroup takes TWO consecutive sync units of one image (pairs[]: index of the first, bit 31 = there
+// is a second), kPairRows local rows, and decodes them in a schedule that wastes less than "everything from a guess, then everything
+// again" (1 + 1 + 0.36 walks per bit): only the EVEN rows start from the assumed state, the odd rows wait for them.
+//   phase A  even rows (the halo is row 0) from the assumed state, no records             0.5 of the bits
+//   phase B  odd rows from A's end state of the row in front (1,024 bits of history: right two times in three), records   0.5
+//   round 1  even rows but the halo, from B's end states, records                         0.5
+//   round 2  odd rows whose start state moved in round 1                                  ~0.18
+//   ...      successors of the rows that moved, the parity alternating; tasks packed into the lowest lanes
+// The staged rows hold what the lanes are about to decode: lane t stages the row of its task into column t itself, so nothing but a
+// lane's own program order stands between staging and walking, and a round with few tasks stages few rows.  A and B are one lane's
+// two rows one after the other: no barrier between them either.
+// In the first workgroup of an image row 0 does not exist: row 1 (subsequence 0) is decoded in B from the exact initial state.
+// What the kernel leaves is per UNIT, as huff_sync_kernel leaves it: states[], the task lists and counts (local rows of the unit),
+// incoming[].  The second unit's incoming[] is the state its first subsequence (row kSyncThreads here) was last decoded from: where the
+// row in front moved after that, the tail kernel sees a state in front that is not incoming[] and decodes the subsequence again --
+// that row is therefore never put on the list.  So when the kernel ends every subsequence was last decoded from the state now in
+// front of it, or is on its unit's list, or its unit's incoming[] differs from the state in front.
+// max_rounds counts the correction rounds (B is none); tail_count == nullptr: the rounds run to the workgroup's fixpoint.
+__global__ __launch_bounds__(kSyncThreads) void huff_sync_pair_kernel(const HuffImage* __restrict__ images, const HuffUnit* __restrict__ units,
+                                                                  const uint32_t* __restrict__ pairs, unsigned long long* __restrict__ states,
+                                                                  unsigned long long* __restrict__ incoming, unsigned int* __restrict__ counters,
+                                                                  int max_rounds, uint16_t* __restrict__ tail_tasks, uint32_t* __restrict__ tail_count,
+                                                                  uint16_t* records)
+{
+    __shared__ PairShared sh;
+    extern __shared__ uint16_t dyn_pool[];
+    HJ_LDS uint16_t* pool = (HJ_LDS uint16_t*)dyn_pool;
+    const uint32_t pair = pairs[blockIdx.x];
+    const uint32_t ui = pair & 0x7FFFFFFFu;
+    const HuffUnit u = units[ui];
+    const HuffImage& im = images[u.image];
+    const HuffGeom geom = make_geom(im);
+    const uint32_t nsub = (geom.total_bits + kSubseqBits - 1) / kSubseqBits;
+    if (u.first >= nsub) return;  // uniform: the stream turned out shorter than planned
+    unsigned long long* gstate = states + im.first_subseq;
+    const int t = threadIdx.x;
+    const int n_rows = (int)min((uint32_t)((pair >> 31) ? kPairRows : kSyncThreads), nsub - u.first + 1);  // rows 1 .. n_rows-1 are owned
+    const bool second = n_rows > kSyncThreads;  // the second unit owns rows (its first subsequence lies inside the stream)
+    const auto subseq_of = [&](int row) { return u.first - 1 + (uint32_t)row; };
+    const bool in_a = 2 * t < n_rows && (t > 0 || u.first > 0);
+    if (in_a) stage_row<kSyncThreads>(sh.stream, im, (int)subseq_of(2 * t));
+    stage_pool<kSyncThreads>(pool, im);
+    stage_constants(sh.tsel, nullptr, nullptr, im, false);
+    __syncthreads();
+
+    DevEnv env = make_env(sh, pool, u.first, geom, im);
+    const bool rst = im.restart_interval != 0;
+    const bool recording = !rst;  // block-start records: every decode but A's takes them (not across restart boundaries)
+    const auto decode = [&](int row, unsigned long long from, bool record) {
+        const SubseqState p = unpack_state(from);
+        const uint32_t jt = subseq_of(row);
+        env.set_column_row(t, row);
+        const SlotRecorder rec = slot_recorder(records, im, jt);
+        const SubseqState st = sync_walk(rst, record, geom, env, p.end_bit, (jt + 1) * kSubseqBits, p.zk & 255, p.zk >> 8, boundary0_of(im, jt), rec);
+        if (record) put_mark(rec, p.end_bit, (jt + 1) * kSubseqBits, geom.total_bits, p.zk & 255, st);
+        return pack_state(st);
+    };
+    // A, then B: rows 2t and 2t + 1
+    unsigned long long mine = 0;  // first workgroup of an image, row 0: the exact initial state (bit 0, z 0, k 0)
+#pragma unroll 1
+    for (int ph = 0; ph < 2; ph++) {
+        const int row = 2 * t + ph;
+        const bool active = ph ? row < n_rows : in_a;
+        if (active) {
+            if (ph) stage_row<kSyncThreads>(sh.stream, im, (int)subseq_of(row));
+            const unsigned long long from = ph ? mine : (unsigned long long)subseq_of(row) * kSubseqBits;
+            if (row == kSyncThreads) sh.second_from = from & kSyncMask;
+            mine = decode(row, from, ph && recording);
+        }
+        if (active || row == 0) sh.end[row] = mine;
+    }
+    __syncthreads();
+    // Round 1: a wrong guess is decoded again.  With records, so is every other even row: A records nothing, and the rows that
+    // guessed right (about one in 300) are decoded again from the same state, record, and stop there.
+    int task = -1;
+    if (t >= 1 && 2 * t < n_rows && (recording || (sh.end[2 * t - 1] & kSyncMask) != (unsigned long long)subseq_of(2 * t) * kSubseqBits)) task = 2 * t;
+    int rounds = 0, pending = 0;
+    for (int round = 0; round < kPairRows + 2; round++) {
+        rounds++;
+        bool moved = false;
+        if (task >= 0) {
+            stage_row<kSyncThreads>(sh.stream, im, (int)subseq_of(task));
+            const unsigned long long from = sh.end[task - 1];
+            if (task == kSyncThreads) sh.second_from = from & kSyncMask;
+            const unsigned long long now = decode(task, from, recording);
+            moved = ((now ^ sh.end[task]) & kSyncMask) != 0;
+            // (a round's rows are of one parity: nobody reads this entry as a start state before the barriers of compact_tasks)
+            sh.end[task] = now;
+        }
+        pending = compact_tasks(sh, moved && task + 1 < n_rows, task + 1, &task);
+        if (pending == 0 || rounds >= max_rounds) break;
+    }
+    // what is left goes to the tail kernel, unit by unit.  The rows ascend with the lanes (compact_tasks keeps the order, a round's
+    // tasks are the successors of the round before): the first unit's tasks are the lowest lanes'.
+    if (tail_count) {
+        const int n_first = __syncthreads_count(task >= 0 && task < kSyncThreads);
+        const int skip = n_first < pending && sh.queue[n_first] == kSyncThreads ? 1 : 0;  // the second unit's first row: incoming[] says it
+        if (task >= 0 && task < kSyncThreads) tail_tasks[(size_t)ui * kSyncThreads + t] = (uint16_t)task;
+        if (task > kSyncThreads) tail_tasks[(size_t)(ui + 1) * kSyncThreads + (t - n_first - skip)] = (uint16_t)(task - kHuffOwn);
+        if (t == 0) {
+            tail_count[ui] = (uint32_t)n_first;
+            if (second) tail_count[ui + 1] = (uint32_t)(pending - n_first - skip);
+        }
+    }
+#pragma unroll
+    for (int row = t; row < 2 * kSyncThreads; row += kSyncThreads)
+        if (row >= 1 && row < n_rows) __hip_atomic_store(&gstate[subseq_of(row)], sh.end[row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == 0) {
+        const unsigned n_units = second ? 2u : 1u;
+        incoming[ui] = sh.end[0] & kSyncMask;
+        if (second) incoming[ui + 1] = sh.second_from;
+        // per unit, as huff_sync_kernel counts: workgroups whose last end state is new; correction rounds (sum, maximum)
+        atomicAdd(counters + 1, n_units);
+        atomicAdd(counters + 2, (unsigned)rounds * n_units);
+        atomicMax(counters + 3, (unsigned)rounds);
     }
 }
 
@@ -784,8 +901,9 @@ __device__ __forceinline__ void wave_sync()
 // anything.  counters[0] counts the groups whose own last end state moved -- zero: the batch has converged.
 //
 // The first launch enters the same way.  When it starts the sync kernel is done, and the state in front of every group has two
-// correction rounds behind it; pass 0's guess (the halo lane's decode from an assumed state), which the group's first subsequence
-// was decoded from, is wrong for one group in three.  So the group takes the state in front as it is when its wave gets there, and
+// correction rounds behind it; the state the group's first subsequence was decoded from (incoming[]: for a pair's first unit the
+// halo lane's decode from an assumed state, wrong for one group in three; for its second unit a state of the first unit's last row)
+// may no longer be that state.  So the group takes the state in front as it is when its wave gets there, and
 // if that is not the guess, its first subsequence joins the first round as one more chain beside the ones handed over.  When its
 // lists are empty the wave looks in front once more (kTailReentries times at most) and follows what it finds as a single chain; it
 // never waits -- not every batch has all its groups resident -- and a group that is done before the one in front of it moved is
@@ -879,9 +997,10 @@ __device__ __forceinline__ void tail_group(TailWave& ws, TailEnv env, HuffImage&
         }
     } else {
         for (uint32_t i = lane; i < pending; i += 64) ws.list[0][i] = tail_tasks[(size_t)ui * kSyncThreads + i];
-        // The sync kernel's rounds moved the state in front since pass 0 guessed it: row 1 is decoded again, an ordinary member of
-        // the first Jacobi round.  Task 1 is never among the tasks handed over -- row 0 does not move in the first launch, so the
-        // sync kernel decodes row 1 once, in its round 1, and hands over successors of rows that moved: 2 and up.
+        // The sync kernel's rounds moved the state in front since the group's row 1 was last decoded from it (a pair's first unit:
+        // from the halo's guess; its second unit: from the first unit's last row as it then was): row 1 is decoded again, an
+        // ordinary member of the first Jacobi round.  Task 1 is never among the tasks handed over -- the sync kernel lists rows 2
+        // and up and leaves row 1 to this test.
         if (entering != incoming[ui]) {  // uniform
             if (lane == 0) {
                 incoming[ui] = entering;
@@ -1807,11 +1926,11 @@ static bool ripple_in_tail_kernel()
     return v;
 }
 
-int launch_huff_sync(HuffImage* images, const HuffUnit* units, int nunits, unsigned long long* states, unsigned long long* incoming,
-                     unsigned int* changed, int first_pass, int max_rounds, uint16_t* tail_tasks, uint32_t* tail_count, uint16_t* records,
-                     unsigned pool_bytes, void* stream, unsigned pass_id)
+int launch_huff_sync(HuffImage* images, const HuffUnit* units, int nunits, const uint32_t* pairs, int npairs, unsigned long long* states,
+                     unsigned long long* incoming, unsigned int* changed, int first_pass, int max_rounds, uint16_t* tail_tasks, uint32_t* tail_count,
+                     uint16_t* records, unsigned pool_bytes, void* stream, unsigned pass_id)
 {
-    if (nunits <= 0) return 0;
+    if (nunits <= 0 || (first_pass && npairs <= 0)) return 0;
     const dim3 tail_grid((nunits + kTailWaves - 1) / kTailWaves);
     if (!first_pass && ripple_in_tail_kernel()) {
         // corrections across group borders: the tail kernel's workgroups (little LDS, a row staged per decode) instead of the
@@ -1820,8 +1939,12 @@ int launch_huff_sync(HuffImage* images, const HuffUnit* units, int nunits, unsig
                            changed, nullptr, nullptr, pass_id, records);
         return (int)hipGetLastError();
     }
-    hipLaunchKernelGGL(huff_sync_kernel, dim3(nunits), dim3(kSyncThreads), pool_bytes, (hipStream_t)stream, images, units, states, incoming, changed,
-                       first_pass, max_rounds, tail_tasks, tail_count, records);
+    if (first_pass)  // two units per workgroup, the paired schedule
+        hipLaunchKernelGGL(huff_sync_pair_kernel, dim3(npairs), dim3(kSyncThreads), pool_bytes, (hipStream_t)stream, images, units, pairs, states, incoming,
+                           changed, max_rounds, tail_tasks, tail_count, records);
+    else  // HIPJPEG_RIPPLE_IN_SYNC=1: the ripple over single units
+        hipLaunchKernelGGL(huff_sync_kernel, dim3(nunits), dim3(kSyncThreads), pool_bytes, (hipStream_t)stream, images, units, states, incoming, changed,
+                           records);
     if (tail_count)
         hipLaunchKernelGGL(huff_tail_kernel<false>, tail_grid, dim3(kTailThreads), pool_bytes, (hipStream_t)stream, images, units, nunits, states, incoming,
                            changed, tail_tasks, tail_count, 0u, records);

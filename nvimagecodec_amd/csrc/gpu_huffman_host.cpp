@@ -347,8 +347,72 @@ struct HostRecorder {
 }  // namespace
 
 namespace {
+// The first sync launch as its workgroups schedule it (gpu_huffman.hip), on one image: `units` sync units per workgroup -- 1:
+// huff_sync_kernel's pass 0 and Jacobi rounds over kHuffOwn subsequences and the halo; 2: huff_sync_pair_kernel's phases A and B and
+// rounds of alternating parity over twice as many -- each workgroup's rounds run to ITS fixpoint, then what the tail and ripple
+// launches do to the workgroup seams: every subsequence whose start state is not the state in front of it is decoded again, in
+// stream order, which ends in the image's fixpoint in one sweep.  walk(i, begin, z, k, record) decodes subsequence i and keeps the
+// record where `record` is set, as the kernels' decodes do: all but those from the assumed state, and none with restart intervals
+// (recording == false).  state[i] receives the end states.  counts: decodes per phase up to correction round 2, and the tasks that
+// are left then (HIPJPEG_TAIL_AFTER's default: the tail kernel's share).  False if a workgroup's rounds do not end.
+template <class Walk>
+bool emulate_sync_launch(uint32_t ns, int units, bool recording, Walk& walk, SubseqState* state, SyncScheduleCounts* counts)
+{
+    const bool paired = units == 2;
+    const uint32_t own = (uint32_t)units * kHuffOwn;
+    std::vector<uint64_t> from(ns, 0);  // the (masked) state each subsequence was last decoded from
+    std::vector<uint64_t> end, start;
+    std::vector<int> tasks, next;
+    const auto assumed = [](uint32_t j) { return (uint64_t)j * kSubseqBits; };
+    for (uint32_t first = 0; first == 0 || first < ns; first += own) {
+        if (first >= ns) break;  // (an empty stream)
+        const int n_rows = (int)std::min<uint32_t>(own + 1, ns - first + 1);  // local row r = subsequence first - 1 + r; row 0: the halo
+        end.assign((size_t)n_rows, 0);
+        const auto decode = [&](int row, uint64_t at, bool record) {
+            const SubseqState p = unpack_state(at);
+            const uint32_t j = first - 1 + (uint32_t)row;
+            if (row > 0) from[j] = at & kSyncMask;
+            end[(size_t)row] = pack_state(walk(j, p.end_bit, p.zk & 255, p.zk >> 8, record));
+        };
+        // from the assumed state: every row (the even rows), no records; row 0 of the image's first workgroup is the exact initial state
+        for (int r = first ? 0 : (paired ? 2 : 1); r < n_rows; r += paired ? 2 : 1, counts->phase[0]++) decode(r, assumed(first - 1 + (uint32_t)r), false);
+        // phase B: the odd rows from their neighbour's end state
+        for (int r = 1; paired && r < n_rows; r += 2, counts->phase[1]++) decode(r, end[(size_t)r - 1], recording);
+        // round 1: with records every row decoded from the assumed state, else the wrong guesses
+        tasks.clear();
+        for (int r = paired ? 2 : 1; r < n_rows; r += paired ? 2 : 1)
+            if (recording || (end[(size_t)r - 1] & kSyncMask) != assumed(first - 1 + (uint32_t)r)) tasks.push_back(r);
+        for (int round = 1; !tasks.empty(); round++) {
+            if (round > n_rows + 2) return false;
+            if (round <= 2) counts->phase[round + 1] += tasks.size();
+            if (round == 3) counts->tail += tasks.size();
+            start.clear();
+            for (int r : tasks) start.push_back(end[(size_t)r - 1]);  // Jacobi: every start state is read before any end state is replaced
+            next.clear();
+            for (size_t q = 0; q < tasks.size(); q++) {
+                const int r = tasks[q];
+                const uint64_t old = end[(size_t)r];
+                decode(r, start[q], recording);
+                if (((end[(size_t)r] ^ old) & kSyncMask) != 0 && r + 1 < n_rows) next.push_back(r + 1);
+            }
+            tasks.swap(next);
+        }
+        for (int r = 1; r < n_rows; r++) state[first - 1 + (uint32_t)r] = unpack_state(end[(size_t)r]);
+    }
+    // the seams: in stream order every start state is final when its subsequence is looked at
+    for (uint32_t j = 1; j < ns; j++) {
+        const uint64_t at = pack_state(state[j - 1]);
+        if ((at & kSyncMask) == from[j]) continue;
+        const SubseqState p = unpack_state(at);
+        from[j] = at & kSyncMask;
+        state[j] = walk(j, p.end_bit, p.zk & 255, p.zk >> 8, recording);
+    }
+    return true;
+}
+
 // One scan of the frame, as the kernels decode it from its own HuffImage.  Returns 0 or the status the kernels would report.
-int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, int16_t* const frame_coef[4], int* sync_passes)
+int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, int16_t* const frame_coef[4], int* sync_passes,
+                 SyncScheduleCounts* schedules)
 {
     // (device scratch: destuff_compact_kernel writes the kept bytes and the 0xFF slack behind them, nothing else)
     std::vector<uint8_t> stream = device_scratch<uint8_t>(destuffed_capacity(sc));
@@ -412,9 +476,10 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
     // (decode_subsequence): same end state and same record, from true and from wrong start states, or `forms_differ` (return 5).
     bool forms_differ = false;
     uint16_t other[kRecShorts];
+    uint16_t* walk_records = records.data();  // (emulate_sync_launch's walks write records of their own)
     auto walk = [&](uint32_t i, uint32_t begin, int z, int k, bool record) {
         const uint32_t limit = (i + 1) * kSubseqBits;
-        uint16_t* rec = &records[(size_t)i * kRecShorts];
+        uint16_t* rec = &walk_records[(size_t)i * kRecShorts];
         SubseqState st, sb;
         uint32_t mark = kRecInvalid;
         size_t named = 0;  // bytes of the record the mark vouches for
@@ -431,7 +496,7 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
             named = mark_valid(mark) ? 2 * (mark & (kRecFresh - 1)) : 0;
         }
         if (pack_state(st) != pack_state(sb) || memcmp(other, rec, named) != 0) forms_differ = true;
-        rec[kRecMark] = (uint16_t)mark;
+        if (record) rec[kRecMark] = (uint16_t)mark;  // (as the kernels: a decode that does not record leaves the mark alone)
         return st;
     };
     // pass 0
@@ -452,6 +517,29 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
     }
     if (sync_passes) *sync_passes = passes;
     if (forms_differ) return 5;
+    // The kernels do not run the image-wide Jacobi above but a schedule of their own, workgroup by workgroup, and leave the rest to the
+    // tail and ripple launches: emulated here for the paired first launch (and, where the counts are wanted, for one unit per
+    // workgroup), followed to the fixpoint.  Same end state, same record for every subsequence, or return 5.
+    for (int units = schedules ? 1 : 2; units <= 2; units++) {
+        std::vector<SubseqState> got = device_scratch<SubseqState>(ns);
+        std::vector<uint16_t> got_records = device_scratch<uint16_t>((size_t)ns * kRecShorts);
+        walk_records = got_records.data();
+        SyncScheduleCounts counts = {};
+        const bool ok = emulate_sync_launch(ns, units, !rst, walk, got.data(), &counts);
+        walk_records = records.data();
+        if (forms_differ || !ok) return 5;
+        for (uint32_t i = 0; i < ns; i++) {
+            const uint16_t *a = &records[(size_t)i * kRecShorts], *b = &got_records[(size_t)i * kRecShorts];
+            if (pack_state(got[i]) != pack_state(cur[i])) return 5;
+            if (rst) continue;  // (no records)
+            if (a[kRecMark] != b[kRecMark]) return 5;
+            if (mark_valid(a[kRecMark]) && memcmp(a, b, 2 * (a[kRecMark] & (kRecFresh - 1))) != 0) return 5;
+        }
+        if (schedules) {
+            for (int q = 0; q < 4; q++) schedules[units - 1].phase[q] += counts.phase[q];
+            schedules[units - 1].tail += counts.tail;
+        }
+    }
     if (!rst) {
         // The kernels follow the last links of a correction chain with the whole wave on one subsequence (cooperative_subsequence):
         // the same routine, here, must reproduce the lane decoder's end state for every subsequence -- from its true start state and
@@ -548,16 +636,17 @@ int emulate_scan(const uint8_t* data, const FrameInfo& f, const ScanHeader& sc, 
 }
 }  // namespace
 
-int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4], int* sync_passes)
+int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4], int* sync_passes, SyncScheduleCounts schedules[2])
 {
     (void)size;
     // the coefficient blocks of a GPU-decoded picture lie in the device-only part of the arena, which nobody clears: emulate_scan()
     // zeroes what the planner's fills zero (the padding of a one-component scan's grid), the write pass writes every coded block
     for (int c = 0; c < f.ncomp; c++) fill_device_scratch(coef[c], (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 128);
     int passes = 0;
+    if (schedules) schedules[0] = schedules[1] = SyncScheduleCounts{};
     for (const ScanHeader& sc : f.scans) {  // the scans are independent: each on its own, as the batched launches take them
         int p = 0;
-        const int rc = emulate_scan(data, f, sc, coef, &p);
+        const int rc = emulate_scan(data, f, sc, coef, &p, schedules);
         passes = std::max(passes, p);
         if (rc != 0) return rc;
     }

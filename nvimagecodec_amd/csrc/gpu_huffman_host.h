@@ -54,7 +54,16 @@ void fill_huff_image(const FrameInfo& f, const ScanHeader& sc, uint32_t stream_b
 // kernels would report; *sync_passes receives the number of passes until the fixpoint.  Self-checks: 4 = the cooperative walk
 // disagrees with the lane walk, 5 = a block-start record disagrees with the position walk, the two forms of the lane walk
 // (select_walk and decode_subsequence) disagree in end state or record, or the table classes do not reproduce the per-position
-// table selection.
-int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4], int* sync_passes);
+// table selection, or the first sync launch's schedule (emulate_sync_launch below) does not end in the Jacobi fixpoint's states and
+// records.
+// schedules (nullptr: not wanted): [0] the one-unit schedule, [1] the paired one, summed over the scans.
+struct SyncScheduleCounts {
+    // Subsequence decodes of the first sync launch's workgroups, halo rows included.  One unit per workgroup: pass 0 | - | correction
+    // round 1 | round 2.  Two units (huff_sync_pair_kernel): phase A | phase B | round 1 | round 2.
+    uint64_t phase[4];
+    uint64_t tail;  // tasks left when round 2 is over: what the tail kernel's first round gets from the launch
+};
+int emulate_gpu_entropy(const uint8_t* data, size_t size, const FrameInfo& f, int16_t* const coef[4], int* sync_passes,
+                        SyncScheduleCounts schedules[2] = nullptr);
 
 }  // namespace hipjpeg

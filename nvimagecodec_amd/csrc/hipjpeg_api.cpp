@@ -271,6 +271,32 @@ hipjpegStatus_t hipjpegEntropyDecodeGpuAlgorithmHost(const uint8_t* data, size_t
     });
 }
 
+hipjpegStatus_t hipjpegTestSyncScheduleCounts(const uint8_t* data, size_t length, uint64_t counts[10])
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!test_hooks_enabled() || !data || !counts) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    FrameInfo f;
+    ParseStatus ps = parse_jpeg(data, length, &f);
+    if (ps != kParseOk) return status_from_parse(ps);
+    if (gpu_progressive_eligible(f) || !gpu_entropy_eligible(f)) return HIPJPEG_STATUS_UNSUPPORTED;
+    std::vector<int16_t> coef(f.total_blocks() * 64);
+    int16_t* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t off = 0;
+    for (int c = 0; c < f.ncomp; c++) {
+        ptr[c] = coef.data() + off;
+        off += (size_t)f.comp[c].blocks_w * f.comp[c].blocks_h * 64;
+    }
+    SyncScheduleCounts schedules[2];
+    const int rc = emulate_gpu_entropy(data, length, f, ptr, nullptr, schedules);
+    for (int s = 0; s < 2; s++) {
+        for (int q = 0; q < 4; q++) counts[5 * s + q] = schedules[s].phase[q];
+        counts[5 * s + 4] = schedules[s].tail;
+    }
+    if (rc == 5) return HIPJPEG_STATUS_INTERNAL_ERROR;
+    return rc == 0 ? HIPJPEG_STATUS_SUCCESS : (rc == 2 ? HIPJPEG_STATUS_TRUNCATED : HIPJPEG_STATUS_CORRUPT);
+    });
+}
+
 hipjpegStatus_t hipjpegEntropyDecodeGpuIntervalAlgorithmHost(const uint8_t* data, size_t length, int16_t* coef, size_t coef_capacity_bytes,
                                                              uint64_t comp_offsets[4])
 {

@@ -12,7 +12,10 @@
 //              few symbols a decoder started in the wrong state falls into step with the true one, so end states stop
 //              changing after a few passes.  When a whole pass changes nothing, every lane has decoded exactly what a
 //              sequential decoder would have decoded in its subsequence (induction from subsequence 0, whose start state
-//              is exact).
+//              is exact).  The fixpoint does not depend on the order in which subsequences are decoded again, only on every
+//              subsequence having been decoded last from the final state in front of it: the kernels' first launch starts
+//              every second subsequence from its neighbour's pass-0 end state instead of the assumption (gpu_huffman.hip,
+//              huff_sync_pair_kernel), which walks 0.71 of the bits.
 //   count      each pass also counts the blocks completed in the subsequence; an exclusive scan gives every lane the
 //              index of its first block.
 //   write      step 1: where every block starts.  The synchronisation decodes record it as they go (block-start records

@@ -110,6 +110,20 @@ def entropy_decode_gpu_algorithm_host(data):
     return coefs, passes.value
 
 
+def sync_schedule_counts(data):
+    """hipjpegTestSyncScheduleCounts: what the first sync launch of the GPU entropy stage decodes, counted by the host twin (no GPU),
+    which also checks that both schedules end in the Jacobi fixpoint's states and records.  Returns {"single": ..., "paired": ...}, each
+    {"phases": [four counts of subsequence decodes], "tail": tasks left behind correction round 2}.  Test processes only."""
+    a = _as_u8(data)
+    counts = (ctypes.c_uint64 * 10)()
+    fn = N.load().hipjpegTestSyncScheduleCounts   # (bound here, not in load(): an A/B library of an older commit has no such hook)
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    st = fn(a.ctypes.data, a.size, ctypes.addressof(counts))
+    if st:
+        raise N.HipJpegError(st, "hipjpegTestSyncScheduleCounts")
+    return {name: {"phases": [int(v) for v in counts[5 * k:5 * k + 4]], "tail": int(counts[5 * k + 4])} for k, name in enumerate(("single", "paired"))}
+
+
 def entropy_decode_gpu_interval_algorithm_host(data):
     """The interval algorithm of gpu_progressive_intervals (a lane per restart interval, then the replay) emulated on the host (no GPU).
     Returns the coefficients in natural order; HipJpegError UNSUPPORTED for anything that is not a progressive file whose scans all have

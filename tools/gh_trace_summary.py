@@ -6,7 +6,7 @@ the start of idct_plane_kernel, and the kernels and copies around the stage's en
 usage: gh_trace_summary.py DIR   (profiles/entropy_residue/ was made with it)"""
 import csv, glob, os, sys
 root = sys.argv[1]
-NAMES = ["destuff_compact_kernel", "huff_sync_kernel", "huff_tail_kernel<false>", "huff_tail_kernel<true>", "huff_scan_kernel",
+NAMES = ["destuff_compact_kernel", "huff_sync_kernel", "huff_sync_pair_kernel", "huff_tail_kernel<false>", "huff_tail_kernel<true>", "huff_scan_kernel",
          "huff_copy_records_kernel", "huff_pos_kernel", "huff_blocks_kernel", "huff_dc_group_kernel"]
 def short(n):
     n = n.replace('(anonymous namespace)::', '').replace('hipjpeg::', '')
