@@ -1,4 +1,5 @@
-"""Test helper: progressive (SOF2) files without restart intervals, written from CHOSEN coefficients like progressive_restart_files.py,
+"""Test helper: progressive (SOF2) files without restart intervals (CASES below; with them: the "interval" option of write_seams and the cases
+of progressive_interval_seams.py), written from CHOSEN coefficients like progressive_restart_files.py,
 by a coder that also says WHERE everything landed: per scan a log of events (block start, coefficient symbol, run of sixteen, end of
 band with its run length, correction bits, DC symbol, DC refinement bit), each with the bit position in the destuffed scan where it starts
 and its length in bits -- the coder knows them from its own put() calls, byte stuffing does not change them.  A case states what it is
@@ -21,7 +22,11 @@ W, C = 64, 2048  # bits of a window of the walk / of a load of its word feed (64
 # position), "zrl" (arg: -1, or where it closes the block the zeros that were left), "eob" (code + extra bits; arg: the run length written), "corr" (nbits correction
 # bits), "dc" (code + value bits; arg: category), "dcbit"
 Ev = collections.namedtuple("Ev", "kind block pos nbits arg")
-Scan = collections.namedtuple("Scan", "entry events bits data")  # bits: before the padding; data: the destuffed bytes
+# bits: before the (last) padding; data: the destuffed bytes, the stream the kernels see (restart markers dropped, the padding in front of
+# them kept); starts: where each restart interval starts in that stream, in bits (0 first; ScanHeader::rst_after * 8 behind it); pads: the
+# 1-bits between each interval's last symbol and its end; raw_starts: the file offset of each interval's first byte; interval: the scan's
+# restart interval (0: none)
+Scan = collections.namedtuple("Scan", "entry events bits data starts pads raw_starts interval")
 
 
 class _LogBits(_Bits):
@@ -177,8 +182,16 @@ def write_seams(width, height, sampling, coefficients, qtables, script, max_run=
       "cuts": {block}     ... or behind one of these blocks
       "zrl_close": True or {block}   these blocks end with a run of sixteen instead of an end of band where the tail allows it
       "declare_last_run": n          the run still open at the scan's end is written as n blocks long
-    At the start the file defines DC_LUMA / DC_CHROMA as DC tables 0 / 1 and AC_PROG as AC tables 0 / 1.  No DRI segment.
-    Returns (file, log): log[i] = Scan(entry, events, bits, destuffed bytes) of script[i]."""
+      "interval": n       the scan's restart interval (MCUs of an interleaved scan, blocks of a one-component scan): a DRI segment in front of
+                          the SOS; in front of every marker the open run and its correction bits are written out, the bits are padded with
+                          ones, RSTn counts modulo 8, and the DC predictors start over (as write_progressive_restart does)
+      with an interval, two ways to end an interval that a sequential decoder accepts and a lane of the interval kernels must refuse:
+      "declare_last_run": {interval: n}   the run still open at the end of that interval is written as n blocks long
+      "extra_ones": {interval}            a whole data byte of ones (FF 00 in the file) behind the padding of these intervals
+    At the start the file defines DC_LUMA / DC_CHROMA as DC tables 0 / 1 and AC_PROG as AC tables 0 / 1.  No DRI segment unless a scan asks
+    for an interval; a scan without the option behind one with it gets a DRI of 0.
+    Returns (file, log): log[i] = Scan(entry, events, bits, destuffed bytes, starts, pads, raw_starts, interval) of script[i]; event positions are bit
+    positions in the destuffed bytes, padding included."""
     ncomp = len(sampling)
     hmax, vmax = max(h for h, _ in sampling), max(v for _, v in sampling)
     mcus_x, mcus_y = -(-width // (8 * hmax)), -(-height // (8 * vmax))
@@ -203,7 +216,7 @@ def write_seams(width, height, sampling, coefficients, qtables, script, max_run=
         cw, ch = -(-width * h // hmax), -(-height * v // vmax)
         return -(-cw // 8), -(-ch // 8)
 
-    log = []
+    log, dri = [], 0
     for entry in script:
         opt = entry[-1] if isinstance(entry[-1], dict) else {}
         e = entry[:-1] if opt else entry
@@ -213,7 +226,29 @@ def write_seams(width, height, sampling, coefficients, qtables, script, max_run=
         for tid, t in sorted(opt.get("ac", {}).items()):
             out += dht(0x10 | tid, t)
             ac_tab[tid] = t
+        interval = int(opt.get("interval", 0))
+        if interval != dri:  # (a DRI stays in force, as the tables do)
+            out += b"\xff\xdd" + (4).to_bytes(2, "big") + interval.to_bytes(2, "big")
+            dri = interval
+        declare, extra = opt.get("declare_last_run"), set(opt.get("extra_ones", ()))
         bw, events = _LogBits(), []
+        starts, pads, raw_starts = [0], [], []
+
+        def close_interval(last=False):
+            """pads the interval that ends here with ones (+ a whole byte of ones where asked for), then the marker"""
+            bw.flush()
+            if len(pads) in extra:
+                bw.put(0xFF, 8)
+            pads.append(bw.pos - bw.bits)
+            if not last:
+                bw.out += bytes([0xFF, 0xD0 + (len(pads) - 1) % 8])
+                starts.append(bw.pos)
+                raw_starts.append(sos + len(bw.out))
+
+        def declared(i):
+            """the run length written for the run open at the end of interval i (None: its own); a plain number is for the scan's end"""
+            return declare.get(i) if isinstance(declare, dict) else declare if i is None else None
+
         if e[0] == "dc":
             comps = list(e[1])
             ah, al = (e[2], e[3]) if len(e) > 2 else (0, 0)
@@ -222,44 +257,58 @@ def write_seams(width, height, sampling, coefficients, qtables, script, max_run=
             for c, t in zip(comps, td):
                 out += bytes([c + 1, t << 4])
             out += bytes([0, 0, (ah << 4) | al])
+            sos = len(out)
+            raw_starts.append(sos)
             codes = {c: _codes(*dc_tab[t]) for c, t in zip(comps, td)}
             if len(comps) == 1:
                 nbx, nby = real_blocks(comps[0])
-                order = [(comps[0], y, x) for y in range(nby) for x in range(nbx)]
+                units = [[(comps[0], y, x)] for y in range(nby) for x in range(nbx)]
             else:
-                order = [(c, my * sampling[c][1] + by, mx * sampling[c][0] + bx) for my in range(mcus_y) for mx in range(mcus_x)
-                         for c in comps for by in range(sampling[c][1]) for bx in range(sampling[c][0])]
-            pred = {}
-            for b, (c, y, x) in enumerate(order):
-                v = int(coefficients[c][y][x][0])
-                if ah:
-                    events.append(Ev("dcbit", b, bw.pos, 1, (v >> al) & 1))
-                    bw.put((v >> al) & 1, 1)
-                    continue
-                v >>= al
-                nb, bits = _magnitude(v - pred.get(c, 0))
-                pred[c] = v
-                assert nb <= 11
-                pos = bw.pos
-                bw.put(*codes[c][nb])
-                if nb:
-                    bw.put(bits, nb)
-                events.append(Ev("dc", b, pos, bw.pos - pos, nb))
+                units = [[(c, my * sampling[c][1] + by, mx * sampling[c][0] + bx) for c in comps for by in range(sampling[c][1]) for bx in range(sampling[c][0])]
+                         for my in range(mcus_y) for mx in range(mcus_x)]
+            pred, b = {}, 0
+            for m, unit in enumerate(units):
+                if interval and m and m % interval == 0:
+                    close_interval()
+                    pred = {}
+                for c, y, x in unit:
+                    v = int(coefficients[c][y][x][0])
+                    b += 1
+                    if ah:
+                        events.append(Ev("dcbit", b - 1, bw.pos, 1, (v >> al) & 1))
+                        bw.put((v >> al) & 1, 1)
+                        continue
+                    v >>= al
+                    nb, bits = _magnitude(v - pred.get(c, 0))
+                    pred[c] = v
+                    assert nb <= 11
+                    pos = bw.pos
+                    bw.put(*codes[c][nb])
+                    if nb:
+                        bw.put(bits, nb)
+                    events.append(Ev("dc", b - 1, pos, bw.pos - pos, nb))
         else:
             c, ss, se = e[1], e[2], e[3]
             ah, al = (e[4], e[5]) if len(e) > 4 else (0, 0)
             assert 1 <= ss <= se <= 63
             ta = opt.get("ta", 0 if c == 0 else 1)
             out += b"\xff\xda" + (8).to_bytes(2, "big") + bytes([1, c + 1, ((ta & 1) << 4) | ta, ss, se, (ah << 4) | al])  # (the DC selector means nothing here)
+            sos = len(out)
+            raw_starts.append(sos)
             nbx, nby = real_blocks(c)
             coder = _SeamCoder(bw, _codes(*ac_tab[ta]), opt.get("max_run", max_run), events, opt.get("pending", 900), opt.get("zrl_close", False),
-                               opt.get("cuts", ()), opt.get("declare_last_run"))
+                               opt.get("cuts", ()), declared(None))
             for b in range(nbx * nby):
+                if interval and b and b % interval == 0:
+                    coder.declare_last_run = declared(len(pads))
+                    coder.close_band(last=True)
+                    close_interval()
                 (coder.refine if ah else coder.first)(b, coefficients[c][b // nbx][b % nbx], ss, se, al)
+            coder.declare_last_run = declared(len(pads)) if isinstance(declare, dict) else declared(None)
             coder.close_band(last=True)
-        bw.flush()
+        close_interval(last=True)
         out += bw.out
-        log.append(Scan(e, events, bw.bits, bytes(bw.raw)))
+        log.append(Scan(e, events, bw.bits, bytes(bw.raw), tuple(starts), tuple(pads), tuple(raw_starts), interval))
     out += b"\xff\xd9"
     return bytes(out), log
 
