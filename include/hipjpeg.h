@@ -716,6 +716,77 @@ HIPJPEG_API hipjpegStatus_t hipjpegPluginLosslessEntropyStats(int64_t* gpu_image
 /* The host entropy stage alone (what hipjpegDecodeLosslessBatch runs on its threads): the same planes, for comparison. */
 HIPJPEG_API hipjpegStatus_t hipjpegLosslessEntropyHost(const uint8_t* data, size_t length, uint16_t* const planes[4], size_t pitch);
 
+/* ---------------------------------------------------------------- lossless JPEG (SOF3, Huffman): encoding
+ * Byte for byte the file libjpeg-turbo writes in lossless mode (jpeg_enable_lossless; jclossls.c / jclhuff.c) from the same samples:
+ * state x = sample >> point_transform, predicted from the states to the left, above and above-left of the INPUT with the decoder's
+ * rules (first sample of the picture and of every restart interval 1 << (P - Pt - 1), rest of that row from the left, column 0 from
+ * above, elsewhere the predictor), difference = (x - prediction) & 0xFFFF, category SSSS 0..16 (16 = 32768, no extra bits).  One scan
+ * holds all components sample by sample.  The library forces optimized coding in lossless mode: every file carries ONE table, built
+ * from the category counts of all its components together (jpeg_gen_optimal_table), which every component names (Td = 0).  Segment
+ * order: SOI, APPn, SOF3, DHT, [DRI = restart_rows * width], SOS, scan, EOI.  One component: JFIF APP0, id 1; three: Adobe APP14 with
+ * transform 0, ids 'R' 'G' 'B'; four: Adobe APP14, ids 'C' 'M' 'Y' 'K'; two: no APPn, ids 0, 1.  A restart interval is a whole
+ * number of rows.  Samples above 2^P - 1 are the caller's error: the file is then unspecified, the call still memory-safe.
+ * INVALID_ARGUMENT: precision outside 2..16, predictor outside 1..7, point_transform >= precision (or negative), num_components outside
+ * 1..4, restart_rows negative, a width or height outside 1..65535, restart_rows * width above 65535 (DRI is 16 bits), sample_bytes other
+ * than 1 or 2, sample_bytes == 1 with precision > 8, a missing plane, or a pitch shorter than a row. */
+typedef struct {
+    int32_t precision;        /* P: 2..16 */
+    int32_t predictor;        /* Ps: 1..7 */
+    int32_t point_transform;  /* Pt: 0 .. P - 1 */
+    int32_t restart_rows;     /* rows per restart interval, 0 = none */
+    int32_t num_components;   /* 1..4 */
+} hipjpegLosslessEncodeParams_t;
+
+/* The const twin of hipjpegLosslessOutput_t, with the picture's size */
+typedef struct {
+    const void* plane[4];  /* planar: one pointer per component; interleaved: plane[0] only */
+    uint32_t pitch[4];     /* bytes per row; any value that holds a row, any alignment */
+    int32_t sample_bytes;  /* 2: uint16 samples; 1: uint8 samples, for precision <= 8 only */
+    int32_t planar;        /* 0: H x W x N interleaved; 1: N planes of H x W */
+    int32_t width, height;
+} hipjpegLosslessEncodeInput_t;
+
+/* The coder kernels' shape, for tests that aim at their seams: samples of a group (one lane codes a group of consecutive samples of
+ * the scan, whatever rows and restart intervals end inside it), samples of a workgroup of the length / write kernels (the write
+ * kernel's LDS window), bytes of a stuffing chunk (count / expand kernels). */
+typedef struct {
+    int32_t group_samples, window_samples, chunk_bytes;
+} hipjpegLosslessEncodeShape_t;
+HIPJPEG_API hipjpegStatus_t hipjpegLosslessEncodeShape(hipjpegLosslessEncodeShape_t* shape);
+/* The kernels' bit offsets are uint32: a picture is taken when 31 * samples + 24 * intervals <= 2^32 - 1 (samples = width * height *
+ * components; intervals = restart intervals of the scan, 1 without).  Returns 1 when it fits, 0 when the batch call answers
+ * HIPJPEG_STATUS_UNSUPPORTED for it.  Host only. */
+HIPJPEG_API int hipjpegLosslessEncodeFitsGpu(uint64_t samples, uint64_t intervals);
+
+/* Host samples in, file out, coded sample by sample as the library does it.  Needs no GPU.  HIPJPEG_STATUS_BUFFER_TOO_SMALL with
+ * *out_length = needed size if capacity is insufficient (as hipjpegEncodeFromCoefficientsHost). */
+HIPJPEG_API hipjpegStatus_t hipjpegEncodeLosslessHost(const hipjpegLosslessEncodeInput_t* input, const hipjpegLosslessEncodeParams_t* params,
+                                                      uint8_t* out, size_t capacity, size_t* out_length);
+/* The same file by the kernels' schedule run on the host, lane by lane: groups, per-workgroup counters, the segmented scan over the
+ * lanes' ranges, LDS windows with shared end words, marker bitmap, stuffing chunk by chunk.  Needs no GPU. */
+HIPJPEG_API hipjpegStatus_t hipjpegEncodeLosslessGpuAlgorithmHost(const hipjpegLosslessEncodeInput_t* input,
+                                                                  const hipjpegLosslessEncodeParams_t* params, uint8_t* out, size_t capacity,
+                                                                  size_t* out_length);
+/* Codes a batch of pictures that lie in device memory, on `stream`: statistics, lengths, offsets, bits, stuffing and file assembly all
+ * run in kernels; the category counts and the total bits come to the host (the call waits for each, twice per batch), the files land
+ * in pinned host memory.  statuses[i] is final on return; an image with bad parameters gets its status and does not disturb the
+ * others; UNSUPPORTED where hipjpegLosslessEncodeFitsGpu says 0.  There is no host fallback inside the call.  The inputs may be
+ * released once `stream` has reached this point; hipjpegEncodeLosslessGetBitstream waits for that itself. */
+HIPJPEG_API hipjpegStatus_t hipjpegEncodeLosslessBatch(hipjpegHandle_t handle, const hipjpegLosslessEncodeInput_t* inputs,
+                                                       const hipjpegLosslessEncodeParams_t* params, int batch_size, hipjpegStatus_t* statuses,
+                                                       void* stream);
+/* File `index` of the handle's last hipjpegEncodeLosslessBatch: valid until the third batch behind it (three pages are used in turn).
+ * INVALID_ARGUMENT for an image that failed. */
+HIPJPEG_API hipjpegStatus_t hipjpegEncodeLosslessGetBitstream(hipjpegHandle_t handle, int index, const uint8_t** data, size_t* length);
+/* Of the handle's last hipjpegEncodeLosslessBatch: images the kernels coded, times the call waited for the device, bytes of the bit
+ * buffers (marker bitmaps included). */
+HIPJPEG_API hipjpegStatus_t hipjpegEncodeLosslessBatchStats(hipjpegHandle_t handle, int32_t* gpu_images, int32_t* waits, uint64_t* bit_buffer_bytes);
+/* Measurement aid: the stages of the handle's last hipjpegEncodeLosslessBatch by HIP events on its stream, in milliseconds (waits for the
+ * batch's end): 0 descriptors up + lenc_stats_kernel, 1 counts down, the first wait and the host's tables, 2 codes up + lenc_length_kernel,
+ * 3 lenc_scan_kernel, 4 totals down, the second wait and the host's layout, 5 descriptors up + clearing the bit buffers,
+ * 6 lenc_write_kernel, 7 count + layout, 8 expand (the files, into pinned memory when it is the library's), 9 the copies behind it. */
+HIPJPEG_API hipjpegStatus_t hipjpegEncodeLosslessBatchStageTimes(hipjpegHandle_t handle, float milliseconds[10]);
+
 #ifdef __cplusplus
 }
 #endif

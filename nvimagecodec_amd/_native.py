@@ -88,6 +88,22 @@ class LosslessEntropyShape(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("subsequence_bits", "subsequences_per_workgroup", "max_rounds", "max_ripple_launches")]
 
 
+class LosslessEncodeParams(ctypes.Structure):
+    """hipjpegLosslessEncodeParams_t"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("precision", "predictor", "point_transform", "restart_rows", "num_components")]
+
+
+class LosslessEncodeInput(ctypes.Structure):
+    """hipjpegLosslessEncodeInput_t: the const twin of LosslessOutput with the picture's size"""
+    _fields_ = [("plane", ctypes.c_void_p * 4), ("pitch", ctypes.c_uint32 * 4), ("sample_bytes", ctypes.c_int32), ("planar", ctypes.c_int32),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
+class LosslessEncodeShape(ctypes.Structure):
+    """hipjpegLosslessEncodeShape_t"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("group_samples", "window_samples", "chunk_bytes")]
+
+
 CSS = {"444": 0, "422": 1, "420": 2, "440": 3, "411": 4, "410": 5, "gray": 6}
 
 
@@ -230,5 +246,14 @@ def load():
     L.hipjpegLosslessEntropyAlgorithmHost.argtypes = [vp, sz, ctypes.POINTER(vp), sz, ctypes.POINTER(ctypes.c_int32)]
     L.hipjpegLosslessEntropyHost.argtypes = [vp, sz, ctypes.POINTER(vp), sz]
     L.hipjpegPluginLosslessEntropyStats.argtypes = [ctypes.POINTER(ctypes.c_int64)] * 2
+    L.hipjpegLosslessEncodeShape.argtypes = [ctypes.POINTER(LosslessEncodeShape)]
+    L.hipjpegLosslessEncodeFitsGpu.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    L.hipjpegLosslessEncodeFitsGpu.restype = i32
+    for name in ("hipjpegEncodeLosslessHost", "hipjpegEncodeLosslessGpuAlgorithmHost"):
+        getattr(L, name).argtypes = [ctypes.POINTER(LosslessEncodeInput), ctypes.POINTER(LosslessEncodeParams), vp, sz, ctypes.POINTER(sz)]
+    L.hipjpegEncodeLosslessBatch.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.hipjpegEncodeLosslessGetBitstream.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(sz)]
+    L.hipjpegEncodeLosslessBatchStageTimes.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    L.hipjpegEncodeLosslessBatchStats.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64)]
     _lib = L
     return L

@@ -58,9 +58,15 @@ class DecodeParams:
 
 
 class JpegEncodeParams:
-    def __init__(self, progressive=False, optimized_huffman=False):
+    """lossless=True: lossless Huffman output (SOF3) of the samples as they are stored -- uint8 or uint16 images, one to four channels,
+    Image.precision bits (0: the type's width) -- with `predictor` 1..7 and `point_transform`; byte for byte libjpeg-turbo's file."""
+
+    def __init__(self, progressive=False, optimized_huffman=False, lossless=False, predictor=1, point_transform=0):
         self.progressive = bool(progressive)
         self.optimized_huffman = bool(optimized_huffman)
+        self.lossless = bool(lossless)
+        self.predictor = int(predictor)
+        self.point_transform = int(point_transform)
 
 
 class EncodeParams:
@@ -500,8 +506,25 @@ class Encoder(_ExecMixin):
         ep = self._make_exec_params(device_id, max_num_cpu_threads, backends)
         self._h = C.c_void_p()
         _check(lib.nvimgcodecEncoderCreate(inst, C.byref(self._h), C.byref(ep), options.encode()), "nvimgcodecEncoderCreate")
+        self._create = (device_id, max_num_cpu_threads, backends, options)
+        self._lossless = {}  # (predictor, point transform) -> an encoder created with those options: the plugin takes them per encoder
+
+    def _lossless_handle(self, predictor, point_transform):
+        key = (int(predictor), int(point_transform))
+        if key not in self._lossless:
+            lib, inst = _api()
+            device_id, threads, backends, options = self._create
+            ep = self._make_exec_params(device_id, threads, backends)
+            h = C.c_void_p()
+            opts = (options + " " if options else "") + "hipjpeg_encoder:lossless_predictor=%d hipjpeg_encoder:lossless_point_transform=%d" % key
+            _check(lib.nvimgcodecEncoderCreate(inst, C.byref(h), C.byref(ep), opts.encode()), "nvimgcodecEncoderCreate")
+            self._lossless[key] = h
+        return self._lossless[key]
 
     def close(self):
+        for h in getattr(self, "_lossless", {}).values():
+            _lib.nvimgcodecEncoderDestroy(h)
+        self._lossless = {}
         if getattr(self, "_h", None):
             _lib.nvimgcodecEncoderDestroy(self._h)
             self._h = None
@@ -548,30 +571,41 @@ class Encoder(_ExecMixin):
         _dbg = os.environ.get("HIPJPEG_DEBUG_TIMING")
         _t0 = _t.perf_counter()
 
+        lossless = params.jpeg_params.lossless
+        handle = self._lossless_handle(params.jpeg_params.predictor, params.jpeg_params.point_transform) if lossless else self._h
         for im in ilist:
             arr = im._array
             if im.buffer_kind == ImageBufferKind.STRIDED_HOST:
                 arr = np.ascontiguousarray(arr)
+                if lossless:  # the lossless coder reads device memory
+                    wide = arr.dtype == np.uint16
+                    arr = torch.from_numpy(arr.view(np.int16) if wide else arr).to(torch.device("cuda", self.device_id))
+                    arr = arr.view(torch.uint16) if wide else arr
             h, w = arr.shape[0], arr.shape[1]
             ch = arr.shape[2] if arr.ndim == 3 else 1
             gray = ch == 1
-            if im.buffer_kind == ImageBufferKind.STRIDED_DEVICE:
-                ptr, pitch, kind = arr.data_ptr(), arr.stride(0), A.BUFFER_KIND_STRIDED_DEVICE
+            if isinstance(arr, torch.Tensor):
+                size = arr.element_size()
+                ptr, pitch, kind = arr.data_ptr(), arr.stride(0) * size, A.BUFFER_KIND_STRIDED_DEVICE
             else:
+                size = arr.itemsize
                 ptr, pitch, kind = arr.ctypes.data, arr.strides[0], A.BUFFER_KIND_STRIDED_HOST
             keep.append(arr)
             css = A.SAMPLING_GRAY if gray else int(params.chroma_subsampling)
             info = A.ImageInfo()
-            _fill_image_info(info, h, w, ch, A.SAMPLEFORMAT_P_Y if gray else A.SAMPLEFORMAT_I_RGB,
-                             A.COLORSPEC_GRAY if gray else A.COLORSPEC_SRGB, ptr, pitch, kind, stream_ptr, subsampling=css)
+            fmt = A.SAMPLEFORMAT_P_Y if gray else A.SAMPLEFORMAT_I_RGB if ch == 3 or not lossless else A.SAMPLEFORMAT_I_UNCHANGED
+            _fill_image_info(info, h, w, ch, fmt, A.COLORSPEC_GRAY if gray else A.COLORSPEC_SRGB, ptr, pitch, kind, stream_ptr, subsampling=css)
+            if size == 2:  # uint16 samples: only lossless output takes them
+                info.plane_info[0].sample_type = A.SAMPLE_DATA_TYPE_UINT16
+            info.plane_info[0].precision = im.precision if lossless else 0
             ih = C.c_void_p()
             _check(lib.nvimgcodecImageCreate(inst, C.byref(ih), C.byref(info)), "nvimgcodecImageCreate")
             # output stream description: codec name, target subsampling, JPEG encoding (baseline / progressive)
             out_info = A.ImageInfo()
             _fill_image_info(out_info, h, w, ch, info.sample_format, info.color_spec, None, 0, A.BUFFER_KIND_STRIDED_HOST, None, subsampling=css)
             out_info.codec_name = b"jpeg"
-            ji = A.init(A.JpegImageInfo, A.ST_JPEG_IMAGE_INFO, encoding=A.JPEG_ENCODING_PROGRESSIVE_DCT_HUFFMAN if params.jpeg_params.progressive
-                        else A.JPEG_ENCODING_BASELINE_DCT)
+            ji = A.init(A.JpegImageInfo, A.ST_JPEG_IMAGE_INFO, encoding=A.JPEG_ENCODING_LOSSLESS_HUFFMAN if lossless
+                        else A.JPEG_ENCODING_PROGRESSIVE_DCT_HUFFMAN if params.jpeg_params.progressive else A.JPEG_ENCODING_BASELINE_DCT)
             out_info.struct_next = C.addressof(ji)
             sink = {"buf": None}
 
@@ -597,7 +631,7 @@ class Encoder(_ExecMixin):
         ep.struct_next = C.addressof(jp)
         fut = C.c_void_p()
         _t1 = _t.perf_counter()
-        _check(lib.nvimgcodecEncoderEncode(self._h, (C.c_void_p * n)(*handles), (C.c_void_p * n)(*streams), n, C.byref(ep), C.byref(fut)),
+        _check(lib.nvimgcodecEncoderEncode(handle, (C.c_void_p * n)(*handles), (C.c_void_p * n)(*streams), n, C.byref(ep), C.byref(fut)),
                "nvimgcodecEncoderEncode")
         _t2 = _t.perf_counter()
         _check(lib.nvimgcodecFutureWaitForAll(fut), "nvimgcodecFutureWaitForAll")

@@ -864,4 +864,17 @@ void encode_jfif(const EncodeGeometry& g, const uint16_t qlum[64], const uint16_
     put16(o, 0xFFD9);
 }
 
+void lossless_optimal_table(const uint32_t counts[17], uint8_t bits[17], uint8_t vals[17], int* nvals, uint32_t codes[17])
+{
+    long freq[257];
+    memset(freq, 0, sizeof freq);
+    for (int i = 0; i < 17; i++) freq[i] = (long)counts[i];
+    HuffTable t;
+    gen_optimal_table(freq, &t);
+    memcpy(bits, t.bits, 17);
+    memcpy(vals, t.vals, (size_t)t.nvals);
+    *nvals = t.nvals;
+    for (int i = 0; i < 17; i++) codes[i] = t.code[i] | ((uint32_t)t.size[i] << 16);
+}
+
 }  // namespace hipjpeg

@@ -79,4 +79,8 @@ void write_progressive_frame_header(const EncodeGeometry& g, const uint16_t qlum
 void progressive_scan_header(const ScanSpec& sc, const uint32_t counts[256], uint32_t codes[256], std::vector<uint8_t>* out,
                              int restart_interval = 0);
 
+// ---- the lossless coder's one table (lossless_encode_host.cpp): jpeg_gen_optimal_table over the counts of the 17 categories ->
+// bits[1..16], the symbols in code order, and code | size << 16 per category (0 for a category without a code)
+void lossless_optimal_table(const uint32_t counts[17], uint8_t bits[17], uint8_t vals[17], int* nvals, uint32_t codes[17]);
+
 }  // namespace hipjpeg

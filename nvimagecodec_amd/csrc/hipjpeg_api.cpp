@@ -15,6 +15,7 @@
 #include "gpu_huffman_encode.h"
 #include "gpu_huffman_host.h"
 #include "lossless_batch.h"
+#include "lossless_encode_batch.h"
 #include "progressive_encode.h"
 #include "progressive_gpu_host.h"
 #include "scratch_fill.h"
@@ -102,6 +103,7 @@ struct hipjpegHandle {
     int32_t coefficients_gpu_decoded = 0, coefficients_gpu_coded = 0;
     int64_t coefficients_blocks = 0;
     std::unique_ptr<LosslessBatch> lossless;  // hipjpegDecodeLosslessBatch: staging pages of its own, made at the first call
+    std::unique_ptr<LosslessEncodeBatch> lossless_encode;  // hipjpegEncodeLosslessBatch: likewise
 };
 
 extern "C" {
@@ -1207,6 +1209,47 @@ hipjpegStatus_t hipjpegDecodeLosslessBatchStats(hipjpegHandle_t handle, int32_t 
         images_per_kernel[1] = handle->lossless ? handle->lossless->wavefront_images() : 0;
     }
     if (h2d_bytes) *h2d_bytes = handle->lossless ? handle->lossless->h2d_bytes() : 0;
+    return HIPJPEG_STATUS_SUCCESS;
+    });
+}
+
+// (hipjpegEncodeLosslessHost / hipjpegEncodeLosslessGpuAlgorithmHost / hipjpegLosslessEncodeShape: lossless_encode_host.cpp, with the rules)
+hipjpegStatus_t hipjpegEncodeLosslessBatch(hipjpegHandle_t handle, const hipjpegLosslessEncodeInput_t* inputs, const hipjpegLosslessEncodeParams_t* params,
+                                           int batch_size, hipjpegStatus_t* statuses, void* stream)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle || batch_size < 0 || (batch_size > 0 && (!inputs || !params))) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    if (!handle->lossless_encode) handle->lossless_encode.reset(new LosslessEncodeBatch(handle->device_id, &handle->hooks));
+    return handle->lossless_encode->encode(inputs, params, batch_size, statuses, (hipStream_t)stream);
+    });
+}
+
+hipjpegStatus_t hipjpegEncodeLosslessGetBitstream(hipjpegHandle_t handle, int index, const uint8_t** data, size_t* length)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle || !handle->lossless_encode || !data || !length) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    return handle->lossless_encode->bitstream(index, data, length);
+    });
+}
+
+hipjpegStatus_t hipjpegEncodeLosslessBatchStageTimes(hipjpegHandle_t handle, float milliseconds[10])
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle || !handle->lossless_encode || !milliseconds) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (hipSetDevice(handle->device_id) != hipSuccess) return HIPJPEG_STATUS_NO_DEVICE;
+    return handle->lossless_encode->stage_times(milliseconds);
+    });
+}
+
+hipjpegStatus_t hipjpegEncodeLosslessBatchStats(hipjpegHandle_t handle, int32_t* gpu_images, int32_t* waits, uint64_t* bit_buffer_bytes)
+{
+    return guarded([&]() -> hipjpegStatus_t {
+    if (!handle) return HIPJPEG_STATUS_INVALID_ARGUMENT;
+    if (gpu_images) *gpu_images = handle->lossless_encode ? handle->lossless_encode->gpu_images() : 0;
+    if (waits) *waits = handle->lossless_encode ? handle->lossless_encode->waits() : 0;
+    if (bit_buffer_bytes) *bit_buffer_bytes = handle->lossless_encode ? handle->lossless_encode->bit_buffer_bytes() : 0;
     return HIPJPEG_STATUS_SUCCESS;
     });
 }

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "encoder_core.h"
+#include "lossless_encode_batch.h"
 #include "plugin_common.h"
 #include "plugin_objects.h"
 
@@ -72,7 +73,17 @@ public:
         // restart interval too (default: the host coder codes it).
         for_each_option(options, kEncoderId, [&](const std::string& key, const std::string& value) {
             std::istringstream v(value);
-            if (key == "gpu_huffman") {
+            if (key == "lossless_predictor" || key == "lossless_point_transform") {
+                // lossless output (NVIMGCODEC_JPEG_ENCODING_LOSSLESS_HUFFMAN): the predictor 1..7 (default 1) and the point transform 0..15
+                // (default 0; one that is not below the picture's precision fails that sample)
+                long long x = -1;
+                char rest;
+                const bool ps = key == "lossless_predictor";
+                if (!(v >> x) || (v >> rest) || x < (ps ? 1 : 0) || x > (ps ? 7 : 15))
+                    HJ_LOG_WARNING(fw_, kEncoderId, "option " << key << "='" << value << "' ignored (an integer " << (ps ? "1..7" : "0..15") << ")");
+                else
+                    (ps ? lossless_predictor_ : lossless_point_transform_) = (int)x;
+            } else if (key == "gpu_huffman") {
                 v >> gpu_huffman_;
             } else if (key == "gpu_progressive_restart") {
                 v >> gpu_progressive_restart_;
@@ -93,6 +104,7 @@ public:
         if (hipSetDevice(device_) != hipSuccess || hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking) != hipSuccess) return;
         if (hipEventCreateWithFlags(&event_, hipEventDisableTiming) != hipSuccess) return;
         batch_.reset(new EncodeBatch(device_, &hooks_));
+        lossless_.reset(new hipjpeg::LosslessEncodeBatch(device_, &hooks_));
         ok_ = true;
     }
     ~HipJpegEncoder()
@@ -102,6 +114,7 @@ public:
             cv_.wait(lk, [&] { return !busy_; });
         }
         batch_.reset();
+        lossless_.reset();
         if (event_) (void)hipEventDestroy(event_);
         if (stream_) {
             (void)hipStreamSynchronize(stream_);
@@ -125,7 +138,11 @@ private:
         nvimgcodecImageDesc_t* image;
         nvimgcodecCodeStreamDesc_t* code_stream;
         nvimgcodecProcessingStatus_t early = NVIMGCODEC_PROCESSING_STATUS_SUCCESS;
+        int lossless = -1;  // place in the lossless batch of this call; -1: a DCT sample
     };
+    // lossless output: checks the image (canEncode's bits) and, with `in` / `p`, describes it for hipjpeg's lossless coder
+    nvimgcodecProcessingStatus_t lossless_input(const nvimgcodecImageInfo_t& info, hipjpegLosslessEncodeInput_t* in,
+                                                hipjpegLosslessEncodeParams_t* p) const;
     void single_can_encode(nvimgcodecProcessingStatus_t* st, nvimgcodecImageDesc_t* image, nvimgcodecCodeStreamDesc_t* cs);
     static void host_task(int tid, int idx, void* ctx);
     void sample_done();
@@ -143,6 +160,8 @@ private:
     hipStream_t stream_ = nullptr;
     hipEvent_t event_ = nullptr;
     std::unique_ptr<EncodeBatch> batch_;
+    std::unique_ptr<hipjpeg::LosslessEncodeBatch> lossless_;  // samples whose code stream asks for LOSSLESS_HUFFMAN
+    int lossless_predictor_ = 1, lossless_point_transform_ = 0;
     std::vector<Sample> samples_;
     std::atomic<int> remaining_{0};
     std::mutex m_;
@@ -150,6 +169,57 @@ private:
     bool busy_ = false;
     std::mutex encode_mutex_;
 };
+
+// Lossless Huffman output takes the samples as they are stored: UINT8 or UINT16 (precision: plane_info[0].precision, 0 = the type's
+// width), P_Y, I_UNCHANGED / P_UNCHANGED or I_RGB / P_RGB (the file `cjpeg -lossless` writes from RGB), 1..4 components.
+nvimgcodecProcessingStatus_t HipJpegEncoder::lossless_input(const nvimgcodecImageInfo_t& info, hipjpegLosslessEncodeInput_t* in,
+                                                            hipjpegLosslessEncodeParams_t* p) const
+{
+    nvimgcodecProcessingStatus_t st = NVIMGCODEC_PROCESSING_STATUS_SUCCESS;
+    const nvimgcodecSampleDataType_t type = info.plane_info[0].sample_type;
+    const int bytes = type == NVIMGCODEC_SAMPLE_DATA_TYPE_UINT8 ? 1 : type == NVIMGCODEC_SAMPLE_DATA_TYPE_UINT16 ? 2 : 0;
+    if (!bytes) st |= NVIMGCODEC_PROCESSING_STATUS_SAMPLE_TYPE_UNSUPPORTED;
+    bool planar = false;
+    switch (info.sample_format) {
+    case NVIMGCODEC_SAMPLEFORMAT_P_Y:
+    case NVIMGCODEC_SAMPLEFORMAT_P_UNCHANGED:
+    case NVIMGCODEC_SAMPLEFORMAT_P_RGB: planar = true; break;
+    case NVIMGCODEC_SAMPLEFORMAT_I_UNCHANGED:
+    case NVIMGCODEC_SAMPLEFORMAT_I_RGB: break;
+    default: st |= NVIMGCODEC_PROCESSING_STATUS_SAMPLE_FORMAT_UNSUPPORTED;
+    }
+    const uint32_t planes = info.num_planes;
+    if (planes < 1 || planes > 4 || (!planar && planes != 1) || (info.sample_format == NVIMGCODEC_SAMPLEFORMAT_P_Y && planes != 1) ||
+        (info.sample_format == NVIMGCODEC_SAMPLEFORMAT_P_RGB && planes != 3))
+        return st | NVIMGCODEC_PROCESSING_STATUS_NUM_PLANES_UNSUPPORTED;
+    const uint32_t channels = info.plane_info[0].num_channels;
+    if (channels < 1 || channels > 4 || (planar && channels != 1) || (info.sample_format == NVIMGCODEC_SAMPLEFORMAT_I_RGB && channels != 3))
+        st |= NVIMGCODEC_PROCESSING_STATUS_NUM_CHANNELS_UNSUPPORTED;
+    for (uint32_t k = 1; k < planes; k++)
+        if (info.plane_info[k].sample_type != type || info.plane_info[k].width != info.plane_info[0].width ||
+            info.plane_info[k].height != info.plane_info[0].height)
+            st |= NVIMGCODEC_PROCESSING_STATUS_SAMPLE_TYPE_UNSUPPORTED;
+    const int precision = info.plane_info[0].precision ? (int)info.plane_info[0].precision : 8 * bytes;
+    if (bytes && (precision < 2 || precision > 8 * bytes)) st |= NVIMGCODEC_PROCESSING_STATUS_SAMPLE_TYPE_UNSUPPORTED;
+    if (st != NVIMGCODEC_PROCESSING_STATUS_SUCCESS || !in) return st;
+    memset(in, 0, sizeof *in);
+    const uint8_t* b = static_cast<const uint8_t*>(info.buffer);
+    for (uint32_t k = 0; k < planes; k++) {
+        in->plane[k] = b;
+        in->pitch[k] = (uint32_t)info.plane_info[k].row_stride;
+        b += info.plane_info[k].row_stride * info.plane_info[k].height;
+    }
+    in->sample_bytes = bytes;
+    in->planar = planar && planes > 1;
+    in->width = (int32_t)info.plane_info[0].width;
+    in->height = (int32_t)info.plane_info[0].height;
+    p->precision = precision;
+    p->predictor = lossless_predictor_;
+    p->point_transform = lossless_point_transform_;
+    p->restart_rows = restart_rows_;
+    p->num_components = (int32_t)(planar ? planes : channels);
+    return st;
+}
 
 void HipJpegEncoder::single_can_encode(nvimgcodecProcessingStatus_t* st, nvimgcodecImageDesc_t* image, nvimgcodecCodeStreamDesc_t* cs)
 {
@@ -163,6 +233,15 @@ void HipJpegEncoder::single_can_encode(nvimgcodecProcessingStatus_t* st, nvimgco
     }
     if (strcmp(out_info.codec_name, "jpeg") != 0) {
         *st = NVIMGCODEC_PROCESSING_STATUS_CODEC_UNSUPPORTED;
+        return;
+    }
+    if (ji.encoding == NVIMGCODEC_JPEG_ENCODING_LOSSLESS_HUFFMAN) {
+        nvimgcodecImageInfo_t info;
+        init_info(&info);
+        if (image->getImageInfo(image->instance, &info) != NVIMGCODEC_STATUS_SUCCESS)
+            *st = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+        else
+            *st = lossless_input(info, nullptr, nullptr);
         return;
     }
     // baseline sequential and progressive Huffman output (cuda_encoder.cpp:77-82); anything else goes down the chain
@@ -231,7 +310,18 @@ void HipJpegEncoder::host_task(int /*tid*/, int idx, void* ctx)
     // nothing may escape an executor task (the reference's pool swallows exceptions, src/thread_pool.cpp:175-185, and a sample
     // that never reports deadlocks the caller's future): whatever is thrown becomes this sample's FAIL
     try {
-    if (ps == NVIMGCODEC_PROCESSING_STATUS_SUCCESS) {
+    if (ps == NVIMGCODEC_PROCESSING_STATUS_SUCCESS && s.lossless >= 0) {
+        // the file is in pinned memory already (encode() waited for the batch's last copy): hand it to the stream
+        const uint8_t* file = nullptr;
+        size_t bytes = 0;
+        nvimgcodecIoStreamDesc_t* io = s.code_stream->io_stream;
+        size_t written = 0;
+        if (self->lossless_->bitstream(s.lossless, &file, &bytes) != HIPJPEG_STATUS_SUCCESS ||
+            io->reserve(io->instance, bytes) != NVIMGCODEC_STATUS_SUCCESS || io->seek(io->instance, 0, SEEK_SET) != NVIMGCODEC_STATUS_SUCCESS ||
+            io->write(io->instance, &written, const_cast<uint8_t*>(file), bytes) != NVIMGCODEC_STATUS_SUCCESS || written != bytes ||
+            io->flush(io->instance) != NVIMGCODEC_STATUS_SUCCESS)
+            ps = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+    } else if (ps == NVIMGCODEC_PROCESSING_STATUS_SUCCESS) {
         hipjpeg::PlannedEncode& im = self->batch_->image(idx);
         if (im.status != HIPJPEG_STATUS_SUCCESS) {
             ps = im.status == HIPJPEG_STATUS_UNSUPPORTED ? NVIMGCODEC_PROCESSING_STATUS_SAMPLING_UNSUPPORTED : NVIMGCODEC_PROCESSING_STATUS_FAIL;
@@ -274,6 +364,9 @@ nvimgcodecStatus_t HipJpegEncoder::encode(nvimgcodecImageDesc_t** images, nvimgc
     std::vector<hipjpegEncodeParams_t> eparams(n);
     memset(inputs.data(), 0, sizeof(hipjpegEncodeInput_t) * n);
     memset(eparams.data(), 0, sizeof(hipjpegEncodeParams_t) * n);
+    std::vector<hipjpegLosslessEncodeInput_t> linputs;  // the samples that ask for lossless output: a batch of their own
+    std::vector<hipjpegLosslessEncodeParams_t> lparams;
+    int dct_samples = 0;
     const auto* jp = find_in_chain<nvimgcodecJpegEncodeParams_t>(params->struct_next, NVIMGCODEC_STRUCTURE_TYPE_JPEG_ENCODE_PARAMS);
     gpu_ok = hipSetDevice(device_) == hipSuccess;
     for (int i = 0; i < n; i++) {
@@ -290,6 +383,21 @@ nvimgcodecStatus_t HipJpegEncoder::encode(nvimgcodecImageDesc_t** images, nvimgc
             s.early = NVIMGCODEC_PROCESSING_STATUS_FAIL;
             continue;
         }
+        if (ji.encoding == NVIMGCODEC_JPEG_ENCODING_LOSSLESS_HUFFMAN) {
+            hipjpegLosslessEncodeInput_t lin;
+            hipjpegLosslessEncodeParams_t lp;
+            s.early = lossless_input(info, &lin, &lp);
+            if (s.early == NVIMGCODEC_PROCESSING_STATUS_SUCCESS && (info.buffer_kind != NVIMGCODEC_IMAGE_BUFFER_KIND_STRIDED_DEVICE || !info.buffer))
+                s.early = NVIMGCODEC_PROCESSING_STATUS_FAIL;
+            if (s.early != NVIMGCODEC_PROCESSING_STATUS_SUCCESS) continue;
+            s.lossless = (int)linputs.size();
+            linputs.push_back(lin);
+            lparams.push_back(lp);
+            if (gpu_ok && (hipEventRecord(event_, (hipStream_t)info.cuda_stream) != hipSuccess || hipStreamWaitEvent(stream_, event_, 0) != hipSuccess))
+                gpu_ok = false;
+            continue;
+        }
+        dct_samples++;
         if (info.plane_info[0].sample_type != NVIMGCODEC_SAMPLE_DATA_TYPE_UINT8) {
             s.early = NVIMGCODEC_PROCESSING_STATUS_SAMPLE_TYPE_UNSUPPORTED;  // cuda_encoder.cpp:304-308
             continue;
@@ -335,9 +443,29 @@ nvimgcodecStatus_t HipJpegEncoder::encode(nvimgcodecImageDesc_t** images, nvimgc
             gpu_ok = false;
     }
     std::vector<hipjpegStatus_t> statuses(n, HIPJPEG_STATUS_SUCCESS);
-    if (gpu_ok) gpu_ok = batch_->device_stage(inputs.data(), eparams.data(), n, statuses.data(), stream_) == HIPJPEG_STATUS_SUCCESS;
+    if (gpu_ok && !linputs.empty()) {
+        // the lossless coder: everything in kernels; the call waits for counts and totals, the first bitstream() for the files -- here,
+        // so that the host tasks only read
+        std::vector<hipjpegStatus_t> lst(linputs.size(), HIPJPEG_STATUS_SUCCESS);
+        gpu_ok = lossless_->encode(linputs.data(), lparams.data(), (int)linputs.size(), lst.data(), stream_) == HIPJPEG_STATUS_SUCCESS;
+        bool waited = false;
+        for (int i = 0; i < n && gpu_ok; i++) {
+            Sample& s = samples_[i];
+            if (s.lossless < 0) continue;
+            if (lst[(size_t)s.lossless] != HIPJPEG_STATUS_SUCCESS) {
+                s.early = NVIMGCODEC_PROCESSING_STATUS_FAIL;  // (a point transform that is not below the precision, a size beyond the coder's)
+            } else if (!waited) {
+                const uint8_t* file;
+                size_t bytes;
+                gpu_ok = lossless_->bitstream(s.lossless, &file, &bytes) == HIPJPEG_STATUS_SUCCESS;
+                waited = true;
+            }
+        }
+    }
+    // (a call with lossless samples only leaves the DCT batch alone: nothing was planned for it)
+    if (gpu_ok && dct_samples) gpu_ok = batch_->device_stage(inputs.data(), eparams.data(), n, statuses.data(), stream_) == HIPJPEG_STATUS_SUCCESS;
     // blocks: the GPU coder, or the coefficients' way down for the host coder (like cudaEventSynchronize in cuda_encoder.cpp:374-375)
-    if (gpu_ok) gpu_ok = batch_->route_entropy(gpu_huffman_, gpu_huffman_, gpu_progressive_restart_) == HIPJPEG_STATUS_SUCCESS;  // the GPU coder takes restart intervals too
+    if (gpu_ok && dct_samples) gpu_ok = batch_->route_entropy(gpu_huffman_, gpu_huffman_, gpu_progressive_restart_) == HIPJPEG_STATUS_SUCCESS;  // the GPU coder takes restart intervals too
     } catch (...) {
         gpu_ok = false;  // an exception while marshalling or in the device stage: the whole batch is reported failed below
     }

@@ -1,5 +1,5 @@
 // scratch_fill.h -- what the host twins of the GPU algorithms (gpu_huffman_host.cpp, progressive_gpu_host.cpp, lossless_gpu_host.cpp,
-// gpu_huffman_encode_host.cpp, progressive_encode_host.cpp) take where the device takes a region of a staging arena.
+// gpu_huffman_encode_host.cpp, progressive_encode_host.cpp, lossless_encode_host.cpp) take where the device takes a region of a staging arena.
 //
 // The arenas (staging.h) are never cleared as a whole: a kernel may read only what an earlier copy, memset or kernel of the same batch
 // wrote (docs/arena_regions.md).  A twin that value-initialises its vectors would agree with the kernels only over zeroed memory, which

@@ -1386,3 +1386,166 @@ class BatchLosslessDecoder:
             raise N.HipJpegError(st, "hipjpegDecodeLosslessBatchEntropyStats")
         return {"rows_images": k[0], "wavefront_images": k[1], "h2d_bytes": b.value, "gpu_images": e[0].value,
                 "host_fallback_images": e[1].value, "ripple_launches": e[2].value}
+
+
+# ------------------------------------------------------------------------------------------------------------- lossless encoding
+def lossless_encode_shape():
+    """hipjpegLosslessEncodeShape: the seams of the lossless coder's kernels, as a dict"""
+    k = N.LosslessEncodeShape()
+    st = N.load().hipjpegLosslessEncodeShape(ctypes.byref(k))
+    if st:
+        raise N.HipJpegError(st, "hipjpegLosslessEncodeShape")
+    return {n: getattr(k, n) for n, _ in N.LosslessEncodeShape._fields_}
+
+
+def lossless_encode_fits_gpu(samples, intervals):
+    """hipjpegLosslessEncodeFitsGpu: whether the kernels' uint32 bit offsets hold a scan of that many samples and restart intervals"""
+    return bool(N.load().hipjpegLosslessEncodeFitsGpu(int(samples), int(intervals)))
+
+
+def _lossless_encode_params(precision, predictor, point_transform, restart_rows, num_components):
+    return N.LosslessEncodeParams(int(precision), int(predictor), int(point_transform), int(restart_rows), int(num_components))
+
+
+def lossless_encode_input(base, shape, strides, itemsize, planar):
+    """hipjpegLosslessEncodeInput_t over samples at address `base`: shape / strides (in bytes) of an H x W x N picture, or N x H x W when
+    planar (H x W: one component).  The samples of a row must be contiguous; the row stride is the pitch.  -> (structure, N)"""
+    shape, strides = tuple(shape), tuple(strides)
+    if len(shape) == 2:
+        shape, strides = (shape + (1,), strides + (itemsize,)) if not planar else ((1,) + shape, (0,) + strides)
+    if len(shape) != 3:
+        raise TypeError("a lossless picture has two or three dimensions")
+    x = N.LosslessEncodeInput()
+    x.sample_bytes = itemsize
+    x.planar = 1 if planar else 0
+    if planar:
+        n, h, w = shape
+        if w > 1 and strides[2] != itemsize:
+            raise TypeError("the samples of a row must be contiguous")
+        for c in range(min(n, 4)):
+            x.plane[c] = base + c * strides[0]
+            x.pitch[c] = strides[1] if h > 1 else w * itemsize
+    else:
+        h, w, n = shape
+        if (n > 1 and strides[2] != itemsize) or (w > 1 and strides[1] != n * itemsize):
+            raise TypeError("the samples of a row must be contiguous")
+        x.plane[0] = base
+        x.pitch[0] = strides[0] if h > 1 else w * n * itemsize
+    x.width, x.height = w, h
+    return x, n
+
+
+def _encode_lossless_host(entry, samples, precision, predictor, point_transform, restart_rows, planar):
+    a = np.asarray(samples)
+    if a.dtype not in (np.uint8, np.uint16):
+        raise TypeError("lossless samples are uint8 or uint16")
+    x, n = lossless_encode_input(a.ctypes.data, a.shape, a.strides, a.itemsize, planar)
+    p = _lossless_encode_params(precision, predictor, point_transform, restart_rows, n)
+    fn = getattr(N.load(), entry)
+    need = ctypes.c_size_t(0)
+    st = fn(ctypes.byref(x), ctypes.byref(p), None, 0, ctypes.byref(need))
+    if st != 9:  # BUFFER_TOO_SMALL names the length
+        raise N.HipJpegError(st, entry)
+    out = np.empty(need.value, dtype=np.uint8)
+    st = fn(ctypes.byref(x), ctypes.byref(p), out.ctypes.data, out.size, ctypes.byref(need))
+    if st:
+        raise N.HipJpegError(st, entry)
+    return out[:need.value].tobytes()
+
+
+def encode_lossless_host(samples, precision, predictor=1, point_transform=0, restart_rows=0, planar=False):
+    """hipjpegEncodeLosslessHost: uint8 / uint16 samples H x W x N (N x H x W when planar, H x W for one component; the row stride is the
+    pitch) to the bytes of the lossless JPEG file libjpeg-turbo writes from them."""
+    return _encode_lossless_host("hipjpegEncodeLosslessHost", samples, precision, predictor, point_transform, restart_rows, planar)
+
+
+def encode_lossless_gpu_algorithm_host(samples, precision, predictor=1, point_transform=0, restart_rows=0, planar=False):
+    """hipjpegEncodeLosslessGpuAlgorithmHost: the same file by the kernels' schedule run on the CPU"""
+    return _encode_lossless_host("hipjpegEncodeLosslessGpuAlgorithmHost", samples, precision, predictor, point_transform, restart_rows, planar)
+
+
+class BatchLosslessEncoder:
+    """hipjpegEncodeLosslessBatch on one device: torch tensors of stored samples (uint8 / uint16, H x W x N, or N x H x W when planar; any
+    row stride) to lossless JPEG files, byte for byte libjpeg-turbo's.  Everything runs in kernels; the files land in pinned host memory."""
+
+    def __init__(self, device=0, num_threads=0, allocators=None):
+        import torch
+        self._torch = torch
+        self.device = int(device)
+        self._h = ctypes.c_void_p()
+        st = N.load().hipjpegCreate(ctypes.byref(self._h), self.device, int(num_threads))
+        if st:
+            raise N.HipJpegError(st, "hipjpegCreate")
+        self._allocators = _set_allocators(self._h, allocators)
+
+    def close(self):
+        if self._h:
+            N.load().hipjpegDestroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream_ptr(self, stream):
+        s = stream if stream is not None else self._torch.cuda.current_stream(self.device)
+        return ctypes.c_void_p(s.cuda_stream)
+
+    def _per_image(self, value, n):
+        return list(value) if isinstance(value, (list, tuple)) else [value] * n
+
+    def encode(self, images, precision, predictor=1, point_transform=0, restart_rows=0, planar=False, stream=None):
+        """-> (statuses, files): files[i] is the bytes of image i's file, None where statuses[i] != 0.  precision, predictor,
+        point_transform, restart_rows and planar may each be one value or a list with one per image."""
+        torch = self._torch
+        n = len(images)
+        per = [self._per_image(v, n) for v in (precision, predictor, point_transform, restart_rows, planar)]
+        X = (N.LosslessEncodeInput * max(n, 1))()
+        P = (N.LosslessEncodeParams * max(n, 1))()
+        for i, t in enumerate(images):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.device.index != self.device:
+                raise TypeError(f"lossless input must be a tensor on cuda:{self.device}")
+            if t.dtype not in (torch.uint16, torch.uint8):
+                raise TypeError("lossless input must be a uint16 or uint8 tensor")
+            size = t.element_size()
+            X[i], comps = lossless_encode_input(t.data_ptr(), t.shape, [s * size for s in t.stride()], size, per[4][i])
+            P[i] = _lossless_encode_params(per[0][i], per[1][i], per[2][i], per[3][i], comps)
+        return self._encode(X, P, n, stream)
+
+    def _encode(self, X, P, n, stream=None):
+        """hipjpegEncodeLosslessBatch over n ready descriptors, then every file"""
+        statuses = (ctypes.c_int * max(n, 1))()
+        st = N.load().hipjpegEncodeLosslessBatch(self._h, X, P, n, statuses, self._stream_ptr(stream))
+        if st:
+            raise N.HipJpegError(st, "hipjpegEncodeLosslessBatch")
+        files = []
+        for i in range(n):
+            if statuses[i]:
+                files.append(None)
+                continue
+            ptr, length = ctypes.c_void_p(), ctypes.c_size_t()
+            st = N.load().hipjpegEncodeLosslessGetBitstream(self._h, i, ctypes.byref(ptr), ctypes.byref(length))
+            if st:
+                raise N.HipJpegError(st, "hipjpegEncodeLosslessGetBitstream")
+            files.append(ctypes.string_at(ptr.value, length.value))
+        return list(statuses)[:n], files
+
+    def stats(self):
+        g, w, b = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_uint64()
+        st = N.load().hipjpegEncodeLosslessBatchStats(self._h, ctypes.byref(g), ctypes.byref(w), ctypes.byref(b))
+        if st:
+            raise N.HipJpegError(st, "hipjpegEncodeLosslessBatchStats")
+        return {"gpu_images": g.value, "waits": w.value, "bit_buffer_bytes": b.value}
+
+    STAGES = ("upload_stats", "counts_wait_tables", "codes_length", "scan", "totals_wait_layout", "upload_zero", "write", "count_layout", "expand",
+              "copies")
+
+    def stage_times(self):
+        """hipjpegEncodeLosslessBatchStageTimes: the stages of the last encode() in milliseconds, by HIP events, as a dict"""
+        ms = (ctypes.c_float * 10)()
+        st = N.load().hipjpegEncodeLosslessBatchStageTimes(self._h, ms)
+        if st:
+            raise N.HipJpegError(st, "hipjpegEncodeLosslessBatchStageTimes")
+        return dict(zip(self.STAGES, list(ms)))
