@@ -233,7 +233,10 @@ typedef struct {
 HIPJPEG_API hipjpegStatus_t hipjpegSetAllocators(hipjpegHandle_t handle, const hipjpegAllocators_t* allocators);
 
 /* One call = host entropy stage (thread pool) + H2D staging + batched device stage, asynchronous on `stream`
- * (the call returns after the last kernel is enqueued; per-image host failures are reported in `statuses`). */
+ * (the call returns after the last kernel is enqueued; per-image host failures are reported in `statuses`).  With
+ * HIPJPEG_FLAG_GPU_HUFFMAN and at least one image on the GPU entropy stage the call then WAITS on `stream` for that stage's verdicts,
+ * and so for everything queued on `stream` before it: `statuses` are final when it returns.  Either way the outputs are written in
+ * the order of `stream` and by nothing else: not before the work queued on it earlier, and visible to the work queued on it later. */
 HIPJPEG_API hipjpegStatus_t hipjpegDecodeBatch(hipjpegHandle_t handle, const uint8_t* const* data, const size_t* lengths, int batch_size,
                                                const hipjpegOutput_t* outputs, hipjpegOutputFormat_t format, unsigned flags,
                                                hipjpegStatus_t* statuses, void* stream);

@@ -118,6 +118,7 @@ private:
         bool issued = false;  // H2D copy and kernels are queued on `stream`
         HipJpegDecoder* owner = nullptr;
         hipEvent_t event = nullptr;
+        hipEvent_t producer = nullptr;  // where the samples' own streams stood when the kernels were queued (ProducerStreams)
         hipStream_t stream = nullptr;  // H2D copy and kernels of this job: jobs overlap each other on the device
     };
 
@@ -173,10 +174,15 @@ private:
     std::unique_ptr<hipjpeg::LosslessBatch> lossless_;  // made by the first lossless sample
     hipStream_t lossless_stream_ = nullptr;
     hipEvent_t lossless_event_ = nullptr;
+    hipEvent_t lossless_producer_event_ = nullptr;
     std::mutex decode_mutex_;  // decode() may be entered from the framework's worker thread and from a fallback re-dispatch
     // Jobs whose device work is queued wait here for the completion thread: no executor thread ever blocks on the GPU, and
     // decode() has long returned when the verdicts of the GPU entropy stage arrive (the host future only means "host work
     // done", reference include/nvimgcodec.h:1455-1459; imageReady is still called once the status is final).
+    // Those verdicts lie behind the samples' own streams (ProducerStreams: the kernels start only when every caller's stream has
+    // reached the decode), so with a GPU entropy stage the completion thread -- and decode_lossless() -- wait on the host for whatever
+    // the callers queued earlier on image_info.cuda_stream.  That is the ordering contract, not a cost of its own: the image is not
+    // the decoder's before.  Jobs of the host entropy stage wait for nothing and report at once.
     std::mutex done_mutex_;
     std::condition_variable done_cv_;
     std::deque<Job*> done_queue_;
@@ -240,7 +246,8 @@ HipJpegDecoder::HipJpegDecoder(const nvimgcodecFrameworkDesc_t* fw, const nvimgc
         j->owner = this;
         j->batch.set_gpu_entropy_threshold(hybrid_huffman_threshold_);
         if (hipStreamCreateWithFlags(&j->stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&j->event, hipEventDisableTiming) != hipSuccess) {
+            hipEventCreateWithFlags(&j->event, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&j->producer, hipEventDisableTiming) != hipSuccess) {
             HJ_LOG_ERROR(fw_, kDecoderId, "could not create a HIP stream on device " << device_);
             return;
         }
@@ -256,6 +263,7 @@ HipJpegDecoder::~HipJpegDecoder()
         (void)hipStreamSynchronize(lossless_stream_);
         lossless_.reset();
         if (lossless_event_) (void)hipEventDestroy(lossless_event_);
+        if (lossless_producer_event_) (void)hipEventDestroy(lossless_producer_event_);
         (void)hipStreamDestroy(lossless_stream_);
     }
     for (auto& j : jobs_) {
@@ -275,6 +283,7 @@ HipJpegDecoder::~HipJpegDecoder()
     for (auto& j : jobs_) {
         if (j && j->stream) (void)hipStreamSynchronize(j->stream);
         if (j && j->event) (void)hipEventDestroy(j->event);
+        if (j && j->producer) (void)hipEventDestroy(j->producer);
         if (j && j->stream) (void)hipStreamDestroy(j->stream);
         j.reset();
     }
@@ -567,6 +576,24 @@ struct ConsumerStreams {
         return ok;
     }
 };
+
+// ... and the decode must not run ahead of them either: the caller's image is the caller's until its stream reaches the decode -- work
+// queued there earlier may still read or write the buffer.  The kernels run on a stream of the decoder's own, so that stream is put
+// behind every DISTINCT stream of the samples before anything that writes an image is queued on it.
+struct ProducerStreams {
+    hipEvent_t reached;  // recorded on one user stream after the other: a wait keeps the state the event had when it was queued
+    hipStream_t ours;
+    void* seen[4] = {nullptr, nullptr, nullptr, nullptr};
+    int nseen = 0;
+    bool order_behind(void* user_stream)
+    {
+        for (int k = 0; k < nseen; k++)
+            if (seen[k] == user_stream) return true;
+        if (hipEventRecord(reached, (hipStream_t)user_stream) != hipSuccess || hipStreamWaitEvent(ours, reached, 0) != hipSuccess) return false;
+        if (nseen < 4) seen[nseen++] = user_stream;
+        return true;
+    }
+};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ the lossless route
@@ -657,9 +684,13 @@ void HipJpegDecoder::decode_lossless(std::vector<Sample>& samples, const nvimgco
         bool ok = hipSetDevice(device_) == hipSuccess;
         if (ok && !lossless_stream_)
             ok = hipStreamCreateWithFlags(&lossless_stream_, hipStreamNonBlocking) == hipSuccess &&
-                 hipEventCreateWithFlags(&lossless_event_, hipEventDisableTiming) == hipSuccess;
+                 hipEventCreateWithFlags(&lossless_event_, hipEventDisableTiming) == hipSuccess &&
+                 hipEventCreateWithFlags(&lossless_producer_event_, hipEventDisableTiming) == hipSuccess;
         if (ok && !lossless_) lossless_.reset(new hipjpeg::LosslessBatch(device_, &hooks_));
         std::vector<hipjpegStatus_t> statuses((size_t)n, HIPJPEG_STATUS_INTERNAL_ERROR);
+        ProducerStreams producers{lossless_producer_event_, lossless_stream_};
+        for (int i = 0; i < n && ok; i++)
+            if (samples[(size_t)i].early_status == NVIMGCODEC_PROCESSING_STATUS_SUCCESS) ok = producers.order_behind(samples[(size_t)i].user_stream);
         // (samples declined above have no data: the batch calls them INVALID_ARGUMENT, their verdict stands)
         if (ok) ok = lossless_->decode(data.data(), sizes.data(), n, outs.data(), statuses.data(), gpu_lossless_entropy_ ? HIPJPEG_FLAG_GPU_HUFFMAN : 0u,
                                        parse_pool_.get(), lossless_stream_) == HIPJPEG_STATUS_SUCCESS;
@@ -721,6 +752,10 @@ void HipJpegDecoder::issue(Job* job)
         ok = hipSetDevice(device_) == hipSuccess;
         job->batch.finalize(job->statuses.data());
         if (ok) ok = job->batch.transfer(job->stream) == HIPJPEG_STATUS_SUCCESS;
+        // the copy reads and writes the job's own arenas; the kernels write the callers' images
+        ProducerStreams producers{job->producer, job->stream};
+        for (size_t i = 0; i < job->samples.size() && ok; i++)
+            if (job->samples[i].early_status == NVIMGCODEC_PROCESSING_STATUS_SUCCESS) ok = producers.order_behind(job->samples[i].user_stream);
         if (ok) ok = job->batch.launch(job->stream) == HIPJPEG_STATUS_SUCCESS;
     } catch (...) {
         ok = false;

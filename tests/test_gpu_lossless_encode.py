@@ -126,8 +126,11 @@ def test_too_many_bits_for_uint32_offsets_is_unsupported_before_any_launch(torch
 
 
 # ------------------------------------------------------------------------------------------------------------- plugin and Python API
-def _plugin_encode(torch, samples, sample_format, encoding, precision=0, options=""):
-    """One image through nvimgcodecEncoderEncode of the host harness -> (processing status, file or None)"""
+def _plugin_encode(torch, samples, sample_format, encoding, precision=0, options="", dev=None, stream=None, encoder=None):
+    """One image through nvimgcodecEncoderEncode of the host harness -> (processing status, file or None).  dev: the device tensor to code
+    instead of an upload of `samples` (which then only give the shape); stream: the image's cuda_stream (default: the current stream's);
+    encoder: an api.Encoder to use, and leave open, instead of one made here."""
+    import contextlib
     import ctypes as C
     from nvimagecodec_amd import abi as A
     from nvimagecodec_amd import api
@@ -136,11 +139,12 @@ def _plugin_encode(torch, samples, sample_format, encoding, precision=0, options
     s = M.as_hwn(samples)
     h, w, n = s.shape
     planar = sample_format in (A.SAMPLEFORMAT_P_Y, A.SAMPLEFORMAT_P_RGB, A.SAMPLEFORMAT_P_UNCHANGED)
-    dev = _tensor(torch, s, planar)
+    if dev is None:
+        dev = _tensor(torch, s, planar)
     size = s.itemsize
     info = A.ImageInfo()
     _fill_image_info(info, h, w, n, sample_format, A.COLORSPEC_GRAY if n == 1 else A.COLORSPEC_SRGB, dev.data_ptr(), w * size * (1 if planar else n),
-                     A.BUFFER_KIND_STRIDED_DEVICE, torch.cuda.current_stream().cuda_stream, planar=planar,
+                     A.BUFFER_KIND_STRIDED_DEVICE, torch.cuda.current_stream().cuda_stream if stream is None else stream, planar=planar,
                      subsampling=A.SAMPLING_GRAY if n == 1 else A.SAMPLING_444)
     for p in range(info.num_planes):
         info.plane_info[p].sample_type = A.SAMPLE_DATA_TYPE_UINT16 if size == 2 else A.SAMPLE_DATA_TYPE_UINT8
@@ -168,7 +172,7 @@ def _plugin_encode(torch, samples, sample_format, encoding, precision=0, options
     _check(lib.nvimgcodecCodeStreamCreateToHostMem(inst, C.byref(cs), None, cb, C.byref(out_info)), "nvimgcodecCodeStreamCreateToHostMem")
     ep = A.init(A.EncodeParams, A.ST_ENCODE_PARAMS, quality=90.0, target_psnr=50.0)
     fut = C.c_void_p()
-    with api.Encoder(max_num_cpu_threads=2, options=options) as enc:
+    with (contextlib.nullcontext(encoder) if encoder is not None else api.Encoder(max_num_cpu_threads=2, options=options)) as enc:
         _check(lib.nvimgcodecEncoderEncode(enc._h, (C.c_void_p * 1)(image), (C.c_void_p * 1)(cs), 1, C.byref(ep), C.byref(fut)), "nvimgcodecEncoderEncode")
         _check(lib.nvimgcodecFutureWaitForAll(fut), "nvimgcodecFutureWaitForAll")
         st = (C.c_uint32 * 1)()
